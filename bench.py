@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the fixed-budget global optimisation on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c5|c2] [--scaling strong|weak]
-                                                            (N > 1 without a launcher: starts the N ranks itself, as below)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c5|c2] [--scaling strong|weak] [--full]
+                  [--dump-outputs DIR]                      (N > 1 without a launcher: starts the N ranks itself, as below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,7 +17,9 @@ upload is not.  Workload at every N: BASELINE config 3 -- 1024-
 100 k points) instead; --scaling weak: every rank fits its OWN whole clip (no data-path collective; `value` = all ranks'
 frames over the slowest rank's time) -- the arrangement that pays on 8 GPUs for a clip one GPU already fits.
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up and exactly K timed steps, writes the outputs of the last
+timed step if asked (--dump-outputs) and prints the line: `value`, `ms_per_step` (milliseconds of one timed step), `config`
+and the `setup` figures its own warm-up measured.  Every other block below is measured only with --full.
   `value`                   loss terms evaluated where they reach a gradient;
   `with_reference_logging`  the like-for-like figure: every term of every iteration evaluated and kept, as the reference
                             prints them (:573-575, :587-589) -- read the two as a pair;
@@ -34,6 +36,10 @@ Rank 0 prints ONE JSON line.
                             fit against a steady one, and `cli_end_to_end` = frames / (registration + one fit) for a 300-frame clip
                             (the reference's real clip length; one process = one clip = one scene there);
   `cpu_baseline`            the oracle timed on this host's cores on a bounded sample.
+
+--dump-outputs DIR: what the last timed step returned to its caller -- body_rec [N,75], scale [1], camera_ext [N,4,4] -- as
+float32 DIR/<name>.npy (a sharded clip gathered in rank order).  The inputs are seeded: the same arguments give the same inputs,
+so two builds can be compared output for output.
 
 --dry-run: no GPU, no kernels, `value` null -- only the multi-process plumbing of this file (gloo instead of RCCL: rendezvous,
 LOCAL_RANK, frame shards, the per-iteration all-gather, barriers, max over ranks, rank-0-only JSON); tests/test_bench_plumbing.py
@@ -90,7 +96,12 @@ def parse(argv=None):
                     "(c3 = the quoted one; explicit size flags override)")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong", help="N > 1: strong = ONE clip sharded over the ranks with the "
                     "per-iteration halo exchange (BASELINE config 3's arrangement); weak = one whole clip per rank, no data-path collective")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs block (configs 2 and 5 measured in the same run)")
+    ap.add_argument("--full", action="store_true", help="also measure every secondary block of the line (logging run, roofline, per-kernel "
+                    "live times, blendshape GEMM, exact_fp32 child, other_configs, cli_end_to_end, cpu_baseline, exchange timing); "
+                    "a plain run measures only the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (body_rec, scale, "
+                    "camera_ext) as float32 DIR/<name>.npy")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the other_configs block (configs 2 and 5 measured in the same run)")
     ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--scene", type=int, default=None)
     ap.add_argument("--contacts-per-leg", type=int, default=250)
@@ -99,15 +110,17 @@ def parse(argv=None):
     ap.add_argument("--verts", type=int, default=10475)
     ap.add_argument("--lbs-nnz", type=int, default=4, help="non-zero skinning weights per vertex of the synthetic body model "
                     "(4 = SURVEY 8d's spec; a real SMPLX_NEUTRAL.npz is not promised to be 4-sparse: 8 / 12 run the wider packed skinning forms)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-logging-run", action="store_true", help="skip the secondary run that evaluates every loss term every iteration")
-    ap.add_argument("--no-exact-fp32", action="store_true", help="skip the child run with FDCAP_GEMM_SPLIT3=0")
-    ap.add_argument("--value-only", action="store_true", help="timed steps only: no roofline / secondary figures (child runs)")
-    ap.add_argument("--profile-logging", action="store_true", help="profiling aid, with --value-only: the timed steps are the "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline block")
+    ap.add_argument("--no-logging-run", action="store_true", help="--full: skip the secondary run that evaluates every loss term every iteration")
+    ap.add_argument("--no-exact-fp32", action="store_true", help="--full: skip the child run with FDCAP_GEMM_SPLIT3=0")
+    ap.add_argument("--value-only", action="store_true", help="timed steps only, even with --full: no roofline / secondary figures (child runs)")
+    ap.add_argument("--profile-logging", action="store_true", help="profiling aid, not with --full: the timed steps are the "
                     "every-iteration-logging step (the line says so in config.workload; never the headline)")
-    ap.add_argument("--cpu-sample-frames", type=int, default=0, help="0 = pick from a ~20 s budget")
+    ap.add_argument("--cpu-sample-frames", type=int, default=0, help="--full: 0 = pick from a ~20 s budget")
     ap.add_argument("--dry-run", action="store_true", help="plumbing only, on CPU with gloo (see the module docstring)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     f, ns, allc = CONFIGS[args.config]
     if args.frames is None:
         args.frames = f
@@ -233,6 +246,32 @@ def base_line(args, rk, nc, value, dt):
                        "frames": N, "scene_points": ns, "contact_verts": nc, "iters": args.iters, "body_verts": args.verts,
                        "lbs_weights_per_vertex": args.lbs_nnz,
                        "frame_iterations_per_s": None if value is None else value * args.iters}}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, res, rk, sharded):
+    """--dump-outputs: the last timed step's results as its caller receives them -- body_rec [N,75], scale [1], camera_ext [N,4,4] --
+    in float32, rank 0 writing (a sharded clip's rows gathered in rank order).  Above DUMP_MAX_BYTES, a fixed seeded sample of the
+    frames is kept and its frame indices go to sample_frames.npy."""
+    body, cam = res[0].numpy(), res[2].numpy()
+    scale = np.asarray(res[1], dtype=np.float32).reshape(1)
+    if sharded and rk.world > 1:
+        import torch.distributed as dist
+        parts = [None] * rk.world
+        dist.all_gather_object(parts, (body, cam))
+        body, cam = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+    if rk.rank != 0:
+        return
+    arrays = {"body_rec": body, "scale": scale, "camera_ext": cam}
+    per_frame = (body[0].size + cam[0].size) * 4
+    if body.shape[0] * per_frame > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(body.shape[0], DUMP_MAX_BYTES // (2 * per_frame), replace=False))
+        arrays.update(body_rec=body[keep], camera_ext=cam[keep], sample_frames=keep.astype(np.float64))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64 if name == "sample_frames" else np.float32))
 
 
 def dry_run(args):
@@ -684,6 +723,8 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # no launcher around us: be the launcher (before any GPU call)
         sys.exit(self_launch(args, sys.argv[1:]))
     if args.dry_run:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs needs the GPU run (--dry-run computes nothing)")
         return dry_run(args)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the HIP path has no CPU fallback; --dry-run checks the multi-process plumbing only)")
@@ -712,8 +753,9 @@ def main():
         body_rec, scale, cam = fop.fitting(body_gpu, "global", log_every=log_every)
         return body_rec.cpu(), scale, cam.cpu()          # D->H of the results is part of the step
 
-    if args.profile_logging and not args.value_only:
-        raise SystemExit("--profile-logging goes with --value-only")
+    full = args.full and not args.value_only
+    if args.profile_logging and full:
+        raise SystemExit("--profile-logging does not go with --full (the secondary blocks describe the plain step)")
     timed_step = (lambda: one_step(log_every=1)) if args.profile_logging else one_step
     first_fit_s = None
     for w in range(args.warmup):
@@ -725,6 +767,8 @@ def main():
             first_fit_s = time.perf_counter() - t0           # the process's first fit (setup block)
     dt, res = rk.timed(timed_step, args.steps)
     assert np.isfinite(res[0].numpy()).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rk, rk.group is not None and not weak)
     nc, ns, nl = len(vid), len(scene), fop.shard.n_local
     clips = rk.world if weak else 1
     out = base_line(args, rk, nc, clips * N * args.steps / dt, dt)
@@ -733,7 +777,7 @@ def main():
         if not weak:      # which iteration schedule rank 0's last fit kept after timing both (same results either way)
             out["config"]["exchange_schedule"] = "next forward's head under the all-gather" if getattr(fop, "exchange_overlap", False) else "plain"
             out["config"]["exchange_inside_library"] = bool(getattr(fop, "_c_comm", False))
-    if (rk.world > 1 or os.environ.get("FDCAP_FORCE_EXCHANGE") == "1") and not weak and getattr(fop, "_c_comm", False):
+    if args.full and (rk.world > 1 or os.environ.get("FDCAP_FORCE_EXCHANGE") == "1") and not weak and getattr(fop, "_c_comm", False):
         # what one iteration's exchange costs on THIS group (every rank makes the call; rank 0's figures go into the line).  Measured
         # after the timed steps: the call steps the optimiser state, the next fit re-initialises it.
         xus, gus = ctypes.c_float(0), ctypes.c_float(0)
@@ -742,7 +786,7 @@ def main():
         out["config"]["exchange_us_measured"] = {"whole_tail": float(xus.value), "allgather_alone": float(gus.value), "ranks": rk.world,
                                                  "note": "mean of 300 back-to-back calls between two HIP events on the compute stream"}
     out["setup"] = setup_block(fop, first_fit_s, dt / max(args.steps, 1), N if weak or rk.world == 1 else nl)
-    if args.value_only:
+    if not full:
         if args.profile_logging:
             out["config"]["workload"] += " [--profile-logging: every loss term of every iteration evaluated and kept]"
         return rk.finish(out)

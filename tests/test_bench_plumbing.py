@@ -149,3 +149,42 @@ def test_config_presets_and_the_blocks_built_from_the_committed_profiles():
         assert rl["bound"] == "valu_issue" and 0.1 < rl["frac"] < 1.0 and 0.0 < rl["hbm_frac_on_counter_bytes"] < 1.0, (cfg, rl)
     # (config 2's launch is too short for the clock counter: its fractions are lower bounds and say so)
     assert "lower bounds" in (nn.get("note") or "")
+
+
+def test_plain_run_options_and_the_output_dump(tmp_path):
+    """A plain run measures the headline only (`--full` adds the secondary blocks); `--steps` must be at least one timed step;
+    `--dump-outputs` writes the last timed step's (body_rec, scale, camera_ext) as float32 .npy, a seeded frame sample above the cap."""
+    import numpy as np
+    import pytest
+    import torch
+    b = _bench_module()
+    a = b.parse(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 2)
+    assert b.parse(["--full", "--dump-outputs", str(tmp_path)]).full
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            b.parse(bad)
+
+    class OneRank:
+        world, rank = 1, 0
+    body, cam = torch.randn(40, 75, dtype=torch.float32), torch.randn(40, 4, 4, dtype=torch.float32)
+    b.dump_outputs(str(tmp_path / "all"), (body, np.float32(1.25), cam), OneRank(), False)
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("body_rec", "scale", "camera_ext")}
+    assert sorted(os.listdir(tmp_path / "all")) == ["body_rec.npy", "camera_ext.npy", "scale.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    np.testing.assert_array_equal(got["body_rec"], body.numpy())
+    np.testing.assert_array_equal(got["camera_ext"], cam.numpy())
+    assert got["scale"].tolist() == [1.25]
+    b.DUMP_MAX_BYTES = 10 * (75 + 16) * 4                                  # room for 10 frames: 5 of them are kept
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), (body, np.float32(1.25), cam), OneRank(), False)
+    rows = np.load(tmp_path / "s1" / "sample_frames.npy")
+    assert rows.dtype == np.float64 and len(rows) == 5 and np.array_equal(rows, np.load(tmp_path / "s2" / "sample_frames.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "body_rec.npy"), body.numpy()[rows.astype(int)])
+
+
+def test_dry_run_refuses_to_dump_outputs(tmp_path):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--dump-outputs", str(tmp_path)], capture_output=True,
+                       text=True, timeout=120, cwd=ROOT)
+    assert p.returncode != 0 and "--dump-outputs" in (p.stderr + p.stdout)
+    assert not _json_lines(p.stdout) and not os.listdir(tmp_path)

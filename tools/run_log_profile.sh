@@ -13,7 +13,7 @@ for m in plain logging; do
 done
 head -16 $O/r4_kernel_trace_plain.txt; head -16 $O/r4_kernel_trace_logging.txt
 cd /root/repo
-for i in 1 2; do python bench.py --steps 3 --warmup 1 --no-exact-fp32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/b_log_$i.json; done
+for i in 1 2; do python bench.py --full --steps 3 --warmup 1 --no-exact-fp32 --no-cpu-baseline 2>/dev/null | tail -1 > $O/b_log_$i.json; done
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/b_log_*.json')):

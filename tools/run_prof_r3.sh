@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out
 P=$OUT/profiles_r3
 mkdir -p $P
-B="python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-logging-run --no-exact-fp32"
+B="python3 $PWD/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-logging-run --no-exact-fp32"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_r3*
 timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_r3 -o r3 -- $B > $OUT/prof_r3_bench.log 2>&1

@@ -22,8 +22,8 @@ print("launches 400..:", " ".join(f"{v:.0f}" for v in d[400:]))
 PY
 cat $P/r5_nn_logging_series.txt | cut -c1-400
 # r4's command (brute-force launch + wide GEMM in the same process) for the two kernels the r5 passes do not run: SQ pass only
+B="python3 $PWD/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-logging-run --no-exact-fp32 --no-other-configs"
 cd /tmp
-B="python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-logging-run --no-exact-fp32 --no-other-configs"
 rm -rf /tmp/prof_r5_bf*
 timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_r5_bf -o t -- $B > /dev/null 2>&1
 timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY -d /tmp/prof_r5_bf_sq -o m -- $B > /dev/null 2>&1
@@ -31,5 +31,5 @@ timeout 900 rocprofv3 --pmc FETCH_SIZE -d /tmp/prof_r5_bf_f -o f -- $B > /dev/nu
 timeout 900 rocprofv3 --pmc WRITE_SIZE -d /tmp/prof_r5_bf_w -o w -- $B > /dev/null 2>&1
 cd $GRAFT_REPO_ROOT
 python tools/make_pmc_json.py /tmp/prof_r5_bf/t_results.db /tmp/prof_r5_bf_f/f_results.db /tmp/prof_r5_bf_w/w_results.db /tmp/prof_r5_bf_sq/m_results.db $P/r5_c3_ops_pmc_summary.json 300 > /dev/null
-python bench.py > gpurun_out/r5_bench_final.json 2> gpurun_out/r5_bench_final.err
-tail -c 400 gpurun_out/r5_bench_final.json
+python bench.py --full > $P/r5_bench_final.json 2> $P/r5_bench_final.err
+tail -c 400 $P/r5_bench_final.json
