@@ -474,9 +474,6 @@ constexpr int ST4_MAXCELL = FDC_ST4_MAXCELL;   // chunks one wave can list befor
 #ifndef FDC_ST4_PF
 #define FDC_ST4_PF 2
 #endif
-#ifndef FDC_ST4_ADAPTIVE_SLACK
-#define FDC_ST4_ADAPTIVE_SLACK 1
-#endif
 #ifndef FDC_AS_MULT
 #define FDC_AS_MULT 4.f
 #endif
@@ -676,7 +673,6 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
             dmax = max_rows01(dmax);
             dmax = fmaxf(dmax, __shfl_xor(dmax, 32, 64));
             const float age = hv >= 0 ? (float)max(hv >> 8, 1) : 1.f;
-#if FDC_ST4_ADAPTIVE_SLACK
             // r5: the slack follows the queries' speed -- 4 launches' worth of motion, between the configured slack and 3 x that --
             // so that lists are also kept while the bodies move centimetres per launch (the first ~150 iterations of a fit; all
             // of phase 2 when its contact term is logged: camera_ext turns the bodies ~1 cm per iteration and no list survived,
@@ -693,9 +689,6 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
             smin = -max_rows01(-smin);
             smin = fminf(smin, __shfl_xor(smin, 32, 64));
             inflate = 3.f * speed <= smin;
-#else
-            inflate = dmax * 6.f <= cache.slack * age;
-#endif
         }
     }
     // The slack of ONE query: the wave's (speed-adaptive) slack for a query near its neighbour; for a far one scaled down by
@@ -1318,13 +1311,9 @@ __global__ void nn_grad_kernel(const float* __restrict__ q, const float4* __rest
 }
 
 // kernel choice: 0 = by size (MFMA-filtered for non-trivial sizes), 1 = plain VALU scan,
-// 2 = MFMA-filtered.  Env FDCAP_NN_KERNEL=direct|mfma or fdcap_set_nn_kernel() override (A/B).
+// 2 = MFMA-filtered.  fdcap_set_nn_kernel() sets it (tests: the reference kernels for bit identity).
 inline std::atomic<int>& nn_mode_ref() {
-    static std::atomic<int> mode{-1};
-    if (mode < 0) {
-        const char* e = getenv("FDCAP_NN_KERNEL");
-        mode = (e && e[0] == 'd') ? 1 : (e && e[0] == 'm') ? 2 : 0;
-    }
+    static std::atomic<int> mode{0};
     return mode;
 }
 static inline bool nn_use_mfma(int nq, int nt) {
@@ -1398,14 +1387,12 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
     // Query blocks per workgroup: 4 waves x NQ x 32.  A brute-force scan wants NQ = 4 (most MFMAs per
     // staged chunk: 9.7 ms vs 10.9 at NQ = 2); a seeded + chunk-culled scan wants NQ = 2 (the union of
     // the chunks 256 queries need is smaller than what 512 need, twice the workgroups: 0.92 ms vs
-    // 1.10 ms at NQ = 4, 1.09 ms at NQ = 1).  FDCAP_NN_NQ overrides.
-    static std::atomic<int> forced_nq{-1};
-    if (forced_nq < 0) { const char* e = getenv("FDCAP_NN_NQ"); forced_nq = e ? atoi(e) : 0; }
+    // 1.10 ms at NQ = 4, 1.09 ms at NQ = 1).
     const bool culled = seed != nullptr && T.bounds != nullptr;
-    // FDCAP_NN_STREAM (A/B): 0 staged kernel, WQ = nn_stream4_kernel with W waves per group of 32 Q queries
-    // (41, 42, 21, 22, 11, 12); default: 32-query groups, waves per group by launch size --
-    // measured (1024 / 512 / 256 / 128 frames x 500 queries): 11: 0.139 / 0.095 / 0.054 / 0.072 ms, 21: 0.140 / 0.087 /
-    // 0.049 / 0.047, 41: 0.153 / 0.086 / 0.047 / 0.036
+    // FDCAP_NN_STREAM (tests: each form the size rule picks, forced): 0 the staged kernel; 11 / 21 / 41 nn_stream4_kernel with
+    // 1 / 2 / 4 waves per group of 32 queries; default: waves per group by launch size.  (Groups of 64 queries, two query blocks
+    // per wave, lost: 92.2 vs 78.2 ms per step.)  Measured (1024 / 512 / 256 / 128 frames x 500 queries): 11: 0.139 / 0.095 /
+    // 0.054 / 0.072 ms, 21: 0.140 / 0.087 / 0.049 / 0.047, 41: 0.153 / 0.086 / 0.047 / 0.036
     static std::atomic<int> use_stream{-1};
     if (use_stream < 0) { const char* e = getenv("FDCAP_NN_STREAM"); use_stream = e ? atoi(e) : -2; }
     // (the streaming kernel's work list holds 16-bit ids 4 k + quarter: scenes up to 16384 chunks = 8.4 M points; beyond, the staged kernel)
@@ -1416,33 +1403,32 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
         // seed aliases idx: every workgroup reads its seeds before it writes its own results, and no other workgroup touches them
         if (seedpt_written) *seedpt_written = true;
         {
-            // (queries per group / 32, waves per group): 42 / 41 four waves, 22 / 21 two, 12 / 11 one
-            int nqv = 1, wpg;
+            int wpg;                                          // waves per group of 32 queries
             if (use_stream < 0) {                             // enough waves to fill 1024 SIMDs x 4 twice over, no more (the
                 const int g32 = (nq + 31) / 32;               // per-group setup is repeated by every wave of the group)
                 // r6 sweep (tools/launch_times.py at 64 .. 224 frames x 500 queries, us per launch; waves per group 1 / 2 / 4):
                 //   2000 groups 25.8 / 23.7 / 22.7, 2500: 25.1 / 24.2 / 25.5, 3000: 25.8 / 26.8 / 28.7, 3500: 24.1 / 26.9 / 30.1
                 wpg = g32 >= 2816 ? 1 : g32 >= 2304 ? 2 : 4;  // (3072 / 4 until r6) re-measured with quarter work items: 128 / 256 / 512 / 768 frames: 11: 0.036 / 0.033 / 0.057 / 0.068 ms, 21: 0.028 / 0.034 / 0.059 / 0.074, 41: 0.024 / 0.036 / 0.063 / 0.084
             } else {
-                nqv = (use_stream % 10 == 2) ? 2 : 1;
                 wpg = (use_stream / 10 == 4) ? 4 : (use_stream / 10 == 2) ? 2 : 1;
             }
-            static std::atomic<int> wpb1{-1};                             // FDCAP_NN_WPB=4 (A/B): four-wave workgroups for one-wave groups too
-            if (wpb1 < 0) { const char* e = getenv("FDCAP_NN_WPB"); wpb1 = (e && atoi(e) == 4) ? 0 : 1; }
-            const int groups = (nq + 32 * nqv - 1) / (32 * nqv);
-            const int wpb = (wpg == 1 && nqv == 1 && wpb1) ? 1 : 4;
+            // one-wave groups run as one-wave workgroups (a workgroup's slot is only handed on when its slowest wave is done)
+            const int groups = (nq + 31) / 32, wpb = wpg == 1 ? 1 : 4;
             const int nwg = (groups * wpg + wpb - 1) / wpb;
             const dim3 grid((nwg + 7) / 8 * 8);
             NNCache nc = cache ? *cache : NNCache{nullptr, nullptr, nullptr, 0.f};
-            const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && nqv == 1 && wpg == 1 && wpb == 1;
+            const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && wpg == 1;
             nc.order_mode = !ordered ? 0 : (ord->sorted_groups == groups ? 2 + ord->cur : 1);
-#define FDC_ST4(NQV, WPGV) hipLaunchKernelGGL((nn_stream4_kernel<NQV, WPGV>), grid, dim3(256), 0, st, q, nq, T, seed, seedpt, dist, idx, nc)
-            note_form(wpg == 4 ? "nn_stream4_kernel(4 waves per group)" : wpg == 2 ? "nn_stream4_kernel(2 waves per group)" :
-                      wpb == 4 ? "nn_stream4_kernel(1 wave per group, 4-wave workgroups)" : "nn_stream4_kernel<1,1,1>");
-            if (nqv == 2 && wpg == 4) FDC_ST4(2, 4); else if (nqv == 2 && wpg == 2) FDC_ST4(2, 2); else if (nqv == 2) FDC_ST4(2, 1);
-            else if (wpg == 4) FDC_ST4(1, 4); else if (wpg == 2) FDC_ST4(1, 2); else if (wpb == 4) FDC_ST4(1, 1);
-            else hipLaunchKernelGGL((nn_stream4_kernel<1, 1, 1>), grid, dim3(64), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-#undef FDC_ST4
+            if (wpg == 4) {
+                note_form("nn_stream4_kernel(4 waves per group)");
+                hipLaunchKernelGGL((nn_stream4_kernel<1, 4>), grid, dim3(256), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
+            } else if (wpg == 2) {
+                note_form("nn_stream4_kernel(2 waves per group)");
+                hipLaunchKernelGGL((nn_stream4_kernel<1, 2>), grid, dim3(256), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
+            } else {
+                note_form("nn_stream4_kernel<1,1,1>");
+                hipLaunchKernelGGL((nn_stream4_kernel<1, 1, 1>), grid, dim3(64), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
+            }
             if (ordered && (ord->sorted_groups != groups || ++ord->age >= ord->every)) {
                 const bool had = nc.order_mode >= 2;
                 const int nxt = had ? 1 - ord->cur : 0;
@@ -1455,12 +1441,8 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
         }
         return hipGetLastError();
     }
-    const int fq_ = forced_nq;
-    const int NQsel = fq_ ? fq_ : (culled ? 2 : 4);
     note_form(nn_use_mfma(nq, T.n) ? "nn_mfma_kernel" : "nn_direct_kernel");
-    if (nn_use_mfma(nq, T.n) && NQsel == 1)
-        hipLaunchKernelGGL((nn_mfma_kernel<1>), dim3(nn_grid_blocks((nq + 127) / 128, nsplit)), dim3(256), 0, st, q, nq, T, nsplit, seed, pd, pi);
-    else if (nn_use_mfma(nq, T.n) && NQsel == 2)
+    if (nn_use_mfma(nq, T.n) && culled)
         hipLaunchKernelGGL((nn_mfma_kernel<2>), dim3(nn_grid_blocks((nq + 255) / 256, nsplit)), dim3(256), 0, st, q, nq, T, nsplit, seed, pd, pi);
     else if (nn_use_mfma(nq, T.n))
         hipLaunchKernelGGL((nn_mfma_kernel<4>), dim3(nn_grid_blocks((nq + 511) / 512, nsplit)), dim3(256), 0, st, q, nq, T, nsplit, seed, pd, pi);

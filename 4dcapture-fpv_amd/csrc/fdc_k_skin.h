@@ -273,9 +273,6 @@ __global__ __launch_bounds__(256, FDC_SKB_OCC) void skin_bwd_kernel(SkinModel sm
     const int c_lo = SPLIT ? (int)blockIdx.y * VCH : 0, c_hi = SPLIT ? min(nc, c_lo + VCH) : nc;
     for (int c0 = c_lo; c0 < c_hi; c0 += VCH) {
         const int c1 = min(c_hi, c0 + VCH);
-#ifdef FDC_SKB_VUNROLL
-#pragma unroll FDC_SKB_VUNROLL
-#endif
         for (int c = c0 + tid; c < c1; c += 256) {
             size_t qi = (size_t)r * nc + c;
             // every global load of this vertex goes out before the first use (the kernel is a chain of latencies: four

@@ -138,42 +138,16 @@ __device__ __forceinline__ void panel_stage(float* __restrict__ sA, const float*
 // Loads under wave-uniform branches make hipcc wait vmcnt(0) in every super-step; unpinned, its scheduler sinks each load
 // to just before its use -- either way one exposed L2 round trip per 4 MFMAs (the blend product ran 27 us instead of ~12).
 // (Inline-asm loads with hand-counted s_waitcnt were tried and are wrong here: the ring is loop-carried, and the register
-// copies hipcc inserts for it read a destination before the wait.)  -DFDC_PN_PLAIN: no pins (A/B reference; same bits).
-// (-DFDC_PN_ABL=1 / 2 / 3: timing ablations -- no fragment loads / no MFMAs / no LDS reads; results are wrong)
-#ifndef FDC_PN_ABL
-#define FDC_PN_ABL 0
-#endif
+// copies hipcc inserts for it read a destination before the wait.)  The pins change no bits, only the schedule.
 // (addresses are per-lane VGPR pairs: a scalar base would be written by SALU / v_readfirstlane right before the load reads
 // it -- a 5-wait-state hazard hipcc does not pad inside an asm statement; measured: wrong fragments)
 struct PnStream { const char* p; };                                   // this lane's byte address in a tile's fragment stream
 __device__ __forceinline__ PnStream pn_stream(const float4* tile_base, int lane) { return PnStream{(const char*)(tile_base + lane)}; }
-__device__ __forceinline__ f32x4_t pn_load_b(PnStream st, int step) {
-#if FDC_PN_ABL == 1
-    return f32x4_t{(float)step, 1.f, 2.f, (float)(size_t)st.p};
-#else
-    return *(const f32x4_t*)(st.p + (size_t)step * 1024);
-#endif
-}
+__device__ __forceinline__ f32x4_t pn_load_b(PnStream st, int step) { return *(const f32x4_t*)(st.p + (size_t)step * 1024); }
 // nothing may be scheduled across this point: the fragment load issued before it stays PF super-steps ahead of its use
-__device__ __forceinline__ void pn_pin() {
-#ifndef FDC_PN_PLAIN
-    __builtin_amdgcn_sched_barrier(0);
-#endif
-}
-__device__ __forceinline__ float4 pn_load_a(const float* __restrict__ p) {
-#if FDC_PN_ABL == 3
-    return make_float4(__builtin_amdgcn_readfirstlane((int)(size_t)p) * 1.f, 1.f, 2.f, 3.f);
-#else
-    return *(const float4*)p;
-#endif
-}
-__device__ __forceinline__ f32x4_t pn_mfma(float a, float b, f32x4_t c) {
-#if FDC_PN_ABL == 2
-    c[0] += a * b; return c;
-#else
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-#endif
-}
+__device__ __forceinline__ void pn_pin() { __builtin_amdgcn_sched_barrier(0); }
+__device__ __forceinline__ float4 pn_load_a(const float* __restrict__ p) { return *(const float4*)p; }
+__device__ __forceinline__ f32x4_t pn_mfma(float a, float b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 // The static fragment is the MFMA's A operand (its 16 rows = output columns n), the LDS block its B operand (its 16 columns =
 // frame rows), so a lane's four results are FOUR CONSECUTIVE OUTPUT COLUMNS of one frame: lane (j = lane & 15, g = lane >> 4),
 // register r  <->  out[frame j][16 tile + 4 g + r].  Epilogues are one 16-byte store per tile -- to global memory and into
@@ -491,11 +465,7 @@ __device__ __forceinline__ void panel_stage3(uint4* __restrict__ sA3, const floa
 __device__ __forceinline__ f32x4_t pn3_step(const uint4* a /*[3] planes h m l of the LDS block*/, const uint4* b /*[3] of the fragment*/, f32x4_t acc) {
     // static fragment = MFMA A operand (rows = output columns), LDS block = B operand (columns = frames): see pn_step
 #define PN3_MMA(wp, ap) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(pn_bf16x8, b[wp]), __builtin_bit_cast(pn_bf16x8, a[ap]), acc, 0, 0, 0)
-#ifdef FDC_PN_EXP2      /* timing only: what two planes / three products per step would cost */
-    PN3_MMA(1, 0); PN3_MMA(0, 1); PN3_MMA(0, 0);
-#else
     PN3_MMA(2, 0); PN3_MMA(0, 2); PN3_MMA(1, 1); PN3_MMA(1, 0); PN3_MMA(0, 1); PN3_MMA(0, 0);
-#endif
 #undef PN3_MMA
     return acc;
 }
@@ -1036,25 +1006,10 @@ static inline hipError_t panel_gemm3(const float* A, int lda, int M, int K, cons
     if ((size_t)B.ntile * B.nst * PNF * 1024 > (size_t)(16u << 20) && M >= 32 && kpad <= 768) {
         // one workgroup per CU (the 98 KB image leaves room for one): as many column parts as it takes to reach 256 workgroups
         const int nrb = (M + 31) / 32, ncb = (B.ntile + 7) / 8, cpg = (ncb + 7) / 8;
-        static std::atomic<int> cs_env{-1};                          // FDCAP_PN_WIDE_CS=1 (A/B): the r2-r4 form, one part
-        if (cs_env < 0) { const char* e = getenv("FDCAP_PN_WIDE_CS"); cs_env = e ? atoi(e) : 0; }
-        // (r5: two column tiles per wave, as in the K-loop product, measured no faster here: 0.186 vs 0.179 ms at 1024 rows, equal at 512)
-        static std::atomic<int> rb_env{-1};                          // FDCAP_PN_WIDE_RB=4 (A/B, r6): 64 rows per workgroup -- half the fragment bytes per MFMA
-        if (rb_env < 0) { const char* e = getenv("FDCAP_PN_WIDE_RB"); rb_env = e ? atoi(e) : 2; }
-        if (rb_env == 4 && M >= 64) {
-            const int nrb4 = (M + 63) / 64;
-            const int cs4 = cs_env > 0 ? (int)cs_env : std::max(1, std::min(cpg, (256 + 8 * nrb4 - 1) / (8 * nrb4)));
-            static std::atomic<uint64_t> attr4{0};
-            if (fdc_attr_needed(attr4)) {
-                hipError_t e = hipFuncSetAttribute((const void*)panel_gemm3_wide_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pnf_lds_bytes(kpad, 4));
-                if (e != hipSuccess) return e;
-                fdc_attr_done(attr4);
-            }
-            note_form("panel_gemm3_wide_kernel<4>");
-            hipLaunchKernelGGL(panel_gemm3_wide_kernel<4>, dim3(8 * nrb4 * cs4), dim3(512), pnf_lds_bytes(kpad, 4), st, A, lda, M, K, B, C, ldc, N, cs4);
-            return hipGetLastError();
-        }
-        const int cs = cs_env > 0 ? (int)cs_env : std::max(1, std::min(cpg, (256 + 8 * nrb - 1) / (8 * nrb)));
+        // (r2-r4 ran one column part.  r5: two column tiles per wave, as in the K-loop product, measured no faster here: 0.186 vs
+        //  0.179 ms at 1024 rows, equal at 512.  r6: 64 rows per workgroup -- half the fragment bytes per MFMA -- took 70 us instead
+        //  of 90 at 512 rows, yet made the config-5 fit 5 % slower: that configuration runs at the chip's power limit.)
+        const int cs = std::max(1, std::min(cpg, (256 + 8 * nrb - 1) / (8 * nrb)));
         note_form("panel_gemm3_wide_kernel"); hipLaunchKernelGGL(panel_gemm3_wide_kernel<2>, dim3(8 * nrb * cs), dim3(512), pnf_lds_bytes(kpad, 2), st, A, lda, M, K, B, C, ldc, N, cs);
         return hipGetLastError();
     }
@@ -1396,14 +1351,11 @@ static inline hipError_t panel_gemm3_ksw(const float* A, int lda, int M, int K, 
         if (e != hipSuccess) return e;
         fdc_attr_done(attr);
     }
-    // column tiles per workgroup: two while that still gives >= 192 workgroups, else one (FDCAP_PN_KSW_T pins it: A/B) -- r6: and two
-    // whenever one tile per workgroup would mean more workgroups than CUs (one workgroup fits a CU: 129-176 rows ran in two rounds,
-    // 14.7 us at 160 rows against 8.8 at 128 and 9.5 at 192: tools/launch_times.py sweep)
-    static std::atomic<int> t_env{-1};
-    if (t_env < 0) { const char* e = getenv("FDCAP_PN_KSW_T"); t_env = e ? atoi(e) : 0; }
+    // column tiles per workgroup: two while that still gives >= 192 workgroups, else one -- r6: and two whenever one tile per
+    // workgroup would mean more workgroups than CUs (one workgroup fits a CU: 129-176 rows ran in two rounds, 14.7 us at 160 rows
+    // against 8.8 at 128 and 9.5 at 192: tools/launch_times.py sweep)
     const int nrb = (M + 15) / 16;
-    int T = (nrb * ((B.ntile + 1) / 2) >= 192 || nrb * B.ntile > 256) ? 2 : 1;
-    if (t_env == 1 || t_env == 2) T = t_env;
+    const int T = (nrb * ((B.ntile + 1) / 2) >= 192 || nrb * B.ntile > 256) ? 2 : 1;
     const PnMap mp = panel_map(nrb, (B.ntile + T - 1) / T, (size_t)M * K * 4, (size_t)B.ntile * B.nst * PNF * 1024);
     note_form("panel_gemm3_ksw_kernel");
     if (T == 2)
@@ -1492,26 +1444,13 @@ __global__ void panel_part_sum_kernel(const float* __restrict__ part, int ks, si
     out[i] = s;
 }
 constexpr int PN3_KLOOP_SLAB = 24;                               // steps (32 columns each) per slab: two 16-row images of 768 columns = 144 KB
+// 16-row blocks per fragment stream and column tiles per wave (measured at 512 / 128 rows: RB 4 T 1 192 / 55 us, RB 2 T 2 139 / 44,
+// RB 4 T 2 166 / 57 with 55 spilled registers)
+constexpr int PN3_KLOOP_RB = 2, PN3_KLOOP_T = 2;
 // parts of K for M rows and B's tiles: enough workgroups for 256 CUs, ks x column blocks a multiple of 8 (XCD <-> slice of B), <= 32
-inline std::atomic<int>& panel_gemm3_kloop_slab() {                          // FDCAP_KLOOP_SLAB (A/B): steps per slab, 4..24
-    static std::atomic<int> v{-1};
-    if (v < 0) { const char* e = getenv("FDCAP_KLOOP_SLAB"); v = e ? std::min(24, std::max(4, atoi(e))) : PN3_KLOOP_SLAB; }
-    return v;
-}
-inline std::atomic<int>& panel_gemm3_kloop_rb() {                             // FDCAP_KLOOP_RB (A/B): 16-row blocks per fragment stream, 2 or 4
-    static std::atomic<int> v{-1};
-    if (v < 0) { const char* e = getenv("FDCAP_KLOOP_RB"); v = (e && atoi(e) == 4) ? 4 : 2; }
-    return v;
-}
-inline std::atomic<int>& panel_gemm3_kloop_t() {                              // FDCAP_KLOOP_T (A/B): column tiles per wave, 1 or 2
-    static std::atomic<int> v{-1};
-    if (v < 0) { const char* e = getenv("FDCAP_KLOOP_T"); v = (e && atoi(e) == 1) ? 1 : 2; }
-    return v;
-}
 static inline int panel_gemm3_kloop_parts(int M, const PanelB3& B) {
-    const int rb = panel_gemm3_kloop_rb(), T = panel_gemm3_kloop_t(), ncb = (B.ntile + 8 * T - 1) / (8 * T), nrp = (M + 16 * rb - 1) / (16 * rb);
-    static std::atomic<int> wgs{-1};                                         // FDCAP_KLOOP_WGS (A/B): workgroups to aim for
-    if (wgs < 0) { const char* e = getenv("FDCAP_KLOOP_WGS"); wgs = e ? atoi(e) : 256; }
+    constexpr int rb = PN3_KLOOP_RB, T = PN3_KLOOP_T, wgs = 256;
+    const int ncb = (B.ntile + 8 * T - 1) / (8 * T), nrp = (M + 16 * rb - 1) / (16 * rb);
     // r6: the LARGEST admissible part count that still fits one round of workgroups (a workgroup fills a CU's LDS: one per CU).  The
     // count used to be rounded UP to the next admissible one -- 288-336 workgroups at 96 / 192 / 320 / 384 / 448 rows, two rounds:
     // 141.8 us at 384 rows against 113.9 at 512 (tools/launch_times.py --config c5 sweep).
@@ -1524,25 +1463,19 @@ static inline int panel_gemm3_kloop_parts(int M, const PanelB3& B) {
 static inline hipError_t panel_gemm3_kloop(const float* A, int lda, int M, int K, const PanelB3& B, float* part, float* C, int ldc, int N,
                                            hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
-    const int rb = panel_gemm3_kloop_rb(), T = panel_gemm3_kloop_t(), ks = panel_gemm3_kloop_parts(M, B), ncb = (B.ntile + 8 * T - 1) / (8 * T), nrp = (M + 16 * rb - 1) / (16 * rb);
+    constexpr int rb = PN3_KLOOP_RB, T = PN3_KLOOP_T;
+    const int ks = panel_gemm3_kloop_parts(M, B), ncb = (B.ntile + 8 * T - 1) / (8 * T), nrp = (M + 16 * rb - 1) / (16 * rb);
     const size_t stride = (size_t)M * ldc;
     // steps per slab: RB images of 32 x slab columns, 6 bytes each, in <= 147 KB
-    const int slab = std::min((int)panel_gemm3_kloop_slab(), rb == 4 ? 12 : 24);   // (measured at 512 / 128 rows: RB 4 T 1 192 / 55 us, RB 2 T 2 139 / 44, RB 4 T 2 166 / 57 with 55 spilled registers)
+    constexpr int slab = PN3_KLOOP_SLAB;
     const size_t lds = pnf_lds_bytes(32 * slab, rb);
     static std::atomic<uint64_t> attr{0};                      // per DEVICE: the attribute belongs to one device's code object
     if (fdc_attr_needed(attr)) {
-        hipError_t e = hipSuccess;
-        const void* fs[] = {(const void*)panel_gemm3_kloop_kernel<2, 1>, (const void*)panel_gemm3_kloop_kernel<4, 1>,
-                            (const void*)panel_gemm3_kloop_kernel<2, 2>, (const void*)panel_gemm3_kloop_kernel<4, 2>};
-        for (const void* f : fs)
-            if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)panel_gemm3_kloop_kernel<rb, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         if (e != hipSuccess) return e;
         fdc_attr_done(attr);
     }
-    const dim3 grid(ks * ncb * nrp);
-#define FDC_KLOOP(RBV, TV) hipLaunchKernelGGL((panel_gemm3_kloop_kernel<RBV, TV>), grid, dim3(512), lds, st, A, lda, M, K, B, part, stride, ldc, N, ks, slab)
-    if (rb == 4 && T == 2) FDC_KLOOP(4, 2); else if (rb == 4) FDC_KLOOP(4, 1); else if (T == 2) FDC_KLOOP(2, 2); else FDC_KLOOP(2, 1);
-#undef FDC_KLOOP
+    hipLaunchKernelGGL((panel_gemm3_kloop_kernel<rb, T>), dim3(ks * ncb * nrp), dim3(512), lds, st, A, lda, M, K, B, part, stride, ldc, N, ks, slab);
     note_form("panel_gemm3_kloop_kernel");
     hipLaunchKernelGGL(panel_part_sum_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, st, part, ks, stride, stride, C);
     return hipGetLastError();

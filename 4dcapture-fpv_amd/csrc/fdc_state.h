@@ -54,13 +54,11 @@ template <bool CONTACT>
 static int skin_bwd_any(DevBuf<float>& part, hipStream_t st, int nrows, SkinModel sm, int nc, const float* X, const float* Voff, const float* A,
                         const float* M, const float* scale, int row0, const float* dVw, float* dVoff, float* dA, float* dbeta_v,
                         float* dtransl_v, float* dMv, float* dsv, ContactGradIn cg) {
-    static std::atomic<int> split_on{-1};                              // FDCAP_SKIN_SPLIT=0: the one-workgroup-per-frame form at every size (A/B)
-    if (split_on < 0) { const char* e = getenv("FDCAP_SKIN_SPLIT"); split_on = (e && e[0] == '0') ? 0 : 1; }
     // dT rows: 12 floats per vertex for the list form; the matrix form keeps them factored (SKB_ROW = 6 floats) and reuses the space for its
     // four waves' partial tiles (16 KB: more than 512 vertices of rows, which is when the matrix form is built)
     const size_t lds = sm.wf_tab ? std::max((size_t)std::min(nc, SKB_VCH) * SKB_ROW, (size_t)4 * 64 * 16) * sizeof(float)
                                  : (size_t)std::min(nc, SKB_VCH) * 12 * sizeof(float);
-    if (nc <= SKB_VCH || !split_on) {
+    if (nc <= SKB_VCH) {
         note_form("skin_bwd_kernel(one workgroup per frame)");
         hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, false>), dim3(nrows), dim3(256), lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
                            dbeta_v, dtransl_v, dMv, dsv, cg, (float*)nullptr);
@@ -429,10 +427,9 @@ int build_skin_set(fdcap_ctx* c, const std::vector<int64_t>& ids, SkinSet* out) 
     }
     tr.mark("lists, vpack, chunk table");
     out->wf_tab.release(); out->wf_step.release(); out->wf_frag.release();
-    {   // the weights as MFMA fragments for skin_bwd_kernel's dA (SkinModel::wf_*): vertex sets beyond the contact-set kernels' reach;
-        // FDCAP_SKIN_DA_MFMA=0: the ordered list form
-        const char* e = getenv("FDCAP_SKIN_DA_MFMA");
-        if (!(e && e[0] == '0') && nv > 512) {
+    {   // the weights as MFMA fragments for skin_bwd_kernel's dA (SkinModel::wf_*): vertex sets beyond the contact-set kernels' reach
+        // (512 vertices or fewer keep the ordered list form)
+        if (nv > 512) {
             const int nchm = (nv + SKB_VCH - 1) / SKB_VCH;
             std::vector<int> tab((size_t)nchm * 16 + 1, 0);
             std::vector<uint2> steps;
@@ -552,9 +549,8 @@ hipError_t blend_backward(const SkinSet& ss, const float* dV, int M, float* dPF,
         }
         // r6: the K-loop form also where one LDS image would still fit, from K = 1664 at clip sizes and K = 1904 from 192 rows -- contact
         // sets of 560-840 vertices ran the one-image forms at 17-35 us where the K-loop form takes 14-21 (tools/launch_times.py
-        // --per-leg 280 / 320 / 375 / 420 at 1024 / 512 / 256 / 128 rows; at 128 rows the one-image forms stay ahead).  FDCAP_KLOOP_MIN_K: A/B.
-        static std::atomic<int> kmin{-1};
-        if (kmin < 0) { const char* e = getenv("FDCAP_KLOOP_MIN_K"); kmin = e ? atoi(e) : 1664; }
+        // --per-leg 280 / 320 / 375 / 420 at 1024 / 512 / 256 / 128 rows; at 128 rows the one-image forms stay ahead).
+        constexpr int kmin = 1664;
         const bool big_k = (M >= 384 && K >= kmin) || (M >= 192 && K >= kmin + 240);
         if (!big_k && panel_gemm3_ksw_ok(M, K, ss.pn_bwd3)) return panel_gemm3_ksw(dV, K, M, K, ss.pn_bwd3, dPF, NPFX, NPFX, st);
         if (!big_k && panel_gemm3_fits(K)) return panel_gemm3(dV, K, M, K, ss.pn_bwd3, dPF, NPFX, NPFX, st);

@@ -3,7 +3,7 @@
 mode 'local', 60 iterations of the bench workload, and a short fit with all 10 475 vertices as contacts) once per library in a child process each and compares parameters, scale,
 camera_ext and the loss log bit for bit.   tools/compare_builds.py <libA.so> <libB.so>
 r6: an argument of the form NAME=value (instead of a path) runs the tree's library with that environment setting, so two
-settings of an A/B switch can be compared the same way:   tools/compare_builds.py FDCAP_PN_WIDE_RB=2 FDCAP_PN_WIDE_RB=4"""
+settings of a switch can be compared the same way:   tools/compare_builds.py FDCAP_PN_RB2=1 FDCAP_PN_RB2=0"""
 import os, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r'''

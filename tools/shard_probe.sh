@@ -1,5 +1,5 @@
 # per-rank cost of the strong-scaling shards on ONE GPU: the 1024-frame workload cut to 128/256/512 frames
-# MODES: FDCAP_NN_STREAM values to compare (-2 = default choice by launch size); FRAMES: clip lengths
+# MODES: FDCAP_NN_STREAM values to compare (-2 = default choice by launch size, 11 / 21 / 41 = waves per group, 0 = staged kernel); FRAMES: clip lengths
 cd $GRAFT_REPO_ROOT
 for mode in ${MODES:--2}; do
 for f in ${FRAMES:-128 256 512 1024}; do

@@ -1,6 +1,5 @@
-cd /tmp && export TMPDIR=/tmp
-for v in 0 1; do
-rm -rf /tmp/p5_$v
-FDCAP_SKIN_SPLIT=$v timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/p5_$v -o t -- python3 $GRAFT_REPO_ROOT/bench.py --config c5 --value-only --steps 1 --warmup 0 --iters 100 > /dev/null 2>&1
-python3 $GRAFT_REPO_ROOT/tools/rocpd_summary.py /tmp/p5_$v/t_results.db /dev/null | sed -n 4,12p | cut -c1-100
-done
+# kernel trace of BASELINE config 5's fit (skinning backward of the full mesh: split form + chunk reduction)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+OUT=$(mktemp -d)
+timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT" -o t -- python3 "$ROOT/bench.py" --config c5 --value-only --steps 1 --warmup 0 --iters 100 > /dev/null 2>&1
+python3 "$ROOT/tools/rocpd_summary.py" "$OUT/t_results.db" /dev/null | sed -n 4,12p | cut -c1-100
