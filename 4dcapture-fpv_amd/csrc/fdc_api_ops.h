@@ -241,7 +241,8 @@ int fdcap_set_scene(fdcap_ctx* c, const float* xyz, int64_t ns) {
     // Spatial order by recursive median splits (k-d cells): every MF_CH-point chunk is one cell and every 32-point MFMA tile inside it
     // a sub-cell, so the boxes the NN scan culls with are compact and disjoint (runs of a Morton curve jump across quadrant borders
     // and give long, overlapping boxes).  r6: sorted, boxed and packed ON THE DEVICE (fdc_scene.h); FDCAP_SCENE_BUILD=host takes the
-    // order from the host recursion of r1-r5 instead (the same order by specification: tests compare the tables of the two).
+    // order from the host recursion of r1-r5 instead (the same order by specification: tests compare the
+    // tables of the two, and of both with tests/scene_spec.py).
     // Results never depend on this order.
     const int64_t nchunk = (ns + MF_CH - 1) / MF_CH, nsuper = (nchunk + ST4_SUPER - 1) / ST4_SUPER;
     HIP_TRY(c->scene.ensure((size_t)ns)); HIP_TRY(c->scene_sorted.ensure((size_t)ns)); HIP_TRY(c->scene_inv.ensure((size_t)ns));
@@ -280,6 +281,22 @@ int fdcap_debug_scene_hash(fdcap_ctx* c, uint64_t* out8) {
         for (size_t k = 0; k < t[i].bytes; ++k) { v ^= h[k]; v *= 1099511628211ull; }
         out8[i] = v;
     }
+    return FDCAP_OK;
+}
+
+// test / diagnosis: one of the same eight tables copied to the host as it is, so a test can compare it with a specification
+// (tests/scene_spec.py).  `which` in the order of fdcap_debug_scene_hash; host_out == nullptr: *bytes <- the table's size
+int fdcap_debug_scene_table(fdcap_ctx* c, int32_t which, void* host_out, int64_t* bytes) {
+    if (!c || !bytes || which < 0 || which > 7) return FDCAP_E_ARG;
+    if (c->ns <= 0 || !c->scene_sorted.p) return FDCAP_E_STATE;
+    const int64_t ns = c->ns, nchunk = (ns + MF_CH - 1) / MF_CH, nsuper = std::max<int64_t>((nchunk + ST4_SUPER - 1) / ST4_SUPER, 1);
+    const void* p[8] = {c->scene.p, c->scene_sorted.p, c->scene_inv.p, c->scene_bounds.p, c->scene_qbounds.p, c->scene_sbounds.p,
+                        c->scene_frags.p, c->scene_centers.p};
+    const int64_t sz[8] = {ns * 16, ns * 16, ns * 4, nchunk * 32, nchunk * 128, nsuper * 32, nchunk * (MF_CH / 32) * 64 * 16, nchunk * 16};
+    if (!host_out) { *bytes = sz[which]; return FDCAP_OK; }
+    if (*bytes != sz[which]) return FDCAP_E_ARG;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(host_out, p[which], (size_t)sz[which], hipMemcpyDeviceToHost));
     return FDCAP_OK;
 }
 

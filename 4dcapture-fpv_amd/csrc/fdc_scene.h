@@ -222,8 +222,12 @@ __device__ __forceinline__ unsigned sc_bf16(float f) {                       // 
     return u >> 16;
 }
 __device__ __forceinline__ float sc_bf16f(unsigned h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ float sc_pad(float lo, float hi) {                // 1e-6 + 1e-6 max(|lo|, |hi|), no contraction
-    return __fadd_rn(1e-6f, __fmul_rn(1e-6f, fmaxf(fabsf(lo), fabsf(hi))));
+// The tables' arithmetic is one rounding per operation (tests/scene_spec.py states it bit for bit): contraction is switched off where
+// it is written.  HIP's __fmul_rn / __fadd_rn are plain operators that -ffp-contract=fast fuses into an FMA all the same, and its
+// __fsqrt_rn is the 1-ulp v_sqrt_f32; sqrtf is correctly rounded.
+__device__ __forceinline__ float sc_pad(float lo, float hi) {                // 1e-6 + 1e-6 max(|lo|, |hi|)
+#pragma clang fp contract(off)
+    return 1e-6f + 1e-6f * fmaxf(fabsf(lo), fabsf(hi));
 }
 
 // one workgroup per cell of MF_CH points: sorted points, inverse permutation, input-order copy, the cell's and its quarters' boxes,
@@ -232,6 +236,7 @@ __global__ __launch_bounds__(MF_CH) void sc_finalize_kernel(const float* __restr
                                                             float4* __restrict__ orig, float4* __restrict__ sorted, int* __restrict__ inv,
                                                             float4* __restrict__ bounds, float4* __restrict__ qbounds,
                                                             uint4* __restrict__ frags, float4* __restrict__ centers) {
+#pragma clang fp contract(off)
     static_assert(MF_CH % 256 == 0 && MF_CH / 4 % 64 == 0, "a quarter cell is a whole number of waves");
     constexpr int NW = MF_CH / 64, WPQ = NW / 4;
     __shared__ float wlo[NW][3], whi[NW][3], wr2[NW];
@@ -276,7 +281,7 @@ __global__ __launch_bounds__(MF_CH) void sc_finalize_kernel(const float* __restr
             for (int w = 0; w < NW; ++w) { cl[k] = fminf(cl[k], wlo[w][k]); chh[k] = fmaxf(chh[k], whi[w][k]); }
             const float pad = sc_pad(cl[k], chh[k]);
             cl[k] -= pad; chh[k] += pad;
-            cen[k] = __fmul_rn(0.5f, __fadd_rn(cl[k], chh[k]));
+            cen[k] = 0.5f * (cl[k] + chh[k]);
         }
         bounds[2 * (size_t)ch] = make_float4(cl[0], cl[1], cl[2], 0.f);
         bounds[2 * (size_t)ch + 1] = make_float4(chh[0], chh[1], chh[2], 0.f);
@@ -286,7 +291,7 @@ __global__ __launch_bounds__(MF_CH) void sc_finalize_kernel(const float* __restr
     float yx = 0.f, yy = 0.f, yz = 0.f, n2 = 1e30f, r2 = 0.f;                  // padding rows: score 1e30
     if (valid) {
         yx = x - cx; yy = y - cy; yz = z - cz;
-        n2 = __fadd_rn(__fmul_rn(yz, yz), __fadd_rn(__fmul_rn(yy, yy), __fmul_rn(yx, yx)));
+        n2 = yz * yz + (yy * yy + yx * yx);
         r2 = n2;
     }
     unsigned hx = sc_bf16(yx), hy = sc_bf16(yy), hz = sc_bf16(yz);
@@ -307,7 +312,7 @@ __global__ __launch_bounds__(MF_CH) void sc_finalize_kernel(const float* __restr
     if (j == 0) {
         float m = 0.f;
         for (int w = 0; w < NW; ++w) m = fmaxf(m, wr2[w]);
-        centers[ch] = make_float4(cx, cy, cz, __fadd_rn(__fmul_rn(__fsqrt_rn(m), 1.00001f), 1e-6f));
+        centers[ch] = make_float4(cx, cy, cz, sqrtf(m) * 1.00001f + 1e-6f);
     }
 }
 

@@ -101,8 +101,14 @@ int fdcap_set_scene(fdcap_ctx* ctx, const float* scene_xyz, int64_t ns);
 /* Diagnosis: out8[0..7] = FNV-1a hashes of the registered scene's device tables (input-order points, cell-ordered points, inverse
  * permutation, cell / quarter-cell / super-cell boxes, MFMA fragments, cell centres).  The tables are built on the device since r6
  * (csrc/fdc_scene.h); with FDCAP_SCENE_BUILD=host in the environment fdcap_set_scene takes the cell order from the host recursion of
- * r1-r5 instead -- the same order by specification, which tests check by comparing these hashes.  Synchronises the device. */
+ * r1-r5 instead -- the same order by specification.  Comparing the hashes of the two builds pins the ORDER only: both run the same
+ * kernels for the boxes, fragments and centres.  Synchronises the device. */
 int fdcap_debug_scene_hash(fdcap_ctx* ctx, uint64_t* out8);
+/* Diagnosis: table `which` (0..7, the order of fdcap_debug_scene_hash) of the registered scene copied as it is to the HOST buffer
+ * host_out, exactly *bytes bytes; host_out == NULL: *bytes <- the table's size.  FDCAP_E_ARG on a bad `which` or a size mismatch,
+ * FDCAP_E_STATE without a registered scene.  Tests compare all eight tables byte for byte with an independent specification
+ * (tests/scene_spec.py).  Synchronises the device. */
+int fdcap_debug_scene_table(fdcap_ctx* ctx, int32_t which, void* host_out, int64_t* bytes);
 /* Diagnosis: names of the kernel FORMS launched by this process since the last reset, "a;b;c" (several stages pick among forms by
  * row count and set size: blend products, contact forward, skinning backward, the Chamfer search).  Tests that mean to cover a form
  * check that it ran.  FDCAP_CLIP_FORMS_MIN_ROWS (environment, read once per process) lowers the row count from which the

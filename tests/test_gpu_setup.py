@@ -2,10 +2,13 @@
 
 fdcap_set_scene builds the search's scene tables on the device (csrc/fdc_scene.h: three radix-sorted index lists, one stable
 partition per k-d level, boxes / fragments per cell).  The order is a specification (longest axis, (coordinate, index) rank,
-512 / 32-point units, input order inside a tile) that the host recursion of r1-r5 also follows, so every table must come out
-the same bit for bit from both -- ragged sizes, duplicate points, coordinate ties that straddle a cut, signed zeros, and the
-BASELINE scenes.  What the search RETURNS never depends on the order at all (tests/test_gpu_parity.py, test_gpu_fullsize.py);
-this file pins the order itself, and that an arbitrary scene's neighbours match the oracle's scan after the device build.
+512 / 32-point units, input order inside a tile) that the host recursion of r1-r5 also follows, so the hashes of all eight tables
+must come out the same from both -- ragged sizes, duplicate points, coordinate ties that straddle a cut, signed zeros, and the
+BASELINE scenes.  That comparison pins the ORDER only: with FDCAP_SCENE_BUILD=host the boxes, fragments and centres still come
+from the same device kernels (sc_finalize_kernel, sc_super_kernel).  All eight tables are pinned byte for byte against an
+independent specification in tests/test_gpu_scene_tables.py (tests/scene_spec.py).  What the search RETURNS never depends on the
+order at all (tests/test_gpu_parity.py, test_gpu_fullsize.py); this file pins the order itself, and that an arbitrary scene's
+neighbours match the oracle's scan after the device build.
 
 fdcap_ctx_create / fdcap_set_contact_ids pack the static operands of the dense products (fp32 fragment order, two scaled fp16
 planes + column scales) with device kernels; FDCAP_PANEL_PACK=host keeps the host loops of csrc/fdc_panel.h as the specification:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised stress of fdcap_set_scene's device build against the host specification (FDCAP_SCENE_BUILD=host): 222 scenes of 1 .. 1 M
-points -- uniform, anisotropic, coordinates on a coarse grid (ties across every cut), duplicated points, the synthetic room -- all
-eight tables compared by hash (fdcap_debug_scene_hash).  r6: 0 mismatches.   usage: python tools/stress_scene_build.py"""
+points -- uniform, anisotropic, coordinates on a coarse grid (ties across every cut), duplicated points, the synthetic room -- the
+hashes of all eight tables compared (fdcap_debug_scene_hash).  Both builds take the boxes, fragments and centres from the same device
+kernels, so this pins the cell ORDER only; tests/test_gpu_scene_tables.py pins all eight tables against an independent
+specification (tests/scene_spec.py).  r6: 0 mismatches.   usage: python tools/stress_scene_build.py"""
 import ctypes, os, sys
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import numpy as np
