@@ -90,11 +90,12 @@ int fdcap_opt_create(fdcap_ctx* c, const fdcap_opt_config* cfg, float* rows_x, f
             hipError_t e_ = o->nnc_ids.ensure(ng4 * NN_CACHE_CAP);
             if (e_ == hipSuccess) e_ = o->nnc_hdr.ensure(ng4 + 3 * ng);                                        // + work counts [ng] + two launch-order tables [ng]
             if (e_ == hipSuccess) e_ = o->nnc_anchor.ensure((size_t)4 * nq_all);
+            if (e_ == hipSuccess && every > 0) e_ = o->nnq_buf.ensure(nn_query_order_ints(nq_all));
             if (e_ == hipSuccess) e_ = hipMemset(o->nnc_hdr.p, 0xFF, ng4 * sizeof(int));                       // -1: nothing kept
             if (e_ == hipSuccess) e_ = hipMemset(o->nnc_hdr.p + ng4, 0, 3 * ng * sizeof(int));
             if (e_ == hipSuccess) e_ = hipMemset(o->nnc_anchor.p, 0, (size_t)4 * nq_all * sizeof(float4));
             if (e_ != hipSuccess) err = (int)e_;
-            if (every > 0) { o->nn_order.on = true; o->nn_order.every = every; }
+            if (every > 0) { o->nn_order.on = true; o->nn_order.every = every; o->nn_order.qbuf = o->nnq_buf.p; }
         }
     }
     if (!err) {
@@ -372,6 +373,32 @@ int fdcap_opt_backward_and_step(fdcap_ctx* c, int32_t ii, int32_t P, int32_t log
     lw.dct = 0.f;
     lw.world_on = phase2;
     return opt_backward_impl(c, lw, log_terms, (hipStream_t)stream, ii, P);
+}
+
+// Tests / diagnosis: which queries share a wave of the in-loop search (fdc_chamfer.h NNCache::perm).  The kept work lists go.
+int fdcap_debug_nn_query_order(fdcap_ctx* c, int32_t mode, const int32_t* perm_host, int32_t n) {
+    if (!c || !c->opt) return FDCAP_E_STATE;
+    if (mode < 0 || mode > 2) return FDCAP_E_ARG;
+    OptState* o = c->opt;
+    NNOrder& ord = o->nn_order;
+    if (!o->contact_on || ord.qbuf == nullptr) return FDCAP_E_STATE;
+    const int nq = o->cfg.n_local * c->nc;
+    if (mode == 2) {                                         // a permutation of [0, nq), or nothing is changed
+        if (!perm_host || n != nq) return FDCAP_E_ARG;
+        std::vector<char> seen((size_t)nq, 0);
+        for (int i = 0; i < nq; ++i) {
+            if (perm_host[i] < 0 || perm_host[i] >= nq || seen[perm_host[i]]) return FDCAP_E_ARG;
+            seen[perm_host[i]] = 1;
+        }
+    }
+    HIP_TRY(hipDeviceSynchronize());                         // (no launch in flight reads the table or the lists)
+    if (mode == 2) HIP_TRY(hipMemcpy(ord.qbuf, perm_host, (size_t)nq * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(o->nnc_hdr.p, 0xFF, (size_t)(nq + 31) / 32 * sizeof(int)));
+    ord.perm_mode = mode;
+    ord.perm_n = mode == 2 ? nq : 0;                         // mode 0: the next launch runs in query order and builds one after it
+    ord.sorted_groups = 0;
+    ord.age = 0;
+    return FDCAP_OK;
 }
 
 }  // extern "C"

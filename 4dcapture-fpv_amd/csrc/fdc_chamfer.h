@@ -521,6 +521,11 @@ struct NNCache {
     // Indexed by POSITION because blockIdx lives in a scalar register for free: the one-wave kernel sits at its 64-register
     // limit, and keeping the group index (or two more pointer arguments) alive for this store cost 8-10 spilled registers.
     int order_mode = 0;       // 0: off, 1: record the work items, 2 / 3: record + launch in the order of table 0 / 1
+    // r7: which queries share a wave (one-wave workgroups only; scheduling, never results): slot s of the launch serves query
+    // perm[s] (nullptr: query s).  A wave's work is the union of the quarters its 32 queries reach; 32 consecutive contact ids of
+    // a frame are scattered over a whole leg, 32 queries whose neighbours share a k-d quarter reach nearly one list
+    // (nn_query_order below).  Kept lists, anchors and the work items stay per slot; dist / idx / seedpt stay per query.
+    const int* perm = nullptr;
 };
 
 template <int NQ, int WPG, int WPB = 4>
@@ -535,6 +540,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     __shared__ float s_d[WPB][32 * NQ];
     __shared__ int s_i[WPB][32 * NQ];
     __shared__ float4 s_p[WPB][32 * NQ];
+    __shared__ int s_q[WPB][32 * NQ];                            // the query each slot serves (cache.perm)
     static_assert(WPG == 1 || WPG == 2 || WPG == 4, "waves per query group");
     static_assert(WPB % WPG == 0 && WPB <= 4, "a group's waves share a workgroup");
     constexpr int GPW = WPB / WPG;                               // query groups per workgroup
@@ -572,9 +578,15 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     float lqx[NQ], lqy[NQ], lqz[NQ];
     int lsj[NQ];
     float4 lsp[NQ];
+    // (the query order costs this wave one dependent round trip before the batch; only the one-wave form takes one)
+    const int* const perm = NQ == 1 && WPB == 1 ? cache.perm : nullptr;
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
-        const size_t qc = (size_t)min(wq0 + n * 32 + col, nq - 1);
+        size_t qc = (size_t)min(wq0 + n * 32 + col, nq - 1);
+        if (perm) {
+            qc = (size_t)perm[qc];
+            if (half == 0) s_q[wave][n * 32 + col] = (int)qc;
+        }
         lqx[n] = q[3 * qc]; lqy[n] = q[3 * qc + 1]; lqz[n] = q[3 * qc + 2];
         lsj[n] = seed[qc];
         lsp[n] = seedpt[qc];                                      // the seed's coordinates, kept from the launch that found it
@@ -1187,9 +1199,10 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
                 const int i = s_i[g * WPG + w][e];
                 if (i >= 0 && (bi < 0 || nn_better(d, i, bd, bi))) { bd = d; bi = i; bw = g * WPG + w; }
             }
-            dist[qo] = bd;
-            idx[qo] = bi;
-            seedpt[qo] = s_p[bw][e];
+            const int qd = perm ? s_q[g][e] : qo;
+            dist[qd] = bd;
+            idx[qd] = bi;
+            seedpt[qd] = s_p[bw][e];
         }
     }
 }
@@ -1375,7 +1388,14 @@ struct NNOrder {
     int cur = 0;                // which of the two order tables is current
     int age = 0;                // launches since it was written
     int every = 32;             // re-sort period (work per group drifts over tens of iterations)
+    // r7: the query order (NNCache::perm).  Rebuilt after the seeding launch and then in place of every re-sort of the launch
+    // order, which follows it one launch later (the work items it sorts must be the new groups').
+    int* qbuf = nullptr;        // device: perm [nq] + sort scratch (nn_query_order_ints); nullptr: no query order
+    int perm_n = 0;             // the nq perm holds an order for (0: none yet)
+    int perm_mode = 0;          // 0: locality order, rebuilt; 1: identity; 2: imposed by the caller, never rebuilt (fdcap_debug_nn_query_order)
 };
+static inline size_t nn_query_order_ints(int nq);                       // fdc_scene.h (the radix sort lives there)
+static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st);
 
 // workspace: pd/pi [nsplit*nq]; seed: optional [nq] original indices (may alias idx: read before idx is rewritten)
 static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, float* dist, int* idx, float* pd, int* pi,
@@ -1419,6 +1439,8 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
             NNCache nc = cache ? *cache : NNCache{nullptr, nullptr, nullptr, 0.f};
             const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && wpg == 1;
             nc.order_mode = !ordered ? 0 : (ord->sorted_groups == groups ? 2 + ord->cur : 1);
+            const bool qorder = ordered && ord->qbuf != nullptr && ord->perm_mode != 1;
+            nc.perm = qorder && ord->perm_n == nq ? ord->qbuf : nullptr;
             if (wpg == 4) {
                 note_form("nn_stream4_kernel(4 waves per group)");
                 hipLaunchKernelGGL((nn_stream4_kernel<1, 4>), grid, dim3(256), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
@@ -1429,7 +1451,16 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
                 note_form("nn_stream4_kernel<1,1,1>");
                 hipLaunchKernelGGL((nn_stream4_kernel<1, 1, 1>), grid, dim3(64), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
             }
-            if (ordered && (ord->sorted_groups != groups || ++ord->age >= ord->every)) {
+            const bool resort = ordered && (ord->sorted_groups != groups || ++ord->age >= ord->every);
+            if (qorder && ord->perm_mode == 0 && (ord->perm_n != nq || seed_missing || (resort && ord->sorted_groups == groups))) {
+                // new groups: their kept lists go (hdr = -1, by the key kernel), the next launch records its work items in
+                // plain launch order and the launch order is sorted after it
+                const hipError_t e = nn_query_order(seedpt, nq, ord->qbuf, nc.hdr, groups, st);
+                if (e != hipSuccess) return e;
+                ord->perm_n = nq;
+                ord->sorted_groups = 0;
+                ord->age = 0;
+            } else if (resort) {
                 const bool had = nc.order_mode >= 2;
                 const int nxt = had ? 1 - ord->cur : 0;
                 hipLaunchKernelGGL(nn_order_kernel, dim3(1), dim3(1024), 0, st, (const int*)(nc.hdr + 4 * groups), groups,

@@ -141,6 +141,7 @@ struct OptState {
     DevBuf<unsigned short> nnc_ids;
     DevBuf<int> nnc_hdr;
     DevBuf<float4> nnc_anchor;
+    DevBuf<int> nnq_buf;                   // the in-loop NN launch's query order + its sort scratch (fdc_chamfer.h NNOrder::qbuf)
     NNOrder nn_order;                      // launch order of the in-loop NN launch (fdc_chamfer.h NNOrder; its tables sit behind nnc_hdr); FDCAP_NN_ORDER=0 turns it off, =k re-sorts every k launches
     float nnc_slack = 0.03f;  // metres; FDCAP_NN_CACHE_SLACK overrides, 0 disables the cache
     // fdcap_opt_launch_timing (r6): a HIP event on the launch stream at every boundary between two launches of an iteration; the time

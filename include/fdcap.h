@@ -476,6 +476,12 @@ int fdcap_panel_gemm(const float* A_d, int32_t lda, int32_t M, int32_t K, const 
 int fdcap_opt_nn_timing(fdcap_ctx* ctx, int32_t max_launches);
 int fdcap_opt_nn_timing_read(fdcap_ctx* ctx, float* mean_ms, int32_t* launches);
 
+/* Tests / diagnosis: which queries share a wave of the in-loop Chamfer NN launch (scheduling only: every mode gives the same
+ * bits).  mode 0 (default): grouped by the k-d quarter of each query's current neighbour, rebuilt after the seeding launch and
+ * every 32 launches; 1: query order (32 consecutive query indices per wave); 2: perm_h [n] (n = frames x contacts, a
+ * permutation: wave slot s serves query perm_h[s]), kept until the next call.  Drops the kept work lists.  Synchronises the device. */
+int fdcap_debug_nn_query_order(fdcap_ctx* ctx, int32_t mode, const int32_t* perm_h, int32_t n);
+
 /* In-loop timing of EVERY launch of an iteration (r6; bench.py's roofline.per_kernel[].us_live): while enabled (max_events > 0) the
  * optimiser records a HIP event on its launch stream at every boundary between two launches of an iteration (up to max_events
  * events in all; 0 disables and resets) -- one fit of 500 iterations records ~4100.  fdcap_opt_launch_timing_read waits for them and
