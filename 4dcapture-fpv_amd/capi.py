@@ -80,6 +80,7 @@ SYMBOLS = {
     "fdcap_smplx_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                        c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_create": (c_int32, [c_void_p, POINTER(OptConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_create_clips": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_set_inputs": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_backward": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "fdcap_opt_step": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),

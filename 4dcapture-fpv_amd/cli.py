@@ -5,19 +5,75 @@
 `<body_path>/results/*/*.pkl` in, `<fit_path>/body_gen_%06d.pkl` out.  The reference hard-codes
 `/home/miao/<sample>/meshed-poisson.ply` and `camerapose.txt` (:667-668); the root is configurable
 here (`--scene-root`, or explicit `--scene` / `--camera`).  `./models`, `./vposer/`,
-`./body_segments` default to the reference's CWD-relative paths (:669-675)."""
+`./body_segments` default to the reference's CWD-relative paths (:669-675).
+
+Several clips in one run (the reference's real workload: every video cut into 300-frame segments, utils/split_frames.py):
+
+    python3 global_optimization_hip.py --clips BODY_PATH [BODY_PATH ...] --fit-root DIR [--clips-per-batch K]
+
+Each clip's scene and camera paths are derived from its sample name as above (`--scene-root`).  Clips are grouped by (scene
+file -- the resolved path, so that the segments of one video may link one scene --, clip length); each group is cut into batches of at most K clips that are fitted as one optimisation (fitting.ClipBatchFitter:
+one context for the whole run).  Clip output: `<fit-root>/<sample_name>/body_gen_%06d.pkl`, the files the one-clip form writes
+with that directory as <fit_path>.  Default K: the largest K with K * N <= MULTICLIP_ROW_CAP.  Mode 'global' only."""
 from __future__ import annotations
 
 import argparse
 import os
 import sys
 
+# Largest row count (clips x frames) of a default batch of the multi-clip form: up to 1024 rows the per-frame kernels run in one
+# round of workgroups (DESIGN 5.2; 1280 frames take a second); profiles/r7_multiclip300.json has the sweep over K at N = 300.
+MULTICLIP_ROW_CAP = 1024
+
+
+def sample_name_of(body_path: str) -> str:
+    """The sample name the reference takes from the body path (:662)."""
+    return body_path.split("/")[-2]
+
+
+def clip_paths(body_path: str, scene_root: str):
+    """(sample name, scene path, camera path) of a clip, derived as the one-clip form derives them (:662-668)."""
+    name = sample_name_of(body_path)
+    return name, os.path.join(scene_root, name, "meshed-poisson.ply"), os.path.join(scene_root, name, "camerapose.txt")
+
+
+def clip_output_dir(fit_root: str, body_path: str) -> str:
+    return os.path.join(fit_root, sample_name_of(body_path))
+
+
+def batch_size(n_frames: int, clips_per_batch=None, row_cap: int = MULTICLIP_ROW_CAP) -> int:
+    """Clips per batch for clips of n_frames: the given K, else the largest K with K * n_frames <= row_cap (at least 1)."""
+    if clips_per_batch:
+        return max(1, int(clips_per_batch))
+    return max(1, row_cap // max(1, int(n_frames)))
+
+
+def plan_batches(clips, clips_per_batch=None, row_cap: int = MULTICLIP_ROW_CAP):
+    """clips: sequence of (scene path, clip length).  Groups them by (scene path, clip length) -- groups in order of their first
+    clip, clips in input order within a group -- and cuts every group into batches of batch_size() clips.
+    Returns [(scene path, clip length, [clip indices])]."""
+    groups = {}
+    for i, (scene, n) in enumerate(clips):
+        groups.setdefault((scene, int(n)), []).append(i)
+    out = []
+    for (scene, n), idx in groups.items():
+        k = batch_size(n, clips_per_batch, row_cap)
+        out.extend((scene, n, idx[j:j + k]) for j in range(0, len(idx), k))
+    return out
+
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="global_optimization (fdcap_amd / MI355X)")
-    ap.add_argument("body_path")
-    ap.add_argument("fit_path")
+    ap.add_argument("body_path", nargs="?")
+    ap.add_argument("fit_path", nargs="?")
     ap.add_argument("mode", nargs="?", default="global", choices=["global", "local", "dct"])
+    ap.add_argument("--clips", nargs="+", default=None, metavar="BODY_PATH",
+                    help="several clips in one run (mode 'global'): fitted in batches of one scene and clip length")
+    ap.add_argument("--fit-root", default=None, help="multi-clip form: clip output goes to <fit-root>/<sample_name>/")
+    ap.add_argument("--clips-per-batch", type=int, default=None,
+                    help=f"multi-clip form: clips per batch (default: the largest K with K * frames <= {MULTICLIP_ROW_CAP})")
+    ap.add_argument("--mode", dest="mode_opt", default=None, choices=["global", "local", "dct"],
+                    help="multi-clip form: the mode (only 'global' is supported)")
     ap.add_argument("--scene-root", default="/home/miao/")
     ap.add_argument("--scene", default=None, help="scene vertices (.ply/.xyz/.npy); default <root>/<sample>/meshed-poisson.ply")
     ap.add_argument("--camera", default=None, help="camerapose.txt; default <root>/<sample>/camerapose.txt")
@@ -30,6 +86,10 @@ def main(argv=None):
     ap.add_argument("--dct-mat", default="../Data/DCT_Basis/60.mat", help="DCT basis .mat (:45); generated if absent")
     ap.add_argument("--dct-num-iter", type=int, default=10000, help="iterations of mode 'dct' (:596)")
     a = ap.parse_args(argv)
+    if a.clips is not None:
+        return _main_clips(ap, a)
+    if a.body_path is None or a.fit_path is None:
+        ap.error("body_path and fit_path are required (or --clips ... --fit-root DIR)")
 
     import torch
     from . import io
@@ -47,6 +107,44 @@ def main(argv=None):
     fop = FittingOP(fittingconfig, lossconfig, data.shape[0], dct_num_iter=a.dct_num_iter)
     body_rec, scale, camera_ext = fop.fitting(torch.tensor(data).cuda(), a.mode, log_every=a.log_every)
     fop.save_result(body_rec, scale, camera_ext, a.fit_path)                     # :714
+    print("[INFO][fitting] fitting finish, returning optimal value")
+    return 0
+
+
+def _main_clips(ap, a):
+    mode = a.mode_opt or "global"
+    if a.body_path is not None or a.fit_path is not None:
+        ap.error("--clips takes the clips' body paths; positional body_path / fit_path belong to the one-clip form")
+    if mode != "global":
+        ap.error(f"--clips fits mode 'global' only (got mode '{mode}'); run modes 'local' and 'dct' one clip at a time")
+    if not a.fit_root:
+        ap.error("--clips needs --fit-root DIR")
+    if a.scene or a.camera:
+        ap.error("--clips derives every clip's scene and camera paths from --scene-root; --scene / --camera are one-clip options")
+    if a.clips_per_batch is not None and a.clips_per_batch < 1:
+        ap.error("--clips-per-batch must be at least 1")
+    from . import io
+    from .fitting import ClipBatchFitter
+    data, cams, scenes = [], [], []
+    for bp in a.clips:
+        _, scene, camera = clip_paths(bp, a.scene_root)
+        data.append(io.load_body_gen(bp))                                       # :688-707
+        cams.append(io.read_camerapose(camera))
+        scenes.append(os.path.realpath(scene))                                  # (segments of one video may link one scene file)
+    fittingconfig = {"human_model_path": a.models, "vposer_ckpt_path": a.vposer, "init_lr_h": a.lr, "num_iter": a.num_iter,
+                     "contact_id_folder": a.body_segments, "contact_part": ["L_Leg", "R_Leg"], "verbose": bool(a.log_every)}
+    lossconfig = {"weight_loss_rec": 1, "weight_loss_vposer": 0.001, "weight_contact": 0.1, "weight_collision": 0.5}
+    fitter = ClipBatchFitter(fittingconfig, lossconfig)
+    try:
+        for scene, n, idx in plan_batches([(s, d.shape[0]) for s, d in zip(scenes, data)], a.clips_per_batch):
+            pts = None if scene == fitter.scene_key else io.read_scene_points(scene)
+            res = fitter.fit([(data[i], cams[i]) for i in idx], pts, scene_key=scene, log_every=a.log_every)
+            for i, (body_rec, scale, camera_ext) in zip(idx, res):
+                io.save_result(body_rec.detach().cpu().numpy(), scale, camera_ext.detach().cpu().numpy(),
+                               clip_output_dir(a.fit_root, a.clips[i]))
+            print(f"[INFO][fitting] batch of {len(idx)} clips x {n} frames fitted ({scene})")
+    finally:
+        fitter.close()
     print("[INFO][fitting] fitting finish, returning optimal value")
     return 0
 

@@ -6,6 +6,7 @@ extern "C" {
 
 // ---- mode 'dct' (global_optimization.py:595-630) -----------------------------------------------
 int fdcap_opt_set_dct(fdcap_ctx* c, const float* dct_mtx, int32_t T, int32_t C, const float* c_dct_d, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !dct_mtx || !c_dct_d || T <= 0 || T > DCT_MAXT || C <= 0 || C > DCT_MAXC) return FDCAP_E_ARG;
     OptState* o = c->opt;
     const int W = o->cfg.n_total / T;
@@ -25,6 +26,7 @@ int fdcap_opt_set_dct(fdcap_ctx* c, const float* dct_mtx, int32_t T, int32_t C, 
 
 int fdcap_opt_dct_fit(fdcap_ctx* c, int32_t iters, int32_t step0, float weight, float* obj_hist, int32_t log_stride,
                       void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || iters < 0 || step0 < 0 || (obj_hist && log_stride <= 0)) return FDCAP_E_ARG;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
     OptState* o = c->opt;
@@ -55,6 +57,7 @@ int fdcap_opt_dct_fit(fdcap_ctx* c, int32_t iters, int32_t step0, float weight, 
 }
 
 int fdcap_opt_backward_dct(fdcap_ctx* c, float w_dct, float w_rec, float w_contact, int32_t log_terms, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt) return FDCAP_E_STATE;
     if (c->opt->dctW <= 0) return FDCAP_E_STATE;
     LossWeights lw;
@@ -63,6 +66,7 @@ int fdcap_opt_backward_dct(fdcap_ctx* c, float w_dct, float w_rec, float w_conta
 }
 
 int fdcap_opt_set_dct_coef(fdcap_ctx* c, const float* c_dct_d, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !c_dct_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     if (o->dctW <= 0) return FDCAP_E_STATE;
@@ -72,6 +76,7 @@ int fdcap_opt_set_dct_coef(fdcap_ctx* c, const float* c_dct_d, void* stream) {
 }
 
 int fdcap_opt_get_dct(fdcap_ctx* c, float* c_dct_d, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !c_dct_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     if (o->dctW <= 0) return FDCAP_E_STATE;
@@ -81,6 +86,7 @@ int fdcap_opt_get_dct(fdcap_ctx* c, float* c_dct_d, void* stream) {
 }
 // Adam's moments of c_dct, [W,69,C] each: what a checkpoint of mode 'dct' needs next to fdcap_opt_get_dct / fdcap_opt_export_state
 static int dct_state_copy(fdcap_ctx* c, float* m_d, float* v_d, bool out, hipStream_t st) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !m_d || !v_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     if (o->dctW <= 0) return FDCAP_E_STATE;
@@ -105,6 +111,7 @@ int32_t fdcap_opt_dct_windows(fdcap_ctx* c, int32_t* w0, int32_t* w1) {
 
 // ---- per-frame inner fit with a 2D reprojection term (outside the reference) ------
 int fdcap_opt_set_keypoints(fdcap_ctx* c, const float* kp_d, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !kp_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     const size_t n = (size_t)o->cfg.n_local * NJW * 3;
@@ -115,6 +122,7 @@ int fdcap_opt_set_keypoints(fdcap_ctx* c, const float* kp_d, void* stream) {
 
 static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses, float* floss, hipStream_t st, bool fold = true);
 int fdcap_opt_backward_fit2d(fdcap_ctx* c, const fdcap_fit2d_stage* sg, int32_t log_terms, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !sg) return FDCAP_E_ARG;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
     OptState* o = c->opt;
@@ -227,6 +235,7 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
 
 int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap_lbfgs_config* cfg, int32_t max_rounds, int32_t* rounds_out,
                           void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !sg || !cfg || max_rounds <= 0) return FDCAP_E_ARG;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
     OptState* o = c->opt;
@@ -273,6 +282,7 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap
 }
 
 int fdcap_opt_fit2d_lbfgs_stats(fdcap_ctx* c, int32_t* it, int32_t* ev, float* loss, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !c->opt->lbfgs) return FDCAP_E_STATE;
     return fdcap_lbfgs_get_stats(c->opt->lbfgs, it, ev, loss, stream);
 }
@@ -292,13 +302,13 @@ int fdcap_opt_reset_adam(fdcap_ctx* c, void* stream) {
 // ---- checkpoint / resume of the optimiser state, finite check (the reference has neither) -----------
 int32_t fdcap_opt_state_len(fdcap_ctx* c) {
     if (!c || !c->opt) return 0;
-    return (int32_t)(2 * ((size_t)c->opt->cfg.n_local * (XDIM + 16)) + 2);
+    return (int32_t)(2 * ((size_t)c->opt->cfg.n_local * (XDIM + 16)) + 2 * (size_t)c->opt->nclip);
 }
 static int opt_state_copy(fdcap_ctx* c, float* state, bool to_state, hipStream_t st) {
     OptState* o = c->opt;
     const size_t nl = o->cfg.n_local, nx = nl * XDIM, ncam = nl * 16;
     struct Part { float* lib; size_t n; } parts[] = {{o->mX.p + 2 * XDIM, nx}, {o->vX.p + 2 * XDIM, nx}, {o->mCAM.p + 2 * 16, ncam},
-                                                     {o->vCAM.p + 2 * 16, ncam}, {o->mS.p, 1}, {o->vS.p, 1}};
+                                                     {o->vCAM.p + 2 * 16, ncam}, {o->mS.p, (size_t)o->nclip}, {o->vS.p, (size_t)o->nclip}};
     size_t off = 0;
     for (const Part& p : parts) {
         HIP_TRY(hipMemcpyAsync(to_state ? state + off : p.lib, to_state ? p.lib : state + off, p.n * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -327,7 +337,7 @@ int fdcap_opt_check_finite(fdcap_ctx* c, int32_t* count_d, void* stream) {
     HIP_TRY(hipMemsetAsync(count_d, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(count_nonfinite_kernel, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, st, o->X.p + 2 * XDIM, nx, count_d);
     hipLaunchKernelGGL(count_nonfinite_kernel, dim3((unsigned)((ncam + 255) / 256)), dim3(256), 0, st, o->CAM.p + 2 * 16, ncam, count_d);
-    hipLaunchKernelGGL(count_nonfinite_kernel, dim3(1), dim3(64), 0, st, o->scale.p, (size_t)1, count_d);
+    hipLaunchKernelGGL(count_nonfinite_kernel, dim3((o->nclip + 63) / 64), dim3(64), 0, st, o->scale.p, (size_t)o->nclip, count_d);
     return (int)hipGetLastError();
 }
 
@@ -361,13 +371,14 @@ int opt_step_launch(fdcap_ctx* c, int32_t ii, int32_t P, bool do_rows, bool do_s
     const int nl = o->cfg.n_local;
     if (do_rows) o->ahead = false;                         // the rows change: a forward that ran ahead of this step is stale
     const StepPlan sp = opt_step_plan(o, ii, P, do_rows, do_scale);
-    const bool tail = sp.step_scale || reduce_scale;                 // the last block: (reduction +) scale (+ message tail)
+    const bool tail = sp.step_scale || reduce_scale;                 // the last block(s): (reduction +) scale (+ message tail)
     if (sp.nb_x + sp.nb_cam + (tail ? 1 : 0) + (o->log_pending ? 1 : 0) == 0) return FDCAP_OK;
     TraceRange tr_("fdcap:adam(K22)");
-    const LogReduceIn lg = {o->loss_rows.p, o->log_dst, o->log_mask, o->log_assign, nl};
-    hipLaunchKernelGGL(adam_step_kernel, dim3(sp.nb_x + sp.nb_cam + 1 + (o->log_pending ? 1 : 0)), dim3(256), 0, st, sp.x, sp.cam, sp.sc, sp.nb_x, sp.nb_cam,
-                       o->dscale_row.p, 2, reduce_scale ? nl : 0, o->dscale.p, (sp.step_scale && ii >= P) ? 1 : 0, xch, nl, o->CAM.p,
-                       (do_rows && o->dz_pending) ? (const float*)o->dZpart.p : (const float*)nullptr, (size_t)o->R * VP_Z, lg);
+    const int K = o->nclip, rpc = o->rows_per_clip();               // (a batch of clips: one scale block and one log block per clip)
+    const LogReduceIn lg = {o->loss_rows.p, o->log_dst, o->log_mask, o->log_assign, rpc};
+    hipLaunchKernelGGL(adam_step_kernel, dim3(sp.nb_x + sp.nb_cam + K + (o->log_pending ? K : 0)), dim3(256), 0, st, sp.x, sp.cam, sp.sc, sp.nb_x, sp.nb_cam,
+                       o->dscale_row.p, 2, reduce_scale ? rpc : 0, o->dscale.p, (sp.step_scale && ii >= P) ? 1 : 0, xch, nl, o->CAM.p,
+                       (do_rows && o->dz_pending) ? (const float*)o->dZpart.p : (const float*)nullptr, (size_t)o->R * VP_Z, lg, K);
     o->log_pending = false;
     if (do_rows) o->dz_pending = false;
     return (int)hipGetLastError();

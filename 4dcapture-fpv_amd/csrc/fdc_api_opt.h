@@ -25,16 +25,24 @@ void fdcap_opt_destroy(fdcap_ctx* c) {
     c->opt = nullptr;
 }
 
-int fdcap_opt_create(fdcap_ctx* c, const fdcap_opt_config* cfg, float* rows_x, float* rows_cam, float* scale_d,
-                     float* dscale_d, double* losses_d) {
+static_assert(LROW == FDCAP_NUM_LOSSES, "a batch's per-clip loss slots are LROW apart on the device");
+int fdcap_opt_create_clips(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_clips, float* rows_x, float* rows_cam, float* scale_d,
+                           float* dscale_d, double* losses_d) {
     if (!c || !cfg || !rows_x || !rows_cam || !scale_d || !dscale_d || !losses_d || cfg->n_local <= 0 || cfg->n_total < cfg->n_local || cfg->frame0 < 0 ||
-        cfg->frame0 + cfg->n_local > cfg->n_total)
+        cfg->frame0 + cfg->n_local > cfg->n_total || n_clips < 1)
+        return FDCAP_E_ARG;
+    // a batch holds whole clips of one length: no shard of a clip, and K N rows that still index as int
+    if (n_clips > 1 && (cfg->frame0 != 0 || cfg->n_local != cfg->n_total || (int64_t)n_clips * cfg->n_total > (1 << 24)))
         return FDCAP_E_ARG;
     SetupTrace tr("fdcap_opt_create");
     // a second clip of the same shape reuses the scratch allocations (every buffer is re-zeroed below)
     OptState* o = c->opt ? c->opt : new OptState();
     c->opt = o;
     o->cfg = *cfg;
+    o->nclip = n_clips;
+    o->clip_len = cfg->n_total;
+    if (n_clips > 1) o->cfg.n_total = o->cfg.n_local = n_clips * cfg->n_total;     // the batch's rows: clip k owns 2 + k N .. 2 + (k + 1) N
+    cfg = &o->cfg;
     o->cam_steps = 0;
     o->dz_pending = false;
     o->log_pending = false;
@@ -59,7 +67,7 @@ int fdcap_opt_create(fdcap_ctx* c, const fdcap_opt_config* cfg, float* rows_x, f
     o->pend.on = false;
     AL(o->X0, (size_t)R * XDIM) AL(o->mask, R)
     AL(o->mX, (size_t)R * XDIM) AL(o->vX, (size_t)R * XDIM) AL(o->mCAM, (size_t)R * 16) AL(o->vCAM, (size_t)R * 16)
-    AL(o->mS, 1) AL(o->vS, 1)
+    AL(o->mS, n_clips) AL(o->vS, n_clips)
     AL(o->H1, (size_t)R * 512) AL(o->H2, (size_t)R * 512) AL(o->O, (size_t)R * O_LD) AL(o->dO, (size_t)R * ODIM)
     AL(o->Opart, (size_t)4 * R * ODIM) AL(o->dZpart, (size_t)4 * R * VP_Z)
     AL(o->Rm, (size_t)R * RM_LD) AL(o->PF, (size_t)R * NPFX) AL(o->Jrest, (size_t)R * JR_LD) AL(o->G, (size_t)R * NJ * 12)
@@ -99,13 +107,18 @@ int fdcap_opt_create(fdcap_ctx* c, const fdcap_opt_config* cfg, float* rows_x, f
         }
     }
     if (!err) {
-        float s = cfg->scale_init;
-        hipError_t e_ = hipMemcpy(o->scale.p, &s, sizeof(float), hipMemcpyHostToDevice);
+        const std::vector<float> s((size_t)n_clips, cfg->scale_init);
+        hipError_t e_ = hipMemcpy(o->scale.p, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e_ != hipSuccess) err = (int)e_;
     }
     tr.mark("search state");
     if (err) { fdcap_opt_destroy(c); return err; }
     return FDCAP_OK;
+}
+
+int fdcap_opt_create(fdcap_ctx* c, const fdcap_opt_config* cfg, float* rows_x, float* rows_cam, float* scale_d,
+                     float* dscale_d, double* losses_d) {
+    return fdcap_opt_create_clips(c, cfg, 1, rows_x, rows_cam, scale_d, dscale_d, losses_d);
 }
 
 int fdcap_opt_set_inputs(fdcap_ctx* c, const float* data78, const float* init78, const float* mask, const float* cam,
@@ -139,12 +152,13 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
         }
         note_form("blend_skin_fwd_kernel");
         hipLaunchKernelGGL(blend_skin_fwd_kernel, dim3(8 * ((nl + 31) / 32)), dim3(768), blend_skin_lds_bytes(smf.ja_hi), st, o->PF.p, nl,
-                           c->contact.pn_fwdS, smf, nc, smf.ja_hi, o->X.p, XDIM, X_TRANSL, o->A.p, o->M.p, o->scale.p, 2, o->Voff.p, o->Vw.p);
+                           c->contact.pn_fwdS, smf, nc, smf.ja_hi, o->X.p, XDIM, X_TRANSL, o->A.p, o->M.p, o->scale.p, 2, o->Voff.p, o->Vw.p,
+                           o->kclip_n());
     } else {
         if (!blend_done) HIP_TRY(blend_forward(c->contact, o->PF.p + 2 * NPFX, nl, o->Voff.p + off, st));
         note_form("skin_fwd_kernel");
         hipLaunchKernelGGL(skin_fwd_kernel, dim3((nc + 255) / 256, nl), dim3(256), 0, st, smf, nc, o->X.p, XDIM,
-                           X_BETAS, X_TRANSL, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, 1, o->Vw.p);
+                           X_BETAS, X_TRANSL, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, 1, o->Vw.p, o->kclip_n());
     }
     lt_mark(o, FDCAP_LT_CONTACT_FWD, st);
     const int nq = nl * nc;
@@ -174,12 +188,13 @@ struct LossWeights { float rec, smooth, contact, world, dct; bool world_on; };
 static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_terms, hipStream_t st, int fuse_ii = -1, int fuse_P = 0) {
     OptState* o = c->opt;
     const fdcap_opt_config& cf = o->cfg;
-    const int nl = cf.n_local, nc = c->nc, N = cf.n_total;
+    // N: the clip length -- the denominators of the means and the stencils' extent (a batch: every clip has N frames)
+    const int nl = cf.n_local, nc = c->nc, N = o->clip_len, rpc = o->rows_per_clip(), kn = o->kclip_n();
     const bool dct_on = lw.dct != 0.f && o->dctW > 0;
     PoseModel pm = c->pose_model();
     TraceRange tr_(fuse_ii >= 0 ? "fdcap:backward_and_step" : "fdcap:backward");
     if (o->log_pending) {                               // a deferred reduction nobody stepped after: deliver it before loss_rows is rewritten
-        hipLaunchKernelGGL(loss_rows_reduce_kernel, dim3(1), dim3(256), 0, st, o->loss_rows.p, 2, nl, o->log_mask, o->log_assign, o->log_dst,
+        hipLaunchKernelGGL(loss_rows_reduce_kernel, dim3(o->nclip), dim3(256), 0, st, o->loss_rows.p, 2, rpc, o->log_mask, o->log_assign, o->log_dst,
                            o->dscale_row.p, o->dscale.p);
         o->log_pending = false;
     }
@@ -187,7 +202,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
     // Logging without a DCT term: every printed term leaves per-frame partials in loss_rows (inside the kernels that run
     // anyway), one small launch sums them.  With the DCT term the separate param_loss_kernel / dct kernel add into losses[].
     const bool rows_log = losses && o->dctW == 0;
-    if (losses && !rows_log) HIP_TRY(hipMemsetAsync(losses, 0, FDCAP_NUM_LOSSES * sizeof(double), st));
+    if (losses && !rows_log) HIP_TRY(hipMemsetAsync(losses, 0, (size_t)o->nclip * FDCAP_NUM_LOSSES * sizeof(double), st));
     int row_lo, row_hi;
     opt_row_range(o, 1, &row_lo, &row_hi);
     const bool ahead = o->ahead, blend_done = o->ahead && o->ahead_blend;
@@ -209,7 +224,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
                                    rows_log ? o->loss_rows.p : nullptr};
     else
         hipLaunchKernelGGL(param_loss_kernel, dim3(nl), dim3(128), 0, st, o->X.p, o->X0.p, o->mask.p, o->Jw.p, 2, cf.frame0, N,
-                           w_rec, w_sm, w_ws, lw.world_on ? 1 : 0, o->dX.p, o->dJw.p, losses);
+                           w_rec, w_sm, w_ws, lw.world_on ? 1 : 0, o->dX.p, o->dJw.p, losses, kn);
     if (o->dctW > 0 && (dct_on || log_terms))
         hipLaunchKernelGGL(dct_joint_grad_kernel, dim3((nl * 69 + 255) / 256), dim3(256), 0, st, o->Jw.p, 2, cf.frame0, nl, o->dctT,
                            o->dctC, o->dctW, o->dctD.p, o->dctCoef.p, dct_on ? lw.dct / (69.f * (float)o->dctW) : 0.f,
@@ -234,30 +249,30 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
             if (o->skin_vec && nc <= 512 && G <= 3 && nnz <= 2048 * G && ldsv <= 60000 && (nc & 3) == 0 && smc.vpack && smc.csc_v16 &&
                 (((size_t)o->Vw.p | (size_t)o->Voff.p | (size_t)o->dVoff.p | (size_t)o->A.p) & 15) == 0) {
 #define FDC_SKV(GG) hipLaunchKernelGGL(skin_bwd_vec_kernel<GG>, dim3(nl), dim3(256), ldsv, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, \
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg)
+                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn)
                 note_form("skin_bwd_vec_kernel");
                 if (G == 1) FDC_SKV(1); else if (G == 2) FDC_SKV(2); else FDC_SKV(3);
 #undef FDC_SKV
             } else if (nc <= 512 && nnz <= 2048) {
                 note_form("skin_bwd_small_kernel");
                 hipLaunchKernelGGL((skin_bwd_small_kernel<2, 8>), dim3(nl), dim3(256), lds, st, c->contact.model(), nc, nnz, o->X.p, o->Voff.p, o->A.p,
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg);
+                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
             } else if (nc <= 512) {                                   // (K > 4 at the loop's contact-set size: up to 6144 list entries)
                 note_form("skin_bwd_small_kernel(K > 4)");
                 hipLaunchKernelGGL((skin_bwd_small_kernel<2, 24>), dim3(nl), dim3(256), lds, st, c->contact.model(), nc, nnz, o->X.p, o->Voff.p, o->A.p,
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg);
+                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
             } else if (nnz <= 4096) {
                 note_form("skin_bwd_small_kernel");
                 hipLaunchKernelGGL((skin_bwd_small_kernel<4, 16>), dim3(nl), dim3(256), lds, st, c->contact.model(), nc, nnz, o->X.p, o->Voff.p, o->A.p,
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg);
+                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
             } else {
                 note_form("skin_bwd_small_kernel");
                 hipLaunchKernelGGL((skin_bwd_small_kernel<4, 24>), dim3(nl), dim3(256), lds, st, c->contact.model(), nc, nnz, o->X.p, o->Voff.p, o->A.p,
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg);
+                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
             }
         } else
         { int es = skin_bwd_any<true>(c->ws_skin, st, nl, c->contact.model(), nc, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2,
-                                      (const float*)nullptr, o->dVoff.p, o->dA.p, (float*)nullptr, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg);
+                                      (const float*)nullptr, o->dVoff.p, o->dA.p, (float*)nullptr, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
           if (es) return es; }
         lt_mark(o, FDCAP_LT_SKIN_BWD, st);
         HIP_TRY(blend_backward(c->contact, o->dVoff.p + (size_t)2 * nc * 3, nl, o->dPF.p + 2 * NPFX, (size_t)o->R * NPFX, c->ws_kpart, st, &dpf_split));
@@ -272,7 +287,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
                        joint_grad ? o->dJw.p : nullptr, contact_grad ? o->dMv.p : nullptr, contact_grad ? o->dsv.p : nullptr,
                        contact_grad ? o->dPF.p + NPF : nullptr, NPFX, contact_grad ? o->dtransl_v.p : nullptr, o->dX.p, o->dO.p,
                        o->dCAM.p, o->dscale_row.p, pli, (contact_grad && dpf_split) ? (const float*)(o->dPF.p + (size_t)o->R * NPFX) : (const float*)nullptr,
-                       dA_rows);
+                       dA_rows, kn);
     lt_mark(o, FDCAP_LT_POSE_BWD, st);
     const unsigned log_mask = (rows_log ? 0x17u : 0u) | (contact_fwd ? 0x8u : 0u);     // 0 rec, 1 z^2, 2 smoothing, 4 world | 3 contact
     bool log_in_tail = false;
@@ -282,11 +297,11 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
             const StepPlan sp = opt_step_plan(o, fuse_ii, fuse_P, false, true);
             tail.dscale_row = o->dscale_row.p; tail.row0 = 2;
             if (sp.step_scale) {
-                tail.block = 0; tail.sc = sp.sc; tail.dscale = o->dscale.p; tail.n = nl;
+                tail.block = 0; tail.sc = sp.sc; tail.dscale = o->dscale.p; tail.n = rpc;
                 tail.zero_grad = fuse_ii >= fuse_P ? 1 : 0;
             }
             if (log_terms == 2 && rows_log) {           // the printed sums: same extra workgroup (loss_rows is complete before this launch)
-                tail.block = 0; tail.lg = LogReduceIn{o->loss_rows.p, losses, log_mask, 1, nl};
+                tail.block = 0; tail.lg = LogReduceIn{o->loss_rows.p, losses, log_mask, 1, rpc};
                 log_in_tail = true;
             }
         }
@@ -300,7 +315,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         if (log_terms == 2 && rows_log) {               // the sums ride in the step launch that follows (one launch less per iteration)
             o->log_pending = true; o->log_mask = log_mask; o->log_assign = 1; o->log_dst = losses;
         } else
-            hipLaunchKernelGGL(loss_rows_reduce_kernel, dim3(1), dim3(256), 0, st, o->loss_rows.p, 2, nl, log_mask, rows_log ? 1 : 0, losses,
+            hipLaunchKernelGGL(loss_rows_reduce_kernel, dim3(o->nclip), dim3(256), 0, st, o->loss_rows.p, 2, rpc, log_mask, rows_log ? 1 : 0, losses,
                                o->dscale_row.p, o->dscale.p);
     }
     return (int)hipGetLastError();
@@ -321,7 +336,7 @@ int fdcap_opt_set_loss_output(fdcap_ctx* c, double* losses_d) {
 // it between fdcap_opt_step_rows_and_pack and fdcap_opt_unpack_and_step_scale, so that it runs while the all-gather is in
 // flight ("overlap C1 with the start of the next forward"); fdcap_opt_backward(ii) then only adds the rest.
 int fdcap_opt_forward_ahead(fdcap_ctx* c, int32_t ii, int32_t P, int32_t log_terms, void* stream) {
-    if (!c || !c->opt) return FDCAP_E_STATE;
+    if (!c || !c->opt || c->opt->nclip > 1) return FDCAP_E_STATE;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
     OptState* o = c->opt;
     hipStream_t st = (hipStream_t)stream;
@@ -359,7 +374,7 @@ int fdcap_opt_backward_and_step(fdcap_ctx* c, int32_t ii, int32_t P, int32_t log
     if (!c || !c->opt) return FDCAP_E_STATE;
     OptState* o = c->opt;
     const fdcap_opt_config& cf = o->cfg;
-    const bool fuse = cf.frame0 == 0 && cf.n_local == cf.n_total && o->dctW == 0;
+    const bool fuse = opt_whole_clips(o) && o->dctW == 0;
     if (!fuse) {
         const int e = fdcap_opt_backward(c, ii, P, log_terms, stream);
         return e ? e : fdcap_opt_step(c, ii, P, stream);

@@ -6,6 +6,7 @@ extern "C" {
 
 // ---- mode 'local' (global_optimization.py:499-556) --------------------------------------------
 int fdcap_opt_detect_contact(fdcap_ctx* c, int32_t n_left, float* weight_left, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !weight_left || n_left <= 0 || n_left > c->nc) return FDCAP_E_ARG;
     OptState* o = c->opt;
     if (!o->contact_on) return FDCAP_E_STATE;
@@ -22,6 +23,7 @@ int fdcap_opt_detect_contact(fdcap_ctx* c, int32_t n_left, float* weight_left, v
 }
 
 int fdcap_opt_backward_local2(fdcap_ctx* c, const float* contact_weight, int32_t n_left, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !contact_weight || n_left <= 0 || n_left >= c->nc) return FDCAP_E_ARG;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
     OptState* o = c->opt;
@@ -71,6 +73,7 @@ int fdcap_opt_backward_local2(fdcap_ctx* c, const float* contact_weight, int32_t
 }
 
 int fdcap_opt_step_x(fdcap_ctx* c, int32_t step, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || step <= 0) return FDCAP_E_ARG;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
     OptState* o = c->opt;
@@ -90,7 +93,7 @@ int fdcap_opt_get_results(fdcap_ctx* c, float* body75, float* scale, float* cam,
     hipStream_t st = (hipStream_t)stream;
     const int nl = o->cfg.n_local;
     if (body75) hipLaunchKernelGGL(p78_to_75_kernel, dim3((nl + 127) / 128), dim3(128), 0, st, o->X.p + 2 * XDIM, nl, body75);
-    if (scale) HIP_TRY(hipMemcpyAsync(scale, o->scale.p, sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (scale) HIP_TRY(hipMemcpyAsync(scale, o->scale.p, (size_t)o->nclip * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (cam) HIP_TRY(hipMemcpyAsync(cam, o->CAM.p + 2 * 16, (size_t)nl * 16 * sizeof(float), hipMemcpyDeviceToDevice, st));
     return (int)hipGetLastError();
 }
@@ -121,11 +124,13 @@ int fdcap_opt_step(fdcap_ctx* c, int32_t ii, int32_t P, void* stream) { return o
 // Multi-GPU iteration tail with ONE collective: Adam on this rank's rows, pack [boundary rows | dscale],
 // (caller all-gathers), unpack halos + rank-ordered dscale sum + Adam on scale.
 int fdcap_opt_step_rows_and_pack(fdcap_ctx* c, int32_t ii, int32_t P, float* send, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !send) return FDCAP_E_ARG;
     return opt_step_impl(c, ii, P, true, false, true, stream, send);     // Adam on the rows + the message, one launch
 }
 int fdcap_opt_unpack_and_step_scale(fdcap_ctx* c, int32_t ii, int32_t P, const float* gathered, int32_t rank, int32_t world,
                                     void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || !gathered || world <= 0 || rank < 0 || rank >= world) return FDCAP_E_ARG;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
     OptState* o = c->opt;
@@ -196,6 +201,7 @@ const char* fdcap_comm_last_error(fdcap_ctx* c) { return c && !c->comm_err.empty
 // Fill the halo rows from the neighbouring ranks (before the first iteration, after fdcap_opt_import_state, after each
 // iteration of mode 'local''s second loop): boundary rows as they are -> all-gather -> unpack, three enqueues on `stream`.
 int fdcap_opt_halo_exchange(fdcap_ctx* c, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt) return FDCAP_E_STATE;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
     if (!c->comm.comm) return FDCAP_E_STATE;
@@ -215,6 +221,7 @@ int fdcap_opt_halo_exchange(fdcap_ctx* c, void* stream) {
 // rank-ordered sum of the scale-gradient partials, Adam on `scale`.  Replaces the caller-side sequence
 // fdcap_opt_step_rows_and_pack / all-gather / fdcap_opt_unpack_and_step_scale (same kernels, same bits).
 int fdcap_opt_exchange(fdcap_ctx* c, int32_t ii, int32_t P, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt) return FDCAP_E_STATE;
     if (!c->comm.comm) return FDCAP_E_STATE;
     int e = comm_buffers(c);
@@ -231,6 +238,7 @@ int fdcap_opt_exchange(fdcap_ctx* c, int32_t ii, int32_t P, void* stream) {
 // the message, each train between two HIP events on `stream`; mean microseconds of each.  EVERY rank of the communicator must make the
 // same call.  The optimiser's parameters and moments are stepped `iters` times with whatever gradients are there: call it after the fit.
 int fdcap_opt_time_exchange(fdcap_ctx* c, int32_t iters, float* us_exchange, float* us_allgather, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
     if (!c || !c->opt || iters <= 0 || !us_exchange || !us_allgather) return FDCAP_E_ARG;
     if (!c->comm.comm) return FDCAP_E_STATE;
     hipStream_t st = (hipStream_t)stream;
@@ -272,16 +280,16 @@ int fdcap_opt_run(fdcap_ctx* c, int32_t ii0, int32_t ii1, int32_t num_iter, int3
     if (!c || !c->opt) return FDCAP_E_STATE;
     if (ii0 < 0 || ii1 < ii0 || ii1 > num_iter || log_every < 0) return FDCAP_E_ARG;
     OptState* o = c->opt;
-    const fdcap_opt_config& cf = o->cfg;
-    const bool sharded = (flags & 2) != 0 || !(cf.frame0 == 0 && cf.n_local == cf.n_total);
-    if (sharded && !c->comm.comm) return FDCAP_E_STATE;
+    const bool sharded = (flags & 2) != 0 || !opt_whole_clips(o);
+    if (sharded && (!c->comm.comm || o->nclip > 1)) return FDCAP_E_STATE;
+    const size_t hist_row = (size_t)o->nclip * FDCAP_NUM_LOSSES;     // (a batch: [hist_rows][nclip][FDCAP_NUM_LOSSES])
     double* const keep = o->losses.p;
     int k = 0, e = 0;
     for (int ii = ii0; ii < ii1 && !e; ++ii) {
         const bool do_log = log_every > 0 && (ii % log_every == 0 || ii == num_iter - 1);
         if (do_log) {
             if (!hist_d || k >= hist_rows) { e = FDCAP_E_ARG; break; }      // (a stretch without logging iterations needs no history)
-            e = fdcap_opt_set_loss_output(c, hist_d + (size_t)k * FDCAP_NUM_LOSSES);
+            e = fdcap_opt_set_loss_output(c, hist_d + (size_t)k * hist_row);
             if (e) break;
             ++k;
         }

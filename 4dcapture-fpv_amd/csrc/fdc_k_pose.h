@@ -135,7 +135,9 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_fwd_kernel(PoseModel pm, co
                                                       const float* __restrict__ CAM, const float* __restrict__ scale,
                                                       int row0, float* Rm, float* PF, float* Jrest, float* G, float* A,
                                                       float* M, float* Jw, const float* AA, const float* __restrict__ Opart,
-                                                      size_t part_stride, int wo_lo = 0, int wo_hi = 0, DeferredStep ds = DeferredStep()) {
+                                                      size_t part_stride, int wo_lo = 0, int wo_hi = 0, DeferredStep ds = DeferredStep(),
+                                                      int clip_n = 0) {
+    // clip_n > 0: a batch of clips of clip_n frames -- this frame's `scale` is its clip's (clip_of_row, fdc_loss.h)
     __shared__ PoseScratch sc;
     __shared__ PoseStage stg;
     __shared__ float s_O[ODIM + 2];
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_fwd_kernel(PoseModel pm, co
         if (threadIdx.x >= 64) return;
         const float* x = X + (size_t)r * XDIM;
         M3 MR; V3 Mt;
-        world_matrix(CAM + (size_t)r * 16, x, *scale, &MR, &Mt);
+        world_matrix(CAM + (size_t)r * 16, x, scale[clip_of_row(r, clip_n)], &MR, &Mt);
         const V3 transl = v3(x[X_TRANSL], x[X_TRANSL + 1], x[X_TRANSL + 2]);
         const int j = threadIdx.x;
         if (j < NJW) {
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_fwd_kernel(PoseModel pm, co
             for (int q = 0; q < VP_NQ; ++q) glds4<2>(Opart + (size_t)q * part_stride + (size_t)r * ODIM, s_Op[q], ODIM);
         }
     }
-    const float sc_v = *scale;
+    const float sc_v = scale[clip_of_row(r, clip_n)];
     // A deferred optimiser step (DeferredStep, fdc_loss.h): this frame's row of body_rotation_rec / camera_ext takes its pending
     // Adam update here -- the loads ride in the staging batch, the stepped row goes to LDS (where the copy of the old one would
     // have gone) and back to global memory with both moments.
@@ -255,7 +257,10 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
                                                       const float* dA, const float* dPF, const float* dJw,
                                                       const float* dMv, const float* dsv, const float* dbeta_v,
                                                       int dbeta_stride, const float* dtransl_v, float* dX, float* dO,
-                                                      float* dCAM, float* dscale_row, ParamLossIn pl, const float* dPF2, int dA_nj = NJ) {
+                                                      float* dCAM, float* dscale_row, ParamLossIn pl, const float* dPF2, int dA_nj = NJ,
+                                                      int clip_n = 0) {
+    // clip_n > 0: a batch of clips of clip_n frames (fdcap_opt_create_clips): the frame's `scale` is its clip's, and the temporal
+    // stencils of the fused prologue see the frame's index within its clip (pl.frame0 = 0, pl.n_total = clip_n): cut at clip boundaries
     // dA_nj: rows of dA that were written (the rest are zero: SkinModel::ja_hi)
     // dPF2 (optional): second partial of dPF -- the data-gradient product split over K (panel_gemm3_rb2k_kernel); the row is
     // dPF + dPF2, d betas its columns NPF.. (dbeta_v must then be dPF + NPF, stride NPFX)
@@ -310,7 +315,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
         stage_pose_part<3>(pm, stg, xrow, camrow);
         glds4<2>(dX + (size_t)r * XDIM, s_dx, XDIM);         // the row a separate param_loss_kernel launch initialised
     }
-    const float sc_v = *scale;
+    const float sc_v = scale[clip_of_row(r, clip_n)];
     __shared__ float s_csum[POSE_NW];
     if (pl.cdist) {                                          // (kernel-uniform) contact_loss_rows_kernel's sum, same threads, same order
         float v = 0.f;
@@ -332,7 +337,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
     if (pl.X0) {
         // param_loss_kernel's gradients formed here: dX row (=) data + temporal terms on the raw rows, world-smoothing
         // gradient of this frame's joints into LDS instead of a round trip through dJw
-        const int g = pl.frame0 + blockIdx.x;
+        const int g = clip_n > 0 ? (int)blockIdx.x % clip_n : pl.frame0 + (int)blockIdx.x;
         const float lmask = s_misc[27];
         float l_rec = 0.f, l_vp = 0.f, l_sm = 0.f, l_ws = 0.f;
         // (two waves side by side: the first takes the parameter row's terms, the second the world joints')

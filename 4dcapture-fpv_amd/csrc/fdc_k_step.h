@@ -112,11 +112,13 @@ __global__ __launch_bounds__(128) void param_loss_kernel(const float* __restrict
                                                          int row0, int frame0, int n_total, float w_rec_over_cnt,
                                                          float w_sm_over_cnt, float w_ws_over_cnt, int world_grad,
                                                          float* __restrict__ dX, float* __restrict__ dJw,
-                                                         double* __restrict__ losses) {
+                                                         double* __restrict__ losses, int clip_n = 0) {
+    // (clip_n > 0: rows of a batch of clips of clip_n frames, frame0 = 0, n_total = clip_n -- the stencils are cut at clip
+    //  boundaries; a batch never takes this kernel's summed losses, its logged sums come from loss_rows)
     __shared__ float sred[2][4];
     const int tid = threadIdx.x;
     const int r = row0 + blockIdx.x;
-    const int g = frame0 + blockIdx.x;
+    const int g = clip_n > 0 ? (int)blockIdx.x % clip_n : frame0 + (int)blockIdx.x;
     float rec = 0.f, sm = 0.f, ws = 0.f, vp = 0.f;
     if (tid < XDIM) {
         const float* x = X + (size_t)r * XDIM + tid;
@@ -157,7 +159,11 @@ __global__ __launch_bounds__(128) void param_loss_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void loss_rows_reduce_kernel(const float* __restrict__ rows, int row0, int n, unsigned mask, int assign,
                                                                double* __restrict__ losses, const float* __restrict__ dscale_row,
                                                                float* __restrict__ dscale_out) {
-    loss_rows_reduce_block(rows, row0, n, mask, assign, losses, dscale_row, dscale_out);
+    // (a batch of clips: one workgroup per clip, n = one clip's rows; clip k's sums go to losses + k FDCAP_NUM_LOSSES, its
+    //  scale gradient to dscale_out[k])
+    const int k = blockIdx.x;
+    loss_rows_reduce_block(rows, row0 + k * n, n, mask, assign, losses ? losses + (size_t)k * LROW : losses, dscale_row,
+                           dscale_out ? dscale_out + k : dscale_out);
 }
 
 // dzpart != nullptr: p is body_rotation_rec from row `row0` on, and the latent columns' gradient still lacks the VPoser backward's
@@ -191,10 +197,13 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamTensor x, AdamTensor
                                                         const float* __restrict__ dscale_row, int row0, int reduce_n,
                                                         float* __restrict__ dscale, int scale_zero_grad,
                                                         float* __restrict__ xch, int n_local, const float* __restrict__ cam_rows,
-                                                        const float* __restrict__ dzpart, size_t dz_stride, LogReduceIn lg) {
+                                                        const float* __restrict__ dzpart, size_t dz_stride, LogReduceIn lg, int nclip = 1) {
+    // nclip > 1: a batch of clips -- blocks nb_x + nb_cam + k step clip k's `scale` (sc.p + k, reduced over that clip's reduce_n
+    // rows), blocks nb_x + nb_cam + nclip + k reduce its logged sums (lg.n rows) into lg.losses + k FDCAP_NUM_LOSSES
     const int b = blockIdx.x;
-    if (b == nb_x + nb_cam + 1) {                      // (only launched when a logging backward left its sums to this launch)
-        loss_rows_reduce_block(lg.rows, row0, lg.n, lg.mask, lg.assign, lg.losses, dscale_row, nullptr);
+    if (b >= nb_x + nb_cam + nclip) {                  // (only launched when a logging backward left its sums to this launch)
+        const int k = b - (nb_x + nb_cam + nclip);
+        loss_rows_reduce_block(lg.rows, row0 + k * lg.n, lg.n, lg.mask, lg.assign, lg.losses + (size_t)k * LROW, dscale_row, nullptr);
         return;
     }
     if (b < nb_x + nb_cam) {
@@ -225,6 +234,12 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamTensor x, AdamTensor
         return;
     }
     __shared__ float sred[4];
+    const int k = b - (nb_x + nb_cam);                 // (the clip whose `scale` this block steps)
+    if (k > 0) {
+        row0 += k * reduce_n;
+        dscale += k;
+        if (sc.p) { sc.p += k; sc.m += k; sc.v += k; }
+    }
     float g = 0.f;
     if (reduce_n > 0) {
         float a = 0.f;

@@ -41,6 +41,10 @@ FDC_HD float world_smooth_grad(int g, int n_total, float jm1, float j0, float jp
     return grad * w_over_cnt;
 }
 
+// A batch of clips (fdcap_opt_create_clips): clip k owns rows 2 + k clip_n .. 2 + (k + 1) clip_n of the optimiser's buffers and its
+// own `scale` (scale[k]).  clip_n = 0: the optimiser holds one clip (or one rank's share of one): every row reads scale[0].
+FDC_HD int clip_of_row(int r, int clip_n) { return clip_n > 0 ? (r - 2) / clip_n : 0; }
+
 struct AdamScalars { float one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps; };
 struct AdamTensor { float* p; float* m; float* v; const float* g; size_t n; AdamScalars a; };
 
@@ -74,6 +78,9 @@ struct ScaleTail {
     // barrier) instead of the extra workgroup: that one has a CU to itself (these kernels fit once per CU) and a regular workgroup
     // waits for it -- two cold reads and eight double-precision reductions there made every logging launch 1.3-3 us longer
     int lg_spread = 0;
+    // a batch of nclip clips (fdcap_opt_create_clips): workgroups block .. block + nclip - 1 are the tails, tail k serves clip k --
+    // rows row0 + k clip_n .., scale / moments / dscale + k, losses + k FDCAP_NUM_LOSSES (n, lg.n: one clip's rows)
+    int nclip = 1, clip_n = 0;
 };
 
 // torch.optim.Adam defaults: betas (0.9, 0.999), eps 1e-8; the bias corrections are evaluated
@@ -174,6 +181,16 @@ __device__ __forceinline__ void loss_rows_reduce_block(const float* __restrict__
         const float g = scale_grad_block(dscale_row, row0, n, sred);
         if (tid == 0) *dscale_out = g;
     }
+}
+// clip k's share of a batch's tail (k = 0: the tail itself)
+__device__ __forceinline__ ScaleTail scale_tail_clip(ScaleTail t, int k) {
+    if (k > 0) {
+        t.row0 += k * t.clip_n;
+        if (t.sc.p) { t.sc.p += k; t.sc.m += k; t.sc.v += k; }
+        if (t.dscale) t.dscale += k;
+        if (t.lg.losses) t.lg.losses += (size_t)k * LROW;
+    }
+    return t;
 }
 __device__ __forceinline__ void scale_tail_block(const ScaleTail& t) {
     __shared__ float s_tail[4];

@@ -1679,8 +1679,9 @@ __global__ __launch_bounds__(512) void vposer_bwd_fused_kernel(VPoserPanels P, c
                                                                float* __restrict__ dZpart, size_t part_stride, ScaleTail tail) {
     // (tail.block == 0: one extra workgroup, FIRST in the grid -- these kernels keep one workgroup per CU (LDS), a 261st at the
     //  end would wait for a CU to come free and then run alone; first, it is done in a microsecond and hands its CU to the rest)
-    if ((int)blockIdx.x == tail.block) { scale_tail_block(tail); return; }
-    const unsigned bid = blockIdx.x - (tail.block == 0 ? 1u : 0u);
+    // (a batch of clips: tail.nclip such workgroups, one per clip -- ScaleTail::nclip)
+    if (tail.block >= 0 && (int)blockIdx.x - tail.block < tail.nclip) { scale_tail_block(scale_tail_clip(tail, (int)blockIdx.x - tail.block)); return; }
+    const unsigned bid = blockIdx.x - (tail.block == 0 ? (unsigned)tail.nclip : 0u);
     __shared__ __attribute__((aligned(16))) float lds[VP_QW * 16 + VP_QW * 16 + VP_H * 16 + 8 * 256];
     float* const sdO = lds;                       // K = 126 padded to 128
     float* const sdH2 = sdO + VP_QW * 16;         // this quarter's 128 columns of dH2
@@ -1884,13 +1885,14 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
                                                                 float* __restrict__ dZpart, size_t part_stride, ScaleTail tail) {
     // (tail.block == 0: one extra workgroup, FIRST in the grid -- these kernels keep one workgroup per CU (LDS), a 261st at the
     //  end would wait for a CU to come free and then run alone; first, it is done in a microsecond and hands its CU to the rest)
-    if ((int)blockIdx.x == tail.block) {
-        ScaleTail t2 = tail;
+    // (a batch of clips: tail.nclip such workgroups, one per clip -- ScaleTail::nclip)
+    if (tail.block >= 0 && (int)blockIdx.x - tail.block < tail.nclip) {
+        ScaleTail t2 = scale_tail_clip(tail, (int)blockIdx.x - tail.block);
         if (tail.lg_spread) t2.lg.rows = nullptr;            // (the logged sums: regular workgroups, below)
         scale_tail_block(t2);
         return;
     }
-    const unsigned bid = blockIdx.x - (tail.block == 0 ? 1u : 0u);
+    const unsigned bid = blockIdx.x - (tail.block == 0 ? (unsigned)tail.nclip : 0u);
     constexpr int NP = VpF::NP;
     __shared__ __attribute__((aligned(16))) uint4 lds3[NP * (VP3_PQ + VP3_PQ + VP3_PH) + VpF::SC_U4 + 8 * 64];
     uint4* const sdO = lds3;                      // K = 126 padded to 128 (PnH2: + the rows' inverse scales behind the planes)

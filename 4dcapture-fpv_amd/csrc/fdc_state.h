@@ -53,7 +53,7 @@ struct DevBuf {
 template <bool CONTACT>
 static int skin_bwd_any(DevBuf<float>& part, hipStream_t st, int nrows, SkinModel sm, int nc, const float* X, const float* Voff, const float* A,
                         const float* M, const float* scale, int row0, const float* dVw, float* dVoff, float* dA, float* dbeta_v,
-                        float* dtransl_v, float* dMv, float* dsv, ContactGradIn cg) {
+                        float* dtransl_v, float* dMv, float* dsv, ContactGradIn cg, int clip_n = 0) {
     // dT rows: 12 floats per vertex for the list form; the matrix form keeps them factored (SKB_ROW = 6 floats) and reuses the space for its
     // four waves' partial tiles (16 KB: more than 512 vertices of rows, which is when the matrix form is built)
     const size_t lds = sm.wf_tab ? std::max((size_t)std::min(nc, SKB_VCH) * SKB_ROW, (size_t)4 * 64 * 16) * sizeof(float)
@@ -61,7 +61,7 @@ static int skin_bwd_any(DevBuf<float>& part, hipStream_t st, int nrows, SkinMode
     if (nc <= SKB_VCH) {
         note_form("skin_bwd_kernel(one workgroup per frame)");
         hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, false>), dim3(nrows), dim3(256), lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
-                           dbeta_v, dtransl_v, dMv, dsv, cg, (float*)nullptr);
+                           dbeta_v, dtransl_v, dMv, dsv, cg, (float*)nullptr, clip_n);
         return (int)hipGetLastError();
     }
     const int nch = (nc + SKB_VCH - 1) / SKB_VCH;
@@ -69,7 +69,7 @@ static int skin_bwd_any(DevBuf<float>& part, hipStream_t st, int nrows, SkinMode
     if (e != hipSuccess) return (int)e;
     note_form(sm.wf_tab ? "skin_bwd_kernel(chunks, MFMA dA)" : "skin_bwd_kernel(chunks, list dA)");
     hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, true>), dim3(nrows, nch), dim3(256), lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
-                       dbeta_v, dtransl_v, dMv, dsv, cg, part.p);
+                       dbeta_v, dtransl_v, dMv, dsv, cg, part.p, clip_n);
     hipLaunchKernelGGL(skin_bwd_reduce_kernel, dim3(nrows), dim3(256), 0, st, part.p, nch, row0, dA, dbeta_v, dtransl_v, dMv, dsv,
                        CONTACT ? cg.loss_rows : (float*)nullptr);
     return (int)hipGetLastError();
@@ -108,8 +108,14 @@ struct SkinSet {          // skinning constants for a vertex set (all V, or the 
 };
 
 struct OptState {
-    fdcap_opt_config cfg;
+    fdcap_opt_config cfg;     // a batch of clips (fdcap_opt_create_clips): n_total = n_local = nclip * clip length, frame0 = 0
     int R = 0;            // rows = n_local + 4
+    // the clips this optimiser holds: nclip clips of clip_len frames each, clip k in rows 2 + k clip_len .. (one clip or one rank's
+    // share of one: nclip = 1, clip_len = n_total).  Each clip has its own scale / moments / dscale / losses slot.
+    int nclip = 1, clip_len = 0;
+    // what the kernels take as clip_n (clip_of_row, fdc_loss.h): 0 unless the optimiser holds several clips
+    int kclip_n() const { return nclip > 1 ? clip_len : 0; }
+    int rows_per_clip() const { return cfg.n_local / nclip; }
     bool contact_on = false;
     int nsplit = 8;           // scene splits of the in-loop NN launch
     int nsplit_bf = 8;        // ... of a brute-force launch (timing API)
@@ -591,9 +597,18 @@ int vposer_forward(fdcap_ctx* c, const float* X, int ldx, int latent_off, int ro
     return (int)hipGetLastError();
 }
 
+// The optimiser holds whole clips -- one clip, or a batch of them (fdcap_opt_create_clips) -- rather than one rank's share of a
+// sharded clip: no halo rows, no exchange, and the single-GPU schedule (deferred row step, `scale` stepped by the backward's tail).
+inline bool opt_whole_clips(const OptState* o) { return o->cfg.frame0 == 0 && o->cfg.n_local == o->cfg.n_total; }
+
+// a batch of several clips (fdcap_opt_create_clips): the entry points of modes 'local' / 'dct', the per-frame inner fit and the
+// sharded exchange refuse it (FDCAP_E_STATE)
+inline bool opt_is_batch(const fdcap_ctx* c) { return c && c->opt && c->opt->nclip > 1; }
+
 // rows of the optimiser's buffers whose pose is needed: the owned frames plus `halo` frames on each side that has a neighbour
 void opt_row_range(const OptState* o, int halo, int* lo, int* hi) {
     const fdcap_opt_config& cf = o->cfg;
+    if (opt_whole_clips(o)) { *lo = 2; *hi = cf.n_local + 2; return; }
     *lo = cf.frame0 > 0 ? 2 - halo : 2;
     *hi = cf.n_local + 2 + (cf.frame0 + cf.n_local < cf.n_total ? halo : 0);
 }
@@ -643,7 +658,7 @@ int opt_pose_forward(fdcap_ctx* c, int lo, int hi, hipStream_t st, bool contact_
     const int nl = o->cfg.n_local;
     DeferredStep ds;
     if (o->pend.on) {
-        if (lo == 2 && hi == 2 + nl && o->cfg.frame0 == 0 && nl == o->cfg.n_total && !o->log_pending) {
+        if (lo == 2 && hi == 2 + nl && opt_whole_clips(o) && !o->log_pending) {
             const StepPlan sp = opt_step_plan(o, o->pend.ii, o->pend.P, true, false);
             ds.on = 1; ds.x = sp.x; ds.cam = sp.cam; ds.row0 = 2;
             ds.dzpart = o->dz_pending ? o->dZpart.p : nullptr; ds.dz_stride = (size_t)o->R * VP_Z;
@@ -663,7 +678,7 @@ int opt_pose_forward(fdcap_ctx* c, int lo, int hi, hipStream_t st, bool contact_
                        (float*)nullptr,
 #endif
                        contact_state ? o->PF.p : (float*)nullptr, o->Jrest.p, o->G.p, contact_state ? o->A.p : (float*)nullptr, o->M.p, o->Jw.p,
-                       (const float*)nullptr, (const float*)o->Opart.p, ps, 0, 0, ds);
+                       (const float*)nullptr, (const float*)o->Opart.p, ps, 0, 0, ds, o->kclip_n());
     lt_mark(o, FDCAP_LT_POSE_FWD, st);
     if (ds.on) {                                            // the step has been issued: the launches that follow see its results
         o->pend.on = false;
@@ -695,15 +710,16 @@ int opt_vposer_backward(fdcap_ctx* c, bool fold, hipStream_t st, ScaleTail tail 
     const size_t ps = (size_t)o->R * VP_Z;
     const int nb = 4 * ((nl + 15) / 16);
     if (tail.block >= 0) tail.block = 0;                   // (first in the grid: fdc_panel.h)
-    if (gemm_split3_enabled() && tail.lg.rows && nb >= LROW) {
+    tail.nclip = o->nclip; tail.clip_n = o->rows_per_clip();      // (a batch: one tail workgroup per clip)
+    if (gemm_split3_enabled() && tail.lg.rows && nb >= LROW && o->nclip == 1) {
         tail.lg_spread = 1;                                // the logged sums: one regular workgroup per term (ScaleTail::lg_spread)
         if (tail.n <= 0) tail.block = -1;                  // ... and with no `scale` step there is nothing left for an extra workgroup
     }
     if (gemm_split3_enabled())
-        hipLaunchKernelGGL(vposer_bwd_split3_kernel, dim3(nb + (tail.block >= 0 ? 1 : 0)), dim3(512), 0, st, c->vp3, o->dO.p, 2, 2 + nl, o->H1.p, o->H2.p,
+        hipLaunchKernelGGL(vposer_bwd_split3_kernel, dim3(nb + (tail.block >= 0 ? tail.nclip : 0)), dim3(512), 0, st, c->vp3, o->dO.p, 2, 2 + nl, o->H1.p, o->H2.p,
                            o->dZpart.p, ps, tail);
     else
-        hipLaunchKernelGGL(vposer_bwd_fused_kernel, dim3(nb + (tail.block >= 0 ? 1 : 0)), dim3(512), 0, st, c->vp, o->dO.p, 2, 2 + nl, o->H1.p, o->H2.p,
+        hipLaunchKernelGGL(vposer_bwd_fused_kernel, dim3(nb + (tail.block >= 0 ? tail.nclip : 0)), dim3(512), 0, st, c->vp, o->dO.p, 2, 2 + nl, o->H1.p, o->H2.p,
                            o->dZpart.p, ps, tail);
     lt_mark(o, FDCAP_LT_VPOSER_BWD, st);
     if (fold) {

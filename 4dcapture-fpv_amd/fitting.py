@@ -92,6 +92,33 @@ def find_outliers(x78: np.ndarray):
     return idx1, pos
 
 
+def clip_inputs(x78: np.ndarray):
+    """init() :459-487 for one clip: x78 [N,78] fp32 (6D form) -> (idx1 outlier rows, init78 [N,78] = the data with every
+    outlier row replaced by its nearest inlier's, mask [N] = 0 on the outliers)."""
+    x78 = np.asarray(x78, dtype=np.float32)
+    idx1, pos = find_outliers(x78)
+    init78 = x78.copy()
+    if idx1.size and pos.size:
+        init78[idx1, :] = x78[pos, :]
+    mask = np.ones(x78.shape[0], np.float32)
+    mask[idx1] = 0.0
+    return idx1, init78, mask
+
+
+def logged_losses(s, n, nc, weight_loss_rec, weight_loss_vposer, weight_contact, phase2, local=False):
+    """One logged iteration of an n-frame clip: the un-normalised partial sums s (losses_d) -> the printed terms (:573-575,
+    :587-589) as (l_rec, l_vposer, loss_smoothing, loss_contact, loss_world_smoothing, total)."""
+    nc = max(nc, 1)
+    l_rec = weight_loss_rec * s[0] / (n * capi.XDIM)
+    l_vp = weight_loss_vposer * s[1] / (n * 32)
+    l_sm = s[2] / ((n - 2) * capi.XDIM) if n >= 3 else float("nan")
+    l_con = weight_contact * s[3] / (n * nc)
+    l_ws = s[4] / ((n - 1) * 69) if n >= 2 else float("nan")
+    total = (l_rec + (0.0 if local else PHASE2_WORLD * l_ws) + PHASE2_SMOOTH * l_sm) if phase2 else \
+        ((LOCAL_PHASE1_CONTACT if local else PHASE1_CONTACT) * l_con + PHASE1_SMOOTH * l_sm + l_rec)
+    return l_rec, l_vp, l_sm, l_con, l_ws, total
+
+
 @dataclass
 class FitLog:
     """Per-logged-iteration losses in the reference's print order (:573-575, :587-589)."""
@@ -251,12 +278,7 @@ class FittingOP:
         copy; returns idx1 like the reference and stages the optimiser's inputs."""
         import torch
         x78 = body_data_rotation.detach().cpu().numpy()
-        idx1, pos = find_outliers(x78)
-        init78 = x78.copy()
-        if idx1.size and pos.size:
-            init78[idx1, :] = x78[pos, :]
-        mask = np.ones(self.num_body, np.float32)
-        mask[idx1] = 0.0
+        idx1, init78, mask = clip_inputs(x78)
         if self._camera_ext_init is None or self._camera_ext_init.shape[0] != self.num_body:
             raise capi.FdcapError("camera_ext / camerapose.txt must have one pose per frame (:455)")
         sh = self.shard
@@ -825,15 +847,9 @@ class FittingOP:
 
     def _append_log(self, log, ii, phase2, s=None):
         s = self._losses.cpu().numpy() if s is None else s
-        N, nc = self.num_body, max(self.ctx.num_contact, 1)
-        l_rec = self.weight_loss_rec * s[0] / (N * capi.XDIM)
-        l_vp = self.weight_loss_vposer * s[1] / (N * 32)
-        l_sm = s[2] / ((N - 2) * capi.XDIM) if N >= 3 else float("nan")
-        l_con = self.weight_contact * s[3] / (N * nc)
-        l_ws = s[4] / ((N - 1) * 69) if N >= 2 else float("nan")
         local = getattr(self, "_mode", "global") == "local"
-        total = (l_rec + (0.0 if local else PHASE2_WORLD * l_ws) + PHASE2_SMOOTH * l_sm) if phase2 else \
-            ((LOCAL_PHASE1_CONTACT if local else PHASE1_CONTACT) * l_con + PHASE1_SMOOTH * l_sm + l_rec)
+        l_rec, l_vp, l_sm, l_con, l_ws, total = logged_losses(s, self.num_body, self.ctx.num_contact, self.weight_loss_rec,
+                                                              self.weight_loss_vposer, self.weight_contact, phase2, local)
         log.iters.append(ii); log.l_rec.append(l_rec); log.l_vposer.append(l_vp)
         log.loss_smoothing.append(l_sm); log.loss_contact.append(l_con)
         log.loss_world_smoothing.append(l_ws); log.total.append(total)
@@ -854,5 +870,162 @@ class FittingOP:
 
     def close(self):
         if getattr(self, "ctx", None) is not None:
+            self.ctx.close()
+            self.ctx = None
+
+
+class ClipBatchFitter:
+    """Several clips of one scene as ONE optimisation (fdcap_opt_create_clips): K clips of N frames each share the scene, the
+    contact ids, the body model, VPoser and the configuration; each keeps its own rows, `scale`, Adam moments, outlier set, loss
+    means and logged sums, and the temporal stencils are cut at clip boundaries.  A clip's result equals its stand-alone
+    FittingOP fit bit for bit whenever both select the same kernel forms (include/fdcap.h).
+
+    The fitter owns ONE context for its whole life -- the persistent worker: the body model and the contact ids are registered
+    once, a scene once per run of batches of that scene (`fit(..., scene_key=...)` skips the registration when the key is the
+    previous batch's).  Mode 'global' only."""
+
+    def __init__(self, fittingconfig, lossconfig, body_model=None, vposer=None, contact_ids=None, legacy_zero_grad=False):
+        import torch
+        cfg = dict(DEFAULT_FITTINGCONFIG)
+        cfg.update(fittingconfig or {})
+        lcfg = dict(DEFAULT_LOSSCONFIG)
+        lcfg.update(lossconfig or {})
+        for k, v in cfg.items():
+            setattr(self, k, v)
+        for k, v in lcfg.items():
+            setattr(self, k, v)
+        self.legacy_zero_grad = bool(legacy_zero_grad)
+        if not torch.cuda.is_available():
+            raise capi.FdcapError("no HIP device: the fdcap_amd optimiser only runs on the GPU")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        if body_model is None or vposer is None:
+            from . import assets
+            body_model = body_model or assets.load_smplx_npz(self.human_model_path)
+            vposer = vposer or assets.load_vposer_snapshot(self.vposer_ckpt_path)
+        self.ctx = capi.Context(body_model, vposer)
+        if contact_ids is None:
+            contact_ids = np.concatenate([io.read_contact_ids(self.contact_id_folder, [p]) for p in self.contact_part])
+        self.vid = np.asarray(contact_ids, dtype=np.int64)
+        self.ctx.set_contact_ids(self.vid)
+        self.scene_key = None
+        self._has_opt = False
+        self.logs = []
+        self.idx1 = []
+
+    def _destroy_opt(self):
+        if self._has_opt:
+            self.ctx.lib.fdcap_opt_destroy(self.ctx.handle)
+            self._has_opt = False
+
+    def set_scene(self, scene_verts, key=None):
+        """Register the scene of the following batches (after the optimiser of the previous batch is gone: the library refuses a
+        new scene while one exists).  `key` (e.g. the scene's path): nothing is done when it is the key of the registered scene."""
+        if key is not None and key == self.scene_key:
+            return
+        self._destroy_opt()
+        self.ctx.set_scene(np.zeros((0, 3), np.float32) if scene_verts is None else scene_verts)
+        self.scene_key = key
+
+    def fit(self, clips, scene_verts=None, scene_key=None, log_every=0):
+        """clips: sequence of K (body_data [N,75], camera_ext [N,4,4]) pairs (numpy or device tensors), one N for all.
+        scene_verts / scene_key: the batch's scene (see set_scene; both None: the registered scene).
+        Returns a list of K (body_rec [N,75] device tensor, scale numpy scalar, camera_ext [N,4,4] device tensor) -- what
+        FittingOP.fitting returns for each clip -- and leaves each clip's FitLog in self.logs, its outlier rows in self.idx1."""
+        if scene_verts is not None or scene_key is not None:
+            self.set_scene(scene_verts, scene_key)
+        self.prepare(clips)
+        return self.run(log_every)
+
+    def prepare(self, clips):
+        """init() of a batch (:450-489 per clip): creates the batch's optimiser on the registered scene and stages its inputs."""
+        import ctypes
+        import torch
+        K = len(clips)
+        if K < 1:
+            raise ValueError("a batch needs at least one clip")
+        dev = self.device
+        bodies, cams = [], []
+        for body, cam in clips:
+            b = body if torch.is_tensor(body) else torch.from_numpy(np.ascontiguousarray(body, dtype=np.float32))
+            bodies.append(b.to(dev, torch.float32))
+            c = cam.detach().cpu().numpy() if torch.is_tensor(cam) else np.asarray(cam)
+            cams.append(np.asarray(c, np.float32).reshape(-1, 16))
+        N = int(bodies[0].shape[0])
+        if any(int(b.shape[0]) != N for b in bodies) or any(c.shape[0] != N for c in cams):
+            raise capi.FdcapError("every clip of a batch has the same number of frames, and one camera pose per frame (:455)")
+        lib, h = self.ctx.lib, self.ctx.handle
+        st = capi.current_stream()
+        body = torch.cat(bodies).contiguous()
+        x78 = torch.empty(K * N, capi.XDIM, device=dev)
+        capi.check(lib.fdcap_params_75_to_78(capi.dptr(body), K * N, capi.dptr(x78), st), "fdcap_params_75_to_78")
+        # init() per clip (:459-487): outliers, their replacement rows and the mask of the data term, each clip on its own
+        x78_h = x78.cpu().numpy()
+        ins = [clip_inputs(x78_h[k * N:(k + 1) * N]) for k in range(K)]
+        self.idx1 = [i[0] for i in ins]
+        oc = capi.OptConfig(N, N, 0, float(self.init_lr_h), float(self.weight_loss_rec), float(self.weight_loss_vposer),
+                            float(self.weight_contact), PHASE1_CONTACT, PHASE1_SMOOTH, PHASE2_WORLD, PHASE2_SMOOTH, SCALE_INIT,
+                            int(self.legacy_zero_grad))
+        R = K * N + 4
+        self._rows_x = torch.zeros(R, capi.XDIM, device=dev)
+        self._rows_cam = torch.zeros(R, 16, device=dev)
+        self._scale = torch.zeros(K, device=dev)
+        self._dscale = torch.zeros(K, device=dev)
+        self._losses = torch.zeros(K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
+        torch.cuda.current_stream().synchronize()
+        capi.check(lib.fdcap_opt_create_clips(h, ctypes.byref(oc), K, capi.dptr(self._rows_x), capi.dptr(self._rows_cam),
+                                              capi.dptr(self._scale), capi.dptr(self._dscale), capi.dptr(self._losses)),
+                   "fdcap_opt_create_clips")
+        self._has_opt = True
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        d_init = t(np.concatenate([i[1] for i in ins]))
+        d_mask = t(np.concatenate([i[2] for i in ins]))
+        d_cam = t(np.concatenate(cams))
+        capi.check(lib.fdcap_opt_set_inputs(h, capi.dptr(x78), capi.dptr(d_init), capi.dptr(d_mask), capi.dptr(d_cam), st),
+                   "fdcap_opt_set_inputs")
+        self.num_clips, self.num_body = K, N
+
+    def run(self, log_every=0):
+        """The loop of the prepared batch (:558-593) and its results (see fit)."""
+        import ctypes
+        import os
+        import torch
+        K, N, dev = self.num_clips, self.num_body, self.device
+        lib, h = self.ctx.lib, self.ctx.handle
+        st = capi.current_stream()
+        # the loop in the library, as FittingOP.fitting runs a plain fit: one fdcap_opt_run for all iterations
+        num_iter = int(self.num_iter)
+        P = first_phase2_iter(num_iter)
+        logged = [ii for ii in range(num_iter) if is_logging_iteration(ii, num_iter, log_every)]
+        hist = torch.zeros(max(len(logged), 1), K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
+        defer = os.environ.get("FDCAP_DEFER_STEP", "1") != "0"
+        n_done = ctypes.c_int32(0)
+        try:
+            capi.check(lib.fdcap_opt_run(h, 0, num_iter, num_iter, P, int(log_every or 0), capi.dptr(hist) if logged else None,
+                                         len(logged), 0 if defer else 1, ctypes.byref(n_done), st), "fdcap_opt_run")
+        finally:
+            if logged:
+                capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
+        assert n_done.value == len(logged)
+        body_rec = torch.empty(K * N, capi.PDIM, device=dev)
+        scale = torch.empty(K, device=dev)
+        cam = torch.empty(K * N, 16, device=dev)
+        capi.check(lib.fdcap_opt_get_results(h, capi.dptr(body_rec), capi.dptr(scale), capi.dptr(cam), st), "fdcap_opt_get_results")
+        rows = hist.cpu().numpy()
+        self.logs = []
+        for k in range(K):
+            log = FitLog([], [], [], [], [], [], [])
+            for j, ii in enumerate(logged):
+                l_rec, l_vp, l_sm, l_con, l_ws, total = logged_losses(rows[j, k], N, self.ctx.num_contact, self.weight_loss_rec,
+                                                                      self.weight_loss_vposer, self.weight_contact, ii >= P)
+                log.iters.append(ii); log.l_rec.append(l_rec); log.l_vposer.append(l_vp)
+                log.loss_smoothing.append(l_sm); log.loss_contact.append(l_con)
+                log.loss_world_smoothing.append(l_ws); log.total.append(total)
+            self.logs.append(log)
+        sc = scale.cpu().numpy()
+        return [(body_rec[k * N:(k + 1) * N], sc[k], cam[k * N:(k + 1) * N].view(N, 4, 4)) for k in range(K)]
+
+    def close(self):
+        if getattr(self, "ctx", None) is not None:
+            self._destroy_opt()
             self.ctx.close()
             self.ctx = None

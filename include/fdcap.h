@@ -205,6 +205,27 @@ int fdcap_params_78_to_75(const float* x78_d, int32_t B, float* p75_d, void* str
  *              [4] sum|Jw_i-Jw_{i+1}| */
 int fdcap_opt_create(fdcap_ctx* ctx, const fdcap_opt_config* cfg, float* rows_x_d, float* rows_cam_d,
                      float* scale_d, float* dscale_d, double* losses_d);
+/* A BATCH of n_clips clips of N frames each, fitted as one optimisation (fdcap_opt_create is the n_clips = 1 case of this call).
+ * cfg: n_total == n_local == N (the clip length), frame0 == 0; the clips share the scene, the contact ids, the body model and
+ * cfg.  Every clip keeps its own rows, `scale`, Adam moments (of all three), outlier mask, loss means (over its own N frames)
+ * and logged sums; the temporal stencils are cut at clip boundaries, and all clips share the iteration counter.
+ *   rows_x_d   [n_clips*N+4,78]  clip k owns rows 2 + k*N .. 2 + (k+1)*N (fdcap_opt_set_inputs takes the n_clips*N rows)
+ *   rows_cam_d [n_clips*N+4,16]  same rows
+ *   scale_d    [n_clips]          set to cfg->scale_init each;  dscale_d [n_clips]: each clip's d loss / d scale
+ *   losses_d   [n_clips][FDCAP_NUM_LOSSES] double: each clip's partial sums
+ * A clip's results equal its stand-alone fit (fdcap_opt_create with n_total = n_local = N) bit for bit when both select the same
+ * kernel forms (chosen by row count: FDCAP_CLIP_FORMS_MIN_ROWS pins them); with the default forms only the rounding of the data
+ * gradient's sum may differ.  The batch takes the single-GPU schedule (deferred row step, `scale` stepped by the backward's tail).
+ * Calls that cover the optimiser's rows cover all n_clips*N of them (fdcap_opt_get_results, fdcap_opt_forward_world,
+ * fdcap_opt_get_contact, fdcap_opt_get_grads, launch timing); fdcap_opt_get_results writes n_clips scales; the state of
+ * fdcap_opt_export_state holds n_clips scale moments; fdcap_opt_run's history rows are [n_clips][FDCAP_NUM_LOSSES].  With
+ * n_clips > 1 these return FDCAP_E_STATE: mode 'local' (fdcap_opt_detect_contact, fdcap_opt_backward_local2), mode 'dct'
+ * (fdcap_opt_set_dct .. fdcap_opt_set_dct_state), the per-frame inner fit (fdcap_opt_set_keypoints, fdcap_opt_backward_fit2d,
+ * fdcap_opt_step_x, fdcap_opt_fit2d_lbfgs[_stats]), fdcap_opt_forward_ahead and the exchange calls (fdcap_opt_step_rows_and_pack,
+ * fdcap_opt_unpack_and_step_scale, fdcap_opt_halo_exchange, fdcap_opt_exchange, fdcap_opt_time_exchange, fdcap_opt_run with
+ * flags bit 1).  FDCAP_E_ARG: n_clips < 1, or n_clips > 1 with frame0 != 0 or n_local != n_total. */
+int fdcap_opt_create_clips(fdcap_ctx* ctx, const fdcap_opt_config* cfg, int32_t n_clips, float* rows_x_d, float* rows_cam_d,
+                           float* scale_d, float* dscale_d, double* losses_d);
 /* data78_d [n_local,78]: the 6D-converted SMPLify-X rows (loss_rec target);
  * init78_d [n_local,78]: initial value of body_rotation_rec (= data with outlier rows replaced, :487);
  * mask_d   [n_local]   : 0 for outlier rows (idx1), 1 otherwise (:255-257);
@@ -238,7 +259,8 @@ int fdcap_opt_sync(fdcap_ctx* ctx, void* stream);
  * above that FittingOP.fitting issues (fdcap_opt_backward_and_step; the fit's last iteration as fdcap_opt_backward + fdcap_opt_step;
  * on a sharded context, which must hold a communicator, fdcap_opt_backward + fdcap_opt_exchange), so the same bits.  Logging
  * iterations (log_every > 0: ii % log_every == 0, and ii == num_iter - 1; the reference prints every iteration) leave their partial
- * sums in consecutive rows of hist_d [hist_rows][FDCAP_NUM_LOSSES] on the device, *n_logged of them, with no host sync; the output
+ * sums in consecutive rows of hist_d [hist_rows][FDCAP_NUM_LOSSES] on the device ([hist_rows][n_clips][FDCAP_NUM_LOSSES] for a
+ * batch of clips, fdcap_opt_create_clips), *n_logged of them, with no host sync; the output
  * registered before the call is registered again after it.  flags bit 0: every optimiser step as its own launch; bit 1: the
  * exchange tail although the context holds the whole clip (a communicator of one rank).  Returns when the
  * work is enqueued.  A caller with something to do between iterations (snapshots, checkpoints, a finite check) calls it per stretch. */
@@ -246,14 +268,16 @@ int fdcap_opt_run(fdcap_ctx* ctx, int32_t ii0, int32_t ii1, int32_t num_iter, in
                   double* hist_d, int32_t hist_rows, int32_t flags, int32_t* n_logged, void* stream);
 /* Checkpoint / resume (the reference only ever writes its final result, :637-653).  The parameters live in the
  * caller's registered tensors; these move the rest of the optimiser state -- Adam's moments of the owned rows:
- * state_d [fdcap_opt_state_len()] floats = [m_x n_local*78 | v_x | m_cam n_local*16 | v_cam | m_scale | v_scale].
+ * state_d [fdcap_opt_state_len()] floats = [m_x n_local*78 | v_x | m_cam n_local*16 | v_cam | m_scale | v_scale]
+ * (a batch of K clips: n_local = K*N rows, and m_scale / v_scale hold K values each).
  * The step counters are functions of the iteration index the caller passes to fdcap_opt_step; seeds and kept work lists of
  * the Chamfer search are pruning state only (results never depend on them) and are not part of a checkpoint.  Mode 'dct''s
  * c_dct moments are not covered. */
 int32_t fdcap_opt_state_len(fdcap_ctx* ctx);
 int fdcap_opt_export_state(fdcap_ctx* ctx, float* state_d, void* stream);
 int fdcap_opt_import_state(fdcap_ctx* ctx, const float* state_d, void* stream);
-/* count_d [1] int32 <- number of non-finite values among the owned rows of body_rotation_rec / camera_ext and scale
+/* count_d [1] int32 <- number of non-finite values among the owned rows of body_rotation_rec / camera_ext and scale (every
+ * clip's, for a batch)
  * (the reference wraps every iteration in torch.autograd.set_detect_anomaly(True), :561, at ~4x the host cost; this is
  * the opt-in equivalent: FittingOP.fitting(check_finite_every=k)). */
 int fdcap_opt_check_finite(fdcap_ctx* ctx, int32_t* count_d, void* stream);
@@ -443,7 +467,8 @@ int fdcap_comm_allreduce_f64(fdcap_ctx* ctx, double* buf_d, int32_t n, void* str
  * what ran ahead. */
 int fdcap_opt_forward_ahead(fdcap_ctx* ctx, int32_t ii, int32_t first_phase2_iter, int32_t log_terms, void* stream);
 
-/* Results: body_rec75_d [n_local,75] (= convert_to_3D_rot, :633), scale_d [1], cam_ext_d [n_local,16]. */
+/* Results: body_rec75_d [n_local,75] (= convert_to_3D_rot, :633), scale_d [1], cam_ext_d [n_local,16].
+ * A batch of K clips: [K*N,75], [K] (clip k's scale at k), [K*N,16]. */
 int fdcap_opt_get_results(fdcap_ctx* ctx, float* body_rec75_d, float* scale_d, float* cam_ext_d,
                           void* stream);
 void fdcap_opt_destroy(fdcap_ctx* ctx);

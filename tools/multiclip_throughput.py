@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Throughput of a batch of clips (fitting.ClipBatchFitter, fdcap_opt_create_clips) on BASELINE config 3's body and scene
+(V = 10 475, 500 contact vertices, 500 k scene points) at the reference's clip length N = 300, 500 iterations:
+  - K in {1, 2, 3, 4, 6, 8} clips per batch: ms per batch (host clock around fits that end in a synchronise, after one warm-up
+    fit of that K), frames/s and clips/s;
+  - 12 clips through the batch driver (one context for all; default K) against 12 FittingOP fits in one process (a context
+    each), host clock from the first constructor to the last result on the host;
+  - the live per-launch table at K = 3 (fdcap_opt_launch_timing, as tools/launch_times.py reads it).
+Prints one JSON line (profiles/r7_multiclip300.json).
+usage: python tools/multiclip_throughput.py [--reps R] [--out FILE]"""
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+
+N, ITERS, NS, KS = 300, 500, 500_000, (1, 2, 3, 4, 6, 8)
+
+
+def main():
+    argv = sys.argv[1:]
+    reps, out = 3, None
+    while argv:
+        if argv[0] == "--reps":
+            reps, argv = int(argv[1]), argv[2:]
+        elif argv[0] == "--out":
+            out, argv = argv[1], argv[2:]
+        else:
+            raise SystemExit(__doc__)
+    import fdcap_amd  # noqa: F401
+    from fdcap_amd import cli, synth
+    from fdcap_amd.fitting import ClipBatchFitter, FittingOP
+    from fdcap_amd.io import read_camerapose
+    bm = synth.make_body_model(10475, seed=0)
+    vp = synth.make_vposer(seed=1)
+    scene = synth.make_scene(NS, seed=2)
+    left, right = synth.make_contact_ids(bm.v_template, per_part=250, seed=4)
+    vid = np.concatenate([left, right])
+    clips = []
+    for k in range(12):
+        c = synth.make_clip(N, seed=100 + k)
+        clips.append((c.body_params, read_camerapose(c.camerapose_lines)))
+    res = {"problem": {"verts": 10475, "contacts": len(vid), "scene": NS, "frames_per_clip": N, "iters": ITERS}, "sweep": []}
+
+    fitter = ClipBatchFitter({"num_iter": ITERS}, {}, body_model=bm, vposer=vp, contact_ids=vid)
+    fitter.set_scene(scene)
+
+    def fit(K):
+        r = fitter.fit(clips[:K])
+        return [(b.cpu(), s, c.cpu()) for b, s, c in r]
+
+    for K in KS:
+        fit(K)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fit(K)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / reps
+        res["sweep"].append({"K": K, "rows": K * N, "ms_per_batch": dt * 1e3, "frames_per_s": K * N / dt, "clips_per_s": K / dt})
+        print(f"K {K}: {dt * 1e3:8.2f} ms per batch  {K * N / dt:9.0f} frames/s  {K / dt:7.2f} clips/s", file=sys.stderr, flush=True)
+    by_k = {r["K"]: r for r in res["sweep"]}
+    res["speedup_k3_over_k1_frames_per_s"] = by_k[3]["frames_per_s"] / by_k[1]["frames_per_s"]
+
+    # the live per-launch table at K = 3 (the same fit, one event per launch boundary)
+    fit(3)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fit(3)
+    torch.cuda.synchronize()
+    live = bench.time_all_launches(fitter, lambda: fit(3), ITERS, time.perf_counter() - t0)
+    res["launch_table_k3"] = {ph: {k: round(v.get("us_corrected", v["us"]), 2) for k, v in live[ph].items()} for ph in ("phase1", "phase2")}
+    fitter.close()
+    torch.cuda.empty_cache()
+
+    # 12 clips: one persistent batch driver vs a FittingOP (context, scene, contact ids) per clip, both in this process
+    k_def = cli.batch_size(N)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    f = ClipBatchFitter({"num_iter": ITERS}, {}, body_model=bm, vposer=vp, contact_ids=vid)
+    f.set_scene(scene)
+    for j in range(0, 12, k_def):
+        [(b.cpu(), s, c.cpu()) for b, s, c in f.fit(clips[j:j + k_def])]
+    f.close()
+    torch.cuda.synchronize()
+    t_batch = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    for body, cam in clips:
+        fop = FittingOP({"num_iter": ITERS}, {}, N, body_model=bm, vposer=vp, scene_verts=scene, contact_ids=vid, camera_ext=cam)
+        b, s, c = fop.fitting(torch.tensor(body).cuda(), "global")
+        b.cpu(), c.cpu()
+        fop.close()
+    torch.cuda.synchronize()
+    t_single = time.perf_counter() - t0
+    res["twelve_clips"] = {"clips_per_batch": k_def, "batch_driver_s": t_batch, "fittingop_each_s": t_single,
+                           "batch_driver_frames_per_s": 12 * N / t_batch, "fittingop_each_frames_per_s": 12 * N / t_single,
+                           "note": "host clock from the first constructor to the last result on the host; model and scene arrays in memory"}
+    res["device"] = torch.cuda.get_device_name(0)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out:
+        with open(out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
