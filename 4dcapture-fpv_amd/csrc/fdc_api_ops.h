@@ -431,8 +431,7 @@ int fdcap_chamfer_fwd_scene(fdcap_ctx* c, const float* xyz1, int32_t B, int32_t 
     const int nsplit = nn_pick_nsplit(nq, (int)c->ns, true);
     HIP_TRY(c->ws_f[0].ensure((size_t)nsplit * nq));
     HIP_TRY(c->ws_i[0].ensure((size_t)nsplit * nq));
-    static std::atomic<float> slack{-1.f};
-    if (slack < 0.f) { const char* e = getenv("FDCAP_NN_CACHE_SLACK"); slack = e ? (float)atof(e) : 0.03f; }
+    static const float slack = forms_read_env().nn_cache_slack;      // (once per process, at the first call)
     const NNCache cache{slack > 0.f ? so.ids.p : nullptr, slack > 0.f ? so.hdr.p : nullptr, so.anchor.p, slack};
     bool pt_written = false;
     HIP_TRY(nn_search(xyz1, nq, T, so.dist.p, so.idx.p, c->ws_f[0].p, c->ws_i[0].p, nsplit, st, so.idx.p, fresh, so.seedpt.p, &pt_written,
@@ -482,7 +481,7 @@ int fdcap_vposer_decode_bwd(fdcap_ctx* c, const float* z, int32_t ldz, int32_t B
     const int n = B * 21;
     hipLaunchKernelGGL(vposer_out_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w[2].p, n, g_rot, g_aa, w[3].p);
     const size_t ps = (size_t)B * VP_Z;
-    if (gemm_split3_enabled())
+    if (plan_decoder(gemm_split3_enabled()) == F_VPOSER_SPLIT)
         hipLaunchKernelGGL(vposer_bwd_split3_kernel, dim3(4 * ((B + 15) / 16)), dim3(512), 0, st, c->vp3, w[3].p, 0, B, w[0].p, w[1].p, w[4].p, ps, ScaleTail());
     else
         hipLaunchKernelGGL(vposer_bwd_fused_kernel, dim3(4 * ((B + 15) / 16)), dim3(512), 0, st, c->vp, w[3].p, 0, B, w[0].p, w[1].p, w[4].p, ps, ScaleTail());

@@ -52,14 +52,9 @@ int fdcap_opt_create_clips(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     const int R = o->R = cfg->n_local + 4;
     o->contact_on = c->ns > 0 && c->nc > 0 && cfg->weight_contact != 0.f;
     const size_t nq = (size_t)R * std::max(c->nc, 1);
-    {
-        const char* e1 = getenv("FDCAP_NN_SEED");
-        const char* e2 = getenv("FDCAP_NN_CULL");
-        o->use_seed = !(e1 && e1[0] == '0');
-        o->use_cull = !(e2 && e2[0] == '0');
-    }
+    o->sw = forms_read_env();                               // (every create: tests flip the per-fit switches between fits in one process)
     const int nq_all = (int)((size_t)cfg->n_local * c->nc);
-    o->nsplit = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, o->use_seed && o->use_cull) : 1;
+    o->nsplit = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, o->sw.nn_seed && o->sw.nn_cull) : 1;
     o->nsplit_bf = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, false) : 1;
     int err = 0;
 #define AL(buf, cnt) if (!err) { hipError_t e_ = (buf).ensure(cnt); if (e_ != hipSuccess) err = (int)e_; else e_ = hipMemset((buf).p, 0, (size_t)(cnt) * sizeof(*(buf).p)); }
@@ -87,13 +82,9 @@ int fdcap_opt_create_clips(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
         if (e_ != hipSuccess) err = (int)e_;
     }
     if (!err && o->contact_on) {
-        if (const char* e = getenv("FDCAP_SKIN_VEC")) o->skin_vec = e[0] != '0';
-        if (const char* e = getenv("FDCAP_FUSE_SKIN")) o->fuse_skin = e[0] != '0';
-        if (const char* e = getenv("FDCAP_NN_CACHE_SLACK")) o->nnc_slack = (float)atof(e);
-        int every = 32;
-        if (const char* e = getenv("FDCAP_NN_ORDER")) every = atoi(e);
+        const int every = o->sw.nn_order;
         o->nn_order = NNOrder{};
-        if (o->nnc_slack > 0.f) {                                        // groups of 32 queries x up to 4 waves per group
+        if (o->sw.nn_cache_slack > 0.f) {                                        // groups of 32 queries x up to 4 waves per group
             const size_t ng = ((size_t)nq_all + 31) / 32, ng4 = ng * 4;
             hipError_t e_ = o->nnc_ids.ensure(ng4 * NN_CACHE_CAP);
             if (e_ == hipSuccess) e_ = o->nnc_hdr.ensure(ng4 + 3 * ng);                                        // + work counts [ng] + two launch-order tables [ng]
@@ -140,24 +131,25 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
     OptState* o = c->opt;
     const int nl = o->cfg.n_local, nc = c->nc;
     const size_t off = (size_t)2 * nc * 3;
-    // clip-sized shares: the blend product and the skinning in one launch (blend_skin_fwd_kernel; FDCAP_FUSE_SKIN=0: two launches)
+    // clip-sized shares: the blend product and the skinning in one launch, else two (plan_contact_forward, fdc_forms.h)
     const SkinModel smf = c->contact.model();
-    const bool fused = !blend_done && o->fuse_skin && gemm_split3_enabled() && c->contact.pn_fwdS.f && smf.vpack && smf.K <= 4 && nl >= clip_forms_min_rows() &&
-                       blend_skin_lds_bytes(smf.ja_hi) <= (size_t)150 * 1024;
-    if (fused) {
+    FormSwitches sw = proc_switches();
+    sw.fuse_skin = o->sw.fuse_skin; sw.gemm_split3 = gemm_split3_enabled();
+    const ContactFwdPlan pl = plan_contact_forward(nl, nc, NPFX, PNF, blend_done, c->contact.pn_fwdS.f != nullptr, smf.vpack != nullptr, smf.K, smf.ja_hi, sw);
+    if (pl.form == F_BLEND_SKIN_FWD) {
         static std::atomic<uint64_t> attr{0};                  // per DEVICE: the attribute belongs to one device's code object
         if (fdc_attr_needed(attr)) {
-            HIP_TRY(hipFuncSetAttribute((const void*)blend_skin_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+            HIP_TRY(hipFuncSetAttribute((const void*)blend_skin_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.max_lds));
             fdc_attr_done(attr);
         }
-        note_form("blend_skin_fwd_kernel");
-        hipLaunchKernelGGL(blend_skin_fwd_kernel, dim3(8 * ((nl + 31) / 32)), dim3(768), blend_skin_lds_bytes(smf.ja_hi), st, o->PF.p, nl,
+        note_form(form_name(pl.form));
+        hipLaunchKernelGGL(blend_skin_fwd_kernel, dim3(pl.grid), dim3(pl.block), pl.lds, st, o->PF.p, nl,
                            c->contact.pn_fwdS, smf, nc, smf.ja_hi, o->X.p, XDIM, X_TRANSL, o->A.p, o->M.p, o->scale.p, 2, o->Voff.p, o->Vw.p,
                            o->kclip_n());
     } else {
         if (!blend_done) HIP_TRY(blend_forward(c->contact, o->PF.p + 2 * NPFX, nl, o->Voff.p + off, st));
-        note_form("skin_fwd_kernel");
-        hipLaunchKernelGGL(skin_fwd_kernel, dim3((nc + 255) / 256, nl), dim3(256), 0, st, smf, nc, o->X.p, XDIM,
+        note_form(form_name(pl.form));
+        hipLaunchKernelGGL(skin_fwd_kernel, dim3(pl.grid, pl.grid_y), dim3(pl.block), 0, st, smf, nc, o->X.p, XDIM,
                            X_BETAS, X_TRANSL, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, 1, o->Vw.p, o->kclip_n());
     }
     lt_mark(o, FDCAP_LT_CONTACT_FWD, st);
@@ -168,8 +160,8 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
     if (timed) HIP_TRY(hipEventRecord(o->nn_ev[o->nn_ev_used], st));
     {
         TraceRange tr_("fdcap:chamfer_nn(K14)");
-        HIP_TRY(nn_search(o->Vw.p + off, nq, c->nn_target(o->use_cull), o->dist.p + 2 * nc, o->idx.p + 2 * nc, o->pd.p, o->pi.p,
-                          o->nsplit, st, o->use_seed ? o->idx.p + 2 * nc : nullptr, !o->seeded, o->seedpt.p + 2 * nc, &o->nnpt_valid,
+        HIP_TRY(nn_search(o->Vw.p + off, nq, c->nn_target(o->sw.nn_cull), o->dist.p + 2 * nc, o->idx.p + 2 * nc, o->pd.p, o->pi.p,
+                          o->nsplit, st, o->sw.nn_seed ? o->idx.p + 2 * nc : nullptr, !o->seeded, o->seedpt.p + 2 * nc, &o->nnpt_valid,
                           &cache, &o->nn_order));
     }
     if (timed) { HIP_TRY(hipEventRecord(o->nn_ev[o->nn_ev_used + 1], st)); o->nn_ev_used += 2; }
@@ -238,42 +230,33 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         cg.nnpt = o->nnpt_valid ? o->seedpt.p : nullptr;
         cg.coef = lw.contact * cf.weight_contact / ((float)N * nc);
         cg.loss_rows = losses ? o->loss_rows.p : nullptr;
-        const size_t lds_small = (size_t)6 * nc * sizeof(float) + (size_t)c->contact.nnz * sizeof(float) + (((size_t)c->contact.nnz * 2 + 15) & ~(size_t)15);
-        if (nc <= SKS_MAXV && c->contact.nnz <= SKS_MAXNNZ && lds_small <= 57000) {      // (+ 6.4 KB of static LDS <= 64 KB)
-            const int nnz = c->contact.nnz;
-            const size_t lds = lds_small;
-            dA_rows = c->contact.ja_hi;
-            const SkinModel smc = c->contact.model();
-            const int G = (smc.K + 3) / 4;                           // weight groups per vertex: the packed layout covers K <= 12
-            const size_t ldsv = (size_t)9 * nc * sizeof(float) + (size_t)((nnz + 3) & ~3) * sizeof(float) + (size_t)((nnz + 7) & ~7) * 2;
-            if (o->skin_vec && nc <= 512 && G <= 3 && nnz <= 2048 * G && ldsv <= 60000 && (nc & 3) == 0 && smc.vpack && smc.csc_v16 &&
-                (((size_t)o->Vw.p | (size_t)o->Voff.p | (size_t)o->dVoff.p | (size_t)o->A.p) & 15) == 0) {
-#define FDC_SKV(GG) hipLaunchKernelGGL(skin_bwd_vec_kernel<GG>, dim3(nl), dim3(256), ldsv, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, \
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn)
-                note_form("skin_bwd_vec_kernel");
-                if (G == 1) FDC_SKV(1); else if (G == 2) FDC_SKV(2); else FDC_SKV(3);
-#undef FDC_SKV
-            } else if (nc <= 512 && nnz <= 2048) {
-                note_form("skin_bwd_small_kernel");
-                hipLaunchKernelGGL((skin_bwd_small_kernel<2, 8>), dim3(nl), dim3(256), lds, st, c->contact.model(), nc, nnz, o->X.p, o->Voff.p, o->A.p,
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
-            } else if (nc <= 512) {                                   // (K > 4 at the loop's contact-set size: up to 6144 list entries)
-                note_form("skin_bwd_small_kernel(K > 4)");
-                hipLaunchKernelGGL((skin_bwd_small_kernel<2, 24>), dim3(nl), dim3(256), lds, st, c->contact.model(), nc, nnz, o->X.p, o->Voff.p, o->A.p,
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
-            } else if (nnz <= 4096) {
-                note_form("skin_bwd_small_kernel");
-                hipLaunchKernelGGL((skin_bwd_small_kernel<4, 16>), dim3(nl), dim3(256), lds, st, c->contact.model(), nc, nnz, o->X.p, o->Voff.p, o->A.p,
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
-            } else {
-                note_form("skin_bwd_small_kernel");
-                hipLaunchKernelGGL((skin_bwd_small_kernel<4, 24>), dim3(nl), dim3(256), lds, st, c->contact.model(), nc, nnz, o->X.p, o->Voff.p, o->A.p,
-                                   o->M.p, o->scale.p, 2, o->dVoff.p, o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
-            }
-        } else
-        { int es = skin_bwd_any<true>(c->ws_skin, st, nl, c->contact.model(), nc, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2,
-                                      (const float*)nullptr, o->dVoff.p, o->dA.p, (float*)nullptr, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
-          if (es) return es; }
+        const SkinModel smc = c->contact.model();
+        const int nnz = c->contact.nnz;
+        const bool aligned16 = (((size_t)o->Vw.p | (size_t)o->Voff.p | (size_t)o->dVoff.p | (size_t)o->A.p) & 15) == 0;
+        const SkinBwdPlan pl = plan_contact_skin_bwd(nl, nc, nnz, smc.K, smc.vpack != nullptr, smc.csc_v16 != nullptr, aligned16, smc.wf_tab != nullptr,
+                                                     o->sw.skin_vec);
+        if (pl.ja_rows) dA_rows = c->contact.ja_hi;
+        const dim3 grid(pl.grid), block(pl.block);
+#define FDC_SKC(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, pl.lds, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, o->dVoff.p, \
+                                           o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn)
+        switch (pl.form) {
+        case F_SKIN_BWD_VEC:
+            note_form(form_name(pl.form));
+            if (pl.G == 1) FDC_SKC(skin_bwd_vec_kernel<1>); else if (pl.G == 2) FDC_SKC(skin_bwd_vec_kernel<2>); else FDC_SKC(skin_bwd_vec_kernel<3>);
+            break;
+        case F_SKIN_BWD_SMALL: case F_SKIN_BWD_SMALL_K:
+            note_form(form_name(pl.form));
+            if (pl.vpt == 2 && pl.kc == 8) FDC_SKC((skin_bwd_small_kernel<2, 8>));
+            else if (pl.vpt == 2) FDC_SKC((skin_bwd_small_kernel<2, 24>));
+            else if (pl.kc == 16) FDC_SKC((skin_bwd_small_kernel<4, 16>));
+            else FDC_SKC((skin_bwd_small_kernel<4, 24>));
+            break;
+        default:
+            { int es = skin_bwd_any<true>(c->ws_skin, st, nl, smc, nc, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2,
+                                          (const float*)nullptr, o->dVoff.p, o->dA.p, (float*)nullptr, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
+              if (es) return es; }
+        }
+#undef FDC_SKC
         lt_mark(o, FDCAP_LT_SKIN_BWD, st);
         HIP_TRY(blend_backward(c->contact, o->dVoff.p + (size_t)2 * nc * 3, nl, o->dPF.p + 2 * NPFX, (size_t)o->R * NPFX, c->ws_kpart, st, &dpf_split));
         lt_mark(o, FDCAP_LT_BLEND_BWD, st);

@@ -355,8 +355,8 @@ int fdcap_panel_gemm(const float* A, int32_t lda, int32_t M, int32_t K, const fl
     if (!A || !B_h || !C || M <= 0 || K <= 0 || N <= 0 || lda < K || ldc < N) return FDCAP_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     {
-        const char* e3 = getenv("FDCAP_GEMM_SPLIT3");                // (read per call here, so a test can run both forms in one process)
-        if (!(e3 && e3[0] == '0') && panel_gemm3_fits(K)) {          // the split form of the same product on the 16-bit matrix cores (format PnF; the default)
+        // (the switch is read per call here, so a test can run both forms in one process)
+        if (forms_read_env().gemm_split3 && panel_gemm3_fits(PNF, K)) {          // the split form of the same product on the 16-bit matrix cores (format PnF; the default)
             std::vector<unsigned> p3;
             std::vector<float> sc;
             PanelB3 B3;
@@ -484,8 +484,8 @@ int fdcap_opt_time_chamfer(fdcap_ctx* c, int32_t iters, int32_t brute_force, flo
     const size_t off = (size_t)2 * nc * 3;
     // brute_force: every (query, scene point) pair is visited (no seed, no chunk bounds);
     // otherwise the launch is exactly what the loop issues in steady state
-    const int* seed = (!brute_force && o->use_seed) ? o->idx.p + 2 * nc : nullptr;
-    NNTarget T = c->nn_target(!brute_force && o->use_cull);
+    const int* seed = (!brute_force && o->sw.nn_seed) ? o->idx.p + 2 * nc : nullptr;
+    NNTarget T = c->nn_target(!brute_force && o->sw.nn_cull);
     if (brute_force) { T.pts = c->scene.p; T.inv_perm = nullptr; T.frags = nullptr; }   // input order (a spatial sort is adversarial for an unseeded running minimum)
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));

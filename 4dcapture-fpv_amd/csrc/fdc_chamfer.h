@@ -19,15 +19,13 @@
 
 #include <atomic>
 
+#include "fdc_forms.h"
 #include "fdc_math.h"
 
 namespace fdc {
 
 constexpr int NN_TILE = 1024;          // scene points per LDS tile of the plain scan
-#ifndef FDC_MF_CH
-#define FDC_MF_CH 512
-#endif
-constexpr int MF_CH = FDC_MF_CH;       // scene points per chunk of the MFMA scans = one k-d cell = culling granularity
+// (MF_CH, scene points per chunk of the MFMA scans, MF_MAXCHUNK and nn_split_len: fdc_forms.h)
 
 // scene as the NN kernels see it
 struct NNTarget {
@@ -53,10 +51,6 @@ __device__ __forceinline__ float nn_exact_d2(float qx, float qy, float qz, float
 __device__ __forceinline__ bool nn_better(float d, int i, float bd, int bi) {
     return d < bd || (d == bd && i < bi);
 }
-__host__ __device__ __forceinline__ int nn_split_len(int nt, int nsplit) {
-    int per = (nt + nsplit - 1) / nsplit;
-    return (per + MF_CH - 1) / MF_CH * MF_CH;             // chunk-aligned so bounds[] indexes uniformly
-}
 
 // Workgroup -> (query block, scene split).  Blocks are dealt to the 8 XCDs round-robin (b % 8), and
 // with chunk culling nearly all the work of a query block sits in the one or two splits that hold
@@ -67,7 +61,6 @@ __device__ __forceinline__ void nn_block_map(int b, int nsplit, int* qb, int* sp
     *split = slot % nsplit;
     *qb = (slot / nsplit) * 8 + xcd;
 }
-static inline int nn_grid_blocks(int qblocks, int nsplit) { return (qblocks + 7) / 8 * 8 * nsplit; }
 
 template <int QPT>
 __global__ __launch_bounds__(256) void nn_direct_kernel(const float* __restrict__ q, int nq, NNTarget T, int nsplit,
@@ -154,7 +147,6 @@ __global__ __launch_bounds__(256) void nn_direct_kernel(const float* __restrict_
 #define FDC_MF_K2 8e-6f
 #endif
 constexpr float MF_K1 = FDC_MF_K1, MF_K2 = FDC_MF_K2;
-constexpr int MF_MAXCHUNK = 2048;      // chunks per split the survivor list can hold (host keeps splits below it)
 
 #ifdef FDC_NN_TIMELINE
 __device__ unsigned long long g_nn_timeline[16384 * 8];            // instrumentation build only: per workgroup {start, end, xcc, after set-up, after list, after filter, after main loop, work items}
@@ -1329,26 +1321,6 @@ inline std::atomic<int>& nn_mode_ref() {
     static std::atomic<int> mode{0};
     return mode;
 }
-static inline bool nn_use_mfma(int nq, int nt) {
-    int mode = nn_mode_ref();
-    if (mode == 1) return false;
-    if (mode == 2) return true;
-    return (long long)nq * nt >= (1LL << 22);
-}
-
-static inline int nn_pick_nsplit(int nq, int nt, bool culled = false) {
-    // Each split re-reads the queries / seeds and writes its own partial minima, so fewer, longer
-    // splits win once there are enough query blocks to occupy 256 CUs x 3 resident workgroups.
-    // Measured on 1024 frames x 500 contacts vs 500k points: brute-force scan nsplit 2 (9.7 ms) beats
-    // 1 (11.1) and 8 (9.9); seeded + chunk-culled scan nsplit 1 (1.09 ms) beats 2 (1.23) and 4 (1.43).
-    int qblocks = culled ? (nq + 255) / 256 : (nq + 511) / 512;
-    int ns = 1;
-    const int target = culled ? 1536 : 1024;
-    while (qblocks * ns < target && ns < 64 && nt / (ns * 2) >= 4 * MF_CH) ns *= 2;
-    if (!culled && qblocks >= 512 && nt >= 8 * MF_CH) ns = max(ns, 2);
-    while (nn_split_len(nt, ns) / MF_CH > MF_MAXCHUNK) ns *= 2;
-    return ns;
-}
 
 // Launch order of nn_stream4_kernel's one-wave workgroups: position -> group, most work items first (counting sort on the
 // counts the last launch wrote; ties in no particular order -- the order decides when a group runs, never what it returns).
@@ -1404,53 +1376,25 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
                                    NNOrder* ord = nullptr) {
     if (seedpt_written) *seedpt_written = false;             // true: seedpt[q] = coordinates of the neighbour idx[q] after this launch
     if (nq <= 0) return hipSuccess;
-    // Query blocks per workgroup: 4 waves x NQ x 32.  A brute-force scan wants NQ = 4 (most MFMAs per
-    // staged chunk: 9.7 ms vs 10.9 at NQ = 2); a seeded + chunk-culled scan wants NQ = 2 (the union of
-    // the chunks 256 queries need is smaller than what 512 need, twice the workgroups: 0.92 ms vs
-    // 1.10 ms at NQ = 4, 1.09 ms at NQ = 1).
-    const bool culled = seed != nullptr && T.bounds != nullptr;
-    // FDCAP_NN_STREAM (tests: each form the size rule picks, forced): 0 the staged kernel; 11 / 21 / 41 nn_stream4_kernel with
-    // 1 / 2 / 4 waves per group of 32 queries; default: waves per group by launch size.  (Groups of 64 queries, two query blocks
-    // per wave, lost: 92.2 vs 78.2 ms per step.)  Measured (1024 / 512 / 256 / 128 frames x 500 queries): 11: 0.139 / 0.095 /
-    // 0.054 / 0.072 ms, 21: 0.140 / 0.087 / 0.049 / 0.047, 41: 0.153 / 0.086 / 0.047 / 0.036
-    static std::atomic<int> use_stream{-1};
-    if (use_stream < 0) { const char* e = getenv("FDCAP_NN_STREAM"); use_stream = e ? atoi(e) : -2; }
-    // (the streaming kernel's work list holds 16-bit ids 4 k + quarter: scenes up to 16384 chunks = 8.4 M points; beyond, the staged kernel)
-    if (culled && T.frags != nullptr && use_stream && nn_use_mfma(nq, T.n) && seedpt != nullptr && seed == idx &&
-        (T.n + MF_CH - 1) / MF_CH <= 16384) {
+    const NNPlan pl = plan_nn_search(nq, T.n, seed != nullptr && T.bounds != nullptr, T.frags != nullptr, seedpt != nullptr && seed == idx, nsplit,
+                                     nn_mode_ref(), proc_switches());
+    const dim3 grid(pl.grid), block(pl.block);
+    note_form(form_name(pl.form));
+    if (pl.wpg) {
         if (seed_missing)                                     // first launch of a fit: cheap seeds (+ their coordinates) instead of a full scan
             hipLaunchKernelGGL(nn_seed_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, q, nq, T, idx, seedpt);
         // seed aliases idx: every workgroup reads its seeds before it writes its own results, and no other workgroup touches them
         if (seedpt_written) *seedpt_written = true;
         {
-            int wpg;                                          // waves per group of 32 queries
-            if (use_stream < 0) {                             // enough waves to fill 1024 SIMDs x 4 twice over, no more (the
-                const int g32 = (nq + 31) / 32;               // per-group setup is repeated by every wave of the group)
-                // r6 sweep (tools/launch_times.py at 64 .. 224 frames x 500 queries, us per launch; waves per group 1 / 2 / 4):
-                //   2000 groups 25.8 / 23.7 / 22.7, 2500: 25.1 / 24.2 / 25.5, 3000: 25.8 / 26.8 / 28.7, 3500: 24.1 / 26.9 / 30.1
-                wpg = g32 >= 2816 ? 1 : g32 >= 2304 ? 2 : 4;  // (3072 / 4 until r6) re-measured with quarter work items: 128 / 256 / 512 / 768 frames: 11: 0.036 / 0.033 / 0.057 / 0.068 ms, 21: 0.028 / 0.034 / 0.059 / 0.074, 41: 0.024 / 0.036 / 0.063 / 0.084
-            } else {
-                wpg = (use_stream / 10 == 4) ? 4 : (use_stream / 10 == 2) ? 2 : 1;
-            }
-            // one-wave groups run as one-wave workgroups (a workgroup's slot is only handed on when its slowest wave is done)
-            const int groups = (nq + 31) / 32, wpb = wpg == 1 ? 1 : 4;
-            const int nwg = (groups * wpg + wpb - 1) / wpb;
-            const dim3 grid((nwg + 7) / 8 * 8);
+            const int groups = pl.groups, wpg = pl.wpg;
             NNCache nc = cache ? *cache : NNCache{nullptr, nullptr, nullptr, 0.f};
             const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && wpg == 1;
             nc.order_mode = !ordered ? 0 : (ord->sorted_groups == groups ? 2 + ord->cur : 1);
             const bool qorder = ordered && ord->qbuf != nullptr && ord->perm_mode != 1;
             nc.perm = qorder && ord->perm_n == nq ? ord->qbuf : nullptr;
-            if (wpg == 4) {
-                note_form("nn_stream4_kernel(4 waves per group)");
-                hipLaunchKernelGGL((nn_stream4_kernel<1, 4>), grid, dim3(256), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-            } else if (wpg == 2) {
-                note_form("nn_stream4_kernel(2 waves per group)");
-                hipLaunchKernelGGL((nn_stream4_kernel<1, 2>), grid, dim3(256), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-            } else {
-                note_form("nn_stream4_kernel<1,1,1>");
-                hipLaunchKernelGGL((nn_stream4_kernel<1, 1, 1>), grid, dim3(64), 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-            }
+            if (wpg == 4) hipLaunchKernelGGL((nn_stream4_kernel<1, 4>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
+            else if (wpg == 2) hipLaunchKernelGGL((nn_stream4_kernel<1, 2>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
+            else hipLaunchKernelGGL((nn_stream4_kernel<1, 1, 1>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
             const bool resort = ordered && (ord->sorted_groups != groups || ++ord->age >= ord->every);
             if (qorder && ord->perm_mode == 0 && (ord->perm_n != nq || seed_missing || (resort && ord->sorted_groups == groups))) {
                 // new groups: their kept lists go (hdr = -1, by the key kernel), the next launch records its work items in
@@ -1472,13 +1416,9 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
         }
         return hipGetLastError();
     }
-    note_form(nn_use_mfma(nq, T.n) ? "nn_mfma_kernel" : "nn_direct_kernel");
-    if (nn_use_mfma(nq, T.n) && culled)
-        hipLaunchKernelGGL((nn_mfma_kernel<2>), dim3(nn_grid_blocks((nq + 255) / 256, nsplit)), dim3(256), 0, st, q, nq, T, nsplit, seed, pd, pi);
-    else if (nn_use_mfma(nq, T.n))
-        hipLaunchKernelGGL((nn_mfma_kernel<4>), dim3(nn_grid_blocks((nq + 511) / 512, nsplit)), dim3(256), 0, st, q, nq, T, nsplit, seed, pd, pi);
-    else
-        hipLaunchKernelGGL((nn_direct_kernel<2>), dim3(nn_grid_blocks((nq + 511) / 512, nsplit)), dim3(256), 0, st, q, nq, T, nsplit, pd, pi);
+    if (pl.form == F_NN_MFMA && pl.nq_blocks == 2) hipLaunchKernelGGL((nn_mfma_kernel<2>), grid, block, 0, st, q, nq, T, nsplit, seed, pd, pi);
+    else if (pl.form == F_NN_MFMA) hipLaunchKernelGGL((nn_mfma_kernel<4>), grid, block, 0, st, q, nq, T, nsplit, seed, pd, pi);
+    else hipLaunchKernelGGL((nn_direct_kernel<2>), grid, block, 0, st, q, nq, T, nsplit, pd, pi);
     hipLaunchKernelGGL(nn_combine_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, pd, pi, nsplit, nq, dist, idx);
     return hipGetLastError();
 }

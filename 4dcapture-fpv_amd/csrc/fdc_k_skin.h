@@ -179,7 +179,7 @@ __global__ __launch_bounds__(768) void blend_skin_fwd_kernel(const float* __rest
         }
     }
 }
-static inline size_t blend_skin_lds_bytes(int ja) { return pnf_lds_bytes((NPFX + 31) & ~31, 2) + (size_t)(32 * ja * 12 + 32 * 12 + 32 * 4 + 2 * 64 * 4 + 3 * 32 * 64) * sizeof(float); }
+// (dynamic LDS of blend_skin_fwd_kernel: blend_skin_lds_bytes, fdc_forms.h)
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 
@@ -193,7 +193,7 @@ __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 // dependent gather scene[idx[q]].
 struct ContactGradIn { const float* Vw; const float* dist; const int* idx; const float4* scene; const float4* nnpt; float coef; float* loss_rows; };
 constexpr int SKB_NACC = NBETA + 3 + 12 + 1;   // dbeta, dtransl, dM, ds
-constexpr int SKB_VCH = 1024;                  // vertices per LDS chunk
+// (SKB_VCH, vertices per LDS chunk, and SKB_ROW: fdc_forms.h)
 constexpr int SKP_STRIDE = 688;                // floats of a (frame, chunk) partial of the split form: dA [660] | the SKB_NACC sums | contact term | pad
 static_assert(NJ * 12 + SKB_NACC + 1 <= SKP_STRIDE, "partial record");
 // SPLIT (r5; vertex sets of more than one chunk: the full mesh -- BASELINE config 5's contact set, mode 'local', the body-model
@@ -241,7 +241,6 @@ __device__ __forceinline__ SkinFwd skin_forward_vertex_packed(const float4 p0, c
 #ifndef FDC_SKB_PACKED
 #define FDC_SKB_PACKED 1
 #endif
-constexpr int SKB_ROW = 6;                             // floats per vertex of the factored dT rows (matrix-form dA): gv[3] | vp[3]
 template <bool CONTACT, bool SPLIT = false>
 __global__ __launch_bounds__(256, FDC_SKB_OCC) void skin_bwd_kernel(SkinModel sm, int nc, const float* __restrict__ X,
                                                        const float* __restrict__ Voff, const float* __restrict__ A,
@@ -535,7 +534,6 @@ __global__ __launch_bounds__(256) void skin_bwd_reduce_kernel(const float* __res
 // The dA sums run joint by joint over ascending vertices with the same wave-sum tree: run-to-run reproducible.
 // (VPT vertices and KC weight-list entries per thread in registers: 130 VGPRs for 4 / 16 cost a wave per SIMD -- the launch
 // then needs a second generation of workgroups; the loop's 500 vertices / 2000 weights take the 2 / 8 instance)
-constexpr int SKS_MAXV = 1024, SKS_MAXNNZ = 6144;
 template <int SKS_VPT, int SKS_KC>
 __global__ __launch_bounds__(256) void skin_bwd_small_kernel(SkinModel sm, int nc, int nnz, const float* __restrict__ X,
                                                              const float* __restrict__ Voff, const float* __restrict__ A,

@@ -29,6 +29,7 @@
 #include <atomic>
 #include <vector>
 
+#include "fdc_forms.h"
 #include "fdc_frame.h"
 #include "fdc_loss.h"
 
@@ -40,26 +41,6 @@ inline bool fdc_attr_needed(const std::atomic<uint64_t>& mask) { int d = 0; (voi
 inline void fdc_attr_done(std::atomic<uint64_t>& mask) { int d = 0; (void)hipGetDevice(&d); mask.fetch_or(1ull << (d & 63)); }
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// Row count from which the clip-sized kernel forms are selected (two row blocks per fragment stream in the blend products, the
-// fused contact forward): measured break-even 336 (r6 sweep: contact forward as two launches / fused 11.7 / 12.6 us at 320 rows,
-// 13.7 / 12.8 at 352; 384 until then).  FDCAP_CLIP_FORMS_MIN_ROWS overrides it -- tests run the reference's own
-// 300-frame fixtures (the reference hard-codes 300, :41-42) through the forms BASELINE configs 2 / 3 / 5 select.
-inline int clip_forms_min_rows() {
-    static std::atomic<int> v{-1};
-    if (v < 0) { const char* e = getenv("FDCAP_CLIP_FORMS_MIN_ROWS"); v = e ? std::max(32, atoi(e)) : 336; }
-    return v;
-}
-
-// ... and for the K-split data gradient (panel_gemm3_rb2k): from 257 rows.  r6 (tools/launch_times.py): the one-tile-stream form
-// (panel_gemm3_ksw) keeps one workgroup per CU, so from 17 row blocks x 16 column groups = 272 workgroups on it runs in two rounds --
-// 16.6 us at 272-352 rows against 9.7 at 256 -- while the two-row-block K-split form takes 10.7-11.0 us there: a 300-frame clip
-// (the reference's real clip length) 42.4 -> 40.0 ms per fit.  At 256 rows and below the one-round form wins (9.7 vs 11.2 us).
-inline int clip_kgrad_min_rows() {
-    static std::atomic<int> v{-1};
-    if (v < 0) { const char* e = getenv("FDCAP_CLIP_FORMS_MIN_ROWS"); v = e ? std::max(32, atoi(e)) : 257; }
-    return v;
-}
 
 // B operand in fragment order: f[(tile * nss + s) * 64 + lane] = { B(16 s + 4 (lane >> 4) + m, 16 tile + (lane & 15)) }, m = 0..3
 struct PanelB {
@@ -289,29 +270,7 @@ __device__ unsigned long long g_pn_times[8192 * 8];
 #define PN_STAMP(i)
 #endif
 
-// Workgroup -> (row block, column block), XCD-aware.  The dispatcher deals consecutive workgroups to the 8 XCDs round-robin
-// (b % 8), and each XCD has its own 4 MiB L2: with a plain 2-D grid every XCD pulls nearly all of A AND all of B through the
-// fabric in every launch (measured: 5.6 k cycles just to stage a 31 KB A block, fragment loads at Infinity-Cache latency).
-// Here XCD x owns the rectangle (row group x / xc, column group x % xc): its slice of the STATIC operand B stays resident in
-// its L2 from one optimiser iteration to the next, and A crosses the fabric xc times instead of 8.
-struct PnMap { int nrb, ncb, xc, rpg, cpg, rfast; };   // row / column blocks; column groups; blocks per group; slot order
-static inline PnMap panel_map(int nrb, int ncb, size_t a_bytes, size_t b_bytes) {
-    PnMap best{nrb, ncb, 1, (nrb + 7) / 8, ncb, 0};
-    double best_cost = 1e300;
-    for (int xc = 1; xc <= 8; xc *= 2) {
-        const int xr = 8 / xc;
-        const int rpg = (nrb + xr - 1) / xr, cpg = (ncb + xc - 1) / xc;
-        // fabric bytes per launch: A once per column group; B once per row group unless an XCD's slice is small enough to
-        // stay in its L2 between launches; + a penalty for idle slots of ragged groups
-        double cost = (double)xc * a_bytes + ((b_bytes / xc <= (size_t)(3u << 19)) ? 0.0 : (double)xr * b_bytes);
-        cost *= (double)(8 * rpg * cpg) / (double)(nrb * ncb);
-        if (cost < best_cost) { best_cost = cost; best = PnMap{nrb, ncb, xc, rpg, cpg, 0}; }
-    }
-    // an XCD's slice of B does not fit its L2 (wide outputs): walk the row blocks of one column block first, so the
-    // workgroups resident at any time share a few column blocks of B and each slice crosses the fabric once
-    best.rfast = b_bytes / best.xc > (size_t)(3u << 19);
-    return best;
-}
+// (workgroup -> (row block, column block), XCD-aware: PnMap / panel_map, fdc_forms.h)
 
 // C[M, N] = A[M, K] x B.  Workgroup = 8 waves = 16 RB rows x 128 columns (a 16-column tile per wave); K in slabs of `kslab`
 // columns (multiple of 16) so any K fits the LDS.  1-D grid of 8 * rpg * cpg workgroups (PnMap).
@@ -750,9 +709,10 @@ typedef PnB3 PnF;
 #endif
 __device__ __forceinline__ f32x4_t PnH2::tile_isc(const PanelB3& B, int tile, int g) { return ((const f32x4_t*)B.isc)[(size_t)min(tile, B.ntile - 1) * 4 + g]; }
 constexpr int PNF = PnF::NP;
-// uint4 per 16-row image of kpad columns; bytes of RB of them
-constexpr __host__ __device__ int pnf_img_u4(int kpad) { return PnF::NP * (kpad >> 3) * 16 + PnF::SC_U4; }
-constexpr __host__ __device__ size_t pnf_lds_bytes(int kpad, int rb) { return (size_t)rb * pnf_img_u4(kpad) * 16; }
+// uint4 per 16-row image of kpad columns; bytes of RB of them (fdc_forms.h, by plane count)
+static_assert(PnB3::SC_U4 == pn_sc_u4(PnB3::NP) && PnH2::SC_U4 == pn_sc_u4(PnH2::NP), "fdc_forms.h sizes the LDS images");
+constexpr __host__ __device__ int pnf_img_u4(int kpad) { return pn_img_u4(PNF, kpad); }
+constexpr __host__ __device__ size_t pnf_lds_bytes(int kpad, int rb) { return pn_lds_bytes(PNF, kpad, rb); }
 
 // acc += A[16 x 32 nst] * B (split operands, PnF::step per 32-column step).  sA3: image at the first step (plane stride
 // `pstride` uint4); bf: the tile's fragments at the first step (no lane offset).  Two register sets of PF steps x planes, loads
@@ -932,18 +892,10 @@ __global__ __launch_bounds__(512) void panel_gemm3_rb2k_kernel(const float* __re
         }
     }
 }
-// may the product take that form?  (the caller then provides the second partial buffer and adds the two)
-static inline bool panel_gemm3_rb2k_ok(int M, int K, const PanelB3& B) {
-    static std::atomic<int> rb2{-1};
-    if (rb2 < 0) { const char* e = getenv("FDCAP_PN_RB2"); rb2 = e ? atoi(e) : 1; }     // 0 off, 1 both forms, 2 forward only, 3 K-split only
-    const int nst_all = (K + 31) >> 5;
-    return (rb2 == 1 || rb2 == 3) && M >= clip_kgrad_min_rows() && B.ntile <= 32 && nst_all >= 2 && 32 * ((nst_all + 1) / 2) <= 768;
-}
-static inline hipError_t panel_gemm3_rb2k(const float* A, int lda, int M, int K, const PanelB3& B, float* Cpart, size_t part_stride,
+static inline hipError_t panel_gemm3_rb2k(const PanelPlan& pl, const float* A, int lda, int M, int K, const PanelB3& B, float* Cpart, size_t part_stride,
                                           int ldc, int N, hipStream_t st) {
-    const int kh = 32 * ((((K + 31) >> 5) + 1) / 2);
-    note_form("panel_gemm3_rb2k_kernel"); hipLaunchKernelGGL(panel_gemm3_rb2k_kernel, dim3(8 * ((M + 31) / 32)), dim3(512), pnf_lds_bytes(kh, 2), st, A, lda, M, K, B, Cpart,
-                       part_stride, ldc, N);
+    note_form(form_name(pl.form));
+    hipLaunchKernelGGL(panel_gemm3_rb2k_kernel, dim3(pl.grid), dim3(pl.block), pl.lds, st, A, lda, M, K, B, Cpart, part_stride, ldc, N);
     return hipGetLastError();
 }
 
@@ -994,47 +946,22 @@ __global__ __launch_bounds__(512) void panel_gemm3_wide_kernel(const float* __re
     }
 }
 
-// longest K whose single-slab LDS image (pnf_lds_bytes(kpad, 1)) fits the 160 KB of a gfx950 CU
-constexpr int PN3_MAX_K = FDC_PN_H2 ? 2528 : 1696;
-static_assert(pnf_lds_bytes(PN3_MAX_K, 1) <= 160 * 1024, "one image per CU");
-static inline bool panel_gemm3_fits(int K) { return ((K + 31) & ~31) <= PN3_MAX_K; }
-
+// executes a plan of plan_panel3 (fdc_forms.h): all of K in one LDS image
 static inline hipError_t panel_gemm3(const float* A, int lda, int M, int K, const PanelB3& B, float* C, int ldc, int N, hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
-    const int kpad = (K + 31) & ~31;
-    if (kpad > PN3_MAX_K) return hipErrorInvalidValue;       // callers fall back to panel_gemm (K slabs) above this
-    if ((size_t)B.ntile * B.nst * PNF * 1024 > (size_t)(16u << 20) && M >= 32 && kpad <= 768) {
-        // one workgroup per CU (the 98 KB image leaves room for one): as many column parts as it takes to reach 256 workgroups
-        const int nrb = (M + 31) / 32, ncb = (B.ntile + 7) / 8, cpg = (ncb + 7) / 8;
-        // (r2-r4 ran one column part.  r5: two column tiles per wave, as in the K-loop product, measured no faster here: 0.186 vs
-        //  0.179 ms at 1024 rows, equal at 512.  r6: 64 rows per workgroup -- half the fragment bytes per MFMA -- took 70 us instead
-        //  of 90 at 512 rows, yet made the config-5 fit 5 % slower: that configuration runs at the chip's power limit.)
-        const int cs = std::max(1, std::min(cpg, (256 + 8 * nrb - 1) / (8 * nrb)));
-        note_form("panel_gemm3_wide_kernel"); hipLaunchKernelGGL(panel_gemm3_wide_kernel<2>, dim3(8 * nrb * cs), dim3(512), pnf_lds_bytes(kpad, 2), st, A, lda, M, K, B, C, ldc, N, cs);
-        return hipGetLastError();
+    const PanelPlan pl = plan_panel3(M, K, B.ntile, B.nst, PNF, proc_switches());
+    const dim3 grid(pl.grid), block(pl.block);
+    if (pl.form != F_NONE) note_form(form_name(pl.form));
+    switch (pl.form) {
+    case F_PANEL3_WIDE: hipLaunchKernelGGL(panel_gemm3_wide_kernel<2>, grid, block, pl.lds, st, A, lda, M, K, B, C, ldc, N, pl.cs); break;
+    case F_PANEL3_RB2: hipLaunchKernelGGL(panel_gemm3_rb2_kernel, grid, block, pl.lds, st, A, lda, M, K, B, C, ldc, N); break;
+    case F_PANEL3:
+        if (pl.nw == 8) hipLaunchKernelGGL(panel_gemm3_kernel<8>, grid, block, pl.lds, st, A, lda, M, K, B, C, ldc, N, pl.mp);
+        else if (pl.nw == 4) hipLaunchKernelGGL(panel_gemm3_kernel<4>, grid, block, pl.lds, st, A, lda, M, K, B, C, ldc, N, pl.mp);
+        else hipLaunchKernelGGL(panel_gemm3_kernel<2>, grid, block, pl.lds, st, A, lda, M, K, B, C, ldc, N, pl.mp);
+        break;
+    default: return hipErrorInvalidValue;                  // K beyond one image: callers fall back to panel_gemm (K slabs)
     }
-    static std::atomic<int> rb2{-1};                                  // FDCAP_PN_RB2=0 (A/B): one row block per fragment stream everywhere
-    if (rb2 < 0) { const char* e = getenv("FDCAP_PN_RB2"); rb2 = e ? atoi(e) : 1; }
-    if ((rb2 == 1 || rb2 == 2) && M >= clip_forms_min_rows() && kpad <= 768 && B.ntile >= 48) {   // (measured: 256 rows 50.2 vs 49.8 ms per step, 384 rows 56.7 vs 57.8)
-        // (r5: six waves x two tiles over the same 32 x 192 block -- half the LDS bytes per MFMA, the lever that took the K-loop
-        //  product from 192 to 139 us -- is SLOWER here: 14.4 vs 12.8 us; with K = 512 the twelve waves' latency hiding is worth more)
-        note_form("panel_gemm3_rb2_kernel"); hipLaunchKernelGGL(panel_gemm3_rb2_kernel, dim3(8 * ((M + 31) / 32)), dim3(768), pnf_lds_bytes(kpad, 2), st, A, lda, M, K, B, C, ldc, N);
-        return hipGetLastError();
-    }
-    // waves per workgroup: eight while that gives >= 192 workgroups, else four, else two (FDCAP_PN_NW pins it: A/B)
-    static std::atomic<int> nw_env{-1};
-    if (nw_env < 0) { const char* e = getenv("FDCAP_PN_NW"); nw_env = e ? atoi(e) : 0; }
-    const int nrb = (M + 15) / 16;
-    int nw = 8;                                            // (measured at 128 rows: forward 7.8 -> 6.6 us with four waves; two waves stage too slowly)
-    if (nrb * ((B.ntile + 7) / 8) < 128 && nrb * ((B.ntile + 3) / 4) >= 128) nw = 4;
-    if (nw_env == 8 || nw_env == 4 || nw_env == 2) nw = nw_env;
-    const PnMap mp = panel_map(nrb, (B.ntile + nw - 1) / nw, (size_t)M * K * 4, (size_t)B.ntile * B.nst * PNF * 1024);
-    const dim3 grid(8 * mp.rpg * mp.cpg);
-    const size_t lds = pnf_lds_bytes(kpad, 1);
-    note_form("panel_gemm3_kernel");
-    if (nw == 8) hipLaunchKernelGGL(panel_gemm3_kernel<8>, grid, dim3(512), lds, st, A, lda, M, K, B, C, ldc, N, mp);
-    else if (nw == 4) hipLaunchKernelGGL(panel_gemm3_kernel<4>, grid, dim3(256), lds, st, A, lda, M, K, B, C, ldc, N, mp);
-    else hipLaunchKernelGGL(panel_gemm3_kernel<2>, grid, dim3(128), lds, st, A, lda, M, K, B, C, ldc, N, mp);
     return hipGetLastError();
 }
 
@@ -1334,34 +1261,20 @@ __global__ __launch_bounds__(512) void panel_gemm3_ksw_kernel(const float* __res
         }
     }
 }
-// when the form pays: a long K in one LDS image, few row blocks (FDCAP_PN_KSW=0: never)
-static inline bool panel_gemm3_ksw_ok(int M, int K, const PanelB3& B) {
-    static std::atomic<int> on{-1};
-    if (on < 0) { const char* e = getenv("FDCAP_PN_KSW"); on = (e && e[0] == '0') ? 0 : 1; }
-    const int kpad = (K + 31) & ~31;
-    return on && kpad <= PN3_MAX_K && kpad >= 768 && ((M + 15) / 16) * ((B.ntile + 7) / 8) < 128;
-}
-static inline hipError_t panel_gemm3_ksw(const float* A, int lda, int M, int K, const PanelB3& B, float* C, int ldc, int N, hipStream_t st) {
+static inline hipError_t panel_gemm3_ksw(const PanelPlan& pl, const float* A, int lda, int M, int K, const PanelB3& B, float* C, int ldc, int N, hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
-    const int kpad = (K + 31) & ~31;
     static std::atomic<uint64_t> attr{0};                      // per DEVICE: the attribute belongs to one device's code object
     if (fdc_attr_needed(attr)) {
-        hipError_t e = hipFuncSetAttribute((const void*)panel_gemm3_ksw_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pnf_lds_bytes(PN3_MAX_K, 1));
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)panel_gemm3_ksw_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pnf_lds_bytes(PN3_MAX_K, 1));
+        hipError_t e = hipFuncSetAttribute((const void*)panel_gemm3_ksw_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.max_lds);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)panel_gemm3_ksw_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.max_lds);
         if (e != hipSuccess) return e;
         fdc_attr_done(attr);
     }
-    // column tiles per workgroup: two while that still gives >= 192 workgroups, else one -- r6: and two whenever one tile per
-    // workgroup would mean more workgroups than CUs (one workgroup fits a CU: 129-176 rows ran in two rounds, 14.7 us at 160 rows
-    // against 8.8 at 128 and 9.5 at 192: tools/launch_times.py sweep)
-    const int nrb = (M + 15) / 16;
-    const int T = (nrb * ((B.ntile + 1) / 2) >= 192 || nrb * B.ntile > 256) ? 2 : 1;
-    const PnMap mp = panel_map(nrb, (B.ntile + T - 1) / T, (size_t)M * K * 4, (size_t)B.ntile * B.nst * PNF * 1024);
-    note_form("panel_gemm3_ksw_kernel");
-    if (T == 2)
-        hipLaunchKernelGGL(panel_gemm3_ksw_kernel<2>, dim3(8 * mp.rpg * mp.cpg), dim3(512), pnf_lds_bytes(kpad, 1), st, A, lda, M, K, B, C, ldc, N, mp);
+    note_form(form_name(pl.form));
+    if (pl.T == 2)
+        hipLaunchKernelGGL(panel_gemm3_ksw_kernel<2>, dim3(pl.grid), dim3(pl.block), pl.lds, st, A, lda, M, K, B, C, ldc, N, pl.mp);
     else
-        hipLaunchKernelGGL(panel_gemm3_ksw_kernel<1>, dim3(8 * mp.rpg * mp.cpg), dim3(512), pnf_lds_bytes(kpad, 1), st, A, lda, M, K, B, C, ldc, N, mp);
+        hipLaunchKernelGGL(panel_gemm3_ksw_kernel<1>, dim3(pl.grid), dim3(pl.block), pl.lds, st, A, lda, M, K, B, C, ldc, N, pl.mp);
     return hipGetLastError();
 }
 
@@ -1443,41 +1356,21 @@ __global__ void panel_part_sum_kernel(const float* __restrict__ part, int ks, si
     for (int p = 1; p < ks; ++p) s += part[(size_t)p * part_stride + i];
     out[i] = s;
 }
-constexpr int PN3_KLOOP_SLAB = 24;                               // steps (32 columns each) per slab: two 16-row images of 768 columns = 144 KB
-// 16-row blocks per fragment stream and column tiles per wave (measured at 512 / 128 rows: RB 4 T 1 192 / 55 us, RB 2 T 2 139 / 44,
-// RB 4 T 2 166 / 57 with 55 spilled registers)
-constexpr int PN3_KLOOP_RB = 2, PN3_KLOOP_T = 2;
-// parts of K for M rows and B's tiles: enough workgroups for 256 CUs, ks x column blocks a multiple of 8 (XCD <-> slice of B), <= 32
-static inline int panel_gemm3_kloop_parts(int M, const PanelB3& B) {
-    constexpr int rb = PN3_KLOOP_RB, T = PN3_KLOOP_T, wgs = 256;
-    const int ncb = (B.ntile + 8 * T - 1) / (8 * T), nrp = (M + 16 * rb - 1) / (16 * rb);
-    // r6: the LARGEST admissible part count that still fits one round of workgroups (a workgroup fills a CU's LDS: one per CU).  The
-    // count used to be rounded UP to the next admissible one -- 288-336 workgroups at 96 / 192 / 320 / 384 / 448 rows, two rounds:
-    // 141.8 us at 384 rows against 113.9 at 512 (tools/launch_times.py --config c5 sweep).
-    int ks = std::min(64, std::max(1, wgs / (ncb * nrp)));
-    while (ks > 1 && (ks * ncb) % 8 != 0) --ks;
-    if ((ks * ncb) % 8 != 0) { ks = 1; while ((ks * ncb) % 8 != 0 && ks < 64) ++ks; }       // (nothing admissible below: the smallest above)
-    return std::min(ks, 64);
-}
-// C [M rows of ldc] = sum of the parts; `part` must hold ks x M x ldc floats (panel_gemm3_kloop_parts)
-static inline hipError_t panel_gemm3_kloop(const float* A, int lda, int M, int K, const PanelB3& B, float* part, float* C, int ldc, int N,
+// C [M rows of ldc] = sum of the parts; `part` must hold pl.ks x M x ldc floats
+static inline hipError_t panel_gemm3_kloop(const PanelPlan& pl, const float* A, int lda, int M, int K, const PanelB3& B, float* part, float* C, int ldc, int N,
                                            hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
     constexpr int rb = PN3_KLOOP_RB, T = PN3_KLOOP_T;
-    const int ks = panel_gemm3_kloop_parts(M, B), ncb = (B.ntile + 8 * T - 1) / (8 * T), nrp = (M + 16 * rb - 1) / (16 * rb);
     const size_t stride = (size_t)M * ldc;
-    // steps per slab: RB images of 32 x slab columns, 6 bytes each, in <= 147 KB
-    constexpr int slab = PN3_KLOOP_SLAB;
-    const size_t lds = pnf_lds_bytes(32 * slab, rb);
     static std::atomic<uint64_t> attr{0};                      // per DEVICE: the attribute belongs to one device's code object
     if (fdc_attr_needed(attr)) {
-        hipError_t e = hipFuncSetAttribute((const void*)panel_gemm3_kloop_kernel<rb, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)panel_gemm3_kloop_kernel<rb, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.max_lds);
         if (e != hipSuccess) return e;
         fdc_attr_done(attr);
     }
-    hipLaunchKernelGGL((panel_gemm3_kloop_kernel<rb, T>), dim3(ks * ncb * nrp), dim3(512), lds, st, A, lda, M, K, B, part, stride, ldc, N, ks, slab);
-    note_form("panel_gemm3_kloop_kernel");
-    hipLaunchKernelGGL(panel_part_sum_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, st, part, ks, stride, stride, C);
+    hipLaunchKernelGGL((panel_gemm3_kloop_kernel<rb, T>), dim3(pl.grid), dim3(pl.block), pl.lds, st, A, lda, M, K, B, part, stride, ldc, N, pl.ks, PN3_KLOOP_SLAB);
+    note_form(form_name(pl.form));
+    hipLaunchKernelGGL(panel_part_sum_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, st, part, pl.ks, stride, stride, C);
     return hipGetLastError();
 }
 

@@ -54,23 +54,18 @@ template <bool CONTACT>
 static int skin_bwd_any(DevBuf<float>& part, hipStream_t st, int nrows, SkinModel sm, int nc, const float* X, const float* Voff, const float* A,
                         const float* M, const float* scale, int row0, const float* dVw, float* dVoff, float* dA, float* dbeta_v,
                         float* dtransl_v, float* dMv, float* dsv, ContactGradIn cg, int clip_n = 0) {
-    // dT rows: 12 floats per vertex for the list form; the matrix form keeps them factored (SKB_ROW = 6 floats) and reuses the space for its
-    // four waves' partial tiles (16 KB: more than 512 vertices of rows, which is when the matrix form is built)
-    const size_t lds = sm.wf_tab ? std::max((size_t)std::min(nc, SKB_VCH) * SKB_ROW, (size_t)4 * 64 * 16) * sizeof(float)
-                                 : (size_t)std::min(nc, SKB_VCH) * 12 * sizeof(float);
-    if (nc <= SKB_VCH) {
-        note_form("skin_bwd_kernel(one workgroup per frame)");
-        hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, false>), dim3(nrows), dim3(256), lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
+    const SkinBwdPlan pl = plan_skin_bwd_any(nrows, nc, sm.wf_tab != nullptr);
+    note_form(form_name(pl.form));
+    if (pl.form == F_SKIN_BWD_FRAME) {
+        hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, false>), dim3(pl.grid), dim3(pl.block), pl.lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
                            dbeta_v, dtransl_v, dMv, dsv, cg, (float*)nullptr, clip_n);
         return (int)hipGetLastError();
     }
-    const int nch = (nc + SKB_VCH - 1) / SKB_VCH;
-    hipError_t e = part.ensure((size_t)nrows * nch * SKP_STRIDE);
+    hipError_t e = part.ensure((size_t)nrows * pl.nch * SKP_STRIDE);
     if (e != hipSuccess) return (int)e;
-    note_form(sm.wf_tab ? "skin_bwd_kernel(chunks, MFMA dA)" : "skin_bwd_kernel(chunks, list dA)");
-    hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, true>), dim3(nrows, nch), dim3(256), lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
+    hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, true>), dim3(pl.grid, pl.nch), dim3(pl.block), pl.lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
                        dbeta_v, dtransl_v, dMv, dsv, cg, part.p, clip_n);
-    hipLaunchKernelGGL(skin_bwd_reduce_kernel, dim3(nrows), dim3(256), 0, st, part.p, nch, row0, dA, dbeta_v, dtransl_v, dMv, dsv,
+    hipLaunchKernelGGL(skin_bwd_reduce_kernel, dim3(nrows), dim3(256), 0, st, part.p, pl.nch, row0, dA, dbeta_v, dtransl_v, dMv, dsv,
                        CONTACT ? cg.loss_rows : (float*)nullptr);
     return (int)hipGetLastError();
 }
@@ -137,8 +132,8 @@ struct OptState {
     fdcap_lbfgs* lbfgs = nullptr;
     DevBuf<float4> seedpt;    // coordinates (+ position in the sorted scene) of each query's current neighbour: next launch's seed
     // work-list cache of the in-loop NN launch (fdc_chamfer.h NNCache): ids [groups * 4][64], hdr [groups * 4], anchors [4][nq]
-    bool skin_vec = true;          // FDCAP_SKIN_VEC=0 (read by fdcap_opt_create; A/B): the scalar-load skinning backward
-    bool fuse_skin = true;         // FDCAP_FUSE_SKIN=0 (read by fdcap_opt_create; A/B): blend product and skinning forward as two launches
+    FormSwitches sw;               // the switches as fdcap_opt_create[_clips] read them (fdc_forms.h): nn_seed, nn_cull, skin_vec, fuse_skin,
+                                   // nn_cache_slack, nn_order hold for this optimiser; the others are per process (proc_switches())
     DevBuf<float> loss_rows;       // [R][LROW] per-frame partial sums of the printed loss terms (logging iterations)
     bool log_pending = false;      // a logging backward (log_terms = 2) left the reduction of loss_rows to the next step launch
     unsigned log_mask = 0;
@@ -149,7 +144,6 @@ struct OptState {
     DevBuf<float4> nnc_anchor;
     DevBuf<int> nnq_buf;                   // the in-loop NN launch's query order + its sort scratch (fdc_chamfer.h NNOrder::qbuf)
     NNOrder nn_order;                      // launch order of the in-loop NN launch (fdc_chamfer.h NNOrder; its tables sit behind nnc_hdr); FDCAP_NN_ORDER=0 turns it off, =k re-sorts every k launches
-    float nnc_slack = 0.03f;  // metres; FDCAP_NN_CACHE_SLACK overrides, 0 disables the cache
     // fdcap_opt_launch_timing (r6): a HIP event on the launch stream at every boundary between two launches of an iteration; the time
     // from one event to the next is booked on the launch in between (its ~1 us dependent-launch gap included), per phase of the fit
     struct LaunchTimes {
@@ -162,7 +156,7 @@ struct OptState {
     bool nn_timing = false;
     std::vector<hipEvent_t> nn_ev;
     int nn_ev_used = 0;
-    NNCache nn_cache(int) { return NNCache{nnc_slack > 0.f ? nnc_ids.p : nullptr, nnc_slack > 0.f ? nnc_hdr.p : nullptr, nnc_anchor.p, nnc_slack}; }
+    NNCache nn_cache(int) { return NNCache{sw.nn_cache_slack > 0.f ? nnc_ids.p : nullptr, sw.nn_cache_slack > 0.f ? nnc_hdr.p : nullptr, nnc_anchor.p, sw.nn_cache_slack}; }
     DevBuf<float> dA, dtransl_v, dMv, dsv, dPF, dJw, dX, dCAM, dscale_row;     // d betas: columns 486.. of dPF
     DevBuf<float> VoffF, VwF, dVF;      // mode 'local' second loop: full-mesh pose offsets / world vertices / gradient
     int cam_steps = 0;
@@ -177,8 +171,6 @@ struct OptState {
     // rows and the scale-dependent outputs (ahead_blend: the contact set's pose-blend product is done as well)
     bool ahead = false, ahead_blend = false;
     bool nnpt_valid = false;  // the last contact forward left the neighbours' coordinates in seedpt
-    bool use_seed = true;     // last iteration's neighbours seed the NN bound (pruning only)
-    bool use_cull = true;     // skip k-d cells whose box is out of every query's reach
 };
 
 // (fdcap_opt_launch_timing) the stage `what` ended here; -1: an iteration begins
@@ -530,9 +522,8 @@ int build_skin_set(fdcap_ctx* c, const std::vector<int64_t>& ids, SkinSet* out) 
 
 // dense products on the split formats of fdc_panel.h (FDCAP_GEMM_SPLIT3=0: exact-fp32 MFMA chains instead)
 inline bool gemm_split3_enabled() {
-    static std::atomic<int> v{-1};
-    if (v < 0) { const char* e = getenv("FDCAP_GEMM_SPLIT3"); v = (e && e[0] == '0') ? 0 : 1; }
-    return v == 1;
+    static const bool on = forms_read_env().gemm_split3;       // (once per process, at the first product)
+    return on;
 }
 // pose + shape blend offsets of a vertex set: Voff[M, 3 nv] = PF[M, 496] x [posedirs ; shapedirs^T]
 hipError_t blend_forward(const SkinSet& ss, const float* PF, int M, float* Voff, hipStream_t st) {
@@ -550,20 +541,18 @@ hipError_t blend_backward(const SkinSet& ss, const float* dV, int M, float* dPF,
     if (split) *split = false;
     const int K = 3 * ss.nv;
     if (gemm_split3_enabled() && ss.pn_bwd3.f) {
-        if (split && part2_stride && panel_gemm3_rb2k_ok(M, K, ss.pn_bwd3)) {
-            *split = true;
-            return panel_gemm3_rb2k(dV, K, M, K, ss.pn_bwd3, dPF, part2_stride, NPFX, NPFX, st);
+        const PanelPlan pl = plan_blend_backward(M, K, ss.pn_bwd3.ntile, ss.pn_bwd3.nst, PNF, split && part2_stride, proc_switches());
+        if (split) *split = pl.two_partials;
+        switch (pl.form) {
+        case F_PANEL3_RB2K: return panel_gemm3_rb2k(pl, dV, K, M, K, ss.pn_bwd3, dPF, part2_stride, NPFX, NPFX, st);
+        case F_PANEL3_KSW: return panel_gemm3_ksw(pl, dV, K, M, K, ss.pn_bwd3, dPF, NPFX, NPFX, st);
+        case F_PANEL3_KLOOP: {
+            hipError_t e = ws.ensure((size_t)pl.ks * M * NPFX);
+            if (e != hipSuccess) return e;
+            return panel_gemm3_kloop(pl, dV, K, M, K, ss.pn_bwd3, ws.p, dPF, NPFX, NPFX, st);
         }
-        // r6: the K-loop form also where one LDS image would still fit, from K = 1664 at clip sizes and K = 1904 from 192 rows -- contact
-        // sets of 560-840 vertices ran the one-image forms at 17-35 us where the K-loop form takes 14-21 (tools/launch_times.py
-        // --per-leg 280 / 320 / 375 / 420 at 1024 / 512 / 256 / 128 rows; at 128 rows the one-image forms stay ahead).
-        constexpr int kmin = 1664;
-        const bool big_k = (M >= 384 && K >= kmin) || (M >= 192 && K >= kmin + 240);
-        if (!big_k && panel_gemm3_ksw_ok(M, K, ss.pn_bwd3)) return panel_gemm3_ksw(dV, K, M, K, ss.pn_bwd3, dPF, NPFX, NPFX, st);
-        if (!big_k && panel_gemm3_fits(K)) return panel_gemm3(dV, K, M, K, ss.pn_bwd3, dPF, NPFX, NPFX, st);
-        hipError_t e = ws.ensure((size_t)panel_gemm3_kloop_parts(M, ss.pn_bwd3) * M * NPFX);
-        if (e != hipSuccess) return e;
-        return panel_gemm3_kloop(dV, K, M, K, ss.pn_bwd3, ws.p, dPF, NPFX, NPFX, st);
+        default: return panel_gemm3(dV, K, M, K, ss.pn_bwd3, dPF, NPFX, NPFX, st);      // one image, the forward's forms
+        }
     }
     if (ss.pn_bwd.f) return panel_gemm(dV, K, M, K, ss.pn_bwd, dPF, NPFX, NPFX, st);
     return gemm_f32(true, EPI_STORE, dV, K, ss.posedirs.p, ss.ldp, dPF, NPFX, M, NPFX, K, nullptr, 0, st);
@@ -583,7 +572,7 @@ int vposer_forward(fdcap_ctx* c, const float* X, int ldx, int latent_off, int ro
     const int nb1 = (rows + 15) / 16, nb2 = (rows2 + 15) / 16;
     if (rows2 > 0) { two.nb1 = nb1; two.row2_lo = row2_lo; two.row2_hi = row2_hi; }
     if (O && rows2 > 0) return FDCAP_E_ARG;                   // (the summed output is only formed for one range)
-    if (gemm_split3_enabled())
+    if (plan_decoder(gemm_split3_enabled()) == F_VPOSER_SPLIT)
         hipLaunchKernelGGL(vposer_fwd_split3_kernel, dim3(4 * (nb1 + nb2)), dim3(512), 0, st, c->vp3, X + latent_off, ldx, row_lo,
                            row_hi, H1, H2, Opart, part_stride, two, ds);
     else
@@ -711,11 +700,12 @@ int opt_vposer_backward(fdcap_ctx* c, bool fold, hipStream_t st, ScaleTail tail 
     const int nb = 4 * ((nl + 15) / 16);
     if (tail.block >= 0) tail.block = 0;                   // (first in the grid: fdc_panel.h)
     tail.nclip = o->nclip; tail.clip_n = o->rows_per_clip();      // (a batch: one tail workgroup per clip)
-    if (gemm_split3_enabled() && tail.lg.rows && nb >= LROW && o->nclip == 1) {
+    const bool split3 = plan_decoder(gemm_split3_enabled()) == F_VPOSER_SPLIT;
+    if (split3 && tail.lg.rows && nb >= LROW && o->nclip == 1) {
         tail.lg_spread = 1;                                // the logged sums: one regular workgroup per term (ScaleTail::lg_spread)
         if (tail.n <= 0) tail.block = -1;                  // ... and with no `scale` step there is nothing left for an extra workgroup
     }
-    if (gemm_split3_enabled())
+    if (split3)
         hipLaunchKernelGGL(vposer_bwd_split3_kernel, dim3(nb + (tail.block >= 0 ? tail.nclip : 0)), dim3(512), 0, st, c->vp3, o->dO.p, 2, 2 + nl, o->H1.p, o->H2.p,
                            o->dZpart.p, ps, tail);
     else

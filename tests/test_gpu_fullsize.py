@@ -122,7 +122,7 @@ def test_clip_sized_kernel_forms_give_the_same_gradient(assets, tmp_path):
     import subprocess
     import sys
     code = r'''
-import sys, numpy as np, torch
+import ctypes, sys, numpy as np, torch
 sys.path.insert(0, %r)
 import fdcap_amd
 from fdcap_amd import capi, synth
@@ -137,14 +137,21 @@ dx = torch.empty(N, 78, device="cuda")
 capi.check(lib.fdcap_opt_get_grads(h, capi.dptr(dx), None, capi.current_stream()), "grads")
 torch.cuda.synchronize()
 np.save(sys.argv[1], dx.cpu().numpy())
+buf = ctypes.create_string_buffer(4096)
+lib.fdcap_debug_kernel_forms(buf, 4096, 0)
+open(sys.argv[1] + ".forms", "w").write(buf.value.decode())
 ''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    grads = []
+    grads, forms = [], []
     for flag in ("0", "1"):
         out = str(tmp_path / ("fullsize_grad_%s.npy" % flag))        # (pytest's per-test directory: two suites on one box do not collide)
         env = dict(os.environ, FDCAP_PN_RB2=flag)
         subprocess.run([sys.executable, "-c", code, out], check=True, env=env, timeout=600)   # (the switch is read once per process)
         grads.append(np.load(out))
+        forms.append(open(out + ".forms").read().split(";"))
         os.remove(out)
+    # the two runs took the two forms of the data gradient (tests/forms_table.json: 1024 rows, 500 contact vertices)
+    assert "panel_gemm3_kernel" in forms[0] and "panel_gemm3_rb2k_kernel" not in forms[0], forms[0]
+    assert "panel_gemm3_rb2k_kernel" in forms[1], forms[1]
     g0, g1 = grads
     assert np.abs(g0).max() > 0
     np.testing.assert_allclose(g1, g0, rtol=2e-4, atol=2e-6 * np.abs(g0).max())
@@ -164,8 +171,8 @@ CONFIGS = {
     # BASELINE config 5: 2M-pt dense scene, 512 frames, contact term over ALL 10 475 vertices (5.4 M queries per launch;
     # nc > 1024: chunked skinning backward, wide blend forward, K = 3V data-gradient GEMM)
     "C5": dict(n=512, ns=2_000_000, all_contacts=True, sample=1500, grad_frames=[0, 1, 255, 511]),
-    # BASELINE config 2: 256-frame clip, full loss vs a 100k-pt scene, 500 contact vertices (one-row-block blend products
-    # below 384 rows)
+    # BASELINE config 2: 256-frame clip, full loss vs a 100k-pt scene, 500 contact vertices (one-row-block blend products:
+    # the clip-sized forward forms start at 336 rows, the K-split data gradient at 257)
     "C2": dict(n=256, ns=100_000, all_contacts=False, sample=2000, grad_frames=[0, 1, 2, 100, 101, 254, 255]),
 }
 
@@ -344,14 +351,14 @@ def test_c2_trajectory_on_a_frame_subset_matches_the_oracle():
 
 @pytest.mark.parametrize("frames", [128, 200])
 def test_shard_sized_kernel_forms_give_the_same_gradient(tmp_path, frames):
-    """r5: at a shard's size (fewer than 384 rows) the data gradient of the blend product splits K over the eight waves of a
+    """r5: at a shard's size (256 rows or fewer) the data gradient of the blend product splits K over the eight waves of a
     workgroup (panel_gemm3_ksw_kernel) and the forward runs four-wave workgroups; FDCAP_PN_KSW=0 / FDCAP_PN_NW=8 select the
     eight-wave one-row-block products of r2-r4.  Same products, another summation order over K in the gradient: the optimiser's
     gradient agrees to rounding of the sums (the bar of the clip-sized forms' test); 200 frames: ragged last row block."""
     import subprocess
     import sys
     code = r'''
-import sys, numpy as np, torch
+import ctypes, sys, numpy as np, torch
 sys.path.insert(0, %r)
 import fdcap_amd
 from fdcap_amd import capi, synth
@@ -371,12 +378,19 @@ dx = torch.empty(n, 78, device="cuda")
 capi.check(lib.fdcap_opt_get_grads(h, capi.dptr(dx), None, capi.current_stream()), "grads")
 torch.cuda.synchronize()
 np.save(sys.argv[1], dx.cpu().numpy())
+buf = ctypes.create_string_buffer(4096)
+lib.fdcap_debug_kernel_forms(buf, 4096, 0)
+open(sys.argv[1] + ".forms", "w").write(buf.value.decode())
 ''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    grads = []
+    grads, forms = [], []
     for env_extra in ({"FDCAP_PN_KSW": "0", "FDCAP_PN_NW": "8"}, {}):
         out = str(tmp_path / ("shard_grad_%d.npy" % len(grads)))
         subprocess.run([sys.executable, "-c", code, out, str(frames)], check=True, env=dict(os.environ, **env_extra), timeout=600)
         grads.append(np.load(out))
+        forms.append(open(out + ".forms").read().split(";"))
+    # the two runs took the two forms of the data gradient (tests/forms_table.json: 128 / 200 rows, 500 contact vertices)
+    assert "panel_gemm3_kernel" in forms[0] and "panel_gemm3_ksw_kernel" not in forms[0], forms[0]
+    assert "panel_gemm3_ksw_kernel" in forms[1], forms[1]
     g0, g1 = grads
     assert np.abs(g0).max() > 0
     np.testing.assert_allclose(g1, g0, rtol=2e-4, atol=2e-6 * np.abs(g0).max())

@@ -6,7 +6,7 @@
 so that "reference loop -> oracle -> HIP" closes on the kernel forms the bench times, not only on toy bodies.
 
 The reference hard-codes 300 frames (:41-42, :465, :472) and the clip-sized forms (two row blocks per fragment stream, the fused
-contact forward) are selected from 384 rows: each fixture is therefore run twice -- as the library would run a 300-frame clip, and
+contact forward) are selected from 336 rows (the K-split data gradient from 257): each fixture is therefore run twice -- as the library would run a 300-frame clip, and
 in a child process with FDCAP_CLIP_FORMS_MIN_ROWS=256 (read once per process), where fdcap_debug_kernel_forms must list the forms
 configs 3 / 5 select.  Bars: those of tests/test_gpu_parity.py::test_trajectory_matches_reference_golden (Adam through L1 kinks)."""
 import json
