@@ -356,7 +356,7 @@ int fdcap_panel_gemm(const float* A, int32_t lda, int32_t M, int32_t K, const fl
     hipStream_t st = (hipStream_t)stream;
     {
         // (the switch is read per call here, so a test can run both forms in one process)
-        if (forms_read_env().gemm_split3 && panel_gemm3_fits(PNF, K)) {          // the split form of the same product on the 16-bit matrix cores (format PnF; the default)
+        if (forms_read_env().gemm_split3 && panel_gemm3_fits(K)) {               // the split form of the same product on the 16-bit matrix cores (format PnF; the default)
             std::vector<unsigned> p3;
             std::vector<float> sc;
             PanelB3 B3;

@@ -94,18 +94,18 @@ inline const char* form_name(Form f) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Split products (fdc_panel.h).  `np`: planes of the operand format (PnH2: 2, PnB3: 3); ntile = ceil(N / 16) column tiles and
+// Split products (fdc_panel.h).  `np`: planes of the operand format (PnH2: 2); ntile = ceil(N / 16) column tiles and
 // nst = ceil(K / 32) steps of the static operand.
 
-// uint4 per 16-row LDS image of kpad columns (behind the planes of the two-plane format: 16 inverse row scales + 16 partial maxima per
-// wave, <= 12 waves); bytes of rb of them
-constexpr FDC_FORMS_HD int pn_sc_u4(int np) { return np == 2 ? 4 + 4 * 12 : 0; }
-constexpr FDC_FORMS_HD int pn_img_u4(int np, int kpad) { return np * (kpad >> 3) * 16 + pn_sc_u4(np); }
+// uint4 per 16-row LDS image of kpad columns (behind the planes: 16 inverse row scales + 16 partial maxima per wave, <= 12 waves);
+// bytes of rb of them
+constexpr int PN_SC_U4 = 4 + 4 * 12;
+constexpr FDC_FORMS_HD int pn_img_u4(int np, int kpad) { return np * (kpad >> 3) * 16 + PN_SC_U4; }
 constexpr FDC_FORMS_HD size_t pn_lds_bytes(int np, int kpad, int rb) { return (size_t)rb * pn_img_u4(np, kpad) * 16; }
-// longest K whose single-slab LDS image (pn_lds_bytes(np, kpad, 1)) fits the 160 KB of a gfx950 CU
-constexpr int pn3_max_k(int np) { return np == 2 ? 2528 : 1696; }
-static_assert(pn_lds_bytes(2, pn3_max_k(2), 1) <= 160 * 1024 && pn_lds_bytes(3, pn3_max_k(3), 1) <= 160 * 1024, "one image per CU");
-constexpr bool panel_gemm3_fits(int np, int K) { return ((K + 31) & ~31) <= pn3_max_k(np); }
+// longest K whose single-slab LDS image (pn_lds_bytes(2, kpad, 1)) fits the 160 KB of a gfx950 CU
+constexpr int PN3_MAX_K = 2528;
+static_assert(pn_lds_bytes(2, PN3_MAX_K, 1) <= 160 * 1024, "one image per CU");
+constexpr bool panel_gemm3_fits(int K) { return ((K + 31) & ~31) <= PN3_MAX_K; }
 constexpr size_t pn_b_bytes(int np, int ntile, int nst) { return (size_t)ntile * nst * np * 1024; }
 
 // Workgroup -> (row block, column block), XCD-aware.  The dispatcher deals consecutive workgroups to the 8 XCDs round-robin
@@ -166,7 +166,7 @@ struct PanelPlan {
 inline PanelPlan plan_panel3(int M, int K, int ntile, int nst, int np, const FormSwitches& sw) {
     PanelPlan p;
     const int kpad = (K + 31) & ~31;
-    if (kpad > pn3_max_k(np)) return p;
+    if (kpad > PN3_MAX_K) return p;
     const size_t b_bytes = pn_b_bytes(np, ntile, nst);
     if (b_bytes > (size_t)(16u << 20) && M >= 32 && kpad <= 768) {
         // wide outputs: one workgroup per CU (the 98 KB image leaves room for one): as many column parts as it takes to reach 256
@@ -217,7 +217,7 @@ inline PanelPlan plan_blend_backward(int M, int K, int ntile, int nst, int np, b
     constexpr int kmin = 1664;
     const bool big_k = (M >= 384 && K >= kmin) || (M >= 192 && K >= kmin + 240);
     // K split over the eight waves of a workgroup: when a long K sits in one LDS image and there are few row blocks
-    if (!big_k && sw.pn_ksw && kpad <= pn3_max_k(np) && kpad >= 768 && ((M + 15) / 16) * ((ntile + 7) / 8) < 128) {
+    if (!big_k && sw.pn_ksw && kpad <= PN3_MAX_K && kpad >= 768 && ((M + 15) / 16) * ((ntile + 7) / 8) < 128) {
         // column tiles per workgroup: two while that still gives >= 192 workgroups, else one -- r6: and two whenever one tile per
         // workgroup would mean more workgroups than CUs (one workgroup fits a CU: 129-176 rows ran in two rounds, 14.7 us at 160 rows
         // against 8.8 at 128 and 9.5 at 192: tools/launch_times.py sweep)
@@ -226,10 +226,10 @@ inline PanelPlan plan_blend_backward(int M, int K, int ntile, int nst, int np, b
         p.T = (nrb * ((ntile + 1) / 2) >= 192 || nrb * ntile > 256) ? 2 : 1;
         p.mp = panel_map(nrb, (ntile + p.T - 1) / p.T, (size_t)M * K * 4, pn_b_bytes(np, ntile, nst));
         p.grid = 8 * p.mp.rpg * p.mp.cpg; p.block = 512; p.lds = pn_lds_bytes(np, kpad, 1);
-        p.max_lds = pn_lds_bytes(np, pn3_max_k(np), 1);
+        p.max_lds = pn_lds_bytes(np, PN3_MAX_K, 1);
         return p;
     }
-    if (!big_k && panel_gemm3_fits(np, K)) return plan_panel3(M, K, ntile, nst, np, sw);
+    if (!big_k && panel_gemm3_fits(K)) return plan_panel3(M, K, ntile, nst, np, sw);
     // K far beyond any LDS image (the FULL mesh's data gradient, K = 3 V = 31 425), or big_k: K in `ks` parts, a partial product each
     constexpr int rb = PN3_KLOOP_RB, T = PN3_KLOOP_T;
     p.form = F_PANEL3_KLOOP;

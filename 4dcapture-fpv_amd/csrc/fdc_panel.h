@@ -17,8 +17,8 @@
 //   vposer_bwd_fused_kernel    the data-gradient chain dO -> dH2 -> dH1 -> d latent in one launch, split the other way round
 //                              (every step is linear in its input once the LeakyReLU masks are applied, so K-slices of a
 //                              step can run independently down to four partial latent gradients, summed by the Adam kernel)
-// Replaces six gemm_f32 launches per iteration (55 us at 1028 rows) by two (~8 us each) and the two blend products'
-// 25 + 24 us by ~12 + 12.
+// Against one LDS-tiled GEMM launch per product (six per iteration for the decoder, 55 us at 1028 rows): two launches of ~8 us each,
+// and the two blend products' 25 + 24 us became ~12 + 12.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -326,125 +326,32 @@ __global__ __launch_bounds__(512) void panel_gemm_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// fp32 products on the bf16 matrix cores: three-way split.
-// An fp32 number is EXACTLY the sum of three bf16 numbers, a = h + m + l (8 + 8 + 8 mantissa bits: h = bf16(a),
-// m = bf16(a - h), l = bf16(a - h - m); both subtractions are exact).  A product a b is then nine bf16 x bf16 partial
-// products (each exact in fp32); the three smallest (m l, l m, l l) are below 2^-23 |a b| together -- one fp32 rounding
-// of the product itself -- and are dropped; the other six go through v_mfma_f32_16x16x32_bf16 with fp32 accumulation,
-// smallest first.  Six bf16 MFMAs cover 32 columns of K in ~100 cycles per SIMD where the fp32 form needs eight
-// v_mfma_f32_16x16x4_f32 = 256 cycles, and the loop's products are bound by exactly that pipe (93 % of its issue slots).
-// Error vs the exact product: <= 2^-22 relative per term, the class of the fp32 fmaf chain's own rounding
-// (tests/test_gpu_panel.py holds both forms to the same bar against fp64).
-typedef __bf16 pn_bf16x8 __attribute__((ext_vector_type(8)));
+// fp32 products on the 16-bit matrix cores: the operands are split into planes of 16-bit numbers (format PnH2 below) and a product
+// becomes a few v_mfma_f32_16x16x32_f16 with fp32 accumulation -- 32 columns of K in a fraction of the cycles the fp32 form needs
+// (eight v_mfma_f32_16x16x4_f32 = 256 cycles per SIMD), and the loop's products are bound by exactly that pipe (93 % of its issue
+// slots).  tests/test_gpu_panel.py holds both forms to the same bar against fp64.
 typedef float f32x4u_t __attribute__((ext_vector_type(4), aligned(4)));      // 16-byte store at 4-byte alignment (3 V is odd)
 struct PanelB3 {
-    const uint4* f = nullptr;       // f[((tile * nst + s) * 3 + plane) * 64 + lane] = 8 bf16: B(32 s + 8 (lane >> 4) + e, 16 tile + (lane & 15))
+    const uint4* f = nullptr;       // f[((tile * nst + s) * 2 + plane) * 64 + lane] = 8 fp16: B(32 s + 8 (lane >> 4) + e, 16 tile + (lane & 15)), scaled
     int ntile = 0, nst = 0;         // ceil(N / 16), ceil(K / 32)
-    const float* isc = nullptr;     // PnH2 panels: isc[16 tile + c] = 1 / (the power-of-two scale of output column c of the tile); two planes there
+    const float* isc = nullptr;     // isc[16 tile + c] = 1 / (the power-of-two scale of output column c of the tile)
 };
-static inline unsigned pn3_bf_host(float f) { unsigned u; memcpy(&u, &f, 4); u += 0x7FFFu + ((u >> 16) & 1u); return u >> 16; }   // RNE
-static inline float pn3_bff_host(unsigned h) { unsigned u = h << 16; float f; memcpy(&f, &u, 4); return f; }
-static inline void panel_pack3(const float* src, long sk, long sn, int K, int N, std::vector<unsigned>& out, int* ntile, int* nst) {
-    const int nt = (N + 15) / 16, ns = (K + 31) / 32;
-    out.assign((size_t)nt * ns * 3 * 64 * 4, 0u);
-    for (int t = 0; t < nt; ++t)
-        for (int s = 0; s < ns; ++s)
-            for (int l = 0; l < 64; ++l) {
-                const int n = 16 * t + (l & 15);
-                if (n >= N) continue;
-                for (int e = 0; e < 8; ++e) {
-                    const int k = 32 * s + 8 * (l >> 4) + e;
-                    if (k >= K) continue;
-                    const float a = src[(long)k * sk + (long)n * sn];
-                    const unsigned h = pn3_bf_host(a);
-                    const float r1 = a - pn3_bff_host(h);
-                    const unsigned m = pn3_bf_host(r1);
-                    const unsigned lo = pn3_bf_host(r1 - pn3_bff_host(m));
-                    const unsigned part[3] = {h, m, lo};
-                    for (int pl = 0; pl < 3; ++pl) {
-                        unsigned& w = out[((((size_t)t * ns + s) * 3 + pl) * 64 + l) * 4 + (e >> 1)];
-                        w |= part[pl] << (16 * (e & 1));
-                    }
-                }
-            }
-    *ntile = nt;
-    *nst = ns;
-}
-
-__device__ __forceinline__ unsigned pn3_bf(float f) { return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)f); }   // RNE
-__device__ __forceinline__ float pn3_bff(unsigned h) { return __uint_as_float(h << 16); }
-
-// The three-way split of TWO values at once (late r4): v_cvt_pk_bf16_f32 converts a pair and packs it -- low half the first value --
-// so a plane's dword needs no shift / or to assemble; the parts are the same round-to-nearest-even conversions of the same
-// residuals as pn3_bf / pn3_bff element by element (46 instead of ~68 VALU instructions per eight values).
-typedef __bf16 pn_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pn_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pn3_pk2(float a, float b) {
-    const pn_f32x2 f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, pn_bf16x2));
-}
-__device__ __forceinline__ void pn3_split2(float a, float b, unsigned& H, unsigned& M, unsigned& L) {
-    H = pn3_pk2(a, b);
-    const float ra = a - __uint_as_float(H << 16), rb = b - __uint_as_float(H & 0xffff0000u);
-    M = pn3_pk2(ra, rb);
-    L = pn3_pk2(ra - __uint_as_float(M << 16), rb - __uint_as_float(M & 0xffff0000u));
-}
-
-// stage rows [r0, r0 + 16) x columns [k0, k0 + kn) of A as three bf16 planes, each [kpad / 8 chunks][16 rows] x 16 bytes
-// (kpad % 32 == 0; rows >= rmax and columns >= kn are zero).  NT threads; one (chunk, row) item = 8 columns.
-template <int NT>
-__device__ __forceinline__ void panel_stage3(uint4* __restrict__ sA3, const float* __restrict__ A, int lda, int r0, int rmax, int k0,
-                                             int kn, int kpad, int tid) {
-    const int nch = kpad >> 3;
-    const bool vec = ((lda & 3) == 0) && ((k0 & 3) == 0) && ((((size_t)A) & 15) == 0);
-    for (int it = tid; it < nch * 16; it += NT) {
-        const int ch = it >> 4, i = it & 15, row = r0 + i, k = 8 * ch;
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.f;
-        if (row < rmax && k < kn) {
-            const float* p = A + (size_t)row * lda + k0 + k;
-            if (vec && k + 7 < kn) {
-                const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-                v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) if (k + e < kn) v[e] = p[e];
-            }
-        }
-        unsigned h[4], m[4], l[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pn3_split2(v[2 * e], v[2 * e + 1], h[e], m[e], l[e]);
-        sA3[(size_t)0 * nch * 16 + it] = make_uint4(h[0], h[1], h[2], h[3]);
-        sA3[(size_t)1 * nch * 16 + it] = make_uint4(m[0], m[1], m[2], m[3]);
-        sA3[(size_t)2 * nch * 16 + it] = make_uint4(l[0], l[1], l[2], l[3]);
-    }
-}
-
-__device__ __forceinline__ f32x4_t pn3_step(const uint4* a /*[3] planes h m l of the LDS block*/, const uint4* b /*[3] of the fragment*/, f32x4_t acc) {
-    // static fragment = MFMA A operand (rows = output columns), LDS block = B operand (columns = frames): see pn_step
-#define PN3_MMA(wp, ap) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(pn_bf16x8, b[wp]), __builtin_bit_cast(pn_bf16x8, a[ap]), acc, 0, 0, 0)
-    PN3_MMA(2, 0); PN3_MMA(0, 2); PN3_MMA(1, 1); PN3_MMA(1, 0); PN3_MMA(0, 1); PN3_MMA(0, 0);
-#undef PN3_MMA
-    return acc;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Operand formats of the split products.  PnB3: the three bf16 planes above (six products per step; -DFDC_PN_H2=0 builds everything on it).
-// PnH2 (late r5; the blend products): TWO fp16 planes and THREE products per step.
+// Operand format of the split products, PnH2 (late r5; three bf16 planes and six products per step until then): TWO fp16 planes and
+// THREE products per step.
 //   a s = h + 2^-11 l,  h = fp16(a s),  l = fp16((a s - h) 2^11)   (both conversions round to nearest even; a s - h is exact)
 // with s a power of two per frame row of the dynamic operand (its largest |a| lands in [2^13, 2^14): found while the block is
 // staged, one extra barrier) and per output column of the static one (host).  |a - (h + 2^-11 l) / s| <= 2^-22 |a| for every element
 // within 2^-27 of its row's largest (below that: 2^-50 of the largest, absolutely).  Products h h -> one accumulator, l h + h l ->
 // a second one, joined as (acc_h + 2^-11 acc_l) / (s_a s_b) in the epilogue (exact scalings, one rounding); l l (<= 2^-22 |a b|)
-// is dropped.  Error <= 3 x 2^-22 |a||b| per term: above PnB3's 2^-22, far below the K 2^-24 bound of an fp32 fmaf chain, and
-// tests/test_gpu_panel.py holds it to the same 1e-6 sum|a||b| bar against fp64.  What it buys: half the MFMA issue, two thirds
-// of the fragment bytes and of the LDS reads per 32 columns of K -- all three of the resources these kernels sit on at once.
-#ifndef FDC_PN_H2
-#define FDC_PN_H2 1
-#endif
+// is dropped.  Error <= 3 x 2^-22 |a||b| per term: far below the K 2^-24 bound of an fp32 fmaf chain, and
+// tests/test_gpu_panel.py holds it to the same 1e-6 sum|a||b| bar against fp64.  Against the three-plane format: half the MFMA
+// issue, two thirds of the fragment bytes and of the LDS reads per 32 columns of K -- all three of the resources these kernels sit
+// on at once.
 typedef _Float16 pn_f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 pn_f16x2 __attribute__((ext_vector_type(2)));
+typedef float pn_f32x2 __attribute__((ext_vector_type(2)));
 static inline unsigned pn2_f16_host(float f) {                  // fp32 -> fp16 bits, round to nearest even (no libgcc soft-float call)
     unsigned u; memcpy(&u, &f, 4);
     const unsigned sign = (u >> 16) & 0x8000u, ex = (u >> 23) & 255u;
@@ -470,27 +377,6 @@ static inline float pn2_f16f_host(unsigned h) {
     memcpy(&f, &u, 4);
     return f;
 }
-struct PnB3 {
-    static constexpr int NP = 3, SC_U4 = 0;                     // planes; uint4 of per-row scales (+ scratch) behind an image's planes
-    typedef f32x4_t Acc;
-    static __device__ __forceinline__ Acc zero() { return f32x4_t{0.f, 0.f, 0.f, 0.f}; }
-    static __device__ __forceinline__ Acc step(const uint4* a, const uint4* b, Acc acc) { return pn3_step(a, b, acc); }
-    static __device__ __forceinline__ f32x4_t value(const Acc& a, float, const f32x4_t&) { return a; }
-    static __device__ __forceinline__ float row_isc(const uint4*, int, int) { return 1.f; }
-    static __device__ __forceinline__ f32x4_t tile_isc(const PanelB3&, int, int) { return f32x4_t{1.f, 1.f, 1.f, 1.f}; }
-    template <int NT, int RB, int MAXIT>
-    static __device__ __forceinline__ void stage(uint4* __restrict__ lds, int img, const float* __restrict__ A, int lda, int m0, int M, int k0,
-                                                 int kn, int kpad, int tid) {
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) panel_stage3<NT>(lds + (size_t)rb * img, A, lda, m0 + 16 * rb, M, k0, kn, kpad, tid);
-    }
-    static __device__ __forceinline__ void pow2(float, float& sc, float& isc) { sc = 1.f; isc = 1.f; }
-    static inline void pack(const float* src, long sk, long sn, int K, int N, std::vector<unsigned>& out, std::vector<float>& isc, int* ntile,
-                            int* nst) {
-        panel_pack3(src, sk, sn, K, N, out, ntile, nst);
-        isc.assign((size_t)*ntile * 16, 1.f);
-    }
-};
 __device__ __forceinline__ unsigned pn2_pk2(float a, float b) {
     const pn_f32x2 f = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f, pn_f16x2));
@@ -702,15 +588,11 @@ __global__ __launch_bounds__(256) void pnh2_pack_kernel(const float* __restrict_
     o[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
 }
 
-#if FDC_PN_H2
 typedef PnH2 PnF;                                               // the format of the panel_gemm3_* family
-#else
-typedef PnB3 PnF;
-#endif
 __device__ __forceinline__ f32x4_t PnH2::tile_isc(const PanelB3& B, int tile, int g) { return ((const f32x4_t*)B.isc)[(size_t)min(tile, B.ntile - 1) * 4 + g]; }
 constexpr int PNF = PnF::NP;
 // uint4 per 16-row image of kpad columns; bytes of RB of them (fdc_forms.h, by plane count)
-static_assert(PnB3::SC_U4 == pn_sc_u4(PnB3::NP) && PnH2::SC_U4 == pn_sc_u4(PnH2::NP), "fdc_forms.h sizes the LDS images");
+static_assert(PnH2::SC_U4 == PN_SC_U4, "fdc_forms.h sizes the LDS images");
 constexpr __host__ __device__ int pnf_img_u4(int kpad) { return pn_img_u4(PNF, kpad); }
 constexpr __host__ __device__ size_t pnf_lds_bytes(int kpad, int rb) { return pn_lds_bytes(PNF, kpad, rb); }
 
@@ -1043,10 +925,10 @@ static inline hipError_t panel_gemm(const float* A, int lda, int M, int K, const
 }
 
 // T tiles share one 16-row LDS block (the fused VPoser kernels' layers)
-template <int T, int PF, class F = PnB3>
-struct PnRing3T { uint4 bA[T][PF][F::NP]; const uint4* st[T]; };
-template <int T, int PF, class F = PnB3>
-__device__ __forceinline__ void panel3_prefetch_t(PnRing3T<T, PF, F>& rg, const uint4* const* bf, int nst, int lane) {
+template <int T, int PF>
+struct PnRing3T { uint4 bA[T][PF][PNF]; const uint4* st[T]; };
+template <int T, int PF>
+__device__ __forceinline__ void panel3_prefetch_t(PnRing3T<T, PF>& rg, const uint4* const* bf, int nst, int lane) {
     const int last = nst - 1;
 #pragma unroll
     for (int t = 0; t < T; ++t) rg.st[t] = bf[t] + lane;
@@ -1055,11 +937,11 @@ __device__ __forceinline__ void panel3_prefetch_t(PnRing3T<T, PF, F>& rg, const 
 #pragma unroll
         for (int t = 0; t < T; ++t)
 #pragma unroll
-            for (int pl = 0; pl < F::NP; ++pl) rg.bA[t][p][pl] = rg.st[t][((size_t)min(p, last) * F::NP + pl) * 64];
+            for (int pl = 0; pl < PNF; ++pl) rg.bA[t][p][pl] = rg.st[t][((size_t)min(p, last) * PNF + pl) * 64];
 }
-template <int T, int PF, class F = PnB3>
-__device__ __forceinline__ void panel3_mma_t(const uint4* __restrict__ sA3, int pstride, PnRing3T<T, PF, F>& rg, int nst, typename F::Acc* acc, int lane) {
-    constexpr int NP = F::NP;
+template <int T, int PF>
+__device__ __forceinline__ void panel3_mma_t(const uint4* __restrict__ sA3, int pstride, PnRing3T<T, PF>& rg, int nst, PnF::Acc* acc, int lane) {
+    constexpr int NP = PNF;
     uint4 (&bA)[T][PF][NP] = rg.bA;
     uint4 bB[T][PF][NP];
     const int last = nst - 1;
@@ -1084,7 +966,7 @@ __device__ __forceinline__ void panel3_mma_t(const uint4* __restrict__ sA3, int 
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) bB[t][p][pl] = rg.st[t][((size_t)(s + PF + p) * NP + pl) * 64];
                 pn_pin();
-                acc[t] = F::step(a, bA[t][p], acc[t]);
+                acc[t] = PnF::step(a, bA[t][p], acc[t]);
             }
             keep(a, an);
         }
@@ -1097,7 +979,7 @@ __device__ __forceinline__ void panel3_mma_t(const uint4* __restrict__ sA3, int 
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) bA[t][p][pl] = rg.st[t][((size_t)min(s + 2 * PF + p, last) * NP + pl) * 64];
                 pn_pin();
-                acc[t] = F::step(a, bB[t][p], acc[t]);
+                acc[t] = PnF::step(a, bB[t][p], acc[t]);
             }
             keep(a, an);
         }
@@ -1111,7 +993,7 @@ __device__ __forceinline__ void panel3_mma_t(const uint4* __restrict__ sA3, int 
             for (int t = 0; t < T; ++t) {
 #pragma unroll
                 for (int pl = 0; pl < NP; ++pl) bB[t][p][pl] = rg.st[t][((size_t)min(s + PF + p, last) * NP + pl) * 64];
-                acc[t] = F::step(a, bA[t][p], acc[t]);
+                acc[t] = PnF::step(a, bA[t][p], acc[t]);
             }
             keep(a, an);
         }
@@ -1122,7 +1004,7 @@ __device__ __forceinline__ void panel3_mma_t(const uint4* __restrict__ sA3, int 
             uint4 an[NP];
             load_a(an, min(s + PF + p + 1, last));
 #pragma unroll
-            for (int t = 0; t < T; ++t) acc[t] = F::step(a, bB[t][p], acc[t]);
+            for (int t = 0; t < T; ++t) acc[t] = PnF::step(a, bB[t][p], acc[t]);
             keep(a, an);
         }
     }
@@ -1130,7 +1012,7 @@ __device__ __forceinline__ void panel3_mma_t(const uint4* __restrict__ sA3, int 
 // RB row blocks x T tiles per wave (r5, the K-loop product): a step's RB LDS fragments are read ONCE for T tiles and its T static
 // fragments once for RB row blocks -- RB T products per (RB LDS reads + T fragment loads).  acc[rb * T + t].  Format PnF.
 template <int RB, int T, int PF>
-__device__ __forceinline__ void panel3_mma_rt(const uint4* __restrict__ sA3, int pstride, int img, PnRing3T<T, PF, PnF>& rg, int nst, PnF::Acc* acc, int lane) {
+__device__ __forceinline__ void panel3_mma_rt(const uint4* __restrict__ sA3, int pstride, int img, PnRing3T<T, PF>& rg, int nst, PnF::Acc* acc, int lane) {
     uint4 (&bA)[T][PF][PNF] = rg.bA;
     uint4 bB[T][PF][PNF];
     const int last = nst - 1;
@@ -1217,12 +1099,12 @@ __global__ __launch_bounds__(512) void panel_gemm3_ksw_kernel(const float* __res
     const int tile0 = cbk * T, m0 = rbk * 16;
     const int kpad = (K + 31) & ~31, nst_all = kpad >> 5, pstride = (kpad >> 3) * 16;
     const int per = (nst_all + 7) >> 3, s_lo = min(nst_all, wave * per), nst = min(nst_all, s_lo + per) - s_lo;
-    PnRing3T<T, 2, PnF> rg;
+    PnRing3T<T, 2> rg;
     if (nst > 0) {                                             // (wave-uniform) in flight while the A block is staged
         const uint4* bf[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) bf[t] = B.f + ((size_t)min(tile0 + t, B.ntile - 1) * B.nst + s_lo) * PNF * 64;
-        panel3_prefetch_t<T, 2, PnF>(rg, bf, nst, lane);
+        panel3_prefetch_t<T, 2>(rg, bf, nst, lane);
     }
     f32x4_t ts[T];
 #pragma unroll
@@ -1295,7 +1177,7 @@ __global__ __launch_bounds__(512) void panel_gemm3_kloop_kernel(const float* __r
     const int nst_all = (K + 31) >> 5, per = (nst_all + ks - 1) / ks, s_lo = part * per, s_hi = min(nst_all, s_lo + per);
     const int tile0 = (cb * 8 + wave) * T;                      // this wave's T consecutive column tiles
     const int kpad = 32 * slab_steps, pstride = (kpad >> 3) * 16, img = pnf_img_u4(kpad);
-    f32x4_t tot[RB * T];                                        // the slabs' products at the tile's scale (PnH2: a row's scale is per slab)
+    f32x4_t tot[RB * T];                                        // the slabs' products at the tile's scale (a row's scale is per slab)
 #pragma unroll
     for (int i = 0; i < RB * T; ++i) tot[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     PnF::Acc acc[RB * T];
@@ -1306,26 +1188,24 @@ __global__ __launch_bounds__(512) void panel_gemm3_kloop_kernel(const float* __r
     for (int t = 0; t < T; ++t) ts[t] = PnF::tile_isc(B, tile0 + t, g);
     for (int s0 = s_lo; s0 < s_hi; s0 += slab_steps) {
         const int nst = min(slab_steps, s_hi - s0), k0 = 32 * s0, kn = min(K, 32 * (s0 + nst)) - k0;
-        PnRing3T<T, 2, PnF> rg;                                 // (requested before the staging: the first round trip hides behind it)
+        PnRing3T<T, 2> rg;                                 // (requested before the staging: the first round trip hides behind it)
         const uint4* bf[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) bf[t] = B.f + ((size_t)min(tile0 + t, B.ntile - 1) * B.nst + s0) * PNF * 64;
-        panel3_prefetch_t<T, 2, PnF>(rg, bf, nst, lane);
+        panel3_prefetch_t<T, 2>(rg, bf, nst, lane);
         if (s0 > s_lo) __syncthreads();                         // every wave is done with the previous slab's images
         PnF::stage<512, RB, 3>(pn3_lds, img, A, lda, m0, M, k0, kn, kpad, tid);
         __syncthreads();
         if (tile0 < B.ntile) panel3_mma_rt<RB, T, 2>(pn3_lds, pstride, img, rg, nst, acc, lane);
-        if (PnF::SC_U4) {                                       // fold the slab in at its rows' scales
 #pragma unroll
-            for (int rb = 0; rb < RB; ++rb) {
-                const float rs = PnF::row_isc(pn3_lds + (size_t)rb * img, pstride, j);
+        for (int rb = 0; rb < RB; ++rb) {                       // fold the slab in at its rows' scales
+            const float rs = PnF::row_isc(pn3_lds + (size_t)rb * img, pstride, j);
 #pragma unroll
-                for (int t = 0; t < T; ++t) {
-                    const f32x4_t v = PnF::value(acc[rb * T + t], rs, f32x4_t{1.f, 1.f, 1.f, 1.f});
+            for (int t = 0; t < T; ++t) {
+                const f32x4_t v = PnF::value(acc[rb * T + t], rs, f32x4_t{1.f, 1.f, 1.f, 1.f});
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) tot[rb * T + t][r] += v[r];
-                    acc[rb * T + t] = PnF::zero();
-                }
+                for (int r = 0; r < 4; ++r) tot[rb * T + t][r] += v[r];
+                acc[rb * T + t] = PnF::zero();
             }
         }
     }
@@ -1339,10 +1219,8 @@ __global__ __launch_bounds__(512) void panel_gemm3_kloop_kernel(const float* __r
                 const int m = m0 + 16 * rb + j;
                 if (m < M) {
                     f32x4_t v;
-                    if (PnF::SC_U4) {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = tot[rb * T + t][r] * ts[t][r];
-                    } else v = PnF::value(acc[rb * T + t], 1.f, f32x4_t{1.f, 1.f, 1.f, 1.f});
+                    for (int r = 0; r < 4; ++r) v[r] = tot[rb * T + t][r] * ts[t][r];
                     pnf_store4(C, ldc, N, m, n4, v);
                 }
             }
@@ -1374,19 +1252,8 @@ static inline hipError_t panel_gemm3_kloop(const PanelPlan& pl, const float* A, 
     return hipGetLastError();
 }
 
-// four consecutive columns n4 .. n4 + 3 of frame row j -> the planes of an LDS block (8 bytes per plane); sc: the row's scale (PnH2)
-__device__ __forceinline__ void pn3_store4(uint4* __restrict__ sA3, int pstride, int n4, int j, float4 v) {
-    unsigned h[2], m[2], l[2];
-    pn3_split2(v.x, v.y, h[0], m[0], l[0]);
-    pn3_split2(v.z, v.w, h[1], m[1], l[1]);
-    const size_t it = (size_t)(n4 >> 3) * 16 + j;
-    const int half = (n4 >> 2) & 1;
-    ((uint2*)(sA3 + (size_t)0 * pstride + it))[half] = make_uint2(h[0], h[1]);
-    ((uint2*)(sA3 + (size_t)1 * pstride + it))[half] = make_uint2(m[0], m[1]);
-    ((uint2*)(sA3 + (size_t)2 * pstride + it))[half] = make_uint2(l[0], l[1]);
-}
-__device__ __forceinline__ void pnf_lds_store4(PnB3*, uint4* __restrict__ sA3, int pstride, int n4, int j, float4 v, float) { pn3_store4(sA3, pstride, n4, j, v); }
-__device__ __forceinline__ void pnf_lds_store4(PnH2*, uint4* __restrict__ sA, int pstride, int n4, int j, float4 v, float sc) {
+// four consecutive columns n4 .. n4 + 3 of frame row j -> the planes of an LDS block (8 bytes per plane); sc: the row's scale
+__device__ __forceinline__ void pnf_lds_store4(uint4* __restrict__ sA, int pstride, int n4, int j, float4 v, float sc) {
     const float x[4] = {v.x * sc, v.y * sc, v.z * sc, v.w * sc};
     unsigned h[2], l[2];
 #pragma unroll
@@ -1401,18 +1268,8 @@ __device__ __forceinline__ void pnf_lds_store4(PnH2*, uint4* __restrict__ sA, in
     ((uint2*)(sA + (size_t)1 * pstride + it))[half] = make_uint2(l[0], l[1]);
 }
 // one latent value per thread (row i = tid >> 5, column k = tid & 31) straight into a 32-column image (plane stride `pstride`)
-__device__ __forceinline__ void pnf_put_latent(PnB3*, uint4* __restrict__ sZ, int pstride, int i, int k, float v) {
-    const unsigned h = pn3_bf(v);
-    const float r1 = v - pn3_bff(h);
-    const unsigned m = pn3_bf(r1), l = pn3_bf(r1 - pn3_bff(m));
-    unsigned short* const img = (unsigned short*)sZ;
-    const int it = (k >> 3) * 16 + i, e = k & 7;
-    img[(size_t)(0 * pstride + it) * 8 + e] = (unsigned short)h;
-    img[(size_t)(1 * pstride + it) * 8 + e] = (unsigned short)m;
-    img[(size_t)(2 * pstride + it) * 8 + e] = (unsigned short)l;
-}
 #define PN_DPP_MAX(m, ctrl) fmaxf(m, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(m), ctrl, 0xF, 0xF, false)))
-__device__ __forceinline__ void pnf_put_latent(PnH2*, uint4* __restrict__ sZ, int pstride, int i, int k, float v) {
+__device__ __forceinline__ void pnf_put_latent(uint4* __restrict__ sZ, int pstride, int i, int k, float v) {
     // the row's largest |z|: its 32 values sit in one half of a wave -- four DPP steps inside each row of 16 lanes, one exchange between rows
     float m = fabsf(v);
     m = PN_DPP_MAX(m, 0xB1);                                     // quad_perm [1,0,3,2]
@@ -1656,12 +1513,12 @@ __global__ void vposer_fold_dz_kernel(const float* __restrict__ part, size_t par
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The fused VPoser kernels on the split format VpF (= PnF: two scaled fp16 planes, r5; three bf16 planes until then) (same decomposition: 16 rows x one quarter of the hidden columns
+// The fused VPoser kernels on the split format VpF (= PnF) (same decomposition: 16 rows x one quarter of the hidden columns
 // per workgroup, four partial outputs / four partial latent gradients; see vposer_fwd_fused_kernel / vposer_bwd_fused_kernel).
 struct VPoserPanels3 {
     PanelB3 w1, w2, w3, w3t, w2t, w1t;
     const float *b1 = nullptr, *b2 = nullptr, *b3 = nullptr;
-    // PnH2: what bounds a hidden row from the row before it -- |x W + b| <= c max|x| + bmax with c = the largest column 1-norm of W --
+    // what bounds a hidden row from the row before it -- |x W + b| <= c max|x| + bmax with c = the largest column 1-norm of W --
     // so every row's power-of-two scale follows from its latent's (its output gradient's) largest entry without a reduction
     float c1 = 0.f, b1max = 0.f, c2 = 0.f, b2max = 0.f, c3t = 0.f, c2t = 0.f;
 };
@@ -1693,8 +1550,8 @@ __global__ __launch_bounds__(512) void vposer_fwd_split3_kernel(VPoserPanels3 P,
     int rblk = (int)(blockIdx.x >> 2);
     if (rblk >= two.nb1) { rblk -= two.nb1; row_lo = two.row2_lo; row_hi = two.row2_hi; }
     const int q = blockIdx.x & 3, r0 = row_lo + rblk * 16;
-    PnRing3T<1, VP3_PF2, VpF> rg2;
-    PnRing3T<1, 2, VpF> rg3;
+    PnRing3T<1, VP3_PF2> rg2;
+    PnRing3T<1, 2> rg3;
     // the biases (and column scales) of all three layers, requested before the first barrier (the compiler does not move a load across
     // one): fetched where they are used -- after each layer's products -- every tile's bias was a round trip of its own
     float4 bias1[4];
@@ -1712,17 +1569,17 @@ __global__ __launch_bounds__(512) void vposer_fwd_split3_kernel(VPoserPanels3 P,
         const uint4* bf[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) { acc[t] = VpF::zero(); bf[t] = P.w1.f + (size_t)(wave * 4 + t) * P.w1.nst * NP * 64; }
-        PnRing3T<4, 1, VpF> rg1;
-        panel3_prefetch_t<4, 1, VpF>(rg1, bf, 1, lane);
+        PnRing3T<4, 1> rg1;
+        panel3_prefetch_t<4, 1>(rg1, bf, 1, lane);
         if (ds.on)                                         // (wave-uniform) the latent rows after the pending optimiser step, straight into the image
-            pnf_put_latent((VpF*)nullptr, sZ, VP3_PZ, tid >> 5, tid & 31, vp_deferred_latent(ds, r0, row_hi, tid));
+            pnf_put_latent(sZ, VP3_PZ, tid >> 5, tid & 31, vp_deferred_latent(ds, r0, row_hi, tid));
         else
             VpF::stage<512, 1, 1>(sZ, 0, Z, ldx, r0, row_hi, 0, VP_Z, VP_Z, tid);
         __syncthreads();
-        panel3_mma_t<4, 1, VpF>(sZ, VP3_PZ, rg1, 1, acc, lane);
+        panel3_mma_t<4, 1>(sZ, VP3_PZ, rg1, 1, acc, lane);
         {
             const uint4* bf2 = P.w2.f + (size_t)(q * 8 + wave) * P.w2.nst * NP * 64;
-            panel3_prefetch_t<1, VP3_PF2, VpF>(rg2, &bf2, VP_H / 32, lane);
+            panel3_prefetch_t<1, VP3_PF2>(rg2, &bf2, VP_H / 32, lane);
         }
         const float zis = VpF::row_isc(sZ, VP3_PZ, j);
         bnd1 = P.c1 * (16384.f * zis) + P.b1max;           // >= every |H1| of row j (2^14 zis >= its largest |z|)
@@ -1733,7 +1590,7 @@ __global__ __launch_bounds__(512) void vposer_fwd_split3_kernel(VPoserPanels3 P,
             const float4 bias = bias1[t];
             const f32x4_t o = VpF::value(acc[t], zis, cs1[t]);
             const float4 v = make_float4(vp_lrelu(o[0] + bias.x), vp_lrelu(o[1] + bias.y), vp_lrelu(o[2] + bias.z), vp_lrelu(o[3] + bias.w));
-            pnf_lds_store4((VpF*)nullptr, sH1, VP3_PH, n4, j, v, s1);
+            pnf_lds_store4(sH1, VP3_PH, n4, j, v, s1);
             if ((n4 / VP_QW) == q && r0 + j < row_hi) ((unsigned char*)H1)[(size_t)(r0 + j) * VP3_MROW + (n4 >> 2)] = vp3_signs(v);
         }
     }
@@ -1742,23 +1599,23 @@ __global__ __launch_bounds__(512) void vposer_fwd_split3_kernel(VPoserPanels3 P,
     {   // layer 2, this quarter's 128 columns (one tile per wave), K = 512 = 16 steps
         VpF::Acc acc = VpF::zero();
         const int tile = q * 8 + wave;
-        panel3_mma_t<1, VP3_PF2, VpF>(sH1, VP3_PH, rg2, VP_H / 32, &acc, lane);
+        panel3_mma_t<1, VP3_PF2>(sH1, VP3_PH, rg2, VP_H / 32, &acc, lane);
         {
             const uint4* bf3 = P.w3.f + ((size_t)wave * P.w3.nst + q * (VP_QW / 32)) * NP * 64;
-            panel3_prefetch_t<1, 2, VpF>(rg3, &bf3, VP_QW / 32, lane);
+            panel3_prefetch_t<1, 2>(rg3, &bf3, VP_QW / 32, lane);
         }
         VpF::pow2(P.c2 * bnd1 + P.b2max, s2, is2);
         const int n4 = tile * 16 + 4 * g;
         const float4 bias = bias2;
         const f32x4_t o = VpF::value(acc, is1, cs2);
         const float4 v = make_float4(vp_lrelu(o[0] + bias.x), vp_lrelu(o[1] + bias.y), vp_lrelu(o[2] + bias.z), vp_lrelu(o[3] + bias.w));
-        pnf_lds_store4((VpF*)nullptr, sH2, VP3_PQ, n4 - q * VP_QW, j, v, s2);
+        pnf_lds_store4(sH2, VP3_PQ, n4 - q * VP_QW, j, v, s2);
         if (r0 + j < row_hi) ((unsigned char*)H2)[(size_t)(r0 + j) * VP3_MROW + (n4 >> 2)] = vp3_signs(v);
     }
     __syncthreads();
     {   // output layer: this quarter's K-slice (128 = 4 steps) of all 126 (128) columns
         VpF::Acc acc = VpF::zero();
-        panel3_mma_t<1, 2, VpF>(sH2, VP3_PQ, rg3, VP_QW / 32, &acc, lane);
+        panel3_mma_t<1, 2>(sH2, VP3_PQ, rg3, VP_QW / 32, &acc, lane);
         const f32x4_t o = VpF::value(acc, is2, cs3);
         const int n4 = wave * 16 + 4 * g, row = r0 + j;
         if (row < row_hi) {
@@ -1794,8 +1651,8 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
     float* const sred = (float*)(sdH1 + NP * VP3_PH);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
     const int q = bid & 3, r0 = row_lo + (int)(bid >> 2) * 16;
-    PnRing3T<4, 2, VpF> rgB;
-    PnRing3T<1, 2, VpF> rgC;
+    PnRing3T<4, 2> rgB;
+    PnRing3T<1, 2> rgC;
     // the forward activations whose signs mask this wave's tiles, requested before the first barrier (rows clamped:
     // unconditional loads).  Fetched after each layer's products they were five dependent round trips on cold data.
     const size_t hrow = (size_t)min(r0 + j, row_hi - 1) * VP3_MROW;          // (sign bytes: vp3_signs)
@@ -1810,18 +1667,18 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
         VpF::Acc acc = VpF::zero();
         const int tile = q * 8 + wave;
         const uint4* bf = P.w3t.f + (size_t)tile * P.w3t.nst * NP * 64;
-        PnRing3T<1, 2, VpF> rgA;
-        panel3_prefetch_t<1, 2, VpF>(rgA, &bf, 4, lane);
+        PnRing3T<1, 2> rgA;
+        panel3_prefetch_t<1, 2>(rgA, &bf, 4, lane);
         if (tail.lg_spread && bid < (unsigned)LROW && wave == 0)     // (wave-uniform) one logged term: ScaleTail::lg_spread
             loss_rows_reduce_slot(tail.lg.rows, tail.row0, tail.lg.n, tail.lg.mask, tail.lg.assign, tail.lg.losses, (int)bid, lane);
         VpF::stage<512, 1, 1>(sdO, 0, dO, ODIM, r0, row_hi, 0, ODIM, 128, tid);
         __syncthreads();
-        panel3_mma_t<1, 2, VpF>(sdO, VP3_PQ, rgA, 4, &acc, lane);
+        panel3_mma_t<1, 2>(sdO, VP3_PQ, rgA, 4, &acc, lane);
         {
             const uint4* bfb[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) bfb[t] = P.w2t.f + ((size_t)(wave + 8 * t) * P.w2t.nst + q * (VP_QW / 32)) * NP * 64;
-            panel3_prefetch_t<4, 2, VpF>(rgB, bfb, VP_QW / 32, lane);
+            panel3_prefetch_t<4, 2>(rgB, bfb, VP_QW / 32, lane);
         }
         const float dois = VpF::row_isc(sdO, VP3_PQ, j);
         bd2 = P.c3t * (16384.f * dois);                   // >= every |dH2| of row j
@@ -1829,7 +1686,7 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
         const f32x4_t o = VpF::value(acc, dois, csA);
         const int n4 = tile * 16 + 4 * g;
         const unsigned h = hm2;
-        pnf_lds_store4((VpF*)nullptr, sdH2, VP3_PQ, n4 - q * VP_QW, j,
+        pnf_lds_store4(sdH2, VP3_PQ, n4 - q * VP_QW, j,
                        make_float4(o[0] * ((h & 1u) ? 1.f : 0.2f), o[1] * ((h & 2u) ? 1.f : 0.2f), o[2] * ((h & 4u) ? 1.f : 0.2f),
                                    o[3] * ((h & 8u) ? 1.f : 0.2f)), sd2);
     }
@@ -1839,10 +1696,10 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
         VpF::Acc acc[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[t] = VpF::zero();
-        panel3_mma_t<4, 2, VpF>(sdH2, VP3_PQ, rgB, VP_QW / 32, acc, lane);
+        panel3_mma_t<4, 2>(sdH2, VP3_PQ, rgB, VP_QW / 32, acc, lane);
         {
             const uint4* bfc = P.w1t.f + ((size_t)(wave & 1) * P.w1t.nst + (wave >> 1) * 4) * NP * 64;
-            panel3_prefetch_t<1, 2, VpF>(rgC, &bfc, 4, lane);
+            panel3_prefetch_t<1, 2>(rgC, &bfc, 4, lane);
         }
         VpF::pow2(P.c2t * bd2, sd1, isd1);
 #pragma unroll
@@ -1850,7 +1707,7 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
             const int n4 = (wave + 8 * t) * 16 + 4 * g;
             const unsigned h = hm1[t];
             const f32x4_t o = VpF::value(acc[t], isd2, csB[t]);
-            pnf_lds_store4((VpF*)nullptr, sdH1, VP3_PH, n4, j,
+            pnf_lds_store4(sdH1, VP3_PH, n4, j,
                            make_float4(o[0] * ((h & 1u) ? 1.f : 0.2f), o[1] * ((h & 2u) ? 1.f : 0.2f),
                                        o[2] * ((h & 4u) ? 1.f : 0.2f), o[3] * ((h & 8u) ? 1.f : 0.2f)), sd1);
         }
@@ -1859,7 +1716,7 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
     {   // partial d latent = partial dH1 x W1: 2 column tiles x 4 K-slices (128 columns = 4 steps each), slices summed in order
         VpF::Acc acc = VpF::zero();
         const int tile = wave & 1, ks = wave >> 1;
-        panel3_mma_t<1, 2, VpF>(sdH1 + (size_t)ks * 4 * 64, VP3_PH, rgC, 4, &acc, lane);
+        panel3_mma_t<1, 2>(sdH1 + (size_t)ks * 4 * 64, VP3_PH, rgC, 4, &acc, lane);
         const f32x4_t o = VpF::value(acc, isd1, csC);
         *(float4*)(sred + (size_t)(ks * 2 + tile) * 256 + lane * 4) = make_float4(o[0], o[1], o[2], o[3]);
     }

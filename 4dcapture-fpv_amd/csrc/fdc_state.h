@@ -308,15 +308,15 @@ int panel_pack_dev(const float* src, size_t src_floats, long sk, long sn, int K,
     hipLaunchKernelGGL(panel_pack_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, 0, src, sk, sn, K, N, nt, ns, (float4*)out.p);
     return (int)hipGetLastError();
 }
-// ... -> the split format PnF (planes + the column tiles' inverse scales)
+// ... -> the split format PnH2 (planes + the column tiles' inverse scales)
 int pnf_pack_dev(const float* src, size_t src_floats, long sk, long sn, int K, int N, DevBuf<unsigned>& out, DevBuf<float>& isc, int* ntile,
                  int* nst) {
     const int nt = (N + 15) / 16, ns = (K + 31) / 32;
-    if (PnF::NP != 2 || panel_pack_on_host() || (sk != 1 && sn != 1)) {
+    if (panel_pack_on_host() || (sk != 1 && sn != 1)) {
         std::vector<float> h(src_floats), sc;
         std::vector<unsigned> p3;
         HIP_TRY(hipMemcpy(h.data(), src, src_floats * sizeof(float), hipMemcpyDeviceToHost));
-        PnF::pack(h.data(), sk, sn, K, N, p3, sc, ntile, nst);
+        PnH2::pack(h.data(), sk, sn, K, N, p3, sc, ntile, nst);
         HIP_TRY(out.upload(p3.data(), p3.size()));
         return (int)isc.upload(sc.data(), sc.size());
     }
@@ -510,7 +510,7 @@ int build_skin_set(fdcap_ctx* c, const std::vector<int64_t>& ids, SkinSet* out) 
         out->pn_fwdS.f = (const uint4*)out->pn_fwdS_f.p; out->pn_fwdS.isc = out->pn_fwdS_s.p;
     }
     tr.mark("permuted forward panel");
-    if (nv > 0) {                                 // ... and the data-gradient operand (one LDS image up to K = 1696: panel_gemm3 / _rb2k; beyond: panel_gemm3_kloop)
+    if (nv > 0) {                                 // ... and the data-gradient operand (one LDS image up to K = 2528: panel_gemm3 / _rb2k / _ksw; beyond: panel_gemm3_kloop)
         int e = pnf_pack_dev(pd, pd_floats, 1, ldp, 3 * nv, NPFX, out->pn_bwd3_f, out->pn_bwd3_s, &out->pn_bwd3.ntile, &out->pn_bwd3.nst);
         if (e) return e;
         out->pn_bwd3.f = (const uint4*)out->pn_bwd3_f.p; out->pn_bwd3.isc = out->pn_bwd3_s.p;
@@ -530,7 +530,7 @@ hipError_t blend_forward(const SkinSet& ss, const float* PF, int M, float* Voff,
     TraceRange tr_("fdcap:blend_fwd(K8)");
     if (gemm_split3_enabled() && ss.pn_fwd3.f) return panel_gemm3(PF, NPFX, M, NPFX, ss.pn_fwd3, Voff, 3 * ss.nv, 3 * ss.nv, st);
     if (ss.pn_fwd.f) return panel_gemm(PF, NPFX, M, NPFX, ss.pn_fwd, Voff, 3 * ss.nv, 3 * ss.nv, st);
-    return gemm_f32(false, EPI_STORE, PF, NPFX, ss.posedirs.p, ss.ldp, Voff, 3 * ss.nv, M, 3 * ss.nv, NPFX, nullptr, 0, st);
+    return hipSuccess;                            // no vertices (build_skin_set packs both panels for every set with nv > 0): nothing to do
 }
 
 // its data gradient: dPF[M, 496] = dVoff[M, 3 nv] x [posedirs ; shapedirs^T]^T.  *split (optional): the product was left as TWO partial
@@ -555,7 +555,9 @@ hipError_t blend_backward(const SkinSet& ss, const float* dV, int M, float* dPF,
         }
     }
     if (ss.pn_bwd.f) return panel_gemm(dV, K, M, K, ss.pn_bwd, dPF, NPFX, NPFX, st);
-    return gemm_f32(true, EPI_STORE, dV, K, ss.posedirs.p, ss.ldp, dPF, NPFX, M, NPFX, K, nullptr, 0, st);
+    // FDCAP_GEMM_SPLIT3=0 and 3 nv > PANEL_MAX_K (more than 2048 vertices: the full mesh, an all-vertices contact set): no fp32 panel of
+    // the operand is kept (build_skin_set) -- the product reads the set's blend matrix as it lies, [496, ldp]
+    return gemm_f32_nt(dV, K, ss.posedirs.p, ss.ldp, dPF, NPFX, M, NPFX, K, st);
 }
 
 // VPoser decoder forward for rows [row_lo, row_hi) of X (latent read in place at column latent_off): H1, H2 and the four

@@ -50,14 +50,13 @@ def test_vposer_decode_backward_matches_autograd(small, B, output_type):
     _close(zg.grad.cpu().numpy(), zt.grad.numpy())
 
 
-@pytest.mark.parametrize("B,use_verts,use_joints", [(3, True, True), (40, True, False), (5, False, True)])
-def test_body_model_backward_matches_autograd(small, B, use_verts, use_joints):
-    bm, vp, ctx = small
+def _body_model_case(bm, ctx, B, use_verts, use_joints):
+    V = bm.v_template.shape[0]
     rng = np.random.default_rng(B)
     inp = {"global_orient": rng.standard_normal((B, 3)) * 0.8, "body_pose": rng.standard_normal((B, 63)) * 0.4,
            "betas": rng.standard_normal((B, 10)) * 0.5, "left_hand_pose": rng.standard_normal((B, 12)) * 0.3,
            "right_hand_pose": rng.standard_normal((B, 12)) * 0.3, "transl": rng.standard_normal((B, 3))}
-    wv, wj = rng.standard_normal((B, 300, 3)), rng.standard_normal((B, 55, 3))
+    wv, wj = rng.standard_normal((B, V, 3)), rng.standard_normal((B, 55, 3))
     t = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in inp.items()}
     out = SMPLXOracle(bm, torch.float64)(return_verts=True, **t)
     loss = 0
@@ -77,6 +76,68 @@ def test_body_model_backward_matches_autograd(small, B, use_verts, use_joints):
     np.testing.assert_allclose(got.vertices.detach().cpu().numpy(), out.vertices.detach().numpy(), atol=3e-5)
     for k in inp:
         _close(g[k].grad.cpu().numpy(), t[k].grad.numpy(), k)
+
+
+@pytest.mark.parametrize("B,use_verts,use_joints", [(3, True, True), (40, True, False), (5, False, True)])
+def test_body_model_backward_matches_autograd(small, B, use_verts, use_joints):
+    bm, vp, ctx = small
+    _body_model_case(bm, ctx, B, use_verts, use_joints)
+
+
+# Exact-fp32 products (FDCAP_GEMM_SPLIT3=0) on a mesh of more than 2048 vertices: the blend product's data gradient has K = 3 V >
+# 6144 columns, no fp32 panel of its operand is kept, and gemm_f32_nt (csrc/fdc_gemm.h) serves it -- one of four kernels by row count
+# (16x16 tiles while 16 ceil(B / 32) < 256, i.e. up to 480 rows) and operand alignment (3 V a multiple of 4: float4 staging).  The
+# smallest shapes that select each; K is ragged against the 128- / 256-deep slabs in all of them, B = 5 leaves a partial 16-row tile
+# and B = 481 a 32-row tile that holds one row.
+EXACT_BIG_K_CASES = {(2052, 5): "gemm_f32_mfma_ksplit16_v4_kernel", (2051, 5): "gemm_f32_mfma_ksplit16_kernel",
+                     (2052, 481): "gemm_f32_mfma_ksplit_v4_kernel", (2051, 481): "gemm_f32_mfma_ksplit_kernel"}
+_EXACT_BIG_K_CHILD = r"""
+import ctypes, json, sys
+sys.path.insert(0, %r)
+import fdcap_amd
+from fdcap_amd import capi, synth
+from tests.test_gpu_ops_autograd import EXACT_BIG_K_CASES, _body_model_case
+res = {}
+buf = ctypes.create_string_buffer(4096)
+for V, B in EXACT_BIG_K_CASES:
+    bm = synth.make_body_model(V, seed=0)
+    ctx = capi.Context(bm, synth.make_vposer(seed=1))
+    ctx.lib.fdcap_debug_kernel_forms(buf, 4096, 1)             # (reset)
+    err = None
+    try:
+        _body_model_case(bm, ctx, B, True, False)
+    except AssertionError as e:
+        err = str(e)[-1500:]
+    ctx.lib.fdcap_debug_kernel_forms(buf, 4096, 0)
+    res["%%d-%%d" %% (V, B)] = {"forms": buf.value.decode(), "error": err}
+    ctx.close()
+print("RESULT " + json.dumps(res))
+"""
+
+
+@pytest.fixture(scope="module")
+def exact_big_k():
+    """All four cases in ONE child process (the switch is read once per process); each test below asserts its own case."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, "-c", _EXACT_BIG_K_CHILD % root], env=dict(os.environ, FDCAP_GEMM_SPLIT3="0"), capture_output=True,
+                       text=True, timeout=600, cwd=root)
+    line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")]
+    assert p.returncode == 0 and line, p.stderr[-2000:]
+    return json.loads(line[-1][7:])
+
+
+@pytest.mark.parametrize("V,B", list(EXACT_BIG_K_CASES))
+def test_body_model_backward_matches_autograd_on_exact_fp32_beyond_the_panels(exact_big_k, V, B):
+    """test_body_model_backward_matches_autograd's body and bars (the oracle's fp64 autograd, _close) where the data gradient of the
+    blend product leaves the panels: each case must have run the kernel of gemm_f32_nt it was sized for."""
+    r = exact_big_k["%d-%d" % (V, B)]
+    print(V, B, r["forms"])
+    assert EXACT_BIG_K_CASES[(V, B)] in r["forms"].split(";"), r["forms"]
+    assert not [f for f in r["forms"].split(";") if f.startswith("gemm_f32_") and f != EXACT_BIG_K_CASES[(V, B)]], r["forms"]
+    assert r["error"] is None, r["error"]
 
 
 class ReferenceShapedFitting:

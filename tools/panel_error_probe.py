@@ -1,5 +1,5 @@
 """Measured error of the split product forms against fp64, as a fraction of sum |a||b| (per output element, worst and rms):
-well-scaled normal data and badly scaled rows / columns.  FDCAP_LIB selects the build (PnH2 default, -DFDC_PN_H2=0: three bf16 planes)."""
+well-scaled normal data and badly scaled rows / columns.  FDCAP_LIB selects the build."""
 import ctypes
 import os
 import sys

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-workgroup phase times (s_memtime) of the panel kernels; needs the -DFDC_PN_TIMING build (FDCAP_LIB).
 The stamps live in the exact-fp32 kernels (panel_gemm_kernel, panel_gemm_wide_kernel, vposer_*_fused_kernel), the FDCAP_GEMM_SPLIT3=0
-twins of the default three-way-split ones: this tool selects them."""
+twins of the default split-format ones: this tool selects them."""
 import ctypes, os, sys
 os.environ.setdefault("FDCAP_GEMM_SPLIT3", "0")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
