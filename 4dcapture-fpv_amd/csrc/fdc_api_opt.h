@@ -138,10 +138,7 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
     const ContactFwdPlan pl = plan_contact_forward(nl, nc, NPFX, PNF, blend_done, c->contact.pn_fwdS.f != nullptr, smf.vpack != nullptr, smf.K, smf.ja_hi, sw);
     if (pl.form == F_BLEND_SKIN_FWD) {
         static std::atomic<uint64_t> attr{0};                  // per DEVICE: the attribute belongs to one device's code object
-        if (fdc_attr_needed(attr)) {
-            HIP_TRY(hipFuncSetAttribute((const void*)blend_skin_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.max_lds));
-            fdc_attr_done(attr);
-        }
+        HIP_TRY(fdc_allow_lds(attr, pl.max_lds, {(const void*)blend_skin_fwd_kernel}));
         note_form(form_name(pl.form));
         hipLaunchKernelGGL(blend_skin_fwd_kernel, dim3(pl.grid), dim3(pl.block), pl.lds, st, o->PF.p, nl,
                            c->contact.pn_fwdS, smf, nc, smf.ja_hi, o->X.p, XDIM, X_TRANSL, o->A.p, o->M.p, o->scale.p, 2, o->Voff.p, o->Vw.p,

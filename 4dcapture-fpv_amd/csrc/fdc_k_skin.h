@@ -97,9 +97,9 @@ __global__ __launch_bounds__(768) void blend_skin_fwd_kernel(const float* __rest
     float* const sVP = sT + 32 * 4;                             // [2][64] float4
     float* const sX = sVP + 2 * 64 * 4;
     const float* const PFr = PF + (size_t)row0 * NPFX;
-    PnRing3<2> rg;
+    PnRing<PnF, 1, 2> rg;
     const int tile = cb * 12 + wave;
-    panel3_prefetch<2>(rg, B.f + (size_t)min(tile, B.ntile - 1) * B.nst * PNF * 64, nst, lane);
+    panel_prefetch<PnF, 1, 2>(rg, {B.f + (size_t)min(tile, B.ntile - 1) * B.nst * PNF * 64}, nst, lane);
     const f32x4_t ts = PnF::tile_isc(B, tile, g);
     // the same batch: the frames' skinning transforms (joints < ja), world transforms and translations by LDS-DMA, this thread's
     // vertex constants into registers (a thread serves vertex tid & 63 of the block for every frame it is dealt)
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(768) void blend_skin_fwd_kernel(const float* __rest
     PnF::stage<768, 2, 2>(bs_lds, img, PFr, NPFX, m0, M, 0, K, kpad, tid);
     __syncthreads();
     PnF::Acc acc[2] = {PnF::zero(), PnF::zero()};
-    if (tile < B.ntile) panel3_mma<2, 2>(bs_lds, pstride, img, rg, nst, acc, lane);
+    if (tile < B.ntile) panel_mma<PnF, 2, 1, 2, PnOrder::StaticPinLds>(bs_lds, {pstride, img}, rg, nst, acc, lane);
     {   // component c = wave % 3 of vertices 16 (wave / 3) + 4 g .. + 3, frames 16 rb + j
         const int c = wave % 3, vg = wave / 3;
 #pragma unroll

@@ -27,6 +27,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "fdc_forms.h"
@@ -35,10 +37,21 @@
 
 namespace fdc {
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a property of ONE device's code object: one bit per device ordinal, set after
-// the attribute took (two threads racing set it twice: harmless)
-inline bool fdc_attr_needed(const std::atomic<uint64_t>& mask) { int d = 0; (void)hipGetDevice(&d); return !(mask.load() & (1ull << (d & 63))); }
-inline void fdc_attr_done(std::atomic<uint64_t>& mask) { int d = 0; (void)hipGetDevice(&d); mask.fetch_or(1ull << (d & 63)); }
+// Lets the kernel(s) take `bytes` of dynamic LDS on the current device.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a property
+// of ONE device's code object: `mask` (the launch site's own static) has one bit per device ordinal, set after the attribute took
+// (two threads racing set it twice: harmless)
+inline hipError_t fdc_allow_lds(std::atomic<uint64_t>& mask, size_t bytes, std::initializer_list<const void*> kernels) {
+    int d = 0;
+    (void)hipGetDevice(&d);
+    const uint64_t bit = 1ull << (d & 63);
+    if (mask.load() & bit) return hipSuccess;
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    mask.fetch_or(bit);
+    return hipSuccess;
+}
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
@@ -112,10 +125,8 @@ __device__ __forceinline__ void panel_stage(float* __restrict__ sA, const float*
     }
 }
 
-// acc[t] += A[16 x 16 nss] * B_t for T tiles that share the A block.  sA: image at the first super-step; bf[t]: tile t's
-// fragments at the first super-step (without the lane offset).  PF fragments per tile in flight.
-//
-// The fragment ring: loads in the main loop are unconditional and pinned by a scheduling barrier right after their issue.
+// The fragment ring (PnRing, panel_prefetch, panel_mma below; PF fragments per tile in flight): loads in the main loop are
+// unconditional and pinned by a scheduling barrier right after their issue.
 // Loads under wave-uniform branches make hipcc wait vmcnt(0) in every super-step; unpinned, its scheduler sinks each load
 // to just before its use -- either way one exposed L2 round trip per 4 MFMAs (the blend product ran 27 us instead of ~12).
 // (Inline-asm loads with hand-counted s_waitcnt were tried and are wrong here: the ring is loop-carried, and the register
@@ -142,124 +153,132 @@ __device__ __forceinline__ f32x4_t pn_step(float4 a, f32x4_t b, f32x4_t acc) {
 }
 __device__ __forceinline__ float4 pn_f4(f32x4_t v) { return make_float4(v[0], v[1], v[2], v[3]); }
 
-// Two register sets, each PF super-steps deep: set A is consumed while set B is being filled and vice versa, so no fragment
+// Operand format of the exact-fp32 chain, as the one product loop (panel_mma) sees a format -- PnH2 below is the other one:
+//   Frag / Stream   a static fragment's element type; a lane's handle on one tile's fragment stream
+//   AFrag / BFrag   what a lane holds of one step: the LDS block's fragment, the static operand's
+//   LdsElem / Lds   the LDS images' element type and their geometry (RB images `img` elements apart); the loop gets the first image at
+//                   the first step as a __restrict__ pointer of its own
+//   load_a          the LDS fragment of (row block, step, lane);   load_b   the static fragment of (stream, step)
+//   Acc / step      one step's MFMAs on one accumulator
+// One step = one super-step: 16 columns of K, four v_mfma_f32_16x16x4_f32.
+struct PnF32 {
+    typedef f32x4_t Acc;
+    typedef float4 Frag;
+    typedef float4 AFrag;
+    typedef f32x4_t BFrag;
+    typedef PnStream Stream;
+    typedef float LdsElem;
+    struct Lds { int img; };
+    static __device__ __forceinline__ Stream stream(const Frag* tile_base, int lane) { return pn_stream(tile_base, lane); }
+    static __device__ __forceinline__ AFrag load_a(const LdsElem* sA, const Lds& l, int rb, int step, int lane) {
+        return pn_load_a(sA + (size_t)rb * l.img + (size_t)step * 256 + lane * 4);
+    }
+    static __device__ __forceinline__ BFrag load_b(Stream st, int step) { return pn_load_b(st, step); }
+    static __device__ __forceinline__ Acc step(const AFrag& a, const BFrag& b, Acc acc) { return pn_step(a, b, acc); }
+};
+
+// Two register sets, each PF steps deep: set A is consumed while set B is being filled and vice versa, so no fragment
 // register is redefined while its previous value is live and the ring needs no copies at the loop's back edge (with one
 // set hipcc rotates the registers there and has to drain the queue once per turn).  The first set is loaded by
 // panel_prefetch -- issued BEFORE the barrier / staging that precedes the product, so the first L2 round trip is hidden.
-template <int T, int PF>
-struct PnRing { f32x4_t bA[T][PF]; PnStream st[T]; };
+// F: the operand format (PnF32, PnH2); T tiles' streams share the LDS block(s).
+template <class F, int T, int PF>
+struct PnRing { typename F::BFrag bA[T][PF]; typename F::Stream st[T]; };
 
-template <int T, int PF>
-__device__ __forceinline__ void panel_prefetch(PnRing<T, PF>& rg, const float4* const* bf, int nss, int lane) {
-    const int last = nss - 1;
+// bf[t]: tile t's fragments at the first step (without the lane offset)
+template <class F, int T, int PF>
+__device__ __forceinline__ void panel_prefetch(PnRing<F, T, PF>& rg, const typename F::Frag* const (&bf)[T], int nst, int lane) {
+    const int last = nst - 1;
 #pragma unroll
-    for (int t = 0; t < T; ++t) rg.st[t] = pn_stream(bf[t], lane);
+    for (int t = 0; t < T; ++t) rg.st[t] = F::stream(bf[t], lane);
 #pragma unroll
     for (int p = 0; p < PF; ++p)
 #pragma unroll
-        for (int t = 0; t < T; ++t) rg.bA[t][p] = pn_load_b(rg.st[t], min(p, last));
+        for (int t = 0; t < T; ++t) rg.bA[t][p] = F::load_b(rg.st[t], min(p, last));
 }
 
-template <int T, int PF>
-__device__ __forceinline__ void panel_mma(const float* __restrict__ sA, PnRing<T, PF>& rg, int nss, f32x4_t* acc, int lane) {
-    f32x4_t (&bA)[T][PF] = rg.bA;
-    f32x4_t bB[T][PF];
-    PnStream (&st)[T] = rg.st;
-    const int last = nss - 1;
-    float4 a = pn_load_a(sA + lane * 4);                             // the A fragment runs one super-step ahead of its MFMAs
-    int s = 0;
-    for (; s + 2 * PF <= nss; s += 2 * PF) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const float4 a_next = pn_load_a(sA + (size_t)(s + p + 1) * 256 + lane * 4);
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                bB[t][p] = pn_load_b(st[t], s + PF + p);
-                pn_pin();
-                acc[t] = pn_step(a, bA[t][p], acc[t]);
-            }
-            a = a_next;
-        }
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            const float4 a_next = pn_load_a(sA + (size_t)min(s + PF + p + 1, last) * 256 + lane * 4);
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                bA[t][p] = pn_load_b(st[t], min(s + 2 * PF + p, last));
-                pn_pin();
-                acc[t] = pn_step(a, bB[t][p], acc[t]);
-            }
-            a = a_next;
-        }
-    }
-    // tail: fewer than 2 PF super-steps; set A holds the first PF of them
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-        if (s + p < nss) {
-            const float4 a_next = pn_load_a(sA + (size_t)min(s + p + 1, last) * 256 + lane * 4);
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                bB[t][p] = pn_load_b(st[t], min(s + PF + p, last));
-                acc[t] = pn_step(a, bA[t][p], acc[t]);
-            }
-            a = a_next;
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < PF - 1; ++p) {
-        if (s + PF + p < nss) {
-            const float4 a_next = pn_load_a(sA + (size_t)min(s + PF + p + 1, last) * 256 + lane * 4);
-#pragma unroll
-            for (int t = 0; t < T; ++t) acc[t] = pn_step(a, bB[t][p], acc[t]);
-            a = a_next;
-        }
-    }
-}
+// Where inside a step of the main loop the two requests -- the NEXT step's LDS fragments, the static fragments PF steps ahead --
+// and the pin stand.  The MFMAs and their order are the same in all three, so the order changes no bit; it does change hipcc's
+// schedule and register count (NOTES, Round 10), and each is what its kernels were tuned with.  Whether one order serves all is
+// an open tuning question.
+enum class PnOrder {
+    // static fragment -> pin -> next LDS fragments -> MFMAs.  The one-tile streams of the blend products: panel_gemm_kernel,
+    // panel_gemm_wide_kernel, panel_gemm3_kernel, panel_gemm3_rb2_kernel, panel_gemm3_rb2k_kernel, panel_gemm3_wide_kernel,
+    // blend_skin_fwd_kernel
+    StaticPinLds,
+    // next LDS fragment, then per tile: static fragment -> pin -> that tile's MFMAs.  The fused VPoser kernels' layers:
+    // vposer_fwd_fused_kernel, vposer_bwd_fused_kernel, vposer_fwd_split3_kernel, vposer_bwd_split3_kernel
+    LdsTilePin,
+    // next LDS fragments -> all tiles' static fragments -> pin -> all MFMAs.  The K-split products: panel_gemm3_ksw_kernel,
+    // panel_gemm3_kloop_kernel
+    LdsStaticPin,
+};
 
-// RB row blocks of 16 share one B fragment stream (wide outputs: B traffic / RB).  sA: RB images, `img` floats apart.
-template <int RB, int PF>
-__device__ __forceinline__ void panel_mma_rows(const float* __restrict__ sA, int img, PnRing<1, PF>& rg, int nss,
-                                               f32x4_t* acc, int lane) {
-    f32x4_t (&bA)[PF] = rg.bA[0];
-    f32x4_t bB[PF];
-    const PnStream st = rg.st[0];
-    const int last = nss - 1;
-    float4 a[RB];
+// acc[rb * T + t] += A_rb[16 x nst steps] * B_t: RB row blocks of 16 (LDS images) x T column tiles (fragment streams) per wave.  A
+// step's RB LDS fragments are read ONCE for T tiles and its T static fragments once for RB row blocks.  lds: the images at the first
+// step; rg: the ring panel_prefetch filled for the same nst (> 0).  The LDS fragments run one step ahead of their MFMAs.
+// Main loop: 2 PF steps per turn, loads pinned.  Tail: at most 2 PF - 1 steps, step indices clamped to the last one, not pinned.
+template <class F, int RB, int T, int PF, PnOrder ORD>
+__device__ __forceinline__ void panel_mma(const typename F::LdsElem* __restrict__ sA, const typename F::Lds lds, PnRing<F, T, PF>& rg, int nst, typename F::Acc* acc, int lane) {
+    typedef typename F::AFrag AF;
+    typedef typename F::BFrag BF;
+    BF (&bA)[T][PF] = rg.bA;
+    BF bB[T][PF];
+    const int last = nst - 1;
+    AF a[RB];
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) a[rb] = pn_load_a(sA + (size_t)rb * img + lane * 4);
-    auto step = [&](int cur, f32x4_t bb) {
+    for (int rb = 0; rb < RB; ++rb) a[rb] = F::load_a(sA, lds, rb, 0, lane);
+    // one step on use[.][p]; it requests the LDS fragments of step `next` and fill[.][p] = the static fragments of step `fs`.
+    // HEAD: the main loop's first half (pinned, both indices in range); BODY: its second half (pinned, indices clamped to the last step:
+    // the loads stay unconditional); TAIL: clamped, not pinned; DRAIN: nothing left to request from the streams
+    constexpr int HEAD = 0, BODY = 1, TAIL = 2, DRAIN = 3;
+    auto step = [&](auto mode, BF (&use)[T][PF], BF (&fill)[T][PF], int p, int fs, int next) {
+        constexpr int MODE = decltype(mode)::value;
+        constexpr bool per_tile = ORD == PnOrder::LdsTilePin, pinned = MODE == HEAD || MODE == BODY;
+        AF an[RB];
+        auto load_an = [&]() {
+            const int n = MODE == HEAD ? next : min(next, last);
 #pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            const float4 a_next = pn_load_a(sA + (size_t)rb * img + (size_t)min(cur + 1, last) * 256 + lane * 4);
-            acc[rb] = pn_step(a[rb], bb, acc[rb]);
-            a[rb] = a_next;
+            for (int rb = 0; rb < RB; ++rb) an[rb] = F::load_a(sA, lds, rb, n, lane);
+        };
+        auto load_fill = [&](int t) { fill[t][p] = F::load_b(rg.st[t], MODE == HEAD ? fs : min(fs, last)); };
+        if (ORD != PnOrder::StaticPinLds) load_an();
+        if (MODE != DRAIN && !per_tile) {
+#pragma unroll
+            for (int t = 0; t < T; ++t) load_fill(t);
+            if (pinned) pn_pin();
         }
+        if (ORD == PnOrder::StaticPinLds) load_an();
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            if (MODE != DRAIN && per_tile) {
+                load_fill(t);
+                if (pinned) pn_pin();
+            }
+#pragma unroll
+            for (int rb = 0; rb < RB; ++rb) acc[rb * T + t] = F::step(a[rb], use[t][p], acc[rb * T + t]);
+        }
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) a[rb] = an[rb];
     };
+    const std::integral_constant<int, HEAD> head;
+    const std::integral_constant<int, BODY> body;
+    const std::integral_constant<int, TAIL> tail;
+    const std::integral_constant<int, DRAIN> drain;
     int s = 0;
-    for (; s + 2 * PF <= nss; s += 2 * PF) {
+    for (; s + 2 * PF <= nst; s += 2 * PF) {
 #pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            bB[p] = pn_load_b(st, s + PF + p);
-            pn_pin();
-            step(s + p, bA[p]);
-        }
+        for (int p = 0; p < PF; ++p) step(head, bA, bB, p, s + PF + p, s + p + 1);
 #pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            bA[p] = pn_load_b(st, min(s + 2 * PF + p, last));
-            pn_pin();
-            step(s + PF + p, bB[p]);
-        }
+        for (int p = 0; p < PF; ++p) step(body, bB, bA, p, s + 2 * PF + p, s + PF + p + 1);
     }
+    // tail: fewer than 2 PF steps; set A holds the first PF of them
 #pragma unroll
-    for (int p = 0; p < PF; ++p) {
-        if (s + p < nss) {
-            bB[p] = pn_load_b(st, min(s + PF + p, last));
-            step(s + p, bA[p]);
-        }
-    }
+    for (int p = 0; p < PF; ++p)
+        if (s + p < nst) step(tail, bA, bB, p, s + PF + p, s + p + 1);
 #pragma unroll
     for (int p = 0; p < PF - 1; ++p)
-        if (s + PF + p < nss) step(s + PF + p, bB[p]);
+        if (s + PF + p < nst) step(drain, bB, bA, p, 0, s + PF + p + 1);
 }
 
 #ifdef FDC_PN_TIMING
@@ -270,7 +289,15 @@ __device__ unsigned long long g_pn_times[8192 * 8];
 #define PN_STAMP(i)
 #endif
 
-// (workgroup -> (row block, column block), XCD-aware: PnMap / panel_map, fdc_forms.h)
+// workgroup -> (row block, column block), XCD-aware: PnMap / panel_map, fdc_forms.h.  blockIdx & 7 = XCD = (row group, column
+// group), blockIdx >> 3 = slot inside the group.  on == false: a ragged group's surplus workgroup (the whole workgroup returns)
+struct PnBlock { int rbk, cbk; bool on; };
+__device__ __forceinline__ PnBlock panel_block(const PnMap& mp) {
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int r_in = mp.rfast ? slot % mp.rpg : slot / mp.cpg, c_in = mp.rfast ? slot / mp.rpg : slot % mp.cpg;
+    const int rbk = (xcd / mp.xc) * mp.rpg + r_in, cbk = (xcd % mp.xc) * mp.cpg + c_in;
+    return PnBlock{rbk, cbk, r_in < mp.rpg && c_in < mp.cpg && rbk < mp.nrb && cbk < mp.ncb};
+}
 
 // C[M, N] = A[M, K] x B.  Workgroup = 8 waves = 16 RB rows x 128 columns (a 16-column tile per wave); K in slabs of `kslab`
 // columns (multiple of 16) so any K fits the LDS.  1-D grid of 8 * rpg * cpg workgroups (PnMap).
@@ -280,10 +307,9 @@ __global__ __launch_bounds__(512) void panel_gemm_kernel(const float* __restrict
                                                          float* __restrict__ C, int ldc, int N, PnMap mp) {
     extern __shared__ __attribute__((aligned(16))) float pn_lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int r_in = mp.rfast ? slot % mp.rpg : slot / mp.cpg, c_in = mp.rfast ? slot / mp.rpg : slot % mp.cpg;
-    const int rbk = (xcd / mp.xc) * mp.rpg + r_in, cbk = (xcd % mp.xc) * mp.cpg + c_in;
-    if (r_in >= mp.rpg || c_in >= mp.cpg || rbk >= mp.nrb || cbk >= mp.ncb) return;  // ragged groups (whole workgroup)
+    const PnBlock pb = panel_block(mp);
+    if (!pb.on) return;
+    const int rbk = pb.rbk, cbk = pb.cbk;
     const int tile = cbk * 8 + wave;
     const int m0 = rbk * (16 * RB);
     const int img = kslab * 16;
@@ -295,15 +321,15 @@ __global__ __launch_bounds__(512) void panel_gemm_kernel(const float* __restrict
     const float4* const tf = B.f + (size_t)(active ? tile : 0) * B.nss * 64;
     for (int k0 = 0; k0 < K; k0 += kslab) {
         const int kn = min(kslab, K - k0), kpad = (kn + 15) & ~15;
-        PnRing<1, 4> rg;
+        PnRing<PnF32, 1, 4> rg;
         const float4* bfp = tf + (size_t)(k0 >> 4) * 64;
-        panel_prefetch<1, 4>(rg, &bfp, kpad >> 4, lane);            // in flight while the A block is staged
+        panel_prefetch<PnF32, 1, 4>(rg, {bfp}, kpad >> 4, lane);            // in flight while the A block is staged
         if (k0) __syncthreads();
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) panel_stage<512>(pn_lds + (size_t)rb * img, A, lda, m0 + 16 * rb, M, k0, kn, kpad, tid);
         __syncthreads();
         PN_STAMP(1);
-        if (active) panel_mma_rows<RB, 4>(pn_lds, img, rg, kpad >> 4, acc, lane);
+        if (active) panel_mma<PnF32, RB, 1, 4, PnOrder::StaticPinLds>(pn_lds, {img}, rg, kpad >> 4, acc, lane);
     }
     PN_STAMP(2);
     const int n4 = tile * 16 + 4 * g;
@@ -385,8 +411,35 @@ struct PnH2 {
     static constexpr int NP = 2, SC_U4 = 4 + 4 * 12;            // 16 inverse row scales + 16 partial maxima per wave (<= 12 waves)
     struct Acc { f32x4_t h, l; };
     static __device__ __forceinline__ Acc zero() { return Acc{f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}}; }
-    static __device__ __forceinline__ Acc step(const uint4* a /*[2] planes h l of the LDS block*/, const uint4* b /*[2] of the fragment*/, Acc acc) {
-#define PN2_MMA(dst, wp, ap) dst = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(pn_f16x8, b[wp]), __builtin_bit_cast(pn_f16x8, a[ap]), dst, 0, 0, 0)
+    // the format as panel_mma sees it (see PnF32).  One step = 32 columns of K: the planes h, l of the LDS block's fragment and of the
+    // static one, three v_mfma_f32_16x16x32_f16.  Lds: plane stride `pstride`, RB images `img` apart (uint4)
+    typedef uint4 Frag;
+    struct AFrag { pn_f16x8 pl[NP]; };                          // (native vectors: copying HIP's uint4 inside a struct splits it into words)
+    typedef AFrag BFrag;
+    typedef const uint4* Stream;
+    typedef uint4 LdsElem;
+    struct Lds { int pstride, img; };
+    static __device__ __forceinline__ Stream stream(const Frag* tile_base, int lane) { return tile_base + lane; }
+    static __device__ __forceinline__ AFrag bits(const uint4* v) {
+        AFrag f;
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) f.pl[pl] = __builtin_bit_cast(pn_f16x8, v[pl]);
+        return f;
+    }
+    static __device__ __forceinline__ AFrag load_a(const LdsElem* sA, const Lds& l, int rb, int step, int lane) {
+        uint4 v[NP];
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) v[pl] = sA[(size_t)rb * l.img + (size_t)pl * l.pstride + (size_t)step * 64 + lane];
+        return bits(v);
+    }
+    static __device__ __forceinline__ BFrag load_b(Stream st, int step) {
+        uint4 v[NP];
+#pragma unroll
+        for (int pl = 0; pl < NP; ++pl) v[pl] = st[((size_t)step * NP + pl) * 64];
+        return bits(v);
+    }
+    static __device__ __forceinline__ Acc step(const AFrag& a, const BFrag& b, Acc acc) {
+#define PN2_MMA(dst, wp, ap) dst = __builtin_amdgcn_mfma_f32_16x16x32_f16(b.pl[wp], a.pl[ap], dst, 0, 0, 0)
         PN2_MMA(acc.l, 1, 0); PN2_MMA(acc.h, 0, 0); PN2_MMA(acc.l, 0, 1);
 #undef PN2_MMA
         return acc;
@@ -596,75 +649,6 @@ static_assert(PnH2::SC_U4 == PN_SC_U4, "fdc_forms.h sizes the LDS images");
 constexpr __host__ __device__ int pnf_img_u4(int kpad) { return pn_img_u4(PNF, kpad); }
 constexpr __host__ __device__ size_t pnf_lds_bytes(int kpad, int rb) { return pn_lds_bytes(PNF, kpad, rb); }
 
-// acc += A[16 x 32 nst] * B (split operands, PnF::step per 32-column step).  sA3: image at the first step (plane stride
-// `pstride` uint4); bf: the tile's fragments at the first step (no lane offset).  Two register sets of PF steps x planes, loads
-// pinned (see panel_mma).
-template <int PF>
-struct PnRing3 { uint4 bA[PF][PNF]; const uint4* st; };
-template <int PF>
-__device__ __forceinline__ void panel3_prefetch(PnRing3<PF>& rg, const uint4* bf, int nst, int lane) {
-    rg.st = bf + lane;
-    const int last = nst - 1;
-#pragma unroll
-    for (int p = 0; p < PF; ++p)
-#pragma unroll
-        for (int pl = 0; pl < PNF; ++pl) rg.bA[p][pl] = rg.st[((size_t)min(p, last) * PNF + pl) * 64];
-}
-// RB row blocks (images `img` uint4 apart) share one fragment stream
-template <int RB, int PF>
-__device__ __forceinline__ void panel3_mma(const uint4* __restrict__ sA3, int pstride, int img, PnRing3<PF>& rg, int nst, PnF::Acc* acc, int lane) {
-    uint4 (&bA)[PF][PNF] = rg.bA;
-    uint4 bB[PF][PNF];
-    const uint4* const st = rg.st;
-    const int last = nst - 1;
-    auto load_a = [&](uint4 (*a)[PNF], int step) {
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int pl = 0; pl < PNF; ++pl) a[rb][pl] = sA3[(size_t)rb * img + (size_t)pl * pstride + (size_t)step * 64 + lane];
-    };
-    auto load_b = [&](uint4* b, int step) {
-#pragma unroll
-        for (int pl = 0; pl < PNF; ++pl) b[pl] = st[((size_t)step * PNF + pl) * 64];
-    };
-    uint4 a[RB][PNF];
-    load_a(a, 0);
-    auto step = [&](const uint4* b, int next) {
-        uint4 an[RB][PNF];
-        load_a(an, next);
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            acc[rb] = PnF::step(a[rb], b, acc[rb]);
-#pragma unroll
-            for (int pl = 0; pl < PNF; ++pl) a[rb][pl] = an[rb][pl];
-        }
-    };
-    int s = 0;
-    for (; s + 2 * PF <= nst; s += 2 * PF) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            load_b(bB[p], s + PF + p);
-            pn_pin();
-            step(bA[p], s + p + 1);
-        }
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            load_b(bA[p], min(s + 2 * PF + p, last));
-            pn_pin();
-            step(bB[p], min(s + PF + p + 1, last));
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-        if (s + p < nst) {
-            load_b(bB[p], min(s + PF + p, last));
-            step(bA[p], min(s + p + 1, last));
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < PF - 1; ++p)
-        if (s + PF + p < nst) step(bB[p], min(s + PF + p + 1, last));
-}
 // a lane's four results of one tile: columns n4 .. n4 + 3 of row m
 __device__ __forceinline__ void pnf_store4(float* __restrict__ C, int ldc, int N, int m, int n4, const f32x4_t v) {
     float* dst = C + (size_t)m * ldc + n4;
@@ -685,20 +669,19 @@ __global__ __launch_bounds__(64 * NW) void panel_gemm3_kernel(const float* __res
                                                           float* __restrict__ C, int ldc, int N, PnMap mp) {
     extern __shared__ __attribute__((aligned(16))) uint4 pn3_lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int r_in = mp.rfast ? slot % mp.rpg : slot / mp.cpg, c_in = mp.rfast ? slot / mp.rpg : slot % mp.cpg;
-    const int rbk = (xcd / mp.xc) * mp.rpg + r_in, cbk = (xcd % mp.xc) * mp.cpg + c_in;
-    if (r_in >= mp.rpg || c_in >= mp.cpg || rbk >= mp.nrb || cbk >= mp.ncb) return;  // ragged groups (whole workgroup)
+    const PnBlock pb = panel_block(mp);
+    if (!pb.on) return;
+    const int rbk = pb.rbk, cbk = pb.cbk;
     const int tile = cbk * NW + wave, m0 = rbk * 16;
     const bool active = tile < B.ntile;
     const int kpad = (K + 31) & ~31, nst = kpad >> 5, pstride = (kpad >> 3) * 16;
-    PnRing3<2> rg;
-    panel3_prefetch<2>(rg, B.f + (size_t)(active ? tile : 0) * B.nst * PNF * 64, nst, lane);      // in flight while the A block is staged
+    PnRing<PnF, 1, 2> rg;
+    panel_prefetch<PnF, 1, 2>(rg, {B.f + (size_t)(active ? tile : 0) * B.nst * PNF * 64}, nst, lane);      // in flight while the A block is staged
     const f32x4_t ts = PnF::tile_isc(B, tile, g);                // (with the first fragments: at the epilogue it would be a cold round trip of its own)
     PnF::stage<64 * NW, 1, (NW == 8 ? 6 : 4)>(pn3_lds, 0, A, lda, m0, M, 0, K, kpad, tid);
     __syncthreads();
     PnF::Acc acc = PnF::zero();
-    if (active) panel3_mma<1, 2>(pn3_lds, pstride, 0, rg, nst, &acc, lane);
+    if (active) panel_mma<PnF, 1, 1, 2, PnOrder::StaticPinLds>(pn3_lds, {pstride, 0}, rg, nst, &acc, lane);
     const int n4 = tile * 16 + 4 * g, m = m0 + j;
     if (active && n4 < N && m < M) pnf_store4(C, ldc, N, m, n4, PnF::value(acc, PnF::row_isc(pn3_lds, pstride, j), ts));
 }
@@ -717,8 +700,8 @@ __global__ __launch_bounds__(768) void panel_gemm3_rb2_kernel(const float* __res
     const int ncb = (B.ntile + 11) / 12, cpg = (ncb + 7) / 8;            // column blocks of 12 tiles; per XCD
     const int kpad = (K + 31) & ~31, nst = kpad >> 5, pstride = (kpad >> 3) * 16, img = pnf_img_u4(kpad);
     if (xcd * cpg >= ncb) return;
-    PnRing3<2> rg;
-    panel3_prefetch<2>(rg, B.f + (size_t)min((xcd * cpg) * 12 + wave, B.ntile - 1) * B.nst * PNF * 64, nst, lane);
+    PnRing<PnF, 1, 2> rg;
+    panel_prefetch<PnF, 1, 2>(rg, {B.f + (size_t)min((xcd * cpg) * 12 + wave, B.ntile - 1) * B.nst * PNF * 64}, nst, lane);
     f32x4_t ts = PnF::tile_isc(B, (xcd * cpg) * 12 + wave, g);   // (requested with the fragments: see panel_gemm3_kernel)
     PnF::stage<768, 2, 2>(pn3_lds, img, A, lda, m0, M, 0, K, kpad, tid);
     __syncthreads();
@@ -726,10 +709,10 @@ __global__ __launch_bounds__(768) void panel_gemm3_rb2_kernel(const float* __res
     for (int cb = xcd * cpg; cb < min(ncb, (xcd + 1) * cpg); ++cb) {
         const int tile = cb * 12 + wave;
         PnF::Acc acc[2] = {PnF::zero(), PnF::zero()};
-        if (tile < B.ntile) panel3_mma<2, 2>(pn3_lds, pstride, img, rg, nst, acc, lane);
+        if (tile < B.ntile) panel_mma<PnF, 2, 1, 2, PnOrder::StaticPinLds>(pn3_lds, {pstride, img}, rg, nst, acc, lane);
         const f32x4_t tsc = ts;
         if (cb + 1 < min(ncb, (xcd + 1) * cpg)) {
-            panel3_prefetch<2>(rg, B.f + (size_t)min((cb + 1) * 12 + wave, B.ntile - 1) * B.nst * PNF * 64, nst, lane);
+            panel_prefetch<PnF, 1, 2>(rg, {B.f + (size_t)min((cb + 1) * 12 + wave, B.ntile - 1) * B.nst * PNF * 64}, nst, lane);
             ts = PnF::tile_isc(B, (cb + 1) * 12 + wave, g);
         }
         const int n4 = tile * 16 + 4 * g;
@@ -757,13 +740,13 @@ __global__ __launch_bounds__(512) void panel_gemm3_rb2k_kernel(const float* __re
     const int pstride = (kpad >> 3) * 16, img = pnf_img_u4(kpad);
     const int tile = cb * 8 + wave;
     const bool active = tile < B.ntile && nst > 0;
-    PnRing3<2> rg;
-    panel3_prefetch<2>(rg, B.f + ((size_t)(active ? tile : 0) * B.nst + s0) * PNF * 64, max(nst, 1), lane);
+    PnRing<PnF, 1, 2> rg;
+    panel_prefetch<PnF, 1, 2>(rg, {B.f + ((size_t)(active ? tile : 0) * B.nst + s0) * PNF * 64}, max(nst, 1), lane);
     const f32x4_t ts = PnF::tile_isc(B, tile, g);               // (requested with the fragments: see panel_gemm3_kernel)
     PnF::stage<512, 2, 3>(pn3_lds, img, A, lda, m0, M, k0, kn, kpad, tid);
     __syncthreads();
     PnF::Acc acc[2] = {PnF::zero(), PnF::zero()};
-    if (active) panel3_mma<2, 2>(pn3_lds, pstride, img, rg, nst, acc, lane);
+    if (active) panel_mma<PnF, 2, 1, 2, PnOrder::StaticPinLds>(pn3_lds, {pstride, img}, rg, nst, acc, lane);
     const int n4 = tile * 16 + 4 * g;
     if (tile < B.ntile && n4 < N) {
         float* const C = Cpart + (size_t)half * part_stride;
@@ -798,8 +781,8 @@ __global__ __launch_bounds__(512) void panel_gemm3_wide_kernel(const float* __re
     const int cb0 = xb0 + part * per, cb1 = min(xb1, cb0 + per);
     const int kpad = (K + 31) & ~31, nst = kpad >> 5, pstride = (kpad >> 3) * 16, img = pnf_img_u4(kpad);
     if (cb0 >= cb1) return;
-    PnRing3<2> rg;
-    panel3_prefetch<2>(rg, B.f + (size_t)min(cb0 * 8 + wave, B.ntile - 1) * B.nst * PNF * 64, nst, lane);
+    PnRing<PnF, 1, 2> rg;
+    panel_prefetch<PnF, 1, 2>(rg, {B.f + (size_t)min(cb0 * 8 + wave, B.ntile - 1) * B.nst * PNF * 64}, nst, lane);
     f32x4_t ts = PnF::tile_isc(B, cb0 * 8 + wave, g);           // (requested with the fragments: see panel_gemm3_kernel)
     PnF::stage<512, RB, 3>(pn3_lds, img, A, lda, m0, M, 0, K, kpad, tid);
     __syncthreads();
@@ -811,10 +794,10 @@ __global__ __launch_bounds__(512) void panel_gemm3_wide_kernel(const float* __re
         PnF::Acc acc[RB];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) acc[rb] = PnF::zero();
-        if (tile < B.ntile) panel3_mma<RB, 2>(pn3_lds, pstride, img, rg, nst, acc, lane);
+        if (tile < B.ntile) panel_mma<PnF, RB, 1, 2, PnOrder::StaticPinLds>(pn3_lds, {pstride, img}, rg, nst, acc, lane);
         const f32x4_t tsc = ts;
         if (cb + 1 < cb1) {
-            panel3_prefetch<2>(rg, B.f + (size_t)min((cb + 1) * 8 + wave, B.ntile - 1) * B.nst * PNF * 64, nst, lane);
+            panel_prefetch<PnF, 1, 2>(rg, {B.f + (size_t)min((cb + 1) * 8 + wave, B.ntile - 1) * B.nst * PNF * 64}, nst, lane);
             ts = PnF::tile_isc(B, (cb + 1) * 8 + wave, g);
         }
         const int n4 = tile * 16 + 4 * g;
@@ -864,11 +847,11 @@ __global__ __launch_bounds__(512) void panel_gemm_wide_kernel(const float* __res
     const int kpad = (K + 15) & ~15, nss = kpad >> 4, img = kpad * 16;
     if (cb0 >= cb1) return;
     PN_STAMP(0);
-    PnRing<1, 4> rg;
+    PnRing<PnF32, 1, 4> rg;
     {
         const int t0 = min(cb0 * 8 + wave, B.ntile - 1);
         const float4* bfp = B.f + (size_t)t0 * B.nss * 64;
-        panel_prefetch<1, 4>(rg, &bfp, nss, lane);
+        panel_prefetch<PnF32, 1, 4>(rg, {bfp}, nss, lane);
     }
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) panel_stage<512>(pn_lds + (size_t)rb * img, A, lda, m0 + 16 * rb, M, 0, K, kpad, tid);
@@ -880,11 +863,11 @@ __global__ __launch_bounds__(512) void panel_gemm_wide_kernel(const float* __res
         f32x4_t acc[RB];
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) acc[rb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        if (tile < B.ntile) panel_mma_rows<RB, 4>(pn_lds, img, rg, nss, acc, lane);
+        if (tile < B.ntile) panel_mma<PnF32, RB, 1, 4, PnOrder::StaticPinLds>(pn_lds, {img}, rg, nss, acc, lane);
         if (cb + 1 < cb1) {                                          // next block's first fragments: in flight during the stores
             const int tn = min((cb + 1) * 8 + wave, B.ntile - 1);
             const float4* bfp = B.f + (size_t)tn * B.nss * 64;
-            panel_prefetch<1, 4>(rg, &bfp, nss, lane);
+            panel_prefetch<PnF32, 1, 4>(rg, {bfp}, nss, lane);
         }
         const int n4 = tile * 16 + 4 * g;
         if (tile < B.ntile && n4 < N) {
@@ -924,165 +907,6 @@ static inline hipError_t panel_gemm(const float* A, int lda, int M, int K, const
     return hipGetLastError();
 }
 
-// T tiles share one 16-row LDS block (the fused VPoser kernels' layers)
-template <int T, int PF>
-struct PnRing3T { uint4 bA[T][PF][PNF]; const uint4* st[T]; };
-template <int T, int PF>
-__device__ __forceinline__ void panel3_prefetch_t(PnRing3T<T, PF>& rg, const uint4* const* bf, int nst, int lane) {
-    const int last = nst - 1;
-#pragma unroll
-    for (int t = 0; t < T; ++t) rg.st[t] = bf[t] + lane;
-#pragma unroll
-    for (int p = 0; p < PF; ++p)
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int pl = 0; pl < PNF; ++pl) rg.bA[t][p][pl] = rg.st[t][((size_t)min(p, last) * PNF + pl) * 64];
-}
-template <int T, int PF>
-__device__ __forceinline__ void panel3_mma_t(const uint4* __restrict__ sA3, int pstride, PnRing3T<T, PF>& rg, int nst, PnF::Acc* acc, int lane) {
-    constexpr int NP = PNF;
-    uint4 (&bA)[T][PF][NP] = rg.bA;
-    uint4 bB[T][PF][NP];
-    const int last = nst - 1;
-    auto load_a = [&](uint4* a, int step) {
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) a[pl] = sA3[(size_t)pl * pstride + (size_t)step * 64 + lane];
-    };
-    auto keep = [&](uint4* a, const uint4* an) {
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) a[pl] = an[pl];
-    };
-    uint4 a[NP];
-    load_a(a, 0);
-    int s = 0;
-    for (; s + 2 * PF <= nst; s += 2 * PF) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            uint4 an[NP];
-            load_a(an, s + p + 1);
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) bB[t][p][pl] = rg.st[t][((size_t)(s + PF + p) * NP + pl) * 64];
-                pn_pin();
-                acc[t] = PnF::step(a, bA[t][p], acc[t]);
-            }
-            keep(a, an);
-        }
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            uint4 an[NP];
-            load_a(an, min(s + PF + p + 1, last));
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) bA[t][p][pl] = rg.st[t][((size_t)min(s + 2 * PF + p, last) * NP + pl) * 64];
-                pn_pin();
-                acc[t] = PnF::step(a, bB[t][p], acc[t]);
-            }
-            keep(a, an);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-        if (s + p < nst) {
-            uint4 an[NP];
-            load_a(an, min(s + p + 1, last));
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-#pragma unroll
-                for (int pl = 0; pl < NP; ++pl) bB[t][p][pl] = rg.st[t][((size_t)min(s + PF + p, last) * NP + pl) * 64];
-                acc[t] = PnF::step(a, bA[t][p], acc[t]);
-            }
-            keep(a, an);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < PF - 1; ++p) {
-        if (s + PF + p < nst) {
-            uint4 an[NP];
-            load_a(an, min(s + PF + p + 1, last));
-#pragma unroll
-            for (int t = 0; t < T; ++t) acc[t] = PnF::step(a, bB[t][p], acc[t]);
-            keep(a, an);
-        }
-    }
-}
-// RB row blocks x T tiles per wave (r5, the K-loop product): a step's RB LDS fragments are read ONCE for T tiles and its T static
-// fragments once for RB row blocks -- RB T products per (RB LDS reads + T fragment loads).  acc[rb * T + t].  Format PnF.
-template <int RB, int T, int PF>
-__device__ __forceinline__ void panel3_mma_rt(const uint4* __restrict__ sA3, int pstride, int img, PnRing3T<T, PF>& rg, int nst, PnF::Acc* acc, int lane) {
-    uint4 (&bA)[T][PF][PNF] = rg.bA;
-    uint4 bB[T][PF][PNF];
-    const int last = nst - 1;
-    auto load_a = [&](uint4 (*a)[PNF], int step) {
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int pl = 0; pl < PNF; ++pl) a[rb][pl] = sA3[(size_t)rb * img + (size_t)pl * pstride + (size_t)step * 64 + lane];
-    };
-    auto load_b = [&](uint4 (*b)[PF][PNF], int p, int step) {
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int pl = 0; pl < PNF; ++pl) b[t][p][pl] = rg.st[t][((size_t)step * PNF + pl) * 64];
-    };
-    auto keep = [&](uint4 (*a)[PNF], uint4 (*an)[PNF]) {
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int pl = 0; pl < PNF; ++pl) a[rb][pl] = an[rb][pl];
-    };
-    uint4 a[RB][PNF];
-    load_a(a, 0);
-    auto mma = [&](uint4 (*b)[PF][PNF], int p) {
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) acc[rb * T + t] = PnF::step(a[rb], b[t][p], acc[rb * T + t]);
-    };
-    int s = 0;
-    for (; s + 2 * PF <= nst; s += 2 * PF) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            uint4 an[RB][PNF];
-            load_a(an, s + p + 1);
-            load_b(bB, p, s + PF + p);
-            pn_pin();
-            mma(bA, p);
-            keep(a, an);
-        }
-#pragma unroll
-        for (int p = 0; p < PF; ++p) {
-            uint4 an[RB][PNF];
-            load_a(an, min(s + PF + p + 1, last));
-            load_b(bA, p, min(s + 2 * PF + p, last));
-            pn_pin();
-            mma(bB, p);
-            keep(a, an);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-        if (s + p < nst) {
-            uint4 an[RB][PNF];
-            load_a(an, min(s + p + 1, last));
-            load_b(bB, p, min(s + PF + p, last));
-            mma(bA, p);
-            keep(a, an);
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < PF - 1; ++p) {
-        if (s + PF + p < nst) {
-            uint4 an[RB][PNF];
-            load_a(an, min(s + PF + p + 1, last));
-            mma(bB, p);
-            keep(a, an);
-        }
-    }
-}
 // Long K, few rows (r5: the data gradient [M,1500] x [1500,496] of a SHARD, M = 128..383 -- too few rows for the two-K-halves form,
 // and as a plain one-row-block product 32 workgroups that each pull 1.1 MB of fragments through one CU: 15 us for 0.2 GFLOP).  K is
 // split over the EIGHT WAVES of a workgroup: every wave streams its eighth of K for the workgroup's T column tiles, the eight partial
@@ -1092,19 +916,18 @@ __global__ __launch_bounds__(512) void panel_gemm3_ksw_kernel(const float* __res
                                                               float* __restrict__ C, int ldc, int N, PnMap mp) {
     extern __shared__ __attribute__((aligned(16))) uint4 pn3_lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int r_in = mp.rfast ? slot % mp.rpg : slot / mp.cpg, c_in = mp.rfast ? slot / mp.rpg : slot % mp.cpg;
-    const int rbk = (xcd / mp.xc) * mp.rpg + r_in, cbk = (xcd % mp.xc) * mp.cpg + c_in;
-    if (r_in >= mp.rpg || c_in >= mp.cpg || rbk >= mp.nrb || cbk >= mp.ncb) return;  // ragged groups (whole workgroup)
+    const PnBlock pb = panel_block(mp);
+    if (!pb.on) return;
+    const int rbk = pb.rbk, cbk = pb.cbk;
     const int tile0 = cbk * T, m0 = rbk * 16;
     const int kpad = (K + 31) & ~31, nst_all = kpad >> 5, pstride = (kpad >> 3) * 16;
     const int per = (nst_all + 7) >> 3, s_lo = min(nst_all, wave * per), nst = min(nst_all, s_lo + per) - s_lo;
-    PnRing3T<T, 2> rg;
+    PnRing<PnF, T, 2> rg;
     if (nst > 0) {                                             // (wave-uniform) in flight while the A block is staged
         const uint4* bf[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) bf[t] = B.f + ((size_t)min(tile0 + t, B.ntile - 1) * B.nst + s_lo) * PNF * 64;
-        panel3_prefetch_t<T, 2>(rg, bf, nst, lane);
+        panel_prefetch<PnF, T, 2>(rg, bf, nst, lane);
     }
     f32x4_t ts[T];
 #pragma unroll
@@ -1114,7 +937,7 @@ __global__ __launch_bounds__(512) void panel_gemm3_ksw_kernel(const float* __res
     PnF::Acc acc[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = PnF::zero();
-    if (nst > 0) panel3_mma_rt<1, T, 2>(pn3_lds + (size_t)s_lo * 64, pstride, 0, rg, nst, acc, lane);
+    if (nst > 0) panel_mma<PnF, 1, T, 2, PnOrder::LdsStaticPin>(pn3_lds + (size_t)s_lo * 64, {pstride, 0}, rg, nst, acc, lane);
     const float rs = PnF::row_isc(pn3_lds, pstride, j);        // (behind the planes: the meeting place below does not reach it)
     __syncthreads();                                           // every wave is done with the image: its head becomes the meeting place
     float4* const red = (float4*)pn3_lds;
@@ -1132,26 +955,14 @@ __global__ __launch_bounds__(512) void panel_gemm3_ksw_kernel(const float* __res
             sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w;
         }
         const int tile = tile0 + wave, n4 = tile * 16 + 4 * g, m = m0 + j;
-        if (tile < B.ntile && n4 < N && m < M) {
-            float* dst = C + (size_t)m * ldc + n4;
-            if (n4 + 3 < N) *(f32x4u_t*)dst = f32x4u_t{sum.x, sum.y, sum.z, sum.w};
-            else {
-                const float r[4] = {sum.x, sum.y, sum.z, sum.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) if (n4 + e < N) dst[e] = r[e];
-            }
-        }
+        if (tile < B.ntile && n4 < N && m < M) pnf_store4(C, ldc, N, m, n4, f32x4_t{sum.x, sum.y, sum.z, sum.w});
     }
 }
 static inline hipError_t panel_gemm3_ksw(const PanelPlan& pl, const float* A, int lda, int M, int K, const PanelB3& B, float* C, int ldc, int N, hipStream_t st) {
     if (M <= 0 || N <= 0) return hipSuccess;
     static std::atomic<uint64_t> attr{0};                      // per DEVICE: the attribute belongs to one device's code object
-    if (fdc_attr_needed(attr)) {
-        hipError_t e = hipFuncSetAttribute((const void*)panel_gemm3_ksw_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.max_lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)panel_gemm3_ksw_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.max_lds);
-        if (e != hipSuccess) return e;
-        fdc_attr_done(attr);
-    }
+    const hipError_t e = fdc_allow_lds(attr, pl.max_lds, {(const void*)panel_gemm3_ksw_kernel<2>, (const void*)panel_gemm3_ksw_kernel<1>});
+    if (e != hipSuccess) return e;
     note_form(form_name(pl.form));
     if (pl.T == 2)
         hipLaunchKernelGGL(panel_gemm3_ksw_kernel<2>, dim3(pl.grid), dim3(pl.block), pl.lds, st, A, lda, M, K, B, C, ldc, N, pl.mp);
@@ -1188,15 +999,15 @@ __global__ __launch_bounds__(512) void panel_gemm3_kloop_kernel(const float* __r
     for (int t = 0; t < T; ++t) ts[t] = PnF::tile_isc(B, tile0 + t, g);
     for (int s0 = s_lo; s0 < s_hi; s0 += slab_steps) {
         const int nst = min(slab_steps, s_hi - s0), k0 = 32 * s0, kn = min(K, 32 * (s0 + nst)) - k0;
-        PnRing3T<T, 2> rg;                                 // (requested before the staging: the first round trip hides behind it)
+        PnRing<PnF, T, 2> rg;                                 // (requested before the staging: the first round trip hides behind it)
         const uint4* bf[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) bf[t] = B.f + ((size_t)min(tile0 + t, B.ntile - 1) * B.nst + s0) * PNF * 64;
-        panel3_prefetch_t<T, 2>(rg, bf, nst, lane);
+        panel_prefetch<PnF, T, 2>(rg, bf, nst, lane);
         if (s0 > s_lo) __syncthreads();                         // every wave is done with the previous slab's images
         PnF::stage<512, RB, 3>(pn3_lds, img, A, lda, m0, M, k0, kn, kpad, tid);
         __syncthreads();
-        if (tile0 < B.ntile) panel3_mma_rt<RB, T, 2>(pn3_lds, pstride, img, rg, nst, acc, lane);
+        if (tile0 < B.ntile) panel_mma<PnF, RB, T, 2, PnOrder::LdsStaticPin>(pn3_lds, {pstride, img}, rg, nst, acc, lane);
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {                       // fold the slab in at its rows' scales
             const float rs = PnF::row_isc(pn3_lds + (size_t)rb * img, pstride, j);
@@ -1241,11 +1052,8 @@ static inline hipError_t panel_gemm3_kloop(const PanelPlan& pl, const float* A, 
     constexpr int rb = PN3_KLOOP_RB, T = PN3_KLOOP_T;
     const size_t stride = (size_t)M * ldc;
     static std::atomic<uint64_t> attr{0};                      // per DEVICE: the attribute belongs to one device's code object
-    if (fdc_attr_needed(attr)) {
-        hipError_t e = hipFuncSetAttribute((const void*)panel_gemm3_kloop_kernel<rb, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.max_lds);
-        if (e != hipSuccess) return e;
-        fdc_attr_done(attr);
-    }
+    const hipError_t e = fdc_allow_lds(attr, pl.max_lds, {(const void*)panel_gemm3_kloop_kernel<rb, T>});
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((panel_gemm3_kloop_kernel<rb, T>), dim3(pl.grid), dim3(pl.block), pl.lds, st, A, lda, M, K, B, part, stride, ldc, N, pl.ks, PN3_KLOOP_SLAB);
     note_form(form_name(pl.form));
     hipLaunchKernelGGL(panel_part_sum_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, st, part, pl.ks, stride, stride, C);
@@ -1341,7 +1149,7 @@ __global__ __launch_bounds__(512) void vposer_fwd_fused_kernel(VPoserPanels P, c
     if (rblk >= two.nb1) { rblk -= two.nb1; row_lo = two.row2_lo; row_hi = two.row2_hi; }
     const int q = blockIdx.x & 3, r0 = row_lo + rblk * 16;
     PN_STAMP(0);
-    PnRing<1, 4> rg2, rg3;                             // next layer's first fragments are requested before the barrier in front of it
+    PnRing<PnF32, 1, 4> rg2, rg3;                             // next layer's first fragments are requested before the barrier in front of it
     // all three layers' biases before the first barrier (see vposer_fwd_split3_kernel)
     float4 bias1[4];
 #pragma unroll
@@ -1355,8 +1163,8 @@ __global__ __launch_bounds__(512) void vposer_fwd_fused_kernel(VPoserPanels P, c
         const float4* bf[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) { acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f}; bf[t] = P.w1.f + (size_t)(wave * 4 + t) * P.w1.nss * 64; }
-        PnRing<4, 2> rg1;
-        panel_prefetch<4, 2>(rg1, bf, VP_Z / 16, lane);
+        PnRing<PnF32, 4, 2> rg1;
+        panel_prefetch<PnF32, 4, 2>(rg1, bf, VP_Z / 16, lane);
         if (ds.on) {                                       // (wave-uniform) the latent rows after the pending optimiser step,
             const int i = tid >> 5, k = tid & 31;          // straight into panel_stage's k-blocked image: [k / 4][row][k % 4]
             sZ[((k >> 2) * 16 + i) * 4 + (k & 3)] = vp_deferred_latent(ds, r0, row_hi, tid);
@@ -1364,10 +1172,10 @@ __global__ __launch_bounds__(512) void vposer_fwd_fused_kernel(VPoserPanels P, c
             panel_stage<512>(sZ, Z, ldx, r0, row_hi, 0, VP_Z, VP_Z, tid);
         __syncthreads();
         PN_STAMP(1);
-        panel_mma<4, 2>(sZ, rg1, VP_Z / 16, acc, lane);
+        panel_mma<PnF32, 1, 4, 2, PnOrder::LdsTilePin>(sZ, {0}, rg1, VP_Z / 16, acc, lane);
         {
             const float4* bf2 = P.w2.f + (size_t)(q * 8 + wave) * P.w2.nss * 64;
-            panel_prefetch<1, 4>(rg2, &bf2, VP_H / 16, lane);
+            panel_prefetch<PnF32, 1, 4>(rg2, {bf2}, VP_H / 16, lane);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -1384,10 +1192,10 @@ __global__ __launch_bounds__(512) void vposer_fwd_fused_kernel(VPoserPanels P, c
     {   // layer 2, this quarter's 128 columns (one tile per wave)
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
         const int tile = q * 8 + wave;
-        panel_mma<1, 4>(sH1, rg2, VP_H / 16, &acc, lane);
+        panel_mma<PnF32, 1, 1, 4, PnOrder::LdsTilePin>(sH1, {0}, rg2, VP_H / 16, &acc, lane);
         {
             const float4* bf3 = P.w3.f + ((size_t)wave * P.w3.nss + q * (VP_QW / 16)) * 64;
-            panel_prefetch<1, 4>(rg3, &bf3, VP_QW / 16, lane);
+            panel_prefetch<PnF32, 1, 4>(rg3, {bf3}, VP_QW / 16, lane);
         }
         const int n4 = tile * 16 + 4 * g;
         const float4 bias = bias2;
@@ -1399,7 +1207,7 @@ __global__ __launch_bounds__(512) void vposer_fwd_fused_kernel(VPoserPanels P, c
     PN_STAMP(3);
     {   // output layer: this quarter's K-slice of all 126 (128) columns
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-        panel_mma<1, 4>(sH2, rg3, VP_QW / 16, &acc, lane);
+        panel_mma<PnF32, 1, 1, 4, PnOrder::LdsTilePin>(sH2, {0}, rg3, VP_QW / 16, &acc, lane);
         const int n4 = wave * 16 + 4 * g, row = r0 + j;              // ODIM = 126: rows are 8-byte aligned -> two float2 stores
         if (row < row_hi) {
             float* dst = Opart + (size_t)q * part_stride + (size_t)row * ODIM + n4;
@@ -1439,8 +1247,8 @@ __global__ __launch_bounds__(512) void vposer_bwd_fused_kernel(VPoserPanels P, c
     float* const sred = sdH1 + VP_H * 16;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
     const int q = bid & 3, r0 = row_lo + (int)(bid >> 2) * 16;
-    PnRing<4, 4> rgB;
-    PnRing<1, 4> rgC;
+    PnRing<PnF32, 4, 4> rgB;
+    PnRing<PnF32, 1, 4> rgC;
     // the masking activations before the first barrier (see vposer_bwd_split3_kernel)
     const size_t hrow = (size_t)min(r0 + j, row_hi - 1) * VP_H;
     const float4 hm2 = *(const float4*)(H2 + hrow + (q * 8 + wave) * 16 + 4 * g);
@@ -1451,16 +1259,16 @@ __global__ __launch_bounds__(512) void vposer_bwd_fused_kernel(VPoserPanels P, c
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
         const int tile = q * 8 + wave;
         const float4* bf = P.w3t.f + (size_t)tile * P.w3t.nss * 64;
-        PnRing<1, 4> rgA;
-        panel_prefetch<1, 4>(rgA, &bf, 8, lane);
+        PnRing<PnF32, 1, 4> rgA;
+        panel_prefetch<PnF32, 1, 4>(rgA, {bf}, 8, lane);
         panel_stage<512>(sdO, dO, ODIM, r0, row_hi, 0, ODIM, 128, tid);
         __syncthreads();
-        panel_mma<1, 4>(sdO, rgA, 8, &acc, lane);
+        panel_mma<PnF32, 1, 1, 4, PnOrder::LdsTilePin>(sdO, {0}, rgA, 8, &acc, lane);
         {
             const float4* bfb[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) bfb[t] = P.w2t.f + ((size_t)(wave + 8 * t) * P.w2t.nss + q * (VP_QW / 16)) * 64;
-            panel_prefetch<4, 4>(rgB, bfb, VP_QW / 16, lane);
+            panel_prefetch<PnF32, 4, 4>(rgB, bfb, VP_QW / 16, lane);
         }
         const int n4 = tile * 16 + 4 * g;
         const float4 h = hm2;
@@ -1473,10 +1281,10 @@ __global__ __launch_bounds__(512) void vposer_bwd_fused_kernel(VPoserPanels P, c
         f32x4_t acc[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        panel_mma<4, 4>(sdH2, rgB, VP_QW / 16, acc, lane);
+        panel_mma<PnF32, 1, 4, 4, PnOrder::LdsTilePin>(sdH2, {0}, rgB, VP_QW / 16, acc, lane);
         {
             const float4* bfc = P.w1t.f + ((size_t)(wave & 1) * P.w1t.nss + (wave >> 1) * 8) * 64;
-            panel_prefetch<1, 4>(rgC, &bfc, 8, lane);
+            panel_prefetch<PnF32, 1, 4>(rgC, {bfc}, 8, lane);
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -1491,7 +1299,7 @@ __global__ __launch_bounds__(512) void vposer_bwd_fused_kernel(VPoserPanels P, c
     {   // partial d latent = partial dH1 x W1: 2 column tiles x 4 K-slices over the 8 waves, slices summed in order
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
         const int tile = wave & 1, ks = wave >> 1;
-        panel_mma<1, 4>(sdH1 + (size_t)ks * 8 * 256, rgC, 8, &acc, lane);
+        panel_mma<PnF32, 1, 1, 4, PnOrder::LdsTilePin>(sdH1 + (size_t)ks * 8 * 256, {0}, rgC, 8, &acc, lane);
         *(float4*)(sred + (size_t)(ks * 2 + tile) * 256 + lane * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
     __syncthreads();
@@ -1550,8 +1358,8 @@ __global__ __launch_bounds__(512) void vposer_fwd_split3_kernel(VPoserPanels3 P,
     int rblk = (int)(blockIdx.x >> 2);
     if (rblk >= two.nb1) { rblk -= two.nb1; row_lo = two.row2_lo; row_hi = two.row2_hi; }
     const int q = blockIdx.x & 3, r0 = row_lo + rblk * 16;
-    PnRing3T<1, VP3_PF2> rg2;
-    PnRing3T<1, 2> rg3;
+    PnRing<VpF, 1, VP3_PF2> rg2;
+    PnRing<VpF, 1, 2> rg3;
     // the biases (and column scales) of all three layers, requested before the first barrier (the compiler does not move a load across
     // one): fetched where they are used -- after each layer's products -- every tile's bias was a round trip of its own
     float4 bias1[4];
@@ -1569,17 +1377,17 @@ __global__ __launch_bounds__(512) void vposer_fwd_split3_kernel(VPoserPanels3 P,
         const uint4* bf[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) { acc[t] = VpF::zero(); bf[t] = P.w1.f + (size_t)(wave * 4 + t) * P.w1.nst * NP * 64; }
-        PnRing3T<4, 1> rg1;
-        panel3_prefetch_t<4, 1>(rg1, bf, 1, lane);
+        PnRing<VpF, 4, 1> rg1;
+        panel_prefetch<VpF, 4, 1>(rg1, bf, 1, lane);
         if (ds.on)                                         // (wave-uniform) the latent rows after the pending optimiser step, straight into the image
             pnf_put_latent(sZ, VP3_PZ, tid >> 5, tid & 31, vp_deferred_latent(ds, r0, row_hi, tid));
         else
             VpF::stage<512, 1, 1>(sZ, 0, Z, ldx, r0, row_hi, 0, VP_Z, VP_Z, tid);
         __syncthreads();
-        panel3_mma_t<4, 1>(sZ, VP3_PZ, rg1, 1, acc, lane);
+        panel_mma<VpF, 1, 4, 1, PnOrder::LdsTilePin>(sZ, {VP3_PZ, 0}, rg1, 1, acc, lane);
         {
             const uint4* bf2 = P.w2.f + (size_t)(q * 8 + wave) * P.w2.nst * NP * 64;
-            panel3_prefetch_t<1, VP3_PF2>(rg2, &bf2, VP_H / 32, lane);
+            panel_prefetch<VpF, 1, VP3_PF2>(rg2, {bf2}, VP_H / 32, lane);
         }
         const float zis = VpF::row_isc(sZ, VP3_PZ, j);
         bnd1 = P.c1 * (16384.f * zis) + P.b1max;           // >= every |H1| of row j (2^14 zis >= its largest |z|)
@@ -1599,10 +1407,10 @@ __global__ __launch_bounds__(512) void vposer_fwd_split3_kernel(VPoserPanels3 P,
     {   // layer 2, this quarter's 128 columns (one tile per wave), K = 512 = 16 steps
         VpF::Acc acc = VpF::zero();
         const int tile = q * 8 + wave;
-        panel3_mma_t<1, VP3_PF2>(sH1, VP3_PH, rg2, VP_H / 32, &acc, lane);
+        panel_mma<VpF, 1, 1, VP3_PF2, PnOrder::LdsTilePin>(sH1, {VP3_PH, 0}, rg2, VP_H / 32, &acc, lane);
         {
             const uint4* bf3 = P.w3.f + ((size_t)wave * P.w3.nst + q * (VP_QW / 32)) * NP * 64;
-            panel3_prefetch_t<1, 2>(rg3, &bf3, VP_QW / 32, lane);
+            panel_prefetch<VpF, 1, 2>(rg3, {bf3}, VP_QW / 32, lane);
         }
         VpF::pow2(P.c2 * bnd1 + P.b2max, s2, is2);
         const int n4 = tile * 16 + 4 * g;
@@ -1615,7 +1423,7 @@ __global__ __launch_bounds__(512) void vposer_fwd_split3_kernel(VPoserPanels3 P,
     __syncthreads();
     {   // output layer: this quarter's K-slice (128 = 4 steps) of all 126 (128) columns
         VpF::Acc acc = VpF::zero();
-        panel3_mma_t<1, 2>(sH2, VP3_PQ, rg3, VP_QW / 32, &acc, lane);
+        panel_mma<VpF, 1, 1, 2, PnOrder::LdsTilePin>(sH2, {VP3_PQ, 0}, rg3, VP_QW / 32, &acc, lane);
         const f32x4_t o = VpF::value(acc, is2, cs3);
         const int n4 = wave * 16 + 4 * g, row = r0 + j;
         if (row < row_hi) {
@@ -1651,8 +1459,8 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
     float* const sred = (float*)(sdH1 + NP * VP3_PH);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
     const int q = bid & 3, r0 = row_lo + (int)(bid >> 2) * 16;
-    PnRing3T<4, 2> rgB;
-    PnRing3T<1, 2> rgC;
+    PnRing<VpF, 4, 2> rgB;
+    PnRing<VpF, 1, 2> rgC;
     // the forward activations whose signs mask this wave's tiles, requested before the first barrier (rows clamped:
     // unconditional loads).  Fetched after each layer's products they were five dependent round trips on cold data.
     const size_t hrow = (size_t)min(r0 + j, row_hi - 1) * VP3_MROW;          // (sign bytes: vp3_signs)
@@ -1667,18 +1475,18 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
         VpF::Acc acc = VpF::zero();
         const int tile = q * 8 + wave;
         const uint4* bf = P.w3t.f + (size_t)tile * P.w3t.nst * NP * 64;
-        PnRing3T<1, 2> rgA;
-        panel3_prefetch_t<1, 2>(rgA, &bf, 4, lane);
+        PnRing<VpF, 1, 2> rgA;
+        panel_prefetch<VpF, 1, 2>(rgA, {bf}, 4, lane);
         if (tail.lg_spread && bid < (unsigned)LROW && wave == 0)     // (wave-uniform) one logged term: ScaleTail::lg_spread
             loss_rows_reduce_slot(tail.lg.rows, tail.row0, tail.lg.n, tail.lg.mask, tail.lg.assign, tail.lg.losses, (int)bid, lane);
         VpF::stage<512, 1, 1>(sdO, 0, dO, ODIM, r0, row_hi, 0, ODIM, 128, tid);
         __syncthreads();
-        panel3_mma_t<1, 2>(sdO, VP3_PQ, rgA, 4, &acc, lane);
+        panel_mma<VpF, 1, 1, 2, PnOrder::LdsTilePin>(sdO, {VP3_PQ, 0}, rgA, 4, &acc, lane);
         {
             const uint4* bfb[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) bfb[t] = P.w2t.f + ((size_t)(wave + 8 * t) * P.w2t.nst + q * (VP_QW / 32)) * NP * 64;
-            panel3_prefetch_t<4, 2>(rgB, bfb, VP_QW / 32, lane);
+            panel_prefetch<VpF, 4, 2>(rgB, bfb, VP_QW / 32, lane);
         }
         const float dois = VpF::row_isc(sdO, VP3_PQ, j);
         bd2 = P.c3t * (16384.f * dois);                   // >= every |dH2| of row j
@@ -1696,10 +1504,10 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
         VpF::Acc acc[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[t] = VpF::zero();
-        panel3_mma_t<4, 2>(sdH2, VP3_PQ, rgB, VP_QW / 32, acc, lane);
+        panel_mma<VpF, 1, 4, 2, PnOrder::LdsTilePin>(sdH2, {VP3_PQ, 0}, rgB, VP_QW / 32, acc, lane);
         {
             const uint4* bfc = P.w1t.f + ((size_t)(wave & 1) * P.w1t.nst + (wave >> 1) * 4) * NP * 64;
-            panel3_prefetch_t<1, 2>(rgC, &bfc, 4, lane);
+            panel_prefetch<VpF, 1, 2>(rgC, {bfc}, 4, lane);
         }
         VpF::pow2(P.c2t * bd2, sd1, isd1);
 #pragma unroll
@@ -1716,7 +1524,7 @@ __global__ __launch_bounds__(512) void vposer_bwd_split3_kernel(VPoserPanels3 P,
     {   // partial d latent = partial dH1 x W1: 2 column tiles x 4 K-slices (128 columns = 4 steps each), slices summed in order
         VpF::Acc acc = VpF::zero();
         const int tile = wave & 1, ks = wave >> 1;
-        panel3_mma_t<1, 2>(sdH1 + (size_t)ks * 4 * 64, VP3_PH, rgC, 4, &acc, lane);
+        panel_mma<VpF, 1, 1, 2, PnOrder::LdsTilePin>(sdH1 + (size_t)ks * 4 * 64, {VP3_PH, 0}, rgC, 4, &acc, lane);
         const f32x4_t o = VpF::value(acc, isd1, csC);
         *(float4*)(sred + (size_t)(ks * 2 + tile) * 256 + lane * 4) = make_float4(o[0], o[1], o[2], o[3]);
     }

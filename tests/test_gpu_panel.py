@@ -27,15 +27,25 @@ pytestmark = pytest.mark.gpu
     (130, 496, 13001, False, 0),        # wide output: four row blocks per fragment stream, column-block-major workgroup order
     (1024, 496, 1500, False, 0),        # clip-sized M: two row blocks per fragment stream (panel_gemm3_rb2_kernel), the bench's product
     (531, 700, 1000, True, 3),          # ... ragged rows / tiles, unaligned operand and output rows
-    (130, 1690, 496, True, 0),          # longest K whose three-plane LDS image fits a CU's 160 KB (kpad 1696)
-    (130, 2000, 496, True, 0),          # (beyond the three-plane image; the two-plane fp16 image reaches kpad 2528)
-    (130, 2600, 496, True, 0),          # beyond it: the split form must hand over to the K-slabbed fp32 kernel, not fail the launch
-    (400, 1700, 496, True, 0),          # clip-sized M above the K-split kernel's range (K <= 1536)
+    (130, 1690, 496, True, 0),          # long K in ONE two-plane fp16 LDS image (kpad 1696; the image reaches kpad 2528 of a CU's 160 KB)
+    (130, 2000, 496, True, 0),          # (kpad 2016: still one image)
+    (130, 2600, 496, True, 0),          # beyond kpad 2528: the split form must hand over to the K-slabbed fp32 kernel, not fail the launch
+    (400, 1700, 496, True, 0),          # clip-sized M above the K-halves kernel's range (K <= 1536)
+] + [
+    # the fragment ring (panel_mma): its tail for every residue of the step count mod 2 PF, its clamp to the last step for counts
+    # below PF.  One workgroup's worth of output, two row blocks, ragged tiles.  K = 32 n - 5: 1 .. 9 steps of the split loop (PF = 2)
+    (17, 32 * n - 5, 40, False, 0) for n in range(1, 10)
+] + [
+    # K = 16 n - 3: 1 .. 9 and 13 super-steps of the fp32 loop (PF = 4; 13 = residue 5 mod 8)
+    (17, 16 * n - 3, 40, False, 0) for n in (1, 2, 3, 4, 5, 6, 7, 8, 9, 13)
+] + [
+    # the smallest shape that selects panel_gemm3_rb2_kernel (336 rows, 48 tiles): 1, 2, 3, 5 steps on two row blocks per stream
+    (336, 32 * n - 5, 760, False, 0) for n in (1, 2, 3, 5)
 ])
 @pytest.mark.parametrize("form", ["split3", "fp32"])
 def test_panel_gemm_matches_fp64(M, K, N, transposed, pad, form, monkeypatch):
-    """Both forms of the loop's dense product against fp64: the three-way bf16 split on the bf16 matrix cores (default) and the
-    exact fp32 MFMA chain (FDCAP_GEMM_SPLIT3=0) are held to the SAME bar."""
+    """Both forms of the loop's dense product against fp64: the split into two fp16 planes on the 16-bit matrix cores (default, PnH2:
+    one LDS image up to kpad 2528) and the exact fp32 MFMA chain (FDCAP_GEMM_SPLIT3=0) are held to the SAME bar."""
     monkeypatch.setenv("FDCAP_GEMM_SPLIT3", "1" if form == "split3" else "0")
     lib = capi.load_library()
     rng = np.random.default_rng(M * 7919 + K * 31 + N)
@@ -140,12 +150,19 @@ def test_fused_vposer_forward_ragged_rows(B):
 def test_fused_vposer_backward_in_the_optimiser_gradient(n, V, per_part):
     """Phase-1 gradient of a clip that spans several 16-row blocks (ragged last block): the latent columns come out of
     vposer_bwd_fused_kernel's four partial sums, folded by fdcap_opt_get_grads; compared with fp64 autograd.
-    The third case has a 180-vertex contact set on a 2000-vertex body (blend products with K, N = 540); the last two are
+    The third case has a 180-vertex contact set on a 2000-vertex body (blend products with K, N = 540); the fourth and fifth are
     clip-sized (>= 512 frames): the data-gradient product runs as two K halves on two row blocks per fragment stream
     (panel_gemm3_rb2k_kernel: 2 + 2 and 9 + 8 steps), the partial products added by pose_bwd_kernel.  The 600- / 566-vertex
-    contact sets (K = 1800 / 1698) are past the single-image three-plane form (kpad <= 1696: 160 KB of LDS) and past the
-    K-split kernel: their data gradient runs on the K-slabbed fp32 panel kernel."""
+    contact sets (K = 1800 / 1698) fit one two-plane fp16 LDS image (kpad <= 2528): at 40 frames the data gradient's K is split
+    over a workgroup's waves (panel_gemm3_ksw_kernel), at 390 frames it runs on the K-loop kernel (K >= 1664 from 384 rows)."""
+    _optimiser_gradient_case(n, V, per_part)
+
+
+def _optimiser_gradient_case(n, V, per_part):
+    """-> the kernel forms the gradient's launches took (fdcap_debug_kernel_forms)"""
+    forms = ctypes.create_string_buffer(4096)
     fop, bm, vp, clip, scene, vid = _make_fop(n, V, 800, per_part, 500)
+    capi.check(fop.ctx.lib.fdcap_debug_kernel_forms(forms, len(forms), 1), "kernel_forms")   # (reset)
     dt = torch.float64
     f = FittingOracle(SMPLXOracle(bm, dt), VPoserDecoder.from_data(vp, dt), scene, vid, clip.camerapose_lines, n, dtype=dt)
     x78 = rotrepr.convert_to_6D_rot(torch.tensor(clip.body_params, dtype=dt)).detach()
@@ -171,4 +188,29 @@ def test_fused_vposer_backward_in_the_optimiser_gradient(n, V, per_part):
     lat = gx[:, 19:51]
     assert np.abs(lat).max() > 0                                          # the latent block is really exercised
     np.testing.assert_allclose(dx.cpu().numpy()[:, 19:51], lat, rtol=2e-3, atol=2e-4 * np.abs(lat).max())
+    capi.check(lib.fdcap_debug_kernel_forms(forms, len(forms), 0), "kernel_forms")
     fop.close()
+    return forms.value.decode().split(";")
+
+
+@pytest.mark.parametrize("n,V,per_part,kernel", [
+    # K split over a workgroup's eight waves (K = 3 x contact vertices, 32 columns per step): the waves' shares are
+    (40, 300, 128, "panel_gemm3_ksw_kernel"),       # K = 768: 3 steps each -- the ring's tail alone
+    (40, 400, 150, "panel_gemm3_ksw_kernel"),       # K = 900: 4 steps (one turn of the main loop), the last wave 1 (clamped prefetch)
+    (40, 500, 200, "panel_gemm3_ksw_kernel"),       # K = 1200: 5 steps (a turn + 1), the last wave 3
+    (40, 400, 172, "panel_gemm3_ksw_kernel"),       # K = 1032: 5 steps, 3 for the seventh wave, NONE for the last
+    (130, 300, 128, "panel_gemm3_ksw_kernel"),      # nine row blocks: two column tiles per workgroup (T = 2), 3 steps each
+    # two K halves on two row blocks per stream, from 257 frames: halves of
+    (257, 300, 10, "panel_gemm3_rb2k_kernel"),      # K = 60: 1 + 1 steps
+    (257, 300, 16, "panel_gemm3_rb2k_kernel"),      # K = 96: 2 + 1
+    (257, 300, 25, "panel_gemm3_rb2k_kernel"),      # K = 150: 3 + 2
+    # K beyond one LDS image (kpad > 2528: from 843 contact vertices; the sets here are even): 80 steps in 32 parts of 3, 2 or 0
+    # steps, two row blocks x two tiles per wave; more than one slab per part: tests/test_gpu_fullsize_golden.py
+    (128, 1000, 422, "panel_gemm3_kloop_kernel"),
+])
+def test_ring_step_counts_in_the_optimiser_gradient(n, V, per_part, kernel):
+    """test_fused_vposer_backward_in_the_optimiser_gradient's check at contact sets whose data-gradient product (dV [n, 3 x vertices]
+    x the blend directions) takes the named kernel with step counts at the fragment ring's edges: a tail of every length, fewer steps
+    than the ring is deep, a wave or a part of K with no step at all."""
+    forms = _optimiser_gradient_case(n, V, per_part)
+    assert any(f.startswith(kernel) for f in forms), forms

@@ -25,7 +25,7 @@ for line in txt.splitlines():
     m = re.search(r"remark:\s+([A-Za-z \[\]/]+): (\d+) \[-Rpass", line)
     if m and cur:
         rows[cur][m.group(1).strip()] = int(m.group(2))
-print(f"{'kernel':70s} {'VGPR':>5s} {'AGPR':>5s} {'spill':>6s} {'LDS':>7s} {'occ':>4s}")
+print(f"{'kernel':70s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'spill':>6s} {'LDS':>7s} {'occ':>4s}")
 for k, r in sorted(rows.items()):
     if flt in k:
-        print(f"{k[:70]:70s} {r.get('VGPRs', 0):5d} {r.get('AGPRs', 0):5d} {r.get('VGPRs Spill', 0):6d} {r.get('LDS Size [bytes/block]', 0):7d} {r.get('Occupancy [waves/SIMD]', 0):4d}")
+        print(f"{k[:70]:70s} {r.get('VGPRs', 0):5d} {r.get('AGPRs', 0):5d} {r.get('TotalSGPRs', 0):5d} {r.get('VGPRs Spill', 0):6d} {r.get('LDS Size [bytes/block]', 0):7d} {r.get('Occupancy [waves/SIMD]', 0):4d}")
