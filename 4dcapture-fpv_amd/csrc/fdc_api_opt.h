@@ -396,4 +396,28 @@ int fdcap_debug_nn_query_order(fdcap_ctx* c, int32_t mode, const int32_t* perm_h
     return FDCAP_OK;
 }
 
+// Tests / diagnosis: the query order's sort on its own (nn_query_order, exactly as nn_search launches it) on neighbour positions
+// given by the caller.  Owns its buffers; needs no optimiser state.
+int fdcap_debug_nn_query_sort(fdcap_ctx* c, const int32_t* pos_host, int32_t nq, int32_t groups, int32_t hdr_len, int32_t* hdr_io,
+                              int32_t* perm_out, void* stream) {
+    if (!c || !pos_host || !hdr_io || !perm_out || nq <= 0 || groups < 0 || hdr_len < groups) return FDCAP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<float4> sp((size_t)nq);
+    for (int i = 0; i < nq; ++i) {                           // (seedpt[i].w carries the position's int bits)
+        sp[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        memcpy(&sp[i].w, &pos_host[i], sizeof(int32_t));
+    }
+    DevBuf<float4> seedpt;
+    DevBuf<int> qbuf, hdr;
+    hipError_t e = seedpt.upload(sp.data(), (size_t)nq);
+    if (e == hipSuccess) e = qbuf.ensure(nn_query_order_ints(nq));
+    if (e == hipSuccess) e = hdr.upload(hdr_io, (size_t)hdr_len);
+    if (e == hipSuccess) e = nn_query_order(seedpt.p, nq, qbuf.p, hdr.p, groups, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(perm_out, qbuf.p, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && hdr_len > 0) e = hipMemcpy(hdr_io, hdr.p, (size_t)hdr_len * sizeof(int), hipMemcpyDeviceToHost);
+    seedpt.release(); qbuf.release(); hdr.release();
+    return e == hipSuccess ? FDCAP_OK : (int)e;
+}
+
 }  // extern "C"

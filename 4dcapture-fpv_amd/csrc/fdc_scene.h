@@ -134,34 +134,143 @@ __global__ __launch_bounds__(256) void sc_rs_scatter_kernel(const unsigned* __re
 // Slot -> query, by the k-d quarter of each query's current neighbour (seedpt.w: its position in the sorted scene, >> 7), ties by
 // query index (the sort is stable and starts from the identity): waves of 32 queries that reach nearly one list of quarters.
 // A log-bucket of the neighbour distance as a second key was modelled on the bench scene and did not shrink the lists further.
-// Buffer: perm [nq] | values [nq] | keys [2][nq] | histogram [256 x blocks].
-static inline size_t nn_query_order_ints(int nq) { return 4 * (size_t)nq + 256 * (size_t)((nq + SC_RS_TILE - 1) / SC_RS_TILE); }
+// The sort (r11) is the query order's own LSD radix sort, two 8-bit passes over the 16-bit key, stable: the order the scene
+// build's sort above would give, without its one-workgroup scan of all 256 x blocks counters.  Six launches: keys + pass-0
+// histogram | row prefixes | scatter | pass-1 histogram | row prefixes | scatter.  A launch boundary is the only synchronisation
+// between workgroups.  Buffer: perm [nq] | values [nq] | keys [2][nq] | histogram [256 x blocks] | digit totals [256].
+constexpr int QS_ROUNDS = 16;                    // a 256-thread block sorts 16 rounds of 256 keys
+constexpr int QS_TILE = 256 * QS_ROUNDS;
+static inline int nn_query_order_blocks(int nq) { return (nq + QS_TILE - 1) / QS_TILE; }
+static inline size_t nn_query_order_ints(int nq) { return 4 * (size_t)nq + 256 * (size_t)nn_query_order_blocks(nq) + 256; }
 
-__global__ __launch_bounds__(256) void nn_order_keys_kernel(const float4* __restrict__ seedpt, int nq, unsigned* __restrict__ key,
-                                                            int* __restrict__ val, int* __restrict__ hdr, int groups) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < nq) {
-        const int pos = __float_as_int(seedpt[i].w);          // -1: no neighbour (a NaN query): last
-        key[i] = pos >= 0 ? min((unsigned)pos >> 7, 0xFFFFu) : 0xFFFFu;
-        val[i] = i;
+// key and identity value of every query, the per-tile histogram of the low digit (hist[digit][tile]) and hdr[0 .. groups) = -1
+__global__ __launch_bounds__(256) void nn_qs_keys_kernel(const float4* __restrict__ seedpt, int nq, unsigned* __restrict__ key,
+                                                         int* __restrict__ val, unsigned* __restrict__ hist, int nb,
+                                                         int* __restrict__ hdr, int groups) {
+    __shared__ unsigned h[256];
+    const int tid = threadIdx.x;
+    h[tid] = 0;
+    __syncthreads();
+    const int tile0 = blockIdx.x * QS_TILE;
+    for (int r = 0; r < QS_ROUNDS; ++r) {
+        const int i = tile0 + r * 256 + tid;
+        if (i < nq) {
+            const int pos = __float_as_int(seedpt[i].w);          // -1: no neighbour (a NaN query): last
+            const unsigned k = pos >= 0 ? min((unsigned)pos >> 7, 0xFFFFu) : 0xFFFFu;
+            key[i] = k;
+            val[i] = i;
+            atomicAdd(&h[k & 255u], 1u);
+        }
     }
-    if (i < groups) hdr[i] = -1;                               // the groups change: no kept list survives
+    // the groups change: no kept list survives (the last block takes whatever lies beyond the tiles)
+    const int ghi = blockIdx.x == gridDim.x - 1 ? groups : min(groups, tile0 + QS_TILE);
+    for (int i = tile0 + tid; i < ghi; i += 256) hdr[i] = -1;
+    __syncthreads();
+    hist[(size_t)tid * nb + blockIdx.x] = h[tid];
+}
+
+// pass 1's per-tile histogram (the high digit of the keys as pass 0 left them)
+__global__ __launch_bounds__(256) void nn_qs_hist_kernel(const unsigned* __restrict__ keys, int n, unsigned* __restrict__ hist, int nb) {
+    __shared__ unsigned h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const int tile0 = blockIdx.x * QS_TILE;
+    for (int r = 0; r < QS_ROUNDS; ++r) {
+        const int i = tile0 + r * 256 + threadIdx.x;
+        if (i < n) atomicAdd(&h[(keys[i] >> 8) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
+}
+
+// one wave per digit row of hist [256][nb]: the row's exclusive prefix in place (64 consecutive counters per step, four steps
+// in flight, the total carried from step to step) and the row's total
+__global__ __launch_bounds__(256) void nn_qs_rows_kernel(unsigned* __restrict__ hist, int nb, unsigned* __restrict__ tot) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    unsigned* const a = hist + (size_t)row * nb;
+    unsigned carry = 0;
+    for (int j0 = 0; j0 < nb; j0 += 256) {
+        unsigned v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const int j = j0 + 64 * k + lane; v[k] = j < nb ? a[j] : 0u; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned s = v[k];
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(s, o); if (lane >= o) s += t; }
+            const int j = j0 + 64 * k + lane;
+            if (j < nb) a[j] = carry + s - v[k];
+            carry += __shfl(s, 63);
+        }
+    }
+    if (lane == 0) tot[row] = carry;
+}
+
+// one pass, as sc_rs_scatter_kernel, but hist holds the row-local prefixes and tot the 256 digit totals: the block forms the
+// digit bases itself (one 256-entry exclusive scan) and adds its own row-local prefix
+__global__ __launch_bounds__(256) void nn_qs_scatter_kernel(const unsigned* __restrict__ kin, const int* __restrict__ vin,
+                                                            unsigned* __restrict__ kout, int* __restrict__ vout, int n, int shift,
+                                                            const unsigned* __restrict__ hist, const unsigned* __restrict__ tot, int nb) {
+    __shared__ unsigned base[256];
+    __shared__ unsigned wcnt[4][256];
+    __shared__ unsigned wtot[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    {
+        const unsigned t = tot[tid];
+        unsigned s = t;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned u = __shfl_up(s, o); if (lane >= o) s += u; }
+        if (lane == 63) wtot[wave] = s;
+        __syncthreads();
+        unsigned off = s - t;
+        for (int k = 0; k < wave; ++k) off += wtot[k];
+        base[tid] = off + hist[(size_t)tid * nb + blockIdx.x];
+    }
+    const int tile0 = blockIdx.x * QS_TILE;
+    for (int r = 0; r < QS_ROUNDS; ++r) {
+        const int i = tile0 + r * 256 + tid;
+        const bool valid = i < n;
+        const unsigned key = valid ? kin[i] : 0u;
+        const int val = valid ? vin[i] : 0;
+        const unsigned d = (key >> shift) & 255u;
+        unsigned long long m = __ballot(valid);                       // lanes of this wave with the same digit
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long bal = __ballot(bit);
+            m &= bit ? bal : ~bal;
+        }
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        for (int k = 0; k < 4; ++k) wcnt[k][tid] = 0;
+        __syncthreads();
+        if (valid && rank == 0) wcnt[wave][d] = (unsigned)__popcll(m);
+        __syncthreads();
+        if (valid) {
+            unsigned off = base[d];
+            for (int k = 0; k < wave; ++k) off += wcnt[k][d];
+            kout[off + rank] = key;
+            vout[off + rank] = val;
+        }
+        __syncthreads();
+        base[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
+        __syncthreads();
+    }
 }
 
 static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st) {
-    const int nb = (nq + SC_RS_TILE - 1) / SC_RS_TILE;
+    const int nb = nn_query_order_blocks(nq);
     int* const perm = qbuf;
     int* const val = qbuf + nq;
     unsigned* const key = (unsigned*)(qbuf + 2 * (size_t)nq);
     unsigned* const hist = key + 2 * (size_t)nq;
-    hipLaunchKernelGGL(nn_order_keys_kernel, dim3((std::max(nq, groups) + 255) / 256), dim3(256), 0, st, seedpt, nq, key, perm, hdr, groups);
-    for (int pass = 0; pass < 2; ++pass) {                     // 16-bit keys: (perm, key) -> (val, key + nq) -> (perm, key)
-        unsigned* const kin = key + (size_t)pass * nq;
-        unsigned* const kout = key + (size_t)(1 - pass) * nq;
-        hipLaunchKernelGGL(sc_rs_hist_kernel, dim3(nb), dim3(256), 0, st, kin, nq, 8 * pass, hist, nb);
-        hipLaunchKernelGGL(sc_scan_kernel, dim3(1), dim3(1024), 0, st, hist, 256 * nb);
-        hipLaunchKernelGGL(sc_rs_scatter_kernel, dim3(nb), dim3(256), 0, st, kin, pass ? val : perm, kout, pass ? perm : val, nq, 8 * pass, hist, nb);
-    }
+    unsigned* const tot = hist + 256 * (size_t)nb;
+    // 16-bit keys: (perm, key) -> (val, key + nq) -> (perm, key)
+    hipLaunchKernelGGL(nn_qs_keys_kernel, dim3(nb), dim3(256), 0, st, seedpt, nq, key, perm, hist, nb, hdr, groups);
+    hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
+    hipLaunchKernelGGL(nn_qs_scatter_kernel, dim3(nb), dim3(256), 0, st, key, perm, key + nq, val, nq, 0, hist, tot, nb);
+    hipLaunchKernelGGL(nn_qs_hist_kernel, dim3(nb), dim3(256), 0, st, key + nq, nq, hist, nb);
+    hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
+    hipLaunchKernelGGL(nn_qs_scatter_kernel, dim3(nb), dim3(256), 0, st, key + nq, val, key, perm, nq, 8, hist, tot, nb);
     return hipGetLastError();
 }
 

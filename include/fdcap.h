@@ -507,6 +507,14 @@ int fdcap_opt_nn_timing_read(fdcap_ctx* ctx, float* mean_ms, int32_t* launches);
  * permutation: wave slot s serves query perm_h[s]), kept until the next call.  Drops the kept work lists.  Synchronises the device. */
 int fdcap_debug_nn_query_order(fdcap_ctx* ctx, int32_t mode, const int32_t* perm_h, int32_t n);
 
+/* Tests / diagnosis: the sort behind mode 0 above on its own, on the launch path the optimiser uses.  pos_h [nq]: the position
+ * of each query's neighbour in the sorted scene (-1: none); the key is min(pos >> 7, 0xFFFF), 0xFFFF without a neighbour.
+ * perm_out [nq] receives the order (stable: by key, ties by query index).  hdr_io [hdr_len >= groups] stands for the kept-list
+ * headers: uploaded as given, returned as the rebuild leaves them (the first `groups` entries -1, the rest untouched).
+ * Needs no optimiser; allocates and frees its own device buffers.  Synchronises `stream`. */
+int fdcap_debug_nn_query_sort(fdcap_ctx* ctx, const int32_t* pos_h, int32_t nq, int32_t groups, int32_t hdr_len, int32_t* hdr_io,
+                              int32_t* perm_out, void* stream);
+
 /* In-loop timing of EVERY launch of an iteration (r6; bench.py's roofline.per_kernel[].us_live): while enabled (max_events > 0) the
  * optimiser records a HIP event on its launch stream at every boundary between two launches of an iteration (up to max_events
  * events in all; 0 disables and resets) -- one fit of 500 iterations records ~4100.  fdcap_opt_launch_timing_read waits for them and
