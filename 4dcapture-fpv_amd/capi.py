@@ -81,6 +81,8 @@ SYMBOLS = {
                                        c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_create": (c_int32, [c_void_p, POINTER(OptConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_create_clips": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_create_clips_var": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
     "fdcap_opt_set_inputs": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_backward": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "fdcap_opt_step": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),

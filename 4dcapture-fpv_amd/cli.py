@@ -14,7 +14,11 @@ Several clips in one run (the reference's real workload: every video cut into 30
 Each clip's scene and camera paths are derived from its sample name as above (`--scene-root`).  Clips are grouped by (scene
 file -- the resolved path, so that the segments of one video may link one scene --, clip length); each group is cut into batches of at most K clips that are fitted as one optimisation (fitting.ClipBatchFitter:
 one context for the whole run).  Clip output: `<fit-root>/<sample_name>/body_gen_%06d.pkl`, the files the one-clip form writes
-with that directory as <fit_path>.  Default K: the largest K with K * N <= MULTICLIP_ROW_CAP.  Mode 'global' only."""
+with that directory as <fit_path>.  Default K: the largest K with K * N <= MULTICLIP_ROW_CAP.  Mode 'global' only.
+
+`--mix-lengths` (with --clips): clips are grouped by scene file alone and a batch may hold clips of different lengths
+(plan_batches_mixed: batches are filled in input order up to MULTICLIP_ROW_CAP rows, so a video's short remainder clip rides with
+its full segments).  Every clip's result is the one its own batch-of-one gives."""
 from __future__ import annotations
 
 import argparse
@@ -62,6 +66,32 @@ def plan_batches(clips, clips_per_batch=None, row_cap: int = MULTICLIP_ROW_CAP):
     return out
 
 
+def plan_batches_mixed(clips, clips_per_batch=None, row_cap: int = MULTICLIP_ROW_CAP):
+    """clips: sequence of (scene path, clip length).  Groups them by scene path alone -- groups in order of their first clip, clips
+    in input order within a group -- and fills batches in that order: a batch is closed when the next clip would push its rows
+    above row_cap (a clip longer than the cap is a batch of its own) or its clip count above clips_per_batch.  For clips of one
+    length these are plan_batches' batches (as long as a given clips_per_batch stays within the row cap, which plan_batches does
+    not apply to it).  Returns [(scene path, [clip indices])]."""
+    groups = {}
+    for i, (scene, n) in enumerate(clips):
+        groups.setdefault(scene, []).append(i)
+    kmax = max(1, int(clips_per_batch)) if clips_per_batch else None
+    out = []
+    for scene, idx in groups.items():
+        cur, rows = [], 0
+        for i in idx:
+            n = int(clips[i][1])
+            full = rows + n > row_cap or (kmax is not None and len(cur) >= kmax)
+            if cur and full:
+                out.append((scene, cur))
+                cur, rows = [], 0
+            cur.append(i)
+            rows += n
+        if cur:
+            out.append((scene, cur))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="global_optimization (fdcap_amd / MI355X)")
     ap.add_argument("body_path", nargs="?")
@@ -72,6 +102,9 @@ def main(argv=None):
     ap.add_argument("--fit-root", default=None, help="multi-clip form: clip output goes to <fit-root>/<sample_name>/")
     ap.add_argument("--clips-per-batch", type=int, default=None,
                     help=f"multi-clip form: clips per batch (default: the largest K with K * frames <= {MULTICLIP_ROW_CAP})")
+    ap.add_argument("--mix-lengths", action="store_true",
+                    help="multi-clip form: group clips by scene alone; a batch may hold clips of different lengths and never more "
+                         f"than {MULTICLIP_ROW_CAP} rows, also with --clips-per-batch (without this flag K alone bounds a batch)")
     ap.add_argument("--mode", dest="mode_opt", default=None, choices=["global", "local", "dct"],
                     help="multi-clip form: the mode (only 'global' is supported)")
     ap.add_argument("--scene-root", default="/home/miao/")
@@ -88,6 +121,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.clips is not None:
         return _main_clips(ap, a)
+    if a.mix_lengths:
+        ap.error("--mix-lengths belongs to the multi-clip form (--clips ... --fit-root DIR)")
     if a.body_path is None or a.fit_path is None:
         ap.error("body_path and fit_path are required (or --clips ... --fit-root DIR)")
 
@@ -136,13 +171,17 @@ def _main_clips(ap, a):
     lossconfig = {"weight_loss_rec": 1, "weight_loss_vposer": 0.001, "weight_contact": 0.1, "weight_collision": 0.5}
     fitter = ClipBatchFitter(fittingconfig, lossconfig)
     try:
-        for scene, n, idx in plan_batches([(s, d.shape[0]) for s, d in zip(scenes, data)], a.clips_per_batch):
+        sized = [(s, d.shape[0]) for s, d in zip(scenes, data)]
+        batches = plan_batches_mixed(sized, a.clips_per_batch) if a.mix_lengths else \
+            [(scene, idx) for scene, _, idx in plan_batches(sized, a.clips_per_batch)]
+        for scene, idx in batches:
             pts = None if scene == fitter.scene_key else io.read_scene_points(scene)
             res = fitter.fit([(data[i], cams[i]) for i in idx], pts, scene_key=scene, log_every=a.log_every)
             for i, (body_rec, scale, camera_ext) in zip(idx, res):
                 io.save_result(body_rec.detach().cpu().numpy(), scale, camera_ext.detach().cpu().numpy(),
                                clip_output_dir(a.fit_root, a.clips[i]))
-            print(f"[INFO][fitting] batch of {len(idx)} clips x {n} frames fitted ({scene})")
+            frames = sorted({sized[i][1] for i in idx})
+            print(f"[INFO][fitting] batch of {len(idx)} clips x {'/'.join(map(str, frames))} frames fitted ({scene})")
     finally:
         fitter.close()
     print("[INFO][fitting] fitting finish, returning optimal value")

@@ -378,7 +378,7 @@ int opt_step_launch(fdcap_ctx* c, int32_t ii, int32_t P, bool do_rows, bool do_s
     const LogReduceIn lg = {o->loss_rows.p, o->log_dst, o->log_mask, o->log_assign, rpc};
     hipLaunchKernelGGL(adam_step_kernel, dim3(sp.nb_x + sp.nb_cam + K + (o->log_pending ? K : 0)), dim3(256), 0, st, sp.x, sp.cam, sp.sc, sp.nb_x, sp.nb_cam,
                        o->dscale_row.p, 2, reduce_scale ? rpc : 0, o->dscale.p, (sp.step_scale && ii >= P) ? 1 : 0, xch, nl, o->CAM.p,
-                       (do_rows && o->dz_pending) ? (const float*)o->dZpart.p : (const float*)nullptr, (size_t)o->R * VP_Z, lg, K);
+                       (do_rows && o->dz_pending) ? (const float*)o->dZpart.p : (const float*)nullptr, (size_t)o->R * VP_Z, lg, K, o->cspan());
     o->log_pending = false;
     if (do_rows) o->dz_pending = false;
     return (int)hipGetLastError();

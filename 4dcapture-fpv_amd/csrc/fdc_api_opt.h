@@ -14,6 +14,7 @@ void fdcap_opt_destroy(fdcap_ctx* c) {
                            &o->dsv, &o->dPF, &o->dJw, &o->dX, &o->dCAM, &o->dscale_row, &o->loss_rows, &o->VoffF, &o->VwF, &o->dVF};
     for (auto* b : fb) b->release();
     o->dctD.release(); o->dctCoef.release(); o->dctM.release(); o->dctV.release(); o->adam_tab.release();
+    o->clip_rows.release(); o->clip_span.release();
     o->idx.release(); o->pi.release(); o->seedpt.release(); o->kp2d.release(); o->floss.release();
     if (o->lbfgs) { fdcap_lbfgs_destroy(o->lbfgs); o->lbfgs = nullptr; }
     o->nnc_ids.release(); o->nnc_hdr.release(); o->nnc_anchor.release();
@@ -26,22 +27,37 @@ void fdcap_opt_destroy(fdcap_ctx* c) {
 }
 
 static_assert(LROW == FDCAP_NUM_LOSSES, "a batch's per-clip loss slots are LROW apart on the device");
-int fdcap_opt_create_clips(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_clips, float* rows_x, float* rows_cam, float* scale_d,
-                           float* dscale_d, double* losses_d) {
-    if (!c || !cfg || !rows_x || !rows_cam || !scale_d || !dscale_d || !losses_d || cfg->n_local <= 0 || cfg->n_total < cfg->n_local || cfg->frame0 < 0 ||
-        cfg->frame0 + cfg->n_local > cfg->n_total || n_clips < 1)
-        return FDCAP_E_ARG;
-    // a batch holds whole clips of one length: no shard of a clip, and K N rows that still index as int
-    if (n_clips > 1 && (cfg->frame0 != 0 || cfg->n_local != cfg->n_total || (int64_t)n_clips * cfg->n_total > (1 << 24)))
-        return FDCAP_E_ARG;
+static_assert(CLIP_XDIM == XDIM && CLIP_NJW == NJW, "fdc_clips.h restates the two dimensions its weights divide by");
+
+// the loss total of iteration ii of mode 'global' (:570 / :582): phase 1 below first_phase2_iter, phase 2 from it
+static LossWeights opt_phase_weights(const fdcap_opt_config& cf, bool phase2) {
+    LossWeights lw;
+    lw.rec = 1.f;
+    lw.smooth = phase2 ? cf.phase2_smooth : cf.phase1_smooth;
+    lw.contact = phase2 ? 0.f : cf.phase1_contact;
+    lw.world = phase2 ? cf.phase2_world : 0.f;
+    lw.dct = 0.f;
+    lw.world_on = phase2;
+    return lw;
+}
+
+// var_len == nullptr: n_clips clips of cfg->n_total frames each (one clip, one rank's share of one, or a batch of one length).
+// var_len != nullptr: clips of these lengths, not all equal; cfg holds the batch's rows (n_total = n_local = their sum, checked
+// by the caller).
+static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_clips, const int32_t* var_len, float* rows_x, float* rows_cam,
+                           float* scale_d, float* dscale_d, double* losses_d) {
     SetupTrace tr("fdcap_opt_create");
     // a second clip of the same shape reuses the scratch allocations (every buffer is re-zeroed below)
     OptState* o = c->opt ? c->opt : new OptState();
     c->opt = o;
     o->cfg = *cfg;
     o->nclip = n_clips;
-    o->clip_len = cfg->n_total;
-    if (n_clips > 1) o->cfg.n_total = o->cfg.n_local = n_clips * cfg->n_total;     // the batch's rows: clip k owns 2 + k N .. 2 + (k + 1) N
+    o->clip_len = var_len ? 0 : cfg->n_total;
+    o->ragged = var_len != nullptr;
+    if (var_len) o->clip_lens.assign(var_len, var_len + n_clips);
+    else o->clip_lens.assign((size_t)n_clips, cfg->n_total);
+    o->clip_start = clip_starts(n_clips, o->clip_lens.data());
+    if (n_clips > 1 && !var_len) o->cfg.n_total = o->cfg.n_local = n_clips * cfg->n_total;     // the batch's rows: clip k owns 2 + k N .. 2 + (k + 1) N
     cfg = &o->cfg;
     o->cam_steps = 0;
     o->dz_pending = false;
@@ -102,9 +118,45 @@ int fdcap_opt_create_clips(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
         hipError_t e_ = hipMemcpy(o->scale.p, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e_ != hipSuccess) err = (int)e_;
     }
+    if (!err && o->ragged) {
+        // the clip tables (fdc_clips.h): every row's record under the weights of phase 1, then of phase 2, and the clips' spans
+        std::vector<ClipRow> rows = clip_rows_build(n_clips, var_len, opt_phase_weights(*cfg, false), cfg->weight_loss_rec, cfg->weight_contact, c->nc);
+        const std::vector<ClipRow> rows2 = clip_rows_build(n_clips, var_len, opt_phase_weights(*cfg, true), cfg->weight_loss_rec, cfg->weight_contact, c->nc);
+        rows.insert(rows.end(), rows2.begin(), rows2.end());
+        std::vector<int> span((size_t)2 * n_clips);
+        for (int k = 0; k < n_clips; ++k) { span[(size_t)2 * k] = o->clip_start[(size_t)k]; span[(size_t)2 * k + 1] = var_len[k]; }
+        hipError_t e_ = rows.size() == (size_t)2 * R ? o->clip_rows.upload(rows.data(), rows.size()) : hipErrorInvalidValue;
+        if (e_ == hipSuccess) e_ = o->clip_span.upload(span.data(), span.size());
+        if (e_ != hipSuccess) err = (int)e_;
+    }
     tr.mark("search state");
     if (err) { fdcap_opt_destroy(c); return err; }
     return FDCAP_OK;
+}
+
+int fdcap_opt_create_clips(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_clips, float* rows_x, float* rows_cam, float* scale_d,
+                           float* dscale_d, double* losses_d) {
+    if (!c || !cfg || !rows_x || !rows_cam || !scale_d || !dscale_d || !losses_d || cfg->n_local <= 0 || cfg->n_total < cfg->n_local || cfg->frame0 < 0 ||
+        cfg->frame0 + cfg->n_local > cfg->n_total || n_clips < 1)
+        return FDCAP_E_ARG;
+    // a batch holds whole clips of one length: no shard of a clip, and K N rows that still index as int
+    if (n_clips > 1 && (cfg->frame0 != 0 || cfg->n_local != cfg->n_total || (int64_t)n_clips * cfg->n_total > (1 << 24)))
+        return FDCAP_E_ARG;
+    return opt_create_impl(c, cfg, n_clips, nullptr, rows_x, rows_cam, scale_d, dscale_d, losses_d);
+}
+
+// Clips of their own lengths.  Equal lengths are fdcap_opt_create_clips' batch (its path, its bits: no table).
+int fdcap_opt_create_clips_var(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_clips, const int32_t* clip_len, float* rows_x, float* rows_cam,
+                               float* scale_d, float* dscale_d, double* losses_d) {
+    if (!c || !cfg || !rows_x || !rows_cam || !scale_d || !dscale_d || !losses_d || cfg->frame0 != 0 || cfg->n_local != cfg->n_total ||
+        !clip_lengths_ok(n_clips, clip_len, cfg->n_total, (int64_t)1 << 24))
+        return FDCAP_E_ARG;
+    if (clip_lengths_equal(n_clips, clip_len)) {
+        fdcap_opt_config one = *cfg;
+        one.n_total = one.n_local = clip_len[0];
+        return fdcap_opt_create_clips(c, &one, n_clips, rows_x, rows_cam, scale_d, dscale_d, losses_d);
+    }
+    return opt_create_impl(c, cfg, n_clips, clip_len, rows_x, rows_cam, scale_d, dscale_d, losses_d);
 }
 
 int fdcap_opt_create(fdcap_ctx* c, const fdcap_opt_config* cfg, float* rows_x, float* rows_cam, float* scale_d,
@@ -142,12 +194,12 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
         note_form(form_name(pl.form));
         hipLaunchKernelGGL(blend_skin_fwd_kernel, dim3(pl.grid), dim3(pl.block), pl.lds, st, o->PF.p, nl,
                            c->contact.pn_fwdS, smf, nc, smf.ja_hi, o->X.p, XDIM, X_TRANSL, o->A.p, o->M.p, o->scale.p, 2, o->Voff.p, o->Vw.p,
-                           o->kclip_n());
+                           o->kclip_n(), o->ctab(false));
     } else {
         if (!blend_done) HIP_TRY(blend_forward(c->contact, o->PF.p + 2 * NPFX, nl, o->Voff.p + off, st));
         note_form(form_name(pl.form));
         hipLaunchKernelGGL(skin_fwd_kernel, dim3(pl.grid, pl.grid_y), dim3(pl.block), 0, st, smf, nc, o->X.p, XDIM,
-                           X_BETAS, X_TRANSL, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, 1, o->Vw.p, o->kclip_n());
+                           X_BETAS, X_TRANSL, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, 1, o->Vw.p, o->kclip_n(), o->ctab(false));
     }
     lt_mark(o, FDCAP_LT_CONTACT_FWD, st);
     const int nq = nl * nc;
@@ -167,24 +219,31 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
     return 0;
 }
 
-namespace {
-// weights of the loss total of one iteration (multipliers of the lossconfig weights, :570 / :582 / :620)
-struct LossWeights { float rec, smooth, contact, world, dct; bool world_on; };
-}
-
 // fuse_ii >= 0 (fdcap_opt_backward_and_step): this backward is followed by the optimiser step of iteration fuse_ii -- `scale`
 // is stepped by one more workgroup of the last launch, the rows' part is left pending for the next forward (DeferredStep)
+// (clips of different lengths: the kernels take each frame's clip, denominators, stencil extent and weights from the half of the
+//  clip table that was built with exactly these lw -- phase 1's or phase 2's; any other weights are refused, never replaced)
 static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_terms, hipStream_t st, int fuse_ii = -1, int fuse_P = 0) {
     OptState* o = c->opt;
     const fdcap_opt_config& cf = o->cfg;
     // N: the clip length -- the denominators of the means and the stencils' extent (a batch: every clip has N frames)
     const int nl = cf.n_local, nc = c->nc, N = o->clip_len, rpc = o->rows_per_clip(), kn = o->kclip_n();
+    const ClipRow* ctab = nullptr;
+    if (o->ragged) {
+        const auto same = [&lw](const LossWeights& t) {
+            return t.rec == lw.rec && t.smooth == lw.smooth && t.contact == lw.contact && t.world == lw.world && t.dct == lw.dct && t.world_on == lw.world_on;
+        };
+        if (same(opt_phase_weights(cf, false))) ctab = o->ctab(false);
+        else if (same(opt_phase_weights(cf, true))) ctab = o->ctab(true);
+        else return FDCAP_E_STATE;
+    }
+    const int* const cspan = o->cspan();
     const bool dct_on = lw.dct != 0.f && o->dctW > 0;
     PoseModel pm = c->pose_model();
     TraceRange tr_(fuse_ii >= 0 ? "fdcap:backward_and_step" : "fdcap:backward");
     if (o->log_pending) {                               // a deferred reduction nobody stepped after: deliver it before loss_rows is rewritten
         hipLaunchKernelGGL(loss_rows_reduce_kernel, dim3(o->nclip), dim3(256), 0, st, o->loss_rows.p, 2, rpc, o->log_mask, o->log_assign, o->log_dst,
-                           o->dscale_row.p, o->dscale.p);
+                           o->dscale_row.p, o->dscale.p, cspan);
         o->log_pending = false;
     }
     double* const losses = log_terms ? o->losses.p : nullptr;       // the partial sums are only formed on logging iterations
@@ -202,15 +261,17 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
     o->ahead = false;
     if (e) return e;
     if (contact_fwd) { e = opt_contact_forward(c, st, blend_done); if (e) return e; }
-    const float w_rec = lw.rec * cf.weight_loss_rec / ((float)N * XDIM);
-    const float w_sm = (N >= 3) ? lw.smooth / ((float)(N - 2) * XDIM) : 0.f;
-    const float w_ws = (lw.world_on && N >= 2) ? lw.world / ((float)(N - 1) * NJW * 3) : 0.f;
+    // one length: every clip's weights.  Clips of different lengths (N = 0): cw and rpc below are placeholders that only keep
+    // ParamLossIn / ContactGradIn / ScaleTail filled in -- the kernels read the table's weights and the tails clip_span's counts
+    const ClipWeights cw = clip_weights(std::max(N, 1), lw, cf.weight_loss_rec, cf.weight_contact, nc);
+    const float w_rec = cw.w_rec, w_sm = cw.w_sm, w_ws = cw.w_ws;
     // the parameter-space terms: their own kernel when the loss sums are wanted or the DCT term also writes dJw, else
     // formed inside pose_bwd_kernel (one launch less per iteration)
     const bool fuse_pl = (!losses || rows_log) && !(o->dctW > 0 && dct_on);
     ParamLossIn pli = {};
     if (fuse_pl) pli = ParamLossIn{o->X0.p, o->mask.p, o->Jw.p, cf.frame0, N, w_rec, w_sm, w_ws, lw.world_on ? 1 : 0,
                                    rows_log ? o->loss_rows.p : nullptr};
+    else if (ctab) return FDCAP_E_STATE;                  // (never: a batch has no DCT term, so its parameter-space terms are always fused)
     else
         hipLaunchKernelGGL(param_loss_kernel, dim3(nl), dim3(128), 0, st, o->X.p, o->X0.p, o->mask.p, o->Jw.p, 2, cf.frame0, N,
                            w_rec, w_sm, w_ws, lw.world_on ? 1 : 0, o->dX.p, o->dJw.p, losses, kn);
@@ -225,7 +286,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         ContactGradIn cg;
         cg.Vw = o->Vw.p; cg.dist = o->dist.p; cg.idx = o->idx.p; cg.scene = c->scene.p;
         cg.nnpt = o->nnpt_valid ? o->seedpt.p : nullptr;
-        cg.coef = lw.contact * cf.weight_contact / ((float)N * nc);
+        cg.coef = cw.coef;
         cg.loss_rows = losses ? o->loss_rows.p : nullptr;
         const SkinModel smc = c->contact.model();
         const int nnz = c->contact.nnz;
@@ -235,7 +296,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         if (pl.ja_rows) dA_rows = c->contact.ja_hi;
         const dim3 grid(pl.grid), block(pl.block);
 #define FDC_SKC(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, pl.lds, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, o->dVoff.p, \
-                                           o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn)
+                                           o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn, ctab)
         switch (pl.form) {
         case F_SKIN_BWD_VEC:
             note_form(form_name(pl.form));
@@ -250,7 +311,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
             break;
         default:
             { int es = skin_bwd_any<true>(c->ws_skin, st, nl, smc, nc, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2,
-                                          (const float*)nullptr, o->dVoff.p, o->dA.p, (float*)nullptr, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn);
+                                          (const float*)nullptr, o->dVoff.p, o->dA.p, (float*)nullptr, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn, ctab);
               if (es) return es; }
         }
 #undef FDC_SKC
@@ -267,7 +328,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
                        joint_grad ? o->dJw.p : nullptr, contact_grad ? o->dMv.p : nullptr, contact_grad ? o->dsv.p : nullptr,
                        contact_grad ? o->dPF.p + NPF : nullptr, NPFX, contact_grad ? o->dtransl_v.p : nullptr, o->dX.p, o->dO.p,
                        o->dCAM.p, o->dscale_row.p, pli, (contact_grad && dpf_split) ? (const float*)(o->dPF.p + (size_t)o->R * NPFX) : (const float*)nullptr,
-                       dA_rows, kn);
+                       dA_rows, kn, ctab);
     lt_mark(o, FDCAP_LT_POSE_BWD, st);
     const unsigned log_mask = (rows_log ? 0x17u : 0u) | (contact_fwd ? 0x8u : 0u);     // 0 rec, 1 z^2, 2 smoothing, 4 world | 3 contact
     bool log_in_tail = false;
@@ -296,7 +357,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
             o->log_pending = true; o->log_mask = log_mask; o->log_assign = 1; o->log_dst = losses;
         } else
             hipLaunchKernelGGL(loss_rows_reduce_kernel, dim3(o->nclip), dim3(256), 0, st, o->loss_rows.p, 2, rpc, log_mask, rows_log ? 1 : 0, losses,
-                               o->dscale_row.p, o->dscale.p);
+                               o->dscale_row.p, o->dscale.p, cspan);
     }
     return (int)hipGetLastError();
 }
@@ -334,13 +395,7 @@ int fdcap_opt_backward(fdcap_ctx* c, int32_t ii, int32_t P, int32_t log_terms, v
     if (!c || !c->opt) return FDCAP_E_STATE;
     const fdcap_opt_config& cf = c->opt->cfg;
     const bool phase2 = ii >= P;
-    LossWeights lw;
-    lw.rec = 1.f;
-    lw.smooth = phase2 ? cf.phase2_smooth : cf.phase1_smooth;
-    lw.contact = phase2 ? 0.f : cf.phase1_contact;
-    lw.world = phase2 ? cf.phase2_world : 0.f;
-    lw.dct = 0.f;
-    lw.world_on = phase2;
+    const LossWeights lw = opt_phase_weights(cf, phase2);
     return opt_backward_impl(c, lw, log_terms, (hipStream_t)stream);
 }
 
@@ -360,13 +415,7 @@ int fdcap_opt_backward_and_step(fdcap_ctx* c, int32_t ii, int32_t P, int32_t log
         return e ? e : fdcap_opt_step(c, ii, P, stream);
     }
     const bool phase2 = ii >= P;
-    LossWeights lw;
-    lw.rec = 1.f;
-    lw.smooth = phase2 ? cf.phase2_smooth : cf.phase1_smooth;
-    lw.contact = phase2 ? 0.f : cf.phase1_contact;
-    lw.world = phase2 ? cf.phase2_world : 0.f;
-    lw.dct = 0.f;
-    lw.world_on = phase2;
+    const LossWeights lw = opt_phase_weights(cf, phase2);
     return opt_backward_impl(c, lw, log_terms, (hipStream_t)stream, ii, P);
 }
 

@@ -136,8 +136,9 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_fwd_kernel(PoseModel pm, co
                                                       int row0, float* Rm, float* PF, float* Jrest, float* G, float* A,
                                                       float* M, float* Jw, const float* AA, const float* __restrict__ Opart,
                                                       size_t part_stride, int wo_lo = 0, int wo_hi = 0, DeferredStep ds = DeferredStep(),
-                                                      int clip_n = 0) {
+                                                      int clip_n = 0, const ClipRow* __restrict__ ctab = nullptr) {
     // clip_n > 0: a batch of clips of clip_n frames -- this frame's `scale` is its clip's (clip_of_row, fdc_loss.h)
+    // ctab != nullptr: a batch of clips of different lengths -- the clip comes from the frame's record
     __shared__ PoseScratch sc;
     __shared__ PoseStage stg;
     __shared__ float s_O[ODIM + 2];
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_fwd_kernel(PoseModel pm, co
         if (threadIdx.x >= 64) return;
         const float* x = X + (size_t)r * XDIM;
         M3 MR; V3 Mt;
-        world_matrix(CAM + (size_t)r * 16, x, scale[clip_of_row(r, clip_n)], &MR, &Mt);
+        world_matrix(CAM + (size_t)r * 16, x, scale[clip_of_row(r, clip_n, ctab)], &MR, &Mt);
         const V3 transl = v3(x[X_TRANSL], x[X_TRANSL + 1], x[X_TRANSL + 2]);
         const int j = threadIdx.x;
         if (j < NJW) {
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_fwd_kernel(PoseModel pm, co
             for (int q = 0; q < VP_NQ; ++q) glds4<2>(Opart + (size_t)q * part_stride + (size_t)r * ODIM, s_Op[q], ODIM);
         }
     }
-    const float sc_v = scale[clip_of_row(r, clip_n)];
+    const float sc_v = scale[clip_of_row(r, clip_n, ctab)];
     // A deferred optimiser step (DeferredStep, fdc_loss.h): this frame's row of body_rotation_rec / camera_ext takes its pending
     // Adam update here -- the loads ride in the staging batch, the stepped row goes to LDS (where the copy of the old one would
     // have gone) and back to global memory with both moments.
@@ -258,7 +259,9 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
                                                       const float* dMv, const float* dsv, const float* dbeta_v,
                                                       int dbeta_stride, const float* dtransl_v, float* dX, float* dO,
                                                       float* dCAM, float* dscale_row, ParamLossIn pl, const float* dPF2, int dA_nj = NJ,
-                                                      int clip_n = 0) {
+                                                      int clip_n = 0, const ClipRow* __restrict__ ctab = nullptr) {
+    // ctab != nullptr: a batch of clips of different lengths -- the frame's clip, its index within it, the clip's length and the
+    // clip's three weights come from the frame's record (requested here with the staging copies) instead of pl and clip_n
     // clip_n > 0: a batch of clips of clip_n frames (fdcap_opt_create_clips): the frame's `scale` is its clip's, and the temporal
     // stencils of the fused prologue see the frame's index within its clip (pl.frame0 = 0, pl.n_total = clip_n): cut at clip boundaries
     // dA_nj: rows of dA that were written (the rest are zero: SkinModel::ja_hi)
@@ -315,7 +318,14 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
         stage_pose_part<3>(pm, stg, xrow, camrow);
         glds4<2>(dX + (size_t)r * XDIM, s_dx, XDIM);         // the row a separate param_loss_kernel launch initialised
     }
-    const float sc_v = scale[clip_of_row(r, clip_n)];
+    int pl_g = clip_n > 0 ? (int)blockIdx.x % clip_n : pl.frame0 + (int)blockIdx.x, pl_n = pl.n_total, clip_k = clip_of_row(r, clip_n);
+    float w_rec = pl.w_rec, w_sm = pl.w_sm, w_ws = pl.w_ws;
+    if (ctab) {                                              // (kernel-uniform; wave-uniform scalar loads)
+        const clip_row_cptr cr = clip_row_at(ctab, r);
+        clip_k = cr->k; pl_g = cr->g; pl_n = cr->n;
+        w_rec = cr->w_rec; w_sm = cr->w_sm; w_ws = cr->w_ws;
+    }
+    const float sc_v = scale[clip_k];
     __shared__ float s_csum[POSE_NW];
     if (pl.cdist) {                                          // (kernel-uniform) contact_loss_rows_kernel's sum, same threads, same order
         float v = 0.f;
@@ -337,7 +347,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
     if (pl.X0) {
         // param_loss_kernel's gradients formed here: dX row (=) data + temporal terms on the raw rows, world-smoothing
         // gradient of this frame's joints into LDS instead of a round trip through dJw
-        const int g = clip_n > 0 ? (int)blockIdx.x % clip_n : pl.frame0 + (int)blockIdx.x;
+        const int g = pl_g;
         const float lmask = s_misc[27];
         float l_rec = 0.f, l_vp = 0.f, l_sm = 0.f, l_ws = 0.f;
         // (two waves side by side: the first takes the parameter row's terms, the second the world joints')
@@ -345,9 +355,9 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
             for (int e = threadIdx.x; e < XDIM; e += 64) {
                 const float xc = stg.x[e];
                 float rec = 0.f, sm = 0.f;
-                s_dx[e] = param_loss_grad(g, pl.n_total, g >= 2 ? s_xn[0][e] : 0.f, g >= 1 ? s_xn[1][e] : 0.f, xc,
-                                          g + 1 < pl.n_total ? s_xn[2][e] : 0.f, g + 2 < pl.n_total ? s_xn[3][e] : 0.f,
-                                          s_x0[e], lmask, pl.w_rec, pl.w_sm, &rec, &sm);
+                s_dx[e] = param_loss_grad(g, pl_n, g >= 2 ? s_xn[0][e] : 0.f, g >= 1 ? s_xn[1][e] : 0.f, xc,
+                                          g + 1 < pl_n ? s_xn[2][e] : 0.f, g + 2 < pl_n ? s_xn[3][e] : 0.f,
+                                          s_x0[e], lmask, w_rec, w_sm, &rec, &sm);
                 l_rec += rec; l_sm += sm;
                 if (e >= X_LATENT && e < X_LATENT + 32) l_vp += xc * xc;
             }
@@ -361,8 +371,8 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
         } else if (threadIdx.x < 128 && (pl.world_grad || pl.loss_rows)) {
             for (int e = threadIdx.x - 64; e < NJW * 3; e += 64) {
                 float ws = 0.f;
-                s_dJw[e] = world_smooth_grad(g, pl.n_total, g >= 1 ? s_jw[0][e] : 0.f, s_jw[1][e], g + 1 < pl.n_total ? s_jw[2][e] : 0.f,
-                                             pl.w_ws, &ws);
+                s_dJw[e] = world_smooth_grad(g, pl_n, g >= 1 ? s_jw[0][e] : 0.f, s_jw[1][e], g + 1 < pl_n ? s_jw[2][e] : 0.f,
+                                             w_ws, &ws);
                 l_ws += ws;
             }
             if (pl.loss_rows) {

@@ -9,8 +9,9 @@ namespace {
 __global__ __launch_bounds__(256) void skin_fwd_kernel(SkinModel sm, int nv, const float* __restrict__ X, int ldx, int beta_off, int transl_off,
                                 const float* __restrict__ Voff, const float* __restrict__ A,
                                 const float* __restrict__ M, const float* __restrict__ scale, int row0, int world,
-                                float* __restrict__ Vout, int clip_n = 0) {
-    // (clip_n > 0: a batch of clips of clip_n frames -- the frame's `scale` is its clip's, clip_of_row in fdc_loss.h)
+                                float* __restrict__ Vout, int clip_n = 0, const ClipRow* __restrict__ ctab = nullptr) {
+    // (clip_n > 0: a batch of clips of clip_n frames -- the frame's `scale` is its clip's, clip_of_row in fdc_loss.h;
+    //  ctab != nullptr: clips of different lengths, the clip comes from the frame's record)
     // the frame's 55 skinning transforms staged in LDS once per block: per vertex they are reached through its joint
     // ids (a dependent load chain from global memory otherwise).  By LDS-DMA, with the vertex's own loads issued before
     // the barrier: one cold round trip (the copy loop that was here waited for each of its three trips, then the
@@ -26,7 +27,7 @@ __global__ __launch_bounds__(256) void skin_fwd_kernel(SkinModel sm, int nv, con
 #pragma unroll
         for (int e = 0; e < 12; ++e) Mr[e] = M[(size_t)r * 12 + e];
     }
-    const float sc_v = world ? scale[clip_of_row(r, clip_n)] : 1.f;
+    const float sc_v = world ? scale[clip_of_row(r, clip_n, ctab)] : 1.f;
     float* o = Vout + ((size_t)r * nv + c) * 3;
     if (sm.vpack && !FDC_SKIN_HAS_S(sm)) {
         // packed per-vertex constants (two 16-byte loads instead of eleven 4-byte ones); same terms, same order
@@ -81,9 +82,12 @@ __global__ __launch_bounds__(768) void blend_skin_fwd_kernel(const float* __rest
                                                              const float* __restrict__ X, int ldx, int transl_off,
                                                              const float* __restrict__ A, const float* __restrict__ Mw,
                                                              const float* __restrict__ scale, int row0, float* __restrict__ Voff,
-                                                             float* __restrict__ Vw, int clip_n = 0) {
+                                                             float* __restrict__ Vw, int clip_n = 0,
+                                                             const ClipRow* __restrict__ ctab = nullptr) {
     // clip_n > 0: a batch of clips of clip_n frames.  The workgroup's 32 frames may straddle a clip boundary (clip_n % 32 != 0):
     // `scale` is then looked up per frame; a workgroup whose frames lie in one clip keeps the one wave-uniform value
+    // ctab != nullptr: clips of different lengths -- the 32 frames may span more than two clips; the wave-uniform value serves when
+    // the first and the last frame share a clip (clips are contiguous), else each frame looks its clip up in its record
     extern __shared__ __attribute__((aligned(16))) uint4 bs_lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
     const int cb = blockIdx.x & 7, m0 = (int)(blockIdx.x >> 3) * 32;
@@ -128,8 +132,8 @@ __global__ __launch_bounds__(768) void blend_skin_fwd_kernel(const float* __rest
         }
     }
     const int vv = tid & 63, v = cb * 64 + vv;
-    const int clip_lo = clip_of_row(row0 + m0, clip_n);
-    const bool one_clip = clip_of_row(row0 + min(m0 + 31, M - 1), clip_n) == clip_lo;
+    const int clip_lo = clip_of_row(row0 + m0, clip_n, ctab);
+    const bool one_clip = clip_of_row(row0 + min(m0 + 31, M - 1), clip_n, ctab) == clip_lo;
     const float sc_v = scale[clip_lo];
     PnF::stage<768, 2, 2>(bs_lds, img, PFr, NPFX, m0, M, 0, K, kpad, tid);
     __syncthreads();
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(768) void blend_skin_fwd_kernel(const float* __rest
             const V3 transl = v3(sT[4 * f], sT[4 * f + 1], sT[4 * f + 2]);
             const V3 vb = v3(T[0] * px + T[1] * py + T[2] * pz + T[3], T[4] * px + T[5] * py + T[6] * pz + T[7],
                              T[8] * px + T[9] * py + T[10] * pz + T[11]) + transl;
-            const V3 sv = (one_clip ? sc_v : scale[clip_of_row((int)r, clip_n)]) * vb;
+            const V3 sv = (one_clip ? sc_v : scale[ctab ? ctab[r].k : clip_of_row((int)r, clip_n)]) * vb;
             const float* Mr = sM + 12 * f;
             float* const o = Vw + (r * nv + v) * 3;
             o[0] = Mr[0] * sv.x + Mr[1] * sv.y + Mr[2] * sv.z + Mr[3];
@@ -249,8 +253,9 @@ __global__ __launch_bounds__(256, FDC_SKB_OCC) void skin_bwd_kernel(SkinModel sm
                                                        float* __restrict__ dA, float* __restrict__ dbeta_v,
                                                        float* __restrict__ dtransl_v, float* __restrict__ dMv,
                                                        float* __restrict__ dsv, ContactGradIn cg, float* __restrict__ part = nullptr,
-                                                       int clip_n = 0) {
-    // (clip_n > 0: a batch of clips of clip_n frames -- the frame's `scale` is its clip's, clip_of_row in fdc_loss.h)
+                                                       int clip_n = 0, const ClipRow* __restrict__ ctab = nullptr) {
+    // (clip_n > 0: a batch of clips of clip_n frames -- the frame's `scale` is its clip's, clip_of_row in fdc_loss.h;
+    //  ctab != nullptr: clips of different lengths -- the clip and the contact term's coefficient come from the frame's record)
     constexpr int VCH = SKB_VCH;
     extern __shared__ float sdT[];                 // [min(nc, VCH) * 12] (dynamic: 500 contact vertices leave room for 6 workgroups per CU)
     __shared__ float sdA[NJ * 12];
@@ -259,7 +264,10 @@ __global__ __launch_bounds__(256, FDC_SKB_OCC) void skin_bwd_kernel(SkinModel sm
     const int r = row0 + blockIdx.x;
     FDC_FR_STAMP(2, 0);
     const float* x = X + (size_t)r * XDIM;
-    const float s = scale[clip_of_row(r, clip_n)];
+    int clip_k = clip_of_row(r, clip_n);
+    float ccoef = cg.coef;                         // the contact term's coefficient: its clip's with clips of different lengths (ctab)
+    if (ctab) { const clip_row_cptr cr = clip_row_at(ctab, r); clip_k = cr->k; ccoef = cr->coef; }     // (kernel-uniform; scalar loads)
+    const float s = scale[clip_k];
     V3 transl = v3(x[X_TRANSL], x[X_TRANSL + 1], x[X_TRANSL + 2]);
     float acc[SKB_NACC];
     float cterm = 0.f;
@@ -299,7 +307,7 @@ __global__ __launch_bounds__(256, FDC_SKB_OCC) void skin_bwd_kernel(SkinModel sm
             if (CONTACT) {
                 float dterm;
                 cterm += contact_term(dq, &dterm);
-                const float gg = jq >= 0 ? 2.f * cg.coef * dterm : 0.f;          // no neighbour (NaN query): zero gradient
+                const float gg = jq >= 0 ? 2.f * ccoef * dterm : 0.f;          // no neighbour (NaN query): zero gradient
                 if (!cg.nnpt && jq >= 0) pq = cg.scene[jq];
                 if (jq < 0) pq = make_float4(0.f, 0.f, 0.f, 0.f);
                 g = v3(gg * (vwx - pq.x), gg * (vwy - pq.y), gg * (vwz - pq.z));
@@ -540,7 +548,8 @@ __global__ __launch_bounds__(256) void skin_bwd_small_kernel(SkinModel sm, int n
                                                              const float* __restrict__ M, const float* __restrict__ scale,
                                                              int row0, float* __restrict__ dVoff, float* __restrict__ dA,
                                                              float* __restrict__ dtransl_v, float* __restrict__ dMv,
-                                                             float* __restrict__ dsv, ContactGradIn cg, int clip_n = 0) {
+                                                             float* __restrict__ dsv, ContactGradIn cg, int clip_n = 0,
+                                                             const ClipRow* __restrict__ ctab = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float sk_lds[];
     // dynamic: sGV [nc][3] | sVP [nc][3] | csc_w [nnz] | csc_v [nnz] (ushort)
     float* const sGV = sk_lds;
@@ -555,7 +564,10 @@ __global__ __launch_bounds__(256) void skin_bwd_small_kernel(SkinModel sm, int n
     const int r = row0 + blockIdx.x;
     FDC_FR_STAMP(2, 0);
     const float* x = X + (size_t)r * XDIM;
-    const float s = scale[clip_of_row(r, clip_n)];
+    int clip_k = clip_of_row(r, clip_n);
+    float ccoef = cg.coef;                         // the contact term's coefficient: its clip's with clips of different lengths (ctab)
+    if (ctab) { const clip_row_cptr cr = clip_row_at(ctab, r); clip_k = cr->k; ccoef = cr->coef; }     // (kernel-uniform; scalar loads)
+    const float s = scale[clip_k];
     const V3 transl = v3(x[X_TRANSL], x[X_TRANSL + 1], x[X_TRANSL + 2]);
     float Mr[12];
 #pragma unroll
@@ -621,7 +633,7 @@ __global__ __launch_bounds__(256) void skin_bwd_small_kernel(SkinModel sm, int n
             f.vb = vl + transl;
             float dterm;
             cterm += contact_term(dq[u], &dterm);
-            const float gg = jq[u] >= 0 ? 2.f * cg.coef * dterm : 0.f;          // no neighbour (NaN query): zero gradient
+            const float gg = jq[u] >= 0 ? 2.f * ccoef * dterm : 0.f;          // no neighbour (NaN query): zero gradient
             float4 pt = pq[u];
             if (!cg.nnpt && jq[u] >= 0) pt = cg.scene[jq[u]];
             if (jq[u] < 0) pt = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -698,7 +710,8 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
                                                            const float* __restrict__ M, const float* __restrict__ scale,
                                                            int row0, float* __restrict__ dVoff, float* __restrict__ dA,
                                                            float* __restrict__ dtransl_v, float* __restrict__ dMv,
-                                                           float* __restrict__ dsv, ContactGradIn cg, int clip_n = 0) {
+                                                           float* __restrict__ dsv, ContactGradIn cg, int clip_n = 0,
+                                                           const ClipRow* __restrict__ ctab = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float sk_lds[];
     // dynamic: sGV [nc][3] (Vw, then gv) | sVP [nc][3] (Voff, then vp) | sDV [nc][3] | csc_w [nnz4] | csc_v [nnz8] (ushort)
     const int nnz4 = (nnz + 3) & ~3, nnz8 = (nnz + 7) & ~7;
@@ -715,7 +728,10 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
     const int r = row0 + blockIdx.x;
     FDC_FR_STAMP(2, 0);
     const float* x = X + (size_t)r * XDIM;
-    const float s = scale[clip_of_row(r, clip_n)];
+    int clip_k = clip_of_row(r, clip_n);
+    float ccoef = cg.coef;                         // the contact term's coefficient: its clip's with clips of different lengths (ctab)
+    if (ctab) { const clip_row_cptr cr = clip_row_at(ctab, r); clip_k = cr->k; ccoef = cr->coef; }     // (kernel-uniform; scalar loads)
+    const float s = scale[clip_k];
     const V3 transl = v3(x[X_TRANSL], x[X_TRANSL + 1], x[X_TRANSL + 2]);
     float Mr[12];
 #pragma unroll
@@ -778,7 +794,7 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
             f.vb = vl + transl;
             float dterm;
             cterm += contact_term(ldq[u], &dterm);
-            const float gg = ljq[u] >= 0 ? 2.f * cg.coef * dterm : 0.f;         // no neighbour (NaN query): zero gradient
+            const float gg = ljq[u] >= 0 ? 2.f * ccoef * dterm : 0.f;         // no neighbour (NaN query): zero gradient
             float4 pt = lpq[u];
             if (!cg.nnpt && ljq[u] >= 0) pt = cg.scene[ljq[u]];
             if (ljq[u] < 0) pt = make_float4(0.f, 0.f, 0.f, 0.f);

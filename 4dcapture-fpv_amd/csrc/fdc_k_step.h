@@ -158,11 +158,13 @@ __global__ __launch_bounds__(128) void param_loss_kernel(const float* __restrict
 // (dscale_out may be null: the launch that also steps `scale` forms that sum itself, in the same order)
 __global__ __launch_bounds__(256) void loss_rows_reduce_kernel(const float* __restrict__ rows, int row0, int n, unsigned mask, int assign,
                                                                double* __restrict__ losses, const float* __restrict__ dscale_row,
-                                                               float* __restrict__ dscale_out) {
+                                                               float* __restrict__ dscale_out, const int* __restrict__ clip_span = nullptr) {
     // (a batch of clips: one workgroup per clip, n = one clip's rows; clip k's sums go to losses + k FDCAP_NUM_LOSSES, its
-    //  scale gradient to dscale_out[k])
+    //  scale gradient to dscale_out[k].  clip_span != nullptr: clips of different lengths, ScaleTail::clip_span)
     const int k = blockIdx.x;
-    loss_rows_reduce_block(rows, row0 + k * n, n, mask, assign, losses ? losses + (size_t)k * LROW : losses, dscale_row,
+    int start = k * n;
+    if (clip_span) clip_span_at(clip_span, k, &start, &n);
+    loss_rows_reduce_block(rows, row0 + start, n, mask, assign, losses ? losses + (size_t)k * LROW : losses, dscale_row,
                            dscale_out ? dscale_out + k : dscale_out);
 }
 
@@ -197,13 +199,17 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamTensor x, AdamTensor
                                                         const float* __restrict__ dscale_row, int row0, int reduce_n,
                                                         float* __restrict__ dscale, int scale_zero_grad,
                                                         float* __restrict__ xch, int n_local, const float* __restrict__ cam_rows,
-                                                        const float* __restrict__ dzpart, size_t dz_stride, LogReduceIn lg, int nclip = 1) {
+                                                        const float* __restrict__ dzpart, size_t dz_stride, LogReduceIn lg, int nclip = 1,
+                                                        const int* __restrict__ clip_span = nullptr) {
     // nclip > 1: a batch of clips -- blocks nb_x + nb_cam + k step clip k's `scale` (sc.p + k, reduced over that clip's reduce_n
     // rows), blocks nb_x + nb_cam + nclip + k reduce its logged sums (lg.n rows) into lg.losses + k FDCAP_NUM_LOSSES
+    // (clip_span != nullptr: clips of different lengths -- clip k's first row and row count come from it, ScaleTail::clip_span)
     const int b = blockIdx.x;
     if (b >= nb_x + nb_cam + nclip) {                  // (only launched when a logging backward left its sums to this launch)
         const int k = b - (nb_x + nb_cam + nclip);
-        loss_rows_reduce_block(lg.rows, row0 + k * lg.n, lg.n, lg.mask, lg.assign, lg.losses + (size_t)k * LROW, dscale_row, nullptr);
+        int start = k * lg.n, n = lg.n;
+        if (clip_span) clip_span_at(clip_span, k, &start, &n);
+        loss_rows_reduce_block(lg.rows, row0 + start, n, lg.mask, lg.assign, lg.losses + (size_t)k * LROW, dscale_row, nullptr);
         return;
     }
     if (b < nb_x + nb_cam) {
@@ -235,8 +241,14 @@ __global__ __launch_bounds__(256) void adam_step_kernel(AdamTensor x, AdamTensor
     }
     __shared__ float sred[4];
     const int k = b - (nb_x + nb_cam);                 // (the clip whose `scale` this block steps)
-    if (k > 0) {
+    if (clip_span) {                                   // (kernel-uniform) its own rows, summed relative to its first one
+        int start, n;
+        clip_span_at(clip_span, k, &start, &n);
+        row0 += start;
+        if (reduce_n > 0) reduce_n = n;
+    } else if (k > 0)
         row0 += k * reduce_n;
+    if (k > 0) {
         dscale += k;
         if (sc.p) { sc.p += k; sc.m += k; sc.v += k; }
     }

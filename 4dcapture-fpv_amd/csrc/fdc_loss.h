@@ -3,6 +3,7 @@
 // :266-267 (loss_smoothing), :304 (loss_world_smoothing), :262-263 (loss_vposer, logged only)
 // and torch.optim.Adam's single-tensor update (:188, :592).
 #pragma once
+#include "fdc_clips.h"
 #include "fdc_math.h"
 
 namespace fdc {
@@ -44,6 +45,22 @@ FDC_HD float world_smooth_grad(int g, int n_total, float jm1, float j0, float jp
 // A batch of clips (fdcap_opt_create_clips): clip k owns rows 2 + k clip_n .. 2 + (k + 1) clip_n of the optimiser's buffers and its
 // own `scale` (scale[k]).  clip_n = 0: the optimiser holds one clip (or one rank's share of one): every row reads scale[0].
 FDC_HD int clip_of_row(int r, int clip_n) { return clip_n > 0 ? (r - 2) / clip_n : 0; }
+// A batch of clips of DIFFERENT lengths (fdcap_opt_create_clips_var, fdc_clips.h): the kernels take clip_n = 0 and a table of one
+// ClipRow per buffer row (`ctab`, null for every other optimiser: the branch on it is kernel-uniform).  A workgroup that serves
+// one row reads its record through the constant address space -- wave-uniform, so scalar loads the compiler merges into one --
+// with its first batch of loads; only scale[k] depends on it.
+#if defined(__HIPCC__)
+typedef const ClipRow __attribute__((address_space(4)))* clip_row_cptr;
+__device__ __forceinline__ clip_row_cptr clip_row_at(const ClipRow* ctab, int r) { return (clip_row_cptr)(const void*)ctab + r; }
+// the clip whose `scale` row r reads (r wave-uniform)
+__device__ __forceinline__ int clip_of_row(int r, int clip_n, const ClipRow* ctab) { return ctab ? clip_row_at(ctab, r)->k : clip_of_row(r, clip_n); }
+// {first row relative to the batch's first, rows} of clip k for the per-clip tail workgroups (`span`: [K][2], null for equal lengths)
+__device__ __forceinline__ void clip_span_at(const int* span, int k, int* start, int* n) {
+    typedef const int __attribute__((address_space(4)))* cint_ptr;
+    const cint_ptr p = (cint_ptr)(const void*)span + 2 * k;
+    *start = p[0]; *n = p[1];
+}
+#endif
 
 struct AdamScalars { float one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps; };
 struct AdamTensor { float* p; float* m; float* v; const float* g; size_t n; AdamScalars a; };
@@ -80,7 +97,9 @@ struct ScaleTail {
     int lg_spread = 0;
     // a batch of nclip clips (fdcap_opt_create_clips): workgroups block .. block + nclip - 1 are the tails, tail k serves clip k --
     // rows row0 + k clip_n .., scale / moments / dscale + k, losses + k FDCAP_NUM_LOSSES (n, lg.n: one clip's rows)
+    // (clip_span != nullptr: clips of different lengths -- clip k's rows start at row0 + clip_span[2 k] and number clip_span[2 k + 1])
     int nclip = 1, clip_n = 0;
+    const int* clip_span = nullptr;
 };
 
 // torch.optim.Adam defaults: betas (0.9, 0.999), eps 1e-8; the bias corrections are evaluated
@@ -184,8 +203,15 @@ __device__ __forceinline__ void loss_rows_reduce_block(const float* __restrict__
 }
 // clip k's share of a batch's tail (k = 0: the tail itself)
 __device__ __forceinline__ ScaleTail scale_tail_clip(ScaleTail t, int k) {
-    if (k > 0) {
+    if (t.clip_span) {                                       // (kernel-uniform) its own start and length; summed relative to its first row
+        int start, n;
+        clip_span_at(t.clip_span, k, &start, &n);
+        t.row0 += start;
+        t.n = t.n > 0 ? n : 0;
+        t.lg.n = n;
+    } else if (k > 0)
         t.row0 += k * t.clip_n;
+    if (k > 0) {
         if (t.sc.p) { t.sc.p += k; t.sc.m += k; t.sc.v += k; }
         if (t.dscale) t.dscale += k;
         if (t.lg.losses) t.lg.losses += (size_t)k * LROW;

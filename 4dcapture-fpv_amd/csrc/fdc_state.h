@@ -53,18 +53,18 @@ struct DevBuf {
 template <bool CONTACT>
 static int skin_bwd_any(DevBuf<float>& part, hipStream_t st, int nrows, SkinModel sm, int nc, const float* X, const float* Voff, const float* A,
                         const float* M, const float* scale, int row0, const float* dVw, float* dVoff, float* dA, float* dbeta_v,
-                        float* dtransl_v, float* dMv, float* dsv, ContactGradIn cg, int clip_n = 0) {
+                        float* dtransl_v, float* dMv, float* dsv, ContactGradIn cg, int clip_n = 0, const ClipRow* ctab = nullptr) {
     const SkinBwdPlan pl = plan_skin_bwd_any(nrows, nc, sm.wf_tab != nullptr);
     note_form(form_name(pl.form));
     if (pl.form == F_SKIN_BWD_FRAME) {
         hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, false>), dim3(pl.grid), dim3(pl.block), pl.lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
-                           dbeta_v, dtransl_v, dMv, dsv, cg, (float*)nullptr, clip_n);
+                           dbeta_v, dtransl_v, dMv, dsv, cg, (float*)nullptr, clip_n, ctab);
         return (int)hipGetLastError();
     }
     hipError_t e = part.ensure((size_t)nrows * pl.nch * SKP_STRIDE);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((skin_bwd_kernel<CONTACT, true>), dim3(pl.grid, pl.nch), dim3(pl.block), pl.lds, st, sm, nc, X, Voff, A, M, scale, row0, dVw, dVoff, dA,
-                       dbeta_v, dtransl_v, dMv, dsv, cg, part.p, clip_n);
+                       dbeta_v, dtransl_v, dMv, dsv, cg, part.p, clip_n, ctab);
     hipLaunchKernelGGL(skin_bwd_reduce_kernel, dim3(nrows), dim3(256), 0, st, part.p, pl.nch, row0, dA, dbeta_v, dtransl_v, dMv, dsv,
                        CONTACT ? cg.loss_rows : (float*)nullptr);
     return (int)hipGetLastError();
@@ -108,9 +108,22 @@ struct OptState {
     // the clips this optimiser holds: nclip clips of clip_len frames each, clip k in rows 2 + k clip_len .. (one clip or one rank's
     // share of one: nclip = 1, clip_len = n_total).  Each clip has its own scale / moments / dscale / losses slot.
     int nclip = 1, clip_len = 0;
-    // what the kernels take as clip_n (clip_of_row, fdc_loss.h): 0 unless the optimiser holds several clips
+    // clips of DIFFERENT lengths (fdcap_opt_create_clips_var, fdc_clips.h): clip k has clip_lens[k] frames in rows 2 + clip_start[k] ..;
+    // clip_len = 0.  The kernels then take clip_n = 0 and the device tables: clip_rows [2][R] ClipRow -- one record per buffer row
+    // with the clip's weights of phase 1, then of phase 2 (the only two weight sets mode 'global' has: built once per create, so
+    // no upload in the loop) -- and clip_span [nclip][2] {start, length} for the per-clip tail workgroups.
+    bool ragged = false;
+    std::vector<int32_t> clip_lens, clip_start;
+    DevBuf<ClipRow> clip_rows;
+    DevBuf<int> clip_span;
+    const ClipRow* ctab(bool phase2) const { return ragged ? clip_rows.p + (phase2 ? (size_t)R : 0) : nullptr; }
+    const int* cspan() const { return ragged ? clip_span.p : nullptr; }
+    // what the kernels take as clip_n (clip_of_row, fdc_loss.h): 0 unless the optimiser holds several clips of one length
     int kclip_n() const { return nclip > 1 ? clip_len : 0; }
-    int rows_per_clip() const { return cfg.n_local / nclip; }
+    // one clip's rows.  Clips of different lengths have no such number: 1, which only says "there are rows" to the tail workgroups
+    // (ScaleTail::n, LogReduceIn::n, adam_step_kernel's reduce_n) -- every launch that takes it also takes cspan(), and the
+    // kernels read each clip's start and count from there
+    int rows_per_clip() const { return ragged ? 1 : cfg.n_local / nclip; }
     bool contact_on = false;
     int nsplit = 8;           // scene splits of the in-loop NN launch
     int nsplit_bf = 8;        // ... of a brute-force launch (timing API)
@@ -669,7 +682,7 @@ int opt_pose_forward(fdcap_ctx* c, int lo, int hi, hipStream_t st, bool contact_
                        (float*)nullptr,
 #endif
                        contact_state ? o->PF.p : (float*)nullptr, o->Jrest.p, o->G.p, contact_state ? o->A.p : (float*)nullptr, o->M.p, o->Jw.p,
-                       (const float*)nullptr, (const float*)o->Opart.p, ps, 0, 0, ds, o->kclip_n());
+                       (const float*)nullptr, (const float*)o->Opart.p, ps, 0, 0, ds, o->kclip_n(), o->ctab(false));
     lt_mark(o, FDCAP_LT_POSE_FWD, st);
     if (ds.on) {                                            // the step has been issued: the launches that follow see its results
         o->pend.on = false;
@@ -702,6 +715,7 @@ int opt_vposer_backward(fdcap_ctx* c, bool fold, hipStream_t st, ScaleTail tail 
     const int nb = 4 * ((nl + 15) / 16);
     if (tail.block >= 0) tail.block = 0;                   // (first in the grid: fdc_panel.h)
     tail.nclip = o->nclip; tail.clip_n = o->rows_per_clip();      // (a batch: one tail workgroup per clip)
+    tail.clip_span = o->cspan();
     const bool split3 = plan_decoder(gemm_split3_enabled()) == F_VPOSER_SPLIT;
     if (split3 && tail.lg.rows && nb >= LROW && o->nclip == 1) {
         tail.lg_spread = 1;                                // the logged sums: one regular workgroup per term (ScaleTail::lg_spread)

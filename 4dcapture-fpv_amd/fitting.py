@@ -875,10 +875,11 @@ class FittingOP:
 
 
 class ClipBatchFitter:
-    """Several clips of one scene as ONE optimisation (fdcap_opt_create_clips): K clips of N frames each share the scene, the
-    contact ids, the body model, VPoser and the configuration; each keeps its own rows, `scale`, Adam moments, outlier set, loss
-    means and logged sums, and the temporal stencils are cut at clip boundaries.  A clip's result equals its stand-alone
-    FittingOP fit bit for bit whenever both select the same kernel forms (include/fdcap.h).
+    """Several clips of one scene as ONE optimisation (fdcap_opt_create_clips): K clips share the scene, the contact ids, the
+    body model, VPoser and the configuration; each keeps its own rows, `scale`, Adam moments, outlier set, loss means (over its
+    own frames) and logged sums, and the temporal stencils are cut at clip boundaries.  The clips may have different lengths
+    (fdcap_opt_create_clips_var: clip k in rows clip_starts[k] .. + clip_lens[k] of the batch).  A clip's result equals its
+    stand-alone FittingOP fit bit for bit whenever both select the same kernel forms (include/fdcap.h).
 
     The fitter owns ONE context for its whole life -- the persistent worker: the body model and the contact ids are registered
     once, a scene once per run of batches of that scene (`fit(..., scene_key=...)` skips the registration when the key is the
@@ -927,9 +928,9 @@ class ClipBatchFitter:
         self.scene_key = key
 
     def fit(self, clips, scene_verts=None, scene_key=None, log_every=0):
-        """clips: sequence of K (body_data [N,75], camera_ext [N,4,4]) pairs (numpy or device tensors), one N for all.
+        """clips: sequence of K (body_data [N_k,75], camera_ext [N_k,4,4]) pairs (numpy or device tensors); every clip has its own N_k.
         scene_verts / scene_key: the batch's scene (see set_scene; both None: the registered scene).
-        Returns a list of K (body_rec [N,75] device tensor, scale numpy scalar, camera_ext [N,4,4] device tensor) -- what
+        Returns a list of K (body_rec [N_k,75] device tensor, scale numpy scalar, camera_ext [N_k,4,4] device tensor) -- what
         FittingOP.fitting returns for each clip -- and leaves each clip's FitLog in self.logs, its outlier rows in self.idx1."""
         if scene_verts is not None or scene_key is not None:
             self.set_scene(scene_verts, scene_key)
@@ -950,31 +951,44 @@ class ClipBatchFitter:
             bodies.append(b.to(dev, torch.float32))
             c = cam.detach().cpu().numpy() if torch.is_tensor(cam) else np.asarray(cam)
             cams.append(np.asarray(c, np.float32).reshape(-1, 16))
-        N = int(bodies[0].shape[0])
-        if any(int(b.shape[0]) != N for b in bodies) or any(c.shape[0] != N for c in cams):
-            raise capi.FdcapError("every clip of a batch has the same number of frames, and one camera pose per frame (:455)")
+        lens = [int(b.shape[0]) for b in bodies]
+        if min(lens) < 1 or any(c.shape[0] != n for c, n in zip(cams, lens)):
+            raise capi.FdcapError("every clip of a batch has at least one frame, and one camera pose per frame (:455)")
+        starts = [0]
+        for n in lens:
+            starts.append(starts[-1] + n)
+        total = starts[-1]
+        equal = all(n == lens[0] for n in lens)
         lib, h = self.ctx.lib, self.ctx.handle
         st = capi.current_stream()
         body = torch.cat(bodies).contiguous()
-        x78 = torch.empty(K * N, capi.XDIM, device=dev)
-        capi.check(lib.fdcap_params_75_to_78(capi.dptr(body), K * N, capi.dptr(x78), st), "fdcap_params_75_to_78")
-        # init() per clip (:459-487): outliers, their replacement rows and the mask of the data term, each clip on its own
+        x78 = torch.empty(total, capi.XDIM, device=dev)
+        capi.check(lib.fdcap_params_75_to_78(capi.dptr(body), total, capi.dptr(x78), st), "fdcap_params_75_to_78")
+        # init() per clip (:459-487): outliers, their replacement rows and the mask of the data term, each clip on its own rows
         x78_h = x78.cpu().numpy()
-        ins = [clip_inputs(x78_h[k * N:(k + 1) * N]) for k in range(K)]
+        ins = [clip_inputs(x78_h[starts[k]:starts[k + 1]]) for k in range(K)]
         self.idx1 = [i[0] for i in ins]
-        oc = capi.OptConfig(N, N, 0, float(self.init_lr_h), float(self.weight_loss_rec), float(self.weight_loss_vposer),
+        # one length: the clip's frames, as fdcap_opt_create_clips takes it; different lengths: the batch's rows
+        n_cfg = lens[0] if equal else total
+        oc = capi.OptConfig(n_cfg, n_cfg, 0, float(self.init_lr_h), float(self.weight_loss_rec), float(self.weight_loss_vposer),
                             float(self.weight_contact), PHASE1_CONTACT, PHASE1_SMOOTH, PHASE2_WORLD, PHASE2_SMOOTH, SCALE_INIT,
                             int(self.legacy_zero_grad))
-        R = K * N + 4
+        R = total + 4
         self._rows_x = torch.zeros(R, capi.XDIM, device=dev)
         self._rows_cam = torch.zeros(R, 16, device=dev)
         self._scale = torch.zeros(K, device=dev)
         self._dscale = torch.zeros(K, device=dev)
         self._losses = torch.zeros(K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
         torch.cuda.current_stream().synchronize()
-        capi.check(lib.fdcap_opt_create_clips(h, ctypes.byref(oc), K, capi.dptr(self._rows_x), capi.dptr(self._rows_cam),
-                                              capi.dptr(self._scale), capi.dptr(self._dscale), capi.dptr(self._losses)),
-                   "fdcap_opt_create_clips")
+        if equal:
+            capi.check(lib.fdcap_opt_create_clips(h, ctypes.byref(oc), K, capi.dptr(self._rows_x), capi.dptr(self._rows_cam),
+                                                  capi.dptr(self._scale), capi.dptr(self._dscale), capi.dptr(self._losses)),
+                       "fdcap_opt_create_clips")
+        else:
+            clip_len = (ctypes.c_int32 * K)(*lens)
+            capi.check(lib.fdcap_opt_create_clips_var(h, ctypes.byref(oc), K, clip_len, capi.dptr(self._rows_x), capi.dptr(self._rows_cam),
+                                                      capi.dptr(self._scale), capi.dptr(self._dscale), capi.dptr(self._losses)),
+                       "fdcap_opt_create_clips_var")
         self._has_opt = True
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         d_init = t(np.concatenate([i[1] for i in ins]))
@@ -982,14 +996,16 @@ class ClipBatchFitter:
         d_cam = t(np.concatenate(cams))
         capi.check(lib.fdcap_opt_set_inputs(h, capi.dptr(x78), capi.dptr(d_init), capi.dptr(d_mask), capi.dptr(d_cam), st),
                    "fdcap_opt_set_inputs")
-        self.num_clips, self.num_body = K, N
+        self.num_clips, self.clip_lens, self.clip_starts = K, lens, starts
+        self.num_body = lens[0] if equal else None           # (the one length of a batch of equal clips)
 
     def run(self, log_every=0):
         """The loop of the prepared batch (:558-593) and its results (see fit)."""
         import ctypes
         import os
         import torch
-        K, N, dev = self.num_clips, self.num_body, self.device
+        K, lens, starts, dev = self.num_clips, self.clip_lens, self.clip_starts, self.device
+        total = starts[-1]
         lib, h = self.ctx.lib, self.ctx.handle
         st = capi.current_stream()
         # the loop in the library, as FittingOP.fitting runs a plain fit: one fdcap_opt_run for all iterations
@@ -1006,23 +1022,24 @@ class ClipBatchFitter:
             if logged:
                 capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
         assert n_done.value == len(logged)
-        body_rec = torch.empty(K * N, capi.PDIM, device=dev)
+        body_rec = torch.empty(total, capi.PDIM, device=dev)
         scale = torch.empty(K, device=dev)
-        cam = torch.empty(K * N, 16, device=dev)
+        cam = torch.empty(total, 16, device=dev)
         capi.check(lib.fdcap_opt_get_results(h, capi.dptr(body_rec), capi.dptr(scale), capi.dptr(cam), st), "fdcap_opt_get_results")
         rows = hist.cpu().numpy()
         self.logs = []
         for k in range(K):
             log = FitLog([], [], [], [], [], [], [])
             for j, ii in enumerate(logged):
-                l_rec, l_vp, l_sm, l_con, l_ws, total = logged_losses(rows[j, k], N, self.ctx.num_contact, self.weight_loss_rec,
-                                                                      self.weight_loss_vposer, self.weight_contact, ii >= P)
+                # (the printed means of a clip run over its own frames)
+                l_rec, l_vp, l_sm, l_con, l_ws, tot = logged_losses(rows[j, k], lens[k], self.ctx.num_contact, self.weight_loss_rec,
+                                                                    self.weight_loss_vposer, self.weight_contact, ii >= P)
                 log.iters.append(ii); log.l_rec.append(l_rec); log.l_vposer.append(l_vp)
                 log.loss_smoothing.append(l_sm); log.loss_contact.append(l_con)
-                log.loss_world_smoothing.append(l_ws); log.total.append(total)
+                log.loss_world_smoothing.append(l_ws); log.total.append(tot)
             self.logs.append(log)
         sc = scale.cpu().numpy()
-        return [(body_rec[k * N:(k + 1) * N], sc[k], cam[k * N:(k + 1) * N].view(N, 4, 4)) for k in range(K)]
+        return [(body_rec[starts[k]:starts[k + 1]], sc[k], cam[starts[k]:starts[k + 1]].view(lens[k], 4, 4)) for k in range(K)]
 
     def close(self):
         if getattr(self, "ctx", None) is not None:

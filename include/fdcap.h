@@ -226,6 +226,19 @@ int fdcap_opt_create(fdcap_ctx* ctx, const fdcap_opt_config* cfg, float* rows_x_
  * flags bit 1).  FDCAP_E_ARG: n_clips < 1, or n_clips > 1 with frame0 != 0 or n_local != n_total. */
 int fdcap_opt_create_clips(fdcap_ctx* ctx, const fdcap_opt_config* cfg, int32_t n_clips, float* rows_x_d, float* rows_cam_d,
                            float* scale_d, float* dscale_d, double* losses_d);
+/* The same batch with clips of their OWN lengths clip_len[0 .. n_clips) (host array, copied): clip k owns rows 2 + s_k .. 2 + s_k +
+ * clip_len[k], s_k = clip_len[0] + .. + clip_len[k-1].  cfg: frame0 == 0 and n_total == n_local == the sum of the lengths; the
+ * buffers are [sum + 4, .] rows, scale_d / dscale_d / losses_d per clip as above.  Same contract: every clip's means run over its
+ * own frame count, its stencils end at its own first and last frame, and its results equal its stand-alone fit bit for bit when
+ * both select the same kernel forms (a clip of one or two frames has no smoothing term, of one frame no world-smoothing term, as in
+ * a stand-alone fit).  Everything above that covers "n_clips*N rows" covers the sum; the state of fdcap_opt_export_state is
+ * [m_x sum*78 | v_x | m_cam sum*16 | v_cam | m_scale n_clips | v_scale n_clips].  Everything fdcap_opt_create_clips refuses with
+ * n_clips > 1 is refused the same way.  Equal lengths ARE fdcap_opt_create_clips' batch (same kernels' arithmetic on the one
+ * length, same bits); with different lengths the per-frame kernels read each frame's clip, index, length and normalised weights
+ * from a small device table built here from cfg (csrc/fdc_clips.h).
+ * FDCAP_E_ARG: clip_len NULL, a length <= 0, a sum that is not cfg->n_total == cfg->n_local or exceeds 2^24, frame0 != 0. */
+int fdcap_opt_create_clips_var(fdcap_ctx* ctx, const fdcap_opt_config* cfg, int32_t n_clips, const int32_t* clip_len, float* rows_x_d,
+                               float* rows_cam_d, float* scale_d, float* dscale_d, double* losses_d);
 /* data78_d [n_local,78]: the 6D-converted SMPLify-X rows (loss_rec target);
  * init78_d [n_local,78]: initial value of body_rotation_rec (= data with outlier rows replaced, :487);
  * mask_d   [n_local]   : 0 for outlier rows (idx1), 1 otherwise (:255-257);

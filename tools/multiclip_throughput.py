@@ -7,7 +7,10 @@
     each), host clock from the first constructor to the last result on the host;
   - the live per-launch table at K = 3 (fdcap_opt_launch_timing, as tools/launch_times.py reads it).
 Prints one JSON line (profiles/r7_multiclip300.json).
-usage: python tools/multiclip_throughput.py [--reps R] [--out FILE]"""
+--lengths n0,n1,... (may be repeated): instead of the sweep, a batch of clips of THOSE lengths (fdcap_opt_create_clips_var when they
+differ) under the same protocol -- one warm-up fit, R timed fits that end in a synchronise -- with ms per batch, us per iteration,
+frames/s and the live per-launch table; one entry per --lengths, all on one fitter.
+usage: python tools/multiclip_throughput.py [--reps R] [--out FILE] [--lengths n0,n1,...]..."""
 import json
 import os
 import sys
@@ -25,12 +28,15 @@ N, ITERS, NS, KS = 300, 500, 500_000, (1, 2, 3, 4, 6, 8)
 
 def main():
     argv = sys.argv[1:]
-    reps, out = 3, None
+    reps, out, lengths = 3, None, []
     while argv:
         if argv[0] == "--reps":
             reps, argv = int(argv[1]), argv[2:]
         elif argv[0] == "--out":
             out, argv = argv[1], argv[2:]
+        elif argv[0] == "--lengths":
+            lengths.append([int(t) for t in argv[1].split(",")])
+            argv = argv[2:]
         else:
             raise SystemExit(__doc__)
     import fdcap_amd  # noqa: F401
@@ -42,6 +48,8 @@ def main():
     scene = synth.make_scene(NS, seed=2)
     left, right = synth.make_contact_ids(bm.v_template, per_part=250, seed=4)
     vid = np.concatenate([left, right])
+    if lengths:
+        return ragged(lengths, reps, out, bm, vp, scene, vid)
     clips = []
     for k in range(12):
         c = synth.make_clip(N, seed=100 + k)
@@ -101,6 +109,48 @@ def main():
     res["twelve_clips"] = {"clips_per_batch": k_def, "batch_driver_s": t_batch, "fittingop_each_s": t_single,
                            "batch_driver_frames_per_s": 12 * N / t_batch, "fittingop_each_frames_per_s": 12 * N / t_single,
                            "note": "host clock from the first constructor to the last result on the host; model and scene arrays in memory"}
+    res["device"] = torch.cuda.get_device_name(0)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out:
+        with open(out, "w") as fh:
+            fh.write(line + "\n")
+
+
+def ragged(lengths, reps, out, bm, vp, scene, vid):
+    """One entry per list of lengths: the sweep's protocol on a batch of clips of those lengths."""
+    from fdcap_amd import synth
+    from fdcap_amd.fitting import ClipBatchFitter
+    from fdcap_amd.io import read_camerapose
+    res = {"problem": {"verts": 10475, "contacts": len(vid), "scene": NS, "iters": ITERS, "reps": reps}, "batches": []}
+    fitter = ClipBatchFitter({"num_iter": ITERS}, {}, body_model=bm, vposer=vp, contact_ids=vid)
+    fitter.set_scene(scene)
+    for lens in lengths:
+        clips = []
+        for k, n in enumerate(lens):
+            c = synth.make_clip(n, seed=100 + k)
+            clips.append((c.body_params, read_camerapose(c.camerapose_lines)))
+
+        def fit():
+            return [(b.cpu(), s, c.cpu()) for b, s, c in fitter.fit(clips)]
+
+        fit()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fit()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        dt = float(np.median(times))
+        live = bench.time_all_launches(fitter, fit, ITERS, dt)
+        rows = sum(lens)
+        entry = {"lengths": lens, "rows": rows, "ms_per_batch": dt * 1e3, "ms_per_batch_all": [t * 1e3 for t in times],
+                 "us_per_iter": dt * 1e6 / ITERS, "frames_per_s": rows / dt, "clips_per_s": len(lens) / dt,
+                 "launch_table": {ph: {k: round(v.get("us_corrected", v["us"]), 2) for k, v in live[ph].items()} for ph in ("phase1", "phase2")}}
+        res["batches"].append(entry)
+        print(f"lengths {lens}: {dt * 1e3:8.2f} ms per batch  {rows / dt:9.0f} frames/s", file=sys.stderr, flush=True)
+    fitter.close()
     res["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(res)
     print(line, flush=True)
