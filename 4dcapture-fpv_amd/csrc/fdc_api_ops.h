@@ -99,6 +99,15 @@ int fdcap_debug_kernel_forms(char* buf, int32_t len, int32_t reset) {
     return FDCAP_OK;
 }
 
+// test / diagnosis: the joint sets (plan_pose_joints, fdc_forms.h) of the optimiser's last pose forward and pose backward launch:
+// out8 = {forward jn, jr, nlev, world; backward jn, jr, nlev, world}
+int fdcap_debug_pose_joint_sets(fdcap_ctx* c, int32_t* out8) {
+    if (!c || !c->opt || !out8) return FDCAP_E_STATE;
+    const PoseJoints* p[2] = {&c->opt->pj_fwd, &c->opt->pj_bwd};
+    for (int k = 0; k < 2; ++k) { out8[4 * k] = p[k]->jn; out8[4 * k + 1] = p[k]->jr; out8[4 * k + 2] = p[k]->nlev; out8[4 * k + 3] = p[k]->world ? 1 : 0; }
+    return FDCAP_OK;
+}
+
 int fdcap_set_nn_kernel(int32_t mode) {
     if (mode < 0 || mode > 2) return FDCAP_E_ARG;
     nn_mode_ref() = mode;
@@ -136,6 +145,7 @@ int fdcap_ctx_create(const fdcap_model_desc* md, fdcap_ctx** out) {
     std::vector<int>&parents = hs.parents, &order = hs.order, &level_start = hs.level_start,
                     &child_start = hs.child_start, &child_list = hs.child_list;
     c->nlevels = hs.nlevels;
+    c->h_parents = hs.parents; c->h_depth = hs.depth;
     std::vector<float> hc(2 * 12 * 45), hm(90);
     memcpy(hc.data(), md->hands_componentsl, 12 * 45 * sizeof(float));
     memcpy(hc.data() + 12 * 45, md->hands_componentsr, 12 * 45 * sizeof(float));

@@ -28,6 +28,7 @@ void fdcap_opt_destroy(fdcap_ctx* c) {
 
 static_assert(LROW == FDCAP_NUM_LOSSES, "a batch's per-clip loss slots are LROW apart on the device");
 static_assert(CLIP_XDIM == XDIM && CLIP_NJW == NJW, "fdc_clips.h restates the two dimensions its weights divide by");
+static_assert(POSE_NJ == NJ && POSE_NJW == NJW, "fdc_forms.h restates the two joint counts plan_pose_joints works with");
 
 // the loss total of iteration ii of mode 'global' (:570 / :582): phase 1 below first_phase2_iter, phase 2 from it
 static LossWeights opt_phase_weights(const fdcap_opt_config& cf, bool phase2) {
@@ -69,6 +70,7 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->contact_on = c->ns > 0 && c->nc > 0 && cfg->weight_contact != 0.f;
     const size_t nq = (size_t)R * std::max(c->nc, 1);
     o->sw = forms_read_env();                               // (every create: tests flip the per-fit switches between fits in one process)
+    { const char* e = getenv("FDCAP_POSE_TRIM"); o->sw.pose_trim = !(e && e[0] == '0'); }     // (FormSwitches::pose_trim's comment)
     const int nq_all = (int)((size_t)cfg->n_local * c->nc);
     o->nsplit = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, o->sw.nn_seed && o->sw.nn_cull) : 1;
     o->nsplit_bf = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, false) : 1;
@@ -188,6 +190,7 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
     FormSwitches sw = proc_switches();
     sw.fuse_skin = o->sw.fuse_skin; sw.gemm_split3 = gemm_split3_enabled();
     const ContactFwdPlan pl = plan_contact_forward(nl, nc, NPFX, PNF, blend_done, c->contact.pn_fwdS.f != nullptr, smf.vpack != nullptr, smf.K, smf.ja_hi, sw);
+    if (smf.ja_hi > o->pj_fwd.jn) return FDCAP_E_STATE;        // (the skinning reads rows below ja_hi of A: the forward must have written them)
     if (pl.form == F_BLEND_SKIN_FWD) {
         static std::atomic<uint64_t> attr{0};                  // per DEVICE: the attribute belongs to one device's code object
         HIP_TRY(fdc_allow_lds(attr, pl.max_lds, {(const void*)blend_skin_fwd_kernel}));
@@ -257,7 +260,17 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
     const bool contact_grad = o->contact_on && lw.contact != 0.f;
     const bool contact_fwd = o->contact_on && (contact_grad || log_terms);
     o->lt.phase = contact_grad ? 0 : 1;
-    int e = ahead ? opt_pose_forward_rest(c, row_lo, row_hi, st) : opt_pose_forward(c, row_lo, row_hi, st, contact_fwd || (dct_on || o->dctW > 0));
+    // The joints this iteration's loss can reach (plan_pose_joints, fdc_forms.h): the contact terms through the skinning transforms of
+    // the joints the contact set is skinned to, everything else through the world joints -- phase 2's world smoothing (world_on), the
+    // DCT term, every printed term of a logging iteration.  A sharded run keeps the world joints too: its run-ahead forward and the
+    // world-only rows of the launch that follows it read G.  The forward and the backward of one iteration take the same sets.
+    // (Mode 'dct' -- a DCT term is set up -- keeps the full sets, as every caller outside this function does.)
+    const bool contact_state = contact_fwd || (dct_on || o->dctW > 0);
+    const bool need_world = lw.world_on || dct_on || o->dctW > 0 || log_terms != 0 || ahead || cf.n_local != cf.n_total;
+    const PoseJoints pj = plan_pose_joints(c->h_parents.data(), c->h_depth.data(), contact_fwd ? c->contact.ja_hi : 0, contact_state, need_world,
+                                           o->sw.pose_trim && o->dctW == 0);
+    if (contact_grad && (pj.jr != NJ || pj.jn < c->contact.ja_hi)) return FDCAP_E_STATE;     // (dPF reaches every rotation, dA the rows below ja_hi)
+    int e = ahead ? opt_pose_forward_rest(c, row_lo, row_hi, st) : opt_pose_forward(c, row_lo, row_hi, st, contact_state, &pj);
     o->ahead = false;
     if (e) return e;
     if (contact_fwd) { e = opt_contact_forward(c, st, blend_done); if (e) return e; }
@@ -328,7 +341,8 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
                        joint_grad ? o->dJw.p : nullptr, contact_grad ? o->dMv.p : nullptr, contact_grad ? o->dsv.p : nullptr,
                        contact_grad ? o->dPF.p + NPF : nullptr, NPFX, contact_grad ? o->dtransl_v.p : nullptr, o->dX.p, o->dO.p,
                        o->dCAM.p, o->dscale_row.p, pli, (contact_grad && dpf_split) ? (const float*)(o->dPF.p + (size_t)o->R * NPFX) : (const float*)nullptr,
-                       dA_rows, kn, ctab);
+                       dA_rows, kn, ctab, pj.jn, pj.jr, pj.nlev);
+    o->pj_bwd = pj;
     lt_mark(o, FDCAP_LT_POSE_BWD, st);
     const unsigned log_mask = (rows_log ? 0x17u : 0u) | (contact_fwd ? 0x8u : 0u);     // 0 rec, 1 z^2, 2 smoothing, 4 world | 3 contact
     bool log_in_tail = false;

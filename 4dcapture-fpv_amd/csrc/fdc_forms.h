@@ -47,6 +47,10 @@ struct FormSwitches {
     float nn_cache_slack = 0.03f;             // FDCAP_NN_CACHE_SLACK: metres; 0 disables the kept work lists
     bool skin_vec = true;        // FDCAP_SKIN_VEC=0 (A/B): the scalar-load skinning backward
     bool fuse_skin = true;       // FDCAP_FUSE_SKIN=0 (A/B): blend product and skinning forward as two launches
+    // FDCAP_POSE_TRIM=0: the pose kernels treat all 55 joints alike (plan_pose_joints' full plan).  Per fit; fdcap_opt_create[_clips]
+    // reads it next to its forms_read_env() call (fdc_api_opt.h), not forms_read_env(): tests/test_forms_cpu.py pins the set of names
+    // this header reads
+    bool pose_trim = true;
 };
 inline FormSwitches forms_read_env() {
     FormSwitches s;
@@ -376,6 +380,35 @@ inline NNPlan plan_nn_search(int nq, int nt, bool culled, bool frags, bool seed_
     // twice the workgroups: 0.92 ms vs 1.10 ms at NQ = 4, 1.09 ms at NQ = 1).
     if (mfma) { p.form = F_NN_MFMA; p.nq_blocks = culled ? 2 : 4; }
     p.grid = nn_grid_blocks(mfma && culled ? (nq + 255) / 256 : (nq + 511) / 512, nsplit);
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Pose kernels (fdc_frame.h, fdc_k_pose.h): the joints one launch's loss can reach.  The loss meets the kinematic chain through the
+// skinning transforms A of the joints the contact set is skinned to (rows below SkinModel::ja_hi) and through the world positions of
+// the first POSE_NJW joints; the local rotations of all joints are needed whenever the pose feature PF is written.
+//   joints [0, jn) need their world transform (chain, G, A, rest position), joints [0, jr) their local rotation,
+//   nlev = 1 + the deepest level among [0, jn).
+// The prefix form needs parents[j] < j below jn (SMPL-X numbers its joints that way); else, and with trim = false
+// (FDCAP_POSE_TRIM=0: the reference the tests compare against), the plan is the full one.
+constexpr int POSE_NJ = 55, POSE_NJW = 23;
+struct PoseJoints {
+    int jn = POSE_NJ, jr = POSE_NJ, nlev = -1;     // nlev < 0: every level of the tree (pose_forward / pose_backward take it so)
+    bool world = true;                             // the world joints Jw are written
+};
+inline PoseJoints plan_pose_joints(const int* parents, const int* depth, int ja_hi, bool contact_state, bool need_world, bool trim = true) {
+    PoseJoints p;                                  // the full plan: what every launch was before the sets existed
+    p.nlev = 0;
+    for (int j = 0; j < POSE_NJ; ++j) p.nlev = std::max(p.nlev, depth[j] + 1);
+    if (!trim) return p;
+    const int jn = std::min(POSE_NJ, std::max(1, std::max(contact_state ? ja_hi : 0, need_world ? POSE_NJW : 0)));
+    if (jn == POSE_NJ) return p;                   // (every vertex a contact: the identical launch)
+    for (int j = 0; j < jn; ++j) if (parents[j] >= j) return p;
+    p.jn = jn;
+    p.jr = contact_state ? POSE_NJ : jn;           // (PF is written with the contact state: the blend product reads every pose feature)
+    p.world = need_world;
+    p.nlev = 0;
+    for (int j = 0; j < jn; ++j) p.nlev = std::max(p.nlev, depth[j] + 1);
     return p;
 }
 

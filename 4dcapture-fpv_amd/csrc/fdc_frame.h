@@ -116,11 +116,16 @@ FDC_HD V3 world_joint(const M3& MR, V3 Mt, V3 Gt, V3 transl) { return m3_vec(MR,
 
 // Forward for one frame.  Global outputs (any may be null):
 //   Rm[55*9], PF[486], Jrest[55*3], G[55*12], A[55*12], M[12], Jw[23*3]
+// jn, jr, nlev (plan_pose_joints, fdc_forms.h; the defaults are the full sets): only joints [0, jn) get their rest position and world
+// transform -- rows >= jn of Jrest / G / A (and of sc.J / sc.G) are NOT written -- over the first nlev levels of the tree, and only
+// joints [0, jr) their local rotation (rows >= jr of Rm / PF not written).  Needs parents[j] < j below jn, and jn >= NJW with Jw.
+// Every joint that is kept goes through the same expressions in the same order.
 template <class Sync>
 FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, const float* cam_ext,
                          float scale, PoseScratch& sc, float* Rm, float* PF, float* Jrest, float* G,
                          float* A, float* M, float* Jw, int tid, int nthr, Sync sync,
-                         const float* aa22 = nullptr, int split = 0) {
+                         const float* aa22 = nullptr, int split = 0, int jn = NJ, int jr = NJ, int nlev = -1) {
+    if (nlev < 0) nlev = pm.nlevels;
     // split = 1 (the staged GPU kernels, r4): FOUR waves call this, tid 0..255 with nthr = 64.  The kinematic chain stays one
     // wave's job; around it the independent pieces run side by side on the workgroup's other SIMDs instead of one after the
     // other in one lone wave (~5.4 cycles per instruction whatever the SIMD could issue): before the chain the 6D / axis-angle
@@ -148,22 +153,22 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
     };
     FDC_FR_STAMP(0, 1);
     if (split) {                                         // (global_orient on the fourth wave: its code path is not the body joints', whose wave then walks one path only)
-        if (wv == 0) { if (ln >= 1 && ln < 25) joint_rotation(ln); }
-        else if (wv == 1) { if (ln + 25 < NJ) joint_rotation(ln + 25); }
-        else if (wv == 2) { if (ln < NJ) joint_rest(ln); }
+        if (wv == 0) { if (ln >= 1 && ln < 25 && ln < jr) joint_rotation(ln); }
+        else if (wv == 1) { if (ln + 25 < jr) joint_rotation(ln + 25); }
+        else if (wv == 2) { if (ln < jn) joint_rest(ln); }
         else if (ln == 0) joint_rotation(0);
     } else {
-        for (int j = tid; j < NJ; j += nthr) { joint_rotation(j); joint_rest(j); }
+        for (int j = tid; j < NJ; j += nthr) { if (j < jr) joint_rotation(j); if (j < jn) joint_rest(j); }
     }
     sync();
     if (split) {
         // while three waves walk the chain, the fourth writes what needs only the rotations and rest joints
         if (wv == 3 && ln < NJ) {
             const int j = ln;
-            if (Rm) for (int e = 0; e < 9; ++e) Rm[9 * j + e] = sc.R[j][e];
-            if (PF && j >= 1)
+            if (Rm && j < jr) for (int e = 0; e < 9; ++e) Rm[9 * j + e] = sc.R[j][e];
+            if (PF && j >= 1 && j < jr)
                 for (int e = 0; e < 9; ++e) PF[9 * (j - 1) + e] = sc.R[j][e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
-            if (Jrest) for (int c = 0; c < 3; ++c) Jrest[3 * j + c] = sc.J[j][c];
+            if (Jrest && j < jn) for (int c = 0; c < 3; ++c) Jrest[3 * j + c] = sc.J[j][c];
         }
         if (wv != 0) tid = 1 << 20;                      // (the generic loops below are the first wave's)
     }
@@ -175,13 +180,13 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
         // read, twelve multiply-adds and one 16-byte write per lane instead of three, thirty-six and three.  Same expressions as
         // m3_mul / m3_vec element by element.
         const int j = ln;
-        const bool act = wv < 3 && j < NJ;
+        const bool act = wv < 3 && j < jn;
         const int p = act ? pm.parents[j] : -1, dep = act ? pm.depth[j] : -1;
         const M3 R = act ? load_m3(sc.R[j]) : m3_identity();
         const V3 Jj = act ? v3(sc.J[j][0], sc.J[j][1], sc.J[j][2]) : v3(0.f, 0.f, 0.f);
         const V3 rel = (act && p >= 0) ? Jj - v3(sc.J[p][0], sc.J[p][1], sc.J[p][2]) : Jj;
         const int row = wv < 3 ? wv : 0;
-        for (int L = 0; L < pm.nlevels; ++L) {
+        for (int L = 0; L < nlev; ++L) {
             if (dep == L) {
                 float4 out;
                 if (p < 0) {
@@ -207,12 +212,12 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
         // re-reads level_start -> order -> parents -> R / J from LDS at every level (measured 970 cycles per level, ten levels).
         // A wave's LDS operations execute in order, so between levels a compiler-only barrier is enough.
         const int j = tid;
-        const bool act = j < NJ;
+        const bool act = j < jn;
         const int p = act ? pm.parents[j] : -1, dep = act ? pm.depth[j] : -1;
         const M3 R = act ? load_m3(sc.R[j]) : m3_identity();
         const V3 Jj = act ? v3(sc.J[j][0], sc.J[j][1], sc.J[j][2]) : v3(0.f, 0.f, 0.f);
         const V3 rel = (act && p >= 0) ? Jj - v3(sc.J[p][0], sc.J[p][1], sc.J[p][2]) : Jj;
-        for (int L = 0; L < pm.nlevels; ++L) {
+        for (int L = 0; L < nlev; ++L) {
             if (dep == L) {
                 if (p < 0) g_store(sc.G[j], R, Jj);
                 else {
@@ -225,9 +230,10 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
         sync();
     } else
 #endif
-    for (int L = 0; L < pm.nlevels; ++L) {
+    for (int L = 0; L < nlev; ++L) {
         for (int k = pm.level_start[L] + tid; k < pm.level_start[L + 1]; k += nthr) {
             int j = pm.order[k];
+            if (j >= jn) continue;
             int p = pm.parents[j];
             M3 R = load_m3(sc.R[j]);
             V3 Jj = v3(sc.J[j][0], sc.J[j][1], sc.J[j][2]);
@@ -246,7 +252,7 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
     world_matrix(cam_ext, x, scale, &MR, &Mt);
     V3 transl = v3(x[X_TRANSL], x[X_TRANSL + 1], x[X_TRANSL + 2]);
     if (split) {
-        if (wv == 0 && ln < NJ) {
+        if (wv == 0 && ln < jn) {
             const int j = ln;
             M3 GR = g_rot(sc.G[j]);
             V3 Gt = g_trn(sc.G[j]);
@@ -255,7 +261,7 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
             if (G) store12(G + 12 * j, sc.G[j]);
         }
         if (wv == 1) {
-            if (Jw && ln < NJW) {
+            if (Jw && ln < NJW && ln < jn) {
                 V3 w = world_joint(MR, Mt, g_trn(sc.G[ln]), transl);
                 Jw[3 * ln] = w.x; Jw[3 * ln + 1] = w.y; Jw[3 * ln + 2] = w.z;
             }
@@ -265,15 +271,16 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
         return;
     }
     for (int j = tid; j < NJ; j += nthr) {
+        if (Rm && j < jr) for (int e = 0; e < 9; ++e) Rm[9 * j + e] = sc.R[j][e];
+        if (PF && j >= 1 && j < jr)
+            for (int e = 0; e < 9; ++e) PF[9 * (j - 1) + e] = sc.R[j][e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+        if (j >= jn) continue;
         M3 GR = g_rot(sc.G[j]);
         V3 Gt = g_trn(sc.G[j]);
         V3 Jj = v3(sc.J[j][0], sc.J[j][1], sc.J[j][2]);
         if (A) { float a12[12]; g_store(a12, GR, Gt - m3_vec(GR, Jj)); store12(A + 12 * j, a12); }
         if (G) store12(G + 12 * j, sc.G[j]);
-        if (Rm) for (int e = 0; e < 9; ++e) Rm[9 * j + e] = sc.R[j][e];
         if (Jrest) for (int c = 0; c < 3; ++c) Jrest[3 * j + c] = sc.J[j][c];
-        if (PF && j >= 1)
-            for (int e = 0; e < 9; ++e) PF[9 * (j - 1) + e] = sc.R[j][e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
         if (Jw && j < NJW) {
             V3 w = world_joint(MR, Mt, Gt, transl);
             Jw[3 * j] = w.x; Jw[3 * j + 1] = w.y; Jw[3 * j + 2] = w.z;
@@ -281,6 +288,14 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
     }
     if (M && tid == 0) g_store(M, MR, Mt);
     FDC_FR_STAMP(0, 4);
+}
+
+// children of p below jn: host_pose_setup lists a joint's children in ascending order, so they are the first ones of its list
+FDC_HD int kept_children(const PoseModel& pm, int p, int jn) {
+    const int c_lo = pm.child_start[p], c_hi = pm.child_start[p + 1];
+    int n = 0;
+    while (c_lo + n < c_hi && pm.child_list[c_lo + n] < jn) ++n;
+    return n;
 }
 
 // Backward for one frame.
@@ -292,6 +307,13 @@ FDC_HD void pose_forward(const PoseModel& pm, const float* x, const float* o, co
 // Operator-level extras (fdcap_smplx_backward; all default to null): aa22 -- the forward took global_orient + the 21 body
 // joints as axis-angle (Rodrigues), their gradient goes to daa22[66] instead of dx's 6D slot / dO; dJb[55*3] -- gradient
 // of the posed body-frame joints (G.t + transl) as the body-model operator returns them.
+// jn, jr, nlev (plan_pose_joints; the defaults are the full sets): rows >= jn of dA are taken as zero WITHOUT being read, dJw / dJb
+// must not reach a joint >= jn, and dPF needs jr = NJ.  Then everything a joint >= jn adds to any output is an exact zero: its
+// prologue, product, subtree sum and dR / drel step are skipped (dR / drel rows >= jn are written as zero), rows >= jn of Jrest / G
+// are not read, rot_backward runs for j < jr only (dO, which is assigned and not added to, gets zeros for the body joints at or
+// above jr) and with jr <= 25 the hands' PCA reduction -- a sum of zeros -- is skipped.
+// Same terms in the same order for every joint that is kept: the outputs equal the full sets' bit for bit, but for the sign of a
+// zero (an accumulator that took -0 terms from the dropped joints may now hold +0).
 template <class Sync>
 FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, const float* cam_ext,
                           float scale, const float* Rm, const float* Jrest, const float* G,
@@ -299,7 +321,8 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
                           const float* dsv, const float* dbeta_v, const float* dtransl_v,
                           PoseScratch& sc, float* dx, float* dO, float* dcam_ext, float* dscale,
                           int tid, int nthr, Sync sync, const float* aa22 = nullptr, float* daa22 = nullptr,
-                          const float* dJb = nullptr, int split = 0) {
+                          const float* dJb = nullptr, int split = 0, int jn = NJ, int jr = NJ, int nlev = -1) {
+    if (nlev < 0) nlev = pm.nlevels;
     // split = 1 (the optimiser's staged kernel, r4): FOUR waves call this, tid 0..255 with nthr = 64.  The second wave idles
     // through the chain (it only meets the barriers) and then forms everything of the tail reductions that does not need the
     // rotation gradients -- d betas, d M, d transl, the camera row -- WHILE the first wave runs the body joints' rotation backward
@@ -313,7 +336,11 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
     M3 MR; V3 Mt;
     world_matrix(cam_ext, x, scale, &MR, &Mt);
     V3 transl = v3(x[X_TRANSL], x[X_TRANSL + 1], x[X_TRANSL + 2]);
-    for (int j = tid; j < NJ; j += nthr) {
+    for (int j = jn + tid; j < NJW; j += nthr) {        // (no world joint there: the sums over 0 .. NJW below read these rows)
+        for (int e = 0; e < 12; ++e) sc.dMj[j][e] = 0.f;
+        sc.dTj[j][0] = sc.dTj[j][1] = sc.dTj[j][2] = 0.f;
+    }
+    for (int j = tid; j < jn; j += nthr) {
         if (G) { float g12[12]; load12(g12, G + 12 * j); for (int e = 0; e < 12; ++e) sc.G[j][e] = g12[e]; }   // null: the caller has put it into sc.G
         for (int c = 0; c < 3; ++c) sc.J[j][c] = Jrest[3 * j + c];
         M3 GR = g_rot(sc.G[j]);
@@ -361,7 +388,7 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
     const bool rows_split = false;
 #endif
     if (!rows_split) {
-        for (int d = tid; d < NJ; d += nthr) {
+        for (int d = tid; d < jn; d += nthr) {
             M3 U = m3_mul_bt(g_rot(sc.dG[d]), g_rot(sc.G[d]));
             V3 gt = g_trn(sc.dG[d]);
             m3_add_outer(U, gt, g_trn(sc.G[d]));
@@ -374,11 +401,14 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
         // The subtree sums on three waves (late r4): they are twelve independent sums per joint, wave w takes numbers 4w .. 4w + 3 --
         // one 16-byte read and four adds per child instead of three and twelve; the waves never meet inside the chain.
         const int cw = tid_all >> 6, p = tid_all & 63;
-        const bool act = cw < 3 && p < NJ;
+        const bool act = cw < 3 && p < jn;
         const int dep = act ? pm.depth[p] : -1;
-        const int c_lo = act ? pm.child_start[p] : 0, nch = act ? pm.child_start[p + 1] - c_lo : 0;
-        const int c0 = nch > 0 ? pm.child_list[c_lo] : 0, c1 = nch > 1 ? pm.child_list[c_lo + 1] : 0, c2 = nch > 2 ? pm.child_list[c_lo + 2] : 0;
-        const int c3 = nch > 3 ? pm.child_list[c_lo + 3] : 0, c4 = nch > 4 ? pm.child_list[c_lo + 4] : 0;
+        const int c_lo = act ? pm.child_start[p] : 0, nch_all = act ? pm.child_start[p + 1] - c_lo : 0;
+        const int c0 = nch_all > 0 ? pm.child_list[c_lo] : 0, c1 = nch_all > 1 ? pm.child_list[c_lo + 1] : 0, c2 = nch_all > 2 ? pm.child_list[c_lo + 2] : 0;
+        const int c3 = nch_all > 3 ? pm.child_list[c_lo + 3] : 0, c4 = nch_all > 4 ? pm.child_list[c_lo + 4] : 0;
+        // (the children below jn: the first ones of the ascending list)
+        const int nch = nch_all <= 5 ? (nch_all > 0 && c0 < jn) + (nch_all > 1 && c1 < jn) + (nch_all > 2 && c2 < jn) + (nch_all > 3 && c3 < jn) + (nch_all > 4 && c4 < jn)
+                                     : kept_children(pm, p, jn);
         const int e0 = 4 * (cw < 3 ? cw : 0);
         auto add4 = [](float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; };
         if (act) {
@@ -394,7 +424,7 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
             *(float4*)&sc.dG[p][e0] = u;
         }
         __builtin_amdgcn_wave_barrier();
-        for (int L = pm.nlevels - 1; L >= 1; --L) {
+        for (int L = nlev - 1; L >= 1; --L) {
             if (dep == L - 1 && nch > 0) {
                 float4 a = *(const float4*)&sc.dG[p][e0];
                 add4(a, *(const float4*)&sc.dG[c0][e0]);
@@ -411,12 +441,15 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
     } else if (nthr == 64 && pm.depth != nullptr) {
         // lane p = joint p with its (at most five) children in registers: a level is "add the children's sums to one's own"
         const int p = tid;
-        const bool act = p < NJ;
+        const bool act = p < jn;
         const int dep = act ? pm.depth[p] : -1;
-        const int c_lo = act ? pm.child_start[p] : 0, nch = act ? pm.child_start[p + 1] - c_lo : 0;
-        const int c0 = nch > 0 ? pm.child_list[c_lo] : 0, c1 = nch > 1 ? pm.child_list[c_lo + 1] : 0, c2 = nch > 2 ? pm.child_list[c_lo + 2] : 0;
-        const int c3 = nch > 3 ? pm.child_list[c_lo + 3] : 0, c4 = nch > 4 ? pm.child_list[c_lo + 4] : 0;
-        for (int L = pm.nlevels - 1; L >= 1; --L) {
+        const int c_lo = act ? pm.child_start[p] : 0, nch_all = act ? pm.child_start[p + 1] - c_lo : 0;
+        const int c0 = nch_all > 0 ? pm.child_list[c_lo] : 0, c1 = nch_all > 1 ? pm.child_list[c_lo + 1] : 0, c2 = nch_all > 2 ? pm.child_list[c_lo + 2] : 0;
+        const int c3 = nch_all > 3 ? pm.child_list[c_lo + 3] : 0, c4 = nch_all > 4 ? pm.child_list[c_lo + 4] : 0;
+        // (the children below jn: the first ones of the ascending list)
+        const int nch = nch_all <= 5 ? (nch_all > 0 && c0 < jn) + (nch_all > 1 && c1 < jn) + (nch_all > 2 && c2 < jn) + (nch_all > 3 && c3 < jn) + (nch_all > 4 && c4 < jn)
+                                     : kept_children(pm, p, jn);
+        for (int L = nlev - 1; L >= 1; --L) {
             if (dep == L - 1 && nch > 0) {
                 float acc[12];
                 for (int e = 0; e < 12; ++e) acc[e] = sc.dG[p][e];
@@ -434,12 +467,13 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
         sync();
     } else
 #endif
-    for (int L = pm.nlevels - 1; L >= 1; --L) {
+    for (int L = nlev - 1; L >= 1; --L) {
         for (int k = pm.level_start[L - 1] + tid; k < pm.level_start[L]; k += nthr) {
             int p = pm.order[k];
+            if (p >= jn) continue;
             float acc[12];
             for (int e = 0; e < 12; ++e) acc[e] = sc.dG[p][e];
-            for (int ci = pm.child_start[p]; ci < pm.child_start[p + 1]; ++ci) {
+            for (int ci = pm.child_start[p]; ci < pm.child_start[p] + kept_children(pm, p, jn); ++ci) {
                 int c = pm.child_list[ci];
                 for (int e = 0; e < 12; ++e) acc[e] += sc.dG[c][e];
             }
@@ -449,7 +483,13 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
     }
     FDC_FR_STAMP(1, 3);
     // subtree sums -> the joint's total gradient -> what it hands to its local rotation and offset (dR, drel)
-    for (int c = tid; c < NJ; c += nthr) {
+    for (int c = jn + tid; c < NJ; c += nthr) {         // (the chain hands them an exact zero)
+        for (int e = 0; e < 9; ++e) sc.dR[c][e] = 0.f;
+        sc.drel[c][0] = sc.drel[c][1] = sc.drel[c][2] = 0.f;
+    }
+    // dO is written with "=": a body joint at or above jr has no rotation backward, its six numbers are the zero that would give
+    if (!aa22) for (int j = (jr > 1 ? jr : 1) + tid; j <= 21; j += nthr) for (int e = 0; e < 6; ++e) dO[6 * (j - 1) + e] = 0.f;
+    for (int c = tid; c < jn; c += nthr) {
         M3 SU = g_rot(sc.dG[c]);
         V3 dGt = g_trn(sc.dG[c]);
         m3_add_outer(SU, -1.f * dGt, g_trn(sc.G[c]));
@@ -483,7 +523,7 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
         if (t < 6 * NBETA) {
             const int part = t / NBETA, b = t % NBETA;
             float acc = 0.f;
-            for (int j = part; j < NJ; j += 6)
+            for (int j = part; j < jn; j += 6)
                 for (int c = 0; c < 3; ++c) acc += pm.Jd[(3 * j + c) * NBETA + b] * sc.dJ[j][c];
             sc.red[part][b] = acc;
         } else {
@@ -499,6 +539,7 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
             for (int part = 0; part < 6; ++part) acc += sc.red[part][t];
             dx[X_BETAS + t] += acc;
         } else if (t < NBETA + 24) {                      // (needs the fingers' rotation gradients)
+            if (jr <= 25) return;                         // (no finger's rotation gradient: daa is all zero)
             int i = t - NBETA, h = i / 12, ii = i % 12;
             const float* comp = pm.hand_comp + (h * 12 + ii) * 45;
             float acc = 0.f;
@@ -528,7 +569,7 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
         // the second wave, beside the first wave's rotation backward: a wave's LDS operations execute in order, so its own
         // hand-overs need a compiler barrier only
         const int l = tid_all - 64;                     // d betas: needs the joints' offset gradients
-        if (l < NJ) joint_offset_grad(l);
+        if (l < jn) joint_offset_grad(l);
         __builtin_amdgcn_wave_barrier();
         if (l < 6 * NBETA) reduce_step1(l);
         __builtin_amdgcn_wave_barrier();
@@ -565,11 +606,11 @@ FDC_HD void pose_backward(const PoseModel& pm, const float* x, const float* o, c
     if (split) {
         // the 21 body joints' 6D backward on the first wave, the fingers' Rodrigues backward on the third, global_orient (the body
         // joints' arithmetic on other pointers: another code path, which their wave would walk after its own) on the fourth
-        if (tid_all >= 1 && tid_all < 25) rot_backward(tid_all);
-        else if (tid_all >= 128 && tid_all < 192) { if (tid_all - 128 + 25 < NJ) rot_backward(tid_all - 128 + 25); }
+        if (tid_all >= 1 && tid_all < 25) { if (tid_all < jr) rot_backward(tid_all); }
+        else if (tid_all >= 128 && tid_all < 192) { if (tid_all - 128 + 25 < jr) rot_backward(tid_all - 128 + 25); }
         else if (tid_all == 192) rot_backward(0);
     } else {
-        for (int j = tid; j < NJ; j += nthr) { joint_offset_grad(j); rot_backward(j); }
+        for (int j = tid; j < NJ; j += nthr) { if (j < jn) joint_offset_grad(j); if (j < jr) rot_backward(j); }
     }
     sync();
     FDC_FR_STAMP(1, 5);

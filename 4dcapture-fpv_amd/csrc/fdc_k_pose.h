@@ -136,7 +136,10 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_fwd_kernel(PoseModel pm, co
                                                       int row0, float* Rm, float* PF, float* Jrest, float* G, float* A,
                                                       float* M, float* Jw, const float* AA, const float* __restrict__ Opart,
                                                       size_t part_stride, int wo_lo = 0, int wo_hi = 0, DeferredStep ds = DeferredStep(),
-                                                      int clip_n = 0, const ClipRow* __restrict__ ctab = nullptr) {
+                                                      int clip_n = 0, const ClipRow* __restrict__ ctab = nullptr,
+                                                      int jn = NJ, int jr = NJ, int nlev = -1) {
+    // jn, jr, nlev: the joints this launch's loss can reach (plan_pose_joints, fdc_forms.h; pose_forward's comment): rows >= jn of
+    // Jrest / G / A and rows >= jr of PF are not written
     // clip_n > 0: a batch of clips of clip_n frames -- this frame's `scale` is its clip's (clip_of_row, fdc_loss.h)
     // ctab != nullptr: a batch of clips of different lengths -- the clip comes from the frame's record
     __shared__ PoseScratch sc;
@@ -231,14 +234,14 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_fwd_kernel(PoseModel pm, co
                      Rm ? Rm + (size_t)r * RM_LD : nullptr, PF ? PF + (size_t)r * NPFX : nullptr,
                      Jrest ? Jrest + (size_t)r * JR_LD : nullptr, G ? G + (size_t)r * NJ * 12 : nullptr,
                      A ? A + (size_t)r * NJ * 12 : nullptr, M ? M + (size_t)r * 12 : nullptr,
-                     Jw ? Jw + (size_t)r * NJW * 3 : nullptr, threadIdx.x, 64, SyncBlock(), nullptr, 1);
+                     Jw ? Jw + (size_t)r * NJW * 3 : nullptr, threadIdx.x, 64, SyncBlock(), nullptr, 1, jn, jr, nlev);
     } else {
         pose_forward(pml, stg.x, O ? O + (size_t)r * ODIM : nullptr, stg.cam, sc_v, sc,
                      Rm ? Rm + (size_t)r * NJ * 9 : nullptr, PF ? PF + (size_t)r * NPFX : nullptr,
                      Jrest ? Jrest + (size_t)r * NJ * 3 : nullptr, G ? G + (size_t)r * NJ * 12 : nullptr,
                      A ? A + (size_t)r * NJ * 12 : nullptr, M ? M + (size_t)r * 12 : nullptr,
                      Jw ? Jw + (size_t)r * NJW * 3 : nullptr, threadIdx.x, 64, SyncBlock(),
-                     AA ? AA + (size_t)r * 66 : nullptr, 1);
+                     AA ? AA + (size_t)r * 66 : nullptr, 1, jn, jr, nlev);
     }
 }
 
@@ -259,7 +262,10 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
                                                       const float* dMv, const float* dsv, const float* dbeta_v,
                                                       int dbeta_stride, const float* dtransl_v, float* dX, float* dO,
                                                       float* dCAM, float* dscale_row, ParamLossIn pl, const float* dPF2, int dA_nj = NJ,
-                                                      int clip_n = 0, const ClipRow* __restrict__ ctab = nullptr) {
+                                                      int clip_n = 0, const ClipRow* __restrict__ ctab = nullptr,
+                                                      int jn = NJ, int jr = NJ, int nlev = -1) {
+    // jn, jr, nlev: the joints this launch's loss can reach (plan_pose_joints; pose_backward's comment): the forward wrote rows
+    // below jn of G / Jrest only, and only those rows of G and dA are staged
     // ctab != nullptr: a batch of clips of different lengths -- the frame's clip, its index within it, the clip's length and the
     // clip's three weights come from the frame's record (requested here with the staging copies) instead of pl and clip_n
     // clip_n > 0: a batch of clips of clip_n frames (fdcap_opt_create_clips): the frame's `scale` is its clip's, and the temporal
@@ -293,7 +299,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
     } else if (wave == 1) {
         stage_pose_part<1>(pm, stg, xrow, camrow);
         glds16<1>(Jrest + (size_t)r * JR_LD, s_Jr, JR_LD / 4);
-        glds16<(NJ * 3 + 63) / 64>(G + (size_t)r * NJ * 12, &sc.G[0][0], NJ * 3);              // rows of sc.G are 12 floats: a flat copy
+        glds16<(NJ * 3 + 63) / 64>(G + (size_t)r * NJ * 12, &sc.G[0][0], jn * 3);              // rows of sc.G are 12 floats: a flat copy
         glds16<1>(O + (size_t)r * O_LD, s_O, O_LD / 4);
         if (dMv) glds4<1>(dMv + (size_t)r * 12, s_misc, 12);
         if (dsv) glds4<1>(dsv + r, s_misc + 12, 1);
@@ -302,8 +308,9 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
     } else if (wave == 2) {
         stage_pose_part<2>(pm, stg, xrow, camrow);
         if (dA) {                                          // waits in sc.dG: lane j reads row j, then overwrites it
-            glds16<(NJ * 3 + 63) / 64>(dA + (size_t)r * NJ * 12, &sc.dG[0][0], dA_nj * 3);
-            for (int e = dA_nj * 12 + (int)(threadIdx.x & 63); e < NJ * 12; e += 64) (&sc.dG[0][0])[e] = 0.f;   // rows nobody wrote
+            const int da_n = dA_nj < jn ? dA_nj : jn;        // (rows >= jn: zero by construction and never read)
+            glds16<(NJ * 3 + 63) / 64>(dA + (size_t)r * NJ * 12, &sc.dG[0][0], da_n * 3);
+            for (int e = da_n * 12 + (int)(threadIdx.x & 63); e < jn * 12; e += 64) (&sc.dG[0][0])[e] = 0.f;   // rows nobody wrote
         }
         if (dPF) glds16<(NPFX / 4 + 63) / 64>(dPF + (size_t)r * NPFX, s_dPF, NPFX / 4);
         if (dPF2) glds16<(NPFX / 4 + 63) / 64>(dPF2 + (size_t)r * NPFX, &sc.dR[0][0], NPFX / 4);   // parked in sc.dR (written much later)
@@ -390,7 +397,7 @@ __global__ __launch_bounds__(64 * POSE_NW) void pose_bwd_kernel(PoseModel pm, co
                   dsv ? s_misc + 12 : nullptr, dbeta_v ? (dPF2 ? s_dPF + NPF : s_misc + 16) : nullptr,
                   dtransl_v ? s_misc + 13 : nullptr, sc, s_dx,
                   dO + (size_t)r * ODIM, dCAM + (size_t)r * 16, dscale_row + r, threadIdx.x, 64, SyncBlock(),
-                  nullptr, nullptr, nullptr, 1);
+                  nullptr, nullptr, nullptr, 1, jn, jr, nlev);
     __syncthreads();
     for (int e = threadIdx.x; e < XDIM; e += 256) dX[(size_t)r * XDIM + e] = s_dx[e];
 }

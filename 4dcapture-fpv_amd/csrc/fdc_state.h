@@ -137,7 +137,10 @@ struct OptState {
     DevBuf<float> Opart, dZpart;       // [4][R*126] partial decoder outputs, [4][R*32] partial latent gradients (fdc_panel.h)
     bool dz_pending = false;           // the last backward left the latent gradient as partials: the next Adam launch (or
                                        // fdcap_opt_get_grads) folds them into dX
+    // Which rows are defined (plan_pose_joints): a forward writes rows [0, jn) of G / A / Jrest, rows [0, jr) of
+    // PF and Jw only with `world`; whatever else these buffers hold is an older launch's and nobody may read it
     DevBuf<float> Rm, PF, Jrest, G, A, M, Jw;
+    PoseJoints pj_fwd, pj_bwd;         // the joint sets of the last pose_fwd_kernel / pose_bwd_kernel launch (fdcap_debug_pose_joint_sets)
     DevBuf<float> Voff, Vw, dist, pd, dVoff;
     DevBuf<int> idx, pi;
     DevBuf<float> kp2d;       // per-frame inner fit: 2D keypoints [n_local,23,3] (u, v, confidence)
@@ -216,6 +219,7 @@ struct fdcap_ctx {
     DevBuf<int> parents, order, level_start, child_start, child_list, depth;
     DevBuf<float> pose_tab;        // all of the above as ONE image in PoseStage's layout (what the staged pose kernels copy)
     int nlevels = 0;
+    std::vector<int> h_parents, h_depth;   // host copies of the tree: what plan_pose_joints (fdc_forms.h) decides a launch's joint sets from
     DevBuf<float> W1, b1, W2, b2, W3, b3;
     DevBuf<float> vp_pn[6];            // decoder weights in MFMA fragment order: forward w1 w2 w3, backward w3t w2t w1t
     VPoserPanels vp;
@@ -655,8 +659,13 @@ int opt_sync(fdcap_ctx* c, hipStream_t st) {
 // applied by these two launches when they cover exactly the frames it steps (no halo rows: one rank), else by its own launch first.
 // contact_state = false: the pose feature PF and the skinning transforms A -- read by the contact forward only -- are not written
 // (phase 2 of a fit that does not log: 4.7 MB less for the end of the launch to write back, tools/launch_overhead_probe.hip)
-int opt_pose_forward(fdcap_ctx* c, int lo, int hi, hipStream_t st, bool contact_state = true) {
+// pj: the joints the caller's loss can reach (plan_pose_joints, fdc_forms.h) -- it then reads no row of G / A / Jrest at or above
+// pj->jn and Jw only with pj->world; nullptr: the full sets
+int opt_pose_forward(fdcap_ctx* c, int lo, int hi, hipStream_t st, bool contact_state = true, const PoseJoints* pj = nullptr) {
     OptState* o = c->opt;
+    const PoseJoints full = plan_pose_joints(c->h_parents.data(), c->h_depth.data(), NJ, true, true, false);
+    const PoseJoints& js = pj ? *pj : full;
+    o->pj_fwd = js;
     o->ahead = false;                                       // (whatever ran ahead is recomputed here)
     const size_t ps = (size_t)o->R * ODIM;
     const int nl = o->cfg.n_local;
@@ -681,8 +690,9 @@ int opt_pose_forward(fdcap_ctx* c, int lo, int hi, hipStream_t st, bool contact_
 #else
                        (float*)nullptr,
 #endif
-                       contact_state ? o->PF.p : (float*)nullptr, o->Jrest.p, o->G.p, contact_state ? o->A.p : (float*)nullptr, o->M.p, o->Jw.p,
-                       (const float*)nullptr, (const float*)o->Opart.p, ps, 0, 0, ds, o->kclip_n(), o->ctab(false));
+                       contact_state ? o->PF.p : (float*)nullptr, o->Jrest.p, o->G.p, contact_state ? o->A.p : (float*)nullptr, o->M.p,
+                       js.world ? o->Jw.p : (float*)nullptr, (const float*)nullptr, (const float*)o->Opart.p, ps, 0, 0, ds, o->kclip_n(), o->ctab(false),
+                       js.jn, js.jr, js.nlev);
     lt_mark(o, FDCAP_LT_POSE_FWD, st);
     if (ds.on) {                                            // the step has been issued: the launches that follow see its results
         o->pend.on = false;

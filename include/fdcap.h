@@ -114,6 +114,10 @@ int fdcap_debug_scene_table(fdcap_ctx* ctx, int32_t which, void* host_out, int64
  * check that it ran.  FDCAP_CLIP_FORMS_MIN_ROWS (environment, read once per process) lowers the row count from which the
  * clip-sized forms are selected (default 336): the reference's 300-frame fixtures then run through them. */
 int fdcap_debug_kernel_forms(char* buf, int32_t len, int32_t reset);
+/* test / diagnosis: the joint sets of the optimiser's last pose forward and pose backward launch,
+   out8 = {forward jn, jr, nlev, world; backward jn, jr, nlev, world}: joints [0, jn) took part in the kinematic chain,
+   joints [0, jr) had their local rotation formed, nlev levels of the tree were walked, world = the world joints were written */
+int fdcap_debug_pose_joint_sets(fdcap_ctx* c, int32_t* out8);
 /* Contact vertex ids = get_contact_id(...) (global_optimization.py:79-94, :288); HOST pointer. */
 int fdcap_set_contact_ids(fdcap_ctx* ctx, const int64_t* vid, int32_t nc);
 
