@@ -85,7 +85,10 @@ class FittingOracle:
     def __init__(self, body_model, vposer, scene_verts, contact_vid, camerapose_lines, num_body,
                  init_lr_h=0.005, num_iter=500, weight_loss_rec=1.0, weight_loss_vposer=0.001,
                  weight_contact=0.1, dtype=torch.float32, legacy_zero_grad=False,
-                 one_direction_chamfer=True, phase_split=0.8, dct_mtx=None, c_dct_init=None):
+                 one_direction_chamfer=True, phase_split=0.8, dct_mtx=None, c_dct_init=None,
+                 phase1_contact=0.1, phase1_smooth=1.0, phase2_world=1.0, phase2_smooth=0.5, scale_init=1.8):
+        """phase1_* / phase2_* / scale_init: the constants the reference buries in fitting() (:570, :582) and __init__ (:179), as
+        keywords so that the tests can move them off their defaults; the defaults are the reference's."""
         self.dtype = dtype
         self.body_mesh_model = body_model
         self.vposer = vposer
@@ -103,7 +106,9 @@ class FittingOracle:
         self.legacy_zero_grad = legacy_zero_grad
         self.one_direction_chamfer = one_direction_chamfer
         self.phase_split = phase_split
-        self.scale = torch.tensor(1.8, dtype=dtype, requires_grad=True)                 # :179
+        self.phase1_contact, self.phase1_smooth = phase1_contact, phase1_smooth
+        self.phase2_world, self.phase2_smooth = phase2_world, phase2_smooth
+        self.scale = torch.tensor(scale_init, dtype=dtype, requires_grad=True)          # :179
         self.body_rotation_rec = torch.zeros(num_body, 78, dtype=dtype, requires_grad=True)
         self.camera_ext = torch.zeros(num_body, 4, 4, dtype=dtype, requires_grad=True)  # :182
         params = [self.body_rotation_rec, self.scale, self.camera_ext]
@@ -237,12 +242,12 @@ class FittingOracle:
             self.camera_ext.requires_grad = False
             self.scale.requires_grad = True
             self.body_rotation_rec.requires_grad = True
-            loss = l_con * 0.1 + l_sm * 1.0 + l_rec                                        # :570
+            loss = l_con * self.phase1_contact + l_sm * self.phase1_smooth + l_rec         # :570
         else:
             self.camera_ext.requires_grad = True
             self.scale.requires_grad = False
             self.body_rotation_rec.requires_grad = True
-            loss = l_rec + l_ws * 1 + l_sm * 0.5                                           # :582
+            loss = l_rec + l_ws * self.phase2_world + l_sm * self.phase2_smooth            # :582
         self.loss_log.append([float(v.detach()) for v in (l_rec, l_vp, l_sm, l_con, l_ws, loss)])
         loss.backward()
         self.optimizer.step()
