@@ -142,6 +142,9 @@ SYMBOLS = {
     "fdcap_opt_nn_timing": (c_int32, [c_void_p, c_int32]),
     "fdcap_opt_nn_timing_read": (c_int32, [c_void_p, POINTER(c_float), POINTER(c_int32)]),
     "fdcap_debug_nn_query_order": (c_int32, [c_void_p, c_int32, c_void_p, c_int32]),
+    "fdcap_debug_nn_records": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "fdcap_debug_contact_diet": (c_int32, [c_void_p, c_void_p]),
+    "fdcap_debug_contact_perm": (c_int32, [c_void_p, c_void_p, c_int32]),
     "fdcap_debug_nn_query_sort": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_launch_timing": (c_int32, [c_void_p, c_int32]),
     "fdcap_opt_launch_timing_read": (c_int32, [c_void_p, c_void_p, c_void_p]),

@@ -64,6 +64,8 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->dz_pending = false;
     o->log_pending = false;
     o->seeded = false;
+    o->nnpt_valid = false;
+    o->n_recompute = 0;
     o->dctT = o->dctC = o->dctW = 0;
     o->dct_grad = false;
     const int R = o->R = cfg->n_local + 4;
@@ -71,6 +73,8 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     const size_t nq = (size_t)R * std::max(c->nc, 1);
     o->sw = forms_read_env();                               // (every create: tests flip the per-fit switches between fits in one process)
     { const char* e = getenv("FDCAP_POSE_TRIM"); o->sw.pose_trim = !(e && e[0] == '0'); }     // (FormSwitches::pose_trim's comment)
+    { const char* e = getenv("FDCAP_NN_KEEP_RECORDS"); o->sw.nn_keep_records = !(e && e[0] == '0'); }
+    { const char* e = getenv("FDCAP_CONTACT_RECOMPUTE"); o->sw.contact_recompute = !(e && e[0] == '0'); }
     const int nq_all = (int)((size_t)cfg->n_local * c->nc);
     o->nsplit = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, o->sw.nn_seed && o->sw.nn_cull) : 1;
     o->nsplit_bf = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, false) : 1;
@@ -307,6 +311,8 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         const SkinBwdPlan pl = plan_contact_skin_bwd(nl, nc, nnz, smc.K, smc.vpack != nullptr, smc.csc_v16 != nullptr, aligned16, smc.wf_tab != nullptr,
                                                      o->sw.skin_vec);
         if (pl.ja_rows) dA_rows = c->contact.ja_hi;
+        cg.recompute = pl.form == F_SKIN_BWD_VEC && cg.nnpt != nullptr && o->sw.contact_recompute;
+        o->n_recompute += cg.recompute;
         const dim3 grid(pl.grid), block(pl.block);
 #define FDC_SKC(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, pl.lds, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, o->dVoff.p, \
                                            o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn, ctab)

@@ -335,6 +335,36 @@ int fdcap_opt_get_contact(fdcap_ctx* c, float* dist, int32_t* idx, void* stream)
     return (int)hipGetLastError();
 }
 
+// Tests / diagnosis: the search's neighbour records {x, y, z, bits(position in the sorted scene)} of the last contact forward, in the
+// caller's contact order like fdcap_opt_get_contact's arrays: [n_local, nc, 4]
+int fdcap_debug_nn_records(fdcap_ctx* c, float* rec4, void* stream) {
+    if (!c || !c->opt || !rec4) return FDCAP_E_STATE;
+    OptState* o = c->opt;
+    if (!o->contact_on || !o->nnpt_valid) return FDCAP_E_STATE;    // (a search form that keeps no records ran last: seedpt is stale)
+    const int nl = o->cfg.n_local, nc = c->nc;
+    const size_t n = (size_t)nl * nc * 4;
+    hipLaunchKernelGGL(unpermute_kernel<float>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)(o->seedpt.p + 2 * nc),
+                       c->contact_perm.p, nl, nc, 4, rec4);
+    return (int)hipGetLastError();
+}
+
+// Tests / diagnosis: did the launches of this optimiser take the paths of r14?  Counts since fdcap_opt_create[_clips]:
+// out[0] search launches that kept unchanged records, out[1] skinning backwards that formed Vw and dist themselves,
+// out[2] search launches under a query order, out[3] rebuilds of the query order
+int fdcap_debug_contact_diet(fdcap_ctx* c, int32_t* out4) {
+    if (!c || !c->opt || !out4) return FDCAP_E_STATE;
+    const OptState* o = c->opt;
+    out4[0] = o->nn_order.n_kept; out4[1] = o->n_recompute; out4[2] = o->nn_order.n_permuted; out4[3] = o->nn_order.n_rebuilds;
+    return FDCAP_OK;
+}
+
+// Tests / diagnosis: internal contact slot -> position in the caller's id array (the order of a frame's queries in idx / seedpt)
+int fdcap_debug_contact_perm(fdcap_ctx* c, int32_t* perm_h, int32_t n) {
+    if (!c || !perm_h || n != c->nc || n <= 0) return FDCAP_E_ARG;
+    HIP_TRY(hipMemcpy(perm_h, c->contact_perm.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return FDCAP_OK;
+}
+
 int fdcap_opt_get_grads(fdcap_ctx* c, float* dx, float* dcam, void* stream) {
     if (!c || !c->opt) return FDCAP_E_STATE;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }

@@ -42,15 +42,7 @@ struct NNTarget {
     const float4* centers;
 };
 
-// The one definition of the squared distance every kernel reports (direct-difference form as
-// the reference CUDA kernel computes it; fixed operation order so all kernels agree bitwise).
-__device__ __forceinline__ float nn_exact_d2(float qx, float qy, float qz, float px, float py, float pz) {
-    float dx = qx - px, dy = qy - py, dz = qz - pz;
-    return __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
-}
-__device__ __forceinline__ bool nn_better(float d, int i, float bd, int bi) {
-    return d < bd || (d == bd && i < bi);
-}
+// (nn_exact_d2, nn_better and NN_NO_NEIGHBOUR_D2: fdc_math.h -- the skinning backward forms the search's distance itself)
 
 // Workgroup -> (query block, scene split).  Blocks are dealt to the 8 XCDs round-robin (b % 8), and
 // with chunk culling nearly all the work of a query block sits in the one or two splits that hold
@@ -518,6 +510,10 @@ struct NNCache {
     // a frame are scattered over a whole leg, 32 queries whose neighbours share a k-d quarter reach nearly one list
     // (nn_query_order below).  Kept lists, anchors and the work items stay per slot; dist / idx / seedpt stay per query.
     const int* perm = nullptr;
+    // r14: a one-wave-workgroup launch that trusts seedpt as the coordinates of idx (nn_search sets this, never the caller alone) writes
+    // idx[q] and seedpt[q] only for the queries whose neighbour changed: for the others memory already holds the very bits.  The caller's
+    // half is the fit's switch (FormSwitches::nn_keep_records).
+    bool keep = false;
 };
 
 template <int NQ, int WPG, int WPB = 4>
@@ -613,7 +609,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         qx[n] = ok ? lqx[n] : 0.f;
         qy[n] = ok ? lqy[n] : 0.f;
         qz[n] = ok ? lqz[n] : 0.f;
-        own_d[n] = INFINITY;
+        own_d[n] = NN_NO_NEIGHBOUR_D2;                             // (fdc_math.h: the skinning backward forms dist itself and needs this value)
         own_i[n] = -1;
         own_p[n] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
         const int sj = ok ? lsj[n] : -1;
@@ -641,6 +637,19 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     }
     const bool cull = __all(all_seeded && finite);
     TL_STAMP(0);
+    // cache.keep (one-wave workgroups only: KEEP): the seed's identity -- global index and position in the sorted scene -- waits in
+    // the LDS words that hold this wave's result at the end: no register lives through the scan for it, not even the flag.  Taken
+    // while the best is still the seed (only the scan replaces it).  -2: no valid seed, or records not kept -- equal to no result.
+    // (Next to the set-up batch the two stores spill six registers; here the kernel keeps its 64 without scratch.)
+    constexpr bool KEEP = WPB == 1;
+    if constexpr (KEEP) {
+#pragma unroll
+        for (int n = 0; n < NQ; ++n)
+            if (half == 0) {
+                s_i[wave][n * 32 + col] = (cache.keep && own_i[n] >= 0) ? own_i[n] : -2;
+                s_d[wave][n * 32 + col] = own_p[n].w;
+            }
+    }
     // DPP reductions (fdc_math.h), no LDS traffic; lanes 32-63 repeat lanes 0-31 here, so two of the four row results suffice
     auto min_rows01 = [](float v) {
         v = fminf(v, dpp_move<0xB1>(v)); v = fminf(v, dpp_move<0x4E>(v)); v = fminf(v, dpp_move<0x141>(v)); v = fminf(v, dpp_move<0x140>(v));
@@ -1149,6 +1158,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     // it follows contention)
     if (cache.order_mode != 0 && lane == 0 && !idle) cache.hdr[4 * ((nq + 31) / 32) + (int)blockIdx.x] = nsurv;
     // the two halves of a wave hold different scene rows of the same queries; then the four waves meet in LDS
+    unsigned keepm[NQ];                                          // wave-uniform: bit col = query n * 32 + col keeps its record
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
         const float od = __shfl_xor(own_d[n], 32, 64);
@@ -1157,6 +1167,13 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         op.x = __shfl_xor(own_p[n].x, 32, 64); op.y = __shfl_xor(own_p[n].y, 32, 64);
         op.z = __shfl_xor(own_p[n].z, 32, 64); op.w = __shfl_xor(own_p[n].w, 32, 64);
         if (oi >= 0 && (own_i[n] < 0 || nn_better(od, oi, own_d[n], own_i[n]))) { own_d[n] = od; own_i[n] = oi; own_p[n] = op; }
+        // a best that is still the seed (a lane only ever replaces its best by a strictly better pair, so the seed never comes back):
+        // idx[q] and seedpt[q] already hold these bits
+        keepm[n] = 0u;
+        if constexpr (KEEP) {
+            const bool same = half == 0 && s_i[wave][n * 32 + col] == own_i[n] && __float_as_int(s_d[wave][n * 32 + col]) == __float_as_int(own_p[n].w);
+            keepm[n] = (unsigned)__ballot(same);
+        }
         if (half == 0) { s_d[wave][n * 32 + col] = own_d[n]; s_i[wave][n * 32 + col] = own_i[n]; s_p[wave][n * 32 + col] = own_p[n]; }
     }
     __syncthreads();
@@ -1193,8 +1210,11 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
             }
             const int qd = perm ? s_q[g][e] : qo;
             dist[qd] = bd;
-            idx[qd] = bi;
-            seedpt[qd] = s_p[bw][e];
+            // (one wave per workgroup: the storing thread's own wave formed the mask)
+            if (!KEEP || !((keepm[e >> 5] >> (e & 31)) & 1u)) {
+                idx[qd] = bi;
+                seedpt[qd] = s_p[bw][e];
+            }
         }
     }
 }
@@ -1365,6 +1385,9 @@ struct NNOrder {
     int* qbuf = nullptr;        // device: perm [nq] + sort scratch (nn_query_order_ints); nullptr: no query order
     int perm_n = 0;             // the nq perm holds an order for (0: none yet)
     int perm_mode = 0;          // 0: locality order, rebuilt; 1: identity; 2: imposed by the caller, never rebuilt (fdcap_debug_nn_query_order)
+    // tests / diagnosis (fdcap_debug_contact_diet): launches that kept unchanged records (NNCache::keep), launches that ran under a
+    // query order, rebuilds of the query order
+    int n_kept = 0, n_permuted = 0, n_rebuilds = 0;
 };
 static inline size_t nn_query_order_ints(int nq);                       // fdc_scene.h (the radix sort lives there)
 static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st);
@@ -1392,6 +1415,12 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
             nc.order_mode = !ordered ? 0 : (ord->sorted_groups == groups ? 2 + ord->cur : 1);
             const bool qorder = ordered && ord->qbuf != nullptr && ord->perm_mode != 1;
             nc.perm = qorder && ord->perm_n == nq ? ord->qbuf : nullptr;
+            // records are kept only where the kernel already trusts seedpt as the coordinates of idx: seeds in place, valid, and
+            // not just written by nn_seed_kernel (which leaves a NaN query's record as it was) -- and only by the one-wave form: in
+            // the two- and four-wave forms, launches of ~15 us that latency bounds, the bookkeeping cost more than the stores
+            // (+0.6 / +0.2 us per launch at 160 / 128 frames x 500 contacts), so they store every record as before
+            nc.keep = nc.keep && wpg == 1 && seedpt != nullptr && seed != nullptr && seed == idx && !seed_missing;
+            if (ord) { ord->n_kept += nc.keep ? 1 : 0; ord->n_permuted += nc.perm ? 1 : 0; }
             if (wpg == 4) hipLaunchKernelGGL((nn_stream4_kernel<1, 4>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
             else if (wpg == 2) hipLaunchKernelGGL((nn_stream4_kernel<1, 2>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
             else hipLaunchKernelGGL((nn_stream4_kernel<1, 1, 1>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
@@ -1404,6 +1433,7 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
                 ord->perm_n = nq;
                 ord->sorted_groups = 0;
                 ord->age = 0;
+                ++ord->n_rebuilds;
             } else if (resort) {
                 const bool had = nc.order_mode >= 2;
                 const int nxt = had ? 1 - ord->cur : 0;

@@ -51,6 +51,11 @@ struct FormSwitches {
     // reads it next to its forms_read_env() call (fdc_api_opt.h), not forms_read_env(): tests/test_forms_cpu.py pins the set of names
     // this header reads
     bool pose_trim = true;
+    // r14, read in the same place and for the same reason.  FDCAP_NN_KEEP_RECORDS=0: the in-loop search rewrites every neighbour
+    // record in every launch (NNCache::keep, fdc_chamfer.h).  FDCAP_CONTACT_RECOMPUTE=0: skin_bwd_vec_kernel stages the world
+    // vertices, the distances and all 55 skinning transforms instead of forming the first two and staging the rows below ja_hi.
+    bool nn_keep_records = true;
+    bool contact_recompute = true;
 };
 inline FormSwitches forms_read_env() {
     FormSwitches s;

@@ -56,10 +56,8 @@ __global__ __launch_bounds__(256) void skin_fwd_kernel(SkinModel sm, int nv, con
             }
         const V3 vb = v3(T[0] * px + T[1] * py + T[2] * pz + T[3], T[4] * px + T[5] * py + T[6] * pz + T[7],
                          T[8] * px + T[9] * py + T[10] * pz + T[11]) + transl;
-        const V3 sv = sc_v * vb;
-        o[0] = Mr[0] * sv.x + Mr[1] * sv.y + Mr[2] * sv.z + Mr[3];
-        o[1] = Mr[4] * sv.x + Mr[5] * sv.y + Mr[6] * sv.z + Mr[7];
-        o[2] = Mr[8] * sv.x + Mr[9] * sv.y + Mr[10] * sv.z + Mr[11];
+        const V3 vw = skin_world_vertex(vb, sc_v, Mr);
+        o[0] = vw.x; o[1] = vw.y; o[2] = vw.z;
         return;
     }
     __syncthreads();
@@ -174,12 +172,9 @@ __global__ __launch_bounds__(768) void blend_skin_fwd_kernel(const float* __rest
             const V3 transl = v3(sT[4 * f], sT[4 * f + 1], sT[4 * f + 2]);
             const V3 vb = v3(T[0] * px + T[1] * py + T[2] * pz + T[3], T[4] * px + T[5] * py + T[6] * pz + T[7],
                              T[8] * px + T[9] * py + T[10] * pz + T[11]) + transl;
-            const V3 sv = (one_clip ? sc_v : scale[ctab ? ctab[r].k : clip_of_row((int)r, clip_n)]) * vb;
-            const float* Mr = sM + 12 * f;
+            const V3 vw = skin_world_vertex(vb, one_clip ? sc_v : scale[ctab ? ctab[r].k : clip_of_row((int)r, clip_n)], sM + 12 * f);
             float* const o = Vw + (r * nv + v) * 3;
-            o[0] = Mr[0] * sv.x + Mr[1] * sv.y + Mr[2] * sv.z + Mr[3];
-            o[1] = Mr[4] * sv.x + Mr[5] * sv.y + Mr[6] * sv.z + Mr[7];
-            o[2] = Mr[8] * sv.x + Mr[9] * sv.y + Mr[10] * sv.z + Mr[11];
+            o[0] = vw.x; o[1] = vw.y; o[2] = vw.z;
         }
     }
 }
@@ -195,7 +190,10 @@ __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 // loss_rows[r][3] when that is non-null (logging iterations only; see ParamLossIn).
 // nnpt (optional): the neighbours' coordinates as the NN kernel keeps them ([q] {x, y, z, -}, coalesced) instead of the
 // dependent gather scene[idx[q]].
-struct ContactGradIn { const float* Vw; const float* dist; const int* idx; const float4* scene; const float4* nnpt; float coef; float* loss_rows; };
+// recompute (skin_bwd_vec_kernel with nnpt only, r14): Vw and dist are not read -- the kernel forms the world vertex from the body-frame
+// vertex it rebuilds anyway (skin_world_vertex, the forward's expression) and the distance from the two (nn_exact_d2, the search's).
+struct ContactGradIn { const float* Vw; const float* dist; const int* idx; const float4* scene; const float4* nnpt; float coef; float* loss_rows;
+                       int recompute = 0; };
 constexpr int SKB_NACC = NBETA + 3 + 12 + 1;   // dbeta, dtransl, dM, ds
 // (SKB_VCH, vertices per LDS chunk, and SKB_ROW: fdc_forms.h)
 constexpr int SKP_STRIDE = 688;                // floats of a (frame, chunk) partial of the split form: dA [660] | the SKB_NACC sums | contact term | pad
@@ -713,7 +711,7 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
                                                            float* __restrict__ dsv, ContactGradIn cg, int clip_n = 0,
                                                            const ClipRow* __restrict__ ctab = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float sk_lds[];
-    // dynamic: sGV [nc][3] (Vw, then gv) | sVP [nc][3] (Voff, then vp) | sDV [nc][3] | csc_w [nnz4] | csc_v [nnz8] (ushort)
+    // dynamic: sGV [nc][3] (Vw unless cg.recompute, then gv) | sVP [nc][3] (Voff, then vp) | sDV [nc][3] | csc_w [nnz4] | csc_v [nnz8] (ushort)
     const int nnz4 = (nnz + 3) & ~3, nnz8 = (nnz + 7) & ~7;
     float* const sGV = sk_lds;
     float* const sVP = sGV + 3 * nc;
@@ -739,11 +737,13 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
     // one batch: the rows and lists go global -> LDS by LDS-DMA (stage_pose_issue's comment), this thread's per-vertex
     // constants and NN results into registers (indices clamped: unconditional loads)
     const int n4 = (3 * nc) >> 2, nw4 = nnz4 >> 2, nv8 = nnz8 >> 3;
-    glds_wg<2, 4, 16>(cg.Vw + (size_t)r * nc * 3, sGV, n4);
+    const bool recompute = cg.recompute != 0;                  // (kernel-uniform)
+    if (!recompute) glds_wg<2, 4, 16>(cg.Vw + (size_t)r * nc * 3, sGV, n4);
     glds_wg<2, 4, 16>(Voff + (size_t)r * nc * 3, sVP, n4);
     glds_wg<2 * G, 4, 16>(sm.csc_w, sCW, nw4);                 // (nnz <= 2048 G)
     glds_wg<G, 4, 16>(sm.csc_v16, sCV, nv8);
-    glds_wg<1, 4, 16>(A + (size_t)r * NJ * 12, sAf, NJ * 3);
+    // (no vertex references a row at or above ja_hi; padding weights sit on joint 0)
+    glds_wg<1, 4, 16>(A + (size_t)r * NJ * 12, sAf, (recompute ? sm.ja_hi : NJ) * 3);
     glds_wg<1, 4, 4>(sm.csc_start, sCS, NJ + 1);
     float4 lvp0[2], lvp1[2][G], lvpj[2], lpq[2];
     float ldq[2];
@@ -756,7 +756,7 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
 #pragma unroll
         for (int g = 0; g < G; ++g) lvp1[k][g] = ((const float4*)sm.vpack)[(size_t)(1 + g) * nc + c];
         lvpj[k] = G > 1 ? ((const float4*)sm.vpack)[(size_t)(1 + G) * nc + c] : make_float4(0.f, 0.f, 0.f, 0.f);
-        ldq[k] = cg.dist[qi];
+        ldq[k] = recompute ? 0.f : cg.dist[qi];
         // (with the NN launch's own neighbour records -- {x, y, z, bits(position)}, position -1: none -- idx is not needed)
         lpq[k] = cg.nnpt ? cg.nnpt[qi] : make_float4(0.f, 0.f, 0.f, 0.f);
         ljq[k] = cg.nnpt ? __float_as_int(lpq[k].w) : cg.idx[qi];
@@ -774,7 +774,8 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
         if (c < nc) {
             SkinFwd f;
             const float p0 = lvp0[u].x + sVP[3 * c], p1 = lvp0[u].y + sVP[3 * c + 1], p2 = lvp0[u].z + sVP[3 * c + 2];
-            const float vwx = sGV[3 * c], vwy = sGV[3 * c + 1], vwz = sGV[3 * c + 2];
+            float vwx = 0.f, vwy = 0.f, vwz = 0.f;
+            if (!recompute) { vwx = sGV[3 * c]; vwy = sGV[3 * c + 1]; vwz = sGV[3 * c + 2]; }
             f.vp = v3(p0, p1, p2);
 #pragma unroll
             for (int e = 0; e < 12; ++e) f.T[e] = 0.f;
@@ -792,11 +793,17 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
             const V3 vl = v3(f.T[0] * p0 + f.T[1] * p1 + f.T[2] * p2 + f.T[3], f.T[4] * p0 + f.T[5] * p1 + f.T[6] * p2 + f.T[7],
                              f.T[8] * p0 + f.T[9] * p1 + f.T[10] * p2 + f.T[11]);
             f.vb = vl + transl;
-            float dterm;
-            cterm += contact_term(ldq[u], &dterm);
-            const float gg = ljq[u] >= 0 ? 2.f * ccoef * dterm : 0.f;         // no neighbour (NaN query): zero gradient
             float4 pt = lpq[u];
             if (!cg.nnpt && ljq[u] >= 0) pt = cg.scene[ljq[u]];
+            float dq = ldq[u];
+            if (recompute) {
+                const V3 vw = skin_world_vertex(f.vb, s, Mr);
+                vwx = vw.x; vwy = vw.y; vwz = vw.z;
+                dq = ljq[u] >= 0 ? nn_exact_d2(vwx, vwy, vwz, pt.x, pt.y, pt.z) : NN_NO_NEIGHBOUR_D2;
+            }
+            float dterm;
+            cterm += contact_term(dq, &dterm);
+            const float gg = ljq[u] >= 0 ? 2.f * ccoef * dterm : 0.f;         // no neighbour (NaN query): zero gradient
             if (ljq[u] < 0) pt = make_float4(0.f, 0.f, 0.f, 0.f);
             const V3 g = v3(gg * (vwx - pt.x), gg * (vwy - pt.y), gg * (vwz - pt.z));
             const SkinBwd b = skin_backward_vertex(f, Mr, s, g);

@@ -60,6 +60,24 @@ __device__ __forceinline__ float wave_min64(float v) {
 __device__ __forceinline__ float wave_max64(float v) { return -wave_min64(-v); }
 #endif
 
+// The one definition of the squared distance every search kernel reports (direct-difference form as
+// the reference CUDA kernel computes it; fixed operation order so all kernels agree bitwise), and of "a better neighbour".
+// (The host form is for tests: it needs -ffp-contract=off to be the same operations.)
+FDC_HD float nn_exact_d2(float qx, float qy, float qz, float px, float py, float pz) {
+    float dx = qx - px, dy = qy - py, dz = qz - pz;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx)));
+#else
+    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+#endif
+}
+FDC_HD bool nn_better(float d, int i, float bd, int bi) {
+    return d < bd || (d == bd && i < bi);
+}
+// what a search leaves in dist[q] for a query without a neighbour (a NaN query): its running minimum's initial value, which no
+// distance of such a query is better than
+constexpr float NN_NO_NEIGHBOUR_D2 = INFINITY;
+
 struct V3 { float x, y, z; };
 struct M3 { float m[9]; };   // row-major m[3*r+c]
 

@@ -55,9 +55,26 @@ struct SkinModel {
 #define FDC_SKIN_HAS_S(sm) ((sm).S != nullptr)
 #endif
 
+// SkinModel::ja_hi from the transposed lists: 1 + the highest joint whose list is not empty.  The per-vertex ids (wj, and the bytes
+// of vpack) name only such joints and joint 0, where the padding weights sit -- so rows [0, ja_hi) of A are all a vertex can reach.
+FDC_HD int skin_ja_hi(const int* csc_start, int nj) {
+    int hi = 1;
+    for (int j = 0; j < nj; ++j) if (csc_start[j + 1] > csc_start[j]) hi = j + 1;
+    return hi;
+}
+
 FDC_HD int skin_vpack_planes(int K) { const int G = (K + 3) / 4; return G <= 1 ? 2 : G + 2; }
 
 struct SkinFwd { V3 vp, vb, vw; float T[12]; };
+
+// body-frame vertex -> world vertex: `*scale` (:284), then verts_transform (:285).  The ONE source expression of it: the forward
+// kernels write its value to Vw, skin_bwd_vec_kernel forms the same bits again instead of reading them (r14).
+FDC_HD V3 skin_world_vertex(V3 vb, float scale, const float* M) {
+    const V3 sv = scale * vb;
+    return v3(M[0] * sv.x + M[1] * sv.y + M[2] * sv.z + M[3],
+              M[4] * sv.x + M[5] * sv.y + M[6] * sv.z + M[7],
+              M[8] * sv.x + M[9] * sv.y + M[10] * sv.z + M[11]);
+}
 
 // v: vertex id in the full mesh; voff: this vertex's 3 pose-blend offsets (PF @ posedirs)
 FDC_HD SkinFwd skin_forward_vertex(const SkinModel& sm, int v, const float* beta, const float* voff,
@@ -83,10 +100,7 @@ FDC_HD SkinFwd skin_forward_vertex(const SkinModel& sm, int v, const float* beta
                r.T[4] * p[0] + r.T[5] * p[1] + r.T[6] * p[2] + r.T[7],
                r.T[8] * p[0] + r.T[9] * p[1] + r.T[10] * p[2] + r.T[11]);
     r.vb = vl + transl;
-    V3 sv = scale * r.vb;
-    r.vw = v3(M[0] * sv.x + M[1] * sv.y + M[2] * sv.z + M[3],
-              M[4] * sv.x + M[5] * sv.y + M[6] * sv.z + M[7],
-              M[8] * sv.x + M[9] * sv.y + M[10] * sv.z + M[11]);
+    r.vw = skin_world_vertex(r.vb, scale, M);
     return r;
 }
 

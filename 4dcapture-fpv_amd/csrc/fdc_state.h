@@ -172,7 +172,11 @@ struct OptState {
     bool nn_timing = false;
     std::vector<hipEvent_t> nn_ev;
     int nn_ev_used = 0;
-    NNCache nn_cache(int) { return NNCache{sw.nn_cache_slack > 0.f ? nnc_ids.p : nullptr, sw.nn_cache_slack > 0.f ? nnc_hdr.p : nullptr, nnc_anchor.p, sw.nn_cache_slack}; }
+    NNCache nn_cache(int) {
+        NNCache nc{sw.nn_cache_slack > 0.f ? nnc_ids.p : nullptr, sw.nn_cache_slack > 0.f ? nnc_hdr.p : nullptr, nnc_anchor.p, sw.nn_cache_slack};
+        nc.keep = sw.nn_keep_records;                        // (nn_search decides per launch whether the records may be kept)
+        return nc;
+    }
     DevBuf<float> dA, dtransl_v, dMv, dsv, dPF, dJw, dX, dCAM, dscale_row;     // d betas: columns 486.. of dPF
     DevBuf<float> VoffF, VwF, dVF;      // mode 'local' second loop: full-mesh pose offsets / world vertices / gradient
     int cam_steps = 0;
@@ -187,6 +191,7 @@ struct OptState {
     // rows and the scale-dependent outputs (ahead_blend: the contact set's pose-blend product is done as well)
     bool ahead = false, ahead_blend = false;
     bool nnpt_valid = false;  // the last contact forward left the neighbours' coordinates in seedpt
+    int n_recompute = 0;      // tests / diagnosis (fdcap_debug_contact_diet): skinning backwards launched with ContactGradIn::recompute
 };
 
 // (fdcap_opt_launch_timing) the stage `what` ended here; -1: an iteration begins
@@ -437,8 +442,7 @@ int build_skin_set(fdcap_ctx* c, const std::vector<int64_t>& ids, SkinSet* out) 
             }
         }
         out->nch = nch;
-        out->ja_hi = 1;
-        for (int j = 0; j < NJ; ++j) if (csc_start[j + 1] > csc_start[j]) out->ja_hi = j + 1;
+        out->ja_hi = skin_ja_hi(csc_start.data(), NJ);
         HIP_TRY(out->csc_chunk.upload(cc.data(), cc.size()));
     }
     tr.mark("lists, vpack, chunk table");

@@ -523,6 +523,17 @@ int fdcap_opt_nn_timing_read(fdcap_ctx* ctx, float* mean_ms, int32_t* launches);
  * every 32 launches; 1: query order (32 consecutive query indices per wave); 2: perm_h [n] (n = frames x contacts, a
  * permutation: wave slot s serves query perm_h[s]), kept until the next call.  Drops the kept work lists.  Synchronises the device. */
 int fdcap_debug_nn_query_order(fdcap_ctx* ctx, int32_t mode, const int32_t* perm_h, int32_t n);
+/* Tests / diagnosis: the in-loop search's neighbour records of the last contact forward, [n_local, nc, 4] floats in the caller's
+ * contact order: {x, y, z} of the neighbour fdcap_opt_get_contact reports and the bits of its position in the sorted scene.
+ * FDCAP_E_STATE when the last contact forward's search took a form that keeps no records (the plain or the staged scan). */
+int fdcap_debug_nn_records(fdcap_ctx* ctx, float* rec4_d, void* stream);
+/* Tests / diagnosis: which paths this optimiser's launches took since fdcap_opt_create[_clips].  out4[0]: search launches that
+ * wrote only the changed neighbour records; out4[1]: skinning backwards that formed the world vertices and distances themselves;
+ * out4[2]: search launches under a query order; out4[3]: rebuilds of the query order. */
+int fdcap_debug_contact_diet(fdcap_ctx* ctx, int32_t* out4);
+/* Tests / diagnosis: perm_h [n = contacts]: internal contact slot -> position in the caller's id array (fdcap_set_contact_ids);
+ * a frame's queries lie in idx / seedpt in slot order.  Synchronous copy. */
+int fdcap_debug_contact_perm(fdcap_ctx* ctx, int32_t* perm_h, int32_t n);
 
 /* Tests / diagnosis: the sort behind mode 0 above on its own, on the launch path the optimiser uses.  pos_h [nq]: the position
  * of each query's neighbour in the sorted scene (-1: none); the key is min(pos >> 7, 0xFFFF), 0xFFFF without a neighbour.
