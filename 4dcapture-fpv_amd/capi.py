@@ -144,6 +144,7 @@ SYMBOLS = {
     "fdcap_debug_nn_query_order": (c_int32, [c_void_p, c_int32, c_void_p, c_int32]),
     "fdcap_debug_nn_records": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_debug_contact_diet": (c_int32, [c_void_p, c_void_p]),
+    "fdcap_debug_nn_box_tests": (c_int32, [c_void_p, c_void_p]),
     "fdcap_debug_contact_perm": (c_int32, [c_void_p, c_void_p, c_int32]),
     "fdcap_debug_nn_query_sort": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_launch_timing": (c_int32, [c_void_p, c_int32]),

@@ -53,6 +53,14 @@ int fdcap_debug_nn_hist(unsigned long long* out) {
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_nn_hist), z, sizeof(z)));
     return 0;
 }
+// r15: counts entering the three box-test stages since the last call (g_nn_box: 3 sites x {<= 8, <= 16, <= 32, > 32, sum, largest})
+int fdcap_debug_nn_box_hist(unsigned long long* out) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_box), 18 * sizeof(unsigned long long)));
+    unsigned long long z[18] = {0};
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_nn_box), z, sizeof(z)));
+    return 0;
+}
 int fdcap_debug_nn_stats(unsigned long long* out) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_stats), 8 * sizeof(unsigned long long)));

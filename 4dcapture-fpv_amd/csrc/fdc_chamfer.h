@@ -148,6 +148,9 @@ __device__ unsigned long long g_nn_timeline[16384 * 8];            // instrument
 // the exact path (wave level), [2] rows re-evaluated exactly (lane level), [3] chunks staged
 __device__ unsigned long long g_nn_hist[96];    // waves by log2(work items)
 __device__ unsigned long long g_nn_stats[8];   // [4] waves on a kept list, [5] waves that built a list, [6] raw list items, [7] items after the filter
+// r15: the count n that enters each box-test stage of nn_stream4_kernel (site 0: near chunks of a batch, 1: quarters of the listed
+// chunks, 2: the filter's raw list), stages with n > 0 only: per site {n <= 8, <= 16, <= 32, > 32, sum of n, largest n}
+__device__ unsigned long long g_nn_box[3 * 6];
 #define FDC_STAT(i, v) st_cnt[i] += (v)
 #else
 #define FDC_STAT(i, v)
@@ -514,7 +517,69 @@ struct NNCache {
     // idx[q] and seedpt[q] only for the queries whose neighbour changed: for the others memory already holds the very bits.  The caller's
     // half is the fit's switch (FormSwitches::nn_keep_records).
     bool keep = false;
+    // r15: lanes per box of the per-query box tests (FormSwitches::nn_box_lanes): 0 by each stage's count, 2 / 4 / 8 forced.
+    // Scheduling, never results: a stage keeps the same entries in the same order whatever the width.
+    int box_lanes = 0;
+    // r15: a wave on a kept list of at most 64 quarters copies their boxes into its sbox with the set-up batch (LDS-DMA), so the
+    // filter's boxes cost no round trip of their own.  Off unless FDCAP_NN_BOX_PREFETCH=1 (the filter fetches them itself, as before
+    // r15): measured no faster (profiles/r15_search_fixed_work_ab.txt)
+    bool box_prefetch = false;
 };
+
+// One stage of the streaming kernel's per-query box tests (r3: lane-parallel; r15: LPB lanes per box).  The group's queries
+// {x, y, z, squared bound} sit in LDS (sq); a pass serves 64 / LPB of the stage's n entries: lane l holds the box of entry
+// p0 + l / LPB in registers and walks queries (l % LPB) * (32 NQ / LPB) onwards.  ONE ballot per pass, OR-folded over each entry's
+// lanes (nn_box_fold, fdc_forms.h); the entries some query needs are handed to emit(position among the stage's kept entries,
+// tag) in ascending entry order by their first lane -- so the output holds the same entries in the same order for every LPB.
+// fetch(j, valid, lo, hi, tag) loads entry j's box (valid = false: any entry, the result is dropped).  n and room are
+// wave-uniform.  Returns the number kept, or -1 as soon as a pass would take it past `room` (nothing of that pass is emitted).
+template <int LPB, int NQ, class Fetch, class Emit>
+__device__ __forceinline__ int nn_box_passes(const float4* sq, int lane, int n, int room, Fetch fetch, Emit emit) {
+    constexpr int QPL = 32 * NQ / LPB;                           // queries per lane
+    const float4* const qs = sq + (lane % LPB) * QPL;
+    int nout = 0;
+    for (int p0 = 0; p0 < n; p0 += 64 / LPB) {
+        const int j = p0 + lane / LPB;
+        const bool valid = j < n;
+        float4 blo, bhi;
+        int tag;
+        fetch(j, valid, blo, bhi, tag);
+        bool hit = false;
+        if (valid) {
+            // (the wider forms unrolled by 4 or fully hoist their LDS reads: 27 / 150 spilled registers in the 64-register one-wave kernel)
+            constexpr int UNR = LPB == 2 ? 8 : 2;
+#pragma unroll UNR
+            for (int i = 0; i < QPL; ++i) {
+                const float4 v = qs[i];
+                hit |= box_d2(blo, bhi, v.x, v.y, v.z) <= v.w;
+            }
+        }
+        const unsigned long long hm = nn_box_fold(__ballot(hit), LPB);
+        const int cnt = nn_box_count(hm);
+        if (nout + cnt > room) return -1;
+        if (lane % LPB == 0 && ((hm >> lane) & 1ull)) emit(nout + nn_box_rank(hm, lane), tag);
+        nout += cnt;
+        __builtin_amdgcn_wave_barrier();
+    }
+    return nout;
+}
+// ... with the lanes per box chosen by the stage's count (nn_box_lanes; BY_COUNT = false: a pair per box, the r3 form alone)
+template <int NQ, bool BY_COUNT, class Fetch, class Emit>
+__device__ __forceinline__ int nn_box_stage(const float4* sq, int lane, int n, int forced, int room, int site, Fetch fetch, Emit emit) {
+#ifdef FDC_NN_STATS
+    if (lane == 0 && n > 0) {
+        atomicAdd(&g_nn_box[site * 6 + (n <= 8 ? 0 : n <= 16 ? 1 : n <= 32 ? 2 : 3)], 1ull);
+        atomicAdd(&g_nn_box[site * 6 + 4], (unsigned long long)n);
+        atomicMax(&g_nn_box[site * 6 + 5], (unsigned long long)n);
+    }
+#endif
+    if constexpr (BY_COUNT) {
+        const int lpb = nn_box_lanes(n, forced);
+        if (lpb == 8) return nn_box_passes<8, NQ>(sq, lane, n, room, fetch, emit);
+        if (lpb == 4) return nn_box_passes<4, NQ>(sq, lane, n, room, fetch, emit);
+    }
+    return nn_box_passes<2, NQ>(sq, lane, n, room, fetch, emit);
+}
 
 template <int NQ, int WPG, int WPB = 4>
 __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) void nn_stream4_kernel(const float* __restrict__ q, int nq, NNTarget T,
@@ -568,35 +633,86 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     float4 lsp[NQ];
     // (the query order costs this wave one dependent round trip before the batch; only the one-wave form takes one)
     const int* const perm = NQ == 1 && WPB == 1 ? cache.perm : nullptr;
-#pragma unroll
-    for (int n = 0; n < NQ; ++n) {
-        size_t qc = (size_t)min(wq0 + n * 32 + col, nq - 1);
-        if (perm) {
-            qc = (size_t)perm[qc];
-            if (half == 0) s_q[wave][n * 32 + col] = (int)qc;
-        }
-        lqx[n] = q[3 * qc]; lqy[n] = q[3 * qc + 1]; lqz[n] = q[3 * qc + 2];
-        lsj[n] = seed[qc];
-        lsp[n] = seedpt[qc];                                      // the seed's coordinates, kept from the launch that found it
-    }
+    // r15 (BOX_PF forms): everything addressed by the GROUP alone -- header, ids, anchors -- travels with perm in that first trip,
+    // and a wave whose header names a kept list of at most 64 quarters copies their boxes (addressed by the ids) into sbox[wave]
+    // by LDS-DMA next to the query / seed / seed-point loads: the filter below then finds its boxes in LDS, one dependent round
+    // trip less before the first fragment.  sbox is free until the list stages; a wave whose anchors turn out invalid builds its
+    // list there, after the batch (and with it the copy) has landed.  Per form, as KEEP.
+    constexpr bool BOX_PF = WPB == 1 && NQ == 1;
     int hv_pre = -1;
     unsigned id_pre = 0;
     float4 anc_pre[NQ];
+    int qcs[NQ];
 #pragma unroll
-    for (int n = 0; n < NQ; ++n) anc_pre[n] = make_float4(0.f, 0.f, 0.f, -1.f);
-    if (caching) {                                                 // wave-uniform
+    for (int n = 0; n < NQ; ++n) {
+        anc_pre[n] = make_float4(0.f, 0.f, 0.f, -1.f);
+        qcs[n] = min(wq0 + n * 32 + col, nq - 1);
+        if (perm) qcs[n] = perm[qcs[n]];
+    }
+    auto load_group = [&]() __attribute__((always_inline)) {      // what is addressed by the group alone: header, ids, anchors
         hv_pre = cache.hdr[cidx];
         id_pre = NN_CACHE_CAP == 64 ? (unsigned)cache.ids[(size_t)cidx * NN_CACHE_CAP + lane]
                                     : ((const unsigned*)cache.ids)[(size_t)cidx * (NN_CACHE_CAP / 2) + lane];
 #pragma unroll
         for (int n = 0; n < NQ; ++n) anc_pre[n] = cache.anchor[(size_t)sub * nq + min(wq0 + n * 32 + col, nq - 1)];
-    }
+    };
+    bool boxes_pre = false;                                        // wave-uniform: sbox[wave] holds the boxes of the kept list's entries
+    auto load_batch = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) {
+            const size_t qc = (size_t)qcs[n];
+            if (perm && half == 0) s_q[wave][n * 32 + col] = (int)qc;
+            lqx[n] = q[3 * qc]; lqy[n] = q[3 * qc + 1]; lqz[n] = q[3 * qc + 2];
+            lsj[n] = seed[qc];
+            lsp[n] = seedpt[qc];                                  // the seed's coordinates, kept from the launch that found it
+        }
+    };
+    // Only a wave that already pays the first trip for perm ends it before the batch (wave-uniform); without a query order, without a
+    // cache or with FDCAP_NN_BOX_PREFETCH=0 the set-up is one batch as before r15.  The batch is issued INSIDE each branch: a result of an
+    // ordinary load that is first used while a copy is in flight makes hipcc wait for the copy as well (vmcnt(0)), and at a join the
+    // other path's pending perm would be such a use -- the copy would be drained before the batch it is meant to travel with.
+    if (BOX_PF && cache.box_prefetch && caching && perm != nullptr) {
+        load_group();
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(qcs[0]), "+v"(anc_pre[0].x), "+v"(anc_pre[0].y), "+v"(anc_pre[0].z), "+v"(anc_pre[0].w), "+v"(hv_pre), "+v"(id_pre));
+#endif
+        const int hv = __builtin_amdgcn_readfirstlane(hv_pre);
+        const int nk = hv & 255;
+        if (hv >= 0 && nk > 0 && nk <= 64) {
+            boxes_pre = true;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                // lane l of instruction k: part l & 1 of entry 32 k + (l >> 1); the destination is lane-linear: sbox[wave][entry][part]
+                const int e = 32 * k + (lane >> 1);
+                const unsigned w = (unsigned)__shfl((int)id_pre, NN_CACHE_CAP == 64 ? e : (e >> 1), 64);
+                const int id = NN_CACHE_CAP == 64 ? (int)(w & 0xFFFFu) : (int)((e & 1) ? (w >> 16) : (w & 0xFFFFu));
+                if (e < nk) {                                      // (lane 0 always: nk > 0 -- and 32 k < nk, or no lane at all)
+                    const float4* const src = T.qbounds + (((size_t)(WPG * (id >> 2) + sub) * 4 + (id & 3)) * 2 + (lane & 1));
+#if defined(__HIP_DEVICE_COMPILE__)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                                     (__attribute__((address_space(3))) void*)&sbox[wave][32 * k][0], 16, 0, 0);
+#endif
+                }
+            }
+        }
+        load_batch();
+#if defined(__HIP_DEVICE_COMPILE__)
+        // (BOX_PF forms have NQ == 1.  The asm text differs from the other branch's on purpose: identical tails are merged behind the
+        // join, and the batch with them -- behind a vmcnt(0) that drains the copy first.)
+        asm volatile("; set-up batch + box copy" : "+v"(lqx[0]), "+v"(lqy[0]), "+v"(lqz[0]), "+v"(lsj[0]), "+v"(lsp[0].x), "+v"(lsp[0].y), "+v"(lsp[0].z), "+v"(lsp[0].w),
+                                                   "+v"(anc_pre[0].x), "+v"(anc_pre[0].y), "+v"(anc_pre[0].z), "+v"(anc_pre[0].w), "+v"(hv_pre), "+v"(id_pre));
+        if (boxes_pre) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the copy has landed before this wave reads or overwrites sbox
+#endif
+    } else {
+        load_batch();
+        if (caching) load_group();                                 // wave-uniform
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
-    for (int n = 0; n < NQ; ++n)
-        asm volatile("" : "+v"(lqx[n]), "+v"(lqy[n]), "+v"(lqz[n]), "+v"(lsj[n]), "+v"(lsp[n].x), "+v"(lsp[n].y), "+v"(lsp[n].z), "+v"(lsp[n].w),
-                          "+v"(anc_pre[n].x), "+v"(anc_pre[n].y), "+v"(anc_pre[n].z), "+v"(anc_pre[n].w), "+v"(hv_pre), "+v"(id_pre));
+        for (int n = 0; n < NQ; ++n)
+            asm volatile("" : "+v"(lqx[n]), "+v"(lqy[n]), "+v"(lqz[n]), "+v"(lsj[n]), "+v"(lsp[n].x), "+v"(lsp[n].y), "+v"(lsp[n].z), "+v"(lsp[n].w),
+                              "+v"(anc_pre[n].x), "+v"(anc_pre[n].y), "+v"(anc_pre[n].z), "+v"(anc_pre[n].w), "+v"(hv_pre), "+v"(id_pre));
 #endif
+    }
     float qx[NQ], qy[NQ], qz[NQ], own_d[NQ], sb[NQ];
     int own_i[NQ], qidx[NQ];
     float4 own_p[NQ];          // the current best {x, y, z, bits(position in T.pts)}: it passes the filter by construction and
@@ -764,7 +880,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     // (Testing all chunk boxes directly costs every workgroup the whole box array through L1/L2: 31 KB x 16000
     // workgroups per launch at 500k points, more than everything else the kernel reads.)
     // The per-query box tests of the list stages are lane-parallel (r3): the group's queries {x, y, z, squared bound} sit in
-    // LDS, a PAIR of lanes holds one box in registers and each lane of the pair walks half of the queries.
+    // LDS, a pair of lanes (r15: 2, 4 or 8 lanes, by the stage's count) holds one box in registers and each of them walks its share of the queries.
     float4* const sq = &s_p[wave][0];                            // [32 NQ] queries (s_p is only needed for the final merge)
     float4* const sbx = &sbox[wave][0][0];                       // [64][2] compacted boxes of a chunk-stage batch
     auto put_queries = [&](const float* bound) {
@@ -774,16 +890,9 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         }
         __builtin_amdgcn_wave_barrier();
     };
-    auto pair_hits = [&](const float4 blo, const float4 bhi) -> bool {
-        const float4* const qs = sq + (lane & 1) * (16 * NQ);
-        bool hit = false;
-#pragma unroll 8
-        for (int i = 0; i < 16 * NQ; ++i) {
-            const float4 v = qs[i];
-            hit |= box_d2(blo, bhi, v.x, v.y, v.z) <= v.w;
-        }
-        return hit;
-    };
+    // r15: lanes per box by each stage's count (nn_box_stage above).  Per form, as KEEP: a form keeps it only where it measured no slower.
+    constexpr bool BOX_BY_COUNT = WPB == 1;
+    const int box_forced = __builtin_amdgcn_readfirstlane(cache.box_lanes);
     int nsurv = 4 * myn;                                         // work items are quarter chunks: 4 k + quarter
     bool listed = false;
     if (cull && n_kept >= 0) {                                    // the kept list is still a superset of what this launch can need
@@ -825,8 +934,8 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
                     near = overlaps(lo, hi);
                 }
                 // Per-query test of the near chunks (17 per wave at 512 k queries, 5 survive), lane-parallel: their boxes are
-                // compacted in chunk order through LDS, a PAIR of lanes takes one chunk and each of the two walks half of the
-                // group's queries (pair_hits) -- up to 32 chunks per pass, no scalar hand-over inside.
+                // compacted in chunk order through LDS, 2, 4 or 8 lanes take one chunk and each of them walks its share of the
+                // group's queries (nn_box_stage) -- up to 32 chunks per pass, no scalar hand-over inside.
                 const unsigned long long m = __ballot(near);
                 const int nnear = __builtin_amdgcn_readfirstlane(__popcll(m));
                 const int k = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
@@ -835,41 +944,35 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
                     sbx[2 * k + 1] = hi;
                 }
                 __builtin_amdgcn_wave_barrier();
-                for (int p0 = 0; p0 < nnear && listed; p0 += 32) {
-                    const int j = min(p0 + (lane >> 1), nnear - 1);
-                    const float4 blo = sbx[2 * j], bhi = sbx[2 * j + 1];
-                    const bool hit = (p0 + (lane >> 1) < nnear) && pair_hits(blo, bhi);
-                    unsigned long long hm = __ballot(hit);
-                    hm = (hm | (hm >> 1)) & 0x5555555555555555ull;           // bit 2 j: chunk j of the pass is needed by some query
-                    const int cnt = __popcll(hm);
-                    if (ncell + cnt > ST4_MAXCELL) { listed = false; break; }
-                    if ((lane & 1) == 0 && ((hm >> lane) & 1ull))
-                        clist[wave][ncell + __popcll(hm & ((1ull << lane) - 1ull))] = (unsigned short)(__float_as_int(blo.w) / WPG);   // k of chunk WPG k + sub
-                    ncell += cnt;
+                {
+                    const int got = nn_box_stage<NQ, BOX_BY_COUNT>(sq, lane, nnear, box_forced, ST4_MAXCELL - ncell, 0,
+                        [&](int j, bool, float4& blo, float4& bhi, int& tag) __attribute__((always_inline)) {
+                            j = min(j, nnear - 1);
+                            blo = sbx[2 * j]; bhi = sbx[2 * j + 1];
+                            tag = __float_as_int(blo.w) / WPG;                                     // k of chunk WPG k + sub
+                        },
+                        [&](int at, int tag) __attribute__((always_inline)) { clist[wave][ncell + at] = (unsigned short)tag; });
+                    if (got < 0) listed = false;
+                    else ncell += got;
                 }
                 __builtin_amdgcn_wave_barrier();
             }
         }
         // Second stage: the QUARTERS (128 points = four MFMA tiles = one k-d node) of the surviving chunks against every
         // query.  Only ~11 of the 80 tiles a wave used to scan hold a point within any query's bound; a chunk is a 30 cm
-        // patch, the part of it some query's ball reaches usually one or two of its quarters.  A pair of lanes per quarter
-        // (32 quarters = 8 chunks per pass), boxes straight from global memory into the pair's registers.
+        // patch, the part of it some query's ball reaches usually one or two of its quarters.  2, 4 or 8 lanes per quarter
+        // (32 quarters = 8 chunks per pass with a pair), boxes straight from global memory into their registers.
         ncell = __builtin_amdgcn_readfirstlane(ncell);
-        for (int p0 = 0; p0 < 4 * ncell && listed; p0 += 32) {
-            const int jq = p0 + (lane >> 1);                      // cell jq >> 2 of the list, its quarter jq & 3
-            const bool valid = jq < 4 * ncell;
-            const int k4 = 4 * (int)clist[wave][valid ? (jq >> 2) : 0];
-            const size_t qb = ((size_t)(WPG * (k4 >> 2) + sub) * 4 + (jq & 3)) * 2;
-            const float4 blo = T.qbounds[qb], bhi = T.qbounds[qb + 1];
-            const bool hit = valid && pair_hits(blo, bhi);
-            unsigned long long hm = __ballot(hit);
-            hm = (hm | (hm >> 1)) & 0x5555555555555555ull;
-            const int cnt = __popcll(hm);
-            if (nsurv + cnt > ST4_MAXLIST) { listed = false; break; }
-            if ((lane & 1) == 0 && ((hm >> lane) & 1ull))
-                slist[wave][nsurv + __popcll(hm & ((1ull << lane) - 1ull))] = (unsigned short)(k4 + (jq & 3));
-            nsurv += cnt;
-            __builtin_amdgcn_wave_barrier();
+        if (listed) {
+            nsurv = nn_box_stage<NQ, BOX_BY_COUNT>(sq, lane, 4 * ncell, box_forced, ST4_MAXLIST, 1,
+                [&](int jq, bool valid, float4& blo, float4& bhi, int& tag) __attribute__((always_inline)) {       // cell jq >> 2 of the list, its quarter jq & 3
+                    const int k4 = 4 * (int)clist[wave][valid ? (jq >> 2) : 0];
+                    const size_t qb = ((size_t)(WPG * (k4 >> 2) + sub) * 4 + (jq & 3)) * 2;
+                    blo = T.qbounds[qb]; bhi = T.qbounds[qb + 1];
+                    tag = k4 + (jq & 3);
+                },
+                [&](int at, int tag) __attribute__((always_inline)) { slist[wave][at] = (unsigned short)tag; });
+            if (nsurv < 0) { listed = false; nsurv = 0; }
         }
         FDC_STAT(5, lane == 0 && !idle);
         if (caching) {                                            // keep the (inflated) list and what it was built for
@@ -893,29 +996,26 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     TL_STAMP(1);
     // With a cache the list (kept or just built) was made for inflated radii: filter it by the per-query box test with the
     // CURRENT bounds, in place.  r3: lane-parallel -- a pair of lanes per listed quarter (32 quarters per pass), each lane walks
-    // half of the group's queries; ONE ballot and one ordered compaction per pass.  The r2 form tested two quarters per round
+    // half of the group's queries (r15: 4 or 8 lanes and a quarter or an eighth each for lists of at most 16 or 8 quarters); ONE ballot and one ordered compaction per pass.  The r2 form tested two quarters per round
     // with every lane on its own query: 11 rounds of LDS read -> 13 VALU -> compare -> scalar branch -> lane-0 store, ~1150
     // cycles per round even for a wave alone on its SIMD (timeline stamps: 5.2 of a lone wave's 19.7 us) -- a chain of
     // VALU / SALU / LDS hand-overs, not work.
     if (cull && caching && listed && (inflate || n_kept >= 0)) {
         const int n_raw = __builtin_amdgcn_readfirstlane(nsurv);
-        int nout = 0;
         FDC_STAT(6, lane == 0 ? n_raw : 0);
         put_queries(sb);
-        for (int k0 = 0; k0 < n_raw; k0 += 32) {
-            const int kk = k0 + (lane >> 1);
-            const bool valid = kk < n_raw;
-            const int id = (int)slist[wave][valid ? kk : 0];
-            const size_t qb = ((size_t)(WPG * (id >> 2) + sub) * 4 + (id & 3)) * 2;
-            const float4 blo = T.qbounds[qb], bhi = T.qbounds[qb + 1];
-            const bool hit = valid && pair_hits(blo, bhi);
-            unsigned long long hm = __ballot(hit);
-            hm = (hm | (hm >> 1)) & 0x5555555555555555ull;
-            if ((lane & 1) == 0 && ((hm >> lane) & 1ull))         // (in place: a pass reads its ids before it writes, and writes trail reads)
-                slist[wave][nout + __popcll(hm & ((1ull << lane) - 1ull))] = (unsigned short)id;
-            nout += __popcll(hm);
-            __builtin_amdgcn_wave_barrier();
-        }
+        const bool boxes_here = boxes_pre && n_kept >= 0;       // (a list built in this launch is not the one whose boxes were copied)
+        const int nout = nn_box_stage<NQ, BOX_BY_COUNT>(sq, lane, n_raw, box_forced, ST4_MAXLIST, 2,
+            [&](int kk, bool valid, float4& blo, float4& bhi, int& id) __attribute__((always_inline)) {
+                id = (int)slist[wave][valid ? kk : 0];
+                if (boxes_here) {                                 // (wave-uniform; entry kk of the kept list is entry kk of the copy)
+                    blo = sbx[2 * (valid ? kk : 0)]; bhi = sbx[2 * (valid ? kk : 0) + 1];
+                } else {
+                    const size_t qb = ((size_t)(WPG * (id >> 2) + sub) * 4 + (id & 3)) * 2;
+                    blo = T.qbounds[qb]; bhi = T.qbounds[qb + 1];
+                }
+            },
+            [&](int at, int id) __attribute__((always_inline)) { slist[wave][at] = (unsigned short)id; });   // (in place: a pass reads its ids before it writes, and writes trail reads)
         nsurv = nout;
         FDC_STAT(7, lane == 0 ? nout : 0);
     }
@@ -1388,6 +1488,9 @@ struct NNOrder {
     // tests / diagnosis (fdcap_debug_contact_diet): launches that kept unchanged records (NNCache::keep), launches that ran under a
     // query order, rebuilds of the query order
     int n_kept = 0, n_permuted = 0, n_rebuilds = 0;
+    // r15 (fdcap_debug_nn_box_tests): one-wave launches by the lanes per box they were given (by count, 2, 4, 8), and those whose
+    // waves on a kept list copy its boxes with the set-up (prefetch on, a cache and a query order)
+    int n_box[5] = {0, 0, 0, 0, 0};
 };
 static inline size_t nn_query_order_ints(int nq);                       // fdc_scene.h (the radix sort lives there)
 static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st);
@@ -1421,6 +1524,10 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
             // (+0.6 / +0.2 us per launch at 160 / 128 frames x 500 contacts), so they store every record as before
             nc.keep = nc.keep && wpg == 1 && seedpt != nullptr && seed != nullptr && seed == idx && !seed_missing;
             if (ord) { ord->n_kept += nc.keep ? 1 : 0; ord->n_permuted += nc.perm ? 1 : 0; }
+            if (ord && wpg == 1) {
+                ++ord->n_box[nc.box_lanes == 2 ? 1 : nc.box_lanes == 4 ? 2 : nc.box_lanes == 8 ? 3 : 0];
+                ord->n_box[4] += (nc.box_prefetch && nc.hdr != nullptr && nc.perm != nullptr) ? 1 : 0;
+            }
             if (wpg == 4) hipLaunchKernelGGL((nn_stream4_kernel<1, 4>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
             else if (wpg == 2) hipLaunchKernelGGL((nn_stream4_kernel<1, 2>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
             else hipLaunchKernelGGL((nn_stream4_kernel<1, 1, 1>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);

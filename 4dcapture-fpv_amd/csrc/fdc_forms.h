@@ -56,6 +56,13 @@ struct FormSwitches {
     // vertices, the distances and all 55 skinning transforms instead of forming the first two and staging the rows below ja_hi.
     bool nn_keep_records = true;
     bool contact_recompute = true;
+    // r15, read in the same place and for the same reason.  FDCAP_NN_BOX_LANES: lanes that share one box in the in-loop search's
+    // per-query box tests (nn_box_lanes below): 0 by the pass's count, 2 a pair everywhere (every launch before r15), 4 / 8 forced.
+    int nn_box_lanes = 0;
+    // FDCAP_NN_BOX_PREFETCH=1: a wave on a kept list copies the listed quarters' boxes into LDS next to its set-up loads instead of
+    // fetching them inside the filter, a round trip of its own (NNCache::box_prefetch).  Off by default: measured alone it is no
+    // faster than the parent (49.36 / 49.14 against 49.17 / 48.76 us per launch, profiles/r15_search_fixed_work_ab.txt).
+    bool nn_box_prefetch = false;
 };
 inline FormSwitches forms_read_env() {
     FormSwitches s;
@@ -347,6 +354,27 @@ inline int nn_pick_nsplit(int nq, int nt, bool culled = false) {
     while (nn_split_len(nt, ns) / MF_CH > MF_MAXCHUNK) ns *= 2;
     return ns;
 }
+// The streaming search's per-query box tests (nn_box_stage, fdc_chamfer.h): a pass gives each of up to 64 / LPB listed boxes LPB
+// lanes, and each of them walks 32 / LPB of the group's 32 queries.  r3 fixed LPB = 2 for kept lists of ~22 quarters; since the
+// queries are sorted by their neighbour's k-d quarter (r7) a steady filter list of a config-3 fit holds 11.8 quarters on average,
+// at most 16 in 92 % of the stages (profiles/r15_nn_list_lengths.txt), and a pair per box left most of the wave idle for 16 iterations.  Lanes per box by the wave-uniform count n of a stage: the widest form that still takes the
+// whole stage in one pass.  forced in {2, 4, 8} overrides (FDCAP_NN_BOX_LANES; longer stages then take several passes).
+constexpr FDC_FORMS_HD int nn_box_lanes(int n, int forced) {
+    return (forced == 2 || forced == 4 || forced == 8) ? forced : n <= 8 ? 8 : n <= 16 ? 4 : 2;
+}
+// The wave's ballot of such a pass (bit l: lane l's share of the queries met its box) -> bit lpb * e set iff any of entry e's lpb
+// lanes hit; every other bit clear.  lpb in {2, 4, 8}.
+constexpr FDC_FORMS_HD unsigned long long nn_box_fold(unsigned long long hits, int lpb) {
+    hits |= hits >> 1;
+    if (lpb >= 4) hits |= hits >> 2;
+    if (lpb >= 8) hits |= hits >> 4;
+    return hits & (lpb == 2 ? 0x5555555555555555ull : lpb == 4 ? 0x1111111111111111ull : 0x0101010101010101ull);
+}
+// ... and where the entry led by `lane` (lane % lpb == 0, its bit set in `folded`) lands among the pass's kept entries: they are
+// written in ascending entry order.  nn_box_count: how many the pass keeps.
+FDC_FORMS_HD inline int nn_box_rank(unsigned long long folded, int lane) { return __builtin_popcountll(folded & ((1ull << lane) - 1ull)); }
+FDC_FORMS_HD inline int nn_box_count(unsigned long long folded) { return __builtin_popcountll(folded); }
+
 struct NNPlan {
     Form form = F_NN_DIRECT;
     int wpg = 0;               // F_NN_STREAM_*: waves per group of 32 queries

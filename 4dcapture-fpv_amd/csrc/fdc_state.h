@@ -175,6 +175,8 @@ struct OptState {
     NNCache nn_cache(int) {
         NNCache nc{sw.nn_cache_slack > 0.f ? nnc_ids.p : nullptr, sw.nn_cache_slack > 0.f ? nnc_hdr.p : nullptr, nnc_anchor.p, sw.nn_cache_slack};
         nc.keep = sw.nn_keep_records;                        // (nn_search decides per launch whether the records may be kept)
+        nc.box_lanes = sw.nn_box_lanes;
+        nc.box_prefetch = sw.nn_box_prefetch;
         return nc;
     }
     DevBuf<float> dA, dtransl_v, dMv, dsv, dPF, dJw, dX, dCAM, dscale_row;     // d betas: columns 486.. of dPF

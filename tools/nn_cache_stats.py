@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
 """Work-list cache of the in-loop NN launch over a whole fit: kept / rebuilt waves and list sizes per block of iterations.
+BOX_HIST=<block> (r15): instead, per block of that many launches, the count n that enters each of the search's three box-test stages
+(near chunks of a batch, 4 x listed chunks, the filter's raw list): stages run, mean and largest n, shares n <= 8 / <= 16 / <= 32.
 Needs the -DFDC_NN_STATS build (FDCAP_LIB)."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,9 +28,21 @@ fop._mode = "global"; fop.init(x78)
 P = first_phase2_iter(500)
 out = (ctypes.c_ulonglong * 8)()
 raw.fdcap_debug_nn_stats(out)
+BOX = int(os.environ.get("BOX_HIST", "0"))
+box = (ctypes.c_ulonglong * 18)()
+if BOX: raw.fdcap_debug_nn_box_hist.argtypes = [ctypes.POINTER(ctypes.c_ulonglong)]; raw.fdcap_debug_nn_box_hist(box)
 for ii in range(P):
     st = capi.current_stream()
     capi.check(lib.fdcap_opt_backward(h, ii, P, 0, st), "bwd"); capi.check(lib.fdcap_opt_step(h, ii, P, st), "step")
+    if BOX:
+        if ii % BOX == BOX - 1 or ii == P - 1:
+            raw.fdcap_debug_nn_box_hist(box)
+            print(f"launches {ii - ii % BOX:3d}-{ii:3d}")
+            for s, name in enumerate(("near chunks per batch", "4 x listed chunks", "filter n_raw")):
+                b = list(box[6 * s:6 * s + 6]); tot = max(sum(b[:4]), 1)
+                print(f"   {name:22s} stages {sum(b[:4]):9d}  mean n {b[4] / tot:6.2f}  max {b[5]:4d}  n<=8 {b[0] / tot:6.1%}  n<=16 {(b[0] + b[1]) / tot:6.1%}"
+                      f"  n<=32 {(b[0] + b[1] + b[2]) / tot:6.1%}")
+        continue
     if ii % 25 == 24 or ii < 3:
         raw.fdcap_debug_nn_stats(out)
         kept, built, rawn, filt, items, mf = out[4], out[5], out[6], out[7], out[3], out[0]
