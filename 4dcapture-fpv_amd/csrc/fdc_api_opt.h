@@ -72,11 +72,6 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->contact_on = c->ns > 0 && c->nc > 0 && cfg->weight_contact != 0.f;
     const size_t nq = (size_t)R * std::max(c->nc, 1);
     o->sw = forms_read_env();                               // (every create: tests flip the per-fit switches between fits in one process)
-    { const char* e = getenv("FDCAP_POSE_TRIM"); o->sw.pose_trim = !(e && e[0] == '0'); }     // (FormSwitches::pose_trim's comment)
-    { const char* e = getenv("FDCAP_NN_KEEP_RECORDS"); o->sw.nn_keep_records = !(e && e[0] == '0'); }
-    { const char* e = getenv("FDCAP_CONTACT_RECOMPUTE"); o->sw.contact_recompute = !(e && e[0] == '0'); }
-    { const char* e = getenv("FDCAP_NN_BOX_LANES"); const int v = e ? atoi(e) : 0; o->sw.nn_box_lanes = (v == 2 || v == 4 || v == 8) ? v : 0; }
-    { const char* e = getenv("FDCAP_NN_BOX_PREFETCH"); o->sw.nn_box_prefetch = e && e[0] == '1'; }
     const int nq_all = (int)((size_t)cfg->n_local * c->nc);
     o->nsplit = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, o->sw.nn_seed && o->sw.nn_cull) : 1;
     o->nsplit_bf = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, false) : 1;

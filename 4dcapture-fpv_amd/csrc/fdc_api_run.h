@@ -359,11 +359,11 @@ int fdcap_debug_contact_diet(fdcap_ctx* c, int32_t* out4) {
 }
 
 // Tests / diagnosis (r15): one-wave search launches since fdcap_opt_create[_clips] by the lanes per box their kernel argument asked
-// for -- out[0] by each stage's count, out[1] / out[2] / out[3] forced 2 / 4 / 8 -- and out[4] those in which a wave on a kept list
-// copies its boxes with the set-up.  (Host counts of what the launches were GIVEN; which width a stage then takes is nn_box_lanes.)
-int fdcap_debug_nn_box_tests(fdcap_ctx* c, int32_t* out5) {
-    if (!c || !c->opt || !out5) return FDCAP_E_STATE;
-    for (int i = 0; i < 5; ++i) out5[i] = c->opt->nn_order.n_box[i];
+// for -- out[0] by each stage's count, out[1] / out[2] / out[3] forced 2 / 4 / 8.  (Host counts of what the launches were GIVEN;
+// which width a stage then takes is nn_box_lanes.)
+int fdcap_debug_nn_box_tests(fdcap_ctx* c, int32_t* out4) {
+    if (!c || !c->opt || !out4) return FDCAP_E_STATE;
+    for (int i = 0; i < 4; ++i) out4[i] = c->opt->nn_order.n_box[i];
     return FDCAP_OK;
 }
 

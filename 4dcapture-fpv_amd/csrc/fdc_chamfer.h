@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) void nn_mfma_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // Streaming variant for seeded + culled launches (the optimiser's steady state).
 // With ~1 % of the cells surviving, the staged kernel above is bound by the per-chunk global-load -> convert ->
-// LDS -> barrier latency, not by the matrix pipe.  Here a group of 32*NQ queries (spatially compact: the contact
+// LDS -> barrier latency, not by the matrix pipe.  Here a group of 32 queries (spatially compact: the contact
 // slots are Morton-ordered) is served by WPG = 1, 2 or 4 waves of a workgroup.  Each wave builds its own survivor
 // list over the cells dealt to it round-robin (cell c belongs to wave c % WPG: neighbouring cells -- which tend to
 // survive together -- spread evenly) in three stages: boxes of 16-cell k-d subtrees and then cell boxes against the box
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(256) void nn_mfma_kernel(const float* __restrict__ 
 constexpr int ST4_MAXLIST = FDC_ST4_MAXLIST;   // quarter chunks one wave can list out of its share of the chunks
 constexpr int ST4_MAXCELL = FDC_ST4_MAXCELL;   // chunks one wave can list before their quarters are tested
 // (tiny values, e.g. -DFDC_ST4_MAXCELL=4 -DFDC_ST4_MAXLIST=8, force the overflow fall-back everywhere: the GPU suite passes with them)
-// Ring depth vs occupancy (measured at 512 k queries, NQ = 1, one wave per group): 8 fragments / 4 waves per SIMD
+// Ring depth vs occupancy (measured at 512 k queries, one wave per group): 8 fragments / 4 waves per SIMD
 // (128 VGPR) 0.148 ms, 4 / 5 (92 VGPR) 0.139, 2 / 6 (80 VGPR) 0.136: the launch is latency-bound on its set-up
 // chain, so resident waves hide more than a deeper ring does.
 #ifndef FDC_ST4_PF
@@ -472,9 +472,6 @@ constexpr int ST4_MAXCELL = FDC_ST4_MAXCELL;   // chunks one wave can list befor
 #endif
 #ifndef FDC_ST4_OCC
 #define FDC_ST4_OCC 8
-#endif
-#ifndef FDC_ST4_OCC2
-#define FDC_ST4_OCC2 3
 #endif
 constexpr int ST4_PF = FDC_ST4_PF;     // A fragments in flight per wave
 constexpr int ST4_SUPER = 16;          // chunks per super-cell of the two-level survivor test (consecutive chunks = one k-d subtree)
@@ -520,22 +517,18 @@ struct NNCache {
     // r15: lanes per box of the per-query box tests (FormSwitches::nn_box_lanes): 0 by each stage's count, 2 / 4 / 8 forced.
     // Scheduling, never results: a stage keeps the same entries in the same order whatever the width.
     int box_lanes = 0;
-    // r15: a wave on a kept list of at most 64 quarters copies their boxes into its sbox with the set-up batch (LDS-DMA), so the
-    // filter's boxes cost no round trip of their own.  Off unless FDCAP_NN_BOX_PREFETCH=1 (the filter fetches them itself, as before
-    // r15): measured no faster (profiles/r15_search_fixed_work_ab.txt)
-    bool box_prefetch = false;
 };
 
 // One stage of the streaming kernel's per-query box tests (r3: lane-parallel; r15: LPB lanes per box).  The group's queries
 // {x, y, z, squared bound} sit in LDS (sq); a pass serves 64 / LPB of the stage's n entries: lane l holds the box of entry
-// p0 + l / LPB in registers and walks queries (l % LPB) * (32 NQ / LPB) onwards.  ONE ballot per pass, OR-folded over each entry's
+// p0 + l / LPB in registers and walks queries (l % LPB) * (32 / LPB) onwards.  ONE ballot per pass, OR-folded over each entry's
 // lanes (nn_box_fold, fdc_forms.h); the entries some query needs are handed to emit(position among the stage's kept entries,
 // tag) in ascending entry order by their first lane -- so the output holds the same entries in the same order for every LPB.
 // fetch(j, valid, lo, hi, tag) loads entry j's box (valid = false: any entry, the result is dropped).  n and room are
 // wave-uniform.  Returns the number kept, or -1 as soon as a pass would take it past `room` (nothing of that pass is emitted).
-template <int LPB, int NQ, class Fetch, class Emit>
+template <int LPB, class Fetch, class Emit>
 __device__ __forceinline__ int nn_box_passes(const float4* sq, int lane, int n, int room, Fetch fetch, Emit emit) {
-    constexpr int QPL = 32 * NQ / LPB;                           // queries per lane
+    constexpr int QPL = 32 / LPB;                                // queries per lane
     const float4* const qs = sq + (lane % LPB) * QPL;
     int nout = 0;
     for (int p0 = 0; p0 < n; p0 += 64 / LPB) {
@@ -564,7 +557,7 @@ __device__ __forceinline__ int nn_box_passes(const float4* sq, int lane, int n, 
     return nout;
 }
 // ... with the lanes per box chosen by the stage's count (nn_box_lanes; BY_COUNT = false: a pair per box, the r3 form alone)
-template <int NQ, bool BY_COUNT, class Fetch, class Emit>
+template <bool BY_COUNT, class Fetch, class Emit>
 __device__ __forceinline__ int nn_box_stage(const float4* sq, int lane, int n, int forced, int room, int site, Fetch fetch, Emit emit) {
 #ifdef FDC_NN_STATS
     if (lane == 0 && n > 0) {
@@ -575,14 +568,14 @@ __device__ __forceinline__ int nn_box_stage(const float4* sq, int lane, int n, i
 #endif
     if constexpr (BY_COUNT) {
         const int lpb = nn_box_lanes(n, forced);
-        if (lpb == 8) return nn_box_passes<8, NQ>(sq, lane, n, room, fetch, emit);
-        if (lpb == 4) return nn_box_passes<4, NQ>(sq, lane, n, room, fetch, emit);
+        if (lpb == 8) return nn_box_passes<8>(sq, lane, n, room, fetch, emit);
+        if (lpb == 4) return nn_box_passes<4>(sq, lane, n, room, fetch, emit);
     }
-    return nn_box_passes<2, NQ>(sq, lane, n, room, fetch, emit);
+    return nn_box_passes<2>(sq, lane, n, room, fetch, emit);
 }
 
-template <int NQ, int WPG, int WPB = 4>
-__global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) void nn_stream4_kernel(const float* __restrict__ q, int nq, NNTarget T,
+template <int WPG, int WPB = 4>
+__global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const float* __restrict__ q, int nq, NNTarget T,
                                                          const int* __restrict__ seed, float4* __restrict__ seedpt,
                                                          float* __restrict__ dist, int* __restrict__ idx, NNCache cache) {
     // WPB waves per workgroup.  Waves of different groups never talk to each other, and a workgroup's slot on the CU is only
@@ -590,17 +583,20 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     __shared__ unsigned short slist[WPB][ST4_MAXLIST];           // a wave's work list: quarter chunks 4 k + quarter (chunk WPG k + sub)
     __shared__ unsigned short clist[WPB][ST4_MAXCELL];           // ... before that, the chunks that passed the per-query test
     __shared__ float4 sbox[WPB][64][2];                          // a wave's near chunk boxes of the current batch {lo, bits(chunk)}, {hi, -}
-    __shared__ float s_d[WPB][32 * NQ];
-    __shared__ int s_i[WPB][32 * NQ];
-    __shared__ float4 s_p[WPB][32 * NQ];
-    __shared__ int s_q[WPB][32 * NQ];                            // the query each slot serves (cache.perm)
+    __shared__ float s_d[WPB][32];
+    __shared__ int s_i[WPB][32];
+    __shared__ float4 s_p[WPB][32];
+    __shared__ int s_q[WPB][32];                                 // the query each slot serves (cache.perm)
     static_assert(WPG == 1 || WPG == 2 || WPG == 4, "waves per query group");
     static_assert(WPB % WPG == 0 && WPB <= 4, "a group's waves share a workgroup");
     constexpr int GPW = WPB / WPG;                               // query groups per workgroup
     constexpr int CPS = ST4_SUPER / WPG;                         // chunks of a super-cell that belong to one wave
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, col = lane & 31;
+    // (the wave's index as a scalar: every [wave] address below is then a scalar base.  As a per-lane value the multi-wave forms kept
+    // those addresses in VGPRs and, at their 64 registers, spilled them -- the two-wave form reloaded slist's behind a vmcnt(0) in
+    // every work item)
+    const int tid = threadIdx.x, wave = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, half = lane >> 5, col = lane & 31;
     const int sub = wave % WPG, gslot = wave / WPG;             // this wave's share of its group's chunks: WPG k + sub
-    const int ngroups = (nq + 32 * NQ - 1) / (32 * NQ);
+    const int ngroups = (nq + 31) / 32;                          // a group is 32 queries, one per lane of a half-wave
     const int nwg = (ngroups + GPW - 1) / GPW;
 #ifdef FDC_NN_TIMELINE
     const unsigned long long tl_t0 = wall_clock64();             // instrumentation build only: 100 MHz device-wide clock
@@ -615,7 +611,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     const int wg = (cache.order_mode >= 2 && (int)blockIdx.x < nwg) ? cache.hdr[(3 + cache.order_mode) * ((nq + 31) / 32) + (int)blockIdx.x] : (int)blockIdx.x;
     const int group = wg * GPW + gslot;
     const bool idle = wg >= nwg || group >= ngroups;            // idle waves still meet the barrier below
-    const int wq0 = idle ? nq : group * (32 * NQ);
+    const int wq0 = idle ? nq : group * 32;
     const int nchunk = (T.n + MF_CH - 1) / MF_CH;
     const int myn = idle ? 0 : (nchunk - sub + WPG - 1) / WPG;  // this wave's chunks: WPG k + sub, k < myn
 #ifdef FDC_NN_STATS
@@ -628,128 +624,54 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     // during the launch's drain is nothing but such round trips).
     const bool caching = cache.hdr != nullptr && !idle;            // (idle waves have no group: nothing kept for them)
     const int cidx = group * WPG + sub;
-    float lqx[NQ], lqy[NQ], lqz[NQ];
-    int lsj[NQ];
-    float4 lsp[NQ];
     // (the query order costs this wave one dependent round trip before the batch; only the one-wave form takes one)
-    const int* const perm = NQ == 1 && WPB == 1 ? cache.perm : nullptr;
-    // r15 (BOX_PF forms): everything addressed by the GROUP alone -- header, ids, anchors -- travels with perm in that first trip,
-    // and a wave whose header names a kept list of at most 64 quarters copies their boxes (addressed by the ids) into sbox[wave]
-    // by LDS-DMA next to the query / seed / seed-point loads: the filter below then finds its boxes in LDS, one dependent round
-    // trip less before the first fragment.  sbox is free until the list stages; a wave whose anchors turn out invalid builds its
-    // list there, after the batch (and with it the copy) has landed.  Per form, as KEEP.
-    constexpr bool BOX_PF = WPB == 1 && NQ == 1;
+    const int* const perm = WPB == 1 ? cache.perm : nullptr;
+    int qs = min(wq0 + col, nq - 1);                               // the query this slot serves
+    if (perm) qs = perm[qs];
+    const size_t qc = (size_t)qs;
+    if (perm && half == 0) s_q[wave][col] = qs;
+    float lqx = q[3 * qc], lqy = q[3 * qc + 1], lqz = q[3 * qc + 2];
+    int lsj = seed[qc];
+    float4 lsp = seedpt[qc];                                       // the seed's coordinates, kept from the launch that found it
     int hv_pre = -1;
     unsigned id_pre = 0;
-    float4 anc_pre[NQ];
-    int qcs[NQ];
-#pragma unroll
-    for (int n = 0; n < NQ; ++n) {
-        anc_pre[n] = make_float4(0.f, 0.f, 0.f, -1.f);
-        qcs[n] = min(wq0 + n * 32 + col, nq - 1);
-        if (perm) qcs[n] = perm[qcs[n]];
-    }
-    auto load_group = [&]() __attribute__((always_inline)) {      // what is addressed by the group alone: header, ids, anchors
+    float4 anc_pre = make_float4(0.f, 0.f, 0.f, -1.f);
+    if (caching) {                                                 // (wave-uniform) what is addressed by the group alone: header, ids, anchors
         hv_pre = cache.hdr[cidx];
         id_pre = NN_CACHE_CAP == 64 ? (unsigned)cache.ids[(size_t)cidx * NN_CACHE_CAP + lane]
                                     : ((const unsigned*)cache.ids)[(size_t)cidx * (NN_CACHE_CAP / 2) + lane];
-#pragma unroll
-        for (int n = 0; n < NQ; ++n) anc_pre[n] = cache.anchor[(size_t)sub * nq + min(wq0 + n * 32 + col, nq - 1)];
-    };
-    bool boxes_pre = false;                                        // wave-uniform: sbox[wave] holds the boxes of the kept list's entries
-    auto load_batch = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int n = 0; n < NQ; ++n) {
-            const size_t qc = (size_t)qcs[n];
-            if (perm && half == 0) s_q[wave][n * 32 + col] = (int)qc;
-            lqx[n] = q[3 * qc]; lqy[n] = q[3 * qc + 1]; lqz[n] = q[3 * qc + 2];
-            lsj[n] = seed[qc];
-            lsp[n] = seedpt[qc];                                  // the seed's coordinates, kept from the launch that found it
-        }
-    };
-    // Only a wave that already pays the first trip for perm ends it before the batch (wave-uniform); without a query order, without a
-    // cache or with FDCAP_NN_BOX_PREFETCH=0 the set-up is one batch as before r15.  The batch is issued INSIDE each branch: a result of an
-    // ordinary load that is first used while a copy is in flight makes hipcc wait for the copy as well (vmcnt(0)), and at a join the
-    // other path's pending perm would be such a use -- the copy would be drained before the batch it is meant to travel with.
-    if (BOX_PF && cache.box_prefetch && caching && perm != nullptr) {
-        load_group();
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(qcs[0]), "+v"(anc_pre[0].x), "+v"(anc_pre[0].y), "+v"(anc_pre[0].z), "+v"(anc_pre[0].w), "+v"(hv_pre), "+v"(id_pre));
-#endif
-        const int hv = __builtin_amdgcn_readfirstlane(hv_pre);
-        const int nk = hv & 255;
-        if (hv >= 0 && nk > 0 && nk <= 64) {
-            boxes_pre = true;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                // lane l of instruction k: part l & 1 of entry 32 k + (l >> 1); the destination is lane-linear: sbox[wave][entry][part]
-                const int e = 32 * k + (lane >> 1);
-                const unsigned w = (unsigned)__shfl((int)id_pre, NN_CACHE_CAP == 64 ? e : (e >> 1), 64);
-                const int id = NN_CACHE_CAP == 64 ? (int)(w & 0xFFFFu) : (int)((e & 1) ? (w >> 16) : (w & 0xFFFFu));
-                if (e < nk) {                                      // (lane 0 always: nk > 0 -- and 32 k < nk, or no lane at all)
-                    const float4* const src = T.qbounds + (((size_t)(WPG * (id >> 2) + sub) * 4 + (id & 3)) * 2 + (lane & 1));
-#if defined(__HIP_DEVICE_COMPILE__)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                     (__attribute__((address_space(3))) void*)&sbox[wave][32 * k][0], 16, 0, 0);
-#endif
-                }
-            }
-        }
-        load_batch();
-#if defined(__HIP_DEVICE_COMPILE__)
-        // (BOX_PF forms have NQ == 1.  The asm text differs from the other branch's on purpose: identical tails are merged behind the
-        // join, and the batch with them -- behind a vmcnt(0) that drains the copy first.)
-        asm volatile("; set-up batch + box copy" : "+v"(lqx[0]), "+v"(lqy[0]), "+v"(lqz[0]), "+v"(lsj[0]), "+v"(lsp[0].x), "+v"(lsp[0].y), "+v"(lsp[0].z), "+v"(lsp[0].w),
-                                                   "+v"(anc_pre[0].x), "+v"(anc_pre[0].y), "+v"(anc_pre[0].z), "+v"(anc_pre[0].w), "+v"(hv_pre), "+v"(id_pre));
-        if (boxes_pre) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the copy has landed before this wave reads or overwrites sbox
-#endif
-    } else {
-        load_batch();
-        if (caching) load_group();                                 // wave-uniform
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-        for (int n = 0; n < NQ; ++n)
-            asm volatile("" : "+v"(lqx[n]), "+v"(lqy[n]), "+v"(lqz[n]), "+v"(lsj[n]), "+v"(lsp[n].x), "+v"(lsp[n].y), "+v"(lsp[n].z), "+v"(lsp[n].w),
-                              "+v"(anc_pre[n].x), "+v"(anc_pre[n].y), "+v"(anc_pre[n].z), "+v"(anc_pre[n].w), "+v"(hv_pre), "+v"(id_pre));
-#endif
+        anc_pre = cache.anchor[(size_t)sub * nq + min(wq0 + col, nq - 1)];
     }
-    float qx[NQ], qy[NQ], qz[NQ], own_d[NQ], sb[NQ];
-    int own_i[NQ], qidx[NQ];
-    float4 own_p[NQ];          // the current best {x, y, z, bits(position in T.pts)}: it passes the filter by construction and
-                               // must not cost a global load every time it is met; next iteration's seed point
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(lqx), "+v"(lqy), "+v"(lqz), "+v"(lsj), "+v"(lsp.x), "+v"(lsp.y), "+v"(lsp.z), "+v"(lsp.w),
+                      "+v"(anc_pre.x), "+v"(anc_pre.y), "+v"(anc_pre.z), "+v"(anc_pre.w), "+v"(hv_pre), "+v"(id_pre));
+#endif
+    const int qidx = wq0 + col;
+    const bool ok = qidx < nq;
+    const float qx = ok ? lqx : 0.f, qy = ok ? lqy : 0.f, qz = ok ? lqz : 0.f;
+    float own_d = NN_NO_NEIGHBOUR_D2;                            // (fdc_math.h: the skinning backward forms dist itself and needs this value)
+    int own_i = -1;
+    // the current best {x, y, z, bits(position in T.pts)}: it passes the filter by construction and must not cost a global load
+    // every time it is met; next iteration's seed point
+    float4 own_p = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
     bool all_seeded = true;
-#pragma unroll
-    for (int n = 0; n < NQ; ++n) {
-        qidx[n] = wq0 + n * 32 + col;
-        const bool ok = qidx[n] < nq;
-        qx[n] = ok ? lqx[n] : 0.f;
-        qy[n] = ok ? lqy[n] : 0.f;
-        qz[n] = ok ? lqz[n] : 0.f;
-        own_d[n] = NN_NO_NEIGHBOUR_D2;                             // (fdc_math.h: the skinning backward forms dist itself and needs this value)
-        own_i[n] = -1;
-        own_p[n] = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-        const int sj = ok ? lsj[n] : -1;
-        const float4 p = ok ? lsp[n] : make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) {
-            if (sj >= 0 && sj < T.n) {
-                own_p[n] = p;
-                own_d[n] = nn_exact_d2(qx[n], qy[n], qz[n], p.x, p.y, p.z);
-                own_i[n] = sj;
-            } else {
-                all_seeded = false;
-            }
+    const int sj = ok ? lsj : -1;
+    const float4 sp = ok ? lsp : make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ok) {
+        if (sj >= 0 && sj < T.n) {
+            own_p = sp;
+            own_d = nn_exact_d2(qx, qy, qz, sp.x, sp.y, sp.z);
+            own_i = sj;
+        } else {
+            all_seeded = false;
         }
-        sb[n] = ok ? own_d[n] * 1.00002f + 1e-9f : -INFINITY;   // bound with the rounding slack of the box test
     }
-    float rq[NQ];                                                // radius of each query's bound (rounded up)
+    const float sb = ok ? own_d * 1.00002f + 1e-9f : -INFINITY; // bound with the rounding slack of the box test
+    float rq = 0.f;                                              // radius of the query's bound (rounded up)
     bool finite = true;
-#pragma unroll
-    for (int n = 0; n < NQ; ++n) {
-        rq[n] = 0.f;
-        if (qidx[n] < nq) {
-            rq[n] = __builtin_amdgcn_sqrtf(sb[n]) * 1.00001f + 1e-6f;   // 1-ulp v_sqrt_f32 inside the 1e-5 slack
-            finite &= rq[n] < INFINITY;
-        }
+    if (ok) {
+        rq = __builtin_amdgcn_sqrtf(sb) * 1.00001f + 1e-6f;      // 1-ulp v_sqrt_f32 inside the 1e-5 slack
+        finite = rq < INFINITY;
     }
     const bool cull = __all(all_seeded && finite);
     TL_STAMP(0);
@@ -759,12 +681,10 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     // (Next to the set-up batch the two stores spill six registers; here the kernel keeps its 64 without scratch.)
     constexpr bool KEEP = WPB == 1;
     if constexpr (KEEP) {
-#pragma unroll
-        for (int n = 0; n < NQ; ++n)
-            if (half == 0) {
-                s_i[wave][n * 32 + col] = (cache.keep && own_i[n] >= 0) ? own_i[n] : -2;
-                s_d[wave][n * 32 + col] = own_p[n].w;
-            }
+        if (half == 0) {
+            s_i[wave][col] = (cache.keep && own_i >= 0) ? own_i : -2;
+            s_d[wave][col] = own_p.w;
+        }
     }
     // DPP reductions (fdc_math.h), no LDS traffic; lanes 32-63 repeat lanes 0-31 here, so two of the four row results suffice
     auto min_rows01 = [](float v) {
@@ -782,18 +702,16 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     int slk = __builtin_amdgcn_readfirstlane(__float_as_int(cache.slack));   // ... with how much (wave-uniform; bits of a float)
     if (cull && caching) {
         const int hv = __builtin_amdgcn_readfirstlane(hv_pre);
-        bool ok = true;
+        bool holds = true;                                       // this query is still inside the ball its anchor vouches for
         float dmax = 0.f;
-#pragma unroll
-        for (int n = 0; n < NQ; ++n)
-            if (qidx[n] < nq) {
-                const float4 a = anc_pre[n];
-                const float ex = qx[n] - a.x, ey = qy[n] - a.y, ez = qz[n] - a.z;
-                const float dl = __builtin_amdgcn_sqrtf(ez * ez + (ey * ey + ex * ex)) * 1.00001f + 1e-7f;
-                ok &= rq[n] + dl <= a.w;
-                dmax = fmaxf(dmax, dl);
-            }
-        if (hv >= 0 && __all(ok)) {
+        if (ok) {
+            const float4 a = anc_pre;
+            const float ex = qx - a.x, ey = qy - a.y, ez = qz - a.z;
+            const float dl = __builtin_amdgcn_sqrtf(ez * ez + (ey * ey + ex * ex)) * 1.00001f + 1e-7f;
+            holds = rq + dl <= a.w;
+            dmax = fmaxf(dmax, dl);
+        }
+        if (hv >= 0 && __all(holds)) {
             n_kept = hv & 255;
             if (lane == 0) cache.hdr[cidx] = hv + 256;            // one launch older
         } else {
@@ -812,9 +730,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
             // is only as durable as its most constrained anchor (late r5: with every vertex a contact and the bodies moving centimetres
             // per launch, config 5's groups built inflated lists that the far queries voided one launch later)
             float smin = __int_as_float(slk);
-#pragma unroll
-            for (int n = 0; n < NQ; ++n)
-                if (qidx[n] < nq && rq[n] > FDC_AS_NEAR) smin = fminf(smin, fmaxf(cache.slack, __int_as_float(slk) * (FDC_AS_NEAR / rq[n])));
+            if (ok && rq > FDC_AS_NEAR) smin = fminf(smin, fmaxf(cache.slack, __int_as_float(slk) * (FDC_AS_NEAR / rq)));
             smin = -max_rows01(-smin);
             smin = fminf(smin, __shfl_xor(smin, 32, 64));
             inflate = 3.f * speed <= smin;
@@ -830,43 +746,33 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         return r <= FDC_AS_NEAR ? sw : fmaxf(cache.slack, sw * (FDC_AS_NEAR / r));
     };
     // the radii / squared bounds the list is BUILT for: inflated by the slack when the list is going to be kept
-    float sbT[NQ];
+    float sbT;
     float glx = INFINITY, gly = INFINITY, glz = INFINITY, ghx = -INFINITY, ghy = -INFINITY, ghz = -INFINITY;
     float scx = 0.f, scy = 0.f, scz = 0.f, sR2 = 0.f;
     if (cull && n_kept < 0) {
-        float rT[NQ];
-#pragma unroll
-        for (int n = 0; n < NQ; ++n) {
-            rT[n] = inflate ? rq[n] + slack_of(rq[n]) : rq[n];
-            sbT[n] = (qidx[n] < nq) ? (inflate ? rT[n] * rT[n] * 1.00002f : sb[n]) : -INFINITY;
-        }
+        const float rT = inflate ? rq + slack_of(rq) : rq;
+        sbT = ok ? (inflate ? rT * rT * 1.00002f : sb) : -INFINITY;
         // Group bound for the box tests: the axis-aligned box around the queries' balls (centre x_i, radius r_i).
         // A cell some query needs intersects that query's ball, hence this box -- and for elongated groups (a shin above a
         // floor) the box is far tighter than a sphere around the centroid with the largest reach.
-#pragma unroll
-        for (int n = 0; n < NQ; ++n)
-            if (qidx[n] < nq) {
-                const float r = rT[n];
-                glx = fminf(glx, qx[n] - r); gly = fminf(gly, qy[n] - r); glz = fminf(glz, qz[n] - r);
-                ghx = fmaxf(ghx, qx[n] + r); ghy = fmaxf(ghy, qy[n] + r); ghz = fmaxf(ghz, qz[n] + r);
-            }
+        if (ok) {
+            glx = fminf(glx, qx - rT); gly = fminf(gly, qy - rT); glz = fminf(glz, qz - rT);
+            ghx = fmaxf(ghx, qx + rT); ghy = fmaxf(ghy, qy + rT); ghz = fmaxf(ghz, qz + rT);
+        }
         glx = min_rows01(glx); gly = min_rows01(gly); glz = min_rows01(glz);
         ghx = max_rows01(ghx); ghy = max_rows01(ghy); ghz = max_rows01(ghz);
         // ... and the sphere around the box centre that contains every ball (radius max_i |x_i - c| + r_i): for a far group the
         // ball box's corners reach much further than any ball does, the sphere cuts them off; a cell has to touch both.
         scx = 0.5f * (glx + ghx); scy = 0.5f * (gly + ghy); scz = 0.5f * (glz + ghz);
         float sR = 0.f;
-#pragma unroll
-        for (int n = 0; n < NQ; ++n)
-            if (qidx[n] < nq) {
-                const float ex = qx[n] - scx, ey = qy[n] - scy, ez = qz[n] - scz;
-                sR = fmaxf(sR, (__builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez) + rT[n]) * 1.00001f + 1e-6f);
-            }
+        if (ok) {
+            const float ex = qx - scx, ey = qy - scy, ez = qz - scz;
+            sR = fmaxf(sR, (__builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez) + rT) * 1.00001f + 1e-6f);
+        }
         sR = max_rows01(sR);
         sR2 = sR * sR * 1.00001f;
     } else {
-#pragma unroll
-        for (int n = 0; n < NQ; ++n) sbT[n] = sb[n];
+        sbT = sb;
     }
     // box-box overlap (closed): false only if the boxes are strictly apart along some axis
     // (bitwise |: with short-circuit || the compiler sinks the component loads into a chain of dependent branches)
@@ -881,13 +787,10 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     // workgroups per launch at 500k points, more than everything else the kernel reads.)
     // The per-query box tests of the list stages are lane-parallel (r3): the group's queries {x, y, z, squared bound} sit in
     // LDS, a pair of lanes (r15: 2, 4 or 8 lanes, by the stage's count) holds one box in registers and each of them walks its share of the queries.
-    float4* const sq = &s_p[wave][0];                            // [32 NQ] queries (s_p is only needed for the final merge)
+    float4* const sq = &s_p[wave][0];                            // [32] queries (s_p is only needed for the final merge)
     float4* const sbx = &sbox[wave][0][0];                       // [64][2] compacted boxes of a chunk-stage batch
-    auto put_queries = [&](const float* bound) {
-        if (half == 0) {
-#pragma unroll
-            for (int n = 0; n < NQ; ++n) sq[n * 32 + col] = make_float4(qx[n], qy[n], qz[n], bound[n]);
-        }
+    auto put_queries = [&](float bound) {
+        if (half == 0) sq[col] = make_float4(qx, qy, qz, bound);
         __builtin_amdgcn_wave_barrier();
     };
     // r15: lanes per box by each stage's count (nn_box_stage above).  Per form, as KEEP: a form keeps it only where it measured no slower.
@@ -945,7 +848,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
                 }
                 __builtin_amdgcn_wave_barrier();
                 {
-                    const int got = nn_box_stage<NQ, BOX_BY_COUNT>(sq, lane, nnear, box_forced, ST4_MAXCELL - ncell, 0,
+                    const int got = nn_box_stage<BOX_BY_COUNT>(sq, lane, nnear, box_forced, ST4_MAXCELL - ncell, 0,
                         [&](int j, bool, float4& blo, float4& bhi, int& tag) __attribute__((always_inline)) {
                             j = min(j, nnear - 1);
                             blo = sbx[2 * j]; bhi = sbx[2 * j + 1];
@@ -964,7 +867,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         // (32 quarters = 8 chunks per pass with a pair), boxes straight from global memory into their registers.
         ncell = __builtin_amdgcn_readfirstlane(ncell);
         if (listed) {
-            nsurv = nn_box_stage<NQ, BOX_BY_COUNT>(sq, lane, 4 * ncell, box_forced, ST4_MAXLIST, 1,
+            nsurv = nn_box_stage<BOX_BY_COUNT>(sq, lane, 4 * ncell, box_forced, ST4_MAXLIST, 1,
                 [&](int jq, bool valid, float4& blo, float4& bhi, int& tag) __attribute__((always_inline)) {       // cell jq >> 2 of the list, its quarter jq & 3
                     const int k4 = 4 * (int)clist[wave][valid ? (jq >> 2) : 0];
                     const size_t qb = ((size_t)(WPG * (k4 >> 2) + sub) * 4 + (jq & 3)) * 2;
@@ -983,13 +886,8 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
                 ((unsigned*)cache.ids)[(size_t)cidx * (NN_CACHE_CAP / 2) + lane] =
                     (unsigned)slist[wave][2 * lane] | ((2 * lane + 1 < nsurv ? (unsigned)slist[wave][2 * lane + 1] : 0u) << 16);
             if (lane == 0) cache.hdr[cidx] = keep ? (nsurv | 256) : -1;
-            if (half == 0) {
-#pragma unroll
-                for (int n = 0; n < NQ; ++n)
-                    if (qidx[n] < nq)                              // R_i with the validity test's rounding margin taken off; no list: never valid
-                        cache.anchor[(size_t)sub * nq + qidx[n]] =
-                            make_float4(qx[n], qy[n], qz[n], keep ? (rq[n] + slack_of(rq[n])) * 0.99998f - 2e-6f : -1.f);
-            }
+            if (half == 0 && ok)                                  // R_i with the validity test's rounding margin taken off; no list: never valid
+                cache.anchor[(size_t)sub * nq + qidx] = make_float4(qx, qy, qz, keep ? (rq + slack_of(rq)) * 0.99998f - 2e-6f : -1.f);
         }
         if (!listed) nsurv = 4 * myn;                           // list overflow: scan this wave's whole share (still exact)
     }
@@ -1004,16 +902,11 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         const int n_raw = __builtin_amdgcn_readfirstlane(nsurv);
         FDC_STAT(6, lane == 0 ? n_raw : 0);
         put_queries(sb);
-        const bool boxes_here = boxes_pre && n_kept >= 0;       // (a list built in this launch is not the one whose boxes were copied)
-        const int nout = nn_box_stage<NQ, BOX_BY_COUNT>(sq, lane, n_raw, box_forced, ST4_MAXLIST, 2,
+        const int nout = nn_box_stage<BOX_BY_COUNT>(sq, lane, n_raw, box_forced, ST4_MAXLIST, 2,
             [&](int kk, bool valid, float4& blo, float4& bhi, int& id) __attribute__((always_inline)) {
                 id = (int)slist[wave][valid ? kk : 0];
-                if (boxes_here) {                                 // (wave-uniform; entry kk of the kept list is entry kk of the copy)
-                    blo = sbx[2 * (valid ? kk : 0)]; bhi = sbx[2 * (valid ? kk : 0) + 1];
-                } else {
-                    const size_t qb = ((size_t)(WPG * (id >> 2) + sub) * 4 + (id & 3)) * 2;
-                    blo = T.qbounds[qb]; bhi = T.qbounds[qb + 1];
-                }
+                const size_t qb = ((size_t)(WPG * (id >> 2) + sub) * 4 + (id & 3)) * 2;
+                blo = T.qbounds[qb]; bhi = T.qbounds[qb + 1];
             },
             [&](int at, int id) __attribute__((always_inline)) { slist[wave][at] = (unsigned short)id; });   // (in place: a pass reads its ids before it writes, and writes trail reads)
         nsurv = nout;
@@ -1031,7 +924,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
 #ifdef FDC_NN_STATS
     if (lane == 0 && !idle) atomicAdd(&g_nn_hist[(listed ? 0 : 16) + (nsurv > 0 ? 32 - __clz(nsurv) : 0)], 1ull);
 #endif
-    // queue of filter survivors awaiting their exact evaluation (NQ == 1; see the main loop): per lane up to ST4_QCAP positions
+    // queue of filter survivors awaiting their exact evaluation (see the main loop): per lane up to ST4_QCAP positions
     // in the LDS the list stages used (sbox: 2 KB per wave, free from here on)
     unsigned* const cq = (unsigned*)&sbox[wave][0][0];
     int cq_n = 0;
@@ -1062,7 +955,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         cf4_t cc_next = centers_c[ch];
         nsurv = __builtin_amdgcn_readfirstlane(nsurv);
         int cur = -1;                                                      // chunk the queries are centred on
-        bf16x8 bfrag[NQ];
+        bf16x8 bfrag = __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u));
         // Per query and current cell: thr (rows with a score below it pass), e2 = 2.01 eps and c2 = eps - |x'|^2, with
         // eps = K1 |x'| rc + K2 (|x'|^2 + rc^2) the filter's error bound for this cell (|score + |x'|^2 - d| <= eps / 1.5).
         // r5: the SCORES tighten the threshold, without an exact evaluation.  The error bound cuts both ways: a row with score s lies
@@ -1074,15 +967,13 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         // full: launches of 150-290 us, tools/phase_switch_probe.py / phase_switch_timeline.py); now only the rows within 2 eps
         // of the tile's best are.  Pruning only: every row that can win or tie still passes.  (What a cell's scores proved is not
         // carried to the next cell: one more live register in this 64-register kernel spills a fragment of the ring.)
-        float thr[NQ], e2[NQ], c2[NQ];
-#pragma unroll
-        for (int n = 0; n < NQ; ++n) { thr[n] = -INFINITY; e2[n] = c2[n] = 0.f; bfrag[n] = __builtin_bit_cast(bf16x8, make_uint4(0u, 0u, 0u, 0u)); }
-        // NQ == 1: the tile of this lane's current best (-1: none in this half) and the mask that clears its row's bit --
+        float thr = -INFINITY, e2 = 0.f, c2 = 0.f;
+        // the tile of this lane's current best (-1: none in this half) and the mask that clears its row's bit --
         // own_p only changes in the queue-full path below, which refreshes them
         int seed_tile = -1;
         unsigned seed_keep = ~0u;
         auto seed_refresh = [&]() {
-            const int spos = __float_as_int(own_p[0].w);
+            const int spos = __float_as_int(own_p.w);
             seed_tile = (spos >= 0 && ((spos >> 2) & 1) == half) ? (spos >> 5) : -1;
             seed_keep = ~(1u << ((spos & 3) + 4 * ((spos >> 3) & 3)));
         };
@@ -1099,24 +990,21 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
                 cur = ch;
                 // re-centre the queries on the chunk centre
                 const float rc = cc.w;
-#pragma unroll
-                for (int n = 0; n < NQ; ++n) {
-                    const float xx = qx[n] - cc.x, xy = qy[n] - cc.y, xz = qz[n] - cc.z;
-                    const float X2 = __fmaf_rn(xz, xz, __fmaf_rn(xy, xy, xx * xx));
-                    const float X = __builtin_amdgcn_sqrtf(X2) * 1.000001f;  // only feeds eps: 1-ulp v_sqrt_f32, rounded up
-                    const unsigned hx = f2bf(xx), hy = f2bf(xy), hz = f2bf(xz);
-                    const unsigned lx = f2bf(xx - bf2f(hx)), ly = f2bf(xy - bf2f(hy)), lz = f2bf(xz - bf2f(hz));
-                    const unsigned px = hx | (lx << 16), py = hy | (ly << 16), pz = hz | (lz << 16);   // (the factor -2 is in the A fragments)
-                    const unsigned one = 0x3F80u;
-                    const uint4 u = half == 0 ? make_uint4(px, px, py, py) : make_uint4(pz, pz, one | (one << 16), one);
-                    bfrag[n] = __builtin_bit_cast(bf16x8, u);
-                    const float eps = MF_K1 * X * rc + MF_K2 * (X2 + rc * rc);
-                    e2[n] = 2.01f * eps;
-                    c2[n] = eps - X2;
-                    // this half's own bound (the other half's may be tighter after an exact hit; it is folded in at the next
-                    // hit -- a looser threshold only lets more pairs through, and saves a cross-half exchange per cell)
-                    thr[n] = (qidx[n] < nq) ? own_d[n] + c2[n] : -INFINITY;
-                }
+                const float xx = qx - cc.x, xy = qy - cc.y, xz = qz - cc.z;
+                const float X2 = __fmaf_rn(xz, xz, __fmaf_rn(xy, xy, xx * xx));
+                const float X = __builtin_amdgcn_sqrtf(X2) * 1.000001f;  // only feeds eps: 1-ulp v_sqrt_f32, rounded up
+                const unsigned hx = f2bf(xx), hy = f2bf(xy), hz = f2bf(xz);
+                const unsigned lx = f2bf(xx - bf2f(hx)), ly = f2bf(xy - bf2f(hy)), lz = f2bf(xz - bf2f(hz));
+                const unsigned px = hx | (lx << 16), py = hy | (ly << 16), pz = hz | (lz << 16);   // (the factor -2 is in the A fragments)
+                const unsigned one = 0x3F80u;
+                const uint4 u = half == 0 ? make_uint4(px, px, py, py) : make_uint4(pz, pz, one | (one << 16), one);
+                bfrag = __builtin_bit_cast(bf16x8, u);
+                const float eps = MF_K1 * X * rc + MF_K2 * (X2 + rc * rc);
+                e2 = 2.01f * eps;
+                c2 = eps - X2;
+                // this half's own bound (the other half's may be tighter after an exact hit; it is folded in at the next
+                // hit -- a looser threshold only lets more pairs through, and saves a cross-half exchange per cell)
+                thr = ok ? own_d + c2 : -INFINITY;
             }
             const int base = ch * MF_CH + qd * (QT * 32);
 #pragma unroll
@@ -1125,103 +1013,71 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
                 const int tn = tile + ST4_PF;                               // a quarter's four tiles are within reach of the immediates
                 // (the tile's offset rides in the SCALAR offset: added to the lane offset it becomes a v_or per tile)
                 f[tile % ST4_PF] = __builtin_amdgcn_raw_buffer_load_b128(frs, lofs, (tn < QT ? fo : fo_next) + (unsigned)(tn < QT ? tn : tn - QT) * 1024u, 0);
-                f32x16_t acc_q[NQ];
+                const f32x16_t acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bfrag, zero, 0, 0, 0);
+                const float t0 = fminf(fminf(acc[0], acc[1]), acc[2]), t1 = fminf(fminf(acc[3], acc[4]), acc[5]);
+                const float t2 = fminf(fminf(acc[6], acc[7]), acc[8]), t3 = fminf(fminf(acc[9], acc[10]), acc[11]);
+                const float t4 = fminf(fminf(acc[12], acc[13]), acc[14]);
+                const float g0 = fminf(fminf(t0, t1), t2), g1 = fminf(fminf(t3, t4), acc[15]);      // rows 0-8, rows 9-15
+                const float m = fminf(g0, g1);
+                FDC_STAT(0, lane == 0);
+                if (__any(m < thr)) {
+                    FDC_STAT(1, lane == 0);
+                    // This lane's rows that passed, as a bit mask: sign(acc[r] - thr) shifted in row by row (v_sub_f32 +
+                    // v_alignbit_b32 per row; a difference of two distinct finite floats is never rounded to zero, an
+                    // invalid lane's thr is -inf, and a row passes iff its triple's minimum does).  r3: 13.5 entries per wave, and FDC_NN_STATS shows most of them carry
+                    // a real candidate next to the seeds (about one other point per query lies within the filter's eps
+                    // of the bound), so the r2 form -- 16 wave ballots + ~50 SALU to recognise seed-only entries, then
+                    // 16 64-bit shifts to recover the per-lane bits -- paid both halves nearly every time: half of the
+                    // kernel's VALU cycles (ablation: 79 -> 44 us steady state without the body).
+                    // Only the HALF of the min tree (rows 0-8 / rows 9-15) in which some lane has a passing row is expanded: an
+                    // entry is usually one candidate or one seed, i.e. one half -- 2 compares + 18 or 14 instead of 32
+                    // instructions, 13.5 entries per wave.  (Finer -- the five row triples of the tree's first level, 6 + 7
+                    // instructions per entry -- costs 15-26 spilled registers in this 64-register kernel; nested under the
+                    // halves it fits, and the extra wave votes and branches make the launch 3 % slower: 67.8 vs 65.9 us.)
+                    unsigned mask = 0;
+                    if (ok) thr = fminf(thr, m + e2);                      // (a lane without a passing row: m >= thr, no change)
+                    const float th = thr;
+                    if (__any(g0 < th)) {
 #pragma unroll
-                for (int n = 0; n < NQ; ++n) acc_q[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bfrag[n], zero, 0, 0, 0);
+                        for (int r = 8; r >= 0; --r) mask = __builtin_amdgcn_alignbit(mask, __float_as_uint(acc[r] - th), 31);
+                    }
+                    if (__any(g1 < th)) {
+                        unsigned hi = 0;
 #pragma unroll
-                for (int n = 0; n < NQ; ++n) {
-                    const f32x16_t acc = acc_q[n];
-                    const float t0 = fminf(fminf(acc[0], acc[1]), acc[2]), t1 = fminf(fminf(acc[3], acc[4]), acc[5]);
-                    const float t2 = fminf(fminf(acc[6], acc[7]), acc[8]), t3 = fminf(fminf(acc[9], acc[10]), acc[11]);
-                    const float t4 = fminf(fminf(acc[12], acc[13]), acc[14]);
-                    const float g0 = fminf(fminf(t0, t1), t2), g1 = fminf(fminf(t3, t4), acc[15]);      // rows 0-8, rows 9-15
-                    const float m = fminf(g0, g1);
-                    FDC_STAT(0, lane == 0);
-                    if (__any(m < thr[n])) {
-                        FDC_STAT(1, lane == 0);
-                        // This lane's rows that passed, as a bit mask: sign(acc[r] - thr) shifted in row by row (v_sub_f32 +
-                        // v_alignbit_b32 per row; a difference of two distinct finite floats is never rounded to zero, an
-                        // invalid lane's thr is -inf, and a row passes iff its triple's minimum does).  r3: 13.5 entries per wave, and FDC_NN_STATS shows most of them carry
-                        // a real candidate next to the seeds (about one other point per query lies within the filter's eps
-                        // of the bound), so the r2 form -- 16 wave ballots + ~50 SALU to recognise seed-only entries, then
-                        // 16 64-bit shifts to recover the per-lane bits -- paid both halves nearly every time: half of the
-                        // kernel's VALU cycles (ablation: 79 -> 44 us steady state without the body).
-                        // Only the HALF of the min tree (rows 0-8 / rows 9-15) in which some lane has a passing row is expanded: an
-                        // entry is usually one candidate or one seed, i.e. one half -- 2 compares + 18 or 14 instead of 32
-                        // instructions, 13.5 entries per wave.  (Finer -- the five row triples of the tree's first level, 6 + 7
-                        // instructions per entry -- costs 15-26 spilled registers in this 64-register kernel; nested under the
-                        // halves it fits, and the extra wave votes and branches make the launch 3 % slower: 67.8 vs 65.9 us.)
-                        unsigned mask = 0;
-                        if (qidx[n] < nq) thr[n] = fminf(thr[n], m + e2[n]);               // (a lane without a passing row: m >= thr, no change)
-                        const float th = thr[n];
-                        if (__any(g0 < th)) {
-#pragma unroll
-                            for (int r = 8; r >= 0; --r) mask = __builtin_amdgcn_alignbit(mask, __float_as_uint(acc[r] - th), 31);
-                        }
-                        if (__any(g1 < th)) {
-                            unsigned hi = 0;
-#pragma unroll
-                            for (int r = 15; r >= 9; --r) hi = __builtin_amdgcn_alignbit(hi, __float_as_uint(acc[r] - th), 31);
-                            mask |= hi << 9;
-                        }
-                        // the lane's current best passes by construction (it sits in this tile's rows of this half when
-                        // its tile comes up) and is never re-evaluated: its row's bit is cleared
-                        if constexpr (NQ == 1) {
-                            mask &= (seed_tile == (base >> 5) + tile) ? seed_keep : ~0u;
-                        } else {
-                            const int spos = __float_as_int(own_p[n].w);
-                            const bool mine = (spos >> 5) == (base >> 5) + tile && ((spos >> 2) & 1) == half;
-                            if (mine) mask &= ~(1u << ((spos & 3) + 4 * ((spos >> 3) & 3)));
-                        }
-                        if (!__any(mask != 0)) continue;
-                        // Real candidates (FDC_NN_STATS over a fit: 84 % of the waves meet at least one per launch, ~13 entries
-                        // per wave -- with bodies hovering above a densely sampled floor about one other point per query lies
-                        // within the filter's eps of the bound).  Evaluated on the spot each one is a dependent L2 round trip
-                        // in the middle of the main loop (nothing else of the wave proceeds meanwhile: ~10 of them in a row are
-                        // most of a lone wave's 11-13 us main loop).  So they are QUEUED -- positions per lane, in
-                        // the LDS the list stages no longer need -- and evaluated together after the loop, all loads in flight at
-                        // once.  The bound is not tightened in between: the filter then lets through a superset of what it would
-                        // have, every member of which is evaluated exactly and merged in (d, index) order -- same result, bit for bit.
-                        if constexpr (NQ == 1) {
-                            while (mask) {
-                                const int r = __ffs(mask) - 1;
-                                mask &= mask - 1;
-                                const int pos = base + tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                                if (pos < T.n) {   // (a padding row scores 1e30, which still passes an INFINITE bound -- unseeded scans; the
-                                                   // lane's own best was cleared from the mask above)
-                                    FDC_STAT(2, 1);
-                                    if (cq_n < ST4_QCAP) { cq[cq_n * 64 + lane] = (unsigned)pos; ++cq_n; }
-                                    else {                                 // queue full (rare): evaluated on the spot
-                                        const float4 p = T.pts[pos];
-                                        const int gi = __float_as_int(p.w);
-                                        const float d = nn_exact_d2(qx[n], qy[n], qz[n], p.x, p.y, p.z);
-                                        if (nn_better(d, gi, own_d[n], own_i[n])) {
-                                            own_d[n] = d; own_i[n] = gi;
-                                            own_p[n] = make_float4(p.x, p.y, p.z, __int_as_float(pos));
-                                            seed_refresh();
-                                        }
-                                    }
-                                }
-                            }
-                            continue;
-                        }
-                        while (mask) {                                     // rows of this lane that passed the filter
-                            const int r = __ffs(mask) - 1;
-                            mask &= mask - 1;
-                            const int pos = base + tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                            if (pos < T.n && pos != __float_as_int(own_p[n].w)) {
-                                FDC_STAT(2, 1);
+                        for (int r = 15; r >= 9; --r) hi = __builtin_amdgcn_alignbit(hi, __float_as_uint(acc[r] - th), 31);
+                        mask |= hi << 9;
+                    }
+                    // the lane's current best passes by construction (it sits in this tile's rows of this half when
+                    // its tile comes up) and is never re-evaluated: its row's bit is cleared
+                    mask &= (seed_tile == (base >> 5) + tile) ? seed_keep : ~0u;
+                    if (!__any(mask != 0)) continue;
+                    // Real candidates (FDC_NN_STATS over a fit: 84 % of the waves meet at least one per launch, ~13 entries
+                    // per wave -- with bodies hovering above a densely sampled floor about one other point per query lies
+                    // within the filter's eps of the bound).  Evaluated on the spot each one is a dependent L2 round trip
+                    // in the middle of the main loop (nothing else of the wave proceeds meanwhile: ~10 of them in a row are
+                    // most of a lone wave's 11-13 us main loop).  So they are QUEUED -- positions per lane, in
+                    // the LDS the list stages no longer need -- and evaluated together after the loop, all loads in flight at
+                    // once.  The bound is not tightened in between: the filter then lets through a superset of what it would
+                    // have, every member of which is evaluated exactly and merged in (d, index) order -- same result, bit for bit.
+                    while (mask) {
+                        const int r = __ffs(mask) - 1;
+                        mask &= mask - 1;
+                        const int pos = base + tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                        if (pos < T.n) {   // (a padding row scores 1e30, which still passes an INFINITE bound -- unseeded scans; the
+                                           // lane's own best was cleared from the mask above)
+                            FDC_STAT(2, 1);
+                            if (cq_n < ST4_QCAP) { cq[cq_n * 64 + lane] = (unsigned)pos; ++cq_n; }
+                            else {                                 // queue full (rare): evaluated on the spot
                                 const float4 p = T.pts[pos];
                                 const int gi = __float_as_int(p.w);
-                                const float d = nn_exact_d2(qx[n], qy[n], qz[n], p.x, p.y, p.z);
-                                if (nn_better(d, gi, own_d[n], own_i[n])) {
-                                    own_d[n] = d; own_i[n] = gi;
-                                    own_p[n] = make_float4(p.x, p.y, p.z, __int_as_float(pos));
+                                const float d = nn_exact_d2(qx, qy, qz, p.x, p.y, p.z);
+                                if (nn_better(d, gi, own_d, own_i)) {
+                                    own_d = d; own_i = gi;
+                                    own_p = make_float4(p.x, p.y, p.z, __int_as_float(pos));
+                                    seed_refresh();
                                 }
                             }
                         }
-                        const float sbest = fminf(own_d[n], __shfl_xor(own_d[n], 32, 64));
-                        if (qidx[n] < nq) thr[n] = fminf(thr[n], sbest + c2[n]);
                     }
                 }
             }
@@ -1230,27 +1086,25 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
             fo = fo_next;
         }
     }
-    if constexpr (NQ == 1) {
-        // the queued candidates: up to four loads in flight per lane and round (a wave's LDS traffic is in order: no barrier)
-        for (int k0 = 0; __any(k0 < cq_n); k0 += 4) {
-            float4 p[4];
-            int ps[4];
+    // the queued candidates: up to four loads in flight per lane and round (a wave's LDS traffic is in order: no barrier)
+    for (int k0 = 0; __any(k0 < cq_n); k0 += 4) {
+        float4 p[4];
+        int ps[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                ps[k] = (k0 + k < cq_n) ? (int)cq[(k0 + k) * 64 + lane] : 0;
-                p[k] = T.pts[ps[k]];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (k0 + k < cq_n) {
-                    const int gi = __float_as_int(p[k].w);
-                    const float d = nn_exact_d2(qx[0], qy[0], qz[0], p[k].x, p[k].y, p[k].z);
-                    if (nn_better(d, gi, own_d[0], own_i[0])) {
-                        own_d[0] = d; own_i[0] = gi;
-                        own_p[0] = make_float4(p[k].x, p[k].y, p[k].z, __int_as_float(ps[k]));
-                    }
-                }
+        for (int k = 0; k < 4; ++k) {
+            ps[k] = (k0 + k < cq_n) ? (int)cq[(k0 + k) * 64 + lane] : 0;
+            p[k] = T.pts[ps[k]];
         }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k0 + k < cq_n) {
+                const int gi = __float_as_int(p[k].w);
+                const float d = nn_exact_d2(qx, qy, qz, p[k].x, p[k].y, p[k].z);
+                if (nn_better(d, gi, own_d, own_i)) {
+                    own_d = d; own_i = gi;
+                    own_p = make_float4(p[k].x, p[k].y, p[k].z, __int_as_float(ps[k]));
+                }
+            }
     }
     TL_STAMP(3);
     // (the launch order's key: the work items scanned, filed under the launch position.  Also tried as keys: + a bonus when the list was built this launch -- no
@@ -1258,24 +1112,20 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
     // it follows contention)
     if (cache.order_mode != 0 && lane == 0 && !idle) cache.hdr[4 * ((nq + 31) / 32) + (int)blockIdx.x] = nsurv;
     // the two halves of a wave hold different scene rows of the same queries; then the four waves meet in LDS
-    unsigned keepm[NQ];                                          // wave-uniform: bit col = query n * 32 + col keeps its record
-#pragma unroll
-    for (int n = 0; n < NQ; ++n) {
-        const float od = __shfl_xor(own_d[n], 32, 64);
-        const int oi = __shfl_xor(own_i[n], 32, 64);
-        float4 op;
-        op.x = __shfl_xor(own_p[n].x, 32, 64); op.y = __shfl_xor(own_p[n].y, 32, 64);
-        op.z = __shfl_xor(own_p[n].z, 32, 64); op.w = __shfl_xor(own_p[n].w, 32, 64);
-        if (oi >= 0 && (own_i[n] < 0 || nn_better(od, oi, own_d[n], own_i[n]))) { own_d[n] = od; own_i[n] = oi; own_p[n] = op; }
-        // a best that is still the seed (a lane only ever replaces its best by a strictly better pair, so the seed never comes back):
-        // idx[q] and seedpt[q] already hold these bits
-        keepm[n] = 0u;
-        if constexpr (KEEP) {
-            const bool same = half == 0 && s_i[wave][n * 32 + col] == own_i[n] && __float_as_int(s_d[wave][n * 32 + col]) == __float_as_int(own_p[n].w);
-            keepm[n] = (unsigned)__ballot(same);
-        }
-        if (half == 0) { s_d[wave][n * 32 + col] = own_d[n]; s_i[wave][n * 32 + col] = own_i[n]; s_p[wave][n * 32 + col] = own_p[n]; }
+    const float od = __shfl_xor(own_d, 32, 64);
+    const int oi = __shfl_xor(own_i, 32, 64);
+    float4 op;
+    op.x = __shfl_xor(own_p.x, 32, 64); op.y = __shfl_xor(own_p.y, 32, 64);
+    op.z = __shfl_xor(own_p.z, 32, 64); op.w = __shfl_xor(own_p.w, 32, 64);
+    if (oi >= 0 && (own_i < 0 || nn_better(od, oi, own_d, own_i))) { own_d = od; own_i = oi; own_p = op; }
+    // a best that is still the seed (a lane only ever replaces its best by a strictly better pair, so the seed never comes back):
+    // idx[q] and seedpt[q] already hold these bits
+    unsigned keepm = 0u;                                         // wave-uniform: bit col = query col keeps its record
+    if constexpr (KEEP) {
+        const bool same = half == 0 && s_i[wave][col] == own_i && __float_as_int(s_d[wave][col]) == __float_as_int(own_p.w);
+        keepm = (unsigned)__ballot(same);
     }
+    if (half == 0) { s_d[wave][col] = own_d; s_i[wave][col] = own_i; s_p[wave][col] = own_p; }
     __syncthreads();
 #ifdef FDC_NN_STATS
     {   // per wave: slow-path entries (wave-level count sits in lane 0) and the longest per-lane chain of exact re-evaluations
@@ -1295,9 +1145,9 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
         tl[0] = tl_t0; tl[1] = wall_clock64(); tl[2] = xcc & 15; tl[3] = tl_p[0]; tl[4] = tl_p[1]; tl[5] = tl_p[2]; tl[6] = tl_p[3]; tl[7] = (unsigned long long)tl_nsurv;
     }
 #endif
-    if (tid < GPW * 32 * NQ) {
-        const int g = tid / (32 * NQ), e = tid % (32 * NQ);      // group slot of this workgroup, query of the group
-        const int qo = (wg * GPW + g) * (32 * NQ) + e;
+    if (tid < GPW * 32) {
+        const int g = tid / 32, e = tid % 32;                    // group slot of this workgroup, query of the group
+        const int qo = (wg * GPW + g) * 32 + e;
         if (wg < nwg && qo < nq) {
             int bw = g * WPG;
             float bd = s_d[bw][e];
@@ -1311,7 +1161,7 @@ __global__ __launch_bounds__(64 * WPB, NQ == 1 ? FDC_ST4_OCC : FDC_ST4_OCC2) voi
             const int qd = perm ? s_q[g][e] : qo;
             dist[qd] = bd;
             // (one wave per workgroup: the storing thread's own wave formed the mask)
-            if (!KEEP || !((keepm[e >> 5] >> (e & 31)) & 1u)) {
+            if (!KEEP || !((keepm >> e) & 1u)) {
                 idx[qd] = bi;
                 seedpt[qd] = s_p[bw][e];
             }
@@ -1488,9 +1338,8 @@ struct NNOrder {
     // tests / diagnosis (fdcap_debug_contact_diet): launches that kept unchanged records (NNCache::keep), launches that ran under a
     // query order, rebuilds of the query order
     int n_kept = 0, n_permuted = 0, n_rebuilds = 0;
-    // r15 (fdcap_debug_nn_box_tests): one-wave launches by the lanes per box they were given (by count, 2, 4, 8), and those whose
-    // waves on a kept list copy its boxes with the set-up (prefetch on, a cache and a query order)
-    int n_box[5] = {0, 0, 0, 0, 0};
+    // r15 (fdcap_debug_nn_box_tests): one-wave launches by the lanes per box they were given (by count, 2, 4, 8)
+    int n_box[4] = {0, 0, 0, 0};
 };
 static inline size_t nn_query_order_ints(int nq);                       // fdc_scene.h (the radix sort lives there)
 static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st);
@@ -1524,13 +1373,10 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
             // (+0.6 / +0.2 us per launch at 160 / 128 frames x 500 contacts), so they store every record as before
             nc.keep = nc.keep && wpg == 1 && seedpt != nullptr && seed != nullptr && seed == idx && !seed_missing;
             if (ord) { ord->n_kept += nc.keep ? 1 : 0; ord->n_permuted += nc.perm ? 1 : 0; }
-            if (ord && wpg == 1) {
-                ++ord->n_box[nc.box_lanes == 2 ? 1 : nc.box_lanes == 4 ? 2 : nc.box_lanes == 8 ? 3 : 0];
-                ord->n_box[4] += (nc.box_prefetch && nc.hdr != nullptr && nc.perm != nullptr) ? 1 : 0;
-            }
-            if (wpg == 4) hipLaunchKernelGGL((nn_stream4_kernel<1, 4>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-            else if (wpg == 2) hipLaunchKernelGGL((nn_stream4_kernel<1, 2>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-            else hipLaunchKernelGGL((nn_stream4_kernel<1, 1, 1>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
+            if (ord && wpg == 1) ++ord->n_box[nc.box_lanes == 2 ? 1 : nc.box_lanes == 4 ? 2 : nc.box_lanes == 8 ? 3 : 0];
+            if (wpg == 4) hipLaunchKernelGGL((nn_stream4_kernel<4>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
+            else if (wpg == 2) hipLaunchKernelGGL((nn_stream4_kernel<2>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
+            else hipLaunchKernelGGL((nn_stream4_kernel<1, 1>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
             const bool resort = ordered && (ord->sorted_groups != groups || ++ord->age >= ord->every);
             if (qorder && ord->perm_mode == 0 && (ord->perm_n != nq || seed_missing || (resort && ord->sorted_groups == groups))) {
                 // new groups: their kept lists go (hdr = -1, by the key kernel), the next launch records its work items in

@@ -21,7 +21,8 @@ namespace fdc {
 // switch's lifetime ("read when"):
 //   once per process     proc_switches(): clip_fwd_rows, clip_kgrad_rows, pn_rb2, pn_nw, pn_ksw, nn_stream;
 //                        gemm_split3 through gemm_split3_enabled(); nn_cache_slack as fdcap_chamfer_fwd_scene uses it
-//   every opt_create     nn_seed, nn_cull, skin_vec, fuse_skin, nn_cache_slack, nn_order (copied into the optimiser state)
+//   every opt_create     nn_seed, nn_cull, skin_vec, fuse_skin, nn_cache_slack, nn_order, pose_trim, nn_keep_records,
+//                        contact_recompute, nn_box_lanes (copied into the optimiser state)
 //   every call           gemm_split3 in fdcap_panel_gemm
 struct FormSwitches {
     // FDCAP_CLIP_FORMS_MIN_ROWS: row count from which the clip-sized forms are selected; it overrides BOTH thresholds -- tests run
@@ -47,22 +48,16 @@ struct FormSwitches {
     float nn_cache_slack = 0.03f;             // FDCAP_NN_CACHE_SLACK: metres; 0 disables the kept work lists
     bool skin_vec = true;        // FDCAP_SKIN_VEC=0 (A/B): the scalar-load skinning backward
     bool fuse_skin = true;       // FDCAP_FUSE_SKIN=0 (A/B): blend product and skinning forward as two launches
-    // FDCAP_POSE_TRIM=0: the pose kernels treat all 55 joints alike (plan_pose_joints' full plan).  Per fit; fdcap_opt_create[_clips]
-    // reads it next to its forms_read_env() call (fdc_api_opt.h), not forms_read_env(): tests/test_forms_cpu.py pins the set of names
-    // this header reads
+    // FDCAP_POSE_TRIM=0: the pose kernels treat all 55 joints alike (plan_pose_joints' full plan).
     bool pose_trim = true;
-    // r14, read in the same place and for the same reason.  FDCAP_NN_KEEP_RECORDS=0: the in-loop search rewrites every neighbour
-    // record in every launch (NNCache::keep, fdc_chamfer.h).  FDCAP_CONTACT_RECOMPUTE=0: skin_bwd_vec_kernel stages the world
-    // vertices, the distances and all 55 skinning transforms instead of forming the first two and staging the rows below ja_hi.
+    // r14.  FDCAP_NN_KEEP_RECORDS=0: the in-loop search rewrites every neighbour record in every launch (NNCache::keep,
+    // fdc_chamfer.h).  FDCAP_CONTACT_RECOMPUTE=0: skin_bwd_vec_kernel stages the world vertices, the distances and all 55 skinning
+    // transforms instead of forming the first two and staging the rows below ja_hi.
     bool nn_keep_records = true;
     bool contact_recompute = true;
-    // r15, read in the same place and for the same reason.  FDCAP_NN_BOX_LANES: lanes that share one box in the in-loop search's
-    // per-query box tests (nn_box_lanes below): 0 by the pass's count, 2 a pair everywhere (every launch before r15), 4 / 8 forced.
+    // r15.  FDCAP_NN_BOX_LANES: lanes that share one box in the in-loop search's per-query box tests (nn_box_lanes below): 0 by the
+    // pass's count, 2 a pair everywhere (every launch before r15), 4 / 8 forced; anything else is 0.
     int nn_box_lanes = 0;
-    // FDCAP_NN_BOX_PREFETCH=1: a wave on a kept list copies the listed quarters' boxes into LDS next to its set-up loads instead of
-    // fetching them inside the filter, a round trip of its own (NNCache::box_prefetch).  Off by default: measured alone it is no
-    // faster than the parent (49.36 / 49.14 against 49.17 / 48.76 us per launch, profiles/r15_search_fixed_work_ab.txt).
-    bool nn_box_prefetch = false;
 };
 inline FormSwitches forms_read_env() {
     FormSwitches s;
@@ -79,6 +74,10 @@ inline FormSwitches forms_read_env() {
     if (const char* e = getenv("FDCAP_NN_CACHE_SLACK")) s.nn_cache_slack = (float)atof(e);
     s.skin_vec = !off("FDCAP_SKIN_VEC");
     s.fuse_skin = !off("FDCAP_FUSE_SKIN");
+    s.pose_trim = !off("FDCAP_POSE_TRIM");
+    s.nn_keep_records = !off("FDCAP_NN_KEEP_RECORDS");
+    s.contact_recompute = !off("FDCAP_CONTACT_RECOMPUTE");
+    if (const char* e = getenv("FDCAP_NN_BOX_LANES")) { const int v = atoi(e); s.nn_box_lanes = (v == 2 || v == 4 || v == 8) ? v : 0; }
     return s;
 }
 inline const FormSwitches& proc_switches() { static const FormSwitches s = forms_read_env(); return s; }
@@ -102,6 +101,7 @@ inline const char* form_name(Form f) {
         "blend_skin_fwd_kernel", "skin_fwd_kernel",
         "skin_bwd_vec_kernel", "skin_bwd_small_kernel", "skin_bwd_small_kernel(K > 4)", "skin_bwd_kernel(one workgroup per frame)",
         "skin_bwd_kernel(chunks, MFMA dA)", "skin_bwd_kernel(chunks, list dA)",
+        // (labels that tests and tests/forms_table.json pin, not template spellings: the one-wave form is nn_stream4_kernel<1, 1>)
         "nn_stream4_kernel(4 waves per group)", "nn_stream4_kernel(2 waves per group)", "nn_stream4_kernel<1,1,1>", "nn_mfma_kernel",
         "nn_direct_kernel",
         nullptr, nullptr,

@@ -149,7 +149,8 @@ struct OptState {
     DevBuf<float4> seedpt;    // coordinates (+ position in the sorted scene) of each query's current neighbour: next launch's seed
     // work-list cache of the in-loop NN launch (fdc_chamfer.h NNCache): ids [groups * 4][64], hdr [groups * 4], anchors [4][nq]
     FormSwitches sw;               // the switches as fdcap_opt_create[_clips] read them (fdc_forms.h): nn_seed, nn_cull, skin_vec, fuse_skin,
-                                   // nn_cache_slack, nn_order hold for this optimiser; the others are per process (proc_switches())
+                                   // nn_cache_slack, nn_order, pose_trim, nn_keep_records, contact_recompute, nn_box_lanes hold for this
+                                   // optimiser; the others are per process (proc_switches())
     DevBuf<float> loss_rows;       // [R][LROW] per-frame partial sums of the printed loss terms (logging iterations)
     bool log_pending = false;      // a logging backward (log_terms = 2) left the reduction of loss_rows to the next step launch
     unsigned log_mask = 0;
@@ -176,7 +177,6 @@ struct OptState {
         NNCache nc{sw.nn_cache_slack > 0.f ? nnc_ids.p : nullptr, sw.nn_cache_slack > 0.f ? nnc_hdr.p : nullptr, nnc_anchor.p, sw.nn_cache_slack};
         nc.keep = sw.nn_keep_records;                        // (nn_search decides per launch whether the records may be kept)
         nc.box_lanes = sw.nn_box_lanes;
-        nc.box_prefetch = sw.nn_box_prefetch;
         return nc;
     }
     DevBuf<float> dA, dtransl_v, dMv, dsv, dPF, dJw, dX, dCAM, dscale_row;     // d betas: columns 486.. of dPF

@@ -532,9 +532,8 @@ int fdcap_debug_nn_records(fdcap_ctx* ctx, float* rec4_d, void* stream);
  * out4[2]: search launches under a query order; out4[3]: rebuilds of the query order. */
 int fdcap_debug_contact_diet(fdcap_ctx* ctx, int32_t* out4);
 /* Tests / diagnosis: one-wave search launches since fdcap_opt_create[_clips] by the lanes per listed box they were launched with
- * (FDCAP_NN_BOX_LANES): out5[0] by each stage's count, out5[1] / [2] / [3] forced 2 / 4 / 8; out5[4]: launches whose waves on a kept
- * list copy its boxes into LDS with their set-up loads (FDCAP_NN_BOX_PREFETCH on, kept lists and a query order in use). */
-int fdcap_debug_nn_box_tests(fdcap_ctx* ctx, int32_t* out5);
+ * (FDCAP_NN_BOX_LANES): out4[0] by each stage's count, out4[1] / [2] / [3] forced 2 / 4 / 8. */
+int fdcap_debug_nn_box_tests(fdcap_ctx* ctx, int32_t* out4);
 /* Tests / diagnosis: perm_h [n = contacts]: internal contact slot -> position in the caller's id array (fdcap_set_contact_ids);
  * a frame's queries lie in idx / seedpt in slot order.  Synchronous copy. */
 int fdcap_debug_contact_perm(fdcap_ctx* ctx, int32_t* perm_h, int32_t n);

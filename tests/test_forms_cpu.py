@@ -18,7 +18,8 @@ EXE = os.path.join(BUILD, "forms_sweep")
 TABLE = os.path.join(ROOT, "tests", "forms_table.json")
 
 SWITCHES = ["FDCAP_CLIP_FORMS_MIN_ROWS", "FDCAP_PN_RB2", "FDCAP_PN_NW", "FDCAP_PN_KSW", "FDCAP_GEMM_SPLIT3", "FDCAP_NN_STREAM", "FDCAP_NN_SEED",
-            "FDCAP_NN_CULL", "FDCAP_NN_ORDER", "FDCAP_NN_CACHE_SLACK", "FDCAP_SKIN_VEC", "FDCAP_FUSE_SKIN"]
+            "FDCAP_NN_CULL", "FDCAP_NN_ORDER", "FDCAP_NN_CACHE_SLACK", "FDCAP_SKIN_VEC", "FDCAP_FUSE_SKIN", "FDCAP_POSE_TRIM",
+            "FDCAP_NN_KEEP_RECORDS", "FDCAP_CONTACT_RECOMPUTE", "FDCAP_NN_BOX_LANES"]
 
 
 @pytest.fixture(scope="module")
@@ -165,7 +166,8 @@ def test_the_switches_are_read_in_one_place_and_documented():
     process, create = "once per process", "every `fdcap_opt_create[_clips]`"
     when = {"FDCAP_CLIP_FORMS_MIN_ROWS": process, "FDCAP_PN_RB2": process, "FDCAP_PN_NW": process, "FDCAP_PN_KSW": process, "FDCAP_NN_STREAM": process,
             "FDCAP_GEMM_SPLIT3": process + " (`fdcap_panel_gemm`: every call)", "FDCAP_NN_SEED": create, "FDCAP_NN_CULL": create,
-            "FDCAP_SKIN_VEC": create, "FDCAP_FUSE_SKIN": create, "FDCAP_NN_ORDER": create,
+            "FDCAP_SKIN_VEC": create, "FDCAP_FUSE_SKIN": create, "FDCAP_NN_ORDER": create, "FDCAP_POSE_TRIM": create,
+            "FDCAP_NN_KEEP_RECORDS": create, "FDCAP_CONTACT_RECOMPUTE": create, "FDCAP_NN_BOX_LANES": create,
             "FDCAP_NN_CACHE_SLACK": create + " (`fdcap_chamfer_fwd_scene`: once per process)"}
     for name in SWITCHES:
         mine = [l.split(" | ") for l in rows if f"`{name}" in l.split(" | ")[0]]

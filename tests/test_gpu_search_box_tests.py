@@ -1,7 +1,7 @@
 """How the in-loop Chamfer search runs its per-query box tests is scheduling only (fdc_chamfer.h nn_box_stage): 2, 4 or 8 lanes per
 listed box (FDCAP_NN_BOX_LANES; 0 = by each stage's count) keep the same entries in the same order, so the search visits the same
 quarters and every neighbour, distance and optimiser row has the same bits as with a pair of lanes per box everywhere (= 2, every
-launch before the switch existed).  FDCAP_NN_BOX_PREFETCH is set next to it in every run (0 with the reference).
+launch before the switch existed).  A setting is that width; the reference is 2.
 
 Shapes as in tests/test_gpu_query_order.py: 255 frames x 500 contacts = 127 500 queries (one-wave workgroups, a ragged last wave)
 against 100 000 scene points, 32 phase-1 + 8 phase-2 iterations.  A forced width holds at every count (tests/test_box_lanes_cpu.py),
@@ -11,13 +11,12 @@ multi-pass compaction run.  Further cases: a 2 000-point scene (four chunks, one
 translation shifted by 3 cm between two iterations (the kept lists are void at the next launch and the waves build again), and one
 frame whose queries are NaN.
 
-The 128- and 160-frame cases (four / two waves per group) check less: those forms keep the pair form and fetch their boxes in the
-filter whatever the switches say, so their three settings run the same code -- the cases pin that the shared helper serves those
-forms and that the switches do not reach them.
+The 128- and 160-frame cases (four / two waves per group) check less: those forms keep the pair form whatever the switch says, so
+their three settings run the same code -- the cases pin that the shared helper serves those forms and that the switch does not
+reach them.
 
 Every run asserts the form the search took, and through fdcap_debug_nn_box_tests that its one-wave launches were given the setting
-under test (lanes per box; boxes copied with the set-up in every launch under a query order): a setting that never reached the
-kernel's argument would make the comparison empty.  What a stage does with the argument is nn_box_lanes, pinned on the CPU.
+under test (lanes per box): a setting that never reached the kernel's argument would make the comparison empty.  What a stage does with the argument is nn_box_lanes, pinned on the CPU.
 """
 import ctypes
 
@@ -34,7 +33,7 @@ pytestmark = pytest.mark.gpu
 
 V, PER_PART = 10475, 250
 P, ITERS = 32, 40                                           # phase-1 iterations (the search runs there), iterations in all
-REFERENCE = (2, 0)
+REFERENCE = 2
 W1, W2, W4 = "nn_stream4_kernel<1,1,1>", "nn_stream4_kernel(2 waves per group)", "nn_stream4_kernel(4 waves per group)"
 
 
@@ -49,8 +48,7 @@ def assets():
 def _fit(assets, monkeypatch, setting, n=255, ns=100_000, form=W1, shift_at=None, nan_frame=None):
     """the last search's distances and neighbours + the optimiser's rows, scale and cameras after a short fit under one setting"""
     bm, vp, scenes, vid = assets
-    monkeypatch.setenv("FDCAP_NN_BOX_LANES", str(setting[0]))          # (read by every fdcap_opt_create)
-    monkeypatch.setenv("FDCAP_NN_BOX_PREFETCH", str(setting[1]))
+    monkeypatch.setenv("FDCAP_NN_BOX_LANES", str(setting))             # (read by every fdcap_opt_create)
     clip = synth.make_clip(n, seed=3)
     params = np.array(clip.body_params, copy=True)
     if nan_frame is not None: params[nan_frame, 0:3] = np.nan
@@ -77,17 +75,16 @@ def _fit(assets, monkeypatch, setting, n=255, ns=100_000, form=W1, shift_at=None
     out = [d.cpu(), i.cpu(), fop._rows_x.cpu(), fop._scale.cpu(), fop._rows_cam.cpu()]
     capi.check(lib.fdcap_debug_kernel_forms(forms, len(forms), 0), "kernel_forms")
     assert form in forms.value.decode(), forms.value.decode()
-    box = (ctypes.c_int32 * 5)()
+    box = (ctypes.c_int32 * 4)()
     diet = (ctypes.c_int32 * 4)()
     capi.check(lib.fdcap_debug_nn_box_tests(h, box), "nn_box_tests")
     capi.check(lib.fdcap_debug_contact_diet(h, diet), "contact_diet")
-    box, slot = list(box), {0: 0, 2: 1, 4: 2, 8: 3}[setting[0]]
+    box, slot = list(box), {0: 0, 2: 1, 4: 2, 8: 3}[setting]
     if form == W1:
-        assert box[slot] >= P and sum(box[:4]) == box[slot], box           # every one-wave launch under the width asked for
+        assert box[slot] >= P and sum(box) == box[slot], box               # every one-wave launch under the width asked for
         assert diet[2] >= P - 2, list(diet)                                 # ... nearly all of them under a query order
-        assert box[4] == (diet[2] if setting[1] else 0), (box, list(diet))  # ... and those copy their boxes iff the switch is on
     else:
-        assert box == [0, 0, 0, 0, 0], box                                  # no one-wave launch: nothing the switches reach
+        assert box == [0, 0, 0, 0], box                                     # no one-wave launch: nothing the switch reaches
     fop.close()
     return out
 
@@ -110,7 +107,8 @@ def _reference(assets, monkeypatch, **case):
     return _references[key]
 
 
-@pytest.mark.parametrize("setting", [(0, 1), (4, 1), (8, 1), (8, 0), (4, 0)])
+# (the ids are the ones these cases had while a setting was a pair: a case keeps its name)
+@pytest.mark.parametrize("setting", [0, 4, 8], ids=["setting0", "setting1", "setting2"])
 def test_every_width_gives_the_fit_of_a_pair_per_box(assets, monkeypatch, setting):
     want = _reference(assets, monkeypatch)
     assert int(want[1].min()) >= 0 and bool(torch.isfinite(want[0]).all())
@@ -126,7 +124,7 @@ CASES = {
 }
 
 
-@pytest.mark.parametrize("setting", [(0, 1), (8, 1)])
+@pytest.mark.parametrize("setting", [0, 8], ids=["setting0", "setting1"])
 @pytest.mark.parametrize("case", list(CASES))
 def test_other_lists_and_forms(assets, monkeypatch, case, setting):
     want = _reference(assets, monkeypatch, **CASES[case])
