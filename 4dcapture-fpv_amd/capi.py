@@ -68,6 +68,8 @@ SYMBOLS = {
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_chamfer_bwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
+    "fdcap_chamfer_bwd_both": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "fdcap_chamfer_fwd_scene": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "fdcap_chamfer_bwd_scene": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_set_nn_kernel": (c_int32, [c_int32]),

@@ -245,6 +245,7 @@ void fdcap_ctx_destroy(fdcap_ctx* c) {
     c->ws_part.release();
     for (auto& b : c->ws_i) b.release();
     c->ws_p.release();
+    c->ws_ck.release(); c->ws_cv.release();
     delete c;
 }
 
@@ -368,7 +369,14 @@ int fdcap_chamfer_fwd(fdcap_ctx* c, const float* xyz1, const float* xyz2, int32_
     hipStream_t st = (hipStream_t)stream;
     const bool shared = (stride2 == 0);
     size_t big = (size_t)std::max(n, m);
-    HIP_TRY(c->ws_p.ensure(shared ? (size_t)m + (dist2 ? big : 0) : big));
+    // Per-batch targets and the reverse direction: one launch set for all batches (nn_search_batched), or -- FDCAP_CHAMFER_BATCHED=0,
+    // read on every call -- the per-batch loop at the end, which is the specification: the batched path returns its bits.
+    const char* const sw = getenv("FDCAP_CHAMFER_BATCHED");
+    const bool batched = !(sw && sw[0] == '0') && (!shared || dist2);
+    // packed targets: the loop keeps the shared scene [m] and one batch's set behind it; the batched path packs all B sets of one
+    // direction at the front (the launches that read the buffer are ordered on the stream, so the directions take turns)
+    if (batched) HIP_TRY(c->ws_p.ensure(std::max(shared ? (size_t)m : dist1 ? (size_t)B * m : 0, dist2 ? (size_t)B * n : 0)));
+    else HIP_TRY(c->ws_p.ensure(shared ? (size_t)m + (dist2 ? big : 0) : big));
     if (shared && dist1) {
         hipLaunchKernelGGL(pack_points_kernel, dim3((m + 255) / 256), dim3(256), 0, st, xyz2, m, c->ws_p.p);
         int nq = B * n;
@@ -376,6 +384,22 @@ int fdcap_chamfer_fwd(fdcap_ctx* c, const float* xyz1, const float* xyz2, int32_
         HIP_TRY(c->ws_f[0].ensure((size_t)nsplit * nq));
         HIP_TRY(c->ws_i[0].ensure((size_t)nsplit * nq));
         { NNTarget T{c->ws_p.p, m, nullptr, nullptr, nullptr, nullptr, nullptr}; HIP_TRY(nn_search(xyz1, nq, T, dist1, idx1, c->ws_f[0].p, c->ws_i[0].p, nsplit, st)); }
+    }
+    if (batched) {
+        const int mode = nn_mode_ref();
+        if (!shared && dist1) {                                  // x1[b] -> x2[b]
+            const NNBatchPlan pl = plan_nn_batched(n, m, B, mode);
+            HIP_TRY(c->ws_f[0].ensure((size_t)B * pl.nsplit * n));
+            HIP_TRY(c->ws_i[0].ensure((size_t)B * pl.nsplit * n));
+            HIP_TRY(nn_search_batched(pl, xyz1, (long long)n * 3, n, xyz2, stride2, m, B, c->ws_p.p, dist1, idx1, c->ws_f[0].p, c->ws_i[0].p, st));
+        }
+        if (dist2) {                                             // x2[b] (or the one shared x2) -> x1[b]
+            const NNBatchPlan pl = plan_nn_batched(m, n, B, mode);
+            HIP_TRY(c->ws_f[1].ensure((size_t)B * pl.nsplit * m));
+            HIP_TRY(c->ws_i[1].ensure((size_t)B * pl.nsplit * m));
+            HIP_TRY(nn_search_batched(pl, xyz2, stride2, m, xyz1, (long long)n * 3, n, B, c->ws_p.p, dist2, idx2, c->ws_f[1].p, c->ws_i[1].p, st));
+        }
+        return (int)hipGetLastError();
     }
     for (int b = 0; b < B && (!shared || dist2); ++b) {
         const float* x1 = xyz1 + (size_t)b * n * 3;
@@ -414,6 +438,53 @@ int fdcap_chamfer_bwd(fdcap_ctx* c, const float* xyz1, const float* xyz2, int32_
             hipLaunchKernelGGL(nn_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, st, xyz1 + (size_t)b * n * 3, c->ws_p.p,
                                gdist1 + (size_t)b * n, idx1 + (size_t)b * n, n, gxyz1 + (size_t)b * n * 3);
         }
+    }
+    return (int)hipGetLastError();
+}
+
+// The whole backward of Op 1 in a defined order (fdc_chamfer_bwd.h): both halves, both inputs, no atomics, O(1) launches in B.
+// Workspace (context-owned, grown on demand): ws_ck / ws_cv, the sort scratch of the larger of the two sides.
+int fdcap_chamfer_bwd_both(fdcap_ctx* c, const float* xyz1, const float* xyz2, int32_t B, int32_t n, int32_t m, int64_t stride2,
+                           const float* gdist1, const int32_t* idx1, const float* gdist2, const int32_t* idx2, float* gxyz1,
+                           float* gxyz2, int32_t reduce2, void* stream) {
+    if (!c || !xyz1 || !xyz2 || B <= 0 || n <= 0 || m <= 0) return FDCAP_E_ARG;
+    if ((gdist1 != nullptr) != (idx1 != nullptr) || (gdist2 != nullptr) != (idx2 != nullptr)) return FDCAP_E_ARG;
+    if ((!gdist1 && !gdist2) || (!gxyz1 && !gxyz2)) return FDCAP_E_ARG;
+    if (reduce2 != 0 && stride2 != 0) return FDCAP_E_ARG;
+    const long long N1 = (long long)B * n, N2 = (long long)B * m;
+    if (N1 > 0x7fffffffLL || N2 > 0x7fffffffLL) return FDCAP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    // side 1's terms are grouped by target for gxyz2, side 2's by query for gxyz1
+    const bool sort1 = gxyz2 && gdist1, sort2 = gxyz1 && gdist2;
+    const long long ns = std::max(sort1 ? N1 : 0, sort2 ? N2 : 0);
+    if (ns > CB_MAX_SORT) return FDCAP_E_ARG;                  // (the sort's tiles index with int)
+    if (ns > 0) {
+        HIP_TRY(c->ws_ck.ensure(cb_key_words(ns)));
+        HIP_TRY(c->ws_cv.ensure(2 * (size_t)ns));
+    }
+    const long long s1 = (long long)n * 3;
+    if (gxyz2) {
+        const CbSide side{xyz2, (long long)stride2, xyz1, s1, B, m, n, gdist2, idx2, gdist1, reduce2 != 0 ? 1 : 0};
+        const long long nd = reduce2 ? (long long)m : N2;
+        const unsigned* skey = nullptr;
+        const int* sval = nullptr;
+        if (sort1) {
+            int buf = 0;
+            HIP_TRY(cb_group(idx1, B, n, m, reduce2 == 0, c->ws_ck.p, c->ws_cv.p, c->ws_ck.p + 2 * (size_t)N1, st, &buf));
+            skey = c->ws_ck.p + (size_t)buf * N1; sval = c->ws_cv.p + (size_t)buf * N1;
+        }
+        hipLaunchKernelGGL(cb_gather_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, side, skey, sval, (int)N1, gxyz2);
+    }
+    if (gxyz1) {
+        const CbSide side{xyz1, s1, xyz2, (long long)stride2, B, n, m, gdist1, idx1, gdist2, 0};
+        const unsigned* skey = nullptr;
+        const int* sval = nullptr;
+        if (sort2) {                                           // (the scratch is reused: the launches are ordered on the stream)
+            int buf = 0;
+            HIP_TRY(cb_group(idx2, B, m, n, true, c->ws_ck.p, c->ws_cv.p, c->ws_ck.p + 2 * (size_t)N2, st, &buf));
+            skey = c->ws_ck.p + (size_t)buf * N2; sval = c->ws_cv.p + (size_t)buf * N2;
+        }
+        hipLaunchKernelGGL(cb_gather_kernel, dim3((unsigned)((N1 + 255) / 256)), dim3(256), 0, st, side, skey, sval, (int)N2, gxyz1);
     }
     return (int)hipGetLastError();
 }

@@ -54,13 +54,29 @@ __device__ __forceinline__ void nn_block_map(int b, int nsplit, int* qb, int* sp
     *qb = (slot / nsplit) * 8 + xcd;
 }
 
-template <int QPT>
+// BATCHED (both scan kernels): blockIdx.y is one of many independent searches of nq queries against T.n targets.  Batch b reads its
+// queries at q + b * qstride floats and its targets at T.pts + b * tstride points (either stride may be 0: one set shared by all
+// batches), and writes its partial minima behind those of the batches before it, [batch][split][query].  All of it is
+// workgroup-uniform: scalar registers only.  grid.x = query blocks x splits exactly (nn_batch_map).
+__device__ __forceinline__ void nn_batch_map(int b, int nsplit, int* qb, int* split) {
+    *split = b % nsplit;
+    *qb = b / nsplit;
+}
+
+template <int QPT, bool BATCHED = false>
 __global__ __launch_bounds__(256) void nn_direct_kernel(const float* __restrict__ q, int nq, NNTarget T, int nsplit,
-                                                        float* __restrict__ pd, int* __restrict__ pi) {
+                                                        float* __restrict__ pd, int* __restrict__ pi, long long qstride, long long tstride) {
     __shared__ float4 tile[NN_TILE];
     const int tid = threadIdx.x;
     int split, qb;
-    nn_block_map(blockIdx.x, nsplit, &qb, &split);
+    if constexpr (BATCHED) {
+        const size_t bb = blockIdx.y;
+        q += bb * qstride; T.pts += bb * tstride;
+        pd += bb * nsplit * nq; pi += bb * nsplit * nq;
+        nn_batch_map(blockIdx.x, nsplit, &qb, &split);
+    } else {
+        nn_block_map(blockIdx.x, nsplit, &qb, &split);
+    }
     if (qb * (256 * QPT) >= nq) return;
     const int per = nn_split_len(T.n, nsplit);
     const int t_begin = min(T.n, split * per);
@@ -184,10 +200,10 @@ __device__ __forceinline__ float box_d2(float4 lo, float4 hi, float x, float y, 
     return dx * dx + dy * dy + dz * dz;
 }
 
-template <int NQ>
+template <int NQ, bool BATCHED = false>
 __global__ __launch_bounds__(256) void nn_mfma_kernel(const float* __restrict__ q, int nq, NNTarget T, int nsplit,
                                                       const int* __restrict__ seed, float* __restrict__ pd,
-                                                      int* __restrict__ pi) {
+                                                      int* __restrict__ pi, long long qstride, long long tstride) {
     __shared__ uint4 sA[2][MF_CH / 32][2][32];     // [buffer][tile][k-half][point] bf16 x 8
     __shared__ float4 sP[2][MF_CH];                // fp32 coordinates (+ index) for the exact re-evaluation
     __shared__ float sred[4][4];
@@ -195,7 +211,14 @@ __global__ __launch_bounds__(256) void nn_mfma_kernel(const float* __restrict__ 
     __shared__ int swcnt[4];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, col = lane & 31;
     int split, qb;
-    nn_block_map(blockIdx.x, nsplit, &qb, &split);
+    if constexpr (BATCHED) {                               // (nn_direct_kernel: the batch's pointers, all scalar)
+        const size_t bb = blockIdx.y;
+        q += bb * qstride; T.pts += bb * tstride;
+        pd += bb * nsplit * nq; pi += bb * nsplit * nq;
+        nn_batch_map(blockIdx.x, nsplit, &qb, &split);
+    } else {
+        nn_block_map(blockIdx.x, nsplit, &qb, &split);
+    }
     if (qb * (128 * NQ) >= nq) return;
     const int per = nn_split_len(T.n, nsplit);
     const int t_begin = min(T.n, split * per);
@@ -1271,8 +1294,33 @@ __global__ void pack_points_kernel(const float* __restrict__ xyz, int n, float4*
     out[i] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __int_as_float(i));
 }
 
-// d dist / d query: NmDistanceGradKernel restricted to the query side (the scene has no grad);
-// tgt is indexed by original index
+// the same for B point sets (blockIdx.y; batch stride `stride` floats), each point tagged with its index WITHIN its set
+__global__ void pack_points_batched_kernel(const float* __restrict__ xyz, long long stride, int n, float4* __restrict__ out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* const p = xyz + (size_t)blockIdx.y * stride + 3 * (size_t)i;
+    out[(size_t)blockIdx.y * n + i] = make_float4(p[0], p[1], p[2], __int_as_float(i));
+}
+// nn_combine_kernel over partial minima [batch][split][query] (blockIdx.y: batch) -> dist / idx [batch][query]
+__global__ void nn_combine_batched_kernel(const float* __restrict__ pd, const int* __restrict__ pi, int nsplit, int nq,
+                                          float* __restrict__ dist, int* __restrict__ idx) {
+    int qi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qi >= nq) return;
+    const size_t bb = blockIdx.y;
+    pd += bb * nsplit * nq; pi += bb * nsplit * nq;
+    float best = INFINITY;
+    int bi = -1;
+    for (int s = 0; s < nsplit; ++s) {
+        float d = pd[(size_t)s * nq + qi];
+        int j = pi[(size_t)s * nq + qi];
+        if (j >= 0 && (bi < 0 || nn_better(d, j, best, bi))) { best = d; bi = j; }
+    }
+    dist[bb * nq + qi] = best;
+    idx[bb * nq + qi] = bi;
+}
+
+// d dist / d query: NmDistanceGradKernel restricted to the query side (a loop that does not differentiate through its target;
+// the target's gradient and the dist2 half: fdc_chamfer_bwd.h); tgt is indexed by original index
 __global__ void nn_grad_kernel(const float* __restrict__ q, const float4* __restrict__ tgt, const float* __restrict__ g,
                                const int* __restrict__ idx, int nq, float* __restrict__ gq) {
     int qi = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1399,10 +1447,36 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
         }
         return hipGetLastError();
     }
-    if (pl.form == F_NN_MFMA && pl.nq_blocks == 2) hipLaunchKernelGGL((nn_mfma_kernel<2>), grid, block, 0, st, q, nq, T, nsplit, seed, pd, pi);
-    else if (pl.form == F_NN_MFMA) hipLaunchKernelGGL((nn_mfma_kernel<4>), grid, block, 0, st, q, nq, T, nsplit, seed, pd, pi);
-    else hipLaunchKernelGGL((nn_direct_kernel<2>), grid, block, 0, st, q, nq, T, nsplit, pd, pi);
+    if (pl.form == F_NN_MFMA && pl.nq_blocks == 2) hipLaunchKernelGGL((nn_mfma_kernel<2>), grid, block, 0, st, q, nq, T, nsplit, seed, pd, pi, 0LL, 0LL);
+    else if (pl.form == F_NN_MFMA) hipLaunchKernelGGL((nn_mfma_kernel<4>), grid, block, 0, st, q, nq, T, nsplit, seed, pd, pi, 0LL, 0LL);
+    else hipLaunchKernelGGL((nn_direct_kernel<2>), grid, block, 0, st, q, nq, T, nsplit, pd, pi, 0LL, 0LL);
     hipLaunchKernelGGL(nn_combine_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, pd, pi, nsplit, nq, dist, idx);
+    return hipGetLastError();
+}
+
+// The every-pair search of B independent batches in one launch set (plan_nn_batched, fdc_forms.h): pack the B target sets (tgt
+// [B][nt], batch stride ts floats; 0: one set for all, packed once), scan, combine.  q [B][nq] with batch stride qs floats (0: one
+// query set for all batches).  pk: [B * nt] (ts == 0: [nt]); pd / pi: [B * nsplit * nq]; dist / idx [B][nq].  Every batch gets
+// what nn_search gives it alone, bit for bit.
+static inline hipError_t nn_search_batched(const NNBatchPlan& pl, const float* q, long long qs, int nq, const float* tgt, long long ts, int nt,
+                                           int B, float4* pk, float* dist, int* idx, float* pd, int* pi, hipStream_t st) {
+    note_form(pl.name);
+    const long long pks = ts == 0 ? 0 : nt;                  // batch stride of the packed targets, in points
+    for (int b0 = 0; b0 < B; b0 += NN_MAX_GRID_Y) {
+        const int nb = std::min(B - b0, NN_MAX_GRID_Y);
+        const float* const qb = q + (size_t)b0 * qs;
+        float4* const pkb = pk + (size_t)b0 * pks;
+        float* const pdb = pd + (size_t)b0 * pl.nsplit * nq;
+        int* const pib = pi + (size_t)b0 * pl.nsplit * nq;
+        if (ts != 0 || b0 == 0)
+            hipLaunchKernelGGL(pack_points_batched_kernel, dim3((nt + 255) / 256, ts == 0 ? 1 : nb), dim3(256), 0, st, tgt + (size_t)b0 * ts, ts, nt, pkb);
+        const NNTarget T{pkb, nt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const dim3 grid(pl.grid_x, nb), block(pl.block);
+        if (pl.mfma) hipLaunchKernelGGL((nn_mfma_kernel<4, true>), grid, block, 0, st, qb, nq, T, pl.nsplit, (const int*)nullptr, pdb, pib, qs, pks);
+        else hipLaunchKernelGGL((nn_direct_kernel<2, true>), grid, block, 0, st, qb, nq, T, pl.nsplit, pdb, pib, qs, pks);
+        hipLaunchKernelGGL(nn_combine_batched_kernel, dim3((nq + 255) / 256, nb), dim3(256), 0, st, pdb, pib, pl.nsplit, nq,
+                           dist + (size_t)b0 * nq, idx + (size_t)b0 * nq);
+    }
     return hipGetLastError();
 }
 

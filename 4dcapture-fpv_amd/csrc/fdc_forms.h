@@ -416,6 +416,31 @@ inline NNPlan plan_nn_search(int nq, int nt, bool culled, bool frags, bool seed_
     return p;
 }
 
+// The every-pair search with a batch axis (fdcap_chamfer_fwd: per-batch targets, the reverse direction): B independent searches of
+// nq queries against nt targets in one launch set, the batch on blockIdx.y in chunks of at most NN_MAX_GRID_Y.  The kernel is the
+// one a single batch's sizes select (nn_use_mfma(nq, nt)), so a batch is scanned by the kernel the per-batch loop gives it; both
+// kernels serve 512 queries per workgroup (nn_direct_kernel<2>, nn_mfma_kernel<4>).  grid_x = query blocks x splits, no padding to
+// the XCD count (the batch axis supplies the workgroups).  nsplit: as nn_pick_nsplit for the B * qblocks query blocks the launch
+// has -- results do not depend on it ((d, index) merge).  Partial minima: [batch][split][query].
+constexpr int NN_MAX_GRID_Y = 65535;
+struct NNBatchPlan {
+    bool mfma = false;
+    const char* name = "nn_direct_batched";       // what fdcap_debug_kernel_forms reports
+    int nsplit = 1, qblocks = 1, grid_x = 1, block = 256;
+    int launches = 1;                              // ceil(B / NN_MAX_GRID_Y)
+};
+inline NNBatchPlan plan_nn_batched(int nq, int nt, int B, int mode) {
+    NNBatchPlan p;
+    p.mfma = nn_use_mfma(nq, nt, mode);
+    p.name = p.mfma ? "nn_mfma_batched" : "nn_direct_batched";
+    p.qblocks = (int)(((long long)nq + 511) / 512);
+    const long long flat = std::min<long long>((long long)p.qblocks * 512 * B, 1LL << 30);
+    p.nsplit = nn_pick_nsplit((int)flat, nt);
+    p.grid_x = p.qblocks * p.nsplit;
+    p.launches = (B + NN_MAX_GRID_Y - 1) / NN_MAX_GRID_Y;
+    return p;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Pose kernels (fdc_frame.h, fdc_k_pose.h): the joints one launch's loss can reach.  The loss meets the kinematic chain through the
 // skinning transforms A of the joints the contact set is skinned to (rows below SkinModel::ja_hi) and through the world positions of

@@ -261,7 +261,9 @@ struct fdcap_ctx {
     DevBuf<float> ws_part;          // partial decoder outputs of the stand-alone operators
     DevBuf<int> ws_i[2];
     DevBuf<float4> ws_p;
-    DevBuf<float> ws_skin;          // chunk partials of the split skinning backward (skin_bwd_any)
+    DevBuf<unsigned> ws_ck;         // fdcap_chamfer_bwd_both: sort keys [2][N] + tile histogram + digit totals (fdc_chamfer_bwd.h cb_key_words)
+    DevBuf<int> ws_cv;              // ... and the positions that travel with them [2][N]; N = max(B n, B m) of the largest call so far
+    DevBuf<float> ws_skin;         // chunk partials of the split skinning backward (skin_bwd_any)
     DevBuf<float> ws_kpart;         // K-part partial products of the full-mesh data gradient (blend_backward)
     // Op 1 against the registered scene (fdcap_chamfer_fwd_scene): the previous call's neighbours = the next call's seeds
     struct SceneOp {

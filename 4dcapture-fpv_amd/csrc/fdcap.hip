@@ -31,6 +31,7 @@ __device__ unsigned long long g_fr_times[3][2048 * 8];
 #endif
 #include "../../include/fdcap.h"
 #include "fdc_chamfer.h"
+#include "fdc_chamfer_bwd.h"
 #include "fdc_comm.h"
 #include "fdc_dct.h"
 #include "fdc_fit2d.h"

@@ -72,6 +72,7 @@ class _ChamferFn(torch.autograd.Function):
                                                   None if scene else capi.dptr(d1), None if scene else capi.dptr(i1),
                                                   capi.dptr(d2), capi.dptr(i2), capi.current_stream()), "fdcap_chamfer_fwd")
         ctx.fctx, ctx.shared, ctx.both, ctx.scene = fctx, shared, both, scene
+        ctx.reduce2 = xyz2.shape[0] == 1              # a [1,m,3] target gets a [1,m,3] gradient; an expand()ed view [B,m,3]
         ctx.save_for_backward(x1, x2, i1, i2 if both else i1)
         ctx.mark_non_differentiable(i1)
         if both:
@@ -84,34 +85,41 @@ class _ChamferFn(torch.autograd.Function):
         B, n, _ = x1.shape
         m = x2.shape[-2]
         fctx = ctx.fctx
+        g1 = g1.contiguous()
+        need2 = ctx.needs_input_grad[1]
+        if ctx.both or need2:
+            # the whole backward -- the target's gradient, the dist2 half -- by the library, in a defined order (reproducible bits)
+            gx1 = torch.empty_like(x1) if ctx.needs_input_grad[0] else None
+            gx2 = None
+            if need2:
+                gx2 = torch.empty((1, m, 3) if ctx.reduce2 else (B, m, 3), device=x1.device)
+            g2 = g2.contiguous() if ctx.both else None
+            capi.check(fctx.lib.fdcap_chamfer_bwd_both(fctx.handle, capi.dptr(x1), capi.dptr(x2), B, n, m, 0 if ctx.shared else m * 3,
+                                                       capi.dptr(g1), capi.dptr(i1), capi.dptr(g2), capi.dptr(i2) if ctx.both else None,
+                                                       capi.dptr(gx1), capi.dptr(gx2), 1 if (need2 and ctx.reduce2) else 0,
+                                                       capi.current_stream()), "fdcap_chamfer_bwd_both")
+            return gx1, gx2, None, None, None
         gx1 = torch.empty_like(x1)
         if ctx.scene:
-            capi.check(fctx.lib.fdcap_chamfer_bwd_scene(fctx.handle, capi.dptr(x1), B, n, capi.dptr(g1.contiguous()), capi.dptr(i1),
+            capi.check(fctx.lib.fdcap_chamfer_bwd_scene(fctx.handle, capi.dptr(x1), B, n, capi.dptr(g1), capi.dptr(i1),
                                                         capi.dptr(gx1), capi.current_stream()), "fdcap_chamfer_bwd_scene")
         else:
             capi.check(fctx.lib.fdcap_chamfer_bwd(fctx.handle, capi.dptr(x1), capi.dptr(x2), B, n, m,
-                                                  0 if ctx.shared else m * 3, capi.dptr(g1.contiguous()),
+                                                  0 if ctx.shared else m * 3, capi.dptr(g1),
                                                   capi.dptr(i1), capi.dptr(gx1), capi.current_stream()),
                        "fdcap_chamfer_bwd")
-        gx2 = None
-        if ctx.needs_input_grad[1] or ctx.both:
-            # cold compatibility path (the reference never differentiates through the scene):
-            # scatter terms done with torch index ops
-            x2b = x2.unsqueeze(0).expand(B, -1, -1) if ctx.shared else x2
-            gx2 = torch.zeros(B, m, 3, device=x1.device)
-            gx2.scatter_add_(1, i1.long().unsqueeze(-1).expand(-1, -1, 3), -gx1)
-            if ctx.both:
-                nb = torch.gather(x1, 1, i2.long().unsqueeze(-1).expand(-1, -1, 3))
-                u = 2.0 * g2.unsqueeze(-1) * (x2b - nb)
-                gx2 = gx2 + u
-                gx1 = gx1.scatter_add(1, i2.long().unsqueeze(-1).expand(-1, -1, 3), -u)
-        return gx1, gx2, None, None, None
+        return gx1, None, None, None, None
 
 
 class chamferDist(torch.nn.Module):
     """`chamferDist(ctx)()`-style module: forward(xyz1[B,n,3], xyz2[B,m,3]) -> (dist1, dist2),
     squared distances.  `both=False` skips the scene->body half the reference discards (dist2 is
-    returned as zeros).  xyz2 may be an expand()ed [1,m,3] scene: it is then read once."""
+    returned as zeros).  xyz2 may be an expand()ed [1,m,3] scene: it is then read once.
+
+    Differentiable with respect to BOTH inputs through both halves, by kernels of the library alone (fdcap_chamfer_bwd_both: terms
+    summed in a defined order, so two backward passes give the same bits).  A target passed as [1,m,3] gets its gradient as
+    [1,m,3], summed over the batch inside the kernel; an expand()ed view gets [B,m,3], the shape autograd asks for.  A loop that
+    needs only the query-side gradient of dist1 (`both=False`, target without grad) stays on fdcap_chamfer_bwd[_scene]."""
 
     def __init__(self, ctx, both: bool = True, use_registered_scene: bool = True):
         """use_registered_scene: when xyz2 is one shared point set that equals the scene registered on the context

@@ -125,7 +125,9 @@ int fdcap_set_contact_ids(fdcap_ctx* ctx, const int64_t* vid, int32_t nc);
 /* xyz1_d [B,n,3] queries, xyz2_d [B,m,3] targets with batch stride `stride2` elements
  * (0 = one scene shared by all batches).  Writes dist1_d [B,n] (squared L2 to the nearest
  * target, direct-difference form) and idx1_d [B,n] (lowest index among ties).  If dist2_d is
- * non-null also the reverse direction dist2_d [B,m], idx2_d [B,m] (the reference discards it). */
+ * non-null also the reverse direction dist2_d [B,m], idx2_d [B,m] (the reference discards it).
+ * Per-batch targets and the reverse direction run as one launch set over all batches (the batch on the grid's y axis);
+ * FDCAP_CHAMFER_BATCHED=0, read on every call, runs them batch by batch instead -- the same bits. */
 int fdcap_chamfer_fwd(fdcap_ctx* ctx, const float* xyz1_d, const float* xyz2_d, int32_t B,
                       int32_t n, int32_t m, int64_t stride2, float* dist1_d, int32_t* idx1_d,
                       float* dist2_d, int32_t* idx2_d, void* stream);
@@ -140,10 +142,28 @@ int fdcap_chamfer_fwd_scene(fdcap_ctx* ctx, const float* xyz1_d, int32_t B, int3
                             void* stream);
 int fdcap_chamfer_bwd_scene(fdcap_ctx* ctx, const float* xyz1_d, int32_t B, int32_t n, const float* gdist1_d, const int32_t* idx1_d,
                             float* gxyz1_d, void* stream);
-/* grad wrt the queries only (the scene needs none): gxyz1_d[b,i] = 2 g1[b,i] (x1[b,i]-x2[b,idx]) */
+/* The dist1 half's gradient wrt the queries alone, the hot path of a loop that does not differentiate through its target:
+ * gxyz1_d[b,i] = 2 g1[b,i] (x1[b,i]-x2[b,idx]).  The target's gradient and the dist2 half: fdcap_chamfer_bwd_both. */
 int fdcap_chamfer_bwd(fdcap_ctx* ctx, const float* xyz1_d, const float* xyz2_d, int32_t B,
                       int32_t n, int32_t m, int64_t stride2, const float* gdist1_d,
                       const int32_t* idx1_d, float* gxyz1_d, void* stream);
+/* The whole backward: both halves, both inputs, computed by the library in a defined order (no float atomics: the same bits in
+ * every run, whatever the launch geometry; O(1) launches in B).  Every operation is fp32 and rounded on its own:
+ *   a[b,i,k] = (2 g1[b,i]) (x1[b,i,k] - x2[b,j,k]), j = idx1[b,i]          (+0 without the dist1 term)
+ *   u[b,j,k] = (2 g2[b,j]) (x2[b,j,k] - x1[b,i,k]), i = idx2[b,j]          (+0 without the dist2 term)
+ *   gxyz1[b,i,k] = a[b,i,k] - S1,  S1 = +0, then + u[b,j,k] for every j with idx2[b,j] == i, ascending j
+ *   gxyz2[b,j,k] = u[b,j,k] - S2,  S2 = +0, then + a[b,i,k] for every i with idx1[b,i] == j, ascending i
+ *   reduce2 != 0 (one shared target, stride2 == 0): gxyz2[j,k] = U - A,  U = +0, then + u[b,j,k] ascending b;
+ *                                                   A = +0, then + a[b,i,k] for every (b,i) with idx1[b,i] == j, ascending (b,i)
+ * An index outside its range (-1: "no neighbour") makes its term +0 everywhere and is never used as an address.
+ * gdist1_d / idx1_d [B,n]: both NULL = no dist1 term; gdist2_d / idx2_d [B,m]: both NULL = no dist2 term.  gxyz1_d [B,n,3] or
+ * NULL; gxyz2_d NULL, [B,m,3] (reduce2 == 0) or [m,3] (reduce2 != 0).  FDCAP_E_ARG: a null ctx / xyz1_d / xyz2_d, a size <= 0,
+ * a gradient without its indices or the reverse, no term or no output at all, reduce2 with stride2 != 0, B*n or B*m above
+ * 2^31 - 1 (a side whose terms have to be grouped: above 2^31 - 8193).  Workspace: context-owned sort scratch, 16 bytes per
+ * grouped term of the larger side, grown on demand and kept. */
+int fdcap_chamfer_bwd_both(fdcap_ctx* ctx, const float* xyz1_d, const float* xyz2_d, int32_t B, int32_t n, int32_t m, int64_t stride2,
+                           const float* gdist1_d, const int32_t* idx1_d, const float* gdist2_d, const int32_t* idx2_d,
+                           float* gxyz1_d, float* gxyz2_d, int32_t reduce2, void* stream);
 
 /* Nearest-neighbour kernel selection for A/B measurement: 0 = by size (default), 1 = plain VALU
  * scan (nn_direct_kernel), 2 = MFMA-filtered exact scan (nn_mfma_kernel).  Both give bit-identical
