@@ -62,6 +62,7 @@ SYMBOLS = {
     "fdcap_debug_scene_hash": (c_int32, [c_void_p, c_void_p]),
     "fdcap_debug_scene_table": (c_int32, [c_void_p, c_int32, c_void_p, POINTER(c_int64)]),
     "fdcap_debug_kernel_forms": (c_int32, [c_void_p, c_int32, c_int32]),
+    "fdcap_debug_live_allocations": (c_int32, [c_void_p]),
     "fdcap_debug_pose_joint_sets": (c_int32, [c_void_p, c_void_p]),
     "fdcap_set_contact_ids": (c_int32, [c_void_p, c_void_p, c_int32]),
     "fdcap_chamfer_fwd": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p,

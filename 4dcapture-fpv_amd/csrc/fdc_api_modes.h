@@ -151,7 +151,7 @@ int fdcap_lbfgs_create(int32_t n, const fdcap_lbfgs_config* cf, fdcap_lbfgs** ou
     if (e == hipSuccess) e = L->W.ensure((size_t)n * lbfgs_ws_floats(cf->history));
     if (e == hipSuccess) e = L->RO.ensure((size_t)n * LB_HMAX);
     if (e == hipSuccess) e = L->active.ensure(2);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&L->active_h, sizeof(int), hipHostMallocDefault);
+    if (e == hipSuccess) e = L->active_h.alloc();
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)lbfgs_advance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lbfgs_lds_bytes(LB_HMAX));
     if (e == hipSuccess) { int r = fdcap_lbfgs_reset(L, nullptr); if (r == 0) e = hipDeviceSynchronize(); else e = (hipError_t)r; }
@@ -159,12 +159,7 @@ int fdcap_lbfgs_create(int32_t n, const fdcap_lbfgs_config* cf, fdcap_lbfgs** ou
     *out = L;
     return FDCAP_OK;
 }
-void fdcap_lbfgs_destroy(fdcap_lbfgs* L) {
-    if (!L) return;
-    L->S.release(); L->W.release(); L->RO.release(); L->active.release();
-    if (L->active_h) (void)hipHostFree(L->active_h);
-    delete L;
-}
+void fdcap_lbfgs_destroy(fdcap_lbfgs* L) { delete L; }
 int fdcap_lbfgs_reset(fdcap_lbfgs* L, void* stream) {
     if (!L) return FDCAP_E_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -264,14 +259,14 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap
         if (e) break;
         ++rounds;
         if (rounds % poll == 0 || rounds == max_rounds) {
-            HIP_TRY(hipMemcpyAsync(L->active_h, L->active.p + ((L->round - 1) & 1), sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(L->active_h.p, L->active.p + ((L->round - 1) & 1), sizeof(int), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            if (*L->active_h == 0) break;
+            if (*L->active_h.p == 0) break;
         }
     }
     if (rounds_out) *rounds_out = rounds;
     // out of rounds with frames still inside a line search: their rows hold trial points -- roll them back to the accepted ones
-    if (!e && rounds >= max_rounds && *L->active_h != 0) e = fdcap_lbfgs_finalize(L, o->X.p + 2 * XDIM, XDIM, nullptr, st);
+    if (!e && rounds >= max_rounds && *L->active_h.p != 0) e = fdcap_lbfgs_finalize(L, o->X.p + 2 * XDIM, XDIM, nullptr, st);
     if (o->dz_pending) {                                      // leave dX complete, as every other backward of the API does
         hipLaunchKernelGGL(vposer_fold_dz_kernel, dim3((nl * VP_Z + 255) / 256), dim3(256), 0, st, o->dZpart.p, (size_t)o->R * VP_Z, 2, nl, o->dX.p);
         o->dz_pending = false;
@@ -352,16 +347,12 @@ int fdcap_frame_smoother(fdcap_ctx* c, const float* data78, int32_t N, int32_t i
     tab_h.resize(n);
     for (size_t i = 0; i < n; ++i) tab_h[i] = adam_scalars(lr, step0 + (int)(i + 1));
     DevBuf<AdamScalars> local_d;
-    DevBuf<AdamScalars>& tab_d = c ? c->ws_adam : local_d;      // ctx == NULL: a temporary, released after a stream sync
+    DevBuf<AdamScalars>& tab_d = c ? c->ws_adam : local_d;      // ctx == NULL: a temporary, freed on return after a stream sync
     HIP_TRY(tab_d.ensure(n));
     HIP_TRY(hipMemcpyAsync(tab_d.p, tab_h.data(), n * sizeof(AdamScalars), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(frame_smoother_kernel, dim3(1), dim3(128), 0, st, data78, N, iters, tab_d.p,
                        smoother_weights(w_rec, w_vposer, w_prev), state, (step0 > 0 || has_prev) ? 1 : 0, has_prev ? 1 : 0, out78);
-    if (!c) {
-        hipError_t e_ = hipStreamSynchronize(st);
-        local_d.release();
-        if (e_ != hipSuccess) return (int)e_;
-    }
+    if (!c) HIP_TRY(hipStreamSynchronize(st));
     return (int)hipGetLastError();
 }
 

@@ -107,6 +107,14 @@ int fdcap_debug_kernel_forms(char* buf, int32_t len, int32_t reset) {
     return FDCAP_OK;
 }
 
+// test / diagnosis: what the owning types of fdc_own.h hold in this process right now: out3 = {blocks (device and pinned host), their
+// bytes, events}.  Tests take differences around a create ... destroy pair.
+int fdcap_debug_live_allocations(int64_t* out3) {
+    if (!out3) return FDCAP_E_ARG;
+    out3[0] = g_live_blocks.load(); out3[1] = g_live_bytes.load(); out3[2] = g_live_events.load();
+    return FDCAP_OK;
+}
+
 // test / diagnosis: the joint sets (plan_pose_joints, fdc_forms.h) of the optimiser's last pose forward and pose backward launch:
 // out8 = {forward jn, jr, nlev, world; backward jn, jr, nlev, world}
 int fdcap_debug_pose_joint_sets(fdcap_ctx* c, int32_t* out8) {
@@ -229,23 +237,7 @@ int fdcap_ctx_create(const fdcap_model_desc* md, fdcap_ctx** out) {
 void fdcap_ctx_destroy(fdcap_ctx* c) {
     if (!c) return;
     fdcap_opt_destroy(c);
-    (void)fdcap_comm_destroy(c);
-    c->xch_send.release(); c->xch_all.release();
-    c->ws_adam.release();
-    c->Jt.release(); c->Jd.release(); c->hand_comp.release(); c->hand_mean.release(); c->d_posedirs.release(); c->d_S10.release();
-    c->parents.release(); c->order.release(); c->level_start.release(); c->child_start.release(); c->child_list.release(); c->depth.release();
-    c->pose_tab.release();
-    c->W1.release(); c->b1.release(); c->W2.release(); c->b2.release(); c->W3.release(); c->b3.release();
-    for (auto& b : c->vp_pn) b.release();
-    for (auto& b : c->vp_pn3) b.release();
-    for (auto& b : c->vp_pn3s) b.release();
-    c->full.release(); c->contact.release(); c->contact_vid.release(); c->contact_perm.release(); c->scene.release(); c->scene_sorted.release(); c->scene_bounds.release(); c->scene_sbounds.release(); c->scene_qbounds.release(); c->scene_inv.release(); c->scene_frags.release(); c->scene_centers.release(); c->sop.release(); c->ws_skin.release(); c->ws_kpart.release();
-    for (auto& b : c->ws_f) b.release();
-    for (auto& b : c->ws_b) b.release();
-    c->ws_part.release();
-    for (auto& b : c->ws_i) b.release();
-    c->ws_p.release();
-    c->ws_ck.release(); c->ws_cv.release();
+    (void)fdcap_comm_destroy(c);                            // (before the exchange buffers, which `delete` frees with everything else)
     delete c;
 }
 
@@ -256,6 +248,7 @@ int fdcap_set_scene(fdcap_ctx* c, const float* xyz, int64_t ns) {
     // a live optimiser holds buffers sized for, and pruning state (seeds, kept work lists) valid for, the registered scene
     if (c->opt) return FDCAP_E_STATE;
     c->sop.nq = 0;                                          // (the scene operator's seeds / kept lists were for the old scene)
+    c->ns = 0;                                              // (no scene until the new tables are complete: a failure below leaves none)
     static_assert(SC_SUPER == ST4_SUPER, "fdc_scene.h builds the super-cell boxes the search reads");
     // Spatial order by recursive median splits (k-d cells): every MF_CH-point chunk is one cell and every 32-point MFMA tile inside it
     // a sub-cell, so the boxes the NN scan culls with are compact and disjoint (runs of a Morton curve jump across quadrant borders

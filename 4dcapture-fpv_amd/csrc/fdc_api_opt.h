@@ -8,20 +8,7 @@ extern "C" {
 void fdcap_opt_destroy(fdcap_ctx* c) {
     if (!c || !c->opt) return;
     OptState* o = c->opt;
-    DevBuf<float>* fb[] = {&o->X0, &o->mask, &o->mX, &o->vX, &o->mCAM, &o->vCAM, &o->mS, &o->vS,
-                           &o->H1, &o->H2, &o->O, &o->dO, &o->Opart, &o->dZpart, &o->Rm, &o->PF, &o->Jrest, &o->G, &o->A, &o->M,
-                           &o->Jw, &o->Voff, &o->Vw, &o->dist, &o->pd, &o->dVoff, &o->dA, &o->dtransl_v, &o->dMv,
-                           &o->dsv, &o->dPF, &o->dJw, &o->dX, &o->dCAM, &o->dscale_row, &o->loss_rows, &o->VoffF, &o->VwF, &o->dVF};
-    for (auto* b : fb) b->release();
-    o->dctD.release(); o->dctCoef.release(); o->dctM.release(); o->dctV.release(); o->adam_tab.release();
-    o->clip_rows.release(); o->clip_span.release();
-    o->idx.release(); o->pi.release(); o->seedpt.release(); o->kp2d.release(); o->floss.release();
-    if (o->lbfgs) { fdcap_lbfgs_destroy(o->lbfgs); o->lbfgs = nullptr; }
-    o->nnc_ids.release(); o->nnc_hdr.release(); o->nnc_anchor.release();
-    for (hipEvent_t e : o->nn_ev) (void)hipEventDestroy(e);
-    o->nn_ev.clear();
-    for (hipEvent_t e : o->lt.ev) (void)hipEventDestroy(e);
-    o->lt.ev.clear(); o->lt.what.clear(); o->lt.on = false; o->lt.used = 0;
+    if (o->lbfgs) fdcap_lbfgs_destroy(o->lbfgs);           // (an incomplete type where OptState is defined: not a member it can own)
     delete o;
     c->opt = nullptr;
 }
@@ -478,11 +465,13 @@ int fdcap_debug_nn_query_sort(fdcap_ctx* c, const int32_t* pos_host, int32_t nq,
     hipError_t e = seedpt.upload(sp.data(), (size_t)nq);
     if (e == hipSuccess) e = qbuf.ensure(nn_query_order_ints(nq));
     if (e == hipSuccess) e = hdr.upload(hdr_io, (size_t)hdr_len);
-    if (e == hipSuccess) e = nn_query_order(seedpt.p, nq, qbuf.p, hdr.p, groups, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) {                                   // (the three buffers are freed on return: wait, whatever the launches said)
+        e = nn_query_order(seedpt.p, nq, qbuf.p, hdr.p, groups, st);
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = es;
+    }
     if (e == hipSuccess) e = hipMemcpy(perm_out, qbuf.p, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess && hdr_len > 0) e = hipMemcpy(hdr_io, hdr.p, (size_t)hdr_len * sizeof(int), hipMemcpyDeviceToHost);
-    seedpt.release(); qbuf.release(); hdr.release();
     return e == hipSuccess ? FDCAP_OK : (int)e;
 }
 

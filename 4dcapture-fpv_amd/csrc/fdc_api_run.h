@@ -244,8 +244,8 @@ int fdcap_opt_time_exchange(fdcap_ctx* c, int32_t iters, float* us_exchange, flo
     hipStream_t st = (hipStream_t)stream;
     int e = comm_buffers(c);
     if (e) return e;
-    hipEvent_t ev[4];
-    for (auto& x : ev) HIP_TRY(hipEventCreate(&x));
+    DevEvents ev;
+    HIP_TRY(ev.grow_to(4));
     const int big = 1 << 30;                                  // (P: every iteration is a phase-1 iteration -- `scale` steps, camera_ext rests)
     for (int k = 0; k < 8 && !e; ++k) e = fdcap_opt_exchange(c, k, big, stream);              // warm-up
     if (!e) e = (int)hipEventRecord(ev[0], st);
@@ -261,7 +261,6 @@ int fdcap_opt_time_exchange(fdcap_ctx* c, int32_t iters, float* us_exchange, flo
     float a = 0.f, b = 0.f;
     if (!e) e = (int)hipEventElapsedTime(&a, ev[0], ev[1]);
     if (!e) e = (int)hipEventElapsedTime(&b, ev[2], ev[3]);
-    for (auto& x : ev) (void)hipEventDestroy(x);
     *us_exchange = a * 1e3f / iters;
     *us_allgather = b * 1e3f / iters;
     return e;
@@ -406,8 +405,7 @@ int fdcap_panel_gemm(const float* A, int32_t lda, int32_t M, int32_t K, const fl
             HIP_TRY(ds.upload(sc.data(), sc.size()));
             B3.f = (const uint4*)d3.p; B3.isc = ds.p;
             hipError_t e = panel_gemm3(A, lda, M, K, B3, C, ldc, N, st);
-            hipError_t e2 = hipStreamSynchronize(st);
-            d3.release(); ds.release();
+            hipError_t e2 = hipStreamSynchronize(st);                    // (d3 and ds are freed on return: the launch must be done with them)
             return (int)(e != hipSuccess ? e : e2);
         }
     }
@@ -418,8 +416,7 @@ int fdcap_panel_gemm(const float* A, int32_t lda, int32_t M, int32_t K, const fl
     HIP_TRY(d.upload(pf.data(), pf.size()));
     B.f = (const float4*)d.p;
     hipError_t e = panel_gemm(A, lda, M, K, B, C, ldc, N, st);
-    hipError_t e2 = hipStreamSynchronize(st);
-    d.release();
+    hipError_t e2 = hipStreamSynchronize(st);                            // (d is freed on return)
     return (int)(e != hipSuccess ? e : e2);
 }
 
@@ -428,12 +425,7 @@ int fdcap_opt_nn_timing(fdcap_ctx* c, int32_t max_launches) {
     OptState* o = c->opt;
     o->nn_timing = max_launches > 0;
     o->nn_ev_used = 0;
-    while ((int)o->nn_ev.size() < 2 * max_launches) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        o->nn_ev.push_back(e);
-    }
-    return FDCAP_OK;
+    return (int)o->nn_ev.grow_to(2 * (size_t)max_launches);     // (on failure: timing stays on with the events there are)
 }
 int fdcap_opt_nn_timing_read(fdcap_ctx* c, float* mean_ms, int32_t* launches) {
     if (!c || !c->opt || !mean_ms || !launches) return FDCAP_E_ARG;
@@ -455,13 +447,9 @@ int fdcap_opt_launch_timing(fdcap_ctx* c, int32_t max_events) {
     OptState::LaunchTimes& t = c->opt->lt;
     t.on = max_events > 0;
     t.used = 0;
-    while ((int)t.ev.size() < max_events) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        t.ev.push_back(e);
-    }
-    t.what.resize(t.ev.size(), (signed char)-1);
-    return FDCAP_OK;
+    const hipError_t e = t.ev.grow_to((size_t)max_events);
+    t.what.resize(t.ev.size(), (signed char)-1);                // (as many as there are events, also when creating one failed)
+    return (int)e;
 }
 int fdcap_opt_launch_timing_read(fdcap_ctx* c, float* mean_us, int32_t* counts) {
     if (!c || !c->opt || !mean_us || !counts) return FDCAP_E_ARG;
@@ -496,9 +484,9 @@ int fdcap_time_blend_gemm(fdcap_ctx* c, int32_t rows, int32_t iters, float* ms, 
     HIP_TRY(c->ws_f[6].ensure((size_t)rows * NPFX));
     HIP_TRY(c->ws_f[11].ensure((size_t)rows * 3 * V));
     HIP_TRY(hipMemsetAsync(c->ws_f[6].p, 0x3c, (size_t)rows * NPFX * sizeof(float), st));   // arbitrary finite pattern
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    DevEvent e0, e1;
+    HIP_TRY(e0.create());
+    HIP_TRY(e1.create());
     HIP_TRY(blend_forward(c->full, c->ws_f[6].p, rows, c->ws_f[11].p, st));
     HIP_TRY(hipEventRecord(e0, st));
     for (int i = 0; i < iters; ++i)
@@ -508,8 +496,6 @@ int fdcap_time_blend_gemm(fdcap_ctx* c, int32_t rows, int32_t iters, float* ms, 
     float t = 0.f;
     HIP_TRY(hipEventElapsedTime(&t, e0, e1));
     *ms = t / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return FDCAP_OK;
 }
 
@@ -526,9 +512,9 @@ int fdcap_opt_time_chamfer(fdcap_ctx* c, int32_t iters, int32_t brute_force, flo
     const int* seed = (!brute_force && o->sw.nn_seed) ? o->idx.p + 2 * nc : nullptr;
     NNTarget T = c->nn_target(!brute_force && o->sw.nn_cull);
     if (brute_force) { T.pts = c->scene.p; T.inv_perm = nullptr; T.frags = nullptr; }   // input order (a spatial sort is adversarial for an unseeded running minimum)
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    DevEvent e0, e1;
+    HIP_TRY(e0.create());
+    HIP_TRY(e1.create());
     const int nsp = brute_force ? o->nsplit_bf : o->nsplit;
     float4* sp = brute_force ? nullptr : o->seedpt.p + 2 * nc;
     // (warm-up launch; after a brute-force launch rewrote idx it also refreshes the neighbours' coordinates)
@@ -546,8 +532,6 @@ int fdcap_opt_time_chamfer(fdcap_ctx* c, int32_t iters, int32_t brute_force, flo
     float t = 0.f;
     HIP_TRY(hipEventElapsedTime(&t, e0, e1));
     *ms = t / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (brute_force) o->seeded = false;      // idx was rewritten without the neighbours' coordinates: refresh them before the next seeded launch
     return FDCAP_OK;
 }

@@ -555,8 +555,6 @@ struct SceneTables {            // device pointers, sized by the caller: ns poin
 
 // `order_host` != nullptr: take this order (the host build's) instead of sorting on the device.  Synchronous.
 inline hipError_t scene_build_device(const float* xyz_host, int64_t ns64, const SceneTables& T, const int* order_host) {
-#define SC_TRY(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { if (arena) (void)hipFree(arena); return e_; } } while (0)
-    char* arena = nullptr;
     const int ns = (int)ns64;
     if (ns <= 0) return hipSuccess;
     const int nchunk = (ns + MF_CH - 1) / MF_CH, nsuper = (nchunk + SC_SUPER - 1) / SC_SUPER;
@@ -573,7 +571,10 @@ inline hipError_t scene_build_device(const float* xyz_host, int64_t ns64, const 
                  o_side = o_key + 2 * al((size_t)ns * 4), o_hist = o_side + al((size_t)ns),
                  o_cnt = o_hist + al((size_t)256 * nb_rs * 4), o_nodes = o_cnt + al((size_t)4 * nb_pt * 4),
                  o_axis = o_nodes + al(std::max<size_t>(nodes.size(), 1) * sizeof(int4)), total = o_axis + al((size_t)max_nodes);
-    SC_TRY(hipMalloc((void**)&arena, total));
+    DevBuf<char> arena_buf;                                      // freed on every way out; nothing returns between the first launch and the wait
+    hipError_t e = arena_buf.ensure(total);
+    if (e != hipSuccess) return e;
+    char* const arena = arena_buf.p;
     float* xyz = (float*)(arena + o_xyz);
     int* list[4][2];
     for (int l = 0; l < 4; ++l) for (int b = 0; b < 2; ++b) list[l][b] = (int*)(arena + o_list + (size_t)(2 * l + b) * al((size_t)ns * 4));
@@ -584,13 +585,16 @@ inline hipError_t scene_build_device(const float* xyz_host, int64_t ns64, const 
     int4* d_nodes = (int4*)(arena + o_nodes);
     unsigned char* axis = (unsigned char*)(arena + o_axis);
     hipStream_t st = 0;
-    SC_TRY(hipMemcpyAsync(xyz, xyz_host, (size_t)ns * 12, hipMemcpyHostToDevice, st));
+    e = hipMemcpyAsync(xyz, xyz_host, (size_t)ns * 12, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
     const int* order = nullptr;
     if (order_host) {
-        SC_TRY(hipMemcpyAsync(list[3][0], order_host, (size_t)ns * 4, hipMemcpyHostToDevice, st));
+        e = hipMemcpyAsync(list[3][0], order_host, (size_t)ns * 4, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
         order = list[3][0];
     } else {
-        if (!nodes.empty()) SC_TRY(hipMemcpyAsync(d_nodes, nodes.data(), nodes.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+        if (!nodes.empty()) e = hipMemcpyAsync(d_nodes, nodes.data(), nodes.size() * sizeof(int4), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
         const dim3 g256((ns + 255) / 256);
         for (int ax = 0; ax < 3; ++ax) {                                       // list[ax][0] <- indices by (coordinate ax, index)
             hipLaunchKernelGGL(sc_keys_kernel, g256, dim3(256), 0, st, xyz, ns, ax, key[0], list[ax][0]);
@@ -620,11 +624,9 @@ inline hipError_t scene_build_device(const float* xyz_host, int64_t ns64, const 
     hipLaunchKernelGGL(sc_finalize_kernel, dim3(nchunk), dim3(MF_CH), 0, st, xyz, order, ns, T.orig, T.sorted, T.inv, T.bounds, T.qbounds,
                        T.frags, T.centers);
     hipLaunchKernelGGL(sc_super_kernel, dim3((nsuper + 255) / 256), dim3(256), 0, st, T.bounds, nchunk, T.sbounds, nsuper);
-    SC_TRY(hipGetLastError());
-    SC_TRY(hipStreamSynchronize(st));
-    (void)hipFree(arena);
-    return hipSuccess;
-#undef SC_TRY
+    e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(st);             // (the arena is freed on return: the launches must be done with it)
+    return e != hipSuccess ? e : es;
 }
 
 }  // namespace fdc

@@ -28,26 +28,6 @@ struct SetupTrace {
     }
 };
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t count) {
-        if (count <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    hipError_t upload(const T* h, size_t count) {
-        hipError_t e = ensure(count);
-        if (e != hipSuccess) return e;
-        return count ? hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
 // skin_bwd_kernel for any vertex set: one workgroup per frame up to a chunk of vertices, the split form + its reduction beyond
 // (`part`: workspace, grown as needed).  Same arguments as the kernel.
 template <bool CONTACT>
@@ -96,10 +76,6 @@ struct SkinSet {          // skinning constants for a vertex set (all V, or the 
         m.wf_tab = wf_tab.p; m.wf_step = (const unsigned*)wf_step.p; m.wf_frag = (const float*)wf_frag.p;
         return m;
     }
-    void release() { vt.release(); ww.release(); posedirs.release(); wj.release(); csc_w.release(); csc_start.release(); csc_v.release();
-                     vpack.release(); csc_v16.release(); csc_chunk.release(); wf_tab.release(); wf_step.release(); wf_frag.release();
-                     pn_fwd_f.release(); pn_bwd_f.release(); pn_fwd = PanelB(); pn_bwd = PanelB();
-                     pn_fwd3_f.release(); pn_bwd3_f.release(); pn_fwd3_s.release(); pn_bwd3_s.release(); pn_fwdS_f.release(); pn_fwdS_s.release(); pn_fwdS = PanelB3(); pn_fwd3 = PanelB3(); pn_bwd3 = PanelB3(); }
 };
 
 struct OptState {
@@ -166,12 +142,12 @@ struct OptState {
     struct LaunchTimes {
         bool on = false;
         int used = 0, phase = 0;
-        std::vector<hipEvent_t> ev;
+        DevEvents ev;
         std::vector<signed char> what;         // what[k]: the stage that ended at event k (FDCAP_LT_*; -1: an iteration's first event), + 16 in phase 2
     } lt;
     // fdcap_opt_nn_timing: HIP events around every in-loop NN launch of a fit (the bench's roofline figure)
     bool nn_timing = false;
-    std::vector<hipEvent_t> nn_ev;
+    DevEvents nn_ev;
     int nn_ev_used = 0;
     NNCache nn_cache(int) {
         NNCache nc{sw.nn_cache_slack > 0.f ? nnc_ids.p : nullptr, sw.nn_cache_slack > 0.f ? nnc_hdr.p : nullptr, nnc_anchor.p, sw.nn_cache_slack};
@@ -212,7 +188,7 @@ struct fdcap_lbfgs {          // batched L-BFGS (csrc/fdc_lbfgs.h): n independen
     DevBuf<LbfgsScalars> S;
     DevBuf<float> W, RO;      // per problem: vector workspace, 1 / (y . s) of the history pairs
     DevBuf<int> active;
-    int* active_h = nullptr;  // pinned
+    PinnedBuf<int> active_h;  // the host's copy of the current counter
     int round = 0;            // rounds since the last reset: active[round & 1] is the counter of the current one
 };
 
@@ -272,7 +248,6 @@ struct fdcap_ctx {
         DevBuf<float4> seedpt, anchor;
         DevBuf<unsigned short> ids;
         int nq = 0;                 // queries of the call that left the state (0: none)
-        void release() { dist.release(); idx.release(); hdr.release(); seedpt.release(); anchor.release(); ids.release(); nq = 0; }
     } sop;
     OptState* opt = nullptr;
     Comm comm;                      // fdcap_comm_create: RCCL communicator of the sharded optimiser
@@ -350,16 +325,12 @@ int pnf_pack_dev(const float* src, size_t src_floats, long sk, long sn, int K, i
     const size_t lanes = (size_t)nt * ns * 64;
     HIP_TRY(out.ensure(lanes * 2 * 4)); HIP_TRY(isc.ensure((size_t)nt * 16));
     DevBuf<float> scl;                                            // the columns' scales: only the packing launch needs them
-    hipError_t e = scl.ensure((size_t)nt * 16);
-    if (e == hipSuccess) {
-        if (sn == 1) hipLaunchKernelGGL(pnh2_colscale_rowmajor_kernel, dim3((nt * 16 + 255) / 256), dim3(256), 0, 0, src, sk, K, N, nt * 16, scl.p, isc.p);
-        else hipLaunchKernelGGL(pnh2_colscale_colmajor_kernel, dim3(nt * 16), dim3(256), 0, 0, src, sn, K, N, nt * 16, scl.p, isc.p);
-        hipLaunchKernelGGL(pnh2_pack_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, 0, src, sk, sn, K, N, nt, ns, scl.p, (uint4*)out.p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();          // (scl is freed below: the launch must be done with it)
-    }
-    scl.release();
-    return (int)e;
+    HIP_TRY(scl.ensure((size_t)nt * 16));
+    if (sn == 1) hipLaunchKernelGGL(pnh2_colscale_rowmajor_kernel, dim3((nt * 16 + 255) / 256), dim3(256), 0, 0, src, sk, K, N, nt * 16, scl.p, isc.p);
+    else hipLaunchKernelGGL(pnh2_colscale_colmajor_kernel, dim3(nt * 16), dim3(256), 0, 0, src, sn, K, N, nt * 16, scl.p, isc.p);
+    hipLaunchKernelGGL(pnh2_pack_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, 0, src, sk, sn, K, N, nt, ns, scl.p, (uint4*)out.p);
+    const hipError_t e = hipGetLastError(), es = hipDeviceSynchronize();     // (scl is freed on return: wait, whatever the launches said)
+    return (int)(e != hipSuccess ? e : es);
 }
 
 int build_skin_set(fdcap_ctx* c, const std::vector<int64_t>& ids, SkinSet* out) {
@@ -392,12 +363,10 @@ int build_skin_set(fdcap_ctx* c, const std::vector<int64_t>& ids, SkinSet* out) 
         std::vector<int> id32((size_t)std::max(nv, 1), 0);
         for (int i = 0; i < nv; ++i) id32[i] = (int)ids[i];
         DevBuf<int> d_ids;
-        { hipError_t eu = d_ids.upload(id32.data(), id32.size()); if (eu != hipSuccess) { d_ids.release(); return (int)eu; } }
+        HIP_TRY(d_ids.upload(id32.data(), id32.size()));
         if (ldp > 0) hipLaunchKernelGGL(blend_rows_gather_kernel, dim3((ldp + 255) / 256, NPFX), dim3(256), 0, 0, c->d_posedirs.p, c->d_S10.p, V, d_ids.p, nv, ldp, out->posedirs.p);
-        hipError_t e_ = hipGetLastError();
-        if (e_ == hipSuccess) e_ = hipDeviceSynchronize();
-        d_ids.release();
-        HIP_TRY(e_);
+        const hipError_t e_ = hipGetLastError(), es_ = hipDeviceSynchronize();   // (d_ids is freed at the brace: wait, whatever the launch said)
+        HIP_TRY(e_ != hipSuccess ? e_ : es_);
     }
     const float* pd = out->posedirs.p;
     tr.mark("gather vt / weights / posedirs");
@@ -525,13 +494,12 @@ int build_skin_set(fdcap_ctx* c, const std::vector<int64_t>& ids, SkinSet* out) 
     if (nv > 0 && nv <= 512 && K <= 4) {          // ... and with permuted columns (blend_rows_permute_kernel)
         const int nb = (nv + 63) / 64, ncs = nb * 192;
         DevBuf<float> ps;
-        { hipError_t ep = ps.ensure((size_t)NPFX * ncs); if (ep != hipSuccess) return (int)ep; }
+        HIP_TRY(ps.ensure((size_t)NPFX * ncs));
         hipLaunchKernelGGL(blend_rows_permute_kernel, dim3((ncs + 255) / 256, NPFX), dim3(256), 0, 0, pd, ldp, nv, ncs, ps.p);
         int e = (int)hipGetLastError();
         if (!e) e = pnf_pack_dev(ps.p, (size_t)NPFX * ncs, ncs, 1, NPFX, ncs, out->pn_fwdS_f, out->pn_fwdS_s, &out->pn_fwdS.ntile, &out->pn_fwdS.nst);
-        if (!e) e = (int)hipDeviceSynchronize();
-        ps.release();
-        if (e) return e;
+        const int es = (int)hipDeviceSynchronize();      // (ps is freed at the brace: wait, whatever the launches said)
+        if (e || es) return e ? e : es;
         out->pn_fwdS.f = (const uint4*)out->pn_fwdS_f.p; out->pn_fwdS.isc = out->pn_fwdS_s.p;
     }
     tr.mark("permuted forward panel");

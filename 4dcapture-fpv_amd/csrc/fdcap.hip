@@ -30,6 +30,7 @@ __device__ unsigned long long g_fr_times[3][2048 * 8];
 #define FDC_FR_STAMP(w, i)
 #endif
 #include "../../include/fdcap.h"
+#include "fdc_own.h"         // DevBuf, PinnedBuf, DevEvent(s): who owns device memory and events (ahead of fdc_scene.h, which uses it)
 #include "fdc_chamfer.h"
 #include "fdc_chamfer_bwd.h"
 #include "fdc_comm.h"
@@ -58,7 +59,7 @@ using namespace fdc;
 #include "fdc_k_pose.h"      // per-frame pose kernels (forward, backward + parameter-space losses)
 #include "fdc_k_skin.h"      // skinning forward / backward (+ contact robustifier)
 #include "fdc_k_step.h"      // mode 'local' kernels, loss reductions, Adam / exchange step, conversions, operator helpers
-#include "fdc_state.h"       // DevBuf, fdcap_ctx, OptState, shared host helpers
+#include "fdc_state.h"       // fdcap_ctx, OptState, shared host helpers
 #include "fdc_api_ops.h"     // C-ABI: context, scene, contact ids, Op 1-3 (+ backward), conversions
 #include "fdc_api_opt.h"     // C-ABI: the clip optimiser's iteration
 #include "fdc_api_modes.h"   // C-ABI: mode 'dct', inner fit / L-BFGS, checkpoint state, per-frame smoother

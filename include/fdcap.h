@@ -114,6 +114,11 @@ int fdcap_debug_scene_table(fdcap_ctx* ctx, int32_t which, void* host_out, int64
  * check that it ran.  FDCAP_CLIP_FORMS_MIN_ROWS (environment, read once per process) lowers the row count from which the
  * clip-sized forms are selected (default 336): the reference's 300-frame fixtures then run through them. */
 int fdcap_debug_kernel_forms(char* buf, int32_t len, int32_t reset);
+/* test / diagnosis: what the library holds in this process right now, out3 = {live memory blocks (device and pinned host), their
+ * bytes, live HIP events}.  Every allocation and every event of the library is owned by a type of csrc/fdc_own.h that counts here
+ * where it allocates and frees; nothing on a per-iteration path does.  A create ... destroy pair leaves all three where they were
+ * (tests/test_gpu_ownership.py takes such differences). */
+int fdcap_debug_live_allocations(int64_t out3[3]);
 /* test / diagnosis: the joint sets of the optimiser's last pose forward and pose backward launch,
    out8 = {forward jn, jr, nlev, world; backward jn, jr, nlev, world}: joints [0, jn) took part in the kinematic chain,
    joints [0, jr) had their local rotation formed, nlev levels of the tree were walked, world = the world joints were written */
