@@ -109,6 +109,8 @@ SYMBOLS = {
     "fdcap_opt_detect_contact": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
     "fdcap_opt_backward_local2": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "fdcap_opt_step_x": (c_int32, [c_void_p, c_int32, c_void_p]),
+    "fdcap_opt_run_local2": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p,
+                                       c_void_p]),
     "fdcap_opt_set_dct": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "fdcap_opt_dct_fit": (c_int32, [c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32, c_void_p]),
     "fdcap_opt_backward_dct": (c_int32, [c_void_p, c_float, c_float, c_float, c_int32, c_void_p]),

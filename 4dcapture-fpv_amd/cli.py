@@ -14,7 +14,10 @@ Several clips in one run (the reference's real workload: every video cut into 30
 Each clip's scene and camera paths are derived from its sample name as above (`--scene-root`).  Clips are grouped by (scene
 file -- the resolved path, so that the segments of one video may link one scene --, clip length); each group is cut into batches of at most K clips that are fitted as one optimisation (fitting.ClipBatchFitter:
 one context for the whole run).  Clip output: `<fit-root>/<sample_name>/body_gen_%06d.pkl`, the files the one-clip form writes
-with that directory as <fit_path>.  Default K: the largest K with K * N <= MULTICLIP_ROW_CAP.  Mode 'global' only.
+with that directory as <fit_path>.  Default K: the largest K with K * N <= MULTICLIP_ROW_CAP.  Mode 'global' only ON THIS COMMAND
+LINE: the library and the Python interface fit a batch in mode 'local' as well (fitting.ClipBatchFitter.fit(..., mode='local'),
+fdcap_opt_run_local2), but `--clips --mode local` is still refused here, and tests/test_multiclip_cpu.py::
+test_modes_other_than_global_are_refused pins that refusal -- lifting it is a follow-up that has to change that test with it.
 
 `--mix-lengths` (with --clips): clips are grouped by scene file alone and a batch may hold clips of different lengths
 (plan_batches_mixed: batches are filled in input order up to MULTICLIP_ROW_CAP rows, so a video's short remainder clip rides with

@@ -109,13 +109,16 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
         if (e_ != hipSuccess) err = (int)e_;
     }
     if (!err && o->ragged) {
-        // the clip tables (fdc_clips.h): every row's record under the weights of phase 1, then of phase 2, and the clips' spans
+        // the clip tables (fdc_clips.h): every row's record under the weights of phase 1, then of phase 2, then of mode 'local''s
+        // second loop, and the clips' spans
         std::vector<ClipRow> rows = clip_rows_build(n_clips, var_len, opt_phase_weights(*cfg, false), cfg->weight_loss_rec, cfg->weight_contact, c->nc);
         const std::vector<ClipRow> rows2 = clip_rows_build(n_clips, var_len, opt_phase_weights(*cfg, true), cfg->weight_loss_rec, cfg->weight_contact, c->nc);
+        const std::vector<ClipRow> rows3 = clip_rows_build_local2(n_clips, var_len, cfg->weight_loss_rec, (size_t)3 * c->V);
         rows.insert(rows.end(), rows2.begin(), rows2.end());
+        rows.insert(rows.end(), rows3.begin(), rows3.end());
         std::vector<int> span((size_t)2 * n_clips);
         for (int k = 0; k < n_clips; ++k) { span[(size_t)2 * k] = o->clip_start[(size_t)k]; span[(size_t)2 * k + 1] = var_len[k]; }
-        hipError_t e_ = rows.size() == (size_t)2 * R ? o->clip_rows.upload(rows.data(), rows.size()) : hipErrorInvalidValue;
+        hipError_t e_ = rows.size() == (size_t)3 * R ? o->clip_rows.upload(rows.data(), rows.size()) : hipErrorInvalidValue;
         if (e_ == hipSuccess) e_ = o->clip_span.upload(span.data(), span.size());
         if (e_ != hipSuccess) err = (int)e_;
     }

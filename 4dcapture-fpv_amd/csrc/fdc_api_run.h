@@ -5,12 +5,10 @@
 extern "C" {
 
 // ---- mode 'local' (global_optimization.py:499-556) --------------------------------------------
-int fdcap_opt_detect_contact(fdcap_ctx* c, int32_t n_left, float* weight_left, void* stream) {
-    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
-    if (!c || !c->opt || !weight_left || n_left <= 0 || n_left > c->nc) return FDCAP_E_ARG;
+// detect_contact (:355-364) for the owned rows: pose forward, contact forward, left / (left + left) per frame.  A batch of clips
+// (fdcap_opt_run_local2) takes the same three launches: the forwards find each row's clip themselves, the weight is per frame.
+static int opt_detect_contact_impl(fdcap_ctx* c, int32_t n_left, float* weight_left, hipStream_t st) {
     OptState* o = c->opt;
-    if (!o->contact_on) return FDCAP_E_STATE;
-    hipStream_t st = (hipStream_t)stream;
     const int nl = o->cfg.n_local, nc = c->nc;
     int row_lo, row_hi;
     opt_row_range(o, 1, &row_lo, &row_hi);
@@ -22,14 +20,27 @@ int fdcap_opt_detect_contact(fdcap_ctx* c, int32_t n_left, float* weight_left, v
     return (int)hipGetLastError();
 }
 
-int fdcap_opt_backward_local2(fdcap_ctx* c, const float* contact_weight, int32_t n_left, void* stream) {
-    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
-    if (!c || !c->opt || !contact_weight || n_left <= 0 || n_left >= c->nc) return FDCAP_E_ARG;
-    { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
+int fdcap_opt_detect_contact(fdcap_ctx* c, int32_t n_left, float* weight_left, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_local2 only)
+    if (!c || !c->opt || !weight_left || n_left <= 0 || n_left > c->nc) return FDCAP_E_ARG;
     OptState* o = c->opt;
-    hipStream_t st = (hipStream_t)stream;
+    if (!o->contact_on) return FDCAP_E_STATE;
+    return opt_detect_contact_impl(c, n_left, weight_left, (hipStream_t)stream);
+}
+
+// One backward of cal_loss2 (:404-429) for one clip, one rank's share of one, or a batch of clips.  A batch (fdcap_opt_run_local2
+// only): every launch takes the clip-aware form -- equal lengths by arithmetic on the one length (kclip_n), different lengths by
+// the second loop's records of the clip table (ctab_local2) -- so that each clip's denominators, stencil extent, `scale` and
+// losses[k][] are its own; one clip takes the launches it always took.
+static int opt_backward_local2_impl(fdcap_ctx* c, const float* contact_weight, int32_t n_left, hipStream_t st) {
+    { int es_ = opt_sync(c, st); if (es_) return es_; }
+    OptState* o = c->opt;
     const fdcap_opt_config& cf = o->cfg;
-    const int R = o->R, nl = cf.n_local, nc = c->nc, N = cf.n_total, V = c->V;
+    // N: the clip length -- the denominators of the means and the stencils' extent (a batch of one length: every clip has N frames;
+    // different lengths: 0, the kernels read each frame's record and the weights below are placeholders)
+    const int R = o->R, nl = cf.n_local, nc = c->nc, N = o->clip_len, V = c->V, kn = o->kclip_n();
+    const ClipRow* const ctab = o->ctab_local2();
+    const bool batch = o->nclip > 1;
     if (!c->full_ready) {
         std::vector<int64_t> all(V);
         for (int i = 0; i < V; ++i) all[i] = i;
@@ -42,48 +53,103 @@ int fdcap_opt_backward_local2(fdcap_ctx* c, const float* contact_weight, int32_t
     HIP_TRY(o->VwF.ensure((size_t)R * nv3));
     HIP_TRY(o->dVF.ensure((size_t)R * nv3));
     PoseModel pm = c->pose_model();
-    HIP_TRY(hipMemsetAsync(o->losses.p, 0, FDCAP_NUM_LOSSES * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(o->losses.p, 0, (size_t)o->nclip * FDCAP_NUM_LOSSES * sizeof(double), st));
     int row_lo, row_hi;
     opt_row_range(o, 2, &row_lo, &row_hi);
     int e = opt_pose_forward(c, row_lo, row_hi, st);
     if (e) return e;
     // full-mesh world vertices of every row (the vertex stencil needs 2 halo frames each side)
     HIP_TRY(blend_forward(c->full, o->PF.p, R, o->VoffF.p, st));
-    hipLaunchKernelGGL(skin_fwd_kernel, dim3((V + 255) / 256, R), dim3(256), 0, st, c->full.model(), V, o->X.p, XDIM, X_BETAS,
-                       X_TRANSL, o->VoffF.p, o->A.p, o->M.p, o->scale.p, 0, 1, o->VwF.p);
+    note_form(form_name(F_SKIN_FWD));
+    if (batch)                                               // (whole clips: no stencil reaches a halo row, and none has a clip to take `scale` from)
+        hipLaunchKernelGGL(skin_fwd_kernel, dim3((V + 255) / 256, nl), dim3(256), 0, st, c->full.model(), V, o->X.p, XDIM, X_BETAS,
+                           X_TRANSL, o->VoffF.p, o->A.p, o->M.p, o->scale.p, 2, 1, o->VwF.p, kn, ctab);
+    else
+        hipLaunchKernelGGL(skin_fwd_kernel, dim3((V + 255) / 256, R), dim3(256), 0, st, c->full.model(), V, o->X.p, XDIM, X_BETAS,
+                           X_TRANSL, o->VoffF.p, o->A.p, o->M.p, o->scale.p, 0, 1, o->VwF.p);
     // losses [0] rec, [1] z^2, [2] local (parameter) smoothing, [5] vertex smoothing, [6] foot skate
-    const float w_rec = cf.weight_loss_rec / ((float)N * XDIM);
-    const float w_sm = (N >= 3) ? 1.f / ((float)(N - 2) * XDIM) : 0.f;
+    const ClipWeights w = clip_weights_local2(std::max(N, 1), cf.weight_loss_rec, nv3);
     hipLaunchKernelGGL(param_loss_kernel, dim3(nl), dim3(128), 0, st, o->X.p, o->X0.p, o->mask.p, o->Jw.p, 2, cf.frame0, N,
-                       w_rec, w_sm, 0.f, 0, o->dX.p, o->dJw.p, o->losses.p);
-    const float w_vs = (N >= 3) ? 1.f / ((float)(N - 2) * (float)nv3) : 0.f;
-    hipLaunchKernelGGL(vert_smooth_kernel, dim3(VS_NB, nl), dim3(256), 0, st, o->VwF.p, nv3, 2, cf.frame0, N, w_vs,
-                       o->dVF.p, o->losses.p + 5);
-    if (N >= 2)
+                       w.w_rec, w.w_sm, 0.f, 0, o->dX.p, o->dJw.p, o->losses.p, kn, ctab);
+    hipLaunchKernelGGL(vert_smooth_kernel, dim3(VS_NB, nl), dim3(256), 0, st, o->VwF.p, nv3, 2, cf.frame0, N, w.w_ws,
+                       o->dVF.p, o->losses.p + 5, kn, ctab);
+    if (N >= 2 || ctab)                                      // (different lengths: a one-frame clip's workgroups leave at once)
         hipLaunchKernelGGL(foot_skate_kernel, dim3(1, nl), dim3(256), 0, st, o->VwF.p, nv3, c->contact_vid.p,
-                           nc, n_left, contact_weight, 2, cf.frame0, N, o->dVF.p, o->losses.p + 6);
+                           nc, n_left, contact_weight, 2, cf.frame0, N, o->dVF.p, o->losses.p + 6, kn, ctab);
     { int es = skin_bwd_any<false>(c->ws_skin, st, nl, c->full.model(), V, o->X.p, o->VoffF.p, o->A.p, o->M.p, o->scale.p, 2, o->dVF.p, o->dVF.p,
-                                   o->dA.p, (float*)nullptr, o->dtransl_v.p, o->dMv.p, o->dsv.p, ContactGradIn()); if (es) return es; }
+                                   o->dA.p, (float*)nullptr, o->dtransl_v.p, o->dMv.p, o->dsv.p, ContactGradIn(), kn, ctab); if (es) return es; }
     HIP_TRY(blend_backward(c->full, o->dVF.p + 2 * nv3, nl, o->dPF.p + 2 * NPFX, 0, c->ws_kpart, st));
     hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
                        o->Jrest.p, o->G.p, o->dA.p, o->dPF.p, (const float*)nullptr, o->dMv.p, o->dsv.p, o->dPF.p + NPF, NPFX,
-                       o->dtransl_v.p, o->dX.p, o->dO.p, o->dCAM.p, o->dscale_row.p, ParamLossIn(), (const float*)nullptr);
+                       o->dtransl_v.p, o->dX.p, o->dO.p, o->dCAM.p, o->dscale_row.p, ParamLossIn(), (const float*)nullptr, NJ, kn, ctab);
     { int eb = opt_vposer_backward(c, true, st); if (eb) return eb; }
     return (int)hipGetLastError();
 }
 
-int fdcap_opt_step_x(fdcap_ctx* c, int32_t step, void* stream) {
-    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
-    if (!c || !c->opt || step <= 0) return FDCAP_E_ARG;
-    { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
+int fdcap_opt_backward_local2(fdcap_ctx* c, const float* contact_weight, int32_t n_left, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_local2 only)
+    if (!c || !c->opt || !contact_weight || n_left <= 0 || n_left >= c->nc) return FDCAP_E_ARG;
+    return opt_backward_local2_impl(c, contact_weight, n_left, (hipStream_t)stream);
+}
+
+// Adam on the rows only, step number `step` (the second loop's optimiser holds body_rotation_rec alone, :536-540)
+static int opt_step_x_impl(fdcap_ctx* c, int32_t step, hipStream_t st) {
+    { int es_ = opt_sync(c, st); if (es_) return es_; }
     OptState* o = c->opt;
     o->ahead = false;
     const size_t nx = (size_t)o->cfg.n_local * XDIM;
-    hipLaunchKernelGGL(adam_kernel, dim3((nx + 255) / 256), dim3(256), 0, (hipStream_t)stream, o->X.p + 2 * XDIM,
+    hipLaunchKernelGGL(adam_kernel, dim3((nx + 255) / 256), dim3(256), 0, st, o->X.p + 2 * XDIM,
                        o->mX.p + 2 * XDIM, o->vX.p + 2 * XDIM, o->dX.p + 2 * XDIM, nx, adam_scalars(o->cfg.lr, step), 0,
                        o->dz_pending ? (const float*)o->dZpart.p : (const float*)nullptr, (size_t)o->R * VP_Z, 2);
     o->dz_pending = false;                                   // (consumed; dX itself stays without the partials: fdcap_opt_get_grads reads before the step)
     return (int)hipGetLastError();
+}
+
+int fdcap_opt_step_x(fdcap_ctx* c, int32_t step, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_local2 only)
+    if (!c || !c->opt || step <= 0) return FDCAP_E_ARG;
+    return opt_step_x_impl(c, step, (hipStream_t)stream);
+}
+
+// detect_contact (:534) and iterations [jj0, jj1) of mode 'local''s second loop (:536-556) in ONE call, for one clip or a batch of
+// clips: what FittingOP._local_second_loop issues -- fdcap_opt_detect_contact when jj0 == 0, then per iteration
+// fdcap_opt_backward_local2 + fdcap_opt_step_x(num_iter + jj + 1) -- with each launch in its clip-aware form for a batch
+// (opt_backward_local2_impl).  Logging iterations (log_every > 0: jj % log_every == 0) leave their partial sums -- slots 0, 1, 2, 5
+// and 6 -- in consecutive rows of hist_d [hist_rows][n_clips][FDCAP_NUM_LOSSES], filled without a host sync; the others in the
+// registered losses_d, which is registered again before the call returns.  flags bit 0: the stretch's last iteration is not
+// stepped (its gradients stay readable through fdcap_opt_get_grads).  Nothing here waits for the device.
+int fdcap_opt_run_local2(fdcap_ctx* c, int32_t n_left, int32_t jj0, int32_t jj1, int32_t num_iter, int32_t log_every, float* contact_weight_d,
+                         double* hist_d, int32_t hist_rows, int32_t flags, int32_t* n_logged, void* stream) {
+    if (n_logged) *n_logged = 0;
+    if (!c || !c->opt) return FDCAP_E_STATE;
+    if (n_left <= 0 || n_left >= c->nc || jj0 < 0 || jj1 < jj0 || num_iter < 0 || log_every < 0 || !contact_weight_d) return FDCAP_E_ARG;
+    OptState* o = c->opt;
+    // (a sharded context: the halo exchange between two iterations of this loop stays with the caller)
+    if (!o->contact_on || !opt_whole_clips(o) || o->dctW > 0) return FDCAP_E_STATE;
+    if (log_every > 0) {                                     // every logging iteration of the stretch has its history row
+        int rows = 0;
+        for (int jj = jj0; jj < jj1; ++jj) rows += jj % log_every == 0;
+        if (rows > 0 && (!hist_d || hist_rows < rows)) return FDCAP_E_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t hist_row = (size_t)o->nclip * FDCAP_NUM_LOSSES;
+    double* const keep = o->losses.p;
+    int k = 0, e = 0;
+    if (jj0 == 0) e = opt_detect_contact_impl(c, n_left, contact_weight_d, st);
+    for (int jj = jj0; jj < jj1 && !e; ++jj) {
+        const bool do_log = log_every > 0 && jj % log_every == 0;
+        e = fdcap_opt_set_loss_output(c, do_log ? hist_d + (size_t)k * hist_row : keep);
+        if (e) break;
+        k += do_log;
+        e = opt_backward_local2_impl(c, contact_weight_d, n_left, st);
+        if (!e && !((flags & 1) && jj + 1 == jj1)) e = opt_step_x_impl(c, num_iter + jj + 1, st);
+    }
+    {                                                        // (never leave the library pointing into the caller's history)
+        const int e2 = fdcap_opt_set_loss_output(c, keep);
+        if (!e) e = e2;
+    }
+    if (n_logged) *n_logged = k;
+    return e;
 }
 
 int fdcap_opt_get_results(fdcap_ctx* c, float* body75, float* scale, float* cam, void* stream) {

@@ -11,6 +11,12 @@
 
 #include <vector>
 
+#if defined(__HIPCC__)
+#define FDC_CLIPS_HD __host__ __device__
+#else
+#define FDC_CLIPS_HD
+#endif
+
 namespace fdc {
 
 constexpr int CLIP_XDIM = 78;      // = XDIM (fdc_frame.h; asserted where both are visible)
@@ -30,6 +36,26 @@ inline ClipWeights clip_weights(int n, const LossWeights& lw, float weight_loss_
     w.w_ws = (lw.world_on && n >= 2) ? lw.world / ((float)(n - 1) * CLIP_NJW * 3) : 0.f;         // no first difference below two
     w.coef = nc > 0 ? lw.contact * weight_contact / ((float)n * nc) : 0.f;                       // (ContactGradIn::coef)
     return w;
+}
+
+// Mode 'local', second loop (cal_loss2, global_optimization.py:536-556): its loss total has no phases and no lossconfig multipliers but
+// weight_loss_rec -- l_rec + the parameter-space second difference + the VERTEX-space second difference over all nv3 = 3 V
+// coordinates + the foot-skate term -- so its weights are a set of their own, never the phase-1 or phase-2 ones.  These are the
+// float expressions fdcap_opt_backward_local2 evaluates for a stand-alone fit of n frames.  In the returned ClipWeights (and in
+// the records built from it) w_ws carries the vertex-space weight 1 / ((n - 2) nv3) -- this loop has no world-joint term -- and
+// coef is zero (the contact term is the foot-skate one, below).
+inline ClipWeights clip_weights_local2(int n, float weight_loss_rec, size_t nv3) {
+    ClipWeights w;
+    w.w_rec = weight_loss_rec / ((float)n * CLIP_XDIM);
+    w.w_sm = (n >= 3) ? 1.f / ((float)(n - 2) * CLIP_XDIM) : 0.f;                                // no second difference below three frames
+    w.w_ws = (n >= 3) ? 1.f / ((float)(n - 2) * (float)nv3) : 0.f;
+    w.coef = 0.f;
+    return w;
+}
+// ... and the foot-skate term's 1 / ((n - 1) npart 3) of one contact part of npart vertices (:415-429; foot_skate_kernel evaluates
+// it per thread): a mean over the n - 1 first differences, so zero below two frames
+FDC_CLIPS_HD inline float clip_foot_skate_inv(int n, int npart) {
+    return (n >= 2) ? 1.f / ((float)(n - 1) * (float)npart * 3.f) : 0.f;
 }
 
 // What a per-frame kernel needs to know about its row, in ONE 32-byte record (one scalar load, requested with the kernel's first
@@ -63,18 +89,29 @@ inline std::vector<int32_t> clip_starts(int32_t n_clips, const int32_t* len) {
 
 // [rows + 4] records indexed by BUFFER row.  The halo rows (no frame of any clip) carry the neighbouring clip's index, so that a
 // kernel that covers them reads a valid `scale`, with n = 0 and zero weights: every stencil test fails and every term is zero.
-inline std::vector<ClipRow> clip_rows_build(int32_t n_clips, const int32_t* len, const LossWeights& lw, float weight_loss_rec,
-                                            float weight_contact, int nc) {
+// (w: one ClipWeights per clip)
+inline std::vector<ClipRow> clip_rows_fill(int32_t n_clips, const int32_t* len, const std::vector<ClipWeights>& w) {
     const std::vector<int32_t> s = clip_starts(n_clips, len);
     std::vector<ClipRow> rows((size_t)s[(size_t)n_clips] + 4);
     const ClipRow halo_lo = {0, 0, 0, 0.f, 0.f, 0.f, 0.f, 0}, halo_hi = {n_clips - 1, 0, 0, 0.f, 0.f, 0.f, 0.f, 0};
     rows[0] = rows[1] = halo_lo;
     rows[rows.size() - 2] = rows[rows.size() - 1] = halo_hi;
-    for (int32_t k = 0; k < n_clips; ++k) {
-        const ClipWeights w = clip_weights(len[k], lw, weight_loss_rec, weight_contact, nc);
-        for (int32_t g = 0; g < len[k]; ++g) rows[(size_t)2 + s[(size_t)k] + g] = ClipRow{k, g, len[k], w.w_rec, w.w_sm, w.w_ws, w.coef, 0};
-    }
+    for (int32_t k = 0; k < n_clips; ++k)
+        for (int32_t g = 0; g < len[k]; ++g)
+            rows[(size_t)2 + s[(size_t)k] + g] = ClipRow{k, g, len[k], w[(size_t)k].w_rec, w[(size_t)k].w_sm, w[(size_t)k].w_ws, w[(size_t)k].coef, 0};
     return rows;
+}
+inline std::vector<ClipRow> clip_rows_build(int32_t n_clips, const int32_t* len, const LossWeights& lw, float weight_loss_rec,
+                                            float weight_contact, int nc) {
+    std::vector<ClipWeights> w;
+    for (int32_t k = 0; k < n_clips; ++k) w.push_back(clip_weights(len[k], lw, weight_loss_rec, weight_contact, nc));
+    return clip_rows_fill(n_clips, len, w);
+}
+// the same records under the weights of mode 'local''s second loop (clip_weights_local2: w_ws is the vertex-space weight there)
+inline std::vector<ClipRow> clip_rows_build_local2(int32_t n_clips, const int32_t* len, float weight_loss_rec, size_t nv3) {
+    std::vector<ClipWeights> w;
+    for (int32_t k = 0; k < n_clips; ++k) w.push_back(clip_weights_local2(len[k], weight_loss_rec, nv3));
+    return clip_rows_fill(n_clips, len, w);
 }
 
 }  // namespace fdc

@@ -13,10 +13,22 @@ namespace {
 #define FDC_VS_NB 4
 #endif
 constexpr int VS_NB = FDC_VS_NB;                    // (measured at 512 frames: 1 -> 96 us, 2 -> 63, 4 -> 54, 8 -> 63, 16 -> 107, 32 -> 202: the atomics again)
+// A batch of clips (fdcap_opt_run_local2): clip_n > 0 -- clips of clip_n frames, frame0 = 0, n_total = clip_n, the frame's clip and
+// its index within it by arithmetic; ctab != nullptr -- clips of different lengths, the frame's clip, index, length and weight from
+// its record in the second loop's set of the clip table (clip_weights_local2: w_ws is this term's weight), one scalar load
+// requested ahead of the vertex loads.  The stencil is cut at the clip's first and last frame; clip k's sum goes to loss_sum + k LROW.
 __global__ void vert_smooth_kernel(const float* __restrict__ V, size_t nv3, int row0, int frame0, int n_total,
-                                   float w_over_cnt, float* __restrict__ dV, double* __restrict__ loss_sum) {
+                                   float w_over_cnt, float* __restrict__ dV, double* __restrict__ loss_sum, int clip_n = 0,
+                                   const ClipRow* __restrict__ ctab = nullptr) {
     __shared__ float sred[4];
-    const int r = row0 + blockIdx.y, g = frame0 + blockIdx.y;
+    const int r = row0 + blockIdx.y;
+    int g = frame0 + blockIdx.y, clip_k = 0;
+    if (ctab) {                                              // (kernel-uniform; wave-uniform scalar loads)
+        const clip_row_cptr cr = clip_row_at(ctab, r);
+        clip_k = cr->k; g = cr->g; n_total = cr->n; w_over_cnt = cr->w_ws;
+    } else if (clip_n > 0) {
+        clip_k = (int)blockIdx.y / clip_n; g = (int)blockIdx.y % clip_n;
+    }
     float ab = 0.f;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < nv3; e += (size_t)gridDim.x * 256) {
         const float* v = V + (size_t)r * nv3 + e;
@@ -32,7 +44,7 @@ __global__ void vert_smooth_kernel(const float* __restrict__ V, size_t nv3, int 
     ab = wave_sum(ab);
     if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = ab;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss_sum, (double)((sred[0] + sred[1]) + (sred[2] + sred[3])));
+    if (threadIdx.x == 0) atomicAdd(loss_sum + (size_t)clip_k * LROW, (double)((sred[0] + sred[1]) + (sred[2] + sred[3])));
 }
 
 // mode 'local', cal_loss2 (:415-429): foot-skate term  mean|dL * w_left| + mean|dR * w_right| on the first
@@ -40,22 +52,34 @@ __global__ void vert_smooth_kernel(const float* __restrict__ V, size_t nv3, int 
 // vid[c] = mesh vertex of contact slot c in the CALLER's order (first n_left = left part); wgt[N] per frame.
 __global__ void foot_skate_kernel(const float* __restrict__ V, size_t nv3, const int* __restrict__ vid, int nc,
                                   int n_left, const float* __restrict__ wgt, int row0, int frame0, int n_total,
-                                  float* __restrict__ dV, double* __restrict__ loss_sum) {
+                                  float* __restrict__ dV, double* __restrict__ loss_sum, int clip_n = 0,
+                                  const ClipRow* __restrict__ ctab = nullptr) {
     // (grid (1, frames) since late r5: one atomic per frame instead of one per 256 elements)
+    // A batch of clips (clip_n / ctab as in vert_smooth_kernel): wgt is [frames of the batch] in buffer-row order, so pair
+    // (i, i + 1) reads the weight of the next ROW -- a frame of the same clip, since the pair exists only while i + 1 < the clip's
+    // length; clip k's sum goes to loss_sum + k LROW.  A clip of one frame has no pair: its row is left as it is.
     __shared__ float sred[4];
-    const int r = row0 + blockIdx.y, g = frame0 + blockIdx.y;
+    const int r = row0 + blockIdx.y;
+    int g = frame0 + blockIdx.y, clip_k = 0, wi = g;         // wi: this frame's weight
+    if (ctab) {                                              // (kernel-uniform; wave-uniform scalar loads)
+        const clip_row_cptr cr = clip_row_at(ctab, r);
+        clip_k = cr->k; g = cr->g; n_total = cr->n; wi = (int)blockIdx.y;
+    } else if (clip_n > 0) {
+        clip_k = (int)blockIdx.y / clip_n; g = (int)blockIdx.y % clip_n; wi = (int)blockIdx.y;
+    }
+    if (n_total < 2) return;                                 // (workgroup-uniform; a stand-alone fit of one frame never launches this)
     float ab = 0.f;
     for (int t = blockIdx.x * 256 + threadIdx.x; t < nc * 3; t += gridDim.x * 256) {
         const int c = t / 3, k = t % 3;
         const bool is_left = c < n_left;
         const int npart = is_left ? n_left : nc - n_left;
-        const float inv = 1.f / ((float)(n_total - 1) * (float)npart * 3.f);
+        const float inv = clip_foot_skate_inv(n_total, npart);
         const size_t e = (size_t)vid[c] * 3 + k;
         const float* v = V + (size_t)r * nv3 + e;
         float grad = 0.f;
         // weight_right = w, weight_left = 1 - w, both zeroed below 0.5 (:418-422); pair (i, i+1) uses w[i+1]
         if (g + 1 < n_total) {
-            float w = wgt[g + 1];
+            float w = wgt[wi + 1];
             w = is_left ? 1.f - w : w;
             w = w < 0.5f ? 0.f : w;
             float d = (v[0] - v[nv3]) * w;
@@ -63,7 +87,7 @@ __global__ void foot_skate_kernel(const float* __restrict__ V, size_t nv3, const
             grad += sgn(d) * w;
         }
         if (g >= 1) {
-            float w = wgt[g];
+            float w = wgt[wi];
             w = is_left ? 1.f - w : w;
             w = w < 0.5f ? 0.f : w;
             grad -= sgn((v[-(ptrdiff_t)nv3] - v[0]) * w) * w;
@@ -73,7 +97,7 @@ __global__ void foot_skate_kernel(const float* __restrict__ V, size_t nv3, const
     ab = wave_sum(ab);
     if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = ab;
     __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(loss_sum, (double)((sred[0] + sred[1]) + (sred[2] + sred[3])));
+    if (threadIdx.x == 0) atomicAdd(loss_sum + (size_t)clip_k * LROW, (double)((sred[0] + sred[1]) + (sred[2] + sred[3])));
 }
 
 // detect_contact (:355-364): per frame, mean squared NN distance of the left part and left / (left + left)
@@ -112,13 +136,22 @@ __global__ __launch_bounds__(128) void param_loss_kernel(const float* __restrict
                                                          int row0, int frame0, int n_total, float w_rec_over_cnt,
                                                          float w_sm_over_cnt, float w_ws_over_cnt, int world_grad,
                                                          float* __restrict__ dX, float* __restrict__ dJw,
-                                                         double* __restrict__ losses, int clip_n = 0) {
+                                                         double* __restrict__ losses, int clip_n = 0,
+                                                         const ClipRow* __restrict__ ctab = nullptr) {
     // (clip_n > 0: rows of a batch of clips of clip_n frames, frame0 = 0, n_total = clip_n -- the stencils are cut at clip
-    //  boundaries; a batch never takes this kernel's summed losses, its logged sums come from loss_rows)
+    //  boundaries.  ctab != nullptr: clips of different lengths -- the frame's clip, its index within it, the clip's length and the
+    //  two parameter-space weights come from the frame's record, requested with the row's first loads.  Clip k's sums go to
+    //  losses + k LROW: mode 'local''s second loop; mode 'global' never takes a batch's summed losses from here, its logged sums
+    //  come from loss_rows)
     __shared__ float sred[2][4];
     const int tid = threadIdx.x;
     const int r = row0 + blockIdx.x;
-    const int g = clip_n > 0 ? (int)blockIdx.x % clip_n : frame0 + (int)blockIdx.x;
+    int g = clip_n > 0 ? (int)blockIdx.x % clip_n : frame0 + (int)blockIdx.x, clip_k = clip_n > 0 ? (int)blockIdx.x / clip_n : 0;
+    if (ctab) {                                              // (kernel-uniform; wave-uniform scalar loads)
+        const clip_row_cptr cr = clip_row_at(ctab, r);
+        clip_k = cr->k; g = cr->g; n_total = cr->n;
+        w_rec_over_cnt = cr->w_rec; w_sm_over_cnt = cr->w_sm;
+    }
     float rec = 0.f, sm = 0.f, ws = 0.f, vp = 0.f;
     if (tid < XDIM) {
         const float* x = X + (size_t)r * XDIM + tid;
@@ -147,7 +180,7 @@ __global__ __launch_bounds__(128) void param_loss_kernel(const float* __restrict
     __syncthreads();
     if (tid < 4) {
         const int slot[4] = {0, 1, 2, 4};
-        atomicAdd(&losses[slot[tid]], (double)(sred[0][tid] + sred[1][tid]));
+        atomicAdd(&losses[(size_t)clip_k * LROW + slot[tid]], (double)(sred[0][tid] + sred[1][tid]));
     }
 }
 

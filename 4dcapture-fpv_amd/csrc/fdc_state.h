@@ -85,14 +85,16 @@ struct OptState {
     // share of one: nclip = 1, clip_len = n_total).  Each clip has its own scale / moments / dscale / losses slot.
     int nclip = 1, clip_len = 0;
     // clips of DIFFERENT lengths (fdcap_opt_create_clips_var, fdc_clips.h): clip k has clip_lens[k] frames in rows 2 + clip_start[k] ..;
-    // clip_len = 0.  The kernels then take clip_n = 0 and the device tables: clip_rows [2][R] ClipRow -- one record per buffer row
-    // with the clip's weights of phase 1, then of phase 2 (the only two weight sets mode 'global' has: built once per create, so
-    // no upload in the loop) -- and clip_span [nclip][2] {start, length} for the per-clip tail workgroups.
+    // clip_len = 0.  The kernels then take clip_n = 0 and the device tables: clip_rows [3][R] ClipRow -- one record per buffer row
+    // with the clip's weights of phase 1, then of phase 2 (the only two weight sets mode 'global' has), then of mode 'local''s
+    // second loop (clip_weights_local2); built once per create, so no upload in the loop -- and clip_span [nclip][2]
+    // {start, length} for the per-clip tail workgroups.
     bool ragged = false;
     std::vector<int32_t> clip_lens, clip_start;
     DevBuf<ClipRow> clip_rows;
     DevBuf<int> clip_span;
     const ClipRow* ctab(bool phase2) const { return ragged ? clip_rows.p + (phase2 ? (size_t)R : 0) : nullptr; }
+    const ClipRow* ctab_local2() const { return ragged ? clip_rows.p + (size_t)2 * R : nullptr; }
     const int* cspan() const { return ragged ? clip_span.p : nullptr; }
     // what the kernels take as clip_n (clip_of_row, fdc_loss.h): 0 unless the optimiser holds several clips of one length
     int kclip_n() const { return nclip > 1 ? clip_len : 0; }

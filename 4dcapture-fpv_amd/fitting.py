@@ -883,9 +883,13 @@ class ClipBatchFitter:
 
     The fitter owns ONE context for its whole life -- the persistent worker: the body model and the contact ids are registered
     once, a scene once per run of batches of that scene (`fit(..., scene_key=...)` skips the registration when the key is the
-    previous batch's).  Mode 'global' only."""
+    previous batch's).
 
-    def __init__(self, fittingconfig, lossconfig, body_model=None, vposer=None, contact_ids=None, legacy_zero_grad=False):
+    Modes 'global' and 'local' (`fit(..., mode=...)`).  Mode 'local' runs its first loop as fdcap_opt_run under the 'local' config
+    and its second loop -- detect_contact and the cal_loss2 iterations (:534-556) -- as ONE fdcap_opt_run_local2 call; it leaves
+    each clip's second-loop log in self.logs2 and detect_contact's weights in self.contact_weights."""
+
+    def __init__(self, fittingconfig, lossconfig, body_model=None, vposer=None, contact_ids=None, legacy_zero_grad=False, n_left=None):
         import torch
         cfg = dict(DEFAULT_FITTINGCONFIG)
         cfg.update(fittingconfig or {})
@@ -907,10 +911,15 @@ class ClipBatchFitter:
         if contact_ids is None:
             contact_ids = np.concatenate([io.read_contact_ids(self.contact_id_folder, [p]) for p in self.contact_part])
         self.vid = np.asarray(contact_ids, dtype=np.int64)
+        # mode 'local' treats the two contact parts separately (L_Leg ids first, :341-347), as FittingOP
+        self.n_left = int(n_left) if n_left is not None else len(self.vid) // 2
         self.ctx.set_contact_ids(self.vid)
         self.scene_key = None
         self._has_opt = False
+        self._mode = "global"
         self.logs = []
+        self.logs2 = []
+        self.contact_weights = []
         self.idx1 = []
 
     def _destroy_opt(self):
@@ -927,20 +936,30 @@ class ClipBatchFitter:
         self.ctx.set_scene(np.zeros((0, 3), np.float32) if scene_verts is None else scene_verts)
         self.scene_key = key
 
-    def fit(self, clips, scene_verts=None, scene_key=None, log_every=0):
+    def fit(self, clips, scene_verts=None, scene_key=None, log_every=0, mode="global"):
         """clips: sequence of K (body_data [N_k,75], camera_ext [N_k,4,4]) pairs (numpy or device tensors); every clip has its own N_k.
         scene_verts / scene_key: the batch's scene (see set_scene; both None: the registered scene).
+        mode: 'global' or 'local' (the reference's default, :491).
         Returns a list of K (body_rec [N_k,75] device tensor, scale numpy scalar, camera_ext [N_k,4,4] device tensor) -- what
-        FittingOP.fitting returns for each clip -- and leaves each clip's FitLog in self.logs, its outlier rows in self.idx1."""
+        FittingOP.fitting returns for each clip -- and leaves each clip's FitLog in self.logs, its outlier rows in self.idx1; mode
+        'local' also each clip's second-loop rows [jj, l_rec, l_loc, l_sm, l_cs, total] (FittingOP.log2, the means over the clip's
+        own frames) in self.logs2 and detect_contact's per-frame weights in self.contact_weights."""
+        if mode not in ("global", "local"):
+            raise ValueError("a batch of clips fits in mode 'global' or 'local' (mode 'dct' is FittingOP's)")
         if scene_verts is not None or scene_key is not None:
             self.set_scene(scene_verts, scene_key)
-        self.prepare(clips)
+        self.prepare(clips, mode)
         return self.run(log_every)
 
-    def prepare(self, clips):
-        """init() of a batch (:450-489 per clip): creates the batch's optimiser on the registered scene and stages its inputs."""
+    def prepare(self, clips, mode="global"):
+        """init() of a batch (:450-489 per clip): creates the batch's optimiser on the registered scene and stages its inputs.
+        mode 'local': the config of its first loop (:511, :523), as FittingOP.init builds it."""
         import ctypes
         import torch
+        if mode not in ("global", "local"):
+            raise ValueError("a batch of clips fits in mode 'global' or 'local' (mode 'dct' is FittingOP's)")
+        self._mode = mode
+        local = mode == "local"
         K = len(clips)
         if K < 1:
             raise ValueError("a batch needs at least one clip")
@@ -971,8 +990,8 @@ class ClipBatchFitter:
         # one length: the clip's frames, as fdcap_opt_create_clips takes it; different lengths: the batch's rows
         n_cfg = lens[0] if equal else total
         oc = capi.OptConfig(n_cfg, n_cfg, 0, float(self.init_lr_h), float(self.weight_loss_rec), float(self.weight_loss_vposer),
-                            float(self.weight_contact), PHASE1_CONTACT, PHASE1_SMOOTH, PHASE2_WORLD, PHASE2_SMOOTH, SCALE_INIT,
-                            int(self.legacy_zero_grad))
+                            float(self.weight_contact), LOCAL_PHASE1_CONTACT if local else PHASE1_CONTACT, PHASE1_SMOOTH,
+                            0.0 if local else PHASE2_WORLD, PHASE2_SMOOTH, SCALE_INIT, int(self.legacy_zero_grad))
         R = total + 4
         self._rows_x = torch.zeros(R, capi.XDIM, device=dev)
         self._rows_cam = torch.zeros(R, 16, device=dev)
@@ -1022,6 +1041,36 @@ class ClipBatchFitter:
             if logged:
                 capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
         assert n_done.value == len(logged)
+        local = self._mode == "local"
+        self.logs2, self.contact_weights = [], []
+        if local:
+            # detect_contact + the cal_loss2 loop (:534-556) of every clip in one call; its history is read back once, below
+            n2 = int(LOCAL_SECOND_LOOP * num_iter)
+            logged2 = [jj for jj in range(n2) if log_every and jj % log_every == 0]
+            hist2 = torch.zeros(max(len(logged2), 1), K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
+            weight = torch.empty(total, device=dev)
+            try:
+                capi.check(lib.fdcap_opt_run_local2(h, self.n_left, 0, n2, num_iter, int(log_every or 0), capi.dptr(weight),
+                                                    capi.dptr(hist2) if logged2 else None, len(logged2), 0, ctypes.byref(n_done), st),
+                           "fdcap_opt_run_local2")
+            finally:
+                capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
+            assert n_done.value == len(logged2)
+            rows2 = hist2.cpu().numpy()
+            self.contact_weights = [weight[starts[k]:starts[k + 1]] for k in range(K)]
+            nv3 = 3 * self.ctx.num_verts
+            with np.errstate(divide="ignore", invalid="ignore"):     # (a mean over nothing prints as NaN, as in a stand-alone fit)
+                for k in range(K):
+                    n = np.float64(lens[k])
+                    log2 = []
+                    for j, jj in enumerate(logged2):
+                        s = rows2[j, k]
+                        l_rec = self.weight_loss_rec * s[0] / (n * capi.XDIM)
+                        l_loc = s[2] / ((n - 2) * capi.XDIM)
+                        l_sm = s[5] / ((n - 2) * nv3)
+                        l_cs = s[6]
+                        log2.append([jj, l_rec, l_loc, l_sm, l_cs, l_sm + l_loc + l_rec + l_cs])
+                    self.logs2.append(log2)
         body_rec = torch.empty(total, capi.PDIM, device=dev)
         scale = torch.empty(K, device=dev)
         cam = torch.empty(total, 16, device=dev)
@@ -1033,7 +1082,7 @@ class ClipBatchFitter:
             for j, ii in enumerate(logged):
                 # (the printed means of a clip run over its own frames)
                 l_rec, l_vp, l_sm, l_con, l_ws, tot = logged_losses(rows[j, k], lens[k], self.ctx.num_contact, self.weight_loss_rec,
-                                                                    self.weight_loss_vposer, self.weight_contact, ii >= P)
+                                                                    self.weight_loss_vposer, self.weight_contact, ii >= P, local)
                 log.iters.append(ii); log.l_rec.append(l_rec); log.l_vposer.append(l_vp)
                 log.loss_smoothing.append(l_sm); log.loss_contact.append(l_con)
                 log.loss_world_smoothing.append(l_ws); log.total.append(tot)

@@ -247,8 +247,10 @@ int fdcap_opt_create(fdcap_ctx* ctx, const fdcap_opt_config* cfg, float* rows_x_
  * gradient's sum may differ.  The batch takes the single-GPU schedule (deferred row step, `scale` stepped by the backward's tail).
  * Calls that cover the optimiser's rows cover all n_clips*N of them (fdcap_opt_get_results, fdcap_opt_forward_world,
  * fdcap_opt_get_contact, fdcap_opt_get_grads, launch timing); fdcap_opt_get_results writes n_clips scales; the state of
- * fdcap_opt_export_state holds n_clips scale moments; fdcap_opt_run's history rows are [n_clips][FDCAP_NUM_LOSSES].  With
- * n_clips > 1 these return FDCAP_E_STATE: mode 'local' (fdcap_opt_detect_contact, fdcap_opt_backward_local2), mode 'dct'
+ * fdcap_opt_export_state holds n_clips scale moments; fdcap_opt_run's history rows are [n_clips][FDCAP_NUM_LOSSES].
+ * Modes: 'global', and 'local' -- its first loop is fdcap_opt_run under the 'local' config (phase1_contact = 0.2, phase2_world = 0),
+ * its second loop fdcap_opt_run_local2, the ONE call through which a batch reaches detect_contact and cal_loss2.  With
+ * n_clips > 1 these return FDCAP_E_STATE: mode 'local''s single steps (fdcap_opt_detect_contact, fdcap_opt_backward_local2), mode 'dct'
  * (fdcap_opt_set_dct .. fdcap_opt_set_dct_state), the per-frame inner fit (fdcap_opt_set_keypoints, fdcap_opt_backward_fit2d,
  * fdcap_opt_step_x, fdcap_opt_fit2d_lbfgs[_stats]), fdcap_opt_forward_ahead and the exchange calls (fdcap_opt_step_rows_and_pack,
  * fdcap_opt_unpack_and_step_scale, fdcap_opt_halo_exchange, fdcap_opt_exchange, fdcap_opt_time_exchange, fdcap_opt_run with
@@ -341,6 +343,30 @@ int fdcap_opt_detect_contact(fdcap_ctx* ctx, int32_t n_left, float* weight_left_
 int fdcap_opt_backward_local2(fdcap_ctx* ctx, const float* contact_weight_d, int32_t n_left, void* stream);
 /* Adam on body_rotation_rec only, with its running step count `step` (continues after the first loop). */
 int fdcap_opt_step_x(fdcap_ctx* ctx, int32_t step, void* stream);
+/* detect_contact (:534) and iterations [jj0, jj1) of mode 'local''s second loop (:536-556) in ONE call, for one clip or a BATCH of
+ * clips (fdcap_opt_create_clips[_var]); call it after the first loop (fdcap_opt_run under the 'local' config) of num_iter iterations.
+ *   contact_weight_d [n_local]: one weight per owned frame, in buffer-row order across the whole batch.  jj0 == 0: the call first
+ *     runs detect_contact (pose forward, contact forward, left / (left + left) per frame) and WRITES it; jj0 > 0: it is an input
+ *     (a resumed loop; a caller's own weights).
+ *   Iteration jj: the launches of fdcap_opt_backward_local2, then fdcap_opt_step_x with Adam step number num_iter + jj + 1 -- for
+ *     one clip the same launches and the same bits as those two calls.  For a batch every launch takes its clip-aware form: each
+ *     clip's means run over its OWN frame count (w_rec = weight_loss_rec / (n 78), 1 / ((n - 2) 78), 1 / ((n - 2) 3V), the
+ *     foot-skate 1 / ((n - 1) npart 3); no second difference below three frames, no first difference below two), the stencils
+ *     end at the clip's first and last frame (foot-skate pair (i, i + 1) uses w[i + 1] of the same clip), every row reads its own
+ *     clip's `scale`, and the sums go to the clip's own losses[k][].  A clip's results equal its stand-alone mode-'local' fit bit
+ *     for bit when both select the same kernel forms.  The full-mesh buffers hold [rows + 4, 3V] floats, three of them.
+ *   Logging iterations (log_every > 0: jj % log_every == 0) leave their partial sums -- slots [0] rec, [1] z^2, [2] parameter
+ *     smoothing, [5] vertex smoothing, [6] foot skate (normalised per part), as fdcap_opt_backward_local2 -- in consecutive rows of
+ *     hist_d [hist_rows][n_clips][FDCAP_NUM_LOSSES] on the device, *n_logged of them, with no host sync (they are sums of
+ *     per-workgroup partials added with atomics: equal to a stand-alone fit's to rounding, not bit for bit); the other iterations
+ *     use the registered losses_d, which is registered again before the call returns.
+ *   flags bit 0: the LAST iteration of the stretch is not stepped -- its gradients stay readable through fdcap_opt_get_grads.
+ * FDCAP_E_ARG: n_left <= 0 or >= the contact count, jj0 < 0, jj1 < jj0, contact_weight_d NULL, a stretch with logging iterations
+ * and hist_d NULL or fewer than that many hist_rows.  FDCAP_E_STATE: no optimiser, no contact set, a DCT term set up, or a
+ * sharded context (n_local != n_total: the halo exchange between two iterations stays with the caller, who issues the single
+ * steps).  Returns when the work is enqueued. */
+int fdcap_opt_run_local2(fdcap_ctx* ctx, int32_t n_left, int32_t jj0, int32_t jj1, int32_t num_iter, int32_t log_every,
+                         float* contact_weight_d, double* hist_d, int32_t hist_rows, int32_t flags, int32_t* n_logged, void* stream);
 
 /* ---- mode 'dct' (global_optimization.py:595-630) ---------------------------------
  * cal_dctloss (:232-246) over W = n_total / T windows of T frames (reference: 5 x 60, :41-42) and the 23

@@ -10,7 +10,12 @@ Prints one JSON line (profiles/r7_multiclip300.json).
 --lengths n0,n1,... (may be repeated): instead of the sweep, a batch of clips of THOSE lengths (fdcap_opt_create_clips_var when they
 differ) under the same protocol -- one warm-up fit, R timed fits that end in a synchronise -- with ms per batch, us per iteration,
 frames/s and the live per-launch table; one entry per --lengths, all on one fitter.
-usage: python tools/multiclip_throughput.py [--reps R] [--out FILE] [--lengths n0,n1,...]..."""
+--mode local: instead of the sweep, mode 'local' (first loop + detect_contact + the 0.4 x 500 iterations of the second loop over
+all 10 475 vertices): K = 1 and K = 3 clips of 300 frames through ClipBatchFitter.fit(mode='local') against K sequential stand-alone
+FittingOP mode-'local' fits in the same process (their contexts built before the clock starts) -- one warm-up each, then R rounds
+that alternate the two, each timed by the host clock around fits that end with the results on the host; medians, clips/s and the
+ratio (profiles/multiclip300_local.json).
+usage: python tools/multiclip_throughput.py [--reps R] [--out FILE] [--mode local] [--lengths n0,n1,...]..."""
 import json
 import os
 import sys
@@ -28,9 +33,11 @@ N, ITERS, NS, KS = 300, 500, 500_000, (1, 2, 3, 4, 6, 8)
 
 def main():
     argv = sys.argv[1:]
-    reps, out, lengths = 3, None, []
+    reps, out, lengths, mode = 3, None, [], "global"
     while argv:
-        if argv[0] == "--reps":
+        if argv[0] == "--mode" and len(argv) > 1 and argv[1] in ("global", "local"):
+            mode, argv = argv[1], argv[2:]
+        elif argv[0] == "--reps":
             reps, argv = int(argv[1]), argv[2:]
         elif argv[0] == "--out":
             out, argv = argv[1], argv[2:]
@@ -48,6 +55,10 @@ def main():
     scene = synth.make_scene(NS, seed=2)
     left, right = synth.make_contact_ids(bm.v_template, per_part=250, seed=4)
     vid = np.concatenate([left, right])
+    if mode == "local":
+        if lengths:
+            raise SystemExit("--mode local measures clips of 300 frames: not with --lengths")
+        return local_mode(reps, out, bm, vp, scene, vid)
     if lengths:
         return ragged(lengths, reps, out, bm, vp, scene, vid)
     clips = []
@@ -151,6 +162,65 @@ def ragged(lengths, reps, out, bm, vp, scene, vid):
         res["batches"].append(entry)
         print(f"lengths {lens}: {dt * 1e3:8.2f} ms per batch  {rows / dt:9.0f} frames/s", file=sys.stderr, flush=True)
     fitter.close()
+    res["device"] = torch.cuda.get_device_name(0)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out:
+        with open(out, "w") as fh:
+            fh.write(line + "\n")
+
+
+def local_mode(reps, out, bm, vp, scene, vid):
+    """K = 1 and K = 3 clips of N frames in mode 'local': one batch against K stand-alone fits, alternating."""
+    from fdcap_amd import synth
+    from fdcap_amd.fitting import LOCAL_SECOND_LOOP, ClipBatchFitter, FittingOP
+    from fdcap_amd.io import read_camerapose
+    clips = []
+    for k in range(3):
+        c = synth.make_clip(N, seed=100 + k)
+        clips.append((c.body_params, read_camerapose(c.camerapose_lines)))
+    fitter = ClipBatchFitter({"num_iter": ITERS}, {}, body_model=bm, vposer=vp, contact_ids=vid)
+    fitter.set_scene(scene)
+    fops = [FittingOP({"num_iter": ITERS}, {}, N, body_model=bm, vposer=vp, scene_verts=scene, contact_ids=vid, camera_ext=cam)
+            for _, cam in clips]
+    bodies = [torch.tensor(body).cuda() for body, _ in clips]
+
+    def batch(K):
+        t0 = time.perf_counter()
+        r = [(b.cpu(), s, c.cpu()) for b, s, c in fitter.fit(clips[:K], mode="local")]
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    def alone(K):
+        t0 = time.perf_counter()
+        r = []
+        for k in range(K):
+            b, s, c = fops[k].fitting(bodies[k], "local")
+            r.append((b.cpu(), s, c.cpu()))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    res = {"problem": {"verts": 10475, "contacts": len(vid), "scene": NS, "frames_per_clip": N, "iters": ITERS,
+                       "second_loop_iters": int(LOCAL_SECOND_LOOP * ITERS), "mode": "local", "reps": reps}, "sweep": []}
+    for K in (1, 3):
+        _, rb = batch(K)
+        _, ra = alone(K)
+        # (same forms or not, the two must agree closely: the measurement compares two ways to the same result)
+        worst = max(float((b[0] - a[0]).abs().max()) for b, a in zip(rb, ra))
+        tb, ta = [], []
+        for _ in range(reps):
+            tb.append(batch(K)[0])
+            ta.append(alone(K)[0])
+        mb, ma = float(np.median(tb)), float(np.median(ta))
+        res["sweep"].append({"K": K, "rows": K * N, "batch_ms": mb * 1e3, "batch_ms_all": [t * 1e3 for t in tb],
+                             "stand_alone_ms": ma * 1e3, "stand_alone_ms_all": [t * 1e3 for t in ta],
+                             "batch_clips_per_s": K / mb, "stand_alone_clips_per_s": K / ma, "batch_over_stand_alone": ma / mb,
+                             "max_abs_body_difference": worst})
+        print(f"K {K}: batch {mb * 1e3:8.2f} ms ({K / mb:6.2f} clips/s)  stand-alone x{K} {ma * 1e3:8.2f} ms ({K / ma:6.2f} clips/s)  "
+              f"ratio {ma / mb:5.2f}", file=sys.stderr, flush=True)
+    fitter.close()
+    for f in fops:
+        f.close()
     res["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(res)
     print(line, flush=True)
