@@ -119,6 +119,10 @@ SYMBOLS = {
     "fdcap_opt_get_dct_state": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_set_dct_state": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_dct_windows": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
+    "fdcap_opt_set_dct_clips": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "fdcap_opt_dct_clip_windows": (c_int32, [c_void_p, POINTER(c_int32), c_int32]),
+    "fdcap_opt_run_dct": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float, c_int32, c_void_p, c_void_p,
+                                    c_int32, c_int32, c_void_p, c_void_p]),
     "fdcap_frame_smoother": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_float, c_float,
                                         c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "fdcap_opt_set_keypoints": (c_int32, [c_void_p, c_void_p, c_void_p]),

@@ -24,19 +24,68 @@ int fdcap_opt_set_dct(fdcap_ctx* c, const float* dct_mtx, int32_t T, int32_t C, 
     return FDCAP_OK;
 }
 
-int fdcap_opt_dct_fit(fdcap_ctx* c, int32_t iters, int32_t step0, float weight, float* obj_hist, int32_t log_stride,
-                      void* stream) {
-    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
-    if (!c || !c->opt || iters < 0 || step0 < 0 || (obj_hist && log_stride <= 0)) return FDCAP_E_ARG;
-    { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }
+// Mode 'dct' for whole clips (fdcap_opt_create_clips[_var], or one clip): the window table, each clip's first window, the zero row of
+// the clips' objective weights and -- clips of different lengths -- the fourth record set, under the second phase's weights
+// (:620: rec 0.5, contact 0.1; fdcap_opt_run_dct refuses other multipliers on such a batch, it never replaces them).  One clip
+// takes fdcap_opt_set_dct's state and, from then on, the launches of a stand-alone fit.
+int fdcap_opt_set_dct_clips(fdcap_ctx* c, const float* dct_mtx, int32_t T, int32_t C, const float* c_dct_d, void* stream) {
+    if (!c || !c->opt) return FDCAP_E_STATE;
+    OptState* o = c->opt;
+    if (!opt_whole_clips(o)) return FDCAP_E_STATE;       // (a shard of a clip: FittingOP's loop, window by window)
+    if (!dct_mtx || !c_dct_d || T <= 0 || T > DCT_MAXT || C <= 0 || C > DCT_MAXC) return FDCAP_E_ARG;
+    if (o->nclip == 1) return fdcap_opt_set_dct(c, dct_mtx, T, C, c_dct_d, stream);
+    const int K = o->nclip;
+    const int32_t* len = o->clip_lens.data();
+    for (int k = 0; k < K; ++k) if (len[k] / T <= 0) return FDCAP_E_ARG;        // (every clip has a window, as a stand-alone fit must)
+    hipStream_t st = (hipStream_t)stream;
+    o->dct_wstart_h = dct_window_starts(K, len, T);
+    const std::vector<DctWindow> tab = dct_window_table(K, len, T);
+    const int W = o->dct_wstart_h[(size_t)K];
+    const size_t n = (size_t)W * 69 * C;
+    HIP_TRY(o->dctD.upload(dct_mtx, (size_t)T * C));
+    HIP_TRY(o->dct_wtab.upload(tab.data(), tab.size()));
+    HIP_TRY(o->dct_wstart.upload(o->dct_wstart_h.data(), o->dct_wstart_h.size()));
+    HIP_TRY(o->dct_wk.ensure((size_t)3 * K));
+    HIP_TRY(hipMemsetAsync(o->dct_wk.p, 0, (size_t)3 * K * sizeof(float), st));
+    for (int s = 0; s < 3; ++s) o->dct_wk_weight[s] = 0.f;
+    o->dct_lw = dct_phase2_weights(0.f, 0.5f, 0.1f);
+    if (o->ragged) {
+        const std::vector<ClipRow> rows = clip_rows_build_dct2(K, len, o->dct_lw.rec, o->dct_lw.contact, o->cfg.weight_loss_rec, o->cfg.weight_contact, c->nc);
+        if (rows.size() != (size_t)o->R) return FDCAP_E_STATE;
+        HIP_TRY(o->clip_rows_dct.upload(rows.data(), rows.size()));
+    }
+    HIP_TRY(o->dctCoef.ensure(n));
+    HIP_TRY(o->dctM.ensure(n));
+    HIP_TRY(o->dctV.ensure(n));
+    HIP_TRY(hipMemcpyAsync(o->dctCoef.p, c_dct_d, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(o->dctM.p, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o->dctV.p, 0, n * sizeof(float), st));
+    o->dctT = T; o->dctC = C; o->dctW = W;
+    o->dct_clips = true;
+    return FDCAP_OK;
+}
+
+// each clip's first window in c_dct, starts[n_clips + 1] (the last entry: fdcap_opt_dct_windows' total); n = n_clips + 1
+int fdcap_opt_dct_clip_windows(fdcap_ctx* c, int32_t* starts, int32_t n) {
+    if (!c || !c->opt || c->opt->dctW <= 0) return FDCAP_E_STATE;
+    const OptState* o = c->opt;
+    if (!starts || n != o->nclip + 1) return FDCAP_E_ARG;
+    if (o->dct_clips) for (int k = 0; k < n; ++k) starts[k] = o->dct_wstart_h[(size_t)k];
+    else { starts[0] = 0; starts[1] = o->dctW; }
+    return FDCAP_OK;
+}
+
+// `iters` Adam iterations on c_dct from step counter step0 in ONE launch: one clip (or one rank's windows of one), or every window
+// of a batch (fdcap_opt_run_dct) through the window table
+static int opt_dct_fit_impl(fdcap_ctx* c, int32_t iters, int32_t step0, float weight, float* obj_hist, int32_t log_stride, hipStream_t st) {
+    { int es_ = opt_sync(c, st); if (es_) return es_; }
     OptState* o = c->opt;
     if (o->dctW <= 0) return FDCAP_E_STATE;
-    hipStream_t st = (hipStream_t)stream;
     const fdcap_opt_config& cf = o->cfg;
     const int T = o->dctT;
-    // windows that lie completely inside this rank's frames (the caller shards on window boundaries)
-    const int w0 = (cf.frame0 + T - 1) / T;
-    const int w1 = std::min((cf.frame0 + cf.n_local) / T, o->dctW);
+    // windows that lie completely inside this rank's frames (the caller shards on window boundaries); a batch: all of them
+    const int w0 = o->dct_clips ? 0 : (cf.frame0 + T - 1) / T;
+    const int w1 = o->dct_clips ? o->dctW : std::min((cf.frame0 + cf.n_local) / T, o->dctW);
     if (iters == 0 || w1 <= w0) return FDCAP_OK;
     // weight 0: every gradient is exactly zero whatever the trajectories are (Adam coasts on its moments: the torch < 2
     // zero_grad semantics of a frozen c_dct) -- no forward needed
@@ -50,23 +99,39 @@ int fdcap_opt_dct_fit(fdcap_ctx* c, int32_t iters, int32_t step0, float weight, 
     for (int i = 0; i < iters; ++i) o->adam_tab_h[i] = adam_scalars(cf.lr, step0 + i + 1);
     HIP_TRY(o->adam_tab.ensure(iters));
     HIP_TRY(hipMemcpyAsync(o->adam_tab.p, o->adam_tab_h.data(), (size_t)iters * sizeof(AdamScalars), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(dct_fit_kernel, dim3((w1 - w0) * 69), dim3(64), 0, st, o->Jw.p, 2 + (w0 * T - cf.frame0), T, o->dctC,
-                       o->dctD.p, o->dctCoef.p, o->dctM.p, o->dctV.p, w0, o->adam_tab.p, iters,
-                       weight / (69.f * (float)o->dctW), obj_hist, log_stride > 0 ? log_stride : 1);
+    if (o->dct_clips) {
+        const float* wk = nullptr;
+        { int ew = opt_dct_clip_weights(o, 1, weight, st, &wk); if (ew) return ew; }
+        hipLaunchKernelGGL(dct_fit_clips_kernel, dim3(o->dctW * 69), dim3(64), 0, st, o->Jw.p, o->dct_wtab.p, T, o->dctC, o->dctD.p, o->dctCoef.p,
+                           o->dctM.p, o->dctV.p, o->adam_tab.p, iters, wk, obj_hist, log_stride > 0 ? log_stride : 1);
+    } else
+        hipLaunchKernelGGL(dct_fit_kernel, dim3((w1 - w0) * 69), dim3(64), 0, st, o->Jw.p, 2 + (w0 * T - cf.frame0), T, o->dctC,
+                           o->dctD.p, o->dctCoef.p, o->dctM.p, o->dctV.p, w0, o->adam_tab.p, iters,
+                           weight / (69.f * (float)o->dctW), obj_hist, log_stride > 0 ? log_stride : 1);
     return (int)hipGetLastError();
 }
 
-int fdcap_opt_backward_dct(fdcap_ctx* c, float w_dct, float w_rec, float w_contact, int32_t log_terms, void* stream) {
-    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
-    if (!c || !c->opt) return FDCAP_E_STATE;
+int fdcap_opt_dct_fit(fdcap_ctx* c, int32_t iters, int32_t step0, float weight, float* obj_hist, int32_t log_stride,
+                      void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_dct only)
+    if (!c || !c->opt || iters < 0 || step0 < 0 || (obj_hist && log_stride <= 0)) return FDCAP_E_ARG;
+    return opt_dct_fit_impl(c, iters, step0, weight, obj_hist, log_stride, (hipStream_t)stream);
+}
+
+// one backward of the second phase's loss (:620) for one clip, one rank's share of one, or a batch (fdcap_opt_run_dct)
+static int opt_backward_dct_impl(fdcap_ctx* c, float w_dct, float w_rec, float w_contact, int32_t log_terms, hipStream_t st) {
     if (c->opt->dctW <= 0) return FDCAP_E_STATE;
-    LossWeights lw;
-    lw.rec = w_rec; lw.smooth = 0.f; lw.contact = w_contact; lw.world = 0.f; lw.dct = w_dct; lw.world_on = false;
-    return opt_backward_impl(c, lw, log_terms, (hipStream_t)stream);
+    return opt_backward_impl(c, dct_phase2_weights(w_dct, w_rec, w_contact), log_terms, st);
+}
+
+int fdcap_opt_backward_dct(fdcap_ctx* c, float w_dct, float w_rec, float w_contact, int32_t log_terms, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_dct only)
+    if (!c || !c->opt) return FDCAP_E_STATE;
+    return opt_backward_dct_impl(c, w_dct, w_rec, w_contact, log_terms, (hipStream_t)stream);
 }
 
 int fdcap_opt_set_dct_coef(fdcap_ctx* c, const float* c_dct_d, void* stream) {
-    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
+    if (opt_is_batch(c) && c->opt->dctW <= 0) return FDCAP_E_STATE;     // (a batch of clips without a DCT term: fdcap_opt_set_dct_clips)
     if (!c || !c->opt || !c_dct_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     if (o->dctW <= 0) return FDCAP_E_STATE;
@@ -76,7 +141,7 @@ int fdcap_opt_set_dct_coef(fdcap_ctx* c, const float* c_dct_d, void* stream) {
 }
 
 int fdcap_opt_get_dct(fdcap_ctx* c, float* c_dct_d, void* stream) {
-    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
+    if (opt_is_batch(c) && c->opt->dctW <= 0) return FDCAP_E_STATE;     // (a batch of clips without a DCT term: fdcap_opt_set_dct_clips)
     if (!c || !c->opt || !c_dct_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     if (o->dctW <= 0) return FDCAP_E_STATE;
@@ -86,7 +151,7 @@ int fdcap_opt_get_dct(fdcap_ctx* c, float* c_dct_d, void* stream) {
 }
 // Adam's moments of c_dct, [W,69,C] each: what a checkpoint of mode 'dct' needs next to fdcap_opt_get_dct / fdcap_opt_export_state
 static int dct_state_copy(fdcap_ctx* c, float* m_d, float* v_d, bool out, hipStream_t st) {
-    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
+    if (opt_is_batch(c) && c->opt->dctW <= 0) return FDCAP_E_STATE;     // (a batch of clips without a DCT term: fdcap_opt_set_dct_clips)
     if (!c || !c->opt || !m_d || !v_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     if (o->dctW <= 0) return FDCAP_E_STATE;
@@ -101,6 +166,11 @@ int fdcap_opt_set_dct_state(fdcap_ctx* c, const float* m_d, const float* v_d, vo
 }
 int32_t fdcap_opt_dct_windows(fdcap_ctx* c, int32_t* w0, int32_t* w1) {
     if (!c || !c->opt || c->opt->dctW <= 0) return 0;
+    if (c->opt->dct_clips) {                             // a batch: every window of every clip (fdcap_opt_dct_clip_windows: per clip)
+        if (w0) *w0 = 0;
+        if (w1) *w1 = c->opt->dctW;
+        return c->opt->dctW;
+    }
     const fdcap_opt_config& cf = c->opt->cfg;
     const int T = c->opt->dctT;
     int a = (cf.frame0 + T - 1) / T, b = std::min((cf.frame0 + cf.n_local) / T, c->opt->dctW);

@@ -54,6 +54,7 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->nnpt_valid = false;
     o->n_recompute = 0;
     o->dctT = o->dctC = o->dctW = 0;
+    o->dct_clips = false;
     o->dct_grad = false;
     const int R = o->R = cfg->n_local + 4;
     o->contact_on = c->ns > 0 && c->nc > 0 && cfg->weight_contact != 0.f;
@@ -213,6 +214,20 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
     return 0;
 }
 
+// Mode 'dct' for a batch: row `slot` of dct_wk -- the clips' objective weights weight / (69 W_k) as the host evaluates them
+// (dct_clip_weights) -- uploaded when `weight` is not what the row holds.  slot 0 is the zero row (written at fdcap_opt_set_dct_clips).
+static int opt_dct_clip_weights(OptState* o, int slot, float weight, hipStream_t st, const float** out) {
+    const size_t K = (size_t)o->nclip;
+    if (weight == 0.f) slot = 0;
+    else if (o->dct_wk_weight[slot] != weight) {
+        o->dct_wk_h[slot] = dct_clip_weights(o->nclip, o->clip_lens.data(), o->dctT, weight);
+        HIP_TRY(hipMemcpyAsync(o->dct_wk.p + (size_t)slot * K, o->dct_wk_h[slot].data(), K * sizeof(float), hipMemcpyHostToDevice, st));
+        o->dct_wk_weight[slot] = weight;
+    }
+    *out = o->dct_wk.p + (size_t)slot * K;
+    return 0;
+}
+
 // fuse_ii >= 0 (fdcap_opt_backward_and_step): this backward is followed by the optimiser step of iteration fuse_ii -- `scale`
 // is stepped by one more workgroup of the last launch, the rows' part is left pending for the next forward (DeferredStep)
 // (clips of different lengths: the kernels take each frame's clip, denominators, stencil extent and weights from the half of the
@@ -229,6 +244,9 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         };
         if (same(opt_phase_weights(cf, false))) ctab = o->ctab(false);
         else if (same(opt_phase_weights(cf, true))) ctab = o->ctab(true);
+        // mode 'dct', second phase: the fourth set (the DCT weight is no part of a record: dct_clip_weights)
+        else if (o->dct_clips && lw.rec == o->dct_lw.rec && lw.smooth == 0.f && lw.contact == o->dct_lw.contact && lw.world == 0.f && !lw.world_on)
+            ctab = o->ctab_dct();
         else return FDCAP_E_STATE;
     }
     const int* const cspan = o->cspan();
@@ -275,11 +293,15 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
     ParamLossIn pli = {};
     if (fuse_pl) pli = ParamLossIn{o->X0.p, o->mask.p, o->Jw.p, cf.frame0, N, w_rec, w_sm, w_ws, lw.world_on ? 1 : 0,
                                    rows_log ? o->loss_rows.p : nullptr};
-    else if (ctab) return FDCAP_E_STATE;                  // (never: a batch has no DCT term, so its parameter-space terms are always fused)
-    else
+    else                                                  // (a batch -- mode 'dct' through fdcap_opt_run_dct -- in the clip-aware form)
         hipLaunchKernelGGL(param_loss_kernel, dim3(nl), dim3(128), 0, st, o->X.p, o->X0.p, o->mask.p, o->Jw.p, 2, cf.frame0, N,
-                           w_rec, w_sm, w_ws, lw.world_on ? 1 : 0, o->dX.p, o->dJw.p, losses, kn);
-    if (o->dctW > 0 && (dct_on || log_terms))
+                           w_rec, w_sm, w_ws, lw.world_on ? 1 : 0, o->dX.p, o->dJw.p, losses, kn, ctab);
+    if (o->dct_clips && (dct_on || log_terms)) {          // a batch: every row finds its clip's window, weight and loss slot
+        const float* wk = nullptr;
+        { int ew = opt_dct_clip_weights(o, 2, dct_on ? lw.dct : 0.f, st, &wk); if (ew) return ew; }
+        hipLaunchKernelGGL(dct_joint_grad_clips_kernel, dim3((nl * 69 + 255) / 256), dim3(256), 0, st, o->Jw.p, 2, nl, o->dctT, o->dctC, kn, ctab,
+                           o->dct_wstart.p, o->dctD.p, o->dctCoef.p, wk, lw.world_on ? 1 : 0, o->dJw.p, losses);
+    } else if (o->dctW > 0 && (dct_on || log_terms))
         hipLaunchKernelGGL(dct_joint_grad_kernel, dim3((nl * 69 + 255) / 256), dim3(256), 0, st, o->Jw.p, 2, cf.frame0, nl, o->dctT,
                            o->dctC, o->dctW, o->dctD.p, o->dctCoef.p, dct_on ? lw.dct / (69.f * (float)o->dctW) : 0.f,
                            lw.world_on ? 1 : 0, o->dJw.p, losses ? losses + 7 : nullptr);

@@ -152,6 +152,60 @@ int fdcap_opt_run_local2(fdcap_ctx* c, int32_t n_left, int32_t jj0, int32_t jj1,
     return e;
 }
 
+// Iterations [ii0, ii1) of mode 'dct''s loop (:595-630) of a fit of num_iter in ONE call, for one clip or a batch of clips (after
+// fdcap_opt_set_dct_clips): what FittingOP._dct_loops issues.  P = ceil(0.95 num_iter).
+//   ii < P   the stretch's share of the first phase as ONE launch over every clip's trajectories (weight w_phase1, Adam's step
+//            counters run on from ii0: a stretch cut anywhere gives the same bits); obj_hist_d (optional, with log_every > 0):
+//            [rows][69 windows] objectives before the update of iterations ii0, ii0 + log_every, ...
+//   ii == P  nothing receives a gradient; with legacy_zero_grad c_dct coasts one step
+//   ii > P   backward of w_dct loss_dct + w_rec loss_rec + w_contact loss_contact, then Adam on the rows and each clip's `scale`
+//            with step number ii - P; with legacy_zero_grad a coasting step of c_dct follows
+// Logging iterations of the second phase (log_every > 0: ii % log_every == 0, and the fit's last) leave their per-clip partial sums --
+// slots 0, 1, 2, 3 and 7 -- in consecutive rows of hist_d [hist_rows][n_clips][FDCAP_NUM_LOSSES], filled without a host sync; the
+// registered losses_d is registered again before the call returns.  flags bit 0: the stretch's last iteration is not stepped (its
+// gradients stay readable through fdcap_opt_get_grads).  Clips of different lengths: w_rec and w_contact must be those the fourth
+// record set was built under (0.5, 0.1), else FDCAP_E_STATE.  Nothing here waits for the device.
+int fdcap_opt_run_dct(fdcap_ctx* c, int32_t ii0, int32_t ii1, int32_t num_iter, float w_phase1, float w_dct, float w_rec, float w_contact,
+                      int32_t log_every, float* obj_hist_d, double* hist_d, int32_t hist_rows, int32_t flags, int32_t* n_logged, void* stream) {
+    if (n_logged) *n_logged = 0;
+    if (!c || !c->opt) return FDCAP_E_STATE;
+    if (ii0 < 0 || ii1 < ii0 || ii1 > num_iter || log_every < 0) return FDCAP_E_ARG;
+    OptState* o = c->opt;
+    if (o->dctW <= 0 || !opt_whole_clips(o)) return FDCAP_E_STATE;      // (a shard of a clip: the exchange stays with the caller)
+    const int P = (int)std::ceil((double)num_iter * 0.95 - 1e-9);       // first ii with not (ii < 0.95 num_iter) (:597)
+    const auto logs = [&](int ii) { return log_every > 0 && (ii % log_every == 0 || ii == num_iter - 1); };
+    {                                                        // every logging iteration of the stretch has its history row
+        int rows = 0;
+        for (int ii = std::max(ii0, P + 1); ii < ii1; ++ii) rows += logs(ii);
+        if (rows > 0 && (!hist_d || hist_rows < rows)) return FDCAP_E_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool legacy = o->cfg.legacy_zero_grad != 0;
+    const int big = 1 << 30;                                 // (P of the step: every second-phase iteration steps `scale`, camera_ext rests)
+    const size_t hist_row = (size_t)o->nclip * FDCAP_NUM_LOSSES;
+    double* const keep = o->losses.p;
+    int k = 0, e = 0;
+    const int end1 = std::min(ii1, P);
+    if (ii0 < end1) e = opt_dct_fit_impl(c, end1 - ii0, ii0, w_phase1, log_every > 0 ? obj_hist_d : nullptr, std::max(log_every, 1), st);
+    if (!e && legacy && ii0 <= P && P < ii1 && !((flags & 1) && P + 1 == ii1)) e = opt_dct_fit_impl(c, 1, P, 0.f, nullptr, 1, st);
+    for (int ii = std::max(ii0, P + 1); ii < ii1 && !e; ++ii) {
+        const bool do_log = logs(ii);
+        e = fdcap_opt_set_loss_output(c, do_log ? hist_d + (size_t)k * hist_row : keep);
+        if (e) break;
+        k += do_log;
+        e = opt_backward_dct_impl(c, w_dct, w_rec, w_contact, do_log ? 1 : 0, st);
+        if (e || ((flags & 1) && ii + 1 == ii1)) break;
+        e = opt_step_impl(c, ii - P - 1, big, true, true, true, stream);
+        if (!e && legacy) e = opt_dct_fit_impl(c, 1, ii, 0.f, nullptr, 1, st);      // optimizer.step() also moves the frozen c_dct
+    }
+    {                                                        // (never leave the library pointing into the caller's history)
+        const int e2 = fdcap_opt_set_loss_output(c, keep);
+        if (!e) e = e2;
+    }
+    if (n_logged) *n_logged = k;
+    return e;
+}
+
 int fdcap_opt_get_results(fdcap_ctx* c, float* body75, float* scale, float* cam, void* stream) {
     if (!c || !c->opt) return FDCAP_E_STATE;
     { int es_ = opt_sync(c, (hipStream_t)stream); if (es_) return es_; }

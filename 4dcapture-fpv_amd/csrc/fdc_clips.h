@@ -114,4 +114,49 @@ inline std::vector<ClipRow> clip_rows_build_local2(int32_t n_clips, const int32_
     return clip_rows_fill(n_clips, len, w);
 }
 
+// ---- mode 'dct' for a batch (fdcap_opt_set_dct_clips) -------------------------------------------------------------------------
+// Clip k of n_k frames has W_k = n_k / T windows over its own frames [0, W_k T); its trailing n_k % T frames belong to no window,
+// as in a stand-alone fit.  The batch's windows are numbered clip after clip: that number is the window's slot in c_dct.
+// starts [K + 1]: the first window of each clip, starts[K] = the batch's windows
+inline std::vector<int32_t> dct_window_starts(int32_t n_clips, const int32_t* len, int32_t T) {
+    std::vector<int32_t> s((size_t)n_clips + 1, 0);
+    for (int32_t k = 0; k < n_clips; ++k) s[(size_t)k + 1] = s[(size_t)k] + (T > 0 ? len[k] / T : 0);
+    return s;
+}
+// One record per window, what the first phase's wavefronts read once: the BUFFER row of the window's first frame (2 + s_k + w T --
+// never (window number) T: wrong as soon as a clip before it has a tail), its clip (selects the clip's objective weight) and its
+// slot in c_dct / the Adam moments.
+struct DctWindow { int32_t row, clip, slot, pad; };
+static_assert(sizeof(DctWindow) == 16, "one s_load_dwordx4 per window");
+inline std::vector<DctWindow> dct_window_table(int32_t n_clips, const int32_t* len, int32_t T) {
+    const std::vector<int32_t> s = clip_starts(n_clips, len), ws = dct_window_starts(n_clips, len, T);
+    std::vector<DctWindow> tab((size_t)ws[(size_t)n_clips]);
+    for (int32_t k = 0; k < n_clips; ++k)
+        for (int32_t w = 0; w < ws[(size_t)k + 1] - ws[(size_t)k]; ++w)
+            tab[(size_t)ws[(size_t)k] + w] = DctWindow{2 + s[(size_t)k] + w * T, k, ws[(size_t)k] + w, 0};
+    return tab;
+}
+// The weight in front of clip k's un-normalised objective sum: the mean runs over the clip's OWN 69 W_k trajectories.  This is the
+// float expression the stand-alone launches evaluate on the host (fdcap_opt_dct_fit, opt_backward_impl) with W = W_k, so the bits
+// are the stand-alone fit's; the batch kernels read the result, they never divide.  (W_k = 0: no window reads it; 0.)
+inline std::vector<float> dct_clip_weights(int32_t n_clips, const int32_t* len, int32_t T, float weight) {
+    std::vector<float> w((size_t)n_clips, 0.f);
+    for (int32_t k = 0; k < n_clips; ++k) {
+        const int32_t W = T > 0 ? len[k] / T : 0;
+        if (W > 0) w[(size_t)k] = weight / (69.f * (float)W);
+    }
+    return w;
+}
+// Mode 'dct', second phase (global_optimization.py:620): loss_dct w_dct + loss_rec w_rec + loss_contact w_contact -- no smoothing, no world
+// term.  Its records are a set of their own (w_sm = w_ws = 0); the DCT weight is no part of a record (dct_clip_weights).
+inline LossWeights dct_phase2_weights(float w_dct, float w_rec, float w_contact) {
+    LossWeights lw;
+    lw.rec = w_rec; lw.smooth = 0.f; lw.contact = w_contact; lw.world = 0.f; lw.dct = w_dct; lw.world_on = false;
+    return lw;
+}
+inline std::vector<ClipRow> clip_rows_build_dct2(int32_t n_clips, const int32_t* len, float w_rec, float w_contact, float weight_loss_rec,
+                                                 float weight_contact, int nc) {
+    return clip_rows_build(n_clips, len, dct_phase2_weights(0.f, w_rec, w_contact), weight_loss_rec, weight_contact, nc);
+}
+
 }  // namespace fdc

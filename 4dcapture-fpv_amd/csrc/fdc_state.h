@@ -88,7 +88,7 @@ struct OptState {
     // clip_len = 0.  The kernels then take clip_n = 0 and the device tables: clip_rows [3][R] ClipRow -- one record per buffer row
     // with the clip's weights of phase 1, then of phase 2 (the only two weight sets mode 'global' has), then of mode 'local''s
     // second loop (clip_weights_local2); built once per create, so no upload in the loop -- and clip_span [nclip][2]
-    // {start, length} for the per-clip tail workgroups.
+    // {start, length} for the per-clip tail workgroups.  (Mode 'dct''s second phase: a fourth set, clip_rows_dct below.)
     bool ragged = false;
     std::vector<int32_t> clip_lens, clip_start;
     DevBuf<ClipRow> clip_rows;
@@ -165,6 +165,22 @@ struct OptState {
     DevBuf<AdamScalars> adam_tab;
     std::vector<AdamScalars> adam_tab_h;
     int dctT = 0, dctC = 0, dctW = 0;
+    // mode 'dct' for a batch (fdcap_opt_set_dct_clips; fdc_clips.h): dctW = the windows of all clips, clip after clip.
+    // dct_wtab [dctW] one record per window; dct_wstart [nclip + 1] each clip's first window (host copy: dct_wstart_h);
+    // dct_wk [3][nclip] the clips' objective weights weight / (69 W_k) from the host -- row 0 zeros (a coasting step, a logging
+    // backward without the term), row 1 under the first phase's weight, row 2 under a backward's -- uploaded when the weight changes;
+    // clip_rows_dct [R]: the fourth record set of clips of different lengths, under the second phase's weights (dct_lw: its rec and
+    // contact multipliers, the only ones a record depends on)
+    bool dct_clips = false;
+    DevBuf<DctWindow> dct_wtab;
+    DevBuf<int> dct_wstart;
+    std::vector<int32_t> dct_wstart_h;
+    DevBuf<float> dct_wk;
+    std::vector<float> dct_wk_h[3];
+    float dct_wk_weight[3] = {0.f, 0.f, 0.f};
+    DevBuf<ClipRow> clip_rows_dct;
+    LossWeights dct_lw = {};
+    const ClipRow* ctab_dct() const { return ragged && dct_clips ? clip_rows_dct.p : nullptr; }
     bool dct_grad = false;    // the last backward gave `scale` a gradient through the DCT term
     bool seeded = false;      // a contact forward has run since fdcap_opt_create (idx holds neighbours)
     // fdcap_opt_forward_ahead ran for the owned rows and nothing has touched them since: the next backward only adds the halo
@@ -587,8 +603,8 @@ int vposer_forward(fdcap_ctx* c, const float* X, int ldx, int latent_off, int ro
 // sharded clip: no halo rows, no exchange, and the single-GPU schedule (deferred row step, `scale` stepped by the backward's tail).
 inline bool opt_whole_clips(const OptState* o) { return o->cfg.frame0 == 0 && o->cfg.n_local == o->cfg.n_total; }
 
-// a batch of several clips (fdcap_opt_create_clips): the entry points of modes 'local' / 'dct', the per-frame inner fit and the
-// sharded exchange refuse it (FDCAP_E_STATE)
+// a batch of several clips (fdcap_opt_create_clips): the single-step entry points of modes 'local' / 'dct', the per-frame inner fit
+// and the sharded exchange refuse it (FDCAP_E_STATE); it reaches those two modes through fdcap_opt_run_local2 / fdcap_opt_run_dct
 inline bool opt_is_batch(const fdcap_ctx* c) { return c && c->opt && c->opt->nclip > 1; }
 
 // rows of the optimiser's buffers whose pose is needed: the owned frames plus `halo` frames on each side that has a neighbour

@@ -885,11 +885,15 @@ class ClipBatchFitter:
     once, a scene once per run of batches of that scene (`fit(..., scene_key=...)` skips the registration when the key is the
     previous batch's).
 
-    Modes 'global' and 'local' (`fit(..., mode=...)`).  Mode 'local' runs its first loop as fdcap_opt_run under the 'local' config
+    Modes 'global', 'local' and 'dct' (`fit(..., mode=...)`).  Mode 'local' runs its first loop as fdcap_opt_run under the 'local' config
     and its second loop -- detect_contact and the cal_loss2 iterations (:534-556) -- as ONE fdcap_opt_run_local2 call; it leaves
-    each clip's second-loop log in self.logs2 and detect_contact's weights in self.contact_weights."""
+    each clip's second-loop log in self.logs2 and detect_contact's weights in self.contact_weights.  Mode 'dct' (:595-630) is
+    fdcap_opt_set_dct_clips + ONE fdcap_opt_run_dct call of `dct_num_iter` iterations: every clip has its own 60-frame windows over
+    its own frames (so at least 60 frames), and the first phase is one launch over all clips' trajectories; it leaves each clip's
+    c_dct [W_k,23,3,C] in self.c_dct, its first-phase log in self.logs_dct and its second-phase log in self.logs2."""
 
-    def __init__(self, fittingconfig, lossconfig, body_model=None, vposer=None, contact_ids=None, legacy_zero_grad=False, n_left=None):
+    def __init__(self, fittingconfig, lossconfig, body_model=None, vposer=None, contact_ids=None, legacy_zero_grad=False, n_left=None,
+                 dct_num_iter=DCT_NUM_ITER):
         import torch
         cfg = dict(DEFAULT_FITTINGCONFIG)
         cfg.update(fittingconfig or {})
@@ -921,6 +925,10 @@ class ClipBatchFitter:
         self.logs2 = []
         self.contact_weights = []
         self.idx1 = []
+        self.dct_num_iter = int(dct_num_iter)
+        self.c_dct = []
+        self.logs_dct = []
+        self._dct_in = (None, None)
 
     def _destroy_opt(self):
         if self._has_opt:
@@ -936,29 +944,40 @@ class ClipBatchFitter:
         self.ctx.set_scene(np.zeros((0, 3), np.float32) if scene_verts is None else scene_verts)
         self.scene_key = key
 
-    def fit(self, clips, scene_verts=None, scene_key=None, log_every=0, mode="global"):
+    @staticmethod
+    def _check_mode(clips, mode):
+        """the refusals that need no device"""
+        if mode not in ("global", "local", "dct"):
+            raise ValueError("a batch of clips fits in mode 'global', 'local' or 'dct'")
+        if mode == "dct" and any(int(np.shape(body)[0]) < BATCH_FRAME_NUM for body, _ in clips):
+            raise ValueError(f"mode 'dct' needs at least one {BATCH_FRAME_NUM}-frame window in every clip (:41-42); "
+                             "shorter clips fit in mode 'global' or 'local'")
+
+    def fit(self, clips, scene_verts=None, scene_key=None, log_every=0, mode="global", c_dct_init=None, dct_mtx=None):
         """clips: sequence of K (body_data [N_k,75], camera_ext [N_k,4,4]) pairs (numpy or device tensors); every clip has its own N_k.
         scene_verts / scene_key: the batch's scene (see set_scene; both None: the registered scene).
-        mode: 'global' or 'local' (the reference's default, :491).
+        mode: 'global', 'local' (the reference's default, :491) or 'dct' -- then c_dct_init: K arrays [W_k,23,3,C], W_k = N_k // 60
+        (None: torch.randn, clip after clip, :186), dct_mtx [60,C] (None: load_dct_base, as FittingOP).
         Returns a list of K (body_rec [N_k,75] device tensor, scale numpy scalar, camera_ext [N_k,4,4] device tensor) -- what
         FittingOP.fitting returns for each clip -- and leaves each clip's FitLog in self.logs, its outlier rows in self.idx1; mode
         'local' also each clip's second-loop rows [jj, l_rec, l_loc, l_sm, l_cs, total] (FittingOP.log2, the means over the clip's
-        own frames) in self.logs2 and detect_contact's per-frame weights in self.contact_weights."""
-        if mode not in ("global", "local"):
-            raise ValueError("a batch of clips fits in mode 'global' or 'local' (mode 'dct' is FittingOP's)")
+        own frames) in self.logs2 and detect_contact's per-frame weights in self.contact_weights; mode 'dct' each clip's c_dct in
+        self.c_dct, its rows [ii, loss_dct] of the first phase in self.logs_dct and [ii, l_rec, l_vposer, loss_smoothing, loss_contact,
+        loss_dct, total] of the second in self.logs2 (FittingOP.log_dct / log2, over the clip's own frames and windows)."""
+        self._check_mode(clips, mode)
         if scene_verts is not None or scene_key is not None:
             self.set_scene(scene_verts, scene_key)
-        self.prepare(clips, mode)
+        self.prepare(clips, mode, c_dct_init, dct_mtx)
         return self.run(log_every)
 
-    def prepare(self, clips, mode="global"):
+    def prepare(self, clips, mode="global", c_dct_init=None, dct_mtx=None):
         """init() of a batch (:450-489 per clip): creates the batch's optimiser on the registered scene and stages its inputs.
-        mode 'local': the config of its first loop (:511, :523), as FittingOP.init builds it."""
+        mode 'local': the config of its first loop (:511, :523), as FittingOP.init builds it; mode 'dct': mode 'global''s, as there."""
         import ctypes
         import torch
-        if mode not in ("global", "local"):
-            raise ValueError("a batch of clips fits in mode 'global' or 'local' (mode 'dct' is FittingOP's)")
+        self._check_mode(clips, mode)
         self._mode = mode
+        self._dct_in = (c_dct_init, dct_mtx)
         local = mode == "local"
         K = len(clips)
         if K < 1:
@@ -1027,6 +1046,8 @@ class ClipBatchFitter:
         total = starts[-1]
         lib, h = self.ctx.lib, self.ctx.handle
         st = capi.current_stream()
+        if self._mode == "dct":
+            return self._run_dct(log_every)
         # the loop in the library, as FittingOP.fitting runs a plain fit: one fdcap_opt_run for all iterations
         num_iter = int(self.num_iter)
         P = first_phase2_iter(num_iter)
@@ -1087,6 +1108,79 @@ class ClipBatchFitter:
                 log.loss_smoothing.append(l_sm); log.loss_contact.append(l_con)
                 log.loss_world_smoothing.append(l_ws); log.total.append(tot)
             self.logs.append(log)
+        sc = scale.cpu().numpy()
+        return [(body_rec[starts[k]:starts[k + 1]], sc[k], cam[starts[k]:starts[k + 1]].view(lens[k], 4, 4)) for k in range(K)]
+
+    def _run_dct(self, log_every=0):
+        """mode 'dct' of the prepared batch: fdcap_opt_set_dct_clips, ONE fdcap_opt_run_dct, the read-backs."""
+        import ctypes
+        import torch
+        K, lens, starts, dev = self.num_clips, self.clip_lens, self.clip_starts, self.device
+        total, T = starts[-1], BATCH_FRAME_NUM
+        lib, h = self.ctx.lib, self.ctx.handle
+        st = capi.current_stream()
+        c_init, D = self._dct_in
+        if D is None:
+            D = io.load_dct_base(getattr(self, "dct_mat_path", None), T, DCT_NUM)
+        D = np.ascontiguousarray(D, np.float32)
+        C = D.shape[1]
+        Wk = [n // T for n in lens]
+        ws = [0]
+        for w in Wk:
+            ws.append(ws[-1] + w)
+        if c_init is not None and len(c_init) != K:
+            raise capi.FdcapError(f"c_dct_init must hold one array per clip ({K}), got {len(c_init)}")
+        c0 = []
+        for k in range(K):
+            a = torch.randn(Wk[k], 23, 3, C) if c_init is None else \
+                torch.as_tensor(np.asarray(c_init[k], dtype=np.float32).reshape(Wk[k], 23, 3, -1))
+            if tuple(a.shape) != (Wk[k], 23, 3, C):
+                raise capi.FdcapError(f"c_dct_init[{k}] must be [{Wk[k]},23,3,{C}], got {tuple(a.shape)}")
+            c0.append(a)
+        c0 = torch.cat(c0).to(dev, torch.float32).contiguous()
+        capi.check(lib.fdcap_opt_set_dct_clips(h, D.ctypes.data_as(ctypes.c_void_p), D.shape[0], C, capi.dptr(c0), st), "fdcap_opt_set_dct_clips")
+        num_iter = self.dct_num_iter
+        P = int(math.ceil(num_iter * DCT_PHASE_SPLIT - 1e-9))
+        log_every = int(log_every or 0)
+        logged1 = list(range(0, P, log_every)) if log_every else []
+        logged2 = [ii for ii in range(P + 1, num_iter) if log_every and (ii % log_every == 0 or ii == num_iter - 1)]
+        hist1 = torch.zeros(max(len(logged1), 1), 69 * ws[-1], device=dev)
+        hist2 = torch.zeros(max(len(logged2), 1), K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
+        wd, wr, wc = DCT_PHASE2
+        n_done = ctypes.c_int32(0)
+        try:
+            capi.check(lib.fdcap_opt_run_dct(h, 0, num_iter, num_iter, DCT_PHASE1_WEIGHT, wd, wr, wc, log_every,
+                                             capi.dptr(hist1) if logged1 else None, capi.dptr(hist2) if logged2 else None, len(logged2), 0,
+                                             ctypes.byref(n_done), st), "fdcap_opt_run_dct")
+        finally:
+            capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
+        assert n_done.value == len(logged2)
+        body_rec = torch.empty(total, capi.PDIM, device=dev)
+        scale = torch.empty(K, device=dev)
+        cam = torch.empty(total, 16, device=dev)
+        capi.check(lib.fdcap_opt_get_results(h, capi.dptr(body_rec), capi.dptr(scale), capi.dptr(cam), st), "fdcap_opt_get_results")
+        cd = torch.empty(ws[-1], 23, 3, C, device=dev)
+        capi.check(lib.fdcap_opt_get_dct(h, capi.dptr(cd), st), "fdcap_opt_get_dct")
+        self.c_dct = [cd[ws[k]:ws[k + 1]] for k in range(K)]
+        self.logs, self.contact_weights = [], []
+        self.logs_dct, self.logs2 = [], []
+        rows2 = hist2.cpu().numpy()
+        nc = max(self.ctx.num_contact, 1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for k in range(K):
+                n, W = lens[k], Wk[k]
+                part = hist1[:, 69 * ws[k]:69 * ws[k + 1]].sum(dim=1, dtype=torch.float64).cpu().numpy()
+                self.logs_dct.append([[ii, float(part[j]) / (69 * W)] for j, ii in enumerate(logged1)])
+                log2 = []
+                for j, ii in enumerate(logged2):
+                    s = rows2[j, k]
+                    l_rec = self.weight_loss_rec * s[0] / (n * capi.XDIM)
+                    l_vp = self.weight_loss_vposer * s[1] / (n * 32)
+                    l_sm = s[2] / ((n - 2) * capi.XDIM) if n >= 3 else float("nan")
+                    l_con = self.weight_contact * s[3] / (n * nc)
+                    l_dct = s[7] / (69 * W)
+                    log2.append([ii, l_rec, l_vp, l_sm, l_con, l_dct, wd * l_dct + wr * l_rec + wc * l_con])
+                self.logs2.append(log2)
         sc = scale.cpu().numpy()
         return [(body_rec[starts[k]:starts[k + 1]], sc[k], cam[starts[k]:starts[k + 1]].view(lens[k], 4, 4)) for k in range(K)]
 

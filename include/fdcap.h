@@ -248,10 +248,12 @@ int fdcap_opt_create(fdcap_ctx* ctx, const fdcap_opt_config* cfg, float* rows_x_
  * Calls that cover the optimiser's rows cover all n_clips*N of them (fdcap_opt_get_results, fdcap_opt_forward_world,
  * fdcap_opt_get_contact, fdcap_opt_get_grads, launch timing); fdcap_opt_get_results writes n_clips scales; the state of
  * fdcap_opt_export_state holds n_clips scale moments; fdcap_opt_run's history rows are [n_clips][FDCAP_NUM_LOSSES].
- * Modes: 'global', and 'local' -- its first loop is fdcap_opt_run under the 'local' config (phase1_contact = 0.2, phase2_world = 0),
- * its second loop fdcap_opt_run_local2, the ONE call through which a batch reaches detect_contact and cal_loss2.  With
- * n_clips > 1 these return FDCAP_E_STATE: mode 'local''s single steps (fdcap_opt_detect_contact, fdcap_opt_backward_local2), mode 'dct'
- * (fdcap_opt_set_dct .. fdcap_opt_set_dct_state), the per-frame inner fit (fdcap_opt_set_keypoints, fdcap_opt_backward_fit2d,
+ * Modes: 'global'; 'local' -- its first loop is fdcap_opt_run under the 'local' config (phase1_contact = 0.2, phase2_world = 0),
+ * its second loop fdcap_opt_run_local2, the ONE call through which a batch reaches detect_contact and cal_loss2; and 'dct' --
+ * fdcap_opt_set_dct_clips, then fdcap_opt_run_dct, the ONE call through which a batch reaches both of that mode's phases.  With
+ * n_clips > 1 these return FDCAP_E_STATE: mode 'local''s single steps (fdcap_opt_detect_contact, fdcap_opt_backward_local2), mode
+ * 'dct''s (fdcap_opt_set_dct, fdcap_opt_dct_fit, fdcap_opt_backward_dct; its read-backs fdcap_opt_get_dct .. fdcap_opt_set_dct_state
+ * until fdcap_opt_set_dct_clips has run), the per-frame inner fit (fdcap_opt_set_keypoints, fdcap_opt_backward_fit2d,
  * fdcap_opt_step_x, fdcap_opt_fit2d_lbfgs[_stats]), fdcap_opt_forward_ahead and the exchange calls (fdcap_opt_step_rows_and_pack,
  * fdcap_opt_unpack_and_step_scale, fdcap_opt_halo_exchange, fdcap_opt_exchange, fdcap_opt_time_exchange, fdcap_opt_run with
  * flags bit 1).  FDCAP_E_ARG: n_clips < 1, or n_clips > 1 with frame0 != 0 or n_local != n_total. */
@@ -401,8 +403,39 @@ int fdcap_opt_get_dct(fdcap_ctx* ctx, float* c_dct_d, void* stream);
  * iterations already made) ends on the uninterrupted fit's bits. */
 int fdcap_opt_get_dct_state(fdcap_ctx* ctx, float* m_d, float* v_d, void* stream);
 int fdcap_opt_set_dct_state(fdcap_ctx* ctx, const float* m_d, const float* v_d, void* stream);
-/* Returns W; *w0 / *w1 = first / one-past-last window this rank fits (0 when fdcap_opt_set_dct has not run). */
+/* Returns W; *w0 / *w1 = first / one-past-last window this rank fits (0 when fdcap_opt_set_dct has not run).  A batch
+ * (fdcap_opt_set_dct_clips): W = the windows of all clips, *w0 = 0, *w1 = W. */
 int32_t fdcap_opt_dct_windows(fdcap_ctx* ctx, int32_t* w0, int32_t* w1);
+/* Mode 'dct' for WHOLE clips: an optimiser of fdcap_opt_create_clips / fdcap_opt_create_clips_var, or one clip (then exactly
+ * fdcap_opt_set_dct).  Clip k of n_k frames has W_k = n_k / T windows over its own frames [0, W_k T); its trailing n_k % T frames
+ * belong to no window, as in a stand-alone fit.  dct_mtx HOST [T,C]; c_dct_d DEVICE [sum W_k, 23, 3, C], clip after clip (copied; the
+ * Adam moments are library-owned and zeroed).  Afterwards fdcap_opt_get_dct, fdcap_opt_set_dct_coef and fdcap_opt_get/set_dct_state
+ * serve the batch with arrays of that layout, and the loop runs through fdcap_opt_run_dct.  Every clip's mean runs over its own
+ * 69 W_k trajectories and lands on the bits of its stand-alone fit under equal kernel forms.
+ * FDCAP_E_ARG: a clip with W_k = 0 (the stand-alone fit refuses it too), T > 64, C > 8.  FDCAP_E_STATE: no optimiser, or one that
+ * holds a shard of a clip (n_local != n_total). */
+int fdcap_opt_set_dct_clips(fdcap_ctx* ctx, const float* dct_mtx, int32_t T, int32_t C, const float* c_dct_d, void* stream);
+/* starts HOST [n_clips + 1] <- each clip's first window in c_dct (starts[n_clips] = fdcap_opt_dct_windows' W); n = n_clips + 1.
+ * FDCAP_E_STATE without a DCT term. */
+int fdcap_opt_dct_clip_windows(fdcap_ctx* ctx, int32_t* starts, int32_t n);
+/* Iterations [ii0, ii1) of mode 'dct''s loop of a fit of num_iter in ONE call (one clip or a batch, after fdcap_opt_set_dct_clips),
+ * P = ceil(0.95 num_iter):
+ *   ii < P   the first phase, ONE fdcap_opt_dct_fit launch over every clip's trajectories with weight w_phase1 (10 at :607); the
+ *            step counters run on from ii0, so a stretch cut anywhere gives the one-call bits.  obj_hist_d (optional; used when
+ *            log_every > 0) DEVICE [ceil((min(ii1, P) - ii0) / log_every)][69 W] as fdcap_opt_dct_fit writes it;
+ *   ii == P  nothing is stepped (cfg.legacy_zero_grad: c_dct coasts one step);
+ *   ii > P   fdcap_opt_backward_dct(w_dct, w_rec, w_contact) + fdcap_opt_step(ii - P - 1, 2^30): the rows and each clip's scale with
+ *            step number ii - P (cfg.legacy_zero_grad: a coasting fdcap_opt_dct_fit(weight 0) follows each step).
+ * Second-phase logging iterations (log_every > 0: ii % log_every == 0, and ii == num_iter - 1) write their per-clip partial sums
+ * (slots 0, 1, 2, 3, 7) to consecutive rows of hist_d DEVICE [hist_rows][n_clips][FDCAP_NUM_LOSSES], without a host sync;
+ * *n_logged rows used.  flags bit 0: the stretch's last iteration is left unstepped for fdcap_opt_get_grads.  Clips of different
+ * lengths take their per-frame weights from records built by fdcap_opt_set_dct_clips under w_rec = 0.5, w_contact = 0.1 (:620):
+ * other values there are FDCAP_E_STATE (w_dct is free).  Nothing here waits for the device.
+ * FDCAP_E_ARG: ii0 < 0, ii1 < ii0, ii1 > num_iter, log_every < 0, a second-phase logging iteration in the stretch with hist_d NULL
+ * or fewer than that many hist_rows.  FDCAP_E_STATE: no optimiser, no DCT term, a shard of a clip. */
+int fdcap_opt_run_dct(fdcap_ctx* ctx, int32_t ii0, int32_t ii1, int32_t num_iter, float w_phase1, float w_dct, float w_rec,
+                      float w_contact, int32_t log_every, float* obj_hist_d, double* hist_d, int32_t hist_rows, int32_t flags,
+                      int32_t* n_logged_out, void* stream);
 
 /* ---- optimization.py: the per-frame smoother (:185-238, driver loop :334-348) -------
  * data78_d [N,78] = convert_to_6D_rot of the SMPLify-X rows in file order; for every frame `iters` (50, :313)

@@ -15,7 +15,12 @@ all 10 475 vertices): K = 1 and K = 3 clips of 300 frames through ClipBatchFitte
 FittingOP mode-'local' fits in the same process (their contexts built before the clock starts) -- one warm-up each, then R rounds
 that alternate the two, each timed by the host clock around fits that end with the results on the host; medians, clips/s and the
 ratio (profiles/multiclip300_local.json).
-usage: python tools/multiclip_throughput.py [--reps R] [--out FILE] [--mode local] [--lengths n0,n1,...]..."""
+--mode dct: instead of the sweep, mode 'dct' at its 10 000 iterations (9 500 first-phase iterations in one launch, a no-op, 499 of the
+second phase): K = 1, 3 and 8 clips of 300 frames through ClipBatchFitter.fit(mode='dct') against K sequential stand-alone FittingOP
+mode-'dct' fits in the same process, under mode 'local''s protocol (one warm-up each, R rounds that alternate the two, medians), and
+the batch's two phases on their own -- fdcap_opt_run_dct cut at the phase switch, each stretch between two device events
+(profiles/multiclip300_dct.json).
+usage: python tools/multiclip_throughput.py [--reps R] [--out FILE] [--mode local|dct] [--lengths n0,n1,...]..."""
 import json
 import os
 import sys
@@ -35,7 +40,7 @@ def main():
     argv = sys.argv[1:]
     reps, out, lengths, mode = 3, None, [], "global"
     while argv:
-        if argv[0] == "--mode" and len(argv) > 1 and argv[1] in ("global", "local"):
+        if argv[0] == "--mode" and len(argv) > 1 and argv[1] in ("global", "local", "dct"):
             mode, argv = argv[1], argv[2:]
         elif argv[0] == "--reps":
             reps, argv = int(argv[1]), argv[2:]
@@ -55,10 +60,10 @@ def main():
     scene = synth.make_scene(NS, seed=2)
     left, right = synth.make_contact_ids(bm.v_template, per_part=250, seed=4)
     vid = np.concatenate([left, right])
-    if mode == "local":
+    if mode in ("local", "dct"):
         if lengths:
-            raise SystemExit("--mode local measures clips of 300 frames: not with --lengths")
-        return local_mode(reps, out, bm, vp, scene, vid)
+            raise SystemExit(f"--mode {mode} measures clips of 300 frames: not with --lengths")
+        return (local_mode if mode == "local" else dct_mode)(reps, out, bm, vp, scene, vid)
     if lengths:
         return ragged(lengths, reps, out, bm, vp, scene, vid)
     clips = []
@@ -218,6 +223,92 @@ def local_mode(reps, out, bm, vp, scene, vid):
                              "max_abs_body_difference": worst})
         print(f"K {K}: batch {mb * 1e3:8.2f} ms ({K / mb:6.2f} clips/s)  stand-alone x{K} {ma * 1e3:8.2f} ms ({K / ma:6.2f} clips/s)  "
               f"ratio {ma / mb:5.2f}", file=sys.stderr, flush=True)
+    fitter.close()
+    for f in fops:
+        f.close()
+    res["device"] = torch.cuda.get_device_name(0)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out:
+        with open(out, "w") as fh:
+            fh.write(line + "\n")
+
+
+def dct_mode(reps, out, bm, vp, scene, vid):
+    """K = 1, 3 and 8 clips of N frames in mode 'dct': one batch against K stand-alone fits, alternating; the batch's two phases."""
+    import ctypes
+    import math
+    from fdcap_amd import capi, synth
+    from fdcap_amd.fitting import DCT_NUM_ITER, DCT_PHASE1_WEIGHT, DCT_PHASE2, DCT_PHASE_SPLIT, ClipBatchFitter, FittingOP
+    from fdcap_amd.io import load_dct_base, read_camerapose
+    ks = (1, 3, 8)
+    D = load_dct_base(None)
+    rng = np.random.Generator(np.random.PCG64(7))
+    clips, c0 = [], []
+    for k in range(max(ks)):
+        c = synth.make_clip(N, seed=100 + k)
+        clips.append((c.body_params, read_camerapose(c.camerapose_lines)))
+        c0.append(rng.standard_normal((N // 60, 23, 3, 5)).astype(np.float32))
+    fitter = ClipBatchFitter({}, {}, body_model=bm, vposer=vp, contact_ids=vid)
+    fitter.set_scene(scene)
+    fops = [FittingOP({}, {}, N, body_model=bm, vposer=vp, scene_verts=scene, contact_ids=vid, camera_ext=cam, dct_mtx=D, c_dct_init=c0[k])
+            for k, (_, cam) in enumerate(clips)]
+    bodies = [torch.tensor(body).cuda() for body, _ in clips]
+    num_iter = DCT_NUM_ITER
+    P = int(math.ceil(num_iter * DCT_PHASE_SPLIT - 1e-9))
+
+    def batch(K):
+        t0 = time.perf_counter()
+        r = [(b.cpu(), s, c.cpu()) for b, s, c in fitter.fit(clips[:K], mode="dct", dct_mtx=D, c_dct_init=c0[:K])]
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    def alone(K):
+        t0 = time.perf_counter()
+        r = []
+        for k in range(K):
+            b, s, c = fops[k].fitting(bodies[k], "dct")
+            r.append((b.cpu(), s, c.cpu()))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    def phases(K):
+        """the batch's first and second phase, each one fdcap_opt_run_dct stretch between two events (ms)"""
+        fitter.prepare(clips[:K], "dct")
+        lib, h, st = fitter.ctx.lib, fitter.ctx.handle, capi.current_stream()
+        cd = torch.cat([torch.tensor(a) for a in c0[:K]]).cuda().contiguous()
+        capi.check(lib.fdcap_opt_set_dct_clips(h, D.ctypes.data_as(ctypes.c_void_p), D.shape[0], D.shape[1], capi.dptr(cd), st), "set_dct_clips")
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        n = ctypes.c_int32(0)
+        wd, wr, wc = DCT_PHASE2
+        ev[0].record()
+        capi.check(lib.fdcap_opt_run_dct(h, 0, P, num_iter, DCT_PHASE1_WEIGHT, wd, wr, wc, 0, None, None, 0, 0, ctypes.byref(n), st), "run_dct")
+        ev[1].record()
+        capi.check(lib.fdcap_opt_run_dct(h, P, num_iter, num_iter, DCT_PHASE1_WEIGHT, wd, wr, wc, 0, None, None, 0, 0, ctypes.byref(n), st), "run_dct")
+        ev[2].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]), ev[1].elapsed_time(ev[2])
+
+    res = {"problem": {"verts": 10475, "contacts": len(vid), "scene": NS, "frames_per_clip": N, "iters": num_iter, "first_phase_iters": P,
+                       "second_phase_iters": num_iter - P - 1, "mode": "dct", "reps": reps}, "sweep": []}
+    for K in ks:
+        _, rb = batch(K)
+        _, ra = alone(K)
+        worst = max(float((b[0] - a[0]).abs().max()) for b, a in zip(rb, ra))
+        tb, ta = [], []
+        for _ in range(reps):
+            tb.append(batch(K)[0])
+            ta.append(alone(K)[0])
+        ph = [phases(K) for _ in range(reps)]
+        p1, p2 = float(np.median([p[0] for p in ph])), float(np.median([p[1] for p in ph]))
+        mb, ma = float(np.median(tb)), float(np.median(ta))
+        res["sweep"].append({"K": K, "rows": K * N, "trajectory_waves": K * (N // 60) * 69, "batch_ms": mb * 1e3,
+                             "batch_ms_all": [t * 1e3 for t in tb], "stand_alone_ms": ma * 1e3, "stand_alone_ms_all": [t * 1e3 for t in ta],
+                             "batch_clips_per_s": K / mb, "stand_alone_clips_per_s": K / ma, "batch_over_stand_alone": ma / mb,
+                             "batch_first_phase_ms": p1, "batch_second_phase_ms": p2, "first_phase_us_per_iter": p1 * 1e3 / P,
+                             "second_phase_us_per_iter": p2 * 1e3 / max(num_iter - P - 1, 1), "max_abs_body_difference": worst})
+        print(f"K {K}: batch {mb * 1e3:8.2f} ms ({K / mb:6.2f} clips/s)  stand-alone x{K} {ma * 1e3:8.2f} ms ({K / ma:6.2f} clips/s)  "
+              f"ratio {ma / mb:5.2f}  phases {p1:7.2f} + {p2:7.2f} ms ({p1 * 1e3 / P:5.2f} us per first-phase iteration)", file=sys.stderr, flush=True)
     fitter.close()
     for f in fops:
         f.close()
