@@ -125,6 +125,20 @@ def allgather_packed(shard: FrameShard, send, gathered, overlap=None) -> None:
             overlap()
 
 
+def staged_collective(group, tensor, parts=None):
+    """-> the device tensor `tensor` summed over `group` (parts None), or every rank's `tensor` gathered into `parts` (one device
+    tensor per rank).  gloo (tests) cannot carry device tensors: there both stage through the host."""
+    import torch.distributed as dist
+    host = dist.get_backend(group) == "gloo"
+    t = tensor.cpu() if host else tensor
+    if parts is None:
+        dist.all_reduce(t, group=group)
+        return t.to(tensor.device)
+    parts = [p.cpu() for p in parts] if host else parts
+    dist.all_gather(parts, t, group=group)
+    return [p.to(tensor.device) for p in parts]
+
+
 def agree_on(shard: FrameShard, value: int) -> int:
     """Rank 0's `value` on every rank (one tiny broadcast).  For per-rank configuration that decides WHETHER a collective is
     issued -- e.g. `verbose`, which makes a fit read its loss history back (an all-reduce) every few logged iterations:

@@ -7,13 +7,18 @@ clip length is free (the reference hard-codes 300), an empty outlier set is lega
 stored once, and log-only terms are evaluated only when logging is requested."""
 from __future__ import annotations
 
+import ctypes
 import math
-from dataclasses import dataclass
+import os
+import time
+from dataclasses import dataclass, field
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import capi, io
-from .dist import FrameShard, agree_on, allgather_packed, allreduce_scalars, exchange_halos, same_on_all_ranks
+from .dist import (FrameShard, agree_on, allgather_packed, allreduce_scalars, exchange_halos, same_on_all_ranks,
+                   staged_collective)
 
 # loss-total constants buried in fitting() (global_optimization.py:564, :570, :582)
 PHASE_SPLIT = 0.8
@@ -47,6 +52,11 @@ DEFAULT_LOSSCONFIG = {"weight_loss_rec": 1, "weight_loss_vposer": 0.001, "weight
 def first_phase2_iter(num_iter: int) -> int:
     """Smallest ii with not (ii < num_iter*0.8) (:564)."""
     return int(math.ceil(num_iter * PHASE_SPLIT - 1e-12))
+
+
+def dct_first_phase2_iter(num_iter: int) -> int:
+    """Mode 'dct': smallest ii with not (ii < num_iter*0.95) (:601)."""
+    return int(math.ceil(num_iter * DCT_PHASE_SPLIT - 1e-9))
 
 
 def is_logging_iteration(ii: int, num_iter: int, log_every: int) -> bool:
@@ -105,9 +115,15 @@ def clip_inputs(x78: np.ndarray):
     return idx1, init78, mask
 
 
+# ---- one function per printed row: the un-normalised partial sums s (losses_d, float64) of an n-frame clip -> the printed terms --------
+MAIN_TERMS = ("l_rec", "l_vposer", "loss_smoothing", "loss_contact", "loss_world_smoothing", "total_loss")
+LOCAL2_TERMS = ("l_rec", "loss_local_smoothing", "loss_smoothing", "loss_contact_smoothing", "total_loss")
+DCT2_TERMS = ("l_rec", "l_vposer", "loss_smoothing", "loss_contact", "loss_dct", "total_loss")
+
+
 def logged_losses(s, n, nc, weight_loss_rec, weight_loss_vposer, weight_contact, phase2, local=False):
-    """One logged iteration of an n-frame clip: the un-normalised partial sums s (losses_d) -> the printed terms (:573-575,
-    :587-589) as (l_rec, l_vposer, loss_smoothing, loss_contact, loss_world_smoothing, total)."""
+    """One logged iteration of the main loop (:573-575, :587-589) as (l_rec, l_vposer, loss_smoothing, loss_contact,
+    loss_world_smoothing, total)."""
     nc = max(nc, 1)
     l_rec = weight_loss_rec * s[0] / (n * capi.XDIM)
     l_vp = weight_loss_vposer * s[1] / (n * 32)
@@ -119,19 +135,161 @@ def logged_losses(s, n, nc, weight_loss_rec, weight_loss_vposer, weight_contact,
     return l_rec, l_vp, l_sm, l_con, l_ws, total
 
 
+def local2_losses(s, n, num_verts, weight_loss_rec):
+    """One logged iteration of mode 'local''s second loop (:404-429) as [l_rec, loss_local_smoothing, loss_smoothing,
+    loss_contact_smoothing, total]; a mean over nothing (n = 2) is inf or NaN, without a warning."""
+    n = np.float64(n)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        l_rec = weight_loss_rec * s[0] / (n * capi.XDIM)
+        l_loc = s[2] / ((n - 2) * capi.XDIM)
+        l_sm = s[5] / ((n - 2) * (3 * num_verts))
+        l_cs = s[6]
+        return [l_rec, l_loc, l_sm, l_cs, l_sm + l_loc + l_rec + l_cs]
+
+
+def dct2_losses(s, n, W, nc, weight_loss_rec, weight_loss_vposer, weight_contact, weights=DCT_PHASE2):
+    """One logged iteration of mode 'dct''s second phase (:620) of a clip of W windows as [l_rec, l_vposer, loss_smoothing,
+    loss_contact, loss_dct, total]; `weights`: of (loss_dct, l_rec, loss_contact) in the total."""
+    wd, wr, wc = weights
+    nc = max(nc, 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        l_rec = weight_loss_rec * s[0] / (n * capi.XDIM)
+        l_vp = weight_loss_vposer * s[1] / (n * 32)
+        l_sm = s[2] / ((n - 2) * capi.XDIM) if n >= 3 else float("nan")
+        l_con = weight_contact * s[3] / (n * nc)
+        l_dct = s[7] / (69 * W)
+        return [l_rec, l_vp, l_sm, l_con, l_dct, wd * l_dct + wr * l_rec + wc * l_con]
+
+
 @dataclass
 class FitLog:
     """Per-logged-iteration losses in the reference's print order (:573-575, :587-589)."""
-    iters: list
-    l_rec: list
-    l_vposer: list
-    loss_smoothing: list
-    loss_contact: list
-    loss_world_smoothing: list
-    total: list
+    iters: list = field(default_factory=list)
+    l_rec: list = field(default_factory=list)
+    l_vposer: list = field(default_factory=list)
+    loss_smoothing: list = field(default_factory=list)
+    loss_contact: list = field(default_factory=list)
+    loss_world_smoothing: list = field(default_factory=list)
+    total: list = field(default_factory=list)
+
+    def append(self, ii, terms):
+        """terms: the six of logged_losses"""
+        self.iters.append(ii)
+        for column, v in zip((self.l_rec, self.l_vposer, self.loss_smoothing, self.loss_contact, self.loss_world_smoothing, self.total), terms):
+            column.append(v)
 
 
-class FittingOP:
+@dataclass
+class _Fit:
+    """What one FittingOP.fitting() call decided, handed to the loops that carry it out."""
+    multi: bool                     # the sharded iteration tail (more than one rank, or FDCAP_FORCE_EXCHANGE)
+    log_every: int
+    ii0: int                        # first iteration to run (0, or where the resumed checkpoint left off)
+    ck_every: int
+    ck_path: str | None
+    finite_every: int
+    snapshot_at: frozenset
+    resumed: dict                   # the mode's own arrays a resumed checkpoint carried (contact_weight; c_dct, dct_m, dct_v)
+
+
+def _c_dct_start(c_dct_init, W, C, name="c_dct_init"):
+    """One clip's start of c_dct [W,23,3,C] on the host: `c_dct_init`, or torch.randn as the reference draws it (:186)."""
+    import torch
+    c0 = torch.randn(W, 23, 3, C) if c_dct_init is None else torch.as_tensor(np.asarray(c_dct_init, dtype=np.float32).reshape(W, 23, 3, -1))
+    if tuple(c0.shape) != (W, 23, 3, C):
+        raise capi.FdcapError(f"{name} must be [{W},23,3,{C}], got {tuple(c0.shape)}")
+    return c0
+
+
+class _Fitter:
+    """What FittingOP and ClipBatchFitter share: the configuration on attributes, the models, the contact ids and the context, and
+    the library plumbing that does not depend on how the rows are laid out."""
+    _n_left_from_files = True       # contact ids read from the parts' files: the left part's size is the first file's
+
+    def __init__(self, fittingconfig, lossconfig, body_model, vposer, contact_ids, n_left, legacy_zero_grad, dct_num_iter):
+        import torch
+        for defaults, given in ((DEFAULT_FITTINGCONFIG, fittingconfig), (DEFAULT_LOSSCONFIG, lossconfig)):
+            for k, v in {**defaults, **(given or {})}.items():
+                setattr(self, k, v)
+        self.legacy_zero_grad = bool(legacy_zero_grad)
+        self.dct_num_iter = int(dct_num_iter)
+        self._mode = "global"
+        if not torch.cuda.is_available():
+            raise capi.FdcapError("no HIP device: the fdcap_amd optimiser only runs on the GPU")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        if body_model is None or vposer is None:
+            from . import assets
+            body_model = body_model or assets.load_smplx_npz(self.human_model_path)
+            vposer = vposer or assets.load_vposer_snapshot(self.vposer_ckpt_path)
+        self.setup_s = {}
+        self.ctx = self._timed("ctx_create", capi.Context, body_model, vposer)
+        if contact_ids is None:
+            parts = [io.read_contact_ids(self.contact_id_folder, [p]) for p in self.contact_part]
+            contact_ids = np.concatenate(parts)
+            if self._n_left_from_files:
+                n_left = len(parts[0])
+        self.vid = np.asarray(contact_ids, dtype=np.int64)
+        # mode 'local' treats the two contact parts separately (L_Leg ids first, :341-347)
+        self.n_left = int(n_left) if n_left is not None else len(self.vid) // 2
+
+    def _timed(self, what, call, *args):
+        """Host seconds of a registration call (each returns with its device work done) -> self.setup_s[what]: what a one-clip process
+        pays before its first iteration -- bench.py publishes them as `setup` (the reference's counterpart: __init__, :142-188)."""
+        t0 = time.perf_counter()
+        out = call(*args)
+        self.setup_s[what] = time.perf_counter() - t0
+        return out
+
+    def _opt_config(self, n_total, n_local, frame0):
+        """The library's configuration for self._mode: mode 'local' has its own first-loop weights (:511, :523), 'dct' mode 'global''s."""
+        local = self._mode == "local"
+        return capi.OptConfig(n_total, n_local, frame0, float(self.init_lr_h), float(self.weight_loss_rec),
+                              float(self.weight_loss_vposer), float(self.weight_contact),
+                              LOCAL_PHASE1_CONTACT if local else PHASE1_CONTACT, PHASE1_SMOOTH,
+                              0.0 if local else PHASE2_WORLD, PHASE2_SMOOTH, SCALE_INIT, int(self.legacy_zero_grad))
+
+    def _new_state(self, rows, K, losses_shape):
+        """The optimiser's state -- `rows` rows (two halo rows either side included) of K clips -- is owned here (torch tensors) and
+        registered with the library, so the same storage is what RCCL exchanges / reduces -> the five pointers fdcap_opt_create* take."""
+        import torch
+        dev = self.device
+        self._rows_x, self._rows_cam = torch.zeros(rows, capi.XDIM, device=dev), torch.zeros(rows, 16, device=dev)
+        self._scale, self._dscale = torch.zeros(K, device=dev), torch.zeros(K, device=dev)
+        self._losses = torch.zeros(*losses_shape, device=dev, dtype=torch.float64)
+        torch.cuda.current_stream().synchronize()
+        return [capi.dptr(t) for t in (self._rows_x, self._rows_cam, self._scale, self._dscale, self._losses)]
+
+    def _results(self, rows, K):
+        """fdcap_opt_get_results -> (body_rec [rows,75], scale [K], camera_ext [rows,16]), fresh device tensors"""
+        import torch
+        body_rec = torch.empty(rows, capi.PDIM, device=self.device)
+        scale = torch.empty(K, device=self.device)
+        cam = torch.empty(rows, 16, device=self.device)
+        capi.check(self.ctx.lib.fdcap_opt_get_results(self.ctx.handle, capi.dptr(body_rec), capi.dptr(scale), capi.dptr(cam),
+                                                      capi.current_stream()), "fdcap_opt_get_results")
+        return body_rec, scale, cam
+
+    def _opt_run(self, ii, end, P, log_every, rows, multi=False):
+        """Iterations ii .. end-1 of the main loop as ONE fdcap_opt_run; `rows`: the history rows of their logging iterations
+        (None: none logs).  FDCAP_DEFER_STEP=0: every optimiser step as its own launch (A/B; the same bits either way)."""
+        flags = (0 if os.environ.get("FDCAP_DEFER_STEP", "1") != "0" else 1) | (2 if multi else 0)
+        n_rows, n_done = 0 if rows is None else rows.shape[0], ctypes.c_int32(0)
+        capi.check(self.ctx.lib.fdcap_opt_run(self.ctx.handle, ii, end, int(self.num_iter), P, int(log_every or 0), capi.dptr(rows), n_rows, flags,
+                                              ctypes.byref(n_done), capi.current_stream()), "fdcap_opt_run")
+        assert n_done.value == n_rows
+
+    def _dct_state(self, W, C):
+        """c_dct [W,69*C] with its two Adam moments, read from the device"""
+        import torch
+        lib, h, st = self.ctx.lib, self.ctx.handle, capi.current_stream()
+        cd = torch.empty(W, 69 * C, device=self.device)
+        dm, dv = torch.empty_like(cd), torch.empty_like(cd)
+        capi.check(lib.fdcap_opt_get_dct(h, capi.dptr(cd), st), "fdcap_opt_get_dct")
+        capi.check(lib.fdcap_opt_get_dct_state(h, capi.dptr(dm), capi.dptr(dv), st), "fdcap_opt_get_dct_state")
+        return {"c_dct": cd, "dct_m": dm, "dct_v": dv}
+
+
+class FittingOP(_Fitter):
     def __init__(self, fittingconfig, lossconfig, num_body, body_model=None, vposer=None, scene_verts=None,
                  contact_ids=None, camera_ext=None, group=None, legacy_zero_grad=False, n_left=None,
                  dct_mtx=None, c_dct_init=None, dct_num_iter=DCT_NUM_ITER):
@@ -143,48 +301,15 @@ class FittingOP:
         reference draws torch.randn, :186 -- so does the default); `dct_num_iter`: the 10000 of :596.
         `group`: torch.distributed process group for frame sharding (None = single GPU);
         `num_body` is the clip length N (the reference's batch_size = num_body, :152)."""
-        import torch
-        cfg = dict(DEFAULT_FITTINGCONFIG)
-        cfg.update(fittingconfig or {})
-        lcfg = dict(DEFAULT_LOSSCONFIG)
-        lcfg.update(lossconfig or {})
-        for k, v in cfg.items():
-            setattr(self, k, v)
-        for k, v in lcfg.items():
-            setattr(self, k, v)
+        super().__init__(fittingconfig, lossconfig, body_model, vposer, contact_ids, n_left, legacy_zero_grad, dct_num_iter)
         self.snapshot_hook = None      # tools: called with k right after the snapshot of step k was taken (`fitting(snapshot_at=...)`)
         self.batch_size = self.num_body = int(num_body)
-        self.legacy_zero_grad = bool(legacy_zero_grad)
-        if not torch.cuda.is_available():
-            raise capi.FdcapError("no HIP device: the fdcap_amd optimiser only runs on the GPU")
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        if body_model is None or vposer is None:
-            from . import assets
-            body_model = body_model or assets.load_smplx_npz(self.human_model_path)
-            vposer = vposer or assets.load_vposer_snapshot(self.vposer_ckpt_path)
-        # host seconds of the three registration calls (each returns with its device work done): what a one-clip process pays
-        # before its first iteration -- bench.py publishes them as `setup` (the reference's counterpart: __init__, :142-188)
-        import time
-        t0 = time.perf_counter()
-        self.ctx = capi.Context(body_model, vposer)
-        self.setup_s = {"ctx_create": time.perf_counter() - t0}
         if scene_verts is None and self.scene_verts_path:
             scene_verts = io.read_scene_points(self.scene_verts_path)
         if scene_verts is None:
             scene_verts = np.zeros((0, 3), np.float32)
-        t0 = time.perf_counter()
-        self.ctx.set_scene(scene_verts)
-        self.setup_s["set_scene"] = time.perf_counter() - t0
-        if contact_ids is None:
-            parts = [io.read_contact_ids(self.contact_id_folder, [p]) for p in self.contact_part]
-            contact_ids = np.concatenate(parts)
-            n_left = len(parts[0])
-        self.vid = np.asarray(contact_ids, dtype=np.int64)
-        # mode 'local' treats the two contact parts separately (L_Leg ids first, :341-347)
-        self.n_left = int(n_left) if n_left is not None else len(self.vid) // 2
-        t0 = time.perf_counter()
-        self.ctx.set_contact_ids(self.vid)
-        self.setup_s["set_contact_ids"] = time.perf_counter() - t0
+        self._timed("set_scene", self.ctx.set_scene, scene_verts)
+        self._timed("set_contact_ids", self.ctx.set_contact_ids, self.vid)
         if camera_ext is None and self.camera_path:
             camera_ext = io.read_camerapose(self.camera_path)
         self._camera_ext_init = None if camera_ext is None else np.asarray(camera_ext, np.float32).reshape(-1, 4, 4)
@@ -195,21 +320,13 @@ class FittingOP:
         # gloo tests -- ranks sharing one GPU, which RCCL refuses -- always take).
         self._c_comm = False
         if group is not None:
-            import os
             import torch.distributed as dist
             if dist.get_backend(group) == "nccl":
-                from .dist import agree_on
                 if agree_on(self.shard, int(os.environ.get("FDCAP_C_COMM", "1") != "0")):      # (rank 0's setting, for everyone)
                     self._init_c_comm()
         self.dct_mtx = None if dct_mtx is None else np.ascontiguousarray(dct_mtx, dtype=np.float32)
         self._c_dct_init = c_dct_init
-        self.dct_num_iter = int(dct_num_iter)
-        self.c_dct = None
-        self.scale = None
-        self.camera_ext = None
-        self.body_rotation_rec = None
-        self.log = None
-        self.idx1 = None
+        self.c_dct = self.scale = self.camera_ext = self.body_rotation_rec = self.log = self.idx1 = None     # (a fit's results)
 
     def _init_c_comm(self):
         """Rank 0 draws the RCCL unique id, torch.distributed carries it to the other ranks (the out-of-band channel any
@@ -218,11 +335,9 @@ class FittingOP:
         fail on one rank alone -- binding librccl, creating the communicator, a first sum over it -- is followed by an
         agreement over torch.distributed, and any failure anywhere sends every rank to torch.distributed's collectives
         (RCCL as well; same kernels either side of the all-gather, same results), with a warning on rank 0."""
-        import ctypes
         import warnings
         import torch
         import torch.distributed as dist
-        from .dist import same_on_all_ranks
         lib, h = self.ctx.lib, self.ctx.handle
         sh = self.shard
 
@@ -283,26 +398,10 @@ class FittingOP:
             raise capi.FdcapError("camera_ext / camerapose.txt must have one pose per frame (:455)")
         sh = self.shard
         lo, hi = sh.frame0, sh.frame0 + sh.n_local
-        local = getattr(self, "_mode", "global") == "local"
-        oc = capi.OptConfig(self.num_body, sh.n_local, sh.frame0, float(self.init_lr_h), float(self.weight_loss_rec),
-                            float(self.weight_loss_vposer), float(self.weight_contact),
-                            LOCAL_PHASE1_CONTACT if local else PHASE1_CONTACT, PHASE1_SMOOTH,
-                            0.0 if local else PHASE2_WORLD, PHASE2_SMOOTH, SCALE_INIT, int(self.legacy_zero_grad))
+        oc = self._opt_config(self.num_body, sh.n_local, sh.frame0)
         lib = self.ctx.lib
-        import ctypes
         dev = self.device
-        R = sh.n_local + 4
-        # optimiser state is owned here (torch tensors) and registered with the library, so the
-        # same storage is what RCCL exchanges / reduces
-        self._rows_x = torch.zeros(R, capi.XDIM, device=dev)
-        self._rows_cam = torch.zeros(R, 16, device=dev)
-        self._scale = torch.zeros(1, device=dev)
-        self._dscale = torch.zeros(1, device=dev)
-        self._losses = torch.zeros(capi.NUM_LOSSES, device=dev, dtype=torch.float64)
-        torch.cuda.current_stream().synchronize()
-        capi.check(lib.fdcap_opt_create(self.ctx.handle, ctypes.byref(oc), capi.dptr(self._rows_x),
-                                        capi.dptr(self._rows_cam), capi.dptr(self._scale), capi.dptr(self._dscale),
-                                        capi.dptr(self._losses)), "fdcap_opt_create")
+        capi.check(lib.fdcap_opt_create(self.ctx.handle, ctypes.byref(oc), *self._new_state(sh.n_local + 4, 1, (capi.NUM_LOSSES,))), "fdcap_opt_create")
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         d_data, d_init = body_data_rotation[lo:hi].contiguous(), t(init78[lo:hi])
         d_mask, d_cam = t(mask[lo:hi]), t(self._camera_ext_init[lo:hi].reshape(-1, 16))
@@ -352,7 +451,6 @@ class FittingOP:
             raise ValueError("mode 'dct': checkpoint_every must be a multiple of log_every (the first phase's objective history is "
                              "written by the launch itself, every log_every-th iteration counted from the launch's first)")
         self._mode = mode
-        lib, h = self.ctx.lib, self.ctx.handle
         dev = self.device
         if not torch.is_tensor(body_data):
             body_data = torch.from_numpy(np.ascontiguousarray(body_data, dtype=np.float32))
@@ -360,44 +458,50 @@ class FittingOP:
         n = body_data.shape[0]
         if n != self.num_body:
             raise capi.FdcapError(f"body_data has {n} frames, FittingOP was built for {self.num_body}")
-        st = capi.current_stream()
         x78 = torch.empty(n, capi.XDIM, device=dev)
-        capi.check(lib.fdcap_params_75_to_78(capi.dptr(body_data), n, capi.dptr(x78), st), "fdcap_params_75_to_78")
+        capi.check(self.ctx.lib.fdcap_params_75_to_78(capi.dptr(body_data), n, capi.dptr(x78), capi.current_stream()), "fdcap_params_75_to_78")
         self.init(x78)                                                                      # :495
-        P = first_phase2_iter(self.num_iter)
-        self._ck_extra = {}
-        ii0 = self._load_checkpoint(resume) if resume else 0
-        self._ck = (int(checkpoint_every), checkpoint_path, int(check_finite_every))
-        log = FitLog([], [], [], [], [], [], [])
+        ii0, resumed = self._load_checkpoint(resume) if resume else (0, {})
         # FDCAP_FORCE_EXCHANGE=1: run the sharded iteration tail (pack -> all-gather -> unpack) even on a one-rank
         # group -- lets a single-GPU box exercise the RCCL calls of the multi-GPU path
-        import os
         multi = self.shard.world > 1 or (self.group is not None and os.environ.get("FDCAP_FORCE_EXCHANGE") == "1")
-        # Forward ahead of the exchange (fdcap_opt_forward_ahead): FDCAP_XCH_OVERLAP=1 always, =0 never; otherwise the rank
-        # times eight iterations of either schedule early in phase 1 and keeps the faster one.  The two give the same bits,
-        # and the choice is local to a rank (the collective is the same call either way).  Why not simply "always": handing
-        # work between the collective's stream and this one costs ~17 us per iteration on a one-rank RCCL group
-        # (tools/host_issue_probe.py), so the overlap only pays when the all-gather takes longer than that to come back.
-        env_ov = os.environ.get("FDCAP_XCH_OVERLAP", "auto")
-        overlap = multi and env_ov == "1" and not self._c_comm        # (the library's own exchange runs on the compute stream: nothing to overlap)
-        tune = None
-        if multi and not self._c_comm and env_ov not in ("0", "1") and mode != "dct" and ii0 + 18 <= min(P, self.num_iter):
-            tune = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        self.exchange_overlap = overlap
+        fit = _Fit(multi, log_every, ii0, int(checkpoint_every), checkpoint_path, int(check_finite_every), snapshot_at, resumed)
+        # FDCAP_XCH_OVERLAP=1: the forward ahead of the exchange from the first iteration on (_per_iteration_issuer)
+        self.exchange_overlap = multi and os.environ.get("FDCAP_XCH_OVERLAP", "auto") == "1" and not self._c_comm
         if mode == "dct":
-            self._dct_loops(lib, h, multi, log_every, ii0)
-        # The reference prints every loss term in every iteration (:573-575, :587-589) with five .item() syncs.  Here the
-        # partial sums of a logging iteration are written into a device-side history row (no host sync inside the loop) and
-        # read back -- and, when sharded, all-reduced -- once after the last iteration.
-        # FDCAP_DEFER_STEP=0: every optimiser step as its own launch (A/B; the results are the same bits either way)
-        defer = os.environ.get("FDCAP_DEFER_STEP", "1") != "0"
-        n_log = 0
-        logged = []
+            log = FitLog()
+            self._dct_loops(fit)
+        else:
+            log = self._main_loop(fit)
+            if mode == "local":
+                self._local_second_loop(fit)
+        nl = self.shard.n_local
+        body_rec, scale, cam = self._results(nl, 1)
+        self.scale = scale
+        self.camera_ext = cam.view(nl, 4, 4)
+        self.body_rotation_rec = self._rows_x[2:2 + nl]
+        self.log = log
+        return body_rec, scale.detach().cpu().numpy().squeeze(), self.camera_ext
+
+    # ---- the main loop of modes 'global' and 'local' (:558-593) -----------------------------------------------------------------
+    def _main_loop(self, fit):
+        """Iterations [fit.ii0, num_iter) -> their FitLog.  The loop runs in stretches [ii, end) between two things THIS side has to
+        do -- a verbose flush, a snapshot, a finite check, a checkpoint; none of them in a plain fit: one stretch for all 500.
+        The reference prints every loss term in every iteration (:573-575, :587-589) with five .item() syncs.  Here the
+        partial sums of a logging iteration are written into a device-side history row (no host sync inside the loop) and
+        read back -- and, when sharded, all-reduced -- after the last iteration (a verbose fit: in batches of VERBOSE_FLUSH logged
+        iterations, to show its progress)."""
+        import torch
+        lib, h = self.ctx.lib, self.ctx.handle
+        num_iter, log_every, multi = self.num_iter, fit.log_every, fit.multi
+        P = first_phase2_iter(num_iter)
+        log = FitLog()
         # in-loop read-backs of the loss history are collectives when sharded: one flag for the whole group (rank 0's)
         flush_in_loop = bool(agree_on(self.shard, 1 if self.verbose else 0)) if multi else bool(self.verbose)
-        if log_every and mode != "dct":
-            n_log = sum(1 for ii in range(ii0, self.num_iter) if ii % log_every == 0 or ii == self.num_iter - 1)
-            hist = torch.zeros(max(n_log, 1), capi.NUM_LOSSES, device=dev, dtype=torch.float64)
+        is_log = lambda i: is_logging_iteration(i, num_iter, log_every)
+        if log_every:
+            hist = torch.zeros(max(sum(1 for i in range(fit.ii0, num_iter) if is_log(i)), 1), capi.NUM_LOSSES, device=self.device, dtype=torch.float64)
+        logged = []
         flushed = 0
 
         def flush(upto):
@@ -414,55 +518,65 @@ class FittingOP:
                 self._append_log(log, logged[flushed + k], logged[flushed + k] >= P, rows[k])
             flushed = upto
 
-        # The loop inside the library (fdcap_opt_run: one C call per stretch of iterations between two things THIS side has to do --
-        # a verbose flush, a snapshot, a finite check, a checkpoint; none of them in a plain fit: one call for all 500) wherever the
-        # iteration is C calls only: one rank, or ranks exchanging through the library's communicator.  FDCAP_C_LOOP=0 keeps the
-        # Python `for` below (same calls in the same order: same bits).
-        c_loop = os.environ.get("FDCAP_C_LOOP", "1") != "0" and mode != "dct" and (not multi or self._c_comm)
-        if c_loop:
-            import ctypes
-            n_done = ctypes.c_int32(0)
-            st = capi.current_stream()
-
-            def is_log(i):
-                return is_logging_iteration(i, self.num_iter, log_every)
-
-            ii = ii0
-            try:
-                while ii < self.num_iter:
-                    # the stretch [ii, end): ends after the first iteration that leaves this side something to do
-                    end = stretch_end(ii, self.num_iter, log_every, snapshot_at, check_finite_every, checkpoint_every,
-                                      VERBOSE_FLUSH if flush_in_loop else 0, len(logged) - flushed)
-                    rows = [i for i in range(ii, end) if is_log(i)]
-                    k0 = len(logged)
-                    capi.check(lib.fdcap_opt_run(h, ii, end, self.num_iter, P, int(log_every or 0),
-                                                 capi.dptr(hist[k0]) if rows else None, len(rows), (0 if defer else 1) | (2 if multi else 0),
-                                                 ctypes.byref(n_done), st), "fdcap_opt_run")
-                    assert n_done.value == len(rows)
-                    logged.extend(rows)
-                    last = end - 1
-                    if flush_in_loop and is_log(last) and len(logged) - flushed >= VERBOSE_FLUSH:
-                        flush(len(logged))
-                    if end in snapshot_at:
-                        capi.check(lib.fdcap_opt_sync(h, st), "fdcap_opt_sync")
-                        nl_ = self.shard.n_local
-                        self.snapshots[end] = (self._rows_x[2:2 + nl_].clone(), self._scale.clone(), self._rows_cam[2:2 + nl_].clone())
-                        if self.snapshot_hook:
-                            self.snapshot_hook(end)
-                    if check_finite_every and end % check_finite_every == 0:
-                        self._check_finite(last)
-                    if checkpoint_every and end % checkpoint_every == 0 and end < self.num_iter:
-                        self._save_checkpoint(checkpoint_path, end)
-                    ii = end
-            finally:
-                if logged:                                   # (fdcap_opt_run re-registers the old output itself; after an error, make sure)
-                    capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
+        # A stretch is ONE library call (fdcap_opt_run) wherever the iteration is C calls only: one rank, or ranks exchanging through
+        # the library's communicator.  FDCAP_C_LOOP=0 keeps the calls of the single iterations (the same, in the same order: same bits).
+        c_loop = os.environ.get("FDCAP_C_LOOP", "1") != "0" and (not multi or self._c_comm)
+        issue = (lambda ii, end, rows: self._opt_run(ii, end, P, log_every, rows, multi)) if c_loop else self._per_iteration_issuer(fit, P)
+        ii = fit.ii0
         try:
-            for ii in range(ii0, self.num_iter if (mode != "dct" and not c_loop) else 0):       # :560
-                do_log = bool(log_every) and (ii % log_every == 0 or ii == self.num_iter - 1)
+            while ii < num_iter:
+                # the stretch [ii, end): ends after the first iteration that leaves this side something to do
+                end = stretch_end(ii, num_iter, log_every, fit.snapshot_at, fit.finite_every, fit.ck_every,
+                                  VERBOSE_FLUSH if flush_in_loop else 0, len(logged) - flushed)
+                rows = [i for i in range(ii, end) if is_log(i)]
+                issue(ii, end, hist[len(logged):len(logged) + len(rows)] if rows else None)
+                logged.extend(rows)
+                if flush_in_loop and is_log(end - 1) and len(logged) - flushed >= VERBOSE_FLUSH:
+                    flush(len(logged))
+                if end in fit.snapshot_at:
+                    capi.check(lib.fdcap_opt_sync(h, capi.current_stream()), "fdcap_opt_sync")      # (applies a deferred step first)
+                    nl = self.shard.n_local
+                    self.snapshots[end] = (self._rows_x[2:2 + nl].clone(), self._scale.clone(), self._rows_cam[2:2 + nl].clone())
+                    if self.snapshot_hook:
+                        self.snapshot_hook(end)
+                if fit.finite_every and end % fit.finite_every == 0:
+                    self._check_finite(end - 1)
+                if fit.ck_every and end % fit.ck_every == 0 and end < num_iter:
+                    self._save_checkpoint(fit.ck_path, end)
+                ii = end
+        finally:
+            # never leave the library pointing into `hist` (freed with this frame if the loop raised).  (After fdcap_opt_run, which
+            # re-registers the old output itself, there have always been two of these calls: tests/driver_trace.json pins them)
+            for _ in range((2 if c_loop else 1) if logged else 0):
+                capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
+        flush(len(logged))
+        return log
+
+    def _per_iteration_issuer(self, fit, P):
+        """-> issue(ii, end, rows): iterations ii .. end-1 call by call (the arguments of _opt_run, which issues them as one)."""
+        import torch
+        lib, h = self.ctx.lib, self.ctx.handle
+        num_iter, log_every, multi = self.num_iter, fit.log_every, fit.multi
+        defer = os.environ.get("FDCAP_DEFER_STEP", "1") != "0"
+        # Forward ahead of the exchange (fdcap_opt_forward_ahead): FDCAP_XCH_OVERLAP=1 always, =0 never; otherwise the rank
+        # times eight iterations of either schedule early in phase 1 and keeps the faster one.  The two give the same bits,
+        # and the choice is local to a rank (the collective is the same call either way).  Why not simply "always": handing
+        # work between the collective's stream and this one costs ~17 us per iteration on a one-rank RCCL group
+        # (tools/host_issue_probe.py), so the overlap only pays when the all-gather takes longer than that to come back.
+        # (The library's own exchange runs on the compute stream: nothing to overlap.)
+        overlap = self.exchange_overlap
+        tune = None
+        if multi and not self._c_comm and os.environ.get("FDCAP_XCH_OVERLAP", "auto") not in ("0", "1") and fit.ii0 + 18 <= min(P, num_iter):
+            tune = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+
+        def issue(first, end, rows):
+            nonlocal overlap, tune
+            n_logged = 0
+            for ii in range(first, end):                                                     # :560
+                do_log = is_logging_iteration(ii, num_iter, log_every)
                 st = capi.current_stream()
                 if tune is not None:                     # iterations ii0+2..9 plain, ii0+10..17 with the forward ahead
-                    k = ii - ii0
+                    k = ii - fit.ii0
                     if k in (2, 10, 18):
                         tune[(k - 2) // 8].record()
                     if k == 10:
@@ -473,73 +587,63 @@ class FittingOP:
                         self.exchange_overlap = overlap
                         tune = None
                 if do_log:                               # this iteration's partial sums go straight into their history row
-                    capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(hist[len(logged)])), "fdcap_opt_set_loss_output")
-                    logged.append(ii)
-                if defer and not multi and ii + 1 < self.num_iter:
+                    capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(rows[n_logged])), "fdcap_opt_set_loss_output")
+                    n_logged += 1
+                if defer and not multi and ii + 1 < num_iter:
                     # loss.backward() + optimizer.step() in one call, the step without a launch of its own (fdcap.h): `scale` (and a
                     # logging iteration's printed sums) ride in the backward's last launch, the rows are stepped by the next
                     # iteration's first two launches; whoever reads the registered tensors before that calls fdcap_opt_sync first
-                    # (snapshots below; export_state does it itself)
+                    # (the snapshots; export_state does it itself)
                     capi.check(lib.fdcap_opt_backward_and_step(h, ii, P, 2 if do_log else 0, st), "fdcap_opt_backward_and_step")
-                    stepped = True
-                else:
-                    # (2: the logged sums are delivered by the step launch that follows -- one launch less per logged iteration)
-                    capi.check(lib.fdcap_opt_backward(h, ii, P, 2 if do_log else 0, st), "fdcap_opt_backward")
-                    stepped = False
-                if stepped:
-                    pass
-                elif multi and self._c_comm:
-                    # the same tail inside the library: Adam on the rows + message, ncclAllGather on this stream, unpack + scale
-                    capi.check(lib.fdcap_opt_exchange(h, ii, P, st), "fdcap_opt_exchange")
-                elif multi:
-                    # one collective per iteration: boundary rows (after Adam) + the scale-gradient partial travel
-                    # together; every rank then sums the partials in rank order and steps `scale` identically
-                    capi.check(lib.fdcap_opt_step_rows_and_pack(h, ii, P, capi.dptr(self._xch_send), st), "step_rows_and_pack")
-                    ahead = None
-                    if overlap and ii + 1 < self.num_iter:
-                        # the next iteration's decoder / pose state / blend product of the owned rows need neither `scale`
-                        # nor the halo rows: they run while the messages travel
-                        nxt_log = bool(log_every) and ((ii + 1) % log_every == 0 or ii + 1 == self.num_iter - 1)
+                    continue
+                # (2: the logged sums are delivered by the step launch that follows -- one launch less per logged iteration)
+                capi.check(lib.fdcap_opt_backward(h, ii, P, 2 if do_log else 0, st), "fdcap_opt_backward")
+                ahead = None
+                if overlap and ii + 1 < num_iter:
+                    # the next iteration's decoder / pose state / blend product of the owned rows need neither `scale`
+                    # nor the halo rows: they run while the messages travel
+                    def ahead(ii=ii, st=st):
+                        capi.check(lib.fdcap_opt_forward_ahead(h, ii + 1, P, 2 if is_logging_iteration(ii + 1, num_iter, log_every) else 0, st),
+                                   "fdcap_opt_forward_ahead")
+                self._step(fit, ii, P, ahead)
+        return issue
 
-                        def ahead(ii=ii, nxt_log=nxt_log, st=st):
-                            capi.check(lib.fdcap_opt_forward_ahead(h, ii + 1, P, 2 if nxt_log else 0, st), "fdcap_opt_forward_ahead")
-                    allgather_packed(self.shard, self._xch_send, self._xch_all, ahead)
-                    capi.check(lib.fdcap_opt_unpack_and_step_scale(h, ii, P, capi.dptr(self._xch_all), self.shard.rank,
-                                                                   self.shard.world, st), "unpack_and_step_scale")
-                else:
-                    capi.check(lib.fdcap_opt_step(h, ii, P, st), "fdcap_opt_step")
-                # the reference prints every iteration live (:573-575); a verbose fit shows its progress in batches of
-                # VERBOSE_FLUSH logged iterations (one read-back each) instead of only after the last one
-                if flush_in_loop and do_log and len(logged) - flushed >= VERBOSE_FLUSH:
-                    flush(len(logged))
-                if ii + 1 in snapshot_at:
-                    capi.check(lib.fdcap_opt_sync(h, st), "fdcap_opt_sync")
-                    nl_ = self.shard.n_local
-                    self.snapshots[ii + 1] = (self._rows_x[2:2 + nl_].clone(), self._scale.clone(), self._rows_cam[2:2 + nl_].clone())
-                    if self.snapshot_hook:
-                        self.snapshot_hook(ii + 1)
-                if check_finite_every and (ii + 1) % check_finite_every == 0:
-                    self._check_finite(ii)
-                if checkpoint_every and (ii + 1) % checkpoint_every == 0 and ii + 1 < self.num_iter:
-                    self._save_checkpoint(checkpoint_path, ii + 1)
-        finally:
-            # never leave the library pointing into `hist` (freed with this frame if the loop raised)
-            if logged:
-                capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
-        flush(len(logged))
-        if mode == "local":
-            self._local_second_loop(lib, h, multi, log_every, max(ii0 - self.num_iter, 0))
-        nl = self.shard.n_local
-        body_rec = torch.empty(nl, capi.PDIM, device=dev)
-        scale = torch.empty(1, device=dev)
-        cam = torch.empty(nl, 16, device=dev)
-        capi.check(lib.fdcap_opt_get_results(h, capi.dptr(body_rec), capi.dptr(scale), capi.dptr(cam),
-                                             capi.current_stream()), "fdcap_opt_get_results")
-        self.scale = scale
-        self.camera_ext = cam.view(nl, 4, 4)
-        self.body_rotation_rec = self._rows_x[2:2 + nl]
-        self.log = log
-        return body_rec, scale.detach().cpu().numpy().squeeze(), self.camera_ext
+    def _step(self, fit, ii, P, ahead=None):
+        """After the backward of iteration ii of a loop whose second phase begins at P: the optimiser step.  `ahead`: enqueues work
+        that needs nothing of the exchange, for the time the messages travel (torch.distributed's collectives only)."""
+        lib, h, sh, st = self.ctx.lib, self.ctx.handle, self.shard, capi.current_stream()
+        if fit.multi and self._c_comm:
+            # the tail inside the library: Adam on the rows + message, ncclAllGather on this stream, unpack + scale
+            capi.check(lib.fdcap_opt_exchange(h, ii, P, st), "fdcap_opt_exchange")
+        elif fit.multi:
+            # one collective per iteration: boundary rows (after Adam) + the scale-gradient partial travel
+            # together; every rank then sums the partials in rank order and steps `scale` identically
+            capi.check(lib.fdcap_opt_step_rows_and_pack(h, ii, P, capi.dptr(self._xch_send), st), "step_rows_and_pack")
+            allgather_packed(sh, self._xch_send, self._xch_all, ahead)
+            capi.check(lib.fdcap_opt_unpack_and_step_scale(h, ii, P, capi.dptr(self._xch_all), sh.rank, sh.world, st),
+                       "unpack_and_step_scale")
+        else:
+            capi.check(lib.fdcap_opt_step(h, ii, P, st), "fdcap_opt_step")
+
+    def _append_log(self, log, ii, phase2, s):
+        terms = logged_losses(s, self.num_body, self.ctx.num_contact, self.weight_loss_rec, self.weight_loss_vposer, self.weight_contact,
+                              phase2, self._mode == "local")
+        log.append(ii, terms)
+        shown = [0, 1, 2, 3, 4, 5] if phase2 else [0, 1, 2, 3, 5]         # (phase 1 prints no loss_world_smoothing, :573-575)
+        self._print_row(ii, [MAIN_TERMS[k] for k in shown], [terms[k] for k in shown])
+
+    def _print_row(self, ii, names, values):
+        """the reference's per-iteration print, from rank 0 of a verbose fit"""
+        if self.verbose and self.shard.rank == 0:
+            print('[INFO][fitting] iter={:d}, '.format(ii) + ', '.join('{}={:f}'.format(k, v) for k, v in zip(names, values)))
+
+    def _logged_sums(self, fit):
+        """the partial sums the last backward logged, summed over the ranks, on the host (one sync)"""
+        import torch
+        s = self._losses.clone()
+        if fit.multi:
+            allreduce_scalars(self.shard, torch.zeros(1, device=self.device), s)
+        return s.cpu().numpy()
 
     # ---- checkpoint / resume / finite check (not in the reference; SURVEY §5) ---------------------
     def _ckpt_file(self, path):
@@ -547,14 +651,13 @@ class FittingOP:
 
     def _budget(self):
         """the iteration budget a checkpoint belongs to (mode 'dct' runs its own, :596)"""
-        return int(self.dct_num_iter if getattr(self, "_mode", "global") == "dct" else self.num_iter)
+        return int(self.dct_num_iter if self._mode == "dct" else self.num_iter)
 
     def _save_checkpoint(self, path, next_iter, extra_fn=None, **extra):
         """`extra_fn`: callable returning more arrays for the file (mode 'dct': c_dct and its moments, read from the device).
         EVERYTHING that can fail on one rank alone -- the allocation, the library's state export, the extras' read-back, the
         write -- runs inside the try whose outcome the ranks then agree on (a HIP error or an out-of-memory in the
         export used to raise before the agreement and leave the peers waiting in it)."""
-        import os
         import torch
         lib, h, nl = self.ctx.lib, self.ctx.handle, self.shard.n_local
         fn = self._ckpt_file(path)
@@ -568,7 +671,7 @@ class FittingOP:
             np.savez(tmp, next_iter=np.int64(next_iter), num_iter=np.int64(self._budget()), n_total=np.int64(self.num_body),
                      frame0=np.int64(self.shard.frame0), n_local=np.int64(nl), rows_x=self._rows_x[2:2 + nl].cpu().numpy(),
                      rows_cam=self._rows_cam[2:2 + nl].cpu().numpy(), scale=self._scale.cpu().numpy(), state=state.cpu().numpy(),
-                     mode=np.array(getattr(self, "_mode", "global")),
+                     mode=np.array(self._mode),
                      **{k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in extra.items()})
         except Exception as e:  # noqa: BLE001 -- agreed on below: one rank's failed write must not leave its peers in a collective
             err = e
@@ -588,7 +691,8 @@ class FittingOP:
         os.replace(tmp, fn)                                      # (a crash mid-write leaves the previous checkpoint intact)
 
     def _load_checkpoint(self, path):
-        """After init(): parameters and Adam moments <- the file; returns the iteration to continue with."""
+        """After init(): parameters and Adam moments <- the file; returns (the iteration to continue with, the mode's own arrays in
+        the file -- contact_weight; c_dct, dct_m, dct_v)."""
         import torch
         lib, h, nl = self.ctx.lib, self.ctx.handle, self.shard.n_local
         with np.load(self._ckpt_file(path)) as ck:
@@ -598,7 +702,7 @@ class FittingOP:
             ck_mode = str(ck["mode"]) if "mode" in ck.files else "global"
             if ck_mode != self._mode:
                 raise capi.FdcapError(f"checkpoint was written by a mode {ck_mode!r} fit, this is mode {self._mode!r}")
-            self._ck_extra = {k: np.array(ck[k]) for k in ("contact_weight", "c_dct", "dct_m", "dct_v") if k in ck.files}
+            extra = {k: np.array(ck[k]) for k in ("contact_weight", "c_dct", "dct_m", "dct_v") if k in ck.files}
             t = lambda k: torch.from_numpy(np.ascontiguousarray(ck[k], dtype=np.float32)).to(self.device)
             self._rows_x[2:2 + nl] = t("rows_x")
             self._rows_cam[2:2 + nl] = t("rows_cam")
@@ -614,7 +718,7 @@ class FittingOP:
         capi.check(lib.fdcap_opt_import_state(h, capi.dptr(state), capi.current_stream()), "fdcap_opt_import_state")
         torch.cuda.current_stream().synchronize()
         self._halos()
-        return nxt
+        return nxt, extra
 
     def _check_finite(self, ii):
         import torch
@@ -628,194 +732,161 @@ class FittingOP:
         if bad:
             raise capi.FdcapError(f"{bad} non-finite optimiser parameters after iteration {ii}")
 
-    # ---- :595-630 -------------------------------------------------------------------------
-    def _dct_loops(self, lib, h, multi, log_every, ii0=0):
+    # ---- mode 'dct' (:595-630) ---------------------------------------------------------------
+    def _dct_loops(self, fit):
         """mode 'dct'.  First 95 % of the iterations: only c_dct moves (loss_dct*10, :601-607) against frozen
         joint trajectories -- ONE launch; iteration ceil(0.95*num_iter) is a no-op (every leaf's flag was
         flipped after its forward, :615-618, so nothing receives a gradient); the rest optimise
-        body_rotation_rec + scale with loss_dct*1e-4 + loss_rec*0.5 + loss_contact*0.1 (:620)."""
+        body_rotation_rec + scale with loss_dct*1e-4 + loss_rec*0.5 + loss_contact*0.1 (:620).
+        Sharded: every rank fits its own windows and ends up with all windows' coefficients (_dct_merge_windows)."""
         import torch
-        # legacy_zero_grad (torch < 2: zero_grad() zeroes gradients instead of dropping them): body / scale / camera never
-        # hold a gradient before the switch, so the first phase is the same; from iteration ceil(0.95 num_iter) on the
-        # frozen c_dct keeps a zero gradient and Adam keeps stepping it on its decaying moments (SURVEY A15).
-        legacy = self.legacy_zero_grad
-        N, T, dev = self.num_body, BATCH_FRAME_NUM, self.device
+        d = self._dct_setup(fit)
+        self._dct_first_phase(fit, d)
+        if fit.multi and fit.ii0 <= d.P:                       # (a checkpoint from after the phase holds merged coefficients)
+            self._dct_merge_windows(d)
+        self._dct_second_phase(fit, d)
+        if fit.multi and self.legacy_zero_grad:                # (each rank coasted its own windows)
+            self._dct_merge_windows(d)
+        cd = torch.empty(d.W, 23, 3, d.C, device=self.device)
+        capi.check(self.ctx.lib.fdcap_opt_get_dct(self.ctx.handle, capi.dptr(cd), capi.current_stream()), "fdcap_opt_get_dct")
+        self.c_dct = cd
+
+    def _dct_setup(self, fit):
+        """The refusals, the basis and c_dct (with its Adam moments as an interrupted fit left them) registered -> W windows of C
+        coefficients, the second phase's first iteration P, `own`: the windows this rank fits."""
+        import torch
+        lib, h, st = self.ctx.lib, self.ctx.handle, capi.current_stream()
+        N, T, dev, sh = self.num_body, BATCH_FRAME_NUM, self.device, self.shard
         W = N // T
         if W < 1:
             raise capi.FdcapError(f"mode 'dct' needs at least one {T}-frame window (:41-42); clip has {N} frames")
-        sh = self.shard
-        if multi and any(sh.bounds(r)[0] % T for r in range(sh.world)):
+        if fit.multi and any(sh.bounds(r)[0] % T for r in range(sh.world)):
             raise capi.FdcapError(f"mode 'dct': frame shards must start on {T}-frame window boundaries "
                                   f"(N={N}, world={sh.world})")
         if self.dct_mtx is None:
             self.dct_mtx = io.load_dct_base(getattr(self, "dct_mat_path", None), T, DCT_NUM)
         D = np.ascontiguousarray(self.dct_mtx, np.float32)
         C = D.shape[1]
-        ck_every, ck_path, finite_every = getattr(self, "_ck", (0, None, 0))
-        ex = getattr(self, "_ck_extra", {})
-        resumed = "c_dct" in ex
-        if ii0 and not resumed:
+        resumed = "c_dct" in fit.resumed
+        if fit.ii0 and not resumed:
             raise capi.FdcapError("the checkpoint holds no c_dct: not written by a mode 'dct' fit")
-        if ii0 and log_every and ii0 % log_every:
-            raise ValueError(f"mode 'dct': resuming at iteration {ii0} needs a log_every that divides it")
-        c0 = ex["c_dct"] if resumed else self._c_dct_init
-        c0 = torch.randn(W, 23, 3, C) if c0 is None else torch.as_tensor(np.asarray(c0, dtype=np.float32).reshape(W, 23, 3, -1))
-        if tuple(c0.shape) != (W, 23, 3, C):
-            raise capi.FdcapError(f"c_dct_init must be [{W},23,3,{C}], got {tuple(c0.shape)}")
-        c0 = c0.to(dev, torch.float32).contiguous()
-        st = capi.current_stream()
-        import ctypes
+        if fit.ii0 and fit.log_every and fit.ii0 % fit.log_every:
+            raise ValueError(f"mode 'dct': resuming at iteration {fit.ii0} needs a log_every that divides it")
+        c0 = _c_dct_start(fit.resumed["c_dct"] if resumed else self._c_dct_init, W, C).to(dev, torch.float32).contiguous()
         capi.check(lib.fdcap_opt_set_dct(h, D.ctypes.data_as(ctypes.c_void_p), D.shape[0], C, capi.dptr(c0), st),
                    "fdcap_opt_set_dct")
-        if resumed:                                            # Adam's moments of c_dct as the interrupted fit left them
-            dm = torch.as_tensor(ex["dct_m"]).to(dev, torch.float32).contiguous()
-            dv = torch.as_tensor(ex["dct_v"]).to(dev, torch.float32).contiguous()
+        if resumed:
+            dm, dv = (torch.as_tensor(fit.resumed[k]).to(dev, torch.float32).contiguous() for k in ("dct_m", "dct_v"))
             capi.check(lib.fdcap_opt_set_dct_state(h, capi.dptr(dm), capi.dptr(dv), st), "fdcap_opt_set_dct_state")
-        num_iter = self.dct_num_iter
-        P = int(math.ceil(num_iter * DCT_PHASE_SPLIT - 1e-9))           # first ii with not (ii < num_iter*0.95)
         w0, w1 = ctypes.c_int32(), ctypes.c_int32()
         lib.fdcap_opt_dct_windows(h, ctypes.byref(w0), ctypes.byref(w1))
-        ntraj = 69 * (w1.value - w0.value)
+        return SimpleNamespace(W=W, C=C, P=dct_first_phase2_iter(self.dct_num_iter), own=slice(w0.value, w1.value))
 
-        def save(next_iter):                                   # parameters + Adam moments + c_dct with ITS moments
-            def dct_state():                                   # (runs inside _save_checkpoint's agreed-on try)
-                cd_ = torch.empty(W, 69 * C, device=dev)
-                dm_, dv_ = torch.empty_like(cd_), torch.empty_like(cd_)
-                capi.check(lib.fdcap_opt_get_dct(h, capi.dptr(cd_), capi.current_stream()), "fdcap_opt_get_dct")
-                capi.check(lib.fdcap_opt_get_dct_state(h, capi.dptr(dm_), capi.dptr(dv_), capi.current_stream()), "fdcap_opt_get_dct_state")
-                return {"c_dct": cd_, "dct_m": dm_, "dct_v": dv_}
-            self._save_checkpoint(ck_path, next_iter, extra_fn=dct_state)
+    def _save_dct_checkpoint(self, fit, d, next_iter):
+        """parameters + Adam moments + c_dct with ITS moments (read inside _save_checkpoint's agreed-on try)"""
+        self._save_checkpoint(fit.ck_path, next_iter, extra_fn=lambda: self._dct_state(d.W, d.C))
 
-        # first phase [ii0, P): ONE launch -- or one per stretch between two checkpoint iterations (the launch keeps coefficients
-        # and moments in registers and writes them back at its end; Adam's step counter runs on through step0: same bits)
+    def _dct_first_phase(self, fit, d):
+        """Iterations [ii0, P): ONE launch -- or one per stretch between two checkpoint / finite-check iterations (the launch keeps
+        coefficients and moments in registers and writes them back at its end; Adam's step counter runs on through step0: same
+        bits).  Leaves its objective history in self.log_dct."""
+        import torch
+        lib, h, st = self.ctx.lib, self.ctx.handle, capi.current_stream()
+        ii0, P, log_every = fit.ii0, d.P, fit.log_every
+        ntraj = 69 * (d.own.stop - d.own.start)
         hist = None
         if log_every and ntraj and P > ii0:
-            hist = torch.zeros((P - ii0 + log_every - 1) // log_every, ntraj, device=dev)
-        def check_dct_finite(done):                            # phase 1 moves only c_dct: count ITS non-finite entries (and its moments')
-            cd_ = torch.empty(W, 69 * C, device=dev)
-            dm_, dv_ = torch.empty_like(cd_), torch.empty_like(cd_)
-            capi.check(lib.fdcap_opt_get_dct(h, capi.dptr(cd_), capi.current_stream()), "fdcap_opt_get_dct")
-            capi.check(lib.fdcap_opt_get_dct_state(h, capi.dptr(dm_), capi.dptr(dv_), capi.current_stream()), "fdcap_opt_get_dct_state")
-            own = slice(w0.value, w1.value)                    # (sharded: the windows this rank fits)
-            bad = sum((~torch.isfinite(t[own])).sum() for t in (cd_, dm_, dv_)).to(torch.float32).reshape(1)
-            if multi:
-                allreduce_scalars(sh, bad)
-            if int(bad.cpu()):
-                raise capi.FdcapError(f"{int(bad.cpu())} non-finite DCT coefficients / Adam moments after iteration {done - 1}")
-
+            hist = torch.zeros((P - ii0 + log_every - 1) // log_every, ntraj, device=self.device)
         # (a stretch's logged rows are counted from its first iteration: a cut must fall on a logging iteration -- checkpoints
         #  already require it; the finite check of this phase therefore runs every lcm(check_finite_every, log_every) iterations)
-        finite_cut = (finite_every * log_every // math.gcd(finite_every, log_every)) if (finite_every and log_every) else finite_every
+        finite_cut = math.lcm(fit.finite_every, log_every) if (fit.finite_every and log_every) else fit.finite_every
         ii = ii0
         while ii < P:
             end = P                                            # cut at the next checkpoint / finite-check iteration, if any
-            for every in (ck_every, finite_cut):
+            for every in (fit.ck_every, finite_cut):
                 if every:
                     end = min(end, (ii // every + 1) * every)
             row = capi.dptr(hist[(ii - ii0) // log_every]) if hist is not None else None
             capi.check(lib.fdcap_opt_dct_fit(h, end - ii, ii, DCT_PHASE1_WEIGHT, row, max(int(log_every), 1), st), "fdcap_opt_dct_fit")
             ii = end
             if finite_cut and (ii % finite_cut == 0 or ii == P):
-                check_dct_finite(ii)
-            if ck_every and ii % ck_every == 0 and ii < num_iter:
-                save(ii)                                       # (sharded: every rank's own windows; merged after the phase, below)
+                self._check_dct_finite(fit, d, ii)
+            if fit.ck_every and ii % fit.ck_every == 0 and ii < self.dct_num_iter:
+                self._save_dct_checkpoint(fit, d, ii)          # (sharded: every rank's own windows; merged after the phase)
         self.log_dct = []
         if hist is not None:
             part = hist.sum(dim=1, dtype=torch.float64)
-            if multi:
-                allreduce_scalars(sh, torch.zeros(1, device=dev), part)
-            self.log_dct = [[ii0 + k * log_every, float(v) / (69 * W)] for k, v in enumerate(part.cpu().numpy())]
+            if fit.multi:
+                allreduce_scalars(self.shard, torch.zeros(1, device=self.device), part)
+            self.log_dct = [[ii0 + k * log_every, float(v) / (69 * d.W)] for k, v in enumerate(part.cpu().numpy())]
 
-        def merge_windows():                                   # every rank ends up with all windows' coefficients
-            import torch.distributed as dist
-            full = torch.zeros(W, 69 * C, device=dev)
-            capi.check(lib.fdcap_opt_get_dct(h, capi.dptr(full), capi.current_stream()), "fdcap_opt_get_dct")
-            own = torch.zeros_like(full)
-            own[w0.value:w1.value] = full[w0.value:w1.value]
-            if dist.get_backend(self.group) == "gloo":
-                t = own.cpu(); dist.all_reduce(t, group=self.group); own = t.to(dev)
-            else:
-                dist.all_reduce(own, group=self.group)
-            capi.check(lib.fdcap_opt_set_dct_coef(h, capi.dptr(own.contiguous()), capi.current_stream()), "fdcap_opt_set_dct_coef")
+    def _check_dct_finite(self, fit, d, done):
+        """the first phase moves only c_dct: count ITS non-finite entries (and its moments') in this rank's windows"""
+        import torch
+        bad = sum((~torch.isfinite(t[d.own])).sum() for t in self._dct_state(d.W, d.C).values()).to(torch.float32).reshape(1)
+        if fit.multi:
+            allreduce_scalars(self.shard, bad)
+        if int(bad.cpu()):
+            raise capi.FdcapError(f"{int(bad.cpu())} non-finite DCT coefficients / Adam moments after iteration {done - 1}")
 
-        if multi and ii0 <= P:                                 # (a checkpoint from after the phase holds merged coefficients)
-            merge_windows()
-        if legacy and num_iter > P and ii0 <= P:               # iteration P: nothing receives a gradient, c_dct coasts
-            capi.check(lib.fdcap_opt_dct_fit(h, 1, P, 0.0, None, 1, st), "fdcap_opt_dct_fit")
-        BIG = 2 ** 30
+    def _dct_merge_windows(self, d):
+        """every rank ends up with all windows' coefficients"""
+        import torch
+        lib, h = self.ctx.lib, self.ctx.handle
+        full = torch.zeros(d.W, 69 * d.C, device=self.device)
+        capi.check(lib.fdcap_opt_get_dct(h, capi.dptr(full), capi.current_stream()), "fdcap_opt_get_dct")
+        own = torch.zeros_like(full)
+        own[d.own] = full[d.own]
+        own = staged_collective(self.group, own)
+        capi.check(lib.fdcap_opt_set_dct_coef(h, capi.dptr(own.contiguous()), capi.current_stream()), "fdcap_opt_set_dct_coef")
+
+    def _dct_second_phase(self, fit, d):
+        """Iterations P+1 .. of the budget (P itself moves nothing); leaves their printed rows in self.log2.
+        legacy_zero_grad (torch < 2: zero_grad() zeroes gradients instead of dropping them): body / scale / camera never
+        hold a gradient before the switch, so the first phase is the same; from iteration P on the frozen c_dct keeps a zero
+        gradient and Adam keeps stepping it on its decaying moments."""
+        lib, h = self.ctx.lib, self.ctx.handle
+        num_iter, P, legacy = self.dct_num_iter, d.P, self.legacy_zero_grad
+        if legacy and num_iter > P and fit.ii0 <= P:           # iteration P: nothing receives a gradient, c_dct coasts
+            capi.check(lib.fdcap_opt_dct_fit(h, 1, P, 0.0, None, 1, capi.current_stream()), "fdcap_opt_dct_fit")
         wd, wr, wc = DCT_PHASE2
         self.log2 = []
-        for k in range(max(ii0 - P - 1, 0), max(num_iter - P - 1, 0)):     # ii = P + 1 + k; Adam step counters k + 1
+        for k in range(max(fit.ii0 - P - 1, 0), max(num_iter - P - 1, 0)):     # ii = P + 1 + k; Adam step counters k + 1
             ii = P + 1 + k
-            do_log = bool(log_every) and (ii % log_every == 0 or ii == num_iter - 1)
             st = capi.current_stream()
+            do_log = is_logging_iteration(ii, num_iter, fit.log_every)
             capi.check(lib.fdcap_opt_backward_dct(h, wd, wr, wc, 1 if do_log else 0, st), "fdcap_opt_backward_dct")
             if do_log:
-                s = self._losses.clone()
-                if multi:
-                    allreduce_scalars(sh, torch.zeros(1, device=dev), s)
-                s = s.cpu().numpy()
-                nc = max(self.ctx.num_contact, 1)
-                l_rec = self.weight_loss_rec * s[0] / (N * capi.XDIM)
-                l_vp = self.weight_loss_vposer * s[1] / (N * 32)
-                l_sm = s[2] / ((N - 2) * capi.XDIM) if N >= 3 else float("nan")
-                l_con = self.weight_contact * s[3] / (N * nc)
-                l_dct = s[7] / (69 * W)
-                self.log2.append([ii, l_rec, l_vp, l_sm, l_con, l_dct, wd * l_dct + wr * l_rec + wc * l_con])
-                if self.verbose and sh.rank == 0:
-                    print('[INFO][fitting] iter={:d}, l_rec={:f}, l_vposer={:f}, loss_smoothing={:f}, loss_contact={:f}, '
-                          'loss_dct={:f}, total_loss={:f}'.format(*self.log2[-1]))
-            if multi and self._c_comm:
-                capi.check(lib.fdcap_opt_exchange(h, k, BIG, st), "fdcap_opt_exchange")
-            elif multi:
-                capi.check(lib.fdcap_opt_step_rows_and_pack(h, k, BIG, capi.dptr(self._xch_send), st), "step_rows_and_pack")
-                allgather_packed(sh, self._xch_send, self._xch_all)
-                capi.check(lib.fdcap_opt_unpack_and_step_scale(h, k, BIG, capi.dptr(self._xch_all), sh.rank, sh.world, st),
-                           "unpack_and_step_scale")
-            else:
-                capi.check(lib.fdcap_opt_step(h, k, BIG, st), "fdcap_opt_step")
+                self.log2.append([ii, *dct2_losses(self._logged_sums(fit), self.num_body, d.W, self.ctx.num_contact, self.weight_loss_rec,
+                                                   self.weight_loss_vposer, self.weight_contact)])
+                self._print_row(ii, DCT2_TERMS, self.log2[-1][1:])
+            self._step(fit, k, 2 ** 30)                        # (a phase split never reached: `scale` is stepped throughout)
             if legacy:                                         # optimizer.step() of this iteration also moves the frozen c_dct
                 capi.check(lib.fdcap_opt_dct_fit(h, 1, ii, 0.0, None, 1, st), "fdcap_opt_dct_fit")
-            if finite_every and (ii + 1) % finite_every == 0:
+            if fit.finite_every and (ii + 1) % fit.finite_every == 0:
                 self._check_finite(ii)
-            if ck_every and (ii + 1) % ck_every == 0 and ii + 1 < num_iter:
-                save(ii + 1)
-        if multi and legacy:                                   # (each rank coasted its own windows)
-            merge_windows()
-        cd = torch.empty(W, 23, 3, C, device=dev)
-        capi.check(lib.fdcap_opt_get_dct(h, capi.dptr(cd), capi.current_stream()), "fdcap_opt_get_dct")
-        self.c_dct = cd
+            if fit.ck_every and (ii + 1) % fit.ck_every == 0 and ii + 1 < num_iter:
+                self._save_dct_checkpoint(fit, d, ii + 1)
 
-    def _local_second_loop(self, lib, h, multi, log_every, jj0=0):
-        """detect_contact + the cal_loss2 loop of mode 'local' (:534-556).  jj0 > 0: resumed inside this loop -- the contact
-        weights (a function of the parameters as the FIRST loop left them) come from the checkpoint."""
+    # ---- mode 'local' (:534-556) -------------------------------------------------------------
+    def _local_second_loop(self, fit):
+        """detect_contact + the cal_loss2 loop of mode 'local' (:534-556).  Resumed inside this loop (the fit's iterations count on
+        from num_iter): the contact weights (a function of the parameters as the FIRST loop left them) come from the checkpoint."""
         import torch
-        nl = self.shard.n_local
-        ck_every, ck_path, finite_every = getattr(self, "_ck", (0, None, 0))
-        ex = getattr(self, "_ck_extra", {})
-        if jj0 and "contact_weight" not in ex:
+        lib, h = self.ctx.lib, self.ctx.handle
+        sh, log_every = self.shard, fit.log_every
+        jj0 = max(fit.ii0 - self.num_iter, 0)
+        if jj0 and "contact_weight" not in fit.resumed:
             raise capi.FdcapError("the checkpoint holds no contact weights: not written inside mode 'local''s second loop")
-        w_local = torch.empty(nl, device=self.device)
         if jj0:
-            weight = torch.as_tensor(ex["contact_weight"]).to(self.device, torch.float32).contiguous()
+            weight = torch.as_tensor(fit.resumed["contact_weight"]).to(self.device, torch.float32).contiguous()
         else:
-            capi.check(lib.fdcap_opt_detect_contact(h, self.n_left, capi.dptr(w_local), capi.current_stream()),
+            weight = torch.empty(sh.n_local, device=self.device)
+            capi.check(lib.fdcap_opt_detect_contact(h, self.n_left, capi.dptr(weight), capi.current_stream()),
                        "fdcap_opt_detect_contact")
-        if jj0:
-            pass
-        elif multi:                                            # every rank needs the weight of its right neighbour's first frame
-            import torch.distributed as dist
-            parts = [torch.empty(self.shard.bounds(r)[1] - self.shard.bounds(r)[0], device=self.device)
-                     for r in range(self.shard.world)]
-            if dist.get_backend(self.group) == "gloo":
-                cpu_parts = [p.cpu() for p in parts]
-                dist.all_gather(cpu_parts, w_local.cpu(), group=self.group)
-                parts = [p.to(self.device) for p in cpu_parts]
-            else:
-                dist.all_gather(parts, w_local, group=self.group)
-            weight = torch.cat(parts).contiguous()
-        else:
-            weight = w_local
+            if fit.multi:                                      # every rank needs the weight of its right neighbour's first frame
+                parts = [torch.empty(sh.bounds(r)[1] - sh.bounds(r)[0], device=self.device) for r in range(sh.world)]
+                weight = torch.cat(staged_collective(self.group, weight, parts)).contiguous()
         self.contact_weight = weight
         self.log2 = []
         n2 = int(LOCAL_SECOND_LOOP * self.num_iter)
@@ -823,43 +894,16 @@ class FittingOP:
             st = capi.current_stream()
             capi.check(lib.fdcap_opt_backward_local2(h, capi.dptr(weight), self.n_left, st), "fdcap_opt_backward_local2")
             if log_every and (jj % log_every == 0):
-                s = self._losses.clone()
-                if multi:
-                    allreduce_scalars(self.shard, torch.zeros(1, device=self.device), s)
-                s = s.cpu().numpy()
-                N = self.num_body
-                l_rec = self.weight_loss_rec * s[0] / (N * capi.XDIM)
-                l_loc = s[2] / ((N - 2) * capi.XDIM)
-                l_sm = s[5] / ((N - 2) * 3 * self.ctx.num_verts)
-                l_cs = s[6]
-                self.log2.append([jj, l_rec, l_loc, l_sm, l_cs, l_sm + l_loc + l_rec + l_cs])
-                if self.verbose and self.shard.rank == 0:
-                    print('[INFO][fitting] iter={:d}, l_rec={:f}, loss_local_smoothing={:f}, loss_smoothing={:f}, '
-                          'loss_contact_smoothing={:f}, total_loss={:f}'.format(*self.log2[-1]))
+                self.log2.append([jj, *local2_losses(self._logged_sums(fit), self.num_body, self.ctx.num_verts, self.weight_loss_rec)])
+                self._print_row(jj, LOCAL2_TERMS, self.log2[-1][1:])
             capi.check(lib.fdcap_opt_step_x(h, self.num_iter + jj + 1, st), "fdcap_opt_step_x")
-            if multi:
+            if fit.multi:
                 self._halos()
             done = self.num_iter + jj + 1                    # iterations of the whole fit made so far
-            if finite_every and done % finite_every == 0:
+            if fit.finite_every and done % fit.finite_every == 0:
                 self._check_finite(done - 1)
-            if ck_every and done % ck_every == 0 and jj + 1 < n2:
-                self._save_checkpoint(ck_path, done, contact_weight=weight)
-
-    def _append_log(self, log, ii, phase2, s=None):
-        s = self._losses.cpu().numpy() if s is None else s
-        local = getattr(self, "_mode", "global") == "local"
-        l_rec, l_vp, l_sm, l_con, l_ws, total = logged_losses(s, self.num_body, self.ctx.num_contact, self.weight_loss_rec,
-                                                              self.weight_loss_vposer, self.weight_contact, phase2, local)
-        log.iters.append(ii); log.l_rec.append(l_rec); log.l_vposer.append(l_vp)
-        log.loss_smoothing.append(l_sm); log.loss_contact.append(l_con)
-        log.loss_world_smoothing.append(l_ws); log.total.append(total)
-        if self.verbose and self.shard.rank == 0:
-            if phase2:
-                print('[INFO][fitting] iter={:d}, l_rec={:f}, l_vposer={:f}, loss_smoothing={:f}, loss_contact={:f}, '
-                      'loss_world_smoothing={:f}, total_loss={:f}'.format(ii, l_rec, l_vp, l_sm, l_con, l_ws, total))
-            else:
-                print('[INFO][fitting] iter={:d}, l_rec={:f}, l_vposer={:f}, loss_smoothing={:f}, loss_contact={:f}, '
-                      'total_loss={:f}'.format(ii, l_rec, l_vp, l_sm, l_con, total))
+            if fit.ck_every and done % fit.ck_every == 0 and jj + 1 < n2:
+                self._save_checkpoint(fit.ck_path, done, contact_weight=weight)
 
     # ---- :637-653 -------------------------------------------------------------------------
     def save_result(self, body_rec, scale, camera_ext, fit_path):
@@ -874,7 +918,7 @@ class FittingOP:
             self.ctx = None
 
 
-class ClipBatchFitter:
+class ClipBatchFitter(_Fitter):
     """Several clips of one scene as ONE optimisation (fdcap_opt_create_clips): K clips share the scene, the contact ids, the
     body model, VPoser and the configuration; each keeps its own rows, `scale`, Adam moments, outlier set, loss means (over its
     own frames) and logged sums, and the temporal stencils are cut at clip boundaries.  The clips may have different lengths
@@ -891,43 +935,15 @@ class ClipBatchFitter:
     fdcap_opt_set_dct_clips + ONE fdcap_opt_run_dct call of `dct_num_iter` iterations: every clip has its own 60-frame windows over
     its own frames (so at least 60 frames), and the first phase is one launch over all clips' trajectories; it leaves each clip's
     c_dct [W_k,23,3,C] in self.c_dct, its first-phase log in self.logs_dct and its second-phase log in self.logs2."""
+    _n_left_from_files = False      # (the left part is half of the contact ids unless `n_left` says otherwise)
 
     def __init__(self, fittingconfig, lossconfig, body_model=None, vposer=None, contact_ids=None, legacy_zero_grad=False, n_left=None,
                  dct_num_iter=DCT_NUM_ITER):
-        import torch
-        cfg = dict(DEFAULT_FITTINGCONFIG)
-        cfg.update(fittingconfig or {})
-        lcfg = dict(DEFAULT_LOSSCONFIG)
-        lcfg.update(lossconfig or {})
-        for k, v in cfg.items():
-            setattr(self, k, v)
-        for k, v in lcfg.items():
-            setattr(self, k, v)
-        self.legacy_zero_grad = bool(legacy_zero_grad)
-        if not torch.cuda.is_available():
-            raise capi.FdcapError("no HIP device: the fdcap_amd optimiser only runs on the GPU")
-        self.device = torch.device("cuda", torch.cuda.current_device())
-        if body_model is None or vposer is None:
-            from . import assets
-            body_model = body_model or assets.load_smplx_npz(self.human_model_path)
-            vposer = vposer or assets.load_vposer_snapshot(self.vposer_ckpt_path)
-        self.ctx = capi.Context(body_model, vposer)
-        if contact_ids is None:
-            contact_ids = np.concatenate([io.read_contact_ids(self.contact_id_folder, [p]) for p in self.contact_part])
-        self.vid = np.asarray(contact_ids, dtype=np.int64)
-        # mode 'local' treats the two contact parts separately (L_Leg ids first, :341-347), as FittingOP
-        self.n_left = int(n_left) if n_left is not None else len(self.vid) // 2
+        super().__init__(fittingconfig, lossconfig, body_model, vposer, contact_ids, n_left, legacy_zero_grad, dct_num_iter)
         self.ctx.set_contact_ids(self.vid)
         self.scene_key = None
         self._has_opt = False
-        self._mode = "global"
-        self.logs = []
-        self.logs2 = []
-        self.contact_weights = []
-        self.idx1 = []
-        self.dct_num_iter = int(dct_num_iter)
-        self.c_dct = []
-        self.logs_dct = []
+        self.logs, self.logs2, self.logs_dct, self.contact_weights, self.idx1, self.c_dct = [], [], [], [], [], []      # (a batch's results)
         self._dct_in = (None, None)
 
     def _destroy_opt(self):
@@ -973,12 +989,10 @@ class ClipBatchFitter:
     def prepare(self, clips, mode="global", c_dct_init=None, dct_mtx=None):
         """init() of a batch (:450-489 per clip): creates the batch's optimiser on the registered scene and stages its inputs.
         mode 'local': the config of its first loop (:511, :523), as FittingOP.init builds it; mode 'dct': mode 'global''s, as there."""
-        import ctypes
         import torch
         self._check_mode(clips, mode)
         self._mode = mode
         self._dct_in = (c_dct_init, dct_mtx)
-        local = mode == "local"
         K = len(clips)
         if K < 1:
             raise ValueError("a batch needs at least one clip")
@@ -1008,25 +1022,12 @@ class ClipBatchFitter:
         self.idx1 = [i[0] for i in ins]
         # one length: the clip's frames, as fdcap_opt_create_clips takes it; different lengths: the batch's rows
         n_cfg = lens[0] if equal else total
-        oc = capi.OptConfig(n_cfg, n_cfg, 0, float(self.init_lr_h), float(self.weight_loss_rec), float(self.weight_loss_vposer),
-                            float(self.weight_contact), LOCAL_PHASE1_CONTACT if local else PHASE1_CONTACT, PHASE1_SMOOTH,
-                            0.0 if local else PHASE2_WORLD, PHASE2_SMOOTH, SCALE_INIT, int(self.legacy_zero_grad))
-        R = total + 4
-        self._rows_x = torch.zeros(R, capi.XDIM, device=dev)
-        self._rows_cam = torch.zeros(R, 16, device=dev)
-        self._scale = torch.zeros(K, device=dev)
-        self._dscale = torch.zeros(K, device=dev)
-        self._losses = torch.zeros(K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
-        torch.cuda.current_stream().synchronize()
+        oc = self._opt_config(n_cfg, n_cfg, 0)
+        state = self._new_state(total + 4, K, (K, capi.NUM_LOSSES))
         if equal:
-            capi.check(lib.fdcap_opt_create_clips(h, ctypes.byref(oc), K, capi.dptr(self._rows_x), capi.dptr(self._rows_cam),
-                                                  capi.dptr(self._scale), capi.dptr(self._dscale), capi.dptr(self._losses)),
-                       "fdcap_opt_create_clips")
+            capi.check(lib.fdcap_opt_create_clips(h, ctypes.byref(oc), K, *state), "fdcap_opt_create_clips")
         else:
-            clip_len = (ctypes.c_int32 * K)(*lens)
-            capi.check(lib.fdcap_opt_create_clips_var(h, ctypes.byref(oc), K, clip_len, capi.dptr(self._rows_x), capi.dptr(self._rows_cam),
-                                                      capi.dptr(self._scale), capi.dptr(self._dscale), capi.dptr(self._losses)),
-                       "fdcap_opt_create_clips_var")
+            capi.check(lib.fdcap_opt_create_clips_var(h, ctypes.byref(oc), K, (ctypes.c_int32 * K)(*lens), *state), "fdcap_opt_create_clips_var")
         self._has_opt = True
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         d_init = t(np.concatenate([i[1] for i in ins]))
@@ -1039,84 +1040,71 @@ class ClipBatchFitter:
 
     def run(self, log_every=0):
         """The loop of the prepared batch (:558-593) and its results (see fit)."""
-        import ctypes
-        import os
         import torch
-        K, lens, starts, dev = self.num_clips, self.clip_lens, self.clip_starts, self.device
-        total = starts[-1]
-        lib, h = self.ctx.lib, self.ctx.handle
-        st = capi.current_stream()
         if self._mode == "dct":
             return self._run_dct(log_every)
+        K, lens = self.num_clips, self.clip_lens
+        lib, h = self.ctx.lib, self.ctx.handle
         # the loop in the library, as FittingOP.fitting runs a plain fit: one fdcap_opt_run for all iterations
         num_iter = int(self.num_iter)
         P = first_phase2_iter(num_iter)
         logged = [ii for ii in range(num_iter) if is_logging_iteration(ii, num_iter, log_every)]
-        hist = torch.zeros(max(len(logged), 1), K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
-        defer = os.environ.get("FDCAP_DEFER_STEP", "1") != "0"
-        n_done = ctypes.c_int32(0)
+        hist = torch.zeros(max(len(logged), 1), K, capi.NUM_LOSSES, device=self.device, dtype=torch.float64)
         try:
-            capi.check(lib.fdcap_opt_run(h, 0, num_iter, num_iter, P, int(log_every or 0), capi.dptr(hist) if logged else None,
-                                         len(logged), 0 if defer else 1, ctypes.byref(n_done), st), "fdcap_opt_run")
+            self._opt_run(0, num_iter, P, log_every, hist if logged else None)
         finally:
             if logged:
                 capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
-        assert n_done.value == len(logged)
         local = self._mode == "local"
         self.logs2, self.contact_weights = [], []
         if local:
-            # detect_contact + the cal_loss2 loop (:534-556) of every clip in one call; its history is read back once, below
-            n2 = int(LOCAL_SECOND_LOOP * num_iter)
-            logged2 = [jj for jj in range(n2) if log_every and jj % log_every == 0]
-            hist2 = torch.zeros(max(len(logged2), 1), K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
-            weight = torch.empty(total, device=dev)
-            try:
-                capi.check(lib.fdcap_opt_run_local2(h, self.n_left, 0, n2, num_iter, int(log_every or 0), capi.dptr(weight),
-                                                    capi.dptr(hist2) if logged2 else None, len(logged2), 0, ctypes.byref(n_done), st),
-                           "fdcap_opt_run_local2")
-            finally:
-                capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
-            assert n_done.value == len(logged2)
-            rows2 = hist2.cpu().numpy()
-            self.contact_weights = [weight[starts[k]:starts[k + 1]] for k in range(K)]
-            nv3 = 3 * self.ctx.num_verts
-            with np.errstate(divide="ignore", invalid="ignore"):     # (a mean over nothing prints as NaN, as in a stand-alone fit)
-                for k in range(K):
-                    n = np.float64(lens[k])
-                    log2 = []
-                    for j, jj in enumerate(logged2):
-                        s = rows2[j, k]
-                        l_rec = self.weight_loss_rec * s[0] / (n * capi.XDIM)
-                        l_loc = s[2] / ((n - 2) * capi.XDIM)
-                        l_sm = s[5] / ((n - 2) * nv3)
-                        l_cs = s[6]
-                        log2.append([jj, l_rec, l_loc, l_sm, l_cs, l_sm + l_loc + l_rec + l_cs])
-                    self.logs2.append(log2)
-        body_rec = torch.empty(total, capi.PDIM, device=dev)
-        scale = torch.empty(K, device=dev)
-        cam = torch.empty(total, 16, device=dev)
-        capi.check(lib.fdcap_opt_get_results(h, capi.dptr(body_rec), capi.dptr(scale), capi.dptr(cam), st), "fdcap_opt_get_results")
+            self._run_local2(log_every)
+        results = self._results(self.clip_starts[-1], K)
         rows = hist.cpu().numpy()
         self.logs = []
         for k in range(K):
-            log = FitLog([], [], [], [], [], [], [])
+            log = FitLog()
             for j, ii in enumerate(logged):
                 # (the printed means of a clip run over its own frames)
-                l_rec, l_vp, l_sm, l_con, l_ws, tot = logged_losses(rows[j, k], lens[k], self.ctx.num_contact, self.weight_loss_rec,
-                                                                    self.weight_loss_vposer, self.weight_contact, ii >= P, local)
-                log.iters.append(ii); log.l_rec.append(l_rec); log.l_vposer.append(l_vp)
-                log.loss_smoothing.append(l_sm); log.loss_contact.append(l_con)
-                log.loss_world_smoothing.append(l_ws); log.total.append(tot)
+                log.append(ii, logged_losses(rows[j, k], lens[k], self.ctx.num_contact, self.weight_loss_rec, self.weight_loss_vposer,
+                                             self.weight_contact, ii >= P, local))
             self.logs.append(log)
+        return self._per_clip(*results)
+
+    def _per_clip(self, body_rec, scale, cam):
+        """the batch's results -> each clip's triple, as FittingOP.fitting returns it"""
+        lens, starts = self.clip_lens, self.clip_starts
         sc = scale.cpu().numpy()
-        return [(body_rec[starts[k]:starts[k + 1]], sc[k], cam[starts[k]:starts[k + 1]].view(lens[k], 4, 4)) for k in range(K)]
+        return [(body_rec[starts[k]:starts[k + 1]], sc[k], cam[starts[k]:starts[k + 1]].view(lens[k], 4, 4)) for k in range(self.num_clips)]
+
+    def _run_local2(self, log_every):
+        """detect_contact + the cal_loss2 loop (:534-556) of every clip of the prepared batch in ONE call; its history is read back once"""
+        import torch
+        K, lens, starts, dev = self.num_clips, self.clip_lens, self.clip_starts, self.device
+        lib, h = self.ctx.lib, self.ctx.handle
+        num_iter = int(self.num_iter)
+        n2 = int(LOCAL_SECOND_LOOP * num_iter)
+        logged2 = [jj for jj in range(n2) if log_every and jj % log_every == 0]
+        hist2 = torch.zeros(max(len(logged2), 1), K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
+        weight = torch.empty(starts[-1], device=dev)
+        n_done = ctypes.c_int32(0)
+        try:
+            capi.check(lib.fdcap_opt_run_local2(h, self.n_left, 0, n2, num_iter, int(log_every or 0), capi.dptr(weight),
+                                                capi.dptr(hist2) if logged2 else None, len(logged2), 0, ctypes.byref(n_done),
+                                                capi.current_stream()), "fdcap_opt_run_local2")
+        finally:
+            capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
+        assert n_done.value == len(logged2)
+        rows2 = hist2.cpu().numpy()
+        self.contact_weights = [weight[starts[k]:starts[k + 1]] for k in range(K)]
+        self.logs2 = [[[jj, *local2_losses(rows2[j, k], lens[k], self.ctx.num_verts, self.weight_loss_rec)] for j, jj in enumerate(logged2)]
+                      for k in range(K)]
 
     def _run_dct(self, log_every=0):
         """mode 'dct' of the prepared batch: fdcap_opt_set_dct_clips, ONE fdcap_opt_run_dct, the read-backs."""
-        import ctypes
         import torch
-        K, lens, starts, dev = self.num_clips, self.clip_lens, self.clip_starts, self.device
-        total, T = starts[-1], BATCH_FRAME_NUM
+        K, lens, dev = self.num_clips, self.clip_lens, self.device
+        T = BATCH_FRAME_NUM
         lib, h = self.ctx.lib, self.ctx.handle
         st = capi.current_stream()
         c_init, D = self._dct_in
@@ -1130,20 +1118,14 @@ class ClipBatchFitter:
             ws.append(ws[-1] + w)
         if c_init is not None and len(c_init) != K:
             raise capi.FdcapError(f"c_dct_init must hold one array per clip ({K}), got {len(c_init)}")
-        c0 = []
-        for k in range(K):
-            a = torch.randn(Wk[k], 23, 3, C) if c_init is None else \
-                torch.as_tensor(np.asarray(c_init[k], dtype=np.float32).reshape(Wk[k], 23, 3, -1))
-            if tuple(a.shape) != (Wk[k], 23, 3, C):
-                raise capi.FdcapError(f"c_dct_init[{k}] must be [{Wk[k]},23,3,{C}], got {tuple(a.shape)}")
-            c0.append(a)
+        c0 = [_c_dct_start(None if c_init is None else c_init[k], Wk[k], C, f"c_dct_init[{k}]") for k in range(K)]
         c0 = torch.cat(c0).to(dev, torch.float32).contiguous()
         capi.check(lib.fdcap_opt_set_dct_clips(h, D.ctypes.data_as(ctypes.c_void_p), D.shape[0], C, capi.dptr(c0), st), "fdcap_opt_set_dct_clips")
         num_iter = self.dct_num_iter
-        P = int(math.ceil(num_iter * DCT_PHASE_SPLIT - 1e-9))
+        P = dct_first_phase2_iter(num_iter)
         log_every = int(log_every or 0)
         logged1 = list(range(0, P, log_every)) if log_every else []
-        logged2 = [ii for ii in range(P + 1, num_iter) if log_every and (ii % log_every == 0 or ii == num_iter - 1)]
+        logged2 = [ii for ii in range(P + 1, num_iter) if is_logging_iteration(ii, num_iter, log_every)]
         hist1 = torch.zeros(max(len(logged1), 1), 69 * ws[-1], device=dev)
         hist2 = torch.zeros(max(len(logged2), 1), K, capi.NUM_LOSSES, device=dev, dtype=torch.float64)
         wd, wr, wc = DCT_PHASE2
@@ -1155,34 +1137,19 @@ class ClipBatchFitter:
         finally:
             capi.check(lib.fdcap_opt_set_loss_output(h, capi.dptr(self._losses)), "fdcap_opt_set_loss_output")
         assert n_done.value == len(logged2)
-        body_rec = torch.empty(total, capi.PDIM, device=dev)
-        scale = torch.empty(K, device=dev)
-        cam = torch.empty(total, 16, device=dev)
-        capi.check(lib.fdcap_opt_get_results(h, capi.dptr(body_rec), capi.dptr(scale), capi.dptr(cam), st), "fdcap_opt_get_results")
+        results = self._results(self.clip_starts[-1], K)
         cd = torch.empty(ws[-1], 23, 3, C, device=dev)
         capi.check(lib.fdcap_opt_get_dct(h, capi.dptr(cd), st), "fdcap_opt_get_dct")
         self.c_dct = [cd[ws[k]:ws[k + 1]] for k in range(K)]
         self.logs, self.contact_weights = [], []
         self.logs_dct, self.logs2 = [], []
         rows2 = hist2.cpu().numpy()
-        nc = max(self.ctx.num_contact, 1)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            for k in range(K):
-                n, W = lens[k], Wk[k]
-                part = hist1[:, 69 * ws[k]:69 * ws[k + 1]].sum(dim=1, dtype=torch.float64).cpu().numpy()
-                self.logs_dct.append([[ii, float(part[j]) / (69 * W)] for j, ii in enumerate(logged1)])
-                log2 = []
-                for j, ii in enumerate(logged2):
-                    s = rows2[j, k]
-                    l_rec = self.weight_loss_rec * s[0] / (n * capi.XDIM)
-                    l_vp = self.weight_loss_vposer * s[1] / (n * 32)
-                    l_sm = s[2] / ((n - 2) * capi.XDIM) if n >= 3 else float("nan")
-                    l_con = self.weight_contact * s[3] / (n * nc)
-                    l_dct = s[7] / (69 * W)
-                    log2.append([ii, l_rec, l_vp, l_sm, l_con, l_dct, wd * l_dct + wr * l_rec + wc * l_con])
-                self.logs2.append(log2)
-        sc = scale.cpu().numpy()
-        return [(body_rec[starts[k]:starts[k + 1]], sc[k], cam[starts[k]:starts[k + 1]].view(lens[k], 4, 4)) for k in range(K)]
+        for k in range(K):
+            part = hist1[:, 69 * ws[k]:69 * ws[k + 1]].sum(dim=1, dtype=torch.float64).cpu().numpy()
+            self.logs_dct.append([[ii, float(part[j]) / (69 * Wk[k])] for j, ii in enumerate(logged1)])
+            self.logs2.append([[ii, *dct2_losses(rows2[j, k], lens[k], Wk[k], self.ctx.num_contact, self.weight_loss_rec,
+                                                 self.weight_loss_vposer, self.weight_contact)] for j, ii in enumerate(logged2)])
+        return self._per_clip(*results)
 
     def close(self):
         if getattr(self, "ctx", None) is not None:

@@ -212,6 +212,69 @@ def test_logged_losses_puts_every_weight_in_its_place(phase2, monkeypatch):
     np.testing.assert_allclose(got, want, rtol=1e-12)
 
 
+ROW_SUMS = np.array([41.7, 3.9, 0.83, 17.3, 5.1, 2.2e3, 0.061, 9.4])       # losses_d of one logged iteration: any positive sums
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 300])
+def test_local2_losses_is_the_second_loops_printed_row(n, recwarn):
+    """fitting.local2_losses (mode 'local''s second loop, global_optimization.py:404-429, :547-552): the means over an n-frame clip
+    of V vertices from the device's sums, each term as written out here (the divisor n - 2 as it is: -1 for one frame); a mean
+    over nothing (n = 2) is inf, NaN for a zero sum, position for position, and nothing warns."""
+    from fdcap_amd import fitting
+    V, w_rec = 217, ODD["weight_loss_rec"]
+    for s in (ROW_SUMS, np.where(np.arange(8) == 2, 0.0, ROW_SUMS)):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            nf = np.float64(n)
+            l_rec = w_rec * s[0] / (nf * 78)                  # weight_loss_rec * mean |x - data| over [n,78]
+            l_loc = s[2] / ((nf - 2) * 78)                    # mean of the second differences of the rows [n-2,78]
+            l_sm = s[5] / ((nf - 2) * (3 * V))                # mean of the second differences of the world vertices [n-2,V,3] (:404-405)
+            l_cs = s[6]                                       # the two contact-smoothing means (:429), divided on the device
+            want = [l_rec, l_loc, l_sm, l_cs, l_sm * 1.0 + l_loc + l_rec + l_cs]      # (:547)
+        got = fitting.local2_losses(s, n, V, w_rec)
+        assert len(got) == 5
+        np.testing.assert_array_equal(np.array(got, dtype=np.float64), np.array(want, dtype=np.float64))
+        assert all(np.isfinite(got)) == (n != 2)
+    assert not [w for w in recwarn.list if issubclass(w.category, RuntimeWarning)]
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 300])
+def test_dct2_losses_is_the_second_phases_printed_row(n, recwarn):
+    """fitting.dct2_losses (mode 'dct''s second phase, :620-626) at the odd weights: each term as written out here, loss_smoothing NaN
+    below three frames, total = loss_dct*0.0001 + loss_rec*0.5 + loss_contact*0.1."""
+    from fdcap_amd import fitting
+    assert fitting.DCT_PHASE2 == (0.0001, 0.5, 0.1)
+    s, W, nc = ROW_SUMS, 5, 16
+    w_rec, w_vp, w_con = ODD["weight_loss_rec"], ODD["weight_loss_vposer"], ODD["weight_contact"]
+    l_rec = w_rec * s[0] / (n * 78)
+    l_vp = w_vp * s[1] / (n * 32)
+    l_sm = s[2] / ((n - 2) * 78) if n >= 3 else float("nan")
+    l_con = w_con * s[3] / (n * nc)
+    l_dct = s[7] / (69 * W)                                    # mean over [W,23,3] trajectories
+    want = [l_rec, l_vp, l_sm, l_con, l_dct, 0.0001 * l_dct + 0.5 * l_rec + 0.1 * l_con]
+    got = fitting.dct2_losses(s, n, W, nc, w_rec, w_vp, w_con)
+    assert len(got) == 6 and np.isnan(got[2]) == (n < 3)
+    np.testing.assert_array_equal(np.array(got, dtype=np.float64), np.array(want, dtype=np.float64))
+    # no contact vertices: the mean runs over one, as in logged_losses
+    assert fitting.dct2_losses(s, n, W, 0, w_rec, w_vp, w_con)[3] == w_con * s[3] / n
+    assert not [w for w in recwarn.list if issubclass(w.category, RuntimeWarning)]
+
+
+def test_dct_first_phase2_iter_is_the_one_place_of_the_split():
+    from fdcap_amd.fitting import dct_first_phase2_iter
+    for k in range(1, 401):
+        assert dct_first_phase2_iter(k) == int(np.ceil(k * 0.95 - 1e-9)), k
+    assert dct_first_phase2_iter(200) == 190 and dct_first_phase2_iter(40) == 38 and dct_first_phase2_iter(10000) == 9500
+
+
+def test_fitlog_appends_a_row_of_logged_losses():
+    from fdcap_amd.fitting import FitLog
+    log = FitLog()
+    log.append(3, (1.0, 2.0, 3.0, 4.0, 5.0, 6.0))
+    log.append(7, (1.5, 2.5, 3.5, 4.5, 5.5, 6.5))
+    assert log == FitLog([3, 7], [1.0, 1.5], [2.0, 2.5], [3.0, 3.5], [4.0, 4.5], [5.0, 5.5], [6.0, 6.5])
+    assert FitLog().iters is not FitLog().iters
+
+
 # ---- the host twin: the kernels' math compiled for the host ---------------------------------------------------------------------
 @pytest.mark.parametrize("phase2", [False, True])
 def test_host_build_of_the_kernels_math_at_the_odd_settings_matches_autograd(phase2):

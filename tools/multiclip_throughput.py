@@ -237,9 +237,8 @@ def local_mode(reps, out, bm, vp, scene, vid):
 def dct_mode(reps, out, bm, vp, scene, vid):
     """K = 1, 3 and 8 clips of N frames in mode 'dct': one batch against K stand-alone fits, alternating; the batch's two phases."""
     import ctypes
-    import math
     from fdcap_amd import capi, synth
-    from fdcap_amd.fitting import DCT_NUM_ITER, DCT_PHASE1_WEIGHT, DCT_PHASE2, DCT_PHASE_SPLIT, ClipBatchFitter, FittingOP
+    from fdcap_amd.fitting import DCT_NUM_ITER, DCT_PHASE1_WEIGHT, DCT_PHASE2, ClipBatchFitter, FittingOP, dct_first_phase2_iter
     from fdcap_amd.io import load_dct_base, read_camerapose
     ks = (1, 3, 8)
     D = load_dct_base(None)
@@ -255,7 +254,7 @@ def dct_mode(reps, out, bm, vp, scene, vid):
             for k, (_, cam) in enumerate(clips)]
     bodies = [torch.tensor(body).cuda() for body, _ in clips]
     num_iter = DCT_NUM_ITER
-    P = int(math.ceil(num_iter * DCT_PHASE_SPLIT - 1e-9))
+    P = dct_first_phase2_iter(num_iter)
 
     def batch(K):
         t0 = time.perf_counter()
