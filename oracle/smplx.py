@@ -68,6 +68,11 @@ class SMPLXOracle(torch.nn.Module):
         self.parents = torch.as_tensor(data.parents).long()
         self.dtype = dtype
 
+    def tap(self, name, value):
+        """A named point of the graph: the identity here.  tests/gradient_bars.py overrides it to detach (parts of) `value`
+        -- a gradient with a contribution missing, values unchanged."""
+        return value
+
     def forward(self, return_verts=True, body_pose=None, transl=None, global_orient=None,
                 betas=None, left_hand_pose=None, right_hand_pose=None, **unused):
         b = body_pose.shape[0]
@@ -80,11 +85,11 @@ class SMPLXOracle(torch.nn.Module):
         shape_components = torch.cat([betas, expression], dim=-1)
 
         v_shaped = self.v_template + torch.einsum("bl,mkl->bmk", shape_components, self.shapedirs)
-        J = torch.einsum("bik,ji->bjk", v_shaped, self.J_regressor)
+        J = torch.einsum("bik,ji->bjk", self.tap("v_shaped_to_joints", v_shaped), self.J_regressor)
         rot_mats = batch_rodrigues(full_pose.reshape(-1, 3)).view(b, -1, 3, 3)
         ident = torch.eye(3, dtype=self.dtype)
-        pose_feature = (rot_mats[:, 1:] - ident).reshape(b, -1)
-        v_posed = v_shaped + torch.matmul(pose_feature, self.posedirs).view(b, -1, 3)
+        pose_feature = self.tap("pose_feature", (rot_mats[:, 1:] - ident).reshape(b, -1))
+        v_posed = self.tap("v_posed", v_shaped + torch.matmul(pose_feature, self.posedirs).view(b, -1, 3))
         J_transformed, A = batch_rigid_transform(rot_mats, J, self.parents)
         W = self.lbs_weights.unsqueeze(0).expand(b, -1, -1)
         nj = self.J_regressor.shape[0]

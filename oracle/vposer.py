@@ -21,6 +21,10 @@ class VPoserDecoder(torch.nn.Module):
         self.register_buffer("out_w", t(out_w)); self.register_buffer("out_b", t(out_b))
         self.eval()
 
+    def tap(self, name, value):
+        """A named point of the graph: the identity here (see oracle/smplx.py SMPLXOracle.tap)."""
+        return value
+
     @classmethod
     def from_data(cls, vp, dtype=torch.float32):
         return cls(vp.fc1_w, vp.fc1_b, vp.fc2_w, vp.fc2_b, vp.out_w, vp.out_b, dtype=dtype)
@@ -28,7 +32,7 @@ class VPoserDecoder(torch.nn.Module):
     def decode_matrot(self, z: torch.Tensor) -> torch.Tensor:
         h = F.leaky_relu(F.linear(z, self.fc1_w, self.fc1_b), negative_slope=0.2)
         # dropout(p=.25) is the identity in eval mode (load_vposer calls .eval())
-        h = F.leaky_relu(F.linear(h, self.fc2_w, self.fc2_b), negative_slope=0.2)
+        h = self.tap("hidden2", F.leaky_relu(F.linear(h, self.fc2_w, self.fc2_b), negative_slope=0.2))
         o = F.linear(h, self.out_w, self.out_b)                       # [B,126]
         return rotrepr.decode_6d(o).view(-1, 1, 21, 9)
 

@@ -13,6 +13,8 @@ from oracle import rotrepr
 from oracle.fitting import FittingOracle
 from oracle.smplx import SMPLXOracle
 from oracle.vposer import VPoserDecoder
+from tests import gradient_bars
+from tests.test_gpu_gradient_bars import check_isolated, isolated_backward
 from tests.test_gpu_parity import _make_fop
 
 pytestmark = pytest.mark.gpu
@@ -159,10 +161,11 @@ def test_fused_vposer_backward_in_the_optimiser_gradient(n, V, per_part):
 
 
 def _optimiser_gradient_case(n, V, per_part):
-    """-> the kernel forms the gradient's launches took (fdcap_debug_kernel_forms)"""
-    forms = ctypes.create_string_buffer(4096)
+    """The gradient at the default phase-1 mix under the whole-matrix bar (an integration check: the L1 terms set max|g|, and what
+    the blend products contribute lies inside atol -- tests/test_gradient_bars_cpu.py), then the contact term ALONE on the same
+    optimiser state (a second FittingOP with weight_loss_rec = 0 and PHASE1_SMOOTH = 0), every column block within its own bar
+    (tests/gradient_bars.py).  -> the kernel forms the isolated gradient's launches took (fdcap_debug_kernel_forms)"""
     fop, bm, vp, clip, scene, vid = _make_fop(n, V, 800, per_part, 500)
-    capi.check(fop.ctx.lib.fdcap_debug_kernel_forms(forms, len(forms), 1), "kernel_forms")   # (reset)
     dt = torch.float64
     f = FittingOracle(SMPLXOracle(bm, dt), VPoserDecoder.from_data(vp, dt), scene, vid, clip.camerapose_lines, n, dtype=dt)
     x78 = rotrepr.convert_to_6D_rot(torch.tensor(clip.body_params, dtype=dt)).detach()
@@ -188,9 +191,12 @@ def _optimiser_gradient_case(n, V, per_part):
     lat = gx[:, 19:51]
     assert np.abs(lat).max() > 0                                          # the latent block is really exercised
     np.testing.assert_allclose(dx.cpu().numpy()[:, 19:51], lat, rtol=2e-3, atol=2e-4 * np.abs(lat).max())
-    capi.check(lib.fdcap_debug_kernel_forms(forms, len(forms), 0), "kernel_forms")
     fop.close()
-    return forms.value.decode().split(";")
+    case = (n, V, 800, per_part, 0)
+    got, forms = isolated_backward(case, "con", gradient_bars.isolated_terms(case))
+    bad = check_isolated(case, "con", got, "fp16 planes")
+    assert not bad, f"blocks outside their bar {{block: (err / bar, bar, max|g|)}}: {bad}"
+    return forms
 
 
 @pytest.mark.parametrize("n,V,per_part,kernel", [

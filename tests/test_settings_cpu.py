@@ -38,7 +38,7 @@ ODD = dict(lr=0.0123, weight_loss_rec=0.7, weight_loss_vposer=0.013, weight_cont
            phase2_world=0.43, phase2_smooth=0.31, scale_init=1.3)
 DEFAULTS = dict(lr=0.005, weight_loss_rec=1.0, weight_loss_vposer=0.001, weight_contact=0.1, phase1_contact=0.1, phase1_smooth=1.0,
                 phase2_world=1.0, phase2_smooth=0.5, scale_init=1.8)
-GRAD_RTOL, GRAD_ATOL = 2e-3, 2e-4          # the project's gradient bar: rtol, atol = 2e-4 max|g| (tests/test_gpu_parity.py _gradient_check)
+GRAD_RTOL, GRAD_ATOL = 2e-3, 2e-4          # the mixed-term gradient bar: rtol, atol = 2e-4 max|g| (tests/test_gpu_parity.py _gradient_check; per term and block: tests/gradient_bars.py)
 LOG_RTOL = 1e-5                            # ... and its bar for the logged terms (1e-4 for the world term)
 FACTOR = 20.0
 GRAD_CASES = {"n12": (12, 300, 800, 20, 0), "ragged": (7, 777, 801, 7, 12)}      # n, V, ns, per_part, seed
@@ -95,26 +95,50 @@ def perturbation(n):
     return 0.01 * torch.randn((n, 78), generator=torch.Generator().manual_seed(5), dtype=torch.float64)
 
 
-@functools.lru_cache(maxsize=None)
-def oracle_terms(case_key, scale_init):
-    """fp64: values and gradients of the UNWEIGHTED terms (rec, vposer, smoothing, contact, world smoothing) at the perturbed start,
-    each term's gradient taken on its own.  -> {"val": {term: float}, "g": {term: (d rows [n,78], d scale, d camera_ext [n,16])}}"""
-    case = make_case(*GRAD_CASES[case_key])
-    n = case[5]
-    f = make_oracle(case, dict(ODD, scale_init=scale_init), torch.float64, unit_weights=True)
-    x78 = rotrepr.convert_to_6D_rot(torch.tensor(case[2].body_params, dtype=torch.float64)).detach()
-    f.init(x78)
-    f.body_rotation_rec.data += perturbation(n)
+TERMS = ("rec", "vp", "sm", "con", "ws")
+
+
+def term_gradients(case, scale_init, dtype=torch.float64, terms=TERMS, as_the_gpu_holds_it=False, body_cls=SMPLXOracle, vposer_cls=VPoserDecoder):
+    """Values and gradients of the UNWEIGHTED terms (rec, vposer, smoothing, contact, world smoothing) at the perturbed start, each
+    term's gradient taken on its own.  -> {"val": {term: float}, "g": {term: (d rows [n,78], d scale, d camera_ext [n,16])}, ...}
+    as_the_gpu_holds_it: the start rows, the perturbation, their sum, scale and camera_ext rounded to fp32 before the oracle
+    (in `dtype`) sees them -- the state a FittingOP holds after init() and `rows += perturbation.float()`.
+    body_cls / vposer_cls: the oracle's models, or subclasses that override tap() (tests/gradient_bars.py)."""
+    bm, vp, clip, scene, vid, n = case
+    if as_the_gpu_holds_it:
+        scale_init = float(np.float32(scale_init))
+    s = dict(DEFAULTS, scale_init=scale_init)
+    f = FittingOracle(body_cls(bm, dtype), vposer_cls.from_data(vp, dtype), scene, vid, clip.camerapose_lines, n, init_lr_h=s["lr"],
+                      weight_loss_rec=1.0, weight_loss_vposer=1.0, weight_contact=1.0, dtype=dtype, scale_init=scale_init)
+    x78 = rotrepr.convert_to_6D_rot(torch.tensor(clip.body_params, dtype=torch.float64)).detach()
     idx1, _ = find_outliers(x78.numpy().astype(np.float32))
+    if as_the_gpu_holds_it:
+        x78 = x78.float()
+        f.init(x78)
+        f.body_rotation_rec.data = (f.body_rotation_rec.data + perturbation(n).float()).to(dtype)       # the sum in fp32, as on the device
+        f.camera_ext.data = f.camera_ext.data.float().to(dtype)                                         # (rounded from its fp64 inverse)
+        x78 = x78.to(dtype)
+    else:
+        x78 = x78.to(dtype)
+        f.init(x78)
+        f.body_rotation_rec.data += perturbation(n).to(dtype)
     l_rec, l_vp, l_con, l_sm, l_ws = f.cal_loss(x78, idx1)
     leaves = (f.body_rotation_rec, f.scale, f.camera_ext)
-    out = {"val": {}, "g": {}, "x78": x78, "idx1": idx1, "rows": f.body_rotation_rec.detach().clone(), "cam": f.camera_ext.detach().clone()}
+    out = {"val": {}, "g": {}, "x78": x78, "idx1": idx1, "rows": f.body_rotation_rec.detach().clone(), "cam": f.camera_ext.detach().clone(), "oracle": f}
     for name, l in (("rec", l_rec), ("vp", l_vp), ("sm", l_sm), ("con", l_con), ("ws", l_ws)):
+        if name not in terms:
+            continue
         g = torch.autograd.grad(l, leaves, retain_graph=True, allow_unused=True)
         g = [torch.zeros_like(p) if gi is None else gi for gi, p in zip(g, leaves)]
         out["val"][name] = float(l.detach())
-        out["g"][name] = (g[0].numpy(), float(g[1]), g[2].numpy().reshape(n, 16))
+        out["g"][name] = (g[0].numpy().astype(np.float64), float(g[1]), g[2].numpy().reshape(n, 16).astype(np.float64))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_terms(case_key, scale_init):
+    """term_gradients of a case of GRAD_CASES in fp64, at the fp64 start."""
+    return term_gradients(make_case(*GRAD_CASES[case_key]), scale_init)
 
 
 def coefficients(s, phase2):
