@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FDCAP_LIB") or os.path.join(_HERE, "libfdcap_hip.so")
 
 NUM_LOSSES = 8
+MAX_SCENES = 8          # FDCAP_MAX_SCENES: scene slots of a context
 XDIM = 78
 PDIM = 75
 
@@ -59,6 +60,7 @@ SYMBOLS = {
     "fdcap_ctx_create": (c_int32, [POINTER(ModelDesc), POINTER(c_void_p)]),
     "fdcap_ctx_destroy": (None, [c_void_p]),
     "fdcap_set_scene": (c_int32, [c_void_p, c_void_p, c_int64]),
+    "fdcap_set_scene_slot": (c_int32, [c_void_p, c_int32, c_void_p, c_int64]),
     "fdcap_debug_scene_hash": (c_int32, [c_void_p, c_void_p]),
     "fdcap_debug_scene_table": (c_int32, [c_void_p, c_int32, c_void_p, POINTER(c_int64)]),
     "fdcap_debug_kernel_forms": (c_int32, [c_void_p, c_int32, c_int32]),
@@ -87,6 +89,8 @@ SYMBOLS = {
     "fdcap_opt_create_clips": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_create_clips_var": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
+    "fdcap_opt_create_clips_scenes": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_set_inputs": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_backward": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "fdcap_opt_step": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
@@ -283,6 +287,13 @@ class Context:
         self._scene_host = s                   # (ops.chamferDist recognises a target tensor that holds exactly these points)
         self._scene_dev = None
         self._scene_gen = getattr(self, "_scene_gen", 0) + 1     # ... and forgets what it concluded about an earlier scene
+
+    def set_scene_slot(self, slot, scene_xyz):
+        """One of the MAX_SCENES registered scenes (slot 0 is set_scene's); an empty array clears a slot above 0."""
+        if int(slot) == 0:
+            return self.set_scene(scene_xyz)
+        s = _f32(np.asarray(scene_xyz).reshape(-1, 3))
+        check(self.lib.fdcap_set_scene_slot(self.handle, int(slot), s.ctypes.data_as(c_void_p), s.shape[0]), "fdcap_set_scene_slot")
 
     def set_contact_ids(self, vid):
         v = np.ascontiguousarray(vid, dtype=np.int64)

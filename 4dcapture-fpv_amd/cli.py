@@ -21,7 +21,13 @@ test_modes_other_than_global_are_refused pins that refusal -- lifting it is a fo
 
 `--mix-lengths` (with --clips): clips are grouped by scene file alone and a batch may hold clips of different lengths
 (plan_batches_mixed: batches are filled in input order up to MULTICLIP_ROW_CAP rows, so a video's short remainder clip rides with
-its full segments).  Every clip's result is the one its own batch-of-one gives."""
+its full segments).  Every clip's result is the one its own batch-of-one gives.
+
+`--mix-scenes` (with --clips; implies --mix-lengths): a batch may also hold clips of different SCENES -- in the reference's data
+every video has its own reconstruction, so without this a video of one or two clips is a batch of one or two.  Batches are filled in
+input order up to MULTICLIP_ROW_CAP rows and MAX_SCENES scenes (plan_batches_scenes); the fitter keeps the scenes in the context's
+slots by path, so a scene that the next batch uses again is neither read nor registered again.  Without the flag every planner,
+batch and refusal above is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -95,6 +101,33 @@ def plan_batches_mixed(clips, clips_per_batch=None, row_cap: int = MULTICLIP_ROW
     return out
 
 
+MAX_SCENES = 8          # = capi.MAX_SCENES (FDCAP_MAX_SCENES), restated so that planning imports nothing
+
+
+def plan_batches_scenes(clips, clips_per_batch=None, row_cap: int = MULTICLIP_ROW_CAP, scene_cap: int = MAX_SCENES):
+    """clips: sequence of (scene path, clip length).  Batches are filled in INPUT order, whatever the scenes: a batch is closed when
+    the next clip would push its rows above row_cap (a clip longer than the cap is a batch of its own), its clip count above
+    clips_per_batch, or its number of different scenes above scene_cap.  Within a batch the fitter orders the clips so that every
+    scene is one run (fitting.ClipBatchFitter.fit(scenes=..., clip_scene=...)).  For clips of one scene these are
+    plan_batches_mixed's batches.  Returns [([scene paths in order of first use], [clip indices])]."""
+    kmax = max(1, int(clips_per_batch)) if clips_per_batch else None
+    out = []
+    cur, rows, scenes = [], 0, []
+    for i, (scene, n) in enumerate(clips):
+        n = int(n)
+        full = rows + n > row_cap or (kmax is not None and len(cur) >= kmax) or (scene not in scenes and len(scenes) >= scene_cap)
+        if cur and full:
+            out.append((scenes, cur))
+            cur, rows, scenes = [], 0, []
+        cur.append(i)
+        rows += n
+        if scene not in scenes:
+            scenes.append(scene)
+    if cur:
+        out.append((scenes, cur))
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="global_optimization (fdcap_amd / MI355X)")
     ap.add_argument("body_path", nargs="?")
@@ -108,6 +141,9 @@ def main(argv=None):
     ap.add_argument("--mix-lengths", action="store_true",
                     help="multi-clip form: group clips by scene alone; a batch may hold clips of different lengths and never more "
                          f"than {MULTICLIP_ROW_CAP} rows, also with --clips-per-batch (without this flag K alone bounds a batch)")
+    ap.add_argument("--mix-scenes", action="store_true",
+                    help="multi-clip form (implies --mix-lengths): a batch may hold clips of different scenes -- batches are filled "
+                         f"in input order up to {MULTICLIP_ROW_CAP} rows and {MAX_SCENES} scenes")
     ap.add_argument("--mode", dest="mode_opt", default=None, choices=["global", "local", "dct"],
                     help="multi-clip form: the mode (only 'global' is supported)")
     ap.add_argument("--scene-root", default="/home/miao/")
@@ -126,6 +162,8 @@ def main(argv=None):
         return _main_clips(ap, a)
     if a.mix_lengths:
         ap.error("--mix-lengths belongs to the multi-clip form (--clips ... --fit-root DIR)")
+    if a.mix_scenes:
+        ap.error("--mix-scenes belongs to the multi-clip form (--clips ... --fit-root DIR)")
     if a.body_path is None or a.fit_path is None:
         ap.error("body_path and fit_path are required (or --clips ... --fit-root DIR)")
 
@@ -175,6 +213,20 @@ def _main_clips(ap, a):
     fitter = ClipBatchFitter(fittingconfig, lossconfig)
     try:
         sized = [(s, d.shape[0]) for s, d in zip(scenes, data)]
+        if a.mix_scenes:
+            for paths, idx in plan_batches_scenes(sized, a.clips_per_batch):
+                # (a scene some slot holds under its path is not read again: the fitter reuses the slot)
+                held = {fitter.scene_key, *fitter._slot_keys}
+                ent = [(p, None if p in held else io.read_scene_points(p)) for p in paths]
+                res = fitter.fit([(data[i], cams[i]) for i in idx], log_every=a.log_every, scenes=ent,
+                                 clip_scene=[paths.index(sized[i][0]) for i in idx])
+                for i, (body_rec, scale, camera_ext) in zip(idx, res):
+                    io.save_result(body_rec.detach().cpu().numpy(), scale, camera_ext.detach().cpu().numpy(),
+                                   clip_output_dir(a.fit_root, a.clips[i]))
+                frames = sorted({sized[i][1] for i in idx})
+                print(f"[INFO][fitting] batch of {len(idx)} clips x {'/'.join(map(str, frames))} frames on {len(paths)} scenes fitted")
+            print("[INFO][fitting] fitting finish, returning optimal value")
+            return 0
         batches = plan_batches_mixed(sized, a.clips_per_batch) if a.mix_lengths else \
             [(scene, idx) for scene, _, idx in plan_batches(sized, a.clips_per_batch)]
         for scene, idx in batches:

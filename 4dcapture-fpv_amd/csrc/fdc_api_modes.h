@@ -32,6 +32,7 @@ int fdcap_opt_set_dct_clips(fdcap_ctx* c, const float* dct_mtx, int32_t T, int32
     if (!c || !c->opt) return FDCAP_E_STATE;
     OptState* o = c->opt;
     if (!opt_whole_clips(o)) return FDCAP_E_STATE;       // (a shard of a clip: FittingOP's loop, window by window)
+    if (o->multi_scene()) return FDCAP_E_STATE;          // (clips of several scenes: mode 'global' only)
     if (!dct_mtx || !c_dct_d || T <= 0 || T > DCT_MAXT || C <= 0 || C > DCT_MAXC) return FDCAP_E_ARG;
     if (o->nclip == 1) return fdcap_opt_set_dct(c, dct_mtx, T, C, c_dct_d, stream);
     const int K = o->nclip;

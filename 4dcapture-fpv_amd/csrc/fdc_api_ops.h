@@ -241,13 +241,8 @@ void fdcap_ctx_destroy(fdcap_ctx* c) {
     delete c;
 }
 
-int fdcap_set_scene(fdcap_ctx* c, const float* xyz, int64_t ns) {
-    // FDCAP_MAX_SCENE_POINTS: the in-loop NN launch streams the scene's MFMA fragments (32 B per point) through one buffer
-    // resource with 32-bit byte offsets; beyond 2 GiB of fragments its loads would silently return zeros
-    if (!c || ns < 0 || (ns > 0 && !xyz) || ns > FDCAP_MAX_SCENE_POINTS) return FDCAP_E_ARG;
-    // a live optimiser holds buffers sized for, and pruning state (seeds, kept work lists) valid for, the registered scene
-    if (c->opt) return FDCAP_E_STATE;
-    c->sop.nq = 0;                                          // (the scene operator's seeds / kept lists were for the old scene)
+// the table set of one slot (fdcap_set_scene: slot 0)
+static int scene_set_build(SceneSet* c, const float* xyz, int64_t ns) {
     c->ns = 0;                                              // (no scene until the new tables are complete: a failure below leaves none)
     static_assert(SC_SUPER == ST4_SUPER, "fdc_scene.h builds the super-cell boxes the search reads");
     // Spatial order by recursive median splits (k-d cells): every MF_CH-point chunk is one cell and every 32-point MFMA tile inside it
@@ -273,6 +268,26 @@ int fdcap_set_scene(fdcap_ctx* c, const float* xyz, int64_t ns) {
     HIP_TRY(scene_build_device(xyz, ns, T, host_order ? order.data() : nullptr));
     c->ns = ns;
     return FDCAP_OK;
+}
+
+int fdcap_set_scene(fdcap_ctx* c, const float* xyz, int64_t ns) {
+    // FDCAP_MAX_SCENE_POINTS: the in-loop NN launch streams the scene's MFMA fragments (32 B per point) through one buffer
+    // resource with 32-bit byte offsets; beyond 2 GiB of fragments its loads would silently return zeros
+    if (!c || ns < 0 || (ns > 0 && !xyz) || ns > FDCAP_MAX_SCENE_POINTS) return FDCAP_E_ARG;
+    // a live optimiser holds buffers sized for, and pruning state (seeds, kept work lists) valid for, the registered scene
+    if (c->opt) return FDCAP_E_STATE;
+    c->sop.nq = 0;                                          // (the scene operator's seeds / kept lists were for the old scene)
+    return scene_set_build(&c->scenes[0], xyz, ns);
+}
+
+// Slot 0 is fdcap_set_scene.  The other slots follow its rules; ns = 0 frees the slot's tables.
+int fdcap_set_scene_slot(fdcap_ctx* c, int32_t slot, const float* xyz, int64_t ns) {
+    if (!c || slot < 0 || slot >= FDCAP_MAX_SCENES) return FDCAP_E_ARG;
+    if (slot == 0) return fdcap_set_scene(c, xyz, ns);
+    if (ns < 0 || (ns > 0 && !xyz) || ns > FDCAP_MAX_SCENE_POINTS) return FDCAP_E_ARG;
+    if (c->opt) return FDCAP_E_STATE;
+    if (ns == 0) { c->scenes[slot].release(); return FDCAP_OK; }
+    return scene_set_build(&c->scenes[slot], xyz, ns);
 }
 
 // test / diagnosis: FNV-1a hashes of the registered scene's eight device tables (input-order points, sorted points, inverse

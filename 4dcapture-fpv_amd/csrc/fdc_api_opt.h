@@ -32,9 +32,17 @@ static LossWeights opt_phase_weights(const fdcap_opt_config& cf, bool phase2) {
 // var_len == nullptr: n_clips clips of cfg->n_total frames each (one clip, one rank's share of one, or a batch of one length).
 // var_len != nullptr: clips of these lengths, not all equal; cfg holds the batch's rows (n_total = n_local = their sum, checked
 // by the caller).
+// scene_slot: the registered scene the optimiser searches.  segments (fdcap_opt_create_clips_scenes; two or more, fdc_clips.h):
+// each run of clips searches its own slot's scene -- the search state is built per segment (OptState::segs) -- and scene_slot is
+// ignored; everything else is the batch it would be on one scene.
 static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_clips, const int32_t* var_len, float* rows_x, float* rows_cam,
-                           float* scale_d, float* dscale_d, double* losses_d) {
+                           float* scale_d, float* dscale_d, double* losses_d, int32_t scene_slot = 0,
+                           const std::vector<ClipSegment>* segments = nullptr) {
     SetupTrace tr("fdcap_opt_create");
+    // (every named slot holds a scene: a batch has one contact switch, and a clip without a scene would have no contact term)
+    if (segments) for (const ClipSegment& g : *segments) if (c->scenes[g.slot].ns <= 0) return FDCAP_E_STATE;
+    if (segments) scene_slot = (*segments)[0].slot;
+    const SceneSet& sc0 = c->scenes[scene_slot];
     // a second clip of the same shape reuses the scratch allocations (every buffer is re-zeroed below)
     OptState* o = c->opt ? c->opt : new OptState();
     c->opt = o;
@@ -57,12 +65,27 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->dct_clips = false;
     o->dct_grad = false;
     const int R = o->R = cfg->n_local + 4;
-    o->contact_on = c->ns > 0 && c->nc > 0 && cfg->weight_contact != 0.f;
+    o->scene_slot = scene_slot;
+    o->nnpt_filled = false;
+    o->segs.clear();
+    o->contact_on = sc0.ns > 0 && c->nc > 0 && cfg->weight_contact != 0.f;
     const size_t nq = (size_t)R * std::max(c->nc, 1);
     o->sw = forms_read_env();                               // (every create: tests flip the per-fit switches between fits in one process)
     const int nq_all = (int)((size_t)cfg->n_local * c->nc);
-    o->nsplit = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, o->sw.nn_seed && o->sw.nn_cull) : 1;
-    o->nsplit_bf = o->contact_on ? nn_pick_nsplit(nq_all, (int)c->ns, false) : 1;
+    o->nsplit = o->contact_on ? nn_pick_nsplit(nq_all, (int)sc0.ns, o->sw.nn_seed && o->sw.nn_cull) : 1;
+    o->nsplit_bf = o->contact_on ? nn_pick_nsplit(nq_all, (int)sc0.ns, false) : 1;
+    size_t pd_floats = (size_t)std::max(o->nsplit, o->nsplit_bf) * nq;
+    if (segments) {                                         // every segment splits its own scene for its own queries; one workspace serves them in turn
+        o->segs.resize(segments->size());
+        pd_floats = 0;
+        for (size_t s = 0; s < segments->size(); ++s) {
+            SegSearch& g = o->segs[s];
+            g.seg = (*segments)[s];
+            g.nsplit = nn_pick_nsplit(g.seg.nq, (int)c->scenes[g.seg.slot].ns, o->sw.nn_seed && o->sw.nn_cull);
+            pd_floats = std::max(pd_floats, (size_t)g.nsplit * g.seg.nq);
+        }
+        o->nsplit = o->nsplit_bf = 1;
+    }
     int err = 0;
 #define AL(buf, cnt) if (!err) { hipError_t e_ = (buf).ensure(cnt); if (e_ != hipSuccess) err = (int)e_; else e_ = hipMemset((buf).p, 0, (size_t)(cnt) * sizeof(*(buf).p)); }
     o->X.p = rows_x; o->CAM.p = rows_cam; o->scale.p = scale_d; o->dscale.p = dscale_d; o->losses.p = losses_d;
@@ -80,7 +103,7 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     AL(o->dCAM, (size_t)R * 16) AL(o->dscale_row, R) AL(o->loss_rows, (size_t)R * LROW)
     if (o->contact_on) {
         AL(o->Voff, nq * 3) AL(o->Vw, nq * 3) AL(o->dist, nq) AL(o->idx, nq) AL(o->dVoff, nq * 3) AL(o->seedpt, nq)
-        AL(o->pd, (size_t)std::max(o->nsplit, o->nsplit_bf) * nq) AL(o->pi, (size_t)std::max(o->nsplit, o->nsplit_bf) * nq)
+        AL(o->pd, pd_floats) AL(o->pi, pd_floats)
     }
 #undef AL
     tr.mark("buffers");
@@ -88,7 +111,26 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
         hipError_t e_ = hipMemset(o->idx.p, 0xFF, nq * sizeof(int));      // -1: no seed yet
         if (e_ != hipSuccess) err = (int)e_;
     }
-    if (!err && o->contact_on) {
+    for (SegSearch& g : o->segs) {                         // clips of several scenes: the same state, one set per segment
+        if (err || !o->contact_on) break;
+        o->nn_order = NNOrder{};                            // (the one-scene state: unused here)
+        const int every = o->sw.nn_order;
+        g.ord = NNOrder{};
+        g.seeded = false;
+        if (o->sw.nn_cache_slack > 0.f) {
+            const size_t ng = (size_t)g.seg.groups, ng4 = ng * 4, snq = (size_t)g.seg.nq;
+            hipError_t e_ = g.ids.ensure(ng4 * NN_CACHE_CAP);
+            if (e_ == hipSuccess) e_ = g.hdr.ensure(ng4 + 3 * ng);
+            if (e_ == hipSuccess) e_ = g.anchor.ensure(4 * snq);
+            if (e_ == hipSuccess && every > 0) e_ = g.qbuf.ensure(nn_query_order_ints((int)snq));
+            if (e_ == hipSuccess) e_ = hipMemset(g.hdr.p, 0xFF, ng4 * sizeof(int));
+            if (e_ == hipSuccess) e_ = hipMemset(g.hdr.p + ng4, 0, 3 * ng * sizeof(int));
+            if (e_ == hipSuccess) e_ = hipMemset(g.anchor.p, 0, 4 * snq * sizeof(float4));
+            if (e_ != hipSuccess) err = (int)e_;
+            if (every > 0) { g.ord.on = true; g.ord.every = every; g.ord.qbuf = g.qbuf.p; }
+        }
+    }
+    if (!err && o->contact_on && o->segs.empty()) {
         const int every = o->sw.nn_order;
         o->nn_order = NNOrder{};
         if (o->sw.nn_cache_slack > 0.f) {                                        // groups of 32 queries x up to 4 waves per group
@@ -153,6 +195,22 @@ int fdcap_opt_create_clips_var(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_
     return opt_create_impl(c, cfg, n_clips, clip_len, rows_x, rows_cam, scale_d, dscale_d, losses_d);
 }
 
+// Clips that name their scene slot.  One slot for all: fdcap_opt_create_clips_var's optimiser on that slot's scene (its path, its
+// bits).  Several: the search state per segment (fdc_clips.h), everything else that batch.
+int fdcap_opt_create_clips_scenes(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_clips, const int32_t* clip_len, const int32_t* clip_scene,
+                                  float* rows_x, float* rows_cam, float* scale_d, float* dscale_d, double* losses_d) {
+    if (!c || !cfg || !rows_x || !rows_cam || !scale_d || !dscale_d || !losses_d || cfg->frame0 != 0 || cfg->n_local != cfg->n_total ||
+        !clip_lengths_ok(n_clips, clip_len, cfg->n_total, (int64_t)1 << 24) || !clip_scenes_ok(n_clips, clip_scene, FDCAP_MAX_SCENES))
+        return FDCAP_E_ARG;
+    const std::vector<ClipSegment> segments = clip_segments(n_clips, clip_len, clip_scene, c->nc, FDCAP_MAX_SCENES);
+    const bool equal = clip_lengths_equal(n_clips, clip_len);
+    fdcap_opt_config one = *cfg;
+    if (equal) one.n_total = one.n_local = clip_len[0];         // (one length: fdcap_opt_create_clips' batch, no table)
+    if (equal && n_clips > 1 && (int64_t)n_clips * clip_len[0] > (1 << 24)) return FDCAP_E_ARG;
+    return opt_create_impl(c, &one, n_clips, equal ? nullptr : clip_len, rows_x, rows_cam, scale_d, dscale_d, losses_d, segments[0].slot,
+                           segments.size() > 1 ? &segments : nullptr);
+}
+
 int fdcap_opt_create(fdcap_ctx* c, const fdcap_opt_config* cfg, float* rows_x, float* rows_cam, float* scale_d,
                      float* dscale_d, double* losses_d) {
     return fdcap_opt_create_clips(c, cfg, 1, rows_x, rows_cam, scale_d, dscale_d, losses_d);
@@ -171,6 +229,50 @@ int fdcap_opt_set_inputs(fdcap_ctx* c, const float* data78, const float* init78,
     HIP_TRY(hipMemcpyAsync(o->mask.p + 2, mask, n * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(o->CAM.p + 2 * 16, cam, n * 16 * sizeof(float), hipMemcpyDeviceToDevice, st));
     return FDCAP_OK;
+}
+
+// The in-loop search of a batch of clips of several scenes: every segment against its own scene with its own pruning state, into
+// the flat dist / idx / seedpt.  One launch for all segments where plan_nn_segments says so, else -- the specification -- one
+// nn_search launch set per segment in segment order.  Either way seedpt holds every neighbour's coordinates afterwards: the
+// backward has ONE scene pointer, so after a form that keeps no records they are gathered from each segment's own scene.
+static int opt_search_segments(fdcap_ctx* c, hipStream_t st) {
+    OptState* o = c->opt;
+    const int nc = c->nc, nseg = (int)o->segs.size();
+    const bool seeds = o->sw.nn_seed, cull = o->sw.nn_cull;
+    std::vector<int> snq((size_t)nseg), snt((size_t)nseg);
+    for (int s = 0; s < nseg; ++s) { snq[s] = o->segs[s].seg.nq; snt[s] = (int)c->scenes[o->segs[s].seg.slot].ns; }
+    // (as nn_search sees each segment: culled = seeds and boxes, fragments with the boxes, seeds in place with their coordinates)
+    FormSwitches sw = proc_switches();                       // (nn_stream: once per process, as nn_search reads it)
+    sw.nn_segments_loop = o->sw.nn_segments_loop;            // (every create)
+    const NNSegPlan pl = plan_nn_segments(nseg, snq.data(), snt.data(), seeds && cull, cull, seeds, 1, nn_mode_ref(), sw);
+    o->nnpt_filled = false;
+    NNSegSearch sg[NN_MAX_SEGS];
+    for (int s = 0; s < nseg; ++s) {
+        SegSearch& g = o->segs[s];
+        const SceneSet& sc = c->scenes[g.seg.slot];
+        const size_t base = (size_t)2 * nc + g.seg.q0;
+        const float* const q = o->Vw.p + 3 * base;
+        float* const dist = o->dist.p + base;
+        int* const idx = o->idx.p + base;
+        float4* const seedpt = o->seedpt.p + base;
+        if (pl.one_launch) {
+            sg[s] = NNSegSearch{q, g.seg.nq, sc.nn_target(cull), dist, idx, seedpt, o->nn_cache_of(g), &g.ord, !g.seeded};
+        } else {
+            const NNCache cache = o->nn_cache_of(g);
+            bool written = false;
+            HIP_TRY(nn_search(q, g.seg.nq, sc.nn_target(cull), dist, idx, o->pd.p, o->pi.p, g.nsplit, st, seeds ? idx : nullptr, !g.seeded, seedpt,
+                              &written, &cache, &g.ord));
+            if (!written) {
+                hipLaunchKernelGGL(nn_records_gather_kernel, dim3((g.seg.nq + 255) / 256), dim3(256), 0, st, (const int*)idx, g.seg.nq,
+                                   (const float4*)sc.scene.p, (const int*)sc.scene_inv.p, seedpt);
+                o->nnpt_filled = true;
+            }
+        }
+        g.seeded = true;
+    }
+    if (pl.one_launch) HIP_TRY(nn_search_segments(pl, sg, nseg, st));
+    o->nnpt_valid = true;
+    return (int)hipGetLastError();
 }
 
 static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = false) {
@@ -202,9 +304,13 @@ static int opt_contact_forward(fdcap_ctx* c, hipStream_t st, bool blend_done = f
     const NNCache cache = o->nn_cache(0);
     const bool timed = o->nn_timing && o->nn_ev_used + 2 <= (int)o->nn_ev.size();
     if (timed) HIP_TRY(hipEventRecord(o->nn_ev[o->nn_ev_used], st));
-    {
+    if (o->multi_scene()) {
         TraceRange tr_("fdcap:chamfer_nn(K14)");
-        HIP_TRY(nn_search(o->Vw.p + off, nq, c->nn_target(o->sw.nn_cull), o->dist.p + 2 * nc, o->idx.p + 2 * nc, o->pd.p, o->pi.p,
+        int es = opt_search_segments(c, st);
+        if (es) return es;
+    } else {
+        TraceRange tr_("fdcap:chamfer_nn(K14)");
+        HIP_TRY(nn_search(o->Vw.p + off, nq, c->scenes[o->scene_slot].nn_target(o->sw.nn_cull), o->dist.p + 2 * nc, o->idx.p + 2 * nc, o->pd.p, o->pi.p,
                           o->nsplit, st, o->sw.nn_seed ? o->idx.p + 2 * nc : nullptr, !o->seeded, o->seedpt.p + 2 * nc, &o->nnpt_valid,
                           &cache, &o->nn_order));
     }
@@ -310,7 +416,8 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
     int dA_rows = NJ;                                       // rows of dA the skinning backward writes (the others are zero and skipped)
     if (contact_grad) {
         ContactGradIn cg;
-        cg.Vw = o->Vw.p; cg.dist = o->dist.p; cg.idx = o->idx.p; cg.scene = c->scene.p;
+        // (clips of several scenes: nnpt is always there -- opt_search_segments -- and `scene` is never read)
+        cg.Vw = o->Vw.p; cg.dist = o->dist.p; cg.idx = o->idx.p; cg.scene = c->scenes[o->scene_slot].scene.p;
         cg.nnpt = o->nnpt_valid ? o->seedpt.p : nullptr;
         cg.coef = cw.coef;
         cg.loss_rows = losses ? o->loss_rows.p : nullptr;
@@ -320,7 +427,8 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         const SkinBwdPlan pl = plan_contact_skin_bwd(nl, nc, nnz, smc.K, smc.vpack != nullptr, smc.csc_v16 != nullptr, aligned16, smc.wf_tab != nullptr,
                                                      o->sw.skin_vec);
         if (pl.ja_rows) dA_rows = c->contact.ja_hi;
-        cg.recompute = pl.form == F_SKIN_BWD_VEC && cg.nnpt != nullptr && o->sw.contact_recompute;
+        // (gathered records stand in for the scene pointer only: the launch stays the one a stand-alone fit's staged search leads to)
+        cg.recompute = pl.form == F_SKIN_BWD_VEC && cg.nnpt != nullptr && o->sw.contact_recompute && !(o->multi_scene() && o->nnpt_filled);
         o->n_recompute += cg.recompute;
         const dim3 grid(pl.grid), block(pl.block);
 #define FDC_SKC(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, pl.lds, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, o->dVoff.p, \
@@ -454,7 +562,7 @@ int fdcap_debug_nn_query_order(fdcap_ctx* c, int32_t mode, const int32_t* perm_h
     if (mode < 0 || mode > 2) return FDCAP_E_ARG;
     OptState* o = c->opt;
     NNOrder& ord = o->nn_order;
-    if (!o->contact_on || ord.qbuf == nullptr) return FDCAP_E_STATE;
+    if (!o->contact_on || ord.qbuf == nullptr || o->multi_scene()) return FDCAP_E_STATE;    // (several scenes: an order per segment, none to impose)
     const int nq = o->cfg.n_local * c->nc;
     if (mode == 2) {                                         // a permutation of [0, nq), or nothing is changed
         if (!perm_host || n != nq) return FDCAP_E_ARG;

@@ -122,6 +122,7 @@ int fdcap_opt_run_local2(fdcap_ctx* c, int32_t n_left, int32_t jj0, int32_t jj1,
                          double* hist_d, int32_t hist_rows, int32_t flags, int32_t* n_logged, void* stream) {
     if (n_logged) *n_logged = 0;
     if (!c || !c->opt) return FDCAP_E_STATE;
+    if (opt_is_multi_scene(c)) return FDCAP_E_STATE;     // (clips of several scenes: mode 'global' only)
     if (n_left <= 0 || n_left >= c->nc || jj0 < 0 || jj1 < jj0 || num_iter < 0 || log_every < 0 || !contact_weight_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     // (a sharded context: the halo exchange between two iterations of this loop stays with the caller)
@@ -169,9 +170,10 @@ int fdcap_opt_run_dct(fdcap_ctx* c, int32_t ii0, int32_t ii1, int32_t num_iter, 
                       int32_t log_every, float* obj_hist_d, double* hist_d, int32_t hist_rows, int32_t flags, int32_t* n_logged, void* stream) {
     if (n_logged) *n_logged = 0;
     if (!c || !c->opt) return FDCAP_E_STATE;
+    if (opt_is_multi_scene(c)) return FDCAP_E_STATE;     // (clips of several scenes: mode 'global' only)
     if (ii0 < 0 || ii1 < ii0 || ii1 > num_iter || log_every < 0) return FDCAP_E_ARG;
     OptState* o = c->opt;
-    if (o->dctW <= 0 || !opt_whole_clips(o)) return FDCAP_E_STATE;      // (a shard of a clip: the exchange stays with the caller)
+    if (o->dctW <= 0 || !opt_whole_clips(o)) return FDCAP_E_STATE;     // (a shard of a clip: the exchange stays with the caller)
     const int P = (int)std::ceil((double)num_iter * 0.95 - 1e-9);       // first ii with not (ii < 0.95 num_iter) (:597)
     const auto logs = [&](int ii) { return log_every > 0 && (ii % log_every == 0 || ii == num_iter - 1); };
     {                                                        // every logging iteration of the stretch has its history row
@@ -474,6 +476,7 @@ int fdcap_debug_contact_diet(fdcap_ctx* c, int32_t* out4) {
     if (!c || !c->opt || !out4) return FDCAP_E_STATE;
     const OptState* o = c->opt;
     out4[0] = o->nn_order.n_kept; out4[1] = o->n_recompute; out4[2] = o->nn_order.n_permuted; out4[3] = o->nn_order.n_rebuilds;
+    for (const SegSearch& g : o->segs) { out4[0] += g.ord.n_kept; out4[2] += g.ord.n_permuted; out4[3] += g.ord.n_rebuilds; }   // (several scenes: per segment)
     return FDCAP_OK;
 }
 
@@ -627,11 +630,28 @@ int fdcap_opt_time_chamfer(fdcap_ctx* c, int32_t iters, int32_t brute_force, flo
     hipStream_t st = (hipStream_t)stream;
     const int nl = o->cfg.n_local, nc = c->nc;
     const size_t off = (size_t)2 * nc * 3;
+    if (o->multi_scene()) {
+        // clips of several scenes: the loop's own search (one launch for all segments, or one launch set each), never brute force
+        if (brute_force) return FDCAP_E_STATE;
+        DevEvent e0, e1;
+        HIP_TRY(e0.create());
+        HIP_TRY(e1.create());
+        { int es_ = opt_search_segments(c, st); if (es_) return es_; }       // (warm-up)
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters; ++i) { int es_ = opt_search_segments(c, st); if (es_) return es_; }
+        HIP_TRY(hipEventRecord(e1, st));
+        HIP_TRY(hipEventSynchronize(e1));
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, e0, e1));
+        *ms = t / iters;
+        return FDCAP_OK;
+    }
     // brute_force: every (query, scene point) pair is visited (no seed, no chunk bounds);
     // otherwise the launch is exactly what the loop issues in steady state
     const int* seed = (!brute_force && o->sw.nn_seed) ? o->idx.p + 2 * nc : nullptr;
-    NNTarget T = c->nn_target(!brute_force && o->sw.nn_cull);
-    if (brute_force) { T.pts = c->scene.p; T.inv_perm = nullptr; T.frags = nullptr; }   // input order (a spatial sort is adversarial for an unseeded running minimum)
+    const SceneSet& sc = c->scenes[o->scene_slot];
+    NNTarget T = sc.nn_target(!brute_force && o->sw.nn_cull);
+    if (brute_force) { T.pts = sc.scene.p; T.inv_perm = nullptr; T.frags = nullptr; }   // input order (a spatial sort is adversarial for an unseeded running minimum)
     DevEvent e0, e1;
     HIP_TRY(e0.create());
     HIP_TRY(e1.create());

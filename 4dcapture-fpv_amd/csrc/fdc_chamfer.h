@@ -597,10 +597,39 @@ __device__ __forceinline__ int nn_box_stage(const float4* sq, int lane, int n, i
     return nn_box_passes<2>(sq, lane, n, room, fetch, emit);
 }
 
-template <int WPG, int WPB = 4>
+// SEGMENTED (the one-wave form only; plan_nn_segments, fdc_forms.h): blockIdx.y is one of several independent searches -- the runs
+// of clips of one scene in a batch of clips of different scenes (fdc_clips.h) -- each with its own target tables, queries, records
+// and pruning state: everything the unsegmented launch takes as arguments, one NNSeg per segment, seeds in place (seed == idx).
+// grid.x is the LARGEST segment's workgroup count; a workgroup past its own segment's groups returns before it touches LDS.
+// The descriptors ARE the kernel's last argument, so they sit in the constant address space (the kernel-argument segment) and the
+// segment's index is blockIdx.y: every field arrives by s_load into SGPRs, exactly like the arguments they replace -- this kernel
+// has no VGPR to spare.  blockIdx.x stays the position within the segment, so the segment's launch-order tables and work counts
+// are indexed as in its own launch: a segment gets the bits -- results and pruning state -- of the unsegmented launch over it alone.
+// The unsegmented instantiations take an empty struct there and compile to the instructions they had without it
+// (tools/asm_kernel_diff.py --pair).
+struct NNSeg {
+    const float* q; int nq; int groups;
+    NNTarget T;
+    int* idx; float4* seedpt; float* dist;
+    NNCache cache;
+};
+struct NNSegs { NNSeg s[NN_MAX_SEGS]; };
+struct NNNoSegs {};
+static_assert(sizeof(NNSegs) <= 3072, "the descriptors travel as a kernel argument (4 KiB for all of them)");
+template <bool SEG> struct NNSegArg { typedef NNNoSegs type; };
+template <> struct NNSegArg<true> { typedef NNSegs type; };
+
+template <int WPG, int WPB = 4, bool SEG = false>
 __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const float* __restrict__ q, int nq, NNTarget T,
                                                          const int* __restrict__ seed, float4* __restrict__ seedpt,
-                                                         float* __restrict__ dist, int* __restrict__ idx, NNCache cache) {
+                                                         float* __restrict__ dist, int* __restrict__ idx, NNCache cache,
+                                                         typename NNSegArg<SEG>::type segs) {
+    if constexpr (SEG) {                                         // (all of it workgroup-uniform: scalar loads, scalar registers)
+        static_assert(WPG == 1 && WPB == 1, "segments: the one-wave form");
+        const NNSeg& d = segs.s[blockIdx.y];
+        if ((int)blockIdx.x >= d.groups) return;
+        q = d.q; nq = d.nq; T = d.T; seed = d.idx; seedpt = d.seedpt; dist = d.dist; idx = d.idx; cache = d.cache;
+    }
     // WPB waves per workgroup.  Waves of different groups never talk to each other, and a workgroup's slot on the CU is only
     // handed on when its slowest wave is done: with one wave per group the launch runs one-wave workgroups (WPB = 1).
     __shared__ unsigned short slist[WPB][ST4_MAXLIST];           // a wave's work list: quarter chunks 4 k + quarter (chunk WPG k + sub)
@@ -1272,6 +1301,19 @@ __global__ __launch_bounds__(256) void nn_seed_kernel(const float* __restrict__ 
     seedpt[qi] = bp;
 }
 
+// The neighbour records of a search form that keeps none (the staged and the plain scan): seedpt[q] = the coordinates of scene
+// point idx[q] and its position in the sorted scene, what the streaming form leaves.  scene: input order; a query without a
+// neighbour (idx < 0) keeps its record.
+__global__ void nn_records_gather_kernel(const int* __restrict__ idx, int nq, const float4* __restrict__ scene, const int* __restrict__ inv_perm,
+                                         float4* __restrict__ seedpt) {
+    const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (qi >= nq) return;
+    const int j = idx[qi];
+    if (j < 0) return;
+    const float4 p = scene[j];
+    seedpt[qi] = make_float4(p.x, p.y, p.z, __int_as_float(inv_perm[j]));
+}
+
 __global__ void nn_combine_kernel(const float* __restrict__ pd, const int* __restrict__ pi, int nsplit, int nq,
                                   float* __restrict__ dist, int* __restrict__ idx) {
     int qi = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1392,6 +1434,52 @@ struct NNOrder {
 static inline size_t nn_query_order_ints(int nq);                       // fdc_scene.h (the radix sort lives there)
 static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st);
 
+// The host's share of ONE streaming launch over `groups` groups of `wpg` waves, in two halves around the launch (nn_search; the
+// segmented launch calls both once per segment).  Before: the kernel's cache argument -- launch order, query order and whether
+// unchanged records are kept, by the order's state.
+static inline NNCache nn_stream_args(const NNCache* cache, NNOrder* ord, int groups, int wpg, int nq, const int* seed, const int* idx,
+                                     const float4* seedpt, bool seed_missing) {
+    NNCache nc = cache ? *cache : NNCache{nullptr, nullptr, nullptr, 0.f};
+    const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && wpg == 1;
+    nc.order_mode = !ordered ? 0 : (ord->sorted_groups == groups ? 2 + ord->cur : 1);
+    const bool qorder = ordered && ord->qbuf != nullptr && ord->perm_mode != 1;
+    nc.perm = qorder && ord->perm_n == nq ? ord->qbuf : nullptr;
+    // records are kept only where the kernel already trusts seedpt as the coordinates of idx: seeds in place, valid, and
+    // not just written by nn_seed_kernel (which leaves a NaN query's record as it was) -- and only by the one-wave form: in
+    // the two- and four-wave forms, launches of ~15 us that latency bounds, the bookkeeping cost more than the stores
+    // (+0.6 / +0.2 us per launch at 160 / 128 frames x 500 contacts), so they store every record as before
+    nc.keep = nc.keep && wpg == 1 && seedpt != nullptr && seed != nullptr && seed == idx && !seed_missing;
+    if (ord) { ord->n_kept += nc.keep ? 1 : 0; ord->n_permuted += nc.perm ? 1 : 0; }
+    if (ord && wpg == 1) ++ord->n_box[nc.box_lanes == 2 ? 1 : nc.box_lanes == 4 ? 2 : nc.box_lanes == 8 ? 3 : 0];
+    return nc;
+}
+// After (nc: what nn_stream_args returned for this launch): the query order's rebuild or the launch order's re-sort, when due.
+static inline hipError_t nn_stream_upkeep(const NNCache& nc, NNOrder* ord, int groups, int wpg, int nq, const float4* seedpt, bool seed_missing,
+                                          hipStream_t st) {
+    const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && wpg == 1;
+    const bool qorder = ordered && ord->qbuf != nullptr && ord->perm_mode != 1;
+    const bool resort = ordered && (ord->sorted_groups != groups || ++ord->age >= ord->every);
+    if (qorder && ord->perm_mode == 0 && (ord->perm_n != nq || seed_missing || (resort && ord->sorted_groups == groups))) {
+        // new groups: their kept lists go (hdr = -1, by the key kernel), the next launch records its work items in
+        // plain launch order and the launch order is sorted after it
+        const hipError_t e = nn_query_order(seedpt, nq, ord->qbuf, nc.hdr, groups, st);
+        if (e != hipSuccess) return e;
+        ord->perm_n = nq;
+        ord->sorted_groups = 0;
+        ord->age = 0;
+        ++ord->n_rebuilds;
+    } else if (resort) {
+        const bool had = nc.order_mode >= 2;
+        const int nxt = had ? 1 - ord->cur : 0;
+        hipLaunchKernelGGL(nn_order_kernel, dim3(1), dim3(1024), 0, st, (const int*)(nc.hdr + 4 * groups), groups,
+                           had ? (const int*)(nc.hdr + (5 + ord->cur) * groups) : (const int*)nullptr, nc.hdr + (5 + nxt) * groups);
+        ord->cur = nxt;
+        ord->sorted_groups = groups;
+        ord->age = 0;
+    }
+    return hipSuccess;
+}
+
 // workspace: pd/pi [nsplit*nq]; seed: optional [nq] original indices (may alias idx: read before idx is rewritten)
 static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, float* dist, int* idx, float* pd, int* pi,
                                    int nsplit, hipStream_t st, const int* seed = nullptr, bool seed_missing = false,
@@ -1410,40 +1498,12 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
         if (seedpt_written) *seedpt_written = true;
         {
             const int groups = pl.groups, wpg = pl.wpg;
-            NNCache nc = cache ? *cache : NNCache{nullptr, nullptr, nullptr, 0.f};
-            const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && wpg == 1;
-            nc.order_mode = !ordered ? 0 : (ord->sorted_groups == groups ? 2 + ord->cur : 1);
-            const bool qorder = ordered && ord->qbuf != nullptr && ord->perm_mode != 1;
-            nc.perm = qorder && ord->perm_n == nq ? ord->qbuf : nullptr;
-            // records are kept only where the kernel already trusts seedpt as the coordinates of idx: seeds in place, valid, and
-            // not just written by nn_seed_kernel (which leaves a NaN query's record as it was) -- and only by the one-wave form: in
-            // the two- and four-wave forms, launches of ~15 us that latency bounds, the bookkeeping cost more than the stores
-            // (+0.6 / +0.2 us per launch at 160 / 128 frames x 500 contacts), so they store every record as before
-            nc.keep = nc.keep && wpg == 1 && seedpt != nullptr && seed != nullptr && seed == idx && !seed_missing;
-            if (ord) { ord->n_kept += nc.keep ? 1 : 0; ord->n_permuted += nc.perm ? 1 : 0; }
-            if (ord && wpg == 1) ++ord->n_box[nc.box_lanes == 2 ? 1 : nc.box_lanes == 4 ? 2 : nc.box_lanes == 8 ? 3 : 0];
-            if (wpg == 4) hipLaunchKernelGGL((nn_stream4_kernel<4>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-            else if (wpg == 2) hipLaunchKernelGGL((nn_stream4_kernel<2>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-            else hipLaunchKernelGGL((nn_stream4_kernel<1, 1>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc);
-            const bool resort = ordered && (ord->sorted_groups != groups || ++ord->age >= ord->every);
-            if (qorder && ord->perm_mode == 0 && (ord->perm_n != nq || seed_missing || (resort && ord->sorted_groups == groups))) {
-                // new groups: their kept lists go (hdr = -1, by the key kernel), the next launch records its work items in
-                // plain launch order and the launch order is sorted after it
-                const hipError_t e = nn_query_order(seedpt, nq, ord->qbuf, nc.hdr, groups, st);
-                if (e != hipSuccess) return e;
-                ord->perm_n = nq;
-                ord->sorted_groups = 0;
-                ord->age = 0;
-                ++ord->n_rebuilds;
-            } else if (resort) {
-                const bool had = nc.order_mode >= 2;
-                const int nxt = had ? 1 - ord->cur : 0;
-                hipLaunchKernelGGL(nn_order_kernel, dim3(1), dim3(1024), 0, st, (const int*)(nc.hdr + 4 * groups), groups,
-                                   had ? (const int*)(nc.hdr + (5 + ord->cur) * groups) : (const int*)nullptr, nc.hdr + (5 + nxt) * groups);
-                ord->cur = nxt;
-                ord->sorted_groups = groups;
-                ord->age = 0;
-            }
+            const NNCache nc = nn_stream_args(cache, ord, groups, wpg, nq, seed, idx, seedpt, seed_missing);
+            if (wpg == 4) hipLaunchKernelGGL((nn_stream4_kernel<4>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc, NNNoSegs{});
+            else if (wpg == 2) hipLaunchKernelGGL((nn_stream4_kernel<2>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc, NNNoSegs{});
+            else hipLaunchKernelGGL((nn_stream4_kernel<1, 1>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc, NNNoSegs{});
+            const hipError_t e = nn_stream_upkeep(nc, ord, groups, wpg, nq, seedpt, seed_missing, st);
+            if (e != hipSuccess) return e;
         }
         return hipGetLastError();
     }
@@ -1451,6 +1511,36 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
     else if (pl.form == F_NN_MFMA) hipLaunchKernelGGL((nn_mfma_kernel<4>), grid, block, 0, st, q, nq, T, nsplit, seed, pd, pi, 0LL, 0LL);
     else hipLaunchKernelGGL((nn_direct_kernel<2>), grid, block, 0, st, q, nq, T, nsplit, pd, pi, 0LL, 0LL);
     hipLaunchKernelGGL(nn_combine_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, pd, pi, nsplit, nq, dist, idx);
+    return hipGetLastError();
+}
+
+// The seeded in-place search of several segments -- each what nn_search takes with seed == idx: its queries, target, records, cache
+// and order state -- in ONE launch of the one-wave streaming form (plan_nn_segments(...).one_launch, fdc_forms.h).  The host's
+// bookkeeping is nn_search's, per segment; the seeding of a segment's first launch and its order upkeep stay launches of their own
+// (off the steady path).  Every segment gets the bits of its own nn_search launch.
+struct NNSegSearch { const float* q; int nq; NNTarget T; float* dist; int* idx; float4* seedpt; NNCache cache; NNOrder* ord; bool seed_missing; };
+static inline hipError_t nn_search_segments(const NNSegPlan& pl, const NNSegSearch* sg, int nseg, hipStream_t st) {
+    if (!pl.one_launch || nseg < 1 || nseg > NN_MAX_SEGS || pl.grid_y != nseg) return hipErrorInvalidValue;
+    note_form(pl.name);
+    NNSegs a{};
+    for (int s = 0; s < nseg; ++s) {
+        const NNSegSearch& g = sg[s];
+        const int groups = (g.nq + 31) / 32;
+        if (g.nq <= 0 || groups > pl.grid_x) return hipErrorInvalidValue;
+        if (g.seed_missing)
+            hipLaunchKernelGGL(nn_seed_kernel, dim3((g.nq + 255) / 256), dim3(256), 0, st, g.q, g.nq, g.T, g.idx, g.seedpt);
+        NNSeg& d = a.s[s];
+        d.q = g.q; d.nq = g.nq; d.groups = groups; d.T = g.T; d.idx = g.idx; d.seedpt = g.seedpt; d.dist = g.dist;
+        d.cache = nn_stream_args(&g.cache, g.ord, groups, 1, g.nq, g.idx, g.idx, g.seedpt, g.seed_missing);
+    }
+    // (the per-launch arguments are unused: every workgroup takes its segment's from the descriptors)
+    hipLaunchKernelGGL((nn_stream4_kernel<1, 1, true>), dim3(pl.grid_x, nseg), dim3(pl.block), 0, st, (const float*)nullptr, 0, NNTarget{},
+                       (const int*)nullptr, (float4*)nullptr, (float*)nullptr, (int*)nullptr, NNCache{nullptr, nullptr, nullptr, 0.f}, a);
+    for (int s = 0; s < nseg; ++s) {
+        const NNSegSearch& g = sg[s];
+        const hipError_t e = nn_stream_upkeep(a.s[s].cache, g.ord, a.s[s].groups, 1, g.nq, g.seedpt, g.seed_missing, st);
+        if (e != hipSuccess) return e;
+    }
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <vector>
 
@@ -112,6 +113,50 @@ inline std::vector<ClipRow> clip_rows_build_local2(int32_t n_clips, const int32_
     std::vector<ClipWeights> w;
     for (int32_t k = 0; k < n_clips; ++k) w.push_back(clip_weights_local2(len[k], weight_loss_rec, nv3));
     return clip_rows_fill(n_clips, len, w);
+}
+
+// ---- clips of different scenes (fdcap_opt_create_clips_scenes) ------------------------------------------------------------------
+// Clip k names the registered scene slot clip_scene[k].  A SEGMENT is a maximal run of adjacent clips of one slot (a slot may come
+// back: A, B, A are three segments); only the Chamfer search knows segments -- its pruning state (kept lists, launch order, query
+// order, seeds) is cut along them, and each searches its own scene.  Everything per query (dist, idx, seedpt) stays flat.
+constexpr int CLIP_MAX_SCENES = 8;     // = FDCAP_MAX_SCENES (asserted where both are visible)
+// row0: the segment's first BUFFER row (2 + its first clip's start); q0: its first query among the batch's rows x nc queries
+// (frame-major: (row0 - 2) nc), nq = rows nc of them; g0 / groups: its one-wave workgroups (32 queries each) among the batch's,
+// segment after segment -- every segment starts a group of its own, so sum(groups) >= ceil(sum(nq) / 32)
+struct ClipSegment { int32_t row0, rows, slot, clip0, nclips, q0, nq, g0, groups; };
+inline bool clip_scenes_ok(int32_t n_clips, const int32_t* clip_scene, int32_t n_slots = CLIP_MAX_SCENES) {
+    if (n_clips < 1 || !clip_scene) return false;
+    for (int32_t k = 0; k < n_clips; ++k) if (clip_scene[k] < 0 || clip_scene[k] >= n_slots) return false;
+    return true;
+}
+// (empty: slots out of range)
+inline std::vector<ClipSegment> clip_segments(int32_t n_clips, const int32_t* len, const int32_t* clip_scene, int nc,
+                                              int32_t n_slots = CLIP_MAX_SCENES) {
+    std::vector<ClipSegment> segs;
+    if (!clip_scenes_ok(n_clips, clip_scene, n_slots)) return segs;
+    const std::vector<int32_t> s = clip_starts(n_clips, len);
+    for (int32_t k = 0; k < n_clips; ++k) {
+        if (segs.empty() || segs.back().slot != clip_scene[k]) {
+            ClipSegment g = {};
+            g.row0 = 2 + s[(size_t)k]; g.slot = clip_scene[k]; g.clip0 = k;
+            g.q0 = s[(size_t)k] * nc;
+            g.g0 = segs.empty() ? 0 : segs.back().g0 + segs.back().groups;
+            segs.push_back(g);
+        }
+        ClipSegment& g = segs.back();
+        g.rows += len[k]; ++g.nclips;
+        g.nq = g.rows * nc;
+        g.groups = (g.nq + 31) / 32;
+    }
+    return segs;
+}
+
+// FDCAP_NN_SEGMENTS=loop in the environment: the search of such a batch runs segment after segment, one launch set each -- the
+// specification of the one-launch form.  Read by forms_read_env() alone (FormSwitches::nn_segments_loop, fdc_forms.h), at every
+// fdcap_opt_create*; any other value, or none: the form plan_nn_segments picks.
+inline bool clip_segments_loop_env() {
+    const char* e = getenv("FDCAP_NN_SEGMENTS");
+    return e && e[0] == 'l' && e[1] == 'o' && e[2] == 'o' && e[3] == 'p' && e[4] == 0;
 }
 
 // ---- mode 'dct' for a batch (fdcap_opt_set_dct_clips) -------------------------------------------------------------------------

@@ -8,6 +8,8 @@
 
 #include <algorithm>
 
+#include "fdc_clips.h"
+
 #if defined(__HIPCC__)
 #define FDC_FORMS_HD __host__ __device__
 #else
@@ -22,7 +24,7 @@ namespace fdc {
 //   once per process     proc_switches(): clip_fwd_rows, clip_kgrad_rows, pn_rb2, pn_nw, pn_ksw, nn_stream;
 //                        gemm_split3 through gemm_split3_enabled(); nn_cache_slack as fdcap_chamfer_fwd_scene uses it
 //   every opt_create     nn_seed, nn_cull, skin_vec, fuse_skin, nn_cache_slack, nn_order, pose_trim, nn_keep_records,
-//                        contact_recompute, nn_box_lanes (copied into the optimiser state)
+//                        contact_recompute, nn_box_lanes, nn_segments_loop (copied into the optimiser state)
 //   every call           gemm_split3 in fdcap_panel_gemm
 struct FormSwitches {
     // FDCAP_CLIP_FORMS_MIN_ROWS: row count from which the clip-sized forms are selected; it overrides BOTH thresholds -- tests run
@@ -58,6 +60,9 @@ struct FormSwitches {
     // r15.  FDCAP_NN_BOX_LANES: lanes that share one box in the in-loop search's per-query box tests (nn_box_lanes below): 0 by the
     // pass's count, 2 a pair everywhere (every launch before r15), 4 / 8 forced; anything else is 0.
     int nn_box_lanes = 0;
+    // FDCAP_NN_SEGMENTS=loop: a batch of clips of several scenes (fdcap_opt_create_clips_scenes) searches segment after segment, one
+    // nn_search launch set each -- the specification of the one-launch form (plan_nn_segments below) -- whatever the sizes.
+    bool nn_segments_loop = false;
 };
 inline FormSwitches forms_read_env() {
     FormSwitches s;
@@ -78,6 +83,7 @@ inline FormSwitches forms_read_env() {
     s.nn_keep_records = !off("FDCAP_NN_KEEP_RECORDS");
     s.contact_recompute = !off("FDCAP_CONTACT_RECOMPUTE");
     if (const char* e = getenv("FDCAP_NN_BOX_LANES")) { const int v = atoi(e); s.nn_box_lanes = (v == 2 || v == 4 || v == 8) ? v : 0; }
+    s.nn_segments_loop = clip_segments_loop_env();           // FDCAP_NN_SEGMENTS=loop (named where segments are defined: fdc_clips.h)
     return s;
 }
 inline const FormSwitches& proc_switches() { static const FormSwitches s = forms_read_env(); return s; }
@@ -413,6 +419,37 @@ inline NNPlan plan_nn_search(int nq, int nt, bool culled, bool frags, bool seed_
     // twice the workgroups: 0.92 ms vs 1.10 ms at NQ = 4, 1.09 ms at NQ = 1).
     if (mfma) { p.form = F_NN_MFMA; p.nq_blocks = culled ? 2 : 4; }
     p.grid = nn_grid_blocks(mfma && culled ? (nq + 255) / 256 : (nq + 511) / 512, nsplit);
+    return p;
+}
+
+// The in-loop search of a batch of clips of several scenes (fdc_clips.h: segments, each with its own scene, queries and pruning
+// state).  The plain form -- the specification -- is one nn_search launch set per segment, in segment order.  When the LARGEST
+// segment's own plan is the one-wave streaming form, all segments go through that form in ONE launch instead
+// (nn_stream4_kernel<1, 1, true>: blockIdx.y the segment, grid.x the largest segment's groups; a smaller segment's surplus
+// workgroups return at once).  Smaller segments then take the one-wave form too where their own size would pick two or four waves
+// per group -- results never depend on the form.  Not taken: with FDCAP_NN_SEGMENTS=loop, for one segment (today's launch), for
+// more segments than the kernel argument holds, and whenever some segment cannot stream at all (its plan is a staged scan).
+// seg_nq / seg_nt [nseg]: each segment's queries and scene points; the other arguments as plan_nn_search takes them.
+constexpr int NN_MAX_SEGS = 16;                  // segment descriptors in the kernel argument (152 B each)
+struct NNSegPlan {
+    bool one_launch = false;
+    const char* name = nullptr;                   // what fdcap_debug_kernel_forms reports for the one launch (the plain form reports each segment's own)
+    int grid_x = 0, grid_y = 0, block = 64;
+};
+inline NNSegPlan plan_nn_segments(int nseg, const int* seg_nq, const int* seg_nt, bool culled, bool frags, bool seed_in_place, int nsplit, int mode,
+                                  const FormSwitches& sw) {
+    NNSegPlan p;
+    if (nseg < 2 || nseg > NN_MAX_SEGS || sw.nn_segments_loop) return p;
+    int big = 0;
+    for (int s = 0; s < nseg; ++s) {
+        if (seg_nq[s] > seg_nq[big]) big = s;
+        if (plan_nn_search(seg_nq[s], seg_nt[s], culled, frags, seed_in_place, nsplit, mode, sw).wpg == 0) return p;
+    }
+    const NNPlan pl = plan_nn_search(seg_nq[big], seg_nt[big], culled, frags, seed_in_place, nsplit, mode, sw);
+    if (pl.form != F_NN_STREAM_W1) return p;
+    p.one_launch = true;
+    p.name = "nn_stream4_kernel(1 wave per group, segments)";
+    p.grid_x = pl.grid; p.grid_y = nseg; p.block = pl.block;
     return p;
 }
 

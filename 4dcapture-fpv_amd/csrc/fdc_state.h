@@ -78,6 +78,44 @@ struct SkinSet {          // skinning constants for a vertex set (all V, or the 
     }
 };
 
+// One registered scene: the full table set fdcap_set_scene builds (fdc_scene.h)
+struct SceneSet {
+    DevBuf<float4> scene;          // original order {x,y,z,bits(i)}: gradient gather by index
+    DevBuf<float4> scene_sorted;   // k-d cell order {x,y,z,bits(original index)}: what the NN scan streams
+    DevBuf<float4> scene_bounds;   // axis-aligned box {lo},{hi} of each MF_CH-point chunk of scene_sorted
+    DevBuf<float4> scene_sbounds;  // ... of each run of ST4_SUPER chunks
+    DevBuf<float4> scene_qbounds;  // ... of each quarter chunk (128 points = four MFMA tiles, one k-d node): [chunk][4]{lo},{hi}
+    DevBuf<int> scene_inv;         // original index -> position in scene_sorted
+    DevBuf<uint4> scene_frags;     // precomputed chunk-centred bf16 MFMA A fragments of scene_sorted
+    DevBuf<float4> scene_centers;  // chunk centres {x,y,z,radius}
+    int64_t ns = 0;
+    NNTarget nn_target(bool cull) const {
+        NNTarget t; t.pts = scene_sorted.p; t.n = (int)ns; t.bounds = cull ? scene_bounds.p : nullptr; t.inv_perm = scene_inv.p;
+        t.sbounds = cull ? scene_sbounds.p : nullptr; t.qbounds = cull ? scene_qbounds.p : nullptr;
+        t.frags = cull ? scene_frags.p : nullptr; t.centers = scene_centers.p;
+        return t;
+    }
+    void release() {
+        scene.release(); scene_sorted.release(); scene_bounds.release(); scene_sbounds.release(); scene_qbounds.release();
+        scene_inv.release(); scene_frags.release(); scene_centers.release();
+        ns = 0;
+    }
+};
+static_assert(CLIP_MAX_SCENES == FDCAP_MAX_SCENES, "fdc_clips.h restates the number of scene slots");
+
+// The search state of ONE segment of a batch of clips of several scenes (fdc_clips.h): what OptState keeps once for a one-scene
+// optimiser -- kept lists, headers + launch-order tables, anchors, the query order and its host bookkeeping, whether it has seeds.
+struct SegSearch {
+    ClipSegment seg = {};
+    DevBuf<unsigned short> ids;
+    DevBuf<int> hdr;
+    DevBuf<float4> anchor;
+    DevBuf<int> qbuf;
+    NNOrder ord;
+    int nsplit = 1;           // scene splits of the segment's staged scans (nn_pick_nsplit for its own queries and scene)
+    bool seeded = false;
+};
+
 struct OptState {
     fdcap_opt_config cfg;     // a batch of clips (fdcap_opt_create_clips): n_total = n_local = nclip * clip length, frame0 = 0
     int R = 0;            // rows = n_local + 4
@@ -157,6 +195,20 @@ struct OptState {
         nc.box_lanes = sw.nn_box_lanes;
         return nc;
     }
+    // Clips of several scenes (fdcap_opt_create_clips_scenes): one entry per segment, each with the search state the members above
+    // are for a one-scene optimiser (which keeps none here: segs is empty, and every path is the one it was).  Mode 'global' only.
+    std::vector<SegSearch> segs;
+    bool multi_scene() const { return segs.size() > 1; }
+    int scene_slot = 0;            // the registered scene a one-scene optimiser searches (fdcap_ctx::scenes)
+    // several scenes, and the last search took a form that keeps no records: seedpt was filled from each segment's own scene
+    // afterwards (the backward's one `scene` pointer cannot serve several), so it holds coordinates but was not the search's own
+    bool nnpt_filled = false;
+    NNCache nn_cache_of(SegSearch& g) {
+        NNCache nc{sw.nn_cache_slack > 0.f ? g.ids.p : nullptr, sw.nn_cache_slack > 0.f ? g.hdr.p : nullptr, g.anchor.p, sw.nn_cache_slack};
+        nc.keep = sw.nn_keep_records;
+        nc.box_lanes = sw.nn_box_lanes;
+        return nc;
+    }
     DevBuf<float> dA, dtransl_v, dMv, dsv, dPF, dJw, dX, dCAM, dscale_row;     // d betas: columns 486.. of dPF
     DevBuf<float> VoffF, VwF, dVF;      // mode 'local' second loop: full-mesh pose offsets / world vertices / gradient
     int cam_steps = 0;
@@ -229,21 +281,19 @@ struct fdcap_ctx {
     VPoserPanels3 vp3;
     SkinSet full, contact;
     bool full_ready = false;
-    DevBuf<float4> scene;          // original order {x,y,z,bits(i)}: gradient gather by index
-    DevBuf<float4> scene_sorted;   // k-d cell order {x,y,z,bits(original index)}: what the NN scan streams
-    DevBuf<float4> scene_bounds;   // axis-aligned box {lo},{hi} of each MF_CH-point chunk of scene_sorted
-    DevBuf<float4> scene_sbounds;  // ... of each run of ST4_SUPER chunks
-    DevBuf<float4> scene_qbounds;  // ... of each quarter chunk (128 points = four MFMA tiles, one k-d node): [chunk][4]{lo},{hi}
-    DevBuf<int> scene_inv;         // original index -> position in scene_sorted
-    DevBuf<uint4> scene_frags;     // precomputed chunk-centred bf16 MFMA A fragments of scene_sorted
-    DevBuf<float4> scene_centers;  // chunk centres {x,y,z,radius}
-    int64_t ns = 0;
-    NNTarget nn_target(bool cull) const {
-        NNTarget t; t.pts = scene_sorted.p; t.n = (int)ns; t.bounds = cull ? scene_bounds.p : nullptr; t.inv_perm = scene_inv.p;
-        t.sbounds = cull ? scene_sbounds.p : nullptr; t.qbounds = cull ? scene_qbounds.p : nullptr;
-        t.frags = cull ? scene_frags.p : nullptr; t.centers = scene_centers.p;
-        return t;
-    }
+    // The registered scenes: slot 0 is THE scene of every one-scene entry point (fdcap_set_scene, the scene operator, the
+    // diagnostics); the other slots only serve a batch whose clips name them (fdcap_opt_create_clips_scenes).
+    SceneSet scenes[FDCAP_MAX_SCENES];
+    DevBuf<float4>& scene = scenes[0].scene;
+    DevBuf<float4>& scene_sorted = scenes[0].scene_sorted;
+    DevBuf<float4>& scene_bounds = scenes[0].scene_bounds;
+    DevBuf<float4>& scene_sbounds = scenes[0].scene_sbounds;
+    DevBuf<float4>& scene_qbounds = scenes[0].scene_qbounds;
+    DevBuf<int>& scene_inv = scenes[0].scene_inv;
+    DevBuf<uint4>& scene_frags = scenes[0].scene_frags;
+    DevBuf<float4>& scene_centers = scenes[0].scene_centers;
+    int64_t& ns = scenes[0].ns;
+    NNTarget nn_target(bool cull) const { return scenes[0].nn_target(cull); }
     int nc = 0;
     DevBuf<int> contact_vid;       // mesh vertex of each contact id (caller's order)
     DevBuf<int> contact_perm;      // internal contact slot -> position in the caller's id array
@@ -606,6 +656,9 @@ inline bool opt_whole_clips(const OptState* o) { return o->cfg.frame0 == 0 && o-
 // a batch of several clips (fdcap_opt_create_clips): the single-step entry points of modes 'local' / 'dct', the per-frame inner fit
 // and the sharded exchange refuse it (FDCAP_E_STATE); it reaches those two modes through fdcap_opt_run_local2 / fdcap_opt_run_dct
 inline bool opt_is_batch(const fdcap_ctx* c) { return c && c->opt && c->opt->nclip > 1; }
+// ... of clips of several scenes (fdcap_opt_create_clips_scenes, more than one segment): mode 'global' only -- on top of what a batch
+// is refused, fdcap_opt_run_local2, fdcap_opt_set_dct_clips and fdcap_opt_run_dct return FDCAP_E_STATE
+inline bool opt_is_multi_scene(const fdcap_ctx* c) { return c && c->opt && c->opt->multi_scene(); }
 
 // rows of the optimiser's buffers whose pose is needed: the owned frames plus `halo` frames on each side that has a neighbour
 void opt_row_range(const OptState* o, int halo, int* lo, int* hi) {

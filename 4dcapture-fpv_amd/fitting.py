@@ -942,6 +942,7 @@ class ClipBatchFitter(_Fitter):
         super().__init__(fittingconfig, lossconfig, body_model, vposer, contact_ids, n_left, legacy_zero_grad, dct_num_iter)
         self.ctx.set_contact_ids(self.vid)
         self.scene_key = None
+        self._slot_keys = [None] * capi.MAX_SCENES          # the keys of the scenes in slots 1.. (slot 0's is scene_key)
         self._has_opt = False
         self.logs, self.logs2, self.logs_dct, self.contact_weights, self.idx1, self.c_dct = [], [], [], [], [], []      # (a batch's results)
         self._dct_in = (None, None)
@@ -969,9 +970,15 @@ class ClipBatchFitter(_Fitter):
             raise ValueError(f"mode 'dct' needs at least one {BATCH_FRAME_NUM}-frame window in every clip (:41-42); "
                              "shorter clips fit in mode 'global' or 'local'")
 
-    def fit(self, clips, scene_verts=None, scene_key=None, log_every=0, mode="global", c_dct_init=None, dct_mtx=None):
+    def fit(self, clips, scene_verts=None, scene_key=None, log_every=0, mode="global", c_dct_init=None, dct_mtx=None, scenes=None,
+            clip_scene=None):
         """clips: sequence of K (body_data [N_k,75], camera_ext [N_k,4,4]) pairs (numpy or device tensors); every clip has its own N_k.
         scene_verts / scene_key: the batch's scene (see set_scene; both None: the registered scene).
+        scenes / clip_scene: clips of DIFFERENT scenes in one batch (mode 'global') -- scenes: a list whose entries are the points
+        [ns,3] or (key, points) pairs (points None: a slot holds the key already), clip_scene: for every clip its entry of scenes;
+        at most capi.MAX_SCENES scenes in use.  The scenes go into the context's slots (a key a slot holds is not registered
+        again), the clips enter the batch ordered so that every scene is one run (fdcap_opt_create_clips_scenes), and the results,
+        self.logs and self.idx1 come back in the caller's order.  One scene in use: the one-scene batch.
         mode: 'global', 'local' (the reference's default, :491) or 'dct' -- then c_dct_init: K arrays [W_k,23,3,C], W_k = N_k // 60
         (None: torch.randn, clip after clip, :186), dct_mtx [60,C] (None: load_dct_base, as FittingOP).
         Returns a list of K (body_rec [N_k,75] device tensor, scale numpy scalar, camera_ext [N_k,4,4] device tensor) -- what
@@ -981,16 +988,89 @@ class ClipBatchFitter(_Fitter):
         self.c_dct, its rows [ii, loss_dct] of the first phase in self.logs_dct and [ii, l_rec, l_vposer, loss_smoothing, loss_contact,
         loss_dct, total] of the second in self.logs2 (FittingOP.log_dct / log2, over the clip's own frames and windows)."""
         self._check_mode(clips, mode)
+        if scenes is not None or clip_scene is not None:
+            return self._fit_scenes(clips, scenes, clip_scene, log_every, mode, c_dct_init, dct_mtx)
         if scene_verts is not None or scene_key is not None:
             self.set_scene(scene_verts, scene_key)
         self.prepare(clips, mode, c_dct_init, dct_mtx)
         return self.run(log_every)
 
-    def prepare(self, clips, mode="global", c_dct_init=None, dct_mtx=None):
+    @staticmethod
+    def plan_scene_runs(clip_scene, n_scenes, max_scenes=capi.MAX_SCENES):
+        """clip_scene[k]: the entry of `scenes` clip k is fitted against.  -> (the scenes in use in order of first use, the order
+        in which the clips enter the batch: every scene ONE run of adjacent clips, runs in order of first use, clips in input order
+        within a run).  Needs no device."""
+        cs = [int(s) for s in clip_scene]
+        if any(s < 0 or s >= n_scenes for s in cs):
+            raise ValueError(f"clip_scene names a scene outside [0, {n_scenes})")
+        used = list(dict.fromkeys(cs))
+        if len(used) > max_scenes:
+            raise ValueError(f"a batch holds clips of at most {max_scenes} scenes (got {len(used)}): split it (cli.plan_batches_scenes)")
+        rank = {s: r for r, s in enumerate(used)}
+        return used, sorted(range(len(cs)), key=lambda k: rank[cs[k]])
+
+    def _fit_scenes(self, clips, scenes, clip_scene, log_every, mode, c_dct_init, dct_mtx):
+        """fit() for clips of several scenes: registers the scenes in slots (a scene whose key a slot already holds is reused),
+        orders the clips so that every scene is one run, fits the batch and hands everything back in the caller's order."""
+        if scenes is None or clip_scene is None or len(clip_scene) != len(clips):
+            raise ValueError("scenes=[...] and clip_scene=[one entry of scenes per clip] go together")
+        # an entry of `scenes`: the points [ns,3], or (key, points) -- points may be None when a slot already holds the key
+        ent = [(s[0], s[1]) if isinstance(s, tuple) else (None, s) for s in scenes]
+        used, order = self.plan_scene_runs(clip_scene, len(ent))
+        if len(used) > 1 and mode != "global":
+            raise ValueError(f"clips of several scenes fit in mode 'global' only (got mode '{mode}'): modes 'local' and 'dct' take "
+                             "batches of one scene")
+        if len(used) == 1:                                   # one scene: the batch it always was
+            key, pts = ent[used[0]]
+            if key is not None and key == self.scene_key:
+                pts = None
+            elif key is not None and key in self._slot_keys[1:]:      # held by another slot: the one-scene batch on that slot
+                self.prepare(clips, mode, c_dct_init, dct_mtx, clip_slots=[self._slot_keys.index(key, 1)] * len(clips))
+                return self.run(log_every)
+            elif pts is None:
+                raise ValueError(f"scene {key!r} is not registered and no points were given")
+            return self.fit(clips, pts, key, log_every, mode, c_dct_init, dct_mtx)
+        # slots: first the scenes whose key a slot holds, then the others into the slots this batch leaves free
+        keys = [self.scene_key] + self._slot_keys[1:]
+        slot_of = {}
+        for s in used:
+            key = ent[s][0]
+            if key is not None and key in keys and keys.index(key) not in slot_of.values():
+                slot_of[s] = keys.index(key)
+        free = [i for i in range(capi.MAX_SCENES) if i not in slot_of.values()]
+        free.sort(key=lambda i: (keys[i] is not None or (i == 0 and self.ctx.num_scene > 0), i))     # empty slots first
+        for s in used:
+            if s in slot_of:
+                continue
+            key, pts = ent[s]
+            if pts is None:
+                raise ValueError(f"scene {key!r} is not registered and no points were given")
+            i = free.pop(0)
+            if i == 0:
+                self.set_scene(pts, key)
+            else:
+                self._destroy_opt()                          # (the library refuses a new scene while an optimiser exists)
+                self.ctx.set_scene_slot(i, pts)
+                self._slot_keys[i] = key
+            slot_of[s] = i
+        batch = [clips[k] for k in order]
+        self.prepare(batch, mode, c_dct_init, dct_mtx, clip_slots=[slot_of[int(clip_scene[k])] for k in order])
+        res = self.run(log_every)
+        back = [0] * len(order)
+        for pos, k in enumerate(order):
+            back[k] = pos
+        self.logs = [self.logs[p] for p in back]
+        self.idx1 = [self.idx1[p] for p in back]
+        return [res[p] for p in back]
+
+    def prepare(self, clips, mode="global", c_dct_init=None, dct_mtx=None, clip_slots=None):
         """init() of a batch (:450-489 per clip): creates the batch's optimiser on the registered scene and stages its inputs.
-        mode 'local': the config of its first loop (:511, :523), as FittingOP.init builds it; mode 'dct': mode 'global''s, as there."""
+        mode 'local': the config of its first loop (:511, :523), as FittingOP.init builds it; mode 'dct': mode 'global''s, as there.
+        clip_slots (optional): the registered scene slot of every clip (fdcap_opt_create_clips_scenes)."""
         import torch
         self._check_mode(clips, mode)
+        if clip_slots is not None and len(set(clip_slots)) > 1 and mode != "global":
+            raise ValueError("clips of several scenes fit in mode 'global' only")
         self._mode = mode
         self._dct_in = (c_dct_init, dct_mtx)
         K = len(clips)
@@ -1024,7 +1104,13 @@ class ClipBatchFitter(_Fitter):
         n_cfg = lens[0] if equal else total
         oc = self._opt_config(n_cfg, n_cfg, 0)
         state = self._new_state(total + 4, K, (K, capi.NUM_LOSSES))
-        if equal:
+        if clip_slots is not None:
+            if len(clip_slots) != K:
+                raise ValueError("clip_slots holds one scene slot per clip")
+            oc = self._opt_config(total, total, 0)           # (the batch's rows, as fdcap_opt_create_clips_var takes them)
+            capi.check(lib.fdcap_opt_create_clips_scenes(h, ctypes.byref(oc), K, (ctypes.c_int32 * K)(*lens), (ctypes.c_int32 * K)(*clip_slots),
+                                                         *state), "fdcap_opt_create_clips_scenes")
+        elif equal:
             capi.check(lib.fdcap_opt_create_clips(h, ctypes.byref(oc), K, *state), "fdcap_opt_create_clips")
         else:
             capi.check(lib.fdcap_opt_create_clips_var(h, ctypes.byref(oc), K, (ctypes.c_int32 * K)(*lens), *state), "fdcap_opt_create_clips_var")

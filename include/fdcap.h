@@ -37,7 +37,8 @@ extern "C" {
 #define FDCAP_XDIM 78         /* optimised row: transl3 6D6 betas10 latent32 lh12 rh12 camt3 */
 #define FDCAP_PDIM 75         /* file row:      transl3 aa3 betas10 latent32 lh12 rh12 camt3 */
 #define FDCAP_MAX_SCENE_POINTS 67000000   /* fdcap_set_scene refuses more (FDCAP_E_ARG): 32 B of MFMA fragments per point, 32-bit offsets */
-#define FDCAP_NUM_LOSSES 8    /* rec, vposer, smoothing, contact, world_smoothing, total, 2 spare */
+#define FDCAP_MAX_SCENES 8    /* scene slots of a context (fdcap_set_scene_slot); slot 0 is fdcap_set_scene's */
+#define FDCAP_NUM_LOSSES 8   /* rec, vposer, smoothing, contact, world_smoothing, total, 2 spare */
 
 typedef struct fdcap_ctx fdcap_ctx;
 
@@ -98,6 +99,13 @@ const char* fdcap_build_info(void);
  * Both setters return FDCAP_E_STATE while an optimiser exists on the context (fdcap_opt_create .. fdcap_opt_destroy): its
  * buffers are sized for the registered sets and its pruning state (seeds, kept work lists) is only valid for them. */
 int fdcap_set_scene(fdcap_ctx* ctx, const float* scene_xyz, int64_t ns);
+/* Several registered scenes per context: slot 0 .. FDCAP_MAX_SCENES - 1, each with its own full table set, built exactly as
+ * fdcap_set_scene builds its one (the same device build, the same FDCAP_SCENE_BUILD=host specification).  Slot 0 IS
+ * fdcap_set_scene: fdcap_chamfer_fwd_scene / fdcap_chamfer_bwd_scene, ops.chamferDist's recognition of the registered scene,
+ * fdcap_debug_scene_hash / fdcap_debug_scene_table and every optimiser but fdcap_opt_create_clips_scenes' mean slot 0.  For the
+ * other slots ns = 0 clears the slot and frees its tables.  FDCAP_E_STATE while an optimiser exists (as fdcap_set_scene, for every
+ * slot); FDCAP_E_ARG for a slot out of range. */
+int fdcap_set_scene_slot(fdcap_ctx* ctx, int32_t slot, const float* scene_xyz, int64_t ns);
 /* Diagnosis: out8[0..7] = FNV-1a hashes of the registered scene's device tables (input-order points, cell-ordered points, inverse
  * permutation, cell / quarter-cell / super-cell boxes, MFMA fragments, cell centres).  The tables are built on the device since r6
  * (csrc/fdc_scene.h); with FDCAP_SCENE_BUILD=host in the environment fdcap_set_scene takes the cell order from the host recursion of
@@ -272,6 +280,21 @@ int fdcap_opt_create_clips(fdcap_ctx* ctx, const fdcap_opt_config* cfg, int32_t 
  * FDCAP_E_ARG: clip_len NULL, a length <= 0, a sum that is not cfg->n_total == cfg->n_local or exceeds 2^24, frame0 != 0. */
 int fdcap_opt_create_clips_var(fdcap_ctx* ctx, const fdcap_opt_config* cfg, int32_t n_clips, const int32_t* clip_len, float* rows_x_d,
                                float* rows_cam_d, float* scale_d, float* dscale_d, double* losses_d);
+/* Clips of DIFFERENT SCENES in one batch: fdcap_opt_create_clips_var plus clip_scene [n_clips], the scene slot
+ * (fdcap_set_scene_slot) clip k is fitted against.  A SEGMENT is a maximal run of adjacent clips of one slot (slots A, B, A: three
+ * segments).  Only the Chamfer search knows segments: each searches its own scene with its own pruning state (kept lists, launch
+ * and query order with their 32-launch cadence, seeding) -- one launch for all segments where the largest is large enough for the
+ * one-wave streaming form, else (and with FDCAP_NN_SEGMENTS=loop in the environment at create) one launch set per segment; the
+ * same bits either way.  Every other kernel sees the rows of fdcap_opt_create_clips_var's batch.  A clip's results equal its
+ * stand-alone fit against its own scene bit for bit under equal kernel forms.
+ * All clips on one slot: exactly fdcap_opt_create_clips_var (one segment, its path and bits), on that slot's scene.
+ * Mode 'global' only: with more than one segment fdcap_opt_run_local2, fdcap_opt_set_dct_clips, fdcap_opt_run_dct,
+ * fdcap_opt_time_chamfer(brute_force) and fdcap_debug_nn_query_order return FDCAP_E_STATE, on top of everything a batch is refused
+ * (mode 'local''s and 'dct''s single steps, the per-frame inner fit, every exchange call, fdcap_opt_forward_ahead).
+ * FDCAP_E_ARG: what fdcap_opt_create_clips_var refuses, clip_scene NULL or a slot outside [0, FDCAP_MAX_SCENES).  FDCAP_E_STATE:
+ * a named slot holds no scene. */
+int fdcap_opt_create_clips_scenes(fdcap_ctx* ctx, const fdcap_opt_config* cfg, int32_t n_clips, const int32_t* clip_len, const int32_t* clip_scene,
+                                  float* rows_x_d, float* rows_cam_d, float* scale_d, float* dscale_d, double* losses_d);
 /* data78_d [n_local,78]: the 6D-converted SMPLify-X rows (loss_rec target);
  * init78_d [n_local,78]: initial value of body_rotation_rec (= data with outlier rows replaced, :487);
  * mask_d   [n_local]   : 0 for outlier rows (idx1), 1 otherwise (:255-257);
@@ -579,7 +602,9 @@ void fdcap_opt_destroy(fdcap_ctx* ctx);
 int fdcap_opt_forward_world(fdcap_ctx* ctx, float* verts_d, float* joints_d, void* stream);
 /* Nearest-neighbour result of the last contact forward (testing): dist_d [n_local,nc] squared
  * distances, idx_d [n_local,nc] scene indices.  The optimiser seeds each search with the previous
- * call's idx (an exact upper bound that only prunes; FDCAP_NN_SEED=0 disables). */
+ * call's idx (an exact upper bound that only prunes; FDCAP_NN_SEED=0 disables).
+ * A batch of clips of several scenes (fdcap_opt_create_clips_scenes): both arrays stay flat per query, and idx is an index into
+ * the scene of the query's OWN clip, in that scene's input order (below that slot's point count, not slot 0's). */
 int fdcap_opt_get_contact(fdcap_ctx* ctx, float* dist_d, int32_t* idx_d, void* stream);
 /* Gradients of the last fdcap_opt_backward (testing): dx_d [n_local,78], dcam_d [n_local,16]. */
 int fdcap_opt_get_grads(fdcap_ctx* ctx, float* dx_d, float* dcam_d, void* stream);

@@ -2,7 +2,7 @@
 """Per-kernel text comparison of two device assembly listings of the library.
 
     hipcc <build()'s flags> --cuda-device-only -S -o a.s 4dcapture-fpv_amd/csrc/fdcap.hip      (once per tree)
-    python tools/asm_kernel_diff.py a.s b.s [--show KERNEL]
+    python tools/asm_kernel_diff.py a.s b.s [--show KERNEL] [--pair A_KERNEL=B_KERNEL ...]
 
 Every kernel (.amdhsa_kernel name) present in either file gets one of
     identical    the same instruction text (comments, debug directives and label numbers aside)
@@ -10,7 +10,9 @@ Every kernel (.amdhsa_kernel name) present in either file gets one of
     differs      other instructions; the instruction counts of both sides are given
     only in A/B
 A generic text diff: it looks for no particular instruction.  --show prints the unified diff of one kernel (demangled name
-prefix or mangled name)."""
+prefix or mangled name).  --pair compares kernel A_KERNEL of a.s with kernel B_KERNEL of b.s (demangled names, as printed) -- for a
+kernel whose signature or template parameter list changed between the two trees, so that its symbol did: e.g.
+--pair 'fdc::nn_stream4_kernel<1, 1>=fdc::nn_stream4_kernel<1, 1, false>'."""
 import argparse
 import difflib
 import re
@@ -66,8 +68,18 @@ def main():
     ap.add_argument("a")
     ap.add_argument("b")
     ap.add_argument("--show", default=None)
+    ap.add_argument("--pair", action="append", default=[], metavar="A_KERNEL=B_KERNEL")
     args = ap.parse_args()
     ka, kb = kernels(args.a), kernels(args.b)
+    if args.pair:                                                   # file B's kernel takes file A's symbol
+        da, db = demangle(sorted(ka)), demangle(sorted(kb))
+        for pr in args.pair:
+            na, nb = pr.split("=", 1)
+            ma, mb = [n for n in ka if da[n] == na], [n for n in kb if db.get(n) == nb]
+            if len(ma) != 1 or len(mb) != 1:
+                sys.exit(f"--pair {pr}: {len(ma)} kernels of that name in A, {len(mb)} in B")
+            kb[ma[0]] = kb.pop(mb[0])
+            print(f"paired     {na}  =  {nb}")
     names = sorted(set(ka) | set(kb))
     dm = demangle(names)
     if args.show:

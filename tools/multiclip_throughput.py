@@ -20,7 +20,11 @@ second phase): K = 1, 3 and 8 clips of 300 frames through ClipBatchFitter.fit(mo
 mode-'dct' fits in the same process, under mode 'local''s protocol (one warm-up each, R rounds that alternate the two, medians), and
 the batch's two phases on their own -- fdcap_opt_run_dct cut at the phase switch, each stretch between two device events
 (profiles/multiclip300_dct.json).
-usage: python tools/multiclip_throughput.py [--reps R] [--out FILE] [--mode local|dct] [--lengths n0,n1,...]..."""
+--scenes: instead of the sweep, K = 3 clips of 300 frames on three different 500 k-point scenes: the multi-scene batch through the
+one-launch segmented search, the same batch searched segment after segment (FDCAP_NN_SEGMENTS=loop), and three one-clip fits that
+each register their scene first -- alternated in one process, medians of R, and the live per-launch tables of the two batches
+(profiles/multiscene300.json).  --scenes-c-only: the third alone, through the one-scene interface (any tree).
+usage: python tools/multiclip_throughput.py [--reps R] [--out FILE] [--mode local|dct] [--lengths n0,n1,...]... [--scenes]"""
 import json
 import os
 import sys
@@ -38,8 +42,11 @@ N, ITERS, NS, KS = 300, 500, 500_000, (1, 2, 3, 4, 6, 8)
 
 def main():
     argv = sys.argv[1:]
-    reps, out, lengths, mode = 3, None, [], "global"
+    reps, out, lengths, mode, multi_scene = 3, None, [], "global", None
     while argv:
+        if argv[0] in ("--scenes", "--scenes-c-only"):
+            multi_scene, argv = argv[0], argv[1:]
+            continue
         if argv[0] == "--mode" and len(argv) > 1 and argv[1] in ("global", "local", "dct"):
             mode, argv = argv[1], argv[2:]
         elif argv[0] == "--reps":
@@ -60,6 +67,10 @@ def main():
     scene = synth.make_scene(NS, seed=2)
     left, right = synth.make_contact_ids(bm.v_template, per_part=250, seed=4)
     vid = np.concatenate([left, right])
+    if multi_scene:
+        if lengths or mode != "global":
+            raise SystemExit("--scenes measures three 300-frame clips in mode 'global': not with --lengths / --mode")
+        return scenes_mode(reps, out, bm, vp, vid, multi_scene == "--scenes-c-only")
     if mode in ("local", "dct"):
         if lengths:
             raise SystemExit(f"--mode {mode} measures clips of 300 frames: not with --lengths")
@@ -125,6 +136,76 @@ def main():
     res["twelve_clips"] = {"clips_per_batch": k_def, "batch_driver_s": t_batch, "fittingop_each_s": t_single,
                            "batch_driver_frames_per_s": 12 * N / t_batch, "fittingop_each_frames_per_s": 12 * N / t_single,
                            "note": "host clock from the first constructor to the last result on the host; model and scene arrays in memory"}
+    res["device"] = torch.cuda.get_device_name(0)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if out:
+        with open(out, "w") as fh:
+            fh.write(line + "\n")
+
+
+def scenes_mode(reps, out, bm, vp, vid, c_only):
+    """K = 3 clips of N frames on three DIFFERENT 500 k-point scenes, mode 'global': (a) one multi-scene batch through the one-launch
+    segmented search, (b) the same batch with FDCAP_NN_SEGMENTS=loop (one search launch set per segment), (c) three one-clip fits
+    through one ClipBatchFitter that registers each clip's scene before its fit -- what a run of videos with a scene each cost before
+    scenes could share a batch.  One warm-up each, then R rounds that alternate the three, each timed by the host clock around fits
+    that end with the results on the host; medians.  (a) and (b) register their scenes once (the slots keep them by key).
+    c_only: only (c), through nothing but the one-scene interface -- runs on a tree without scene slots too."""
+    from fdcap_amd import synth
+    from fdcap_amd.fitting import ClipBatchFitter
+    from fdcap_amd.io import read_camerapose
+    K = 3
+    clips, scenes = [], []
+    for k in range(K):
+        c = synth.make_clip(N, seed=100 + k)
+        clips.append((c.body_params, read_camerapose(c.camerapose_lines)))
+        scenes.append(synth.make_scene(NS, seed=2 + 10 * k) + np.array([0.0, 0.0, 0.05 * k], np.float32))
+    fitter = ClipBatchFitter({"num_iter": ITERS}, {}, body_model=bm, vposer=vp, contact_ids=vid)
+    fitter_c = ClipBatchFitter({"num_iter": ITERS}, {}, body_model=bm, vposer=vp, contact_ids=vid)      # (its own context: (c) replaces slot 0's scene)
+
+    def batch(loop):
+        if loop:
+            os.environ["FDCAP_NN_SEGMENTS"] = "loop"
+        try:
+            t0 = time.perf_counter()
+            r = [(b.cpu(), s, c.cpu()) for b, s, c in fitter.fit(clips, scenes=[(f"scene{k}", scenes[k]) for k in range(K)], clip_scene=list(range(K)))]
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, r
+        finally:
+            os.environ.pop("FDCAP_NN_SEGMENTS", None)
+
+    def each():
+        t0 = time.perf_counter()
+        r = []
+        for k in range(K):
+            (b, s, c), = fitter_c.fit([clips[k]], scenes[k], scene_key=f"one{k}")
+            r.append((b.cpu(), s, c.cpu()))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, r
+
+    res = {"problem": {"verts": 10475, "contacts": len(vid), "scene": NS, "scenes": K, "frames_per_clip": N, "iters": ITERS, "clips": K,
+                       "reps": reps}}
+    ways = {"c_one_clip_fits_scene_registered_per_clip": each} if c_only else \
+        {"a_segmented_launch": lambda: batch(False), "b_segment_loop": lambda: batch(True), "c_one_clip_fits_scene_registered_per_clip": each}
+    first = {name: fn()[1] for name, fn in ways.items()}                       # (warm-up; and the three ways agree)
+    if not c_only:
+        ra, rb, rc = first["a_segmented_launch"], first["b_segment_loop"], first["c_one_clip_fits_scene_registered_per_clip"]
+        res["a_equals_b_bit_for_bit"] = all(torch.equal(x[0], y[0]) and torch.equal(x[2], y[2]) for x, y in zip(ra, rb))
+        res["max_abs_body_difference_a_c"] = max(float((x[0] - y[0]).abs().max()) for x, y in zip(ra, rc))
+    times = {name: [] for name in ways}
+    for _ in range(reps):
+        for name, fn in ways.items():
+            times[name].append(fn()[0])
+    for name, ts in times.items():
+        m = float(np.median(ts))
+        res[name] = {"ms": m * 1e3, "ms_all": [t * 1e3 for t in ts], "frames_per_s": K * N / m, "clips_per_s": K / m}
+        print(f"{name}: {m * 1e3:8.2f} ms  {K * N / m:9.0f} frames/s", file=sys.stderr, flush=True)
+    if not c_only:
+        for name, loop in (("a_segmented_launch", False), ("b_segment_loop", True)):
+            live = bench.time_all_launches(fitter, lambda: batch(loop), ITERS, res[name]["ms"] * 1e-3)
+            res[name]["launch_table"] = {ph: {k: round(v.get("us_corrected", v["us"]), 2) for k, v in live[ph].items()} for ph in ("phase1", "phase2")}
+    fitter.close()
+    fitter_c.close()
     res["device"] = torch.cuda.get_device_name(0)
     line = json.dumps(res)
     print(line, flush=True)
