@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("FDCAP_LIB") or os.path.join(_HERE, "libfdcap_hip.so")
 
 NUM_LOSSES = 8
 MAX_SCENES = 8          # FDCAP_MAX_SCENES: scene slots of a context
+MAX_KEYPOINTS = 160     # FDCAP_MAX_KEYPOINTS: keypoints of a context's map
 XDIM = 78
 PDIM = 75
 
@@ -130,6 +131,9 @@ SYMBOLS = {
     "fdcap_frame_smoother": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_float, c_float, c_float,
                                         c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "fdcap_opt_set_keypoints": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "fdcap_set_keypoint_map": (c_int32, [c_void_p, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_float)]),
+    "fdcap_opt_set_keypoints_mapped": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "fdcap_debug_keypoints3d": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_backward_fit2d": (c_int32, [c_void_p, POINTER(Fit2dStage), c_int32, c_void_p]),
     "fdcap_opt_reset_adam": (c_int32, [c_void_p, c_void_p]),
     "fdcap_lbfgs_create": (c_int32, [c_int32, POINTER(LbfgsConfig), POINTER(c_void_p)]),
@@ -300,6 +304,17 @@ class Context:
         check(self.lib.fdcap_set_contact_ids(self.handle, v.ctypes.data_as(c_void_p), v.shape[0]),
               "fdcap_set_contact_ids")
         self.num_contact = v.shape[0]
+
+    def set_keypoint_map(self, joint, tri, bary):
+        """The inner fit's keypoint map (innerfit.KeypointMap holds the three arrays); empty arrays clear it."""
+        j = np.ascontiguousarray(joint, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+        b = _f32(np.asarray(bary).reshape(-1, 3))
+        if t.shape[0] != j.shape[0] or b.shape[0] != j.shape[0]:
+            raise FdcapError("joint [n], tri [n,3] and bary [n,3] must describe the same keypoints")
+        check(self.lib.fdcap_set_keypoint_map(self.handle, j.shape[0], j.ctypes.data_as(POINTER(c_int32)), t.ctypes.data_as(POINTER(c_int32)),
+                                              _fp(b)), "fdcap_set_keypoint_map")
+        self.num_keypoints = j.shape[0]
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle:

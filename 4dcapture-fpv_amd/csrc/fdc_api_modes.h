@@ -188,7 +188,135 @@ int fdcap_opt_set_keypoints(fdcap_ctx* c, const float* kp_d, void* stream) {
     const size_t n = (size_t)o->cfg.n_local * NJW * 3;
     HIP_TRY(o->kp2d.ensure(n));
     HIP_TRY(hipMemcpyAsync(o->kp2d.p, kp_d, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    o->kp_mapped = false;
     return FDCAP_OK;
+}
+
+// ---- ... on a detector's keypoints: the keypoint map (csrc/fdc_keypoints.h) --------------------------------------------------
+static_assert(KP_MAX == FDCAP_MAX_KEYPOINTS, "fdc_keypoints.h restates the largest map");
+int fdcap_set_keypoint_map(fdcap_ctx* c, int32_t n_kp, const int32_t* joint, const int32_t* tri, const float* bary) {
+    if (!c) return FDCAP_E_ARG;
+    KeypointTables t;
+    if (keypoint_map_build(n_kp, joint, tri, bary, c->V, &t)) return FDCAP_E_ARG;
+    if (c->opt) return FDCAP_E_STATE;                  // (see fdcap_set_scene: a live optimiser may hold keypoints in this map's order)
+    KeypointSet& ks = c->kpset;
+    ks.release();
+    if (n_kp == 0) return FDCAP_OK;
+    const int nr = t.nr, np = t.np, nu = nr + np, V = c->V;
+    // skinning weights of the set: a real vertex's non-zero ones, a pseudo-vertex's single 1 on its joint; and their transpose
+    int K = 1;
+    for (int u = 0; u < nr; ++u) {
+        int k = 0;
+        for (int j = 0; j < NJ; ++j) k += c->h_lbs[(size_t)t.real_ids[u] * NJ + j] != 0.f;
+        K = std::max(K, k);
+    }
+    std::vector<int32_t> wj((size_t)nu * K, 0), csc_start(NJ + 1, 0), csc_u;
+    std::vector<float> ww((size_t)nu * K, 0.f), csc_w, vt((size_t)nr * 3);
+    auto weight = [&](int u, int j) { return u < nr ? c->h_lbs[(size_t)t.real_ids[u] * NJ + j] : (t.pseudo_joint[u - nr] == j ? 1.f : 0.f); };
+    for (int u = 0; u < nu; ++u) {
+        int k = 0;
+        for (int j = 0; j < NJ; ++j) { const float w = weight(u, j); if (w != 0.f) { wj[(size_t)u * K + k] = j; ww[(size_t)u * K + k] = w; ++k; } }
+        if (u < nr) for (int e = 0; e < 3; ++e) vt[3 * u + e] = c->h_vt[(size_t)3 * t.real_ids[u] + e];
+    }
+    for (int j = 0; j < NJ; ++j) {
+        csc_start[j] = (int32_t)csc_u.size();
+        for (int u = 0; u < nu; ++u) { const float w = weight(u, j); if (w != 0.f) { csc_u.push_back(u); csc_w.push_back(w); } }
+    }
+    csc_start[NJ] = (int32_t)csc_u.size();
+    // the set's blend matrix [posedirs ; shapedirs^T]: the real vertices' columns gathered on the device as every vertex set's
+    // (build_skin_set), a pseudo-vertex's columns zero but for Jd_j^T in the betas' rows (its d betas through the panel product);
+    // the real columns' transpose for the in-kernel backward; and the panels of both products
+    const int ldb = (3 * nu + 3) & ~3, ldr = (3 * nr + 3) & ~3;
+    std::vector<float> b((size_t)NPFX * ldb, 0.f), bt((size_t)3 * nr * NPFX);
+    if (nr > 0) {
+        DevBuf<float> d_b;
+        DevBuf<int> d_ids;
+        HIP_TRY(d_b.ensure((size_t)NPFX * ldr));
+        HIP_TRY(d_ids.upload(t.real_ids.data(), t.real_ids.size()));
+        hipLaunchKernelGGL(blend_rows_gather_kernel, dim3((ldr + 255) / 256, NPFX), dim3(256), 0, 0, c->d_posedirs.p, c->d_S10.p, V, d_ids.p, nr, ldr, d_b.p);
+        const hipError_t e_ = hipGetLastError(), es_ = hipDeviceSynchronize();   // (the two are freed at the brace: wait, whatever the launch said)
+        HIP_TRY(e_ != hipSuccess ? e_ : es_);
+        std::vector<float> br((size_t)NPFX * ldr);
+        HIP_TRY(hipMemcpy(br.data(), d_b.p, br.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int k = 0; k < NPFX; ++k)
+            for (int col = 0; col < 3 * nr; ++col) bt[(size_t)col * NPFX + k] = b[(size_t)k * ldb + col] = br[(size_t)k * ldr + col];
+    }
+    if (np > 0) {
+        std::vector<float> jd((size_t)NJ * 3 * NBETA);
+        HIP_TRY(hipMemcpy(jd.data(), c->Jd.p, jd.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int i = 0; i < np; ++i)
+            for (int e = 0; e < 3; ++e)
+                for (int l = 0; l < NBETA; ++l) b[(size_t)(NPF + l) * ldb + 3 * (nr + i) + e] = jd[(size_t)(3 * t.pseudo_joint[i] + e) * NBETA + l];
+    }
+    SkinSet& ss = ks.ss;
+    ss.nv = nu; ss.ldp = ldb;
+    HIP_TRY(ss.posedirs.upload(b.data(), b.size()));
+    HIP_TRY(ks.Bt.upload(bt.data(), bt.size()));
+    if (nu > 0) {
+        const float* pd = ss.posedirs.p;
+        const size_t pdn = b.size();
+        int nt = 0, ns = 0, e = panel_pack_dev(pd, pdn, ldb, 1, NPFX, 3 * nu, ss.pn_fwd_f, &nt, &ns);
+        if (e) return e;
+        ss.pn_fwd.f = (const float4*)ss.pn_fwd_f.p; ss.pn_fwd.ntile = nt; ss.pn_fwd.nss = ns;
+        e = panel_pack_dev(pd, pdn, 1, ldb, 3 * nu, NPFX, ss.pn_bwd_f, &nt, &ns);
+        if (e) return e;
+        ss.pn_bwd.f = (const float4*)ss.pn_bwd_f.p; ss.pn_bwd.ntile = nt; ss.pn_bwd.nss = ns;
+        e = pnf_pack_dev(pd, pdn, ldb, 1, NPFX, 3 * nu, ss.pn_fwd3_f, ss.pn_fwd3_s, &ss.pn_fwd3.ntile, &ss.pn_fwd3.nst);
+        if (e) return e;
+        ss.pn_fwd3.f = (const uint4*)ss.pn_fwd3_f.p; ss.pn_fwd3.isc = ss.pn_fwd3_s.p;
+        e = pnf_pack_dev(pd, pdn, 1, ldb, 3 * nu, NPFX, ss.pn_bwd3_f, ss.pn_bwd3_s, &ss.pn_bwd3.ntile, &ss.pn_bwd3.nst);
+        if (e) return e;
+        ss.pn_bwd3.f = (const uint4*)ss.pn_bwd3_f.p; ss.pn_bwd3.isc = ss.pn_bwd3_s.p;
+        HIP_TRY(hipDeviceSynchronize());
+    }
+    HIP_TRY(ks.kjoint.upload(t.kjoint.data(), t.kjoint.size())); HIP_TRY(ks.kref.upload(t.kref.data(), t.kref.size()));
+    HIP_TRY(ks.kbary.upload(t.kbary.data(), t.kbary.size()));
+    HIP_TRY(ks.vl_start.upload(t.vl_start.data(), t.vl_start.size())); HIP_TRY(ks.vl_k.upload(t.vl_k.data(), t.vl_k.size()));
+    HIP_TRY(ks.vl_w.upload(t.vl_w.data(), t.vl_w.size()));
+    HIP_TRY(ks.jl_start.upload(t.jl_start.data(), t.jl_start.size())); HIP_TRY(ks.jl_k.upload(t.jl_k.data(), t.jl_k.size()));
+    HIP_TRY(ks.pjoint.upload(t.pseudo_joint.data(), t.pseudo_joint.size()));
+    HIP_TRY(ks.wj.upload(wj.data(), wj.size())); HIP_TRY(ks.ww.upload(ww.data(), ww.size())); HIP_TRY(ks.vt.upload(vt.data(), vt.size()));
+    HIP_TRY(ks.csc_start.upload(csc_start.data(), csc_start.size())); HIP_TRY(ks.csc_u.upload(csc_u.data(), csc_u.size()));
+    HIP_TRY(ks.csc_w.upload(csc_w.data(), csc_w.size()));
+    ks.K = K;
+    ks.h = std::move(t);                               // (last: a failure above leaves no map)
+    return FDCAP_OK;
+}
+
+int fdcap_opt_set_keypoints_mapped(fdcap_ctx* c, const float* kp_d, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
+    if (!c || !c->opt || !kp_d) return FDCAP_E_ARG;
+    if (c->kpset.h.n_kp <= 0) return FDCAP_E_STATE;
+    OptState* o = c->opt;
+    const size_t n = (size_t)o->cfg.n_local * c->kpset.h.n_kp * 3;
+    HIP_TRY(o->kp2d.ensure(n));
+    HIP_TRY(hipMemcpyAsync(o->kp2d.p, kp_d, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    o->kp_mapped = true;
+    o->kp_panel = kp_blend_by_panels(o->cfg.n_local, 3 * c->kpset.h.nr);
+    if (o->kp_panel) {
+        const size_t nv = (size_t)o->cfg.n_local * 3 * c->kpset.h.nu();
+        HIP_TRY(o->kpV.ensure(nv));
+        HIP_TRY(o->kpdV.ensure(nv));
+    }
+    return FDCAP_OK;
+}
+
+int fdcap_debug_keypoints3d(fdcap_ctx* c, float* out_d, void* stream) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;
+    if (!c || !c->opt || !out_d) return FDCAP_E_ARG;
+    if (c->kpset.h.n_kp <= 0) return FDCAP_E_STATE;
+    hipStream_t st = (hipStream_t)stream;
+    { int es_ = opt_sync(c, st); if (es_) return es_; }
+    OptState* o = c->opt;
+    int row_lo, row_hi;
+    opt_row_range(o, 1, &row_lo, &row_hi);
+    int e = opt_pose_forward(c, row_lo, row_hi, st);
+    if (e) return e;
+    hipLaunchKernelGGL((fit2d_kp_kernel<true, false>), dim3(o->cfg.n_local), dim3(KP_NT), 0, st, Fit2dStage(), c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p,
+                       o->scale.p, o->Jw.p, (const float*)nullptr, 2, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, (float*)nullptr, (float*)nullptr, (double*)nullptr, (float*)nullptr, out_d, (const float*)nullptr,
+                       (float*)nullptr);
+    return (int)hipGetLastError();
 }
 
 static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses, float* floss, hipStream_t st, bool fold = true);
@@ -290,6 +418,29 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
     opt_row_range(o, 1, &row_lo, &row_hi);
     int e = opt_pose_forward(c, row_lo, row_hi, st);
     if (e) return e;
+    if (o->kp_mapped) {
+        // the mapped data term: one launch in the loss kernel's place; a map with surface points or finger joints hands the pose
+        // backward its vertex branch's sums as mode 'local''s full-mesh pass does (dA, dPF with betas, dtransl_v, dMv, dsv)
+        // (kp_panel: the set's two blend products as panel products around it, kp_blend_by_panels)
+        const bool vb = c->kpset.h.nu() > 0;
+        if (o->kp_panel) {
+            HIP_TRY(blend_forward(c->kpset.ss, o->PF.p + 2 * NPFX, nl, o->kpV.p, st));
+            hipLaunchKernelGGL((fit2d_kp_kernel<false, true>), dim3(nl), dim3(KP_NT), 0, st, s, c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p, o->scale.p,
+                               o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, losses, floss,
+                               (float*)nullptr, o->kpV.p, o->kpdV.p);
+            HIP_TRY(blend_backward(c->kpset.ss, o->kpdV.p, nl, o->dPF.p + 2 * NPFX, 0, c->ws_kpart, st));
+        } else
+            hipLaunchKernelGGL((fit2d_kp_kernel<false, false>), dim3(nl), dim3(KP_NT), 0, st, s, c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p, o->scale.p,
+                               o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, losses, floss,
+                               (float*)nullptr, (const float*)nullptr, (float*)nullptr);
+        hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
+                           o->Jrest.p, o->G.p, vb ? o->dA.p : (const float*)nullptr, vb ? o->dPF.p : (const float*)nullptr, o->dJw.p,
+                           vb ? o->dMv.p : (const float*)nullptr, vb ? o->dsv.p : (const float*)nullptr,
+                           vb ? o->dPF.p + NPF : (const float*)nullptr, vb ? NPFX : 0, vb ? o->dtransl_v.p : (const float*)nullptr, o->dX.p, o->dO.p,
+                           o->dCAM.p, o->dscale_row.p, ParamLossIn(), (const float*)nullptr);
+        { int eb = opt_vposer_backward(c, fold, st); if (eb) return eb; }
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(fit2d_loss_kernel, dim3(nl), dim3(128), 0, st, s, o->X.p, o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, losses, floss);
     hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
                        o->Jrest.p, o->G.p, (const float*)nullptr, (const float*)nullptr, o->dJw.p, (const float*)nullptr,

@@ -58,6 +58,7 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->cam_steps = 0;
     o->dz_pending = false;
     o->log_pending = false;
+    o->kp_mapped = false;
     o->seeded = false;
     o->nnpt_valid = false;
     o->n_recompute = 0;

@@ -78,6 +78,16 @@ struct SkinSet {          // skinning constants for a vertex set (all V, or the 
     }
 };
 
+// The keypoint map of the inner fit (fdcap_set_keypoint_map, fdc_keypoints.h): the host tables and the keypoint set's constants
+struct KeypointSet {
+    KeypointTables h;
+    int K = 1;
+    DevBuf<int32_t> kjoint, kref, vl_start, vl_k, jl_start, jl_k, pjoint, wj, csc_start, csc_u;
+    DevBuf<float> kbary, vl_w, vt, ww, csc_w, Bt;
+    SkinSet ss;               // the set's blend matrix (posedirs, ldp) and its panels: what blend_forward / blend_backward take; nothing else of it is filled
+    void release() { *this = KeypointSet(); }
+};
+
 // One registered scene: the full table set fdcap_set_scene builds (fdc_scene.h)
 struct SceneSet {
     DevBuf<float4> scene;          // original order {x,y,z,bits(i)}: gradient gather by index
@@ -159,7 +169,10 @@ struct OptState {
     PoseJoints pj_fwd, pj_bwd;         // the joint sets of the last pose_fwd_kernel / pose_bwd_kernel launch (fdcap_debug_pose_joint_sets)
     DevBuf<float> Voff, Vw, dist, pd, dVoff;
     DevBuf<int> idx, pi;
-    DevBuf<float> kp2d;       // per-frame inner fit: 2D keypoints [n_local,23,3] (u, v, confidence)
+    DevBuf<float> kp2d;       // per-frame inner fit: 2D keypoints [n_local,23,3] (u, v, confidence), or [n_local,n_kp,3] in map order
+    bool kp_mapped = false;   // ... the latter (fdcap_opt_set_keypoints_mapped): the data term runs over the context's keypoint map
+    bool kp_panel = false;    // ... with the set's blend products as panel products around the kernel (kp_blend_by_panels)
+    DevBuf<float> kpV, kpdV;  // ... their output and input: the set's offsets / offset gradients [n_local, 3 nu]
     DevBuf<float> floss;      // ... and the per-frame objective of its L-BFGS variant
     fdcap_lbfgs* lbfgs = nullptr;
     DevBuf<float4> seedpt;    // coordinates (+ position in the sorted scene) of each query's current neighbour: next launch's seed
@@ -281,6 +294,12 @@ struct fdcap_ctx {
     VPoserPanels3 vp3;
     SkinSet full, contact;
     bool full_ready = false;
+    KeypointSet kpset;             // fdcap_set_keypoint_map (h.n_kp = 0: no map)
+    KpSet kp_view() const {
+        const KeypointSet& k = kpset;
+        return KpSet{k.h.n_kp, k.h.nr, k.h.np, k.K, k.ss.ldp, k.kjoint.p, k.kref.p, k.kbary.p, k.vl_start.p, k.vl_k.p, k.vl_w.p, k.jl_start.p, k.jl_k.p,
+                     k.vt.p, k.pjoint.p, k.wj.p, k.ww.p, k.csc_start.p, k.csc_u.p, k.csc_w.p, k.ss.posedirs.p, k.Bt.p, Jt.p, Jd.p};
+    }
     // The registered scenes: slot 0 is THE scene of every one-scene entry point (fdcap_set_scene, the scene operator, the
     // diagnostics); the other slots only serve a batch whose clips name them (fdcap_opt_create_clips_scenes).
     SceneSet scenes[FDCAP_MAX_SCENES];

@@ -25,12 +25,74 @@ DEFAULT_LBFGS = dict(history=100, max_iter=30, max_eval=0, max_steps=30, max_ls=
                      tolerance_change=1e-9, ftol=2e-9, gtol=1e-9)
 
 
+# OpenPose's keypoint orders as indices into smplx's 127-joint output (55 joints, 21 vertex joints, 51 + 17 face landmarks).
+# [upstream-recall: SMPLify-X's smpl_to_openpose(model_type="smplx", use_hands=True, openpose_format="coco25"); neither smplx nor
+# SMPLify-X is part of this repository, so a caller who has them passes the lists they give instead]
+OPENPOSE_BODY25 = (55, 12, 17, 19, 21, 16, 18, 20, 0, 2, 5, 8, 1, 4, 7, 56, 57, 58, 59, 60, 61, 62, 63, 64, 65)
+OPENPOSE_LHAND = (20, 37, 38, 39, 66, 25, 26, 27, 67, 28, 29, 30, 68, 34, 35, 36, 69, 31, 32, 33, 70)
+OPENPOSE_RHAND = (21, 52, 53, 54, 71, 40, 41, 42, 72, 43, 44, 45, 73, 49, 50, 51, 74, 46, 47, 48, 75)
+NUM_SMPLX_JOINTS, NUM_EXTRA_VERTEX_JOINTS = 55, 21
+
+
+class KeypointMap:
+    """Which body point each detected keypoint is (include/fdcap.h fdcap_set_keypoint_map): joint[k] >= 0 an SMPL-X joint, else the
+    surface point bary[k] . vertices[tri[k]] (a plain vertex: (v, v, v), (1, 0, 0))."""
+
+    def __init__(self, joint, tri, bary):
+        self.joint = np.ascontiguousarray(joint, dtype=np.int32).reshape(-1)
+        self.tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1, 3)
+        self.bary = np.ascontiguousarray(bary, dtype=np.float32).reshape(-1, 3)
+        n = self.joint.shape[0]
+        if self.tri.shape[0] != n or self.bary.shape[0] != n:
+            raise capi.FdcapError("joint [n], tri [n,3] and bary [n,3] must describe the same keypoints")
+        if n > capi.MAX_KEYPOINTS:
+            raise capi.FdcapError(f"{n} keypoints: a map holds at most {capi.MAX_KEYPOINTS}")
+
+    def __len__(self):
+        return int(self.joint.shape[0])
+
+    @classmethod
+    def joints23(cls):
+        """SMPL-X joints 0..22 in order: the layout fitting() takes without a map."""
+        return cls(np.arange(23), np.zeros((23, 3)), np.zeros((23, 3)))
+
+    @classmethod
+    def from_smplx_indices(cls, indices, extra_vertex_ids, lmk_vertex_triples=None, lmk_bary=None):
+        """indices in smplx's 127-joint output convention: < 55 a joint; 55..75 the caller's 21 `extra_vertex_ids` in smplx's order
+        (nose, eyes, ears, big toe / small toe / heel left then right, the ten fingertips: smplx.vertex_ids, never hard-coded here);
+        >= 76 landmark i - 76 = lmk_bary[i - 76] . vertices[lmk_vertex_triples[i - 76]] (the model file's lmk_faces_idx resolved
+        through its faces, and lmk_bary_coords)."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        n = idx.shape[0]
+        joint, tri, bary = np.full(n, -1, np.int32), np.zeros((n, 3), np.int32), np.zeros((n, 3), np.float32)
+        extra = np.asarray(extra_vertex_ids, dtype=np.int64).reshape(-1)
+        first_lmk = NUM_SMPLX_JOINTS + NUM_EXTRA_VERTEX_JOINTS
+        for k, i in enumerate(idx):
+            if i < 0:
+                raise capi.FdcapError(f"keypoint {k}: index {i}")
+            if i < NUM_SMPLX_JOINTS:
+                joint[k] = i
+            elif i < first_lmk:
+                if extra.shape[0] != NUM_EXTRA_VERTEX_JOINTS:
+                    raise capi.FdcapError(f"extra_vertex_ids must hold smplx's {NUM_EXTRA_VERTEX_JOINTS} vertex joints")
+                tri[k], bary[k] = extra[i - NUM_SMPLX_JOINTS], (1.0, 0.0, 0.0)
+            else:
+                if lmk_vertex_triples is None or lmk_bary is None or i - first_lmk >= len(lmk_vertex_triples):
+                    raise capi.FdcapError(f"keypoint {k}: landmark {i - first_lmk} without lmk_vertex_triples / lmk_bary")
+                tri[k], bary[k] = lmk_vertex_triples[i - first_lmk], lmk_bary[i - first_lmk]
+        return cls(joint, tri, bary)
+
+
 class InnerFitOP:
     def __init__(self, body_model, vposer, num_frames, intrinsics=DEFAULT_INTRINSICS, rho=100.0, lr=0.01,
-                 stages=DEFAULT_STAGES, iters_per_stage=30, optimizer="adam", lbfgs=None, max_rounds=4000):
+                 stages=DEFAULT_STAGES, iters_per_stage=30, optimizer="adam", lbfgs=None, max_rounds=4000,
+                 keypoint_map=None, group_of=None, group_weights=None):
         """optimizer "adam": iters_per_stage steps of Adam(lr) per stage; "lbfgs": per frame and stage, SMPLify-X's L-BFGS loop
         with the settings `lbfgs` (keys of DEFAULT_LBFGS; missing ones take their defaults), at most max_rounds objective
-        evaluations per stage."""
+        evaluations per stage.
+        keypoint_map (KeypointMap): fitting() then takes keypoints [N, len(map), 3] in the map's order.  group_of [len(map)] names
+        each keypoint's group (0 without it) and group_weights[stage][group] multiplies the group's confidences before that stage's
+        upload -- SMPLify-X's per-stage hand and face data weights; default all 1."""
         import torch
         if not torch.cuda.is_available():
             raise capi.FdcapError("no HIP device: the fdcap_amd inner fit only runs on the GPU")
@@ -46,17 +108,32 @@ class InnerFitOP:
         if unknown:
             raise capi.FdcapError(f"unknown L-BFGS settings {sorted(unknown)}")
         self.optimizer, self.lbfgs, self.max_rounds = optimizer, {**DEFAULT_LBFGS, **(lbfgs or {})}, int(max_rounds)
+        self.keypoint_map, self.group_of, self.group_weights = keypoint_map, None, None
+        if keypoint_map is None:
+            if group_of is not None or group_weights is not None:
+                raise capi.FdcapError("group_of / group_weights belong to a keypoint_map")
+        else:
+            self.group_of = np.zeros(len(keypoint_map), np.int64) if group_of is None else np.asarray(group_of, dtype=np.int64).reshape(-1)
+            if self.group_of.shape[0] != len(keypoint_map) or (len(keypoint_map) and self.group_of.min() < 0):
+                raise capi.FdcapError("group_of must name a group >= 0 for every keypoint of the map")
+            if group_weights is not None:
+                gw = np.asarray(group_weights, dtype=np.float32)
+                if gw.ndim != 2 or gw.shape[0] != len(self.stages) or gw.shape[1] <= int(self.group_of.max(initial=0)):
+                    raise capi.FdcapError("group_weights must be [stages][groups]")
+                self.group_weights = gw
+            self.ctx.set_keypoint_map(keypoint_map.joint, keypoint_map.tri, keypoint_map.bary)
         self.log, self.rounds, self.frame_iterations, self.frame_loss = [], [], [], []
 
     def fitting(self, rows75, keypoints, log_every=0):
-        """rows75 [N,75] initial parameters (device tensor or numpy), keypoints [N,23,3] (u, v, confidence)
-        -> optimised rows [N,75] (device tensor)."""
+        """rows75 [N,75] initial parameters (device tensor or numpy), keypoints [N,23,3] (u, v, confidence) -- with a keypoint_map
+        [N,len(map),3] in its order -- -> optimised rows [N,75] (device tensor)."""
         import torch
         lib, h, dev, n = self.ctx.lib, self.ctx.handle, self.device, self.n
         t = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))).to(dev, torch.float32).contiguous()
         rows75, kp = t(rows75), t(keypoints)
-        if tuple(rows75.shape) != (n, capi.PDIM) or tuple(kp.shape) != (n, 23, 3):
-            raise capi.FdcapError(f"expected rows [{n},75] and keypoints [{n},23,3]")
+        nkp = 23 if self.keypoint_map is None else len(self.keypoint_map)
+        if tuple(rows75.shape) != (n, capi.PDIM) or tuple(kp.shape) != (n, nkp, 3):
+            raise capi.FdcapError(f"expected rows [{n},75] and keypoints [{n},{nkp},3]")
         st = capi.current_stream()
         x78 = torch.empty(n, capi.XDIM, device=dev)
         capi.check(lib.fdcap_params_75_to_78(capi.dptr(rows75), n, capi.dptr(x78), st), "fdcap_params_75_to_78")
@@ -75,10 +152,17 @@ class InnerFitOP:
         self._rows_cam[:] = torch.eye(4, device=dev).reshape(1, 16)          # halo rows too (their forward is evaluated, never used)
         capi.check(lib.fdcap_opt_set_inputs(h, capi.dptr(x78), capi.dptr(x78), capi.dptr(torch.ones(n, device=dev)), capi.dptr(eye), st),
                    "fdcap_opt_set_inputs")
-        capi.check(lib.fdcap_opt_set_keypoints(h, capi.dptr(kp), st), "fdcap_opt_set_keypoints")
+        if self.keypoint_map is None:
+            capi.check(lib.fdcap_opt_set_keypoints(h, capi.dptr(kp), st), "fdcap_opt_set_keypoints")
+        else:
+            capi.check(lib.fdcap_opt_set_keypoints_mapped(h, capi.dptr(kp), st), "fdcap_opt_set_keypoints_mapped")
         self.log, self.rounds, self.frame_iterations, self.frame_loss = [], [], [], []
         fx, fy, cx, cy = self.intrinsics
-        for w_data, w_pose, w_shape, w_hand in self.stages:
+        for si, (w_data, w_pose, w_shape, w_hand) in enumerate(self.stages):
+            if self.group_weights is not None:                 # this stage's confidences: the detector's times the groups' weights
+                kps = kp.clone()
+                kps[:, :, 2] *= torch.from_numpy(self.group_weights[si][self.group_of]).to(dev)
+                capi.check(lib.fdcap_opt_set_keypoints_mapped(h, capi.dptr(kps), capi.current_stream()), "fdcap_opt_set_keypoints_mapped")
             sg = capi.Fit2dStage(fx, fy, cx, cy, self.rho, w_data, w_pose, w_shape, w_hand)
             if self.optimizer == "lbfgs":
                 q = self.lbfgs

@@ -246,3 +246,22 @@ def colmap_points_to_xyz(points3d_txt: str, out_path: str | None = None) -> np.n
             for it in rows:
                 f.write(" " + " ".join(it[1:7]) + "\n")
     return np.array([[float(it[1]), float(it[2]), float(it[3])] for it in rows], dtype=np.float32).reshape(-1, 3)
+
+
+OPENPOSE_PARTS = (("pose_keypoints_2d", 25), ("hand_left_keypoints_2d", 21), ("hand_right_keypoints_2d", 21), ("face_keypoints_2d", 70))
+
+
+def read_openpose_json(path: str, hands: bool = True, face: bool = False) -> np.ndarray:
+    """One frame of OpenPose's JSON output -> [n_kp,3] (u, v, confidence) in BODY_25 | left hand | right hand (| face) order:
+    25 (+ 42) (+ 70) rows.  Reads people[0], the person utils/openpose_filter.py:13-17 keeps; an empty `people`, or a part the file
+    does not hold, gives zeros -- confidence 0, no data term."""
+    with open(path) as f:
+        d = json.load(f)
+    people = d.get("people") or []
+    person = people[0] if people else {}
+    parts = [OPENPOSE_PARTS[0]] + (list(OPENPOSE_PARTS[1:3]) if hands else []) + ([OPENPOSE_PARTS[3]] if face else [])
+    out = []
+    for key, n in parts:
+        a = np.asarray(person.get(key) or [], dtype=np.float32).reshape(-1)
+        out.append(a.reshape(n, 3) if a.size == 3 * n else np.zeros((n, 3), np.float32))
+    return np.concatenate(out, axis=0)

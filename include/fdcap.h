@@ -490,6 +490,21 @@ typedef struct fdcap_fit2d_stage {
 } fdcap_fit2d_stage;
 /* kp_d DEVICE [n_local,23,3]: (u, v, confidence) of SMPL-X joints 0..22 (the joints[:, 0:23] the reference reads, :298). */
 int fdcap_opt_set_keypoints(fdcap_ctx* ctx, const float* kp_d, void* stream);
+/* ... on a detector's keypoints (csrc/fdc_keypoints.h): a map, static per context, from keypoint k to an SMPL-X joint or a point of
+ * the mesh surface.  Every kind's position is "SMPL-X output + transl + camera_translation" under the inner fit's set-up above
+ * (camera_ext rows = identity, scale = 1); joints 0..22 are the 23-joint path's own world joints, so a map of exactly those in
+ * order gives that path's bits. */
+#define FDCAP_MAX_KEYPOINTS 160
+/* joint[k] >= 0: SMPL-X joint; joint[k] < 0: surface point tri[k][0..2] (vertex ids), bary[k][0..2].  HOST arrays.
+ * n_kp = 0 clears the map.  FDCAP_E_ARG: n_kp < 0 or > FDCAP_MAX_KEYPOINTS, joint >= 55, a vertex id outside [0, V),
+ * a non-finite weight.  FDCAP_E_STATE: a live optimiser (as scene registration). */
+int fdcap_set_keypoint_map(fdcap_ctx* ctx, int32_t n_kp, const int32_t* joint, const int32_t* tri, const float* bary);
+/* kp_d DEVICE [n_local, n_kp, 3] (u, v, confidence) in map order.  From here on fdcap_opt_backward_fit2d,
+ * fdcap_opt_fit2d_lbfgs and its stats use the mapped data term; fdcap_opt_set_keypoints switches back.
+ * FDCAP_E_STATE without a map or for a batch of clips (as fdcap_opt_set_keypoints). */
+int fdcap_opt_set_keypoints_mapped(fdcap_ctx* ctx, const float* kp_d, void* stream);
+/* the mapped keypoints' camera-frame 3D positions of the current rows, out_d DEVICE [n_local, n_kp, 3] (diagnostic; runs the forward) */
+int fdcap_debug_keypoints3d(fdcap_ctx* ctx, float* out_d, void* stream);
 /* zero_grad + loss + backward; only body_rotation_rec gets a gradient.  log_terms != 0: losses_d [0] = data term,
  * [1] = priors (both already weighted, summed over this rank's frames).  (The latent columns' gradient is left in the VPoser
  * backward's four partial arrays; fdcap_opt_step_x and fdcap_opt_get_grads add them -- one launch less per iteration.) */
