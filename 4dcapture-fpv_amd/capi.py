@@ -40,6 +40,12 @@ class Fit2dStage(ctypes.Structure):
                 ("w_data", c_float), ("w_pose", c_float), ("w_shape", c_float), ("w_hand", c_float)]
 
 
+class Fit2dExtra(ctypes.Structure):
+    """include/fdcap.h fdcap_fit2d_extra: the jaw prior's weights, the bending prior's weight and terms."""
+    _fields_ = [("w_jaw", c_float * 3), ("w_bend", c_float), ("n_bend", c_int32), ("joint", c_int32 * 8), ("axis", c_int32 * 8),
+                ("sign", c_float * 8)]
+
+
 class LbfgsConfig(ctypes.Structure):
     """include/fdcap.h fdcap_lbfgs_config: torch.optim.LBFGS's arguments + SMPLify-X's loop around optimizer.step()."""
     _fields_ = [("dim", c_int32), ("history", c_int32), ("max_iter", c_int32), ("max_eval", c_int32), ("max_steps", c_int32),
@@ -135,6 +141,9 @@ SYMBOLS = {
     "fdcap_opt_set_keypoints_mapped": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_debug_keypoints3d": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_backward_fit2d": (c_int32, [c_void_p, POINTER(Fit2dStage), c_int32, c_void_p]),
+    "fdcap_opt_set_fit2d_extra": (c_int32, [c_void_p, POINTER(Fit2dExtra)]),
+    "fdcap_opt_set_jaw": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_get_jaw": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_reset_adam": (c_int32, [c_void_p, c_void_p]),
     "fdcap_lbfgs_create": (c_int32, [c_int32, POINTER(LbfgsConfig), POINTER(c_void_p)]),
     "fdcap_lbfgs_destroy": (None, [c_void_p]),
@@ -143,6 +152,7 @@ SYMBOLS = {
     "fdcap_lbfgs_get_stats": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_lbfgs_finalize": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "fdcap_opt_fit2d_lbfgs": (c_int32, [c_void_p, POINTER(Fit2dStage), POINTER(LbfgsConfig), c_int32, POINTER(c_int32), c_void_p]),
+    "fdcap_opt_fit2d_lbfgs_rolled_back": (c_int32, [c_void_p, POINTER(c_int32)]),
     "fdcap_opt_fit2d_lbfgs_stats": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_step_rows_and_pack": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "fdcap_opt_unpack_and_step_scale": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),

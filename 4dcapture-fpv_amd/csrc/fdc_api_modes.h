@@ -312,6 +312,12 @@ int fdcap_debug_keypoints3d(fdcap_ctx* c, float* out_d, void* stream) {
     opt_row_range(o, 1, &row_lo, &row_hi);
     int e = opt_pose_forward(c, row_lo, row_hi, st);
     if (e) return e;
+    if (o->jaw_on)
+        hipLaunchKernelGGL((fit2d_kp_jaw_kernel<true, false>), dim3(o->cfg.n_local), dim3(KP_NT), 0, st, Fit2dStage(), c->kp_view(), o->X.p, o->PF.p, o->A.p,
+                           o->M.p, o->scale.p, o->Jw.p, (const float*)nullptr, 2, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                           (float*)nullptr, (float*)nullptr, (float*)nullptr, (double*)nullptr, (float*)nullptr, out_d, (const float*)nullptr,
+                           (float*)nullptr, JawIO{o->jaw.p, o->jawR9.p, {0.f, 0.f, 0.f}});
+    else
     hipLaunchKernelGGL((fit2d_kp_kernel<true, false>), dim3(o->cfg.n_local), dim3(KP_NT), 0, st, Fit2dStage(), c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p,
                        o->scale.p, o->Jw.p, (const float*)nullptr, 2, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
                        (float*)nullptr, (float*)nullptr, (float*)nullptr, (double*)nullptr, (float*)nullptr, out_d, (const float*)nullptr,
@@ -331,6 +337,60 @@ int fdcap_opt_backward_fit2d(fdcap_ctx* c, const fdcap_fit2d_stage* sg, int32_t 
     if (losses) HIP_TRY(hipMemsetAsync(losses, 0, FDCAP_NUM_LOSSES * sizeof(double), st));
     // (the latent gradient stays in the VPoser backward's four partials: fdcap_opt_step_x / fdcap_opt_get_grads add them)
     return fit2d_eval(c, sg, losses, nullptr, st, false);
+}
+
+static_assert(FIT2D_MAX_BEND == FDCAP_MAX_BEND_TERMS, "fdc_fit2d.h restates the longest list of bending terms");
+int fdcap_opt_set_fit2d_extra(fdcap_ctx* c, const fdcap_fit2d_extra* ex) {
+    if (!c || !c->opt || opt_is_batch(c) || !opt_whole_clips(c->opt)) return FDCAP_E_STATE;
+    Fit2dBend b = {};
+    if (ex) {
+        if (fit2d_bend_check(ex->w_bend, ex->n_bend, ex->joint, ex->axis, ex->sign)) return FDCAP_E_ARG;
+        for (int e = 0; e < 3; ++e) if (!std::isfinite(ex->w_jaw[e])) return FDCAP_E_ARG;
+        b.w = ex->w_bend; b.n = ex->w_bend != 0.f ? ex->n_bend : 0;      // (weight 0: every term and gradient an exact zero -- no launch)
+        for (int t = 0; t < b.n; ++t) { b.joint[t] = ex->joint[t]; b.axis[t] = ex->axis[t]; b.sign[t] = ex->sign[t]; }
+    }
+    for (int e = 0; e < 3; ++e) c->opt->w_jaw[e] = ex ? ex->w_jaw[e] : 0.f;
+    c->opt->bend = b;
+    return FDCAP_OK;
+}
+
+// ---- the free jaw (csrc/fdc_keypoints.h) -----------------------------------------------------------------------------------------
+static JawGradIn opt_jaw_grad_in(fdcap_ctx* c) {
+    OptState* o = c->opt;
+    JawGradIn jg;
+    jg.jaw = o->jaw.p; jg.R9 = o->jawR9.p;
+    jg.gP = o->jaw_gp ? o->dPF.p + (size_t)2 * NPFX + 9 * (JAW_J - 1) : nullptr; jg.gp_stride = NPFX;
+    for (int e = 0; e < 3; ++e) jg.w[e] = o->w_jaw[e];
+    return jg;
+}
+int fdcap_opt_set_jaw(fdcap_ctx* c, const float* jaw_d, void* stream) {
+    if (!c || !c->opt || opt_is_batch(c) || !opt_whole_clips(c->opt)) return FDCAP_E_STATE;
+    OptState* o = c->opt;
+    hipStream_t st = (hipStream_t)stream;
+    o->jaw_eval = false;
+    if (!jaw_d) { o->jaw_on = false; return FDCAP_OK; }
+    for (int j = 0; j < NJ; ++j) if (c->h_parents[j] == JAW_J) return FDCAP_E_ARG;      // (the leaf argument needs a leaf)
+    const size_t n = (size_t)o->cfg.n_local;
+    HIP_TRY(o->jaw.ensure(3 * n)); HIP_TRY(o->mJaw.ensure(3 * n)); HIP_TRY(o->vJaw.ensure(3 * n)); HIP_TRY(o->jawR9.ensure(9 * n));
+    HIP_TRY(hipMemcpyAsync(o->jaw.p, jaw_d, 3 * n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(o->mJaw.p, 0, 3 * n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o->vJaw.p, 0, 3 * n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o->jawR9.p, 0, 9 * n * sizeof(float), st));
+    o->jaw_on = true;
+    return FDCAP_OK;
+}
+int fdcap_opt_get_jaw(fdcap_ctx* c, float* jaw_d, float* djaw_d, void* stream) {
+    if (!c || !c->opt || !c->opt->jaw_on) return FDCAP_E_STATE;
+    if (!jaw_d && !djaw_d) return FDCAP_E_ARG;
+    OptState* o = c->opt;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = o->cfg.n_local;
+    if (djaw_d && !o->jaw_eval) return FDCAP_E_STATE;        // (no evaluation since fdcap_opt_set_jaw: no gradient)
+    if (jaw_d) HIP_TRY(hipMemcpyAsync(jaw_d, o->jaw.p, (size_t)3 * n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (djaw_d)
+        hipLaunchKernelGGL(jaw_grad_kernel, dim3((n + 63) / 64), dim3(64), 0, st, opt_jaw_grad_in(c), n, djaw_d, (float*)nullptr, (float*)nullptr,
+                           AdamScalars());
+    return (int)hipGetLastError();
 }
 
 // ---- batched L-BFGS (csrc/fdc_lbfgs.h) ------------------------------------------------------------------------------
@@ -353,6 +413,8 @@ int fdcap_lbfgs_create(int32_t n, const fdcap_lbfgs_config* cf, fdcap_lbfgs** ou
     if (e == hipSuccess) e = L->active_h.alloc();
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)lbfgs_advance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lbfgs_lds_bytes(LB_HMAX));
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)lbfgs_advance_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lbfgs_lds_bytes(LB_HMAX));
     if (e == hipSuccess) { int r = fdcap_lbfgs_reset(L, nullptr); if (r == 0) e = hipDeviceSynchronize(); else e = (hipError_t)r; }
     if (e != hipSuccess) { fdcap_lbfgs_destroy(L); return (int)e; }
     *out = L;
@@ -370,28 +432,38 @@ int fdcap_lbfgs_reset(fdcap_lbfgs* L, void* stream) {
     return FDCAP_OK;
 }
 static int lbfgs_advance_impl(fdcap_lbfgs* L, float* x, int32_t x_stride, const float* f, const float* g, int32_t g_stride, int32_t* n_active,
-                              LbfgsFold fold, void* stream);
+                              LbfgsFold fold, void* stream, JawGradIn tail = JawGradIn());
 int fdcap_lbfgs_advance(fdcap_lbfgs* L, float* x, int32_t x_stride, const float* f, const float* g, int32_t g_stride, int32_t* n_active,
                         void* stream) {
     return lbfgs_advance_impl(L, x, x_stride, f, g, g_stride, n_active, LbfgsFold(), stream);
 }
 static int lbfgs_advance_impl(fdcap_lbfgs* L, float* x, int32_t x_stride, const float* f, const float* g, int32_t g_stride, int32_t* n_active,
-                              LbfgsFold fold, void* stream) {
-    if (!L || !x || !f || !g || x_stride < L->cf.dim || g_stride < L->cf.dim) return FDCAP_E_ARG;
+                              LbfgsFold fold, void* stream, JawGradIn tail) {
+    const int in_row = L ? L->cf.dim - (tail.jaw ? 3 : 0) : 0;          // (the tail's three columns live in its own array)
+    if (!L || !x || !f || !g || in_row <= 0 || x_stride < in_row || g_stride < in_row || (tail.jaw && in_row < 64)) return FDCAP_E_ARG;   // (the tail form keeps its three columns in a lane's second element)
     hipStream_t st = (hipStream_t)stream;
     int* const cnt = L->active.p + (L->round & 1);            // this round's counter was zeroed by the previous round's launch
+    if (tail.jaw)
+        hipLaunchKernelGGL(lbfgs_advance_tail_kernel, dim3(L->n), dim3(LB_NT), lbfgs_lds_bytes(L->cf.hist), st, L->cf, L->S.p, L->W.p, L->RO.p, x, x_stride,
+                           f, g, g_stride, cnt, L->active.p + ((L->round + 1) & 1), fold, tail);
+    else
     hipLaunchKernelGGL(lbfgs_advance_kernel, dim3(L->n), dim3(LB_NT), lbfgs_lds_bytes(L->cf.hist), st, L->cf, L->S.p, L->W.p, L->RO.p, x, x_stride,
                        f, g, g_stride, cnt, L->active.p + ((L->round + 1) & 1), fold);
     L->round++;
     if (n_active) HIP_TRY(hipMemcpyAsync(n_active, cnt, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     return (int)hipGetLastError();
 }
-int fdcap_lbfgs_finalize(fdcap_lbfgs* L, float* x, int32_t x_stride, int32_t* n_unfinished, void* stream) {
-    if (!L || !x || x_stride < L->cf.dim) return FDCAP_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
+// in_tail: the last columns of the vector that are NOT in the x row (the tail form; lbfgs_finalize_tail_kernel has put them back)
+static int lbfgs_finalize_impl(fdcap_lbfgs* L, float* x, int32_t x_stride, int32_t* n_unfinished, int in_tail, hipStream_t st) {
+    if (!L || !x || x_stride < L->cf.dim - in_tail) return FDCAP_E_ARG;
     if (n_unfinished) HIP_TRY(hipMemsetAsync(n_unfinished, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(lbfgs_finalize_kernel, dim3(L->n), dim3(LB_DPAD), 0, st, L->cf, L->S.p, L->W.p, x, x_stride, n_unfinished);
+    LbfgsCfg cf = L->cf;
+    cf.dim -= in_tail;
+    hipLaunchKernelGGL(lbfgs_finalize_kernel, dim3(L->n), dim3(LB_DPAD), 0, st, cf, L->S.p, L->W.p, x, x_stride, n_unfinished);
     return (int)hipGetLastError();
+}
+int fdcap_lbfgs_finalize(fdcap_lbfgs* L, float* x, int32_t x_stride, int32_t* n_unfinished, void* stream) {
+    return lbfgs_finalize_impl(L, x, x_stride, n_unfinished, 0, (hipStream_t)stream);
 }
 namespace {
 __global__ void lbfgs_stats_kernel(const LbfgsScalars* __restrict__ S, int n, int* __restrict__ it, int* __restrict__ ev, float* __restrict__ loss) {
@@ -414,6 +486,9 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
     const int nl = o->cfg.n_local;
     Fit2dStage s = {sg->fx, sg->fy, sg->cx, sg->cy, sg->rho, sg->w_data, sg->w_pose, sg->w_shape, sg->w_hand};
     PoseModel pm = c->pose_model();
+    if (o->jaw_on && !o->kp_mapped) return FDCAP_E_STATE;     // (no keypoint of the 23-joint layout follows the jaw)
+    const JawIO jw = {o->jaw.p, o->jawR9.p, {o->w_jaw[0], o->w_jaw[1], o->w_jaw[2]}};
+    const bool bend = o->bend.n > 0;                          // (fdcap_opt_set_fit2d_extra; off: not one launch or argument differs)
     int row_lo, row_hi;
     opt_row_range(o, 1, &row_lo, &row_hi);
     int e = opt_pose_forward(c, row_lo, row_hi, st);
@@ -423,18 +498,32 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
         // backward its vertex branch's sums as mode 'local''s full-mesh pass does (dA, dPF with betas, dtransl_v, dMv, dsv)
         // (kp_panel: the set's two blend products as panel products around it, kp_blend_by_panels)
         const bool vb = c->kpset.h.nu() > 0;
+        if (o->jaw_on) { o->jaw_eval = true; o->jaw_gp = vb; }
         if (o->kp_panel) {
             HIP_TRY(blend_forward(c->kpset.ss, o->PF.p + 2 * NPFX, nl, o->kpV.p, st));
+            if (o->jaw_on)
+                hipLaunchKernelGGL((fit2d_kp_jaw_kernel<false, true>), dim3(nl), dim3(KP_NT), 0, st, s, c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p,
+                                   o->scale.p, o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, losses,
+                                   floss, (float*)nullptr, o->kpV.p, o->kpdV.p, jw);
+            else
             hipLaunchKernelGGL((fit2d_kp_kernel<false, true>), dim3(nl), dim3(KP_NT), 0, st, s, c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p, o->scale.p,
                                o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, losses, floss,
                                (float*)nullptr, o->kpV.p, o->kpdV.p);
             HIP_TRY(blend_backward(c->kpset.ss, o->kpdV.p, nl, o->dPF.p + 2 * NPFX, 0, c->ws_kpart, st));
-        } else
+        } else if (o->jaw_on)
+            hipLaunchKernelGGL((fit2d_kp_jaw_kernel<false, false>), dim3(nl), dim3(KP_NT), 0, st, s, c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p,
+                               o->scale.p, o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, losses,
+                               floss, (float*)nullptr, (const float*)nullptr, (float*)nullptr, jw);
+        else
             hipLaunchKernelGGL((fit2d_kp_kernel<false, false>), dim3(nl), dim3(KP_NT), 0, st, s, c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p, o->scale.p,
                                o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, losses, floss,
                                (float*)nullptr, (const float*)nullptr, (float*)nullptr);
+        // the bending prior: its launch adds to the dPF the vertex branch left (the kernel's or blend_backward's), or -- a map of
+        // joints 0..22 alone -- assigns the row, which pose_bwd_kernel then reads without the branch's other sums
+        if (bend && vb) hipLaunchKernelGGL(fit2d_bend_kernel<true>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
+        else if (bend) hipLaunchKernelGGL(fit2d_bend_kernel<false>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
         hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
-                           o->Jrest.p, o->G.p, vb ? o->dA.p : (const float*)nullptr, vb ? o->dPF.p : (const float*)nullptr, o->dJw.p,
+                           o->Jrest.p, o->G.p, vb ? o->dA.p : (const float*)nullptr, (vb || bend) ? o->dPF.p : (const float*)nullptr, o->dJw.p,
                            vb ? o->dMv.p : (const float*)nullptr, vb ? o->dsv.p : (const float*)nullptr,
                            vb ? o->dPF.p + NPF : (const float*)nullptr, vb ? NPFX : 0, vb ? o->dtransl_v.p : (const float*)nullptr, o->dX.p, o->dO.p,
                            o->dCAM.p, o->dscale_row.p, ParamLossIn(), (const float*)nullptr);
@@ -442,8 +531,9 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
         return (int)hipGetLastError();
     }
     hipLaunchKernelGGL(fit2d_loss_kernel, dim3(nl), dim3(128), 0, st, s, o->X.p, o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, losses, floss);
+    if (bend) hipLaunchKernelGGL(fit2d_bend_kernel<false>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
     hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
-                       o->Jrest.p, o->G.p, (const float*)nullptr, (const float*)nullptr, o->dJw.p, (const float*)nullptr,
+                       o->Jrest.p, o->G.p, (const float*)nullptr, bend ? o->dPF.p : (const float*)nullptr, o->dJw.p, (const float*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, o->dX.p, o->dO.p, o->dCAM.p,
                        o->dscale_row.p, ParamLossIn(), (const float*)nullptr);
     { int eb = opt_vposer_backward(c, fold, st); if (eb) return eb; }
@@ -460,7 +550,7 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap
     hipStream_t st = (hipStream_t)stream;
     const int nl = o->cfg.n_local;
     fdcap_lbfgs_config cf = *cfg;
-    cf.dim = XDIM;
+    cf.dim = o->jaw_on ? XDIM + 3 : XDIM;                     // a free jaw: [the row | the jaw], the last three in the jaw's own array
     if (!lbfgs_cfg_ok(&cf)) return FDCAP_E_ARG;
     if (o->lbfgs && (o->lbfgs->n != nl || o->lbfgs->cf.hist != cf.history)) { fdcap_lbfgs_destroy(o->lbfgs); o->lbfgs = nullptr; }
     if (!o->lbfgs) { int e = fdcap_lbfgs_create(nl, &cf, &o->lbfgs); if (e) return e; }
@@ -477,7 +567,8 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap
         if (e) break;
         LbfgsFold fold;
         fold.part = o->dZpart.p + (size_t)2 * VP_Z; fold.stride = (size_t)o->R * VP_Z; fold.col0 = X_LATENT; fold.n = VP_Z;
-        e = lbfgs_advance_impl(L, o->X.p + 2 * XDIM, XDIM, o->floss.p, o->dX.p + 2 * XDIM, XDIM, nullptr, fold, st);
+        e = lbfgs_advance_impl(L, o->X.p + 2 * XDIM, XDIM, o->floss.p, o->dX.p + 2 * XDIM, XDIM, nullptr, fold, st,
+                               o->jaw_on ? opt_jaw_grad_in(c) : JawGradIn());
         if (e) break;
         ++rounds;
         if (rounds % poll == 0 || rounds == max_rounds) {
@@ -488,13 +579,26 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap
     }
     if (rounds_out) *rounds_out = rounds;
     // out of rounds with frames still inside a line search: their rows hold trial points -- roll them back to the accepted ones
-    if (!e && rounds >= max_rounds && *L->active_h.p != 0) e = fdcap_lbfgs_finalize(L, o->X.p + 2 * XDIM, XDIM, nullptr, st);
+    o->lbfgs_rolled_back = 0;
+    if (!e && rounds >= max_rounds && *L->active_h.p != 0) {
+        o->lbfgs_rolled_back = *L->active_h.p;               // (a problem that is not finished waits inside a line search, a trial point in its row)
+        if (o->jaw_on) hipLaunchKernelGGL(lbfgs_finalize_tail_kernel, dim3((nl + 63) / 64), dim3(64), 0, st, L->cf, L->S.p, L->W.p, o->jaw.p, nl);
+        e = lbfgs_finalize_impl(L, o->X.p + 2 * XDIM, XDIM, nullptr, o->jaw_on ? 3 : 0, st);
+    }
     if (o->dz_pending) {                                      // leave dX complete, as every other backward of the API does
         hipLaunchKernelGGL(vposer_fold_dz_kernel, dim3((nl * VP_Z + 255) / 256), dim3(256), 0, st, o->dZpart.p, (size_t)o->R * VP_Z, 2, nl, o->dX.p);
         o->dz_pending = false;
     }
     if (e) return e;
     HIP_TRY(hipStreamSynchronize(st));
+    return FDCAP_OK;
+}
+
+int fdcap_opt_fit2d_lbfgs_rolled_back(fdcap_ctx* c, int32_t* n_frames) {
+    if (opt_is_batch(c)) return FDCAP_E_STATE;
+    if (!c || !c->opt || !c->opt->lbfgs) return FDCAP_E_STATE;
+    if (!n_frames) return FDCAP_E_ARG;
+    *n_frames = c->opt->lbfgs_rolled_back;
     return FDCAP_OK;
 }
 
@@ -513,6 +617,10 @@ int fdcap_opt_reset_adam(fdcap_ctx* c, void* stream) {
     o->log_pending = false; o->log_dst = nullptr;
     HIP_TRY(hipMemsetAsync(o->mX.p, 0, n, (hipStream_t)stream));
     HIP_TRY(hipMemsetAsync(o->vX.p, 0, n, (hipStream_t)stream));
+    if (o->jaw_on) {
+        HIP_TRY(hipMemsetAsync(o->mJaw.p, 0, (size_t)3 * o->cfg.n_local * sizeof(float), (hipStream_t)stream));
+        HIP_TRY(hipMemsetAsync(o->vJaw.p, 0, (size_t)3 * o->cfg.n_local * sizeof(float), (hipStream_t)stream));
+    }
     return FDCAP_OK;
 }
 

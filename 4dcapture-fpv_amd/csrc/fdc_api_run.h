@@ -102,6 +102,11 @@ static int opt_step_x_impl(fdcap_ctx* c, int32_t step, hipStream_t st) {
                        o->mX.p + 2 * XDIM, o->vX.p + 2 * XDIM, o->dX.p + 2 * XDIM, nx, adam_scalars(o->cfg.lr, step), 0,
                        o->dz_pending ? (const float*)o->dZpart.p : (const float*)nullptr, (size_t)o->R * VP_Z, 2);
     o->dz_pending = false;                                   // (consumed; dX itself stays without the partials: fdcap_opt_get_grads reads before the step)
+    if (o->jaw_on && o->jaw_eval) {                          // the free jaw of the inner fit: same lr, same step number
+        hipLaunchKernelGGL(jaw_grad_kernel, dim3((o->cfg.n_local + 63) / 64), dim3(64), 0, st, opt_jaw_grad_in(c), o->cfg.n_local, (float*)nullptr,
+                           o->mJaw.p, o->vJaw.p, adam_scalars(o->cfg.lr, step));
+        o->jaw_eval = false;                                 // (consumed: a step after another mode's backward must not read this gradient's parts again)
+    }
     return (int)hipGetLastError();
 }
 

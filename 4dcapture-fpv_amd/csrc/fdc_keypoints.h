@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "fdc_fit2d.h"
+#include "fdc_lbfgs.h"
 #include "fdc_skin.h"
 
 namespace fdc {
@@ -144,6 +145,56 @@ FDC_HD V3 kp_joint_grad(int j, const int32_t* jl_start, const int32_t* jl_k, con
     for (int q = q0 + 1; q < q1; ++q) { const float* d = dkp + 3 * jl_k[q]; g.x += d[0]; g.y += d[1]; g.z += d[2]; }
     return g;
 }
+// ---- the free jaw (host and device) --------------------------------------------------------------------------------------------
+// Joint 22 has parent 15 and no child, so a jaw pose w (axis-angle) changes two things of the model at w = 0 and nothing else: the
+// pose-feature block 9 (22 - 1) .. = R_w - I, and the joint's skinning transform A' = (R_A R_w, t_A + R_A (I - R_w) J22), with
+// (R_A, t_A) the transform pose_fwd_kernel writes for R_22 = I and J22 the joint's rest position.  The joint's own position, every
+// other transform and every Jw row stay.  At w = 0 every line is the fixed model.
+constexpr int JAW_J = 22;
+// rest position of joint j: Jt_j + Jd_j betas (pose_forward's joint_rest, term for term)
+FDC_HD V3 kp_joint_rest(const float* Jt, const float* Jd, const float* betas, int j) {
+    float p[3];
+    for (int c = 0; c < 3; ++c) {
+        float acc = Jt[3 * j + c];
+        for (int l = 0; l < NBETA; ++l) acc += Jd[(3 * j + c) * NBETA + l] * betas[l];
+        p[c] = acc;
+    }
+    return v3(p[0], p[1], p[2]);
+}
+struct JawFwd { M3 Rw, RA; V3 J22, lever; };               // lever = (I - R_w) J22
+// A22 [12] (rows [R | t]): A_22 in, A'_22 out; pf9 (=) R_w - I
+FDC_HD JawFwd jaw_forward(V3 w, V3 J22, float* A22, float* pf9) {
+    JawFwd f;
+    f.Rw = rodrigues_forward(w);
+    f.J22 = J22;
+    for (int i = 0; i < 3; ++i) for (int c = 0; c < 3; ++c) f.RA.m[3 * i + c] = A22[4 * i + c];
+    f.lever = J22 - m3_vec(f.Rw, J22);
+    const M3 R = m3_mul(f.RA, f.Rw);
+    const V3 sh = m3_vec(f.RA, f.lever);
+    for (int i = 0; i < 3; ++i) for (int c = 0; c < 3; ++c) A22[4 * i + c] = R.m[3 * i + c];
+    A22[3] += sh.x; A22[7] += sh.y; A22[11] += sh.z;
+    for (int e = 0; e < 9; ++e) pf9[e] = f.Rw.m[e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+    return f;
+}
+// dAp [12] = (dR', dt'): d loss / d A'_22  ->  the skinning part of d loss / d R_w (the pose-feature block's gradient g_P is added by
+// whoever consumes the jaw's gradient: jaw_grad), what the pose backward receives as d loss / d A_22, and d loss / d J22
+struct JawBwd { M3 dRw; float dA22[12]; V3 dJ22; };
+FDC_HD JawBwd jaw_backward(const JawFwd& f, const float* dAp) {
+    JawBwd b;
+    M3 dRp;
+    for (int i = 0; i < 3; ++i) for (int c = 0; c < 3; ++c) dRp.m[3 * i + c] = dAp[4 * i + c];
+    const V3 dtp = v3(dAp[3], dAp[7], dAp[11]);
+    const V3 q = m3t_vec(f.RA, dtp);                       // R_A^T dt' = d loss / d lever
+    b.dRw = m3_mul_at(f.RA, dRp);                          // R_A^T dR' - q J22^T
+    m3_add_outer(b.dRw, -1.f * q, f.J22);
+    M3 r = m3_mul_bt(dRp, f.Rw);                           // dR' R_w^T + dt' lever^T
+    m3_add_outer(r, dtp, f.lever);
+    for (int i = 0; i < 3; ++i) for (int c = 0; c < 3; ++c) b.dA22[4 * i + c] = r.m[3 * i + c];
+    b.dA22[3] = dtp.x; b.dA22[7] = dtp.y; b.dA22[11] = dtp.z;
+    b.dJ22 = q - m3t_vec(f.Rw, q);                         // (I - R_w)^T q
+    return b;
+}
+
 // One frame on the host, in the kernel's order: positions, data term and d loss / d keypoint, then the gradients of the set
 // vertices' positions (gvw [nu][3]) and of the 23 world joints (dJw [23][3]).  Returns the frame's data term.
 inline float kp_frame_host(const Fit2dStage& s, const KeypointTables& t, const float* Jw, const float* vw, const float* kp, float* pos,
@@ -190,205 +241,38 @@ constexpr int KP_NT = 1024, KP_PART = 4096;     // sixteen waves per frame: the 
 // PANEL (kp_blend_by_panels): the real vertices' offsets arrive in Voff [frame][3 nu] (blend_forward) and every set vertex's
 // d loss / d v_posed leaves in dVoff [frame][3 nu] for blend_backward, which then forms dPF with the betas' columns (dPF is not written
 // here); else both products are plain fp32 multiply-adds here, over the real vertices' columns only (pseudo-vertices have none).
-template <bool POS, bool PANEL>
-__global__ __launch_bounds__(KP_NT) void fit2d_kp_kernel(Fit2dStage s, KpSet ks, const float* __restrict__ X, const float* __restrict__ PF,
-                                                         const float* __restrict__ A, const float* __restrict__ M,
-                                                         const float* __restrict__ scale, const float* __restrict__ Jw,
-                                                         const float* __restrict__ kp, int row0, float* __restrict__ dX,
-                                                         float* __restrict__ dJw, float* __restrict__ dA, float* __restrict__ dPF,
-                                                         float* __restrict__ dtransl_v, float* __restrict__ dMv, float* __restrict__ dsv,
-                                                         double* __restrict__ losses, float* __restrict__ floss, float* __restrict__ pos_out,
-                                                         const float* __restrict__ Voff, float* __restrict__ dVoff) {
-    __shared__ float s_x[XDIM + 2], s_pf[NPFX], s_A[NJ * 12], s_M[12], s_jw[NJW * 3 + 3], s_kp[KP_MAX * 3], s_dk[KP_MAX * 3];
-    __shared__ float s_v[KP_MAXV * 3];         // pose + shape offsets of the real vertices, later every set vertex's d loss / d v_posed
-    __shared__ float s_vp[KP_MAXV * 3], s_vb[KP_MAXV * 3], s_vw[KP_MAXV * 3], s_gv[KP_MAXV * 3];   // (s_vw: positions, later their gradients)
-    __shared__ float s_part[KP_PART];
-    __shared__ float s_red[16][16], s_sred[4][2], s_db[NBETA];
-    const int tid = threadIdx.x, r = row0 + blockIdx.x;
-    const int nr = ks.nr, nu = ks.nr + ks.np, nkp = ks.n_kp, ncol = 3 * ks.nr;
-    // everything of this frame, requested in one batch in front of the first barrier
-    for (int e = tid; e < XDIM; e += KP_NT) s_x[e] = X[(size_t)r * XDIM + e];
-    for (int e = tid; e < NJW * 3; e += KP_NT) s_jw[e] = Jw[(size_t)r * NJW * 3 + e];
-    if (!POS) for (int e = tid; e < nkp * 3; e += KP_NT) s_kp[e] = kp[(size_t)blockIdx.x * nkp * 3 + e];
-    if (nu > 0) {
-        for (int e = tid; e < NPFX; e += KP_NT) s_pf[e] = PF[(size_t)r * NPFX + e];
-        for (int e = tid; e < NJ * 12; e += KP_NT) s_A[e] = A[(size_t)r * NJ * 12 + e];
-        if (tid < 12) s_M[tid] = M[(size_t)r * 12 + tid];
-        if (PANEL) for (int e = tid; e < ncol; e += KP_NT) s_v[e] = Voff[(size_t)blockIdx.x * 3 * nu + e];
-    }
-    const float sc = scale[0];
-    __syncthreads();
-    // pose + shape offsets of the real vertices: s_v[c] = sum_k pf[k] B[k][c], K split over as many parts as the workspace holds
-    if (!PANEL && ncol > 0) {
-        const int nparts = min(16, KP_PART / ncol), kper = (NPFX + nparts - 1) / nparts;
-        for (int w = tid; w < nparts * ncol; w += KP_NT) {
-            const int p = w / ncol, c = w - p * ncol, k1 = min(NPFX, (p + 1) * kper);
-            float acc = 0.f;
-#pragma unroll 8
-            for (int k = p * kper; k < k1; ++k) acc += s_pf[k] * ks.B[(size_t)k * ks.ldb + c];
-            s_part[w] = acc;
-        }
-        __syncthreads();
-        for (int c = tid; c < ncol; c += KP_NT) {
-            float acc = s_part[c];
-            for (int p = 1; p < nparts; ++p) acc += s_part[p * ncol + c];
-            s_v[c] = acc;
-        }
-        __syncthreads();
-    }
-    const V3 transl = v3(s_x[X_TRANSL], s_x[X_TRANSL + 1], s_x[X_TRANSL + 2]);
-    // v_posed of a set vertex and its skinning transform T = sum_k w_k A_{j_k}
-    auto vertex_posed = [&](int u) {
-        if (u < nr) return v3(ks.vt[3 * u] + s_v[3 * u], ks.vt[3 * u + 1] + s_v[3 * u + 1], ks.vt[3 * u + 2] + s_v[3 * u + 2]);
-        const int j = ks.pjoint[u - nr];
-        float p[3];
-        for (int c = 0; c < 3; ++c) {                      // (pose_forward's joint_rest, term for term)
-            float acc = ks.Jt[3 * j + c];
-            for (int l = 0; l < NBETA; ++l) acc += ks.Jd[(3 * j + c) * NBETA + l] * s_x[X_BETAS + l];
-            p[c] = acc;
-        }
-        return v3(p[0], p[1], p[2]);
-    };
-    auto vertex_T = [&](int u, float* T) {
-        for (int e = 0; e < 12; ++e) T[e] = 0.f;
-        for (int k = 0; k < ks.K; ++k) {
-            const float w = ks.ww[(size_t)u * ks.K + k];
-            const float* a = s_A + 12 * ks.wj[(size_t)u * ks.K + k];
-            for (int e = 0; e < 12; ++e) T[e] += w * a[e];
-        }
-    };
-    for (int u = tid; u < nu; u += KP_NT) {
-        const V3 p = vertex_posed(u);
-        float T[12];
-        vertex_T(u, T);
-        const V3 vb = v3(T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3], T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7],
-                         T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11]) + transl;
-        const V3 vw = skin_world_vertex(vb, sc, s_M);
-        s_vp[3 * u] = p.x; s_vp[3 * u + 1] = p.y; s_vp[3 * u + 2] = p.z;
-        s_vb[3 * u] = vb.x; s_vb[3 * u + 1] = vb.y; s_vb[3 * u + 2] = vb.z;
-        s_vw[3 * u] = vw.x; s_vw[3 * u + 1] = vw.y; s_vw[3 * u + 2] = vw.z;
-    }
-    __syncthreads();
-    // keypoint tid: position, data term, d loss / d position -- fit2d_loss_kernel's thread for thread (and its sums' order)
-    float data = 0.f, prior = 0.f;
-    if (tid < nkp) {
-        const V3 p = kp_position(ks.kjoint[tid], ks.kref + 3 * tid, ks.kbary + 3 * tid, s_jw, s_vw);
-        if (POS) {
-            float* o = pos_out + ((size_t)blockIdx.x * nkp + tid) * 3;
-            o[0] = p.x; o[1] = p.y; o[2] = p.z;
-        } else {
-            V3 dJ;
-            data = fit2d_joint(s, p, s_kp[3 * tid], s_kp[3 * tid + 1], s_kp[3 * tid + 2], &dJ);
-            s_dk[3 * tid] = dJ.x; s_dk[3 * tid + 1] = dJ.y; s_dk[3 * tid + 2] = dJ.z;
-        }
-    }
-    if (POS) return;
-    if (tid < XDIM) dX[(size_t)r * XDIM + tid] = fit2d_prior_grad(s, tid, s_x[tid], &prior);
-    if (losses || floss) {
-        float vals[2] = {data, prior};
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float v = vals[i];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-            if ((tid & 63) == 0 && tid < 256) s_sred[tid >> 6][i] = v;         // (keypoints and parameters sit in the first four waves)
-        }
-    }
-    __syncthreads();
-    if (floss && tid == 0)
-        floss[blockIdx.x] = ((s_sred[0][0] + s_sred[1][0]) + (s_sred[2][0] + s_sred[3][0])) + ((s_sred[0][1] + s_sred[1][1]) + (s_sred[2][1] + s_sred[3][1]));
-    if (losses && tid < 2) atomicAdd(&losses[tid], (double)((s_sred[0][tid] + s_sred[1][tid]) + (s_sred[2][tid] + s_sred[3][tid])));
-    if (tid < NJW) {
-        const V3 g = kp_joint_grad(tid, ks.jl_start, ks.jl_k, s_dk);
-        float* o = dJw + ((size_t)r * NJW + tid) * 3;
-        o[0] = g.x; o[1] = g.y; o[2] = g.z;
-    }
-    if (nu == 0) return;                                   // (kernel-uniform: no vertex branch, nothing else is written or read)
-    // set vertex u: its position's gradient from its list, back through the world transform and the skinning
-    for (int u = tid; u < nu; u += KP_NT) {
-        const V3 g = kp_vertex_grad(u, ks.vl_start, ks.vl_k, ks.vl_w, s_dk);
-        SkinFwd f;
-        f.vp = v3(s_vp[3 * u], s_vp[3 * u + 1], s_vp[3 * u + 2]);
-        f.vb = v3(s_vb[3 * u], s_vb[3 * u + 1], s_vb[3 * u + 2]);
-        vertex_T(u, f.T);
-        const SkinBwd b = skin_backward_vertex(f, s_M, sc, g);
-        s_vw[3 * u] = g.x; s_vw[3 * u + 1] = g.y; s_vw[3 * u + 2] = g.z;
-        s_gv[3 * u] = b.gv.x; s_gv[3 * u + 1] = b.gv.y; s_gv[3 * u + 2] = b.gv.z;
-        s_v[3 * u] = b.dvp.x; s_v[3 * u + 1] = b.dvp.y; s_v[3 * u + 2] = b.dvp.z;
-    }
-    __syncthreads();
-    // dA_j = sum over the vertices skinned to j, ascending, of w dT,  dT = gv (x) [v_posed; 1] (skin_backward_vertex's dT, formed here)
-    for (int it = tid; it < NJ * 12; it += KP_NT) {
-        const int j = it / 12, e = it - 12 * j, i = e >> 2, c = e & 3;
-        float acc = 0.f;
-        for (int q = ks.csc_start[j]; q < ks.csc_start[j + 1]; ++q) {
-            const int u = ks.csc_u[q];
-            acc += ks.csc_w[q] * (c < 3 ? s_gv[3 * u + i] * s_vp[3 * u + c] : s_gv[3 * u + i]);
-        }
-        dA[(size_t)r * NJ * 12 + it] = acc;
-    }
-    // the sixteen per-frame sums over the set's vertices -- dM [12], d scale, d transl [3] (skin_backward_vertex's dM, ds, gv) -- in two
-    // steps: sixteen partial sums over u = part, part + 16, .. each, then those in order
-    if (tid < 256) {
-        const int o = tid & 15, part = tid >> 4;
-        float acc = 0.f;
-        for (int u = part; u < nu; u += 16) {
-            const V3 g = v3(s_vw[3 * u], s_vw[3 * u + 1], s_vw[3 * u + 2]), vb = v3(s_vb[3 * u], s_vb[3 * u + 1], s_vb[3 * u + 2]);
-            if (o < 12) {
-                const int i = o >> 2, c = o & 3;
-                const float gi = i == 0 ? g.x : i == 1 ? g.y : g.z;
-                const V3 sv = sc * vb;
-                acc += c == 0 ? gi * sv.x : c == 1 ? gi * sv.y : c == 2 ? gi * sv.z : gi;
-            } else if (o == 12) {
-                const V3 gs = v3(s_M[0] * g.x + s_M[4] * g.y + s_M[8] * g.z, s_M[1] * g.x + s_M[5] * g.y + s_M[9] * g.z,
-                                 s_M[2] * g.x + s_M[6] * g.y + s_M[10] * g.z);
-                acc += dot(gs, vb);
-            } else
-                acc += s_gv[3 * u + o - 13];
-        }
-        s_red[part][o] = acc;
-    }
-    if (PANEL) {                                           // the products' share is blend_backward's
-        for (int e = tid; e < 3 * nu; e += KP_NT) dVoff[(size_t)blockIdx.x * 3 * nu + e] = s_v[e];
-        __syncthreads();
-    } else {
-    // d betas through the pseudo-vertices' rest positions: Jd^T d v_posed, pseudo-vertices ascending
-    if (tid >= 256 && tid < 256 + NBETA) {
-        const int b = tid - 256;
-        float acc = 0.f;
-        for (int u = nr; u < nu; ++u) {
-            const int j = ks.pjoint[u - nr];
-            for (int c = 0; c < 3; ++c) acc += ks.Jd[(3 * j + c) * NBETA + b] * s_v[3 * u + c];
-        }
-        s_db[b] = acc;
-    }
-    // dPF[k] = sum_c Bt[c][k] d v_posed[c] over the real vertices' columns, in eight parts
-    constexpr int BP = 8;
-    static_assert(BP * NPFX <= KP_PART, "the workspace holds the backward's partial sums");
-    const int cper = (ncol + BP - 1) / BP;
-    for (int w = tid; w < BP * NPFX; w += KP_NT) {
-        const int p = w / NPFX, k = w - p * NPFX, c1 = min(ncol, (p + 1) * cper);
-        float acc = 0.f;
-#pragma unroll 8
-        for (int c = p * cper; c < c1; ++c) acc += ks.Bt[(size_t)c * NPFX + k] * s_v[c];
-        s_part[w] = acc;
-    }
-    __syncthreads();
-    for (int k = tid; k < NPFX; k += KP_NT) {
-        float acc = ((s_part[k] + s_part[NPFX + k]) + (s_part[2 * NPFX + k] + s_part[3 * NPFX + k])) +
-                    ((s_part[4 * NPFX + k] + s_part[5 * NPFX + k]) + (s_part[6 * NPFX + k] + s_part[7 * NPFX + k]));
-        if (k >= NPF) acc += s_db[k - NPF];
-        dPF[(size_t)r * NPFX + k] = acc;
-    }
-    }
-    if (tid < 16) {
-        float acc = s_red[0][tid];
-        for (int p = 1; p < 16; ++p) acc += s_red[p][tid];
-        if (tid < 12) dMv[(size_t)r * 12 + tid] = acc;
-        else if (tid == 12) dsv[r] = acc;
-        else dtransl_v[(size_t)r * 3 + tid - 13] = acc;
-    }
-}
+// JAW (fit2d_kp_jaw_kernel): a free jaw, jw.jaw [frame][3].  After staging, thread 0 replaces A_22 and the pose-feature block in LDS
+// (PANEL: the block's nine-row share of the offsets is added here, blend_forward ran on a PF whose block is zero); in the backward
+// the sum for A'_22 goes through jaw_backward: d A_22 to dA, the skinning part of d loss / d R_w to jw.R9 [frame][9] (the consumer of
+// the jaw's gradient adds dPF's block -- written here or by blend_backward afterwards -- and applies Rodrigues' backward: jaw_grad),
+// and Jd_22^T dJ22 is added to the betas' entries of this frame's dX row by the threads that wrote them.  The jaw prior's three terms
+// join `prior` on threads XDIM .. XDIM + 2.  No float atomics.  The kernel's text is csrc/fdc_keypoints_kernel.inc, included once per form, so
+// that fit2d_kp_kernel is compiled from exactly the text it had: not one instruction differs.
+struct JawIO { const float* jaw; float* R9; float w[3]; };
+#define FDC_KP_KERNEL fit2d_kp_kernel
+#define FDC_KP_JAW 0
+#include "fdc_keypoints_kernel.inc"
+#undef FDC_KP_KERNEL
+#undef FDC_KP_JAW
+#define FDC_KP_KERNEL fit2d_kp_jaw_kernel
+#define FDC_KP_JAW 1
+#include "fdc_keypoints_kernel.inc"
+#undef FDC_KP_KERNEL
+#undef FDC_KP_JAW
+
+// The inner fit's L-BFGS with a free jaw: 81 unknowns per frame, the row's 78 and the jaw, which lives in its own array and whose gradient
+// jaw_grad completes (csrc/fdc_fit2d.h) -- the advance kernel's form with three more columns in a second array (csrc/fdc_lbfgs.h).
+#define FDC_LB_KERNEL lbfgs_advance_tail_kernel
+#define FDC_LB_TAIL 1
+#define FDC_LB_TAIL_T JawGradIn
+#define FDC_LB_TAIL_X2(t) (t).jaw
+#define FDC_LB_TAIL_GRAD(t, p) jaw_grad_frame(t, p)
+#include "fdc_lbfgs_advance.inc"
+#undef FDC_LB_KERNEL
+#undef FDC_LB_TAIL
+#undef FDC_LB_TAIL_T
+#undef FDC_LB_TAIL_X2
+#undef FDC_LB_TAIL_GRAD
 #endif
 
 }  // namespace fdc

@@ -174,6 +174,12 @@ struct OptState {
     bool kp_panel = false;    // ... with the set's blend products as panel products around the kernel (kp_blend_by_panels)
     DevBuf<float> kpV, kpdV;  // ... their output and input: the set's offsets / offset gradients [n_local, 3 nu]
     DevBuf<float> floss;      // ... and the per-frame objective of its L-BFGS variant
+    DevBuf<float> jaw, mJaw, vJaw, jawR9;   // ... its free jaw (fdcap_opt_set_jaw) [n_local, 3], Adam's moments of it, and the skinning part of
+                              // d loss / d R_w [n_local, 9] an evaluation leaves (fit2d_kp_jaw_kernel; jaw_grad adds dPF's block)
+    bool jaw_on = false, jaw_eval = false, jaw_gp = false;     // free; an evaluation's gradient parts are there (until a step consumes them); ... with dPF (a set with vertices)
+    int lbfgs_rolled_back = 0;                                 // frames the last fdcap_opt_fit2d_lbfgs call found inside a line search when its rounds ran out
+    float w_jaw[3] = {0.f, 0.f, 0.f};                          // the jaw prior's weights (fdcap_opt_set_fit2d_extra)
+    Fit2dBend bend = {};      // ... its bending prior (fdcap_opt_set_fit2d_extra): w_bend and the terms; n = 0: off
     fdcap_lbfgs* lbfgs = nullptr;
     DevBuf<float4> seedpt;    // coordinates (+ position in the sorted scene) of each query's current neighbour: next launch's seed
     // work-list cache of the in-loop NN launch (fdc_chamfer.h NNCache): ids [groups * 4][64], hdr [groups * 4], anchors [4][nq]

@@ -32,6 +32,15 @@ OPENPOSE_BODY25 = (55, 12, 17, 19, 21, 16, 18, 20, 0, 2, 5, 8, 1, 4, 7, 56, 57, 
 OPENPOSE_LHAND = (20, 37, 38, 39, 66, 25, 26, 27, 67, 28, 29, 30, 68, 34, 35, 36, 69, 31, 32, 33, 70)
 OPENPOSE_RHAND = (21, 52, 53, 54, 71, 40, 41, 42, 72, 43, 44, 45, 73, 49, 50, 51, 74, 46, 47, 48, 75)
 NUM_SMPLX_JOINTS, NUM_EXTRA_VERTEX_JOINTS = 55, 21
+# The bending prior's terms (body joint 1..21, axis, sign): elbows about y, knees about x, and its weight as a multiple of the
+# stage's w_pose.  [upstream-recall: SMPLify-X's angle_prior_idxs 55, 58, 12, 15 of the full pose minus the global orientation's
+# three entries, with signs (1, -1, -1, -1); fitting.py's bending_prior_weight = 3.17 * body_pose_weight.  Neither package is part of
+# this repository: defaults a caller can replace through bend_prior, never constants of a kernel]
+DEFAULT_BEND_TERMS = ((18, 1, 1.0), (19, 1, -1.0), (4, 0, -1.0), (5, 0, -1.0))
+DEFAULT_BEND_RATIO = 3.17
+MAX_BEND_TERMS = 8      # FDCAP_MAX_BEND_TERMS
+# The jaw prior's weights (x, y, z of the jaw's axis-angle) per stage.  [upstream-recall: fit_smplx.yaml's jaw_pose_prior_weights]
+DEFAULT_JAW_PRIOR = ((4.04e3, 4.04e4, 4.04e4), (4.04e3, 4.04e4, 4.04e4), (574.0, 5740.0, 5740.0), (47.8, 478.0, 478.0), (47.8, 478.0, 478.0))
 
 
 class KeypointMap:
@@ -86,13 +95,20 @@ class KeypointMap:
 class InnerFitOP:
     def __init__(self, body_model, vposer, num_frames, intrinsics=DEFAULT_INTRINSICS, rho=100.0, lr=0.01,
                  stages=DEFAULT_STAGES, iters_per_stage=30, optimizer="adam", lbfgs=None, max_rounds=4000,
-                 keypoint_map=None, group_of=None, group_weights=None):
+                 keypoint_map=None, group_of=None, group_weights=None, fit_jaw=False, jaw_prior=None,
+                 bend_prior=None):
         """optimizer "adam": iters_per_stage steps of Adam(lr) per stage; "lbfgs": per frame and stage, SMPLify-X's L-BFGS loop
         with the settings `lbfgs` (keys of DEFAULT_LBFGS; missing ones take their defaults), at most max_rounds objective
         evaluations per stage.
         keypoint_map (KeypointMap): fitting() then takes keypoints [N, len(map), 3] in the map's order.  group_of [len(map)] names
         each keypoint's group (0 without it) and group_weights[stage][group] multiplies the group's confidences before that stage's
-        upload -- SMPLify-X's per-stage hand and face data weights; default all 1."""
+        upload -- SMPLify-X's per-stage hand and face data weights; default all 1.
+        fit_jaw: the jaw pose (SMPL-X joint 22, a leaf: the vertices skinned to it follow, no joint moves) is a free axis-angle per
+        frame next to the row -- needs a keypoint_map, whose face landmarks are what sees it; fitting() leaves it in self.jaw_pose.
+        jaw_prior [stages][3]: the weights of sum_c (w[c] jaw[c])^2 per stage (default DEFAULT_JAW_PRIOR when stages has its five).
+        bend_prior: None (off: not one more library call), or dict(terms=DEFAULT_BEND_TERMS, ratio=DEFAULT_BEND_RATIO) -- SMPLify-X's
+        bending prior ratio * w_pose * sum exp(sign * aa_joint[axis])^2 over the (joint 1..21, axis, sign) terms, added to every
+        stage's priors (missing keys take their defaults; the weight is not squared)."""
         import torch
         if not torch.cuda.is_available():
             raise capi.FdcapError("no HIP device: the fdcap_amd inner fit only runs on the GPU")
@@ -122,11 +138,43 @@ class InnerFitOP:
                     raise capi.FdcapError("group_weights must be [stages][groups]")
                 self.group_weights = gw
             self.ctx.set_keypoint_map(keypoint_map.joint, keypoint_map.tri, keypoint_map.bary)
+        self.fit_jaw, self.jaw_prior, self.jaw_pose = bool(fit_jaw), None, None
+        if self.fit_jaw:
+            if keypoint_map is None:
+                raise capi.FdcapError("fit_jaw needs a keypoint_map: no keypoint of the 23-joint layout follows the jaw")
+            jp = DEFAULT_JAW_PRIOR if jaw_prior is None else jaw_prior
+            self.jaw_prior = np.asarray(jp, dtype=np.float32)
+            if self.jaw_prior.shape != (len(self.stages), 3):
+                raise capi.FdcapError("jaw_prior must be [stages][3]")
+        elif jaw_prior is not None:
+            raise capi.FdcapError("jaw_prior belongs to fit_jaw")
+        self.bend_prior = None
+        if bend_prior is not None:
+            unknown = set(bend_prior) - {"terms", "ratio"}
+            if unknown:
+                raise capi.FdcapError(f"unknown bend_prior settings {sorted(unknown)}")
+            terms = tuple((int(j), int(a), float(s)) for j, a, s in bend_prior.get("terms", DEFAULT_BEND_TERMS))
+            if len(terms) > MAX_BEND_TERMS or any(not (1 <= j <= 21 and 0 <= a <= 2) for j, a, _ in terms):
+                raise capi.FdcapError(f"bend_prior: at most {MAX_BEND_TERMS} terms (joint 1..21, axis 0..2, sign)")
+            self.bend_prior = (terms, float(bend_prior.get("ratio", DEFAULT_BEND_RATIO)))
         self.log, self.rounds, self.frame_iterations, self.frame_loss = [], [], [], []
 
-    def fitting(self, rows75, keypoints, log_every=0):
+    def _set_extra(self, si, w_pose):
+        """this stage's jaw prior weights and bending prior (ratio * w_pose on the terms)"""
+        ex = capi.Fit2dExtra()
+        if self.jaw_prior is not None:
+            ex.w_jaw[0], ex.w_jaw[1], ex.w_jaw[2] = (float(v) for v in self.jaw_prior[si])
+        if self.bend_prior is not None:
+            terms, ratio = self.bend_prior
+            ex.w_bend, ex.n_bend = ratio * w_pose, len(terms)
+            for t, (j, a, s) in enumerate(terms):
+                ex.joint[t], ex.axis[t], ex.sign[t] = j, a, s
+        capi.check(self.ctx.lib.fdcap_opt_set_fit2d_extra(self.ctx.handle, ctypes.byref(ex)), "fdcap_opt_set_fit2d_extra")
+
+    def fitting(self, rows75, keypoints, log_every=0, jaw_init=None):
         """rows75 [N,75] initial parameters (device tensor or numpy), keypoints [N,23,3] (u, v, confidence) -- with a keypoint_map
-        [N,len(map),3] in its order -- -> optimised rows [N,75] (device tensor)."""
+        [N,len(map),3] in its order -- -> optimised rows [N,75] (device tensor).  fit_jaw: the jaw starts from jaw_init [N,3] (default
+        zero) and ends in self.jaw_pose [N,3] (device tensor)."""
         import torch
         lib, h, dev, n = self.ctx.lib, self.ctx.handle, self.device, self.n
         t = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))).to(dev, torch.float32).contiguous()
@@ -156,6 +204,13 @@ class InnerFitOP:
             capi.check(lib.fdcap_opt_set_keypoints(h, capi.dptr(kp), st), "fdcap_opt_set_keypoints")
         else:
             capi.check(lib.fdcap_opt_set_keypoints_mapped(h, capi.dptr(kp), st), "fdcap_opt_set_keypoints_mapped")
+        if self.fit_jaw:
+            jaw0 = torch.zeros(n, 3, device=dev) if jaw_init is None else t(jaw_init)
+            if tuple(jaw0.shape) != (n, 3):
+                raise capi.FdcapError(f"expected jaw_init [{n},3]")
+            capi.check(lib.fdcap_opt_set_jaw(h, capi.dptr(jaw0), st), "fdcap_opt_set_jaw")
+        elif jaw_init is not None:
+            raise capi.FdcapError("jaw_init belongs to fit_jaw")
         self.log, self.rounds, self.frame_iterations, self.frame_loss = [], [], [], []
         fx, fy, cx, cy = self.intrinsics
         for si, (w_data, w_pose, w_shape, w_hand) in enumerate(self.stages):
@@ -164,6 +219,8 @@ class InnerFitOP:
                 kps[:, :, 2] *= torch.from_numpy(self.group_weights[si][self.group_of]).to(dev)
                 capi.check(lib.fdcap_opt_set_keypoints_mapped(h, capi.dptr(kps), capi.current_stream()), "fdcap_opt_set_keypoints_mapped")
             sg = capi.Fit2dStage(fx, fy, cx, cy, self.rho, w_data, w_pose, w_shape, w_hand)
+            if self.bend_prior is not None or self.fit_jaw:
+                self._set_extra(si, w_pose)
             if self.optimizer == "lbfgs":
                 q = self.lbfgs
                 cf = capi.LbfgsConfig(capi.XDIM, q["history"], q["max_iter"], q["max_eval"], q["max_steps"], q["max_ls"], q["lr"],
@@ -195,6 +252,9 @@ class InnerFitOP:
         out = torch.empty(n, capi.PDIM, device=dev)
         capi.check(lib.fdcap_opt_get_results(h, capi.dptr(out), None, None, capi.current_stream()), "fdcap_opt_get_results")
         self.body_rotation_rec = self._rows_x[2:2 + n]
+        if self.fit_jaw:
+            self.jaw_pose = torch.empty(n, 3, device=dev)
+            capi.check(lib.fdcap_opt_get_jaw(h, capi.dptr(self.jaw_pose), None, capi.current_stream()), "fdcap_opt_get_jaw")
         return out
 
     def close(self):

@@ -86,12 +86,18 @@ def save_result(body_rec, scale, camera_ext, fit_path: str) -> list:
     return files
 
 
-def write_body_gen(body_params: np.ndarray, body_path: str) -> None:
-    """Inverse of load_body_gen: lay a [N,75] array out as SMPLify-X result folders."""
+def write_body_gen(body_params: np.ndarray, body_path: str, jaw_pose=None) -> None:
+    """Inverse of load_body_gen: lay a [N,75] array out as SMPLify-X result folders.  jaw_pose [N,3] (the inner fit's free jaw) adds
+    SMPLify-X's `jaw_pose` key; load_body_gen does not read it, as the reference's loader does not."""
+    jaw = None if jaw_pose is None else np.asarray(jaw_pose, dtype=np.float32).reshape(-1, 3)
+    if jaw is not None and jaw.shape[0] != len(body_params):
+        raise ValueError("jaw_pose must hold one axis-angle per row of body_params")
     for i, row in enumerate(np.asarray(body_params, dtype=np.float32)):
         d = os.path.join(body_path, "results", "frame_%06d" % i)
         os.makedirs(d, exist_ok=True)
         rec = {k: row[None, lo:hi].copy() for k, (lo, hi) in SLICES_75.items()}
+        if jaw is not None:
+            rec["jaw_pose"] = jaw[None, i].copy()
         with open(os.path.join(d, "000.pkl"), "wb") as f:
             pickle.dump(rec, f)
 

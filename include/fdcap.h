@@ -509,6 +509,40 @@ int fdcap_debug_keypoints3d(fdcap_ctx* ctx, float* out_d, void* stream);
  * [1] = priors (both already weighted, summed over this rank's frames).  (The latent columns' gradient is left in the VPoser
  * backward's four partial arrays; fdcap_opt_step_x and fdcap_opt_get_grads add them -- one launch less per iteration.) */
 int fdcap_opt_backward_fit2d(fdcap_ctx* ctx, const fdcap_fit2d_stage* stage, int32_t log_terms, void* stream);
+/* What the stage struct does not hold of SMPLify-X's objective (fdcap_fit2d_stage keeps its layout).  The BENDING PRIOR on the body
+ * joints (SMPLify-X's angle prior: elbows and knees must not bend backwards; csrc/fdc_fit2d.h):
+ *     w_bend * sum_t exp(sign[t] * aa_{joint[t]}[axis[t]])^2
+ * with aa_j the axis-angle of body joint j in 1..21 as vposer.decode(z, 'aa') returns it; w_bend enters as it is (SMPLify-X: 3.17 x
+ * the stage's body-pose prior weight), the terms are the caller's (elbows about y, knees about x in SMPL-X: fdcap_amd.innerfit).  It
+ * joins the priors (losses_d [1], the per-frame objective of fdcap_opt_fit2d_lbfgs) on the 23-joint and the mapped data term alike,
+ * by one small launch per evaluation; with n_bend = 0 or w_bend = 0 there is no such launch and every result has the bits it had.
+ * w_jaw: the weights of the prior on a free jaw (fdcap_opt_set_jaw), sum_c (w_jaw[c] * jaw[c])^2, which joins the priors as well;
+ * without a free jaw the term is exactly zero and nothing reads them. */
+#define FDCAP_MAX_BEND_TERMS 8
+typedef struct fdcap_fit2d_extra {
+    float w_jaw[3];
+    float w_bend;
+    int32_t n_bend;                               /* 0 .. FDCAP_MAX_BEND_TERMS */
+    int32_t joint[FDCAP_MAX_BEND_TERMS];          /* 1 .. 21 */
+    int32_t axis[FDCAP_MAX_BEND_TERMS];           /* 0 .. 2 */
+    float sign[FDCAP_MAX_BEND_TERMS];             /* +1 / -1: the direction that is penalised */
+} fdcap_fit2d_extra;
+/* Holds until the next call; extra = NULL: off.  FDCAP_E_ARG: more than FDCAP_MAX_BEND_TERMS terms, a joint outside 1..21, an axis
+ * outside 0..2, a non-finite weight or sign.  FDCAP_E_STATE: no optimiser, a batch of clips or one rank's share of a clip (as the
+ * rest of the inner fit). */
+int fdcap_opt_set_fit2d_extra(fdcap_ctx* ctx, const fdcap_fit2d_extra* extra);
+/* A FREE JAW for the mapped data term (csrc/fdc_keypoints.h): one axis-angle per frame, jaw_d DEVICE [n_local, 3], copied; NULL: fixed
+ * at zero again, the model every other call of this library uses.  SMPL-X's joint 22 is a leaf of the tree, so the jaw changes the
+ * pose-feature block of that joint and its skinning transform and nothing else: the vertices skinned to the jaw follow it, no joint
+ * moves.  From here on fdcap_debug_keypoints3d, fdcap_opt_backward_fit2d and fdcap_opt_fit2d_lbfgs (81 unknowns per frame: the row,
+ * then the jaw) honour it, fdcap_opt_step_x steps it with the rows' lr and step number, fdcap_opt_reset_adam zeroes its moments too.
+ * fdcap_opt_get_results, the full-mesh operators and the clip-level modes keep the jaw at zero.
+ * FDCAP_E_ARG: a model whose joint 22 has a child.  FDCAP_E_STATE: no optimiser, a batch of clips or one rank's share of a clip; and
+ * from an evaluation with a free jaw on the 23-joint layout (fdcap_opt_set_keypoints: no keypoint there follows the jaw). */
+int fdcap_opt_set_jaw(fdcap_ctx* ctx, const float* jaw_d, void* stream);
+/* the jaw and -- optional -- the objective's gradient with respect to it at the last evaluation, DEVICE [n_local, 3] each (either may
+ * be NULL, not both).  FDCAP_E_STATE: no free jaw; djaw_d before an evaluation. */
+int fdcap_opt_get_jaw(fdcap_ctx* ctx, float* jaw_d, float* djaw_d, void* stream);
 int fdcap_opt_reset_adam(fdcap_ctx* ctx, void* stream);
 
 /* ---- batched L-BFGS with a strong-Wolfe line search (csrc/fdc_lbfgs.h) ----
@@ -556,6 +590,9 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* ctx, const fdcap_fit2d_stage* stage, const 
                           int32_t* rounds_out, void* stream);
 /* fdcap_lbfgs_get_stats of the last fdcap_opt_fit2d_lbfgs call, per frame [n_local] (FDCAP_E_STATE before the first) */
 int fdcap_opt_fit2d_lbfgs_stats(fdcap_ctx* ctx, int32_t* iterations_d, int32_t* evaluations_d, float* loss_d, void* stream);
+/* *n_frames (HOST) = the frames the last fdcap_opt_fit2d_lbfgs call found inside a line search when max_rounds ran out and rolled back
+ * to their last accepted point (rows, and the jaw when it is free); 0 when every frame had finished.  FDCAP_E_STATE before the first call. */
+int fdcap_opt_fit2d_lbfgs_rolled_back(fdcap_ctx* ctx, int32_t* n_frames);
 
 /* Multi-GPU iteration tail with ONE collective per iteration (instead of an all-reduce before the
  * step and point-to-point halo messages after it):
