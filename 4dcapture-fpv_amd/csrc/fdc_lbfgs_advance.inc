@@ -280,7 +280,12 @@ __global__ __launch_bounds__(LB_NT) void FDC_LB_KERNEL(LbfgsCfg cf, LbfgsScalars
             st = stop ? STEP_END : ITER_BEGIN;
         } break;
         case STEP_END: {                                     // SMPLify-X's loop around optimizer.step()
-            bool stop = !(fabsf(s.orig_loss) <= 3.0e38f);    // NaN or infinite
+            // (exponent bits all ones -- tested on the bit pattern: the library is built with -fno-honor-nans, which lets a NaN compare fold.
+            // The bits pass an empty asm first: on a value it can trace back to a float the compiler turns the mask test itself into
+            // |x| == inf -- through a readfirstlane too -- and that is false for NaN again.)
+            unsigned loss_bits = __float_as_uint(s.orig_loss);
+            asm volatile("" : "+v"(loss_bits));
+            bool stop = (loss_bits & 0x7f800000u) == 0x7f800000u;    // NaN or infinite
             if (!stop && s.step > 0 && cf.ftol > 0.f) {
                 const float rel = fabsf(s.prev_orig - s.orig_loss) / fmaxf(fmaxf(fabsf(s.prev_orig), fabsf(s.orig_loss)), 1.f);
                 stop = rel <= cf.ftol;

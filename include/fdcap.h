@@ -551,7 +551,10 @@ int fdcap_opt_reset_adam(fdcap_ctx* ctx, void* stream);
  * of torch.optim.LBFGS, restated as a resumable state machine per problem: n_problems INDEPENDENT problems of `dim` <= 128
  * unknowns advance together, one launch between two evaluations of the caller's objective.
  *   max_iter / max_eval / history / lr / tolerance_grad / tolerance_change: torch.optim.LBFGS's arguments (max_eval <= 0:
- *       max_iter * 5 / 4; history <= 128);  max_ls: evaluations per line search (torch: 25);
+ *       max_iter * 5 / 4; history <= 128);
+ *   max_ls: extrapolation / zoom rounds of ONE line search after its first evaluation, i.e. at most max_ls + 1 evaluations per
+ *       search, whatever the step has already spent (the fixed 25 of older torch.  Current torch caps a search at the step's
+ *       remaining evaluations instead, max_eval - evaluations so far: the same decisions unless a search reaches the smaller cap);
  *   max_steps, ftol, gtol: SMPLify-X's loop around optimizer.step(): at most max_steps calls, stop when the loss at the start
  *       of two successive calls differs by <= ftol relative to max(|a|, |b|, 1) or every gradient entry is below gtol
  *       (max_steps = 1, ftol = gtol = 0: exactly one optimizer.step()). */
