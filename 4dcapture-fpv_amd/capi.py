@@ -46,6 +46,12 @@ class Fit2dExtra(ctypes.Structure):
                 ("sign", c_float * 8)]
 
 
+class Fit2dInit(ctypes.Structure):
+    """include/fdcap.h fdcap_fit2d_init: the depth guess's edges, the camera stage's torso and weights, the side-view test."""
+    _fields_ = [("n_edge", c_int32), ("edge", (c_int32 * 2) * 4), ("n_torso", c_int32), ("torso", c_int32 * 8), ("shoulder", c_int32 * 2),
+                ("conf_thr", c_float), ("default_depth", c_float), ("side_view_px", c_float), ("w_data", c_float), ("w_depth", c_float)]
+
+
 class LbfgsConfig(ctypes.Structure):
     """include/fdcap.h fdcap_lbfgs_config: torch.optim.LBFGS's arguments + SMPLify-X's loop around optimizer.step()."""
     _fields_ = [("dim", c_int32), ("history", c_int32), ("max_iter", c_int32), ("max_eval", c_int32), ("max_steps", c_int32),
@@ -154,6 +160,13 @@ SYMBOLS = {
     "fdcap_opt_fit2d_lbfgs": (c_int32, [c_void_p, POINTER(Fit2dStage), POINTER(LbfgsConfig), c_int32, POINTER(c_int32), c_void_p]),
     "fdcap_opt_fit2d_lbfgs_rolled_back": (c_int32, [c_void_p, POINTER(c_int32)]),
     "fdcap_opt_fit2d_lbfgs_stats": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_fit2d_guess": (c_int32, [c_void_p, POINTER(Fit2dStage), POINTER(Fit2dInit), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_backward_fit2d_camera": (c_int32, [c_void_p, POINTER(Fit2dStage), POINTER(Fit2dInit), c_int32, c_void_p]),
+    "fdcap_opt_fit2d_camera_lbfgs": (c_int32, [c_void_p, POINTER(Fit2dStage), POINTER(Fit2dInit), POINTER(LbfgsConfig), c_int32,
+                                               POINTER(c_int32), c_void_p]),
+    "fdcap_opt_fit2d_frame_loss": (c_int32, [c_void_p, POINTER(Fit2dStage), c_void_p, c_void_p]),
+    "fdcap_fit2d_flip_orient": (c_int32, [c_void_p, c_int32, c_void_p]),
+    "fdcap_fit2d_select": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_step_rows_and_pack": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "fdcap_opt_unpack_and_step_scale": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "fdcap_opt_forward_ahead": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),

@@ -1,0 +1,102 @@
+"""Command line of the per-frame inner fit, from a detector's output to what global_optimization_hip.py reads:
+
+    python3 innerfit_hip.py KEYPOINT_DIR BODY_PATH [--models DIR] [--vposer DIR] [--intrinsics FX FY CX CY] [--optimizer lbfgs|adam]
+                            [--hands] [--vertex-ids FILE] [--fit-jaw] [--frames-per-batch N]
+
+KEYPOINT_DIR holds OpenPose's `*_keypoints.json`, one per frame (io.read_openpose_json; sorted by name).  Every frame starts from
+neutral rows: innerfit.InnerFitOP(init={}) makes the depth guess, runs the camera stage and tries the turned body where the
+shoulders nearly coincide.  Output: `<BODY_PATH>/results/frame_%06d/000.pkl` (io.write_body_gen), with `jaw_pose` under --fit-jaw.
+
+The keypoint map holds the BODY_25 (with --hands: and hand) keypoints that are SMPL-X joints.  The keypoints smplx regresses from
+mesh vertices (nose, eyes, ears, toes, heels, fingertips) join it only when --vertex-ids names a file with smplx's 21 vertex ids
+in its order (JSON list or whitespace-separated; innerfit.KeypointMap.from_smplx_indices) -- they are not part of this repository.
+A keypoint without a target is left OUT of the map, not weighted zero.  The planning is pure functions (tests/test_fit2d_init_cpu.py)."""
+from __future__ import annotations
+
+import argparse
+import glob
+import json
+import os
+
+import numpy as np
+
+from .innerfit import NUM_EXTRA_VERTEX_JOINTS, NUM_SMPLX_JOINTS, OPENPOSE_BODY25, OPENPOSE_LHAND, OPENPOSE_RHAND
+
+DEFAULT_FRAMES_PER_BATCH = 256
+
+
+def keypoint_files(keypoint_dir: str) -> list:
+    files = sorted(glob.glob(os.path.join(keypoint_dir, "*_keypoints.json")))
+    if not files:
+        raise FileNotFoundError(f"no *_keypoints.json under {keypoint_dir}")
+    return files
+
+
+def plan_keypoints(hands: bool, have_vertex_ids: bool):
+    """-> (columns, indices): the columns of io.read_openpose_json(hands=hands)'s rows that get a place in the map, and their
+    targets in smplx's 127-joint convention.  Joints always; the 21 vertex keypoints only with their ids; nothing else."""
+    order = list(OPENPOSE_BODY25) + (list(OPENPOSE_LHAND) + list(OPENPOSE_RHAND) if hands else [])
+    limit = NUM_SMPLX_JOINTS + (NUM_EXTRA_VERTEX_JOINTS if have_vertex_ids else 0)
+    columns = [c for c, i in enumerate(order) if i < limit]
+    return columns, [order[c] for c in columns]
+
+
+def read_vertex_ids(path: str) -> np.ndarray:
+    with open(path) as f:
+        text = f.read()
+    try:
+        ids = json.loads(text)
+    except ValueError:
+        ids = text.split()
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if ids.shape[0] != NUM_EXTRA_VERTEX_JOINTS:
+        raise ValueError(f"{path}: {ids.shape[0]} vertex ids, smplx has {NUM_EXTRA_VERTEX_JOINTS}")
+    return ids
+
+
+def plan_frame_batches(n_frames: int, frames_per_batch: int) -> list:
+    """[(first, end)] covering 0..n_frames in order, each at most frames_per_batch long"""
+    if n_frames <= 0 or frames_per_batch <= 0:
+        raise ValueError("n_frames and frames_per_batch must be positive")
+    return [(lo, min(lo + frames_per_batch, n_frames)) for lo in range(0, n_frames, frames_per_batch)]
+
+
+def main(argv=None, body_model=None, vposer=None):
+    """body_model / vposer: model data already in memory (tests); else --models / --vposer are read"""
+    ap = argparse.ArgumentParser(prog="innerfit (fdcap_amd / MI355X)")
+    ap.add_argument("keypoint_dir")
+    ap.add_argument("body_path")
+    ap.add_argument("--models", default="./models")
+    ap.add_argument("--vposer", default="./vposer/")
+    ap.add_argument("--intrinsics", nargs=4, type=float, default=None, metavar=("FX", "FY", "CX", "CY"))
+    ap.add_argument("--optimizer", default="lbfgs", choices=["lbfgs", "adam"])
+    ap.add_argument("--hands", action="store_true", help="read and fit the hand keypoints too")
+    ap.add_argument("--vertex-ids", default=None, metavar="FILE", help="smplx's 21 vertex ids: adds the keypoints regressed from vertices")
+    ap.add_argument("--fit-jaw", action="store_true")
+    ap.add_argument("--frames-per-batch", type=int, default=DEFAULT_FRAMES_PER_BATCH)
+    a = ap.parse_args(argv)
+
+    from . import assets, io
+    from .innerfit import DEFAULT_INTRINSICS, InnerFitOP, KeypointMap
+
+    files = keypoint_files(a.keypoint_dir)
+    vertex_ids = read_vertex_ids(a.vertex_ids) if a.vertex_ids else None
+    columns, indices = plan_keypoints(a.hands, vertex_ids is not None)
+    kmap = KeypointMap.from_smplx_indices(indices, vertex_ids if vertex_ids is not None else [])
+    kp = np.stack([io.read_openpose_json(fn, hands=a.hands)[columns] for fn in files])
+    bm = body_model if body_model is not None else assets.load_smplx_npz(a.models)
+    vp = vposer if vposer is not None else assets.load_vposer_snapshot(a.vposer)
+    intrinsics = tuple(a.intrinsics) if a.intrinsics else DEFAULT_INTRINSICS
+    rows, jaws, ops = [], [], {}
+    for lo, hi in plan_frame_batches(len(files), a.frames_per_batch):
+        n = hi - lo
+        if n not in ops:                                     # (at most two sizes: the full batches and the remainder)
+            ops[n] = InnerFitOP(bm, vp, n, intrinsics=intrinsics, optimizer=a.optimizer, keypoint_map=kmap, fit_jaw=a.fit_jaw, init={})
+        rows.append(ops[n].fitting(None, kp[lo:hi]).cpu().numpy())
+        if a.fit_jaw:
+            jaws.append(ops[n].jaw_pose.cpu().numpy())
+    for op in ops.values():
+        op.close()
+    io.write_body_gen(np.concatenate(rows), a.body_path, jaw_pose=np.concatenate(jaws) if a.fit_jaw else None)
+    print(f"[INFO][innerfit] {len(files)} frames -> {a.body_path}/results")
+    return 0

@@ -608,6 +608,150 @@ int fdcap_opt_fit2d_lbfgs_stats(fdcap_ctx* c, int32_t* it, int32_t* ev, float* l
     return fdcap_lbfgs_get_stats(c->opt->lbfgs, it, ev, loss, stream);
 }
 
+// ---- the inner fit's start from keypoints alone (csrc/fdc_fit2d_init.h) ----------------------------------------------------------
+static_assert(sizeof(((fdcap_fit2d_init*)nullptr)->edge) == sizeof(int32_t) * INIT_MAX_EDGE * 2 && sizeof(((fdcap_fit2d_init*)nullptr)->torso) == sizeof(int32_t) * INIT_MAX_TORSO,
+              "fdc_fit2d_init.h restates the longest lists of fdcap_fit2d_init");
+// the state the three calls need, then the caller's settings with their slots resolved against the current keypoint layout
+static int fit2d_init_resolve(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap_fit2d_init* in, Fit2dInit* out, int* n_kp) {
+    if (!c || !c->opt || opt_is_batch(c) || !opt_whole_clips(c->opt) || !c->opt->kp2d.p) return FDCAP_E_STATE;
+    if (!sg || !in) return FDCAP_E_ARG;
+    std::vector<int32_t> slot_joint;
+    if (c->opt->kp_mapped) {                                  // (a joint 23..54 is a pseudo-vertex of the set: KeypointTables)
+        const KeypointTables& t = c->kpset.h;
+        for (int k = 0; k < t.n_kp; ++k)
+            slot_joint.push_back(t.kjoint[k] >= 0 ? t.kjoint[k] : t.kref[3 * k] >= t.nr ? t.pseudo_joint[t.kref[3 * k] - t.nr] : -1);
+    } else
+        for (int k = 0; k < NJW; ++k) slot_joint.push_back(k);
+    *n_kp = (int)slot_joint.size();
+    if (fit2d_init_build(in->n_edge, in->edge, in->n_torso, in->torso, in->shoulder, in->conf_thr, in->default_depth, in->side_view_px, in->w_data,
+                         in->w_depth, *n_kp, slot_joint.data(), out))
+        return FDCAP_E_ARG;
+    return FDCAP_OK;
+}
+static int fit2d_full_forward(fdcap_ctx* c, hipStream_t st) {
+    int row_lo, row_hi;
+    opt_row_range(c->opt, 1, &row_lo, &row_hi);
+    return opt_pose_forward(c, row_lo, row_hi, st);
+}
+
+int fdcap_opt_fit2d_guess(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap_fit2d_init* init, float* z_d, int32_t* valid_d, int32_t* side_view_d,
+                          void* stream) {
+    Fit2dInit ci;
+    int n_kp = 0;
+    { int e = fit2d_init_resolve(c, sg, init, &ci, &n_kp); if (e) return e; }
+    hipStream_t st = (hipStream_t)stream;
+    { int es_ = opt_sync(c, st); if (es_) return es_; }
+    OptState* o = c->opt;
+    const int nl = o->cfg.n_local;
+    { int e = fit2d_full_forward(c, st); if (e) return e; }
+    hipLaunchKernelGGL(fit2d_guess_kernel, dim3((nl + 63) / 64), dim3(64), 0, st, ci, sg->fx, sg->fy, o->G.p, o->kp2d.p, n_kp, 2, nl, o->X.p, z_d,
+                       (int*)valid_d, (int*)side_view_d);
+    return (int)hipGetLastError();
+}
+
+// one evaluation of the camera stage (set-up first where it is due): the whole of dX's owned rows, optionally the per-frame value
+static int fit2d_camera_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const Fit2dInit& ci, int n_kp, bool setup, double* losses, float* floss,
+                             hipStream_t st) {
+    OptState* o = c->opt;
+    const int nl = o->cfg.n_local;
+    if (setup || !o->cam_ready || !fit2d_init_same_torso(o->cam_init, ci)) {
+        HIP_TRY(o->cam_setup.ensure((size_t)nl * CAM_SETUP_LD));
+        { int e = fit2d_full_forward(c, st); if (e) return e; }
+        hipLaunchKernelGGL(fit2d_camera_setup_kernel, dim3(nl), dim3(64), 0, st, ci, o->X.p, o->G.p, 2, o->cam_setup.p);
+        o->cam_ready = true;
+        o->cam_init = ci;
+    }
+    const Fit2dStage s = {sg->fx, sg->fy, sg->cx, sg->cy, sg->rho, sg->w_data, sg->w_pose, sg->w_shape, sg->w_hand};
+    hipLaunchKernelGGL(fit2d_camera_kernel, dim3(nl), dim3(64), 0, st, s, ci, o->X.p, o->cam_setup.p, o->kp2d.p, n_kp, 2, o->dX.p, losses, floss);
+    o->dz_pending = false;                                    // (the latent's columns are zeros of this launch: no partial belongs to them)
+    o->jaw_eval = false;                                      // (... and no gradient part to a free jaw: a step leaves it where it is)
+    return (int)hipGetLastError();
+}
+
+int fdcap_opt_backward_fit2d_camera(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap_fit2d_init* init, int32_t log_terms, void* stream) {
+    Fit2dInit ci;
+    int n_kp = 0;
+    { int e = fit2d_init_resolve(c, sg, init, &ci, &n_kp); if (e) return e; }
+    hipStream_t st = (hipStream_t)stream;
+    { int es_ = opt_sync(c, st); if (es_) return es_; }
+    double* const losses = (log_terms & 1) ? c->opt->losses.p : nullptr;
+    if (losses) HIP_TRY(hipMemsetAsync(losses, 0, FDCAP_NUM_LOSSES * sizeof(double), st));
+    return fit2d_camera_eval(c, sg, ci, n_kp, (log_terms & 2) != 0, losses, nullptr, st);
+}
+
+int fdcap_opt_fit2d_camera_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap_fit2d_init* init, const fdcap_lbfgs_config* cfg,
+                                 int32_t max_rounds, int32_t* rounds_out, void* stream) {
+    Fit2dInit ci;
+    int n_kp = 0;
+    { int e = fit2d_init_resolve(c, sg, init, &ci, &n_kp); if (e) return e; }
+    if (!cfg || max_rounds <= 0) return FDCAP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    { int es_ = opt_sync(c, st); if (es_) return es_; }
+    OptState* o = c->opt;
+    const int nl = o->cfg.n_local;
+    fdcap_lbfgs_config cf = *cfg;
+    cf.dim = XDIM;                                            // the whole row: 69 of its columns never get a gradient, so never a direction
+    if (!lbfgs_cfg_ok(&cf)) return FDCAP_E_ARG;
+    if (o->lbfgs && (o->lbfgs->n != nl || o->lbfgs->cf.hist != cf.history)) { fdcap_lbfgs_destroy(o->lbfgs); o->lbfgs = nullptr; }
+    if (!o->lbfgs) { int e = fdcap_lbfgs_create(nl, &cf, &o->lbfgs); if (e) return e; }
+    fdcap_lbfgs* L = o->lbfgs;
+    L->cf = {cf.dim, cf.history, cf.max_iter, cf.max_eval > 0 ? cf.max_eval : cf.max_iter * 5 / 4, cf.max_steps, cf.max_ls,
+             cf.lr, cf.tolerance_grad, cf.tolerance_change, cf.ftol, cf.gtol};
+    { int e = fdcap_lbfgs_reset(L, st); if (e) return e; }
+    HIP_TRY(o->floss.ensure(nl));
+    o->ahead = false; o->log_pending = false; o->log_dst = nullptr;
+    int rounds = 0, e = 0;
+    const int poll = 8;                                       // (fdcap_opt_fit2d_lbfgs's)
+    while (rounds < max_rounds) {
+        e = fit2d_camera_eval(c, sg, ci, n_kp, false, nullptr, o->floss.p, st);
+        if (e) break;
+        e = lbfgs_advance_impl(L, o->X.p + 2 * XDIM, XDIM, o->floss.p, o->dX.p + 2 * XDIM, XDIM, nullptr, LbfgsFold(), st);
+        if (e) break;
+        ++rounds;
+        if (rounds % poll == 0 || rounds == max_rounds) {
+            HIP_TRY(hipMemcpyAsync(L->active_h.p, L->active.p + ((L->round - 1) & 1), sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (*L->active_h.p == 0) break;
+        }
+    }
+    if (rounds_out) *rounds_out = rounds;
+    o->lbfgs_rolled_back = 0;
+    if (!e && rounds >= max_rounds && *L->active_h.p != 0) {   // out of rounds inside a line search: back to the accepted points
+        o->lbfgs_rolled_back = *L->active_h.p;
+        e = lbfgs_finalize_impl(L, o->X.p + 2 * XDIM, XDIM, nullptr, 0, st);
+    }
+    if (e) return e;
+    HIP_TRY(hipStreamSynchronize(st));
+    return FDCAP_OK;
+}
+
+int fdcap_opt_fit2d_frame_loss(fdcap_ctx* c, const fdcap_fit2d_stage* sg, float* floss_d, void* stream) {
+    if (!c || !c->opt || opt_is_batch(c) || !opt_whole_clips(c->opt) || !c->opt->kp2d.p) return FDCAP_E_STATE;
+    if (!sg || !floss_d) return FDCAP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    { int es_ = opt_sync(c, st); if (es_) return es_; }
+    OptState* o = c->opt;
+    HIP_TRY(o->floss.ensure(o->cfg.n_local));
+    { int e = fit2d_eval(c, sg, nullptr, o->floss.p, st, true); if (e) return e; }
+    HIP_TRY(hipMemcpyAsync(floss_d, o->floss.p, (size_t)o->cfg.n_local * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return FDCAP_OK;
+}
+
+int fdcap_fit2d_flip_orient(float* rows75_d, int32_t n, void* stream) {
+    if (!rows75_d || n <= 0) return FDCAP_E_ARG;
+    hipLaunchKernelGGL(fit2d_flip_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, rows75_d, n);
+    return (int)hipGetLastError();
+}
+
+int fdcap_fit2d_select(const float* rows_d, const float* loss_d, const int32_t* src_d, int32_t n, int32_t m, const float* jaw_d, float* rows_out_d,
+                       float* jaw_out_d, int32_t* chosen_d, void* stream) {
+    if (!rows_d || !loss_d || !rows_out_d || n <= 0 || m < 0 || m > n || (m > 0 && !src_d) || (jaw_d == nullptr) != (jaw_out_d == nullptr))
+        return FDCAP_E_ARG;
+    hipLaunchKernelGGL(fit2d_select_kernel, dim3(n), dim3(128), 0, (hipStream_t)stream, rows_d, loss_d, (const int*)src_d, n, m, jaw_d, rows_out_d,
+                       jaw_out_d, (int*)chosen_d);
+    return (int)hipGetLastError();
+}
+
 // zero Adam's moments of body_rotation_rec (SMPLify-X builds a fresh optimiser for every stage of the fit)
 int fdcap_opt_reset_adam(fdcap_ctx* c, void* stream) {
     if (!c || !c->opt) return FDCAP_E_STATE;

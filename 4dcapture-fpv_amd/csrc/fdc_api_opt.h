@@ -59,6 +59,7 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->dz_pending = false;
     o->log_pending = false;
     o->kp_mapped = false;
+    o->cam_ready = false;
     o->seeded = false;
     o->nnpt_valid = false;
     o->n_recompute = 0;
@@ -224,6 +225,7 @@ int fdcap_opt_set_inputs(fdcap_ctx* c, const float* data78, const float* init78,
     OptState* o = c->opt;
     hipStream_t st = (hipStream_t)stream;
     const size_t n = o->cfg.n_local;
+    o->cam_ready = false;                                   // (new rows: the camera stage sets itself up again, csrc/fdc_fit2d_init.h)
     o->log_pending = false; o->log_dst = nullptr;
     HIP_TRY(hipMemcpyAsync(o->X0.p + 2 * XDIM, data78, n * XDIM * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(o->X.p + 2 * XDIM, init78, n * XDIM * sizeof(float), hipMemcpyDeviceToDevice, st));

@@ -180,6 +180,9 @@ struct OptState {
     int lbfgs_rolled_back = 0;                                 // frames the last fdcap_opt_fit2d_lbfgs call found inside a line search when its rounds ran out
     float w_jaw[3] = {0.f, 0.f, 0.f};                          // the jaw prior's weights (fdcap_opt_set_fit2d_extra)
     Fit2dBend bend = {};      // ... its bending prior (fdcap_opt_set_fit2d_extra): w_bend and the terms; n = 0: off
+    DevBuf<float> cam_setup;  // ... its camera stage (csrc/fdc_fit2d_init.h): per frame the torso's offsets, the pelvis base and z0 [n_local, CAM_SETUP_LD]
+    bool cam_ready = false;   // ... they belong to the current rows and to cam_init's torso (fdcap_opt_set_inputs, any other pose forward: no longer)
+    Fit2dInit cam_init = {};
     fdcap_lbfgs* lbfgs = nullptr;
     DevBuf<float4> seedpt;    // coordinates (+ position in the sorted scene) of each query's current neighbour: next launch's seed
     // work-list cache of the in-loop NN launch (fdc_chamfer.h NNCache): ids [groups * 4][64], hdr [groups * 4], anchors [4][nq]
@@ -739,6 +742,7 @@ int opt_pose_forward(fdcap_ctx* c, int lo, int hi, hipStream_t st, bool contact_
     const PoseJoints& js = pj ? *pj : full;
     o->pj_fwd = js;
     o->ahead = false;                                       // (whatever ran ahead is recomputed here)
+    o->cam_ready = false;                                   // (whoever runs the model may step any column: the camera stage sets itself up again, fdc_fit2d_init.h)
     const size_t ps = (size_t)o->R * ODIM;
     const int nl = o->cfg.n_local;
     DeferredStep ds;

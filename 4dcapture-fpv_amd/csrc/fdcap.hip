@@ -36,6 +36,7 @@ __device__ unsigned long long g_fr_times[3][2048 * 8];
 #include "fdc_comm.h"
 #include "fdc_dct.h"
 #include "fdc_fit2d.h"
+#include "fdc_fit2d_init.h"
 #include "fdc_frame.h"
 #include "fdc_keypoints.h"
 #include "fdc_gemm.h"

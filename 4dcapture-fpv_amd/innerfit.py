@@ -42,6 +42,16 @@ MAX_BEND_TERMS = 8      # FDCAP_MAX_BEND_TERMS
 # The jaw prior's weights (x, y, z of the jaw's axis-angle) per stage.  [upstream-recall: fit_smplx.yaml's jaw_pose_prior_weights]
 DEFAULT_JAW_PRIOR = ((4.04e3, 4.04e4, 4.04e4), (4.04e3, 4.04e4, 4.04e4), (574.0, 5740.0, 5740.0), (47.8, 478.0, 478.0), (47.8, 478.0, 478.0))
 
+# How a fit starts from keypoints alone (csrc/fdc_fit2d_init.h), as SMPL-X JOINTS -- resolved to keypoint slots per layout: the depth
+# guess's torso edges (left shoulder - left hip, right shoulder - right hip), the camera stage's keypoints (both shoulders, both hips)
+# and weights, the shoulders of the side-view test.  w_data None: 1000 / image height, the height taken as 2 cy.
+# [upstream-recall: SMPLify-X's guess_init (edge_idxs 5-12 and 2-9 of OpenPose's BODY_25), init_joints_idxs 9, 12, 2, 5,
+# data_weight = 1000 / H, depth_loss_weight 1e2, side_view_thsh 25, its default init_t depth 2.5 and fitting.py's camera loss without
+# a robustifier or confidences; not part of this repository: defaults a caller can replace through init, never constants of a kernel]
+DEFAULT_INIT = dict(edges=((16, 1), (17, 2)), torso=(16, 17, 1, 2), shoulders=(16, 17), conf_thr=0.0, default_depth=2.5, side_view_px=25.0,
+                    w_data=None, w_depth=100.0)
+MAX_INIT_EDGES, MAX_INIT_TORSO = 4, 8       # fdcap_fit2d_init's lists
+
 
 class KeypointMap:
     """Which body point each detected keypoint is (include/fdcap.h fdcap_set_keypoint_map): joint[k] >= 0 an SMPL-X joint, else the
@@ -92,11 +102,48 @@ class KeypointMap:
         return cls(joint, tri, bary)
 
 
+def init_slots(joints, keypoint_map):
+    """SMPL-X joints -> slots of a frame's keypoint array: the joint itself in the 23-joint layout (keypoint_map None), else the first
+    entry of the map that is this joint"""
+    out = []
+    for j in joints:
+        j = int(j)
+        if keypoint_map is None:
+            if not 0 <= j < 23:
+                raise capi.FdcapError(f"init: joint {j} is not in the 23-joint layout")
+            out.append(j)
+        else:
+            hit = np.flatnonzero(keypoint_map.joint == j)
+            if j < 0 or hit.size == 0:
+                raise capi.FdcapError(f"init: joint {j} is not a keypoint of the map")
+            out.append(int(hit[0]))
+    return out
+
+
+def init_struct(settings, keypoint_map, intrinsics):
+    """capi.Fit2dInit of a full settings dict (DEFAULT_INIT's keys, joints) for this keypoint layout and camera"""
+    edges = [init_slots(e, keypoint_map) for e in settings["edges"]]
+    torso, shoulders = init_slots(settings["torso"], keypoint_map), init_slots(settings["shoulders"], keypoint_map)
+    if not 1 <= len(edges) <= MAX_INIT_EDGES or any(len(e) != 2 for e in edges) or not 1 <= len(torso) <= MAX_INIT_TORSO or len(shoulders) != 2:
+        raise capi.FdcapError(f"init: 1..{MAX_INIT_EDGES} edges of two joints, 1..{MAX_INIT_TORSO} torso joints, two shoulders")
+    ci = capi.Fit2dInit()
+    ci.n_edge, ci.n_torso = len(edges), len(torso)
+    for e, (a, b) in enumerate(edges):
+        ci.edge[e][0], ci.edge[e][1] = a, b
+    for k, v in enumerate(torso):
+        ci.torso[k] = v
+    ci.shoulder[0], ci.shoulder[1] = shoulders
+    w_data = 1000.0 / (2.0 * intrinsics[3]) if settings["w_data"] is None else settings["w_data"]
+    ci.conf_thr, ci.default_depth, ci.side_view_px = float(settings["conf_thr"]), float(settings["default_depth"]), float(settings["side_view_px"])
+    ci.w_data, ci.w_depth = float(w_data), float(settings["w_depth"])
+    return ci
+
+
 class InnerFitOP:
     def __init__(self, body_model, vposer, num_frames, intrinsics=DEFAULT_INTRINSICS, rho=100.0, lr=0.01,
                  stages=DEFAULT_STAGES, iters_per_stage=30, optimizer="adam", lbfgs=None, max_rounds=4000,
                  keypoint_map=None, group_of=None, group_weights=None, fit_jaw=False, jaw_prior=None,
-                 bend_prior=None):
+                 bend_prior=None, init=None, orientations="auto"):
         """optimizer "adam": iters_per_stage steps of Adam(lr) per stage; "lbfgs": per frame and stage, SMPLify-X's L-BFGS loop
         with the settings `lbfgs` (keys of DEFAULT_LBFGS; missing ones take their defaults), at most max_rounds objective
         evaluations per stage.
@@ -108,7 +155,12 @@ class InnerFitOP:
         jaw_prior [stages][3]: the weights of sum_c (w[c] jaw[c])^2 per stage (default DEFAULT_JAW_PRIOR when stages has its five).
         bend_prior: None (off: not one more library call), or dict(terms=DEFAULT_BEND_TERMS, ratio=DEFAULT_BEND_RATIO) -- SMPLify-X's
         bending prior ratio * w_pose * sum exp(sign * aa_joint[axis])^2 over the (joint 1..21, axis, sign) terms, added to every
-        stage's priors (missing keys take their defaults; the weight is not squared)."""
+        stage's priors (missing keys take their defaults; the weight is not squared).
+        init: None (off: fitting() needs rows that already stand in front of the camera, and not one call differs), or a dict with
+        keys of DEFAULT_INIT (missing ones take their defaults; {} is all defaults): fitting() then starts as SMPLify-X does -- a depth
+        guess from torso edge lengths, a camera stage over global_orient and camera_translation alone on the torso keypoints, and
+        by `orientations` a twin problem per frame with the body turned 180 degrees about y, the fit with the lower final objective
+        kept: "auto" for the frames whose shoulders nearly coincide in the image, "both" for all, "given" for none."""
         import torch
         if not torch.cuda.is_available():
             raise capi.FdcapError("no HIP device: the fdcap_amd inner fit only runs on the GPU")
@@ -157,6 +209,17 @@ class InnerFitOP:
             if len(terms) > MAX_BEND_TERMS or any(not (1 <= j <= 21 and 0 <= a <= 2) for j, a, _ in terms):
                 raise capi.FdcapError(f"bend_prior: at most {MAX_BEND_TERMS} terms (joint 1..21, axis 0..2, sign)")
             self.bend_prior = (terms, float(bend_prior.get("ratio", DEFAULT_BEND_RATIO)))
+        self.init = None
+        if orientations not in ("auto", "both", "given"):
+            raise capi.FdcapError(f"orientations must be 'auto', 'both' or 'given', not {orientations!r}")
+        self.orientations = orientations
+        if init is not None:
+            unknown = set(init) - set(DEFAULT_INIT)
+            if unknown:
+                raise capi.FdcapError(f"unknown init settings {sorted(unknown)}")
+            self.init = init_struct({**DEFAULT_INIT, **init}, keypoint_map, self.intrinsics)
+        self.depth_guess = self.depth_valid = self.tried_both = self.chosen = self.camera_rows = self.final_loss = None
+        self.camera_rounds = []
         self.log, self.rounds, self.frame_iterations, self.frame_loss = [], [], [], []
 
     def _set_extra(self, si, w_pose):
@@ -174,11 +237,93 @@ class InnerFitOP:
     def fitting(self, rows75, keypoints, log_every=0, jaw_init=None):
         """rows75 [N,75] initial parameters (device tensor or numpy), keypoints [N,23,3] (u, v, confidence) -- with a keypoint_map
         [N,len(map),3] in its order -- -> optimised rows [N,75] (device tensor).  fit_jaw: the jaw starts from jaw_init [N,3] (default
-        zero) and ends in self.jaw_pose [N,3] (device tensor)."""
+        zero) and ends in self.jaw_pose [N,3] (device tensor).
+        With init: rows75 may be None (neutral rows: all zero); of given rows everything but camera_translation is kept.  Leaves
+        self.depth_guess / depth_valid [N] (numpy), self.camera_rows [N,75] (the rows after the camera stage), self.tried_both [N]
+        (numpy bool), self.chosen [N] (numpy, 1: the turned body won), self.camera_rounds (L-BFGS: the camera stages' evaluations) and, when a
+        twin was tried, self.final_loss [N + twins] (device: the full objective under the last stage);
+        self.rounds / frame_iterations / frame_loss / body_rotation_rec then cover the N frames followed by the twins."""
+        if self.init is None:
+            if rows75 is None:
+                raise capi.FdcapError("fitting(None, ...) needs init: without it the rows must already stand in front of the camera")
+            return self._fit(self.n, rows75, keypoints, log_every, jaw_init)
+        return self._fit_from_keypoints(rows75, keypoints, log_every, jaw_init)
+
+    def _tensor(self, a):
+        import torch
+        return (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))).to(self.device, torch.float32).contiguous()
+
+    def _camera_stage(self, n, rows75, kp, guess):
+        """n problems: [the depth guess into camera_translation,] the camera stage -> the rows after it (+ z, valid, side_view [n])"""
+        import torch
+        lib, h, dev = self.ctx.lib, self.ctx.handle, self.device
+        self._setup(n, rows75, kp)
+        fx, fy, cx, cy = self.intrinsics
+        sg = capi.Fit2dStage(fx, fy, cx, cy, self.rho, 1.0, 0.0, 0.0, 0.0)
+        ci = ctypes.byref(self.init)
+        found = None
+        if guess:
+            found = (torch.empty(n, device=dev), torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            capi.check(lib.fdcap_opt_fit2d_guess(h, ctypes.byref(sg), ci, *(capi.dptr(v) for v in found), capi.current_stream()), "fdcap_opt_fit2d_guess")
+        if self.optimizer == "lbfgs":
+            q = self.lbfgs
+            cf = capi.LbfgsConfig(capi.XDIM, q["history"], q["max_iter"], q["max_eval"], q["max_steps"], q["max_ls"], q["lr"],
+                                  q["tolerance_grad"], q["tolerance_change"], q["ftol"], q["gtol"])
+            rounds = ctypes.c_int32(0)
+            capi.check(lib.fdcap_opt_fit2d_camera_lbfgs(h, ctypes.byref(sg), ci, ctypes.byref(cf), self.max_rounds, ctypes.byref(rounds),
+                                                        capi.current_stream()), "fdcap_opt_fit2d_camera_lbfgs")
+            self.camera_rounds.append(int(rounds.value))
+        else:
+            capi.check(lib.fdcap_opt_reset_adam(h, capi.current_stream()), "fdcap_opt_reset_adam")
+            for it in range(self.iters_per_stage):
+                capi.check(lib.fdcap_opt_backward_fit2d_camera(h, ctypes.byref(sg), ci, 0, capi.current_stream()), "fdcap_opt_backward_fit2d_camera")
+                capi.check(lib.fdcap_opt_step_x(h, it + 1, capi.current_stream()), "fdcap_opt_step_x")
+        out = torch.empty(n, capi.PDIM, device=dev)
+        capi.check(lib.fdcap_opt_get_results(h, capi.dptr(out), None, None, capi.current_stream()), "fdcap_opt_get_results")
+        return out, found
+
+    def _fit_from_keypoints(self, rows75, keypoints, log_every, jaw_init):
         import torch
         lib, h, dev, n = self.ctx.lib, self.ctx.handle, self.device, self.n
-        t = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))).to(dev, torch.float32).contiguous()
-        rows75, kp = t(rows75), t(keypoints)
+        kp = self._tensor(keypoints)
+        start = torch.zeros(n, capi.PDIM, device=dev) if rows75 is None else self._tensor(rows75).clone()
+        if not self.stages:
+            raise capi.FdcapError("init needs at least one stage: the two fits of a frame are compared under the last one")
+        self.camera_rounds = []
+        rows, (z, valid, side) = self._camera_stage(n, start, kp, True)
+        self.depth_guess, self.depth_valid = z.cpu().numpy(), valid.cpu().numpy()            # (the one set-up synchronisation)
+        flagged = {"auto": side.cpu().numpy() != 0, "both": np.ones(n, bool), "given": np.zeros(n, bool)}[self.orientations]
+        self.tried_both, self.chosen, self.camera_rows = flagged, np.zeros(n, np.int32), rows
+        src = torch.from_numpy(np.flatnonzero(flagged).astype(np.int32)).to(dev)
+        m = int(src.shape[0])
+        if m == 0:
+            return self._fit(n, rows, kp, log_every, jaw_init)
+        # the twins: the same start at the guessed depth, the body turned, their own camera stage -- then all n + m through the stages
+        pick = src.long()
+        twin = start[pick].contiguous()
+        twin[:, 72:74], twin[:, 74] = 0.0, z[pick]
+        capi.check(lib.fdcap_fit2d_flip_orient(capi.dptr(twin), m, capi.current_stream()), "fdcap_fit2d_flip_orient")
+        twin, _ = self._camera_stage(m, twin, kp[pick].contiguous(), False)
+        jaw_all = None
+        if jaw_init is not None:
+            jaw0 = self._tensor(jaw_init)
+            jaw_all = torch.cat([jaw0, jaw0[pick]]).contiguous()
+        both = self._fit(n + m, torch.cat([rows, twin]).contiguous(), torch.cat([kp, kp[pick]]).contiguous(), log_every, jaw_all)
+        floss = torch.empty(n + m, device=dev)
+        capi.check(lib.fdcap_opt_fit2d_frame_loss(h, ctypes.byref(self._last_stage), capi.dptr(floss), capi.current_stream()), "fdcap_opt_fit2d_frame_loss")
+        out, chosen = torch.empty(n, capi.PDIM, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        jaw_out = torch.empty(n, 3, device=dev) if self.fit_jaw else None
+        capi.check(lib.fdcap_fit2d_select(capi.dptr(both), capi.dptr(floss), capi.dptr(src), n, m, capi.dptr(self.jaw_pose) if self.fit_jaw else None,
+                                          capi.dptr(out), capi.dptr(jaw_out), capi.dptr(chosen), capi.current_stream()), "fdcap_fit2d_select")
+        self.chosen, self.final_loss = chosen.cpu().numpy(), floss
+        if self.fit_jaw:
+            self.jaw_pose = jaw_out
+        return out
+
+    def _setup(self, n, rows75, kp):
+        """the optimiser state of n problems at these rows and keypoints"""
+        import torch
+        lib, h, dev = self.ctx.lib, self.ctx.handle, self.device
         nkp = 23 if self.keypoint_map is None else len(self.keypoint_map)
         if tuple(rows75.shape) != (n, capi.PDIM) or tuple(kp.shape) != (n, nkp, 3):
             raise capi.FdcapError(f"expected rows [{n},75] and keypoints [{n},{nkp},3]")
@@ -204,6 +349,15 @@ class InnerFitOP:
             capi.check(lib.fdcap_opt_set_keypoints(h, capi.dptr(kp), st), "fdcap_opt_set_keypoints")
         else:
             capi.check(lib.fdcap_opt_set_keypoints_mapped(h, capi.dptr(kp), st), "fdcap_opt_set_keypoints_mapped")
+
+    def _fit(self, n, rows75, keypoints, log_every, jaw_init):
+        """the stages over n problems from rows that stand in front of the camera"""
+        import torch
+        lib, h, dev = self.ctx.lib, self.ctx.handle, self.device
+        t = self._tensor
+        rows75, kp = t(rows75), t(keypoints)
+        self._setup(n, rows75, kp)
+        st = capi.current_stream()
         if self.fit_jaw:
             jaw0 = torch.zeros(n, 3, device=dev) if jaw_init is None else t(jaw_init)
             if tuple(jaw0.shape) != (n, 3):
@@ -218,7 +372,7 @@ class InnerFitOP:
                 kps = kp.clone()
                 kps[:, :, 2] *= torch.from_numpy(self.group_weights[si][self.group_of]).to(dev)
                 capi.check(lib.fdcap_opt_set_keypoints_mapped(h, capi.dptr(kps), capi.current_stream()), "fdcap_opt_set_keypoints_mapped")
-            sg = capi.Fit2dStage(fx, fy, cx, cy, self.rho, w_data, w_pose, w_shape, w_hand)
+            sg = self._last_stage = capi.Fit2dStage(fx, fy, cx, cy, self.rho, w_data, w_pose, w_shape, w_hand)
             if self.bend_prior is not None or self.fit_jaw:
                 self._set_extra(si, w_pose)
             if self.optimizer == "lbfgs":

@@ -597,6 +597,53 @@ int fdcap_opt_fit2d_lbfgs_stats(fdcap_ctx* ctx, int32_t* iterations_d, int32_t* 
  * to their last accepted point (rows, and the jaw when it is free); 0 when every frame had finished.  FDCAP_E_STATE before the first call. */
 int fdcap_opt_fit2d_lbfgs_rolled_back(fdcap_ctx* ctx, int32_t* n_frames);
 
+/* ---- the inner fit's start from keypoints alone (csrc/fdc_fit2d_init.h): SMPLify-X's depth guess, camera stage and 180-degree twin ----
+ * Outside the reference repository like the rest of the inner fit; every constant is the caller's (defaults: innerfit.py DEFAULT_INIT).
+ * A SLOT is an index into a frame's keypoint array: with fdcap_opt_set_keypoints the joint itself (0..22), with a keypoint map an
+ * entry of the map that is an SMPL-X joint.
+ *   edge [n_edge <= 4][2] : the torso edges of the depth guess, z = mean |G_a.t - G_b.t| / mean |((u_a - u_b) / fx, (v_a - v_b) / fy)|
+ *                           over the edges whose two confidences exceed conf_thr; no such edge (or a mean image length below 1e-6):
+ *                           z = default_depth and valid = 0
+ *   torso [n_torso <= 8]  : the keypoints of the camera stage's objective
+ *                           w_data^2 sum_{k, conf_k > conf_thr} [(u_k - kp_k.u)^2 + (v_k - kp_k.v)^2] + w_depth^2 (cam_t.z - z0)^2
+ *                           over global_orient (6 columns) and camera_translation (3) alone; z0: camera_translation's z at set-up
+ *   shoulder [2]          : side_view = both detected and closer than side_view_px in the image
+ * The three calls that take it return FDCAP_E_STATE for a batch of clips, a shard of a clip or before keypoints are set, FDCAP_E_ARG for
+ * n_edge outside 1..4, n_torso outside 1..8, a slot outside the keypoint array or on a surface point, or a non-finite setting. */
+typedef struct fdcap_fit2d_init {
+    int32_t n_edge, edge[4][2], n_torso, torso[8], shoulder[2];
+    float conf_thr, default_depth, side_view_px, w_data, w_depth;
+} fdcap_fit2d_init;
+/* One pose forward, then per frame camera_translation = (0, 0, z) -- nothing else of a row is written -- and, DEVICE [n_local], each
+ * optional: z_d (float), valid_d and side_view_d (int32). */
+int fdcap_opt_fit2d_guess(fdcap_ctx* ctx, const fdcap_fit2d_stage* stage, const fdcap_fit2d_init* init, float* z_d, int32_t* valid_d,
+                          int32_t* side_view_d, void* stream);
+/* One evaluation of the camera stage's objective and its gradient: nine columns of the rows' gradient, the other 69 written as exact
+ * zeros; fdcap_opt_get_grads / fdcap_opt_step_x work after it as after fdcap_opt_backward_fit2d (Adam from zero moments leaves a
+ * zero-gradient column where it is).  The body model runs at SET-UP only -- the first evaluation after fdcap_opt_set_inputs, after
+ * any other call that runs the model (fdcap_opt_fit2d_guess, fdcap_opt_backward_fit2d, ...: whatever may step the other columns), after a
+ * change of the torso list, or any call with log_terms & 2 -- which stores each torso joint's offset from the pelvis in the root's
+ * frame and z0.  A caller who writes the registered rows directly changes only the nine columns in between, or asks for set-up.  log_terms & 1: losses_d [0] = the
+ * data term, [1] = the depth term.  A free jaw is ignored and stays where it is. */
+int fdcap_opt_backward_fit2d_camera(fdcap_ctx* ctx, const fdcap_fit2d_stage* stage, const fdcap_fit2d_init* init, int32_t log_terms, void* stream);
+/* The camera stage with L-BFGS, shaped like fdcap_opt_fit2d_lbfgs (same polling, roll-back, fdcap_opt_fit2d_lbfgs_stats and
+ * fdcap_opt_fit2d_lbfgs_rolled_back afterwards): rounds of one evaluation (the first with set-up where it is due, as above) +
+ * fdcap_lbfgs_advance on the 78-wide rows.  A column
+ * whose gradient is exactly zero in every round keeps a zero direction, so the 69 fixed columns keep their bits. */
+int fdcap_opt_fit2d_camera_lbfgs(fdcap_ctx* ctx, const fdcap_fit2d_stage* stage, const fdcap_fit2d_init* init, const fdcap_lbfgs_config* cfg,
+                                 int32_t max_rounds, int32_t* rounds_out, void* stream);
+/* The FULL objective of fdcap_opt_backward_fit2d per frame at the current rows, under the current keypoints, map, jaw and
+ * fdcap_opt_set_fit2d_extra settings: floss_d DEVICE [n_local].  One evaluation (the gradients are that evaluation's afterwards). */
+int fdcap_opt_fit2d_frame_loss(fdcap_ctx* ctx, const fdcap_fit2d_stage* stage, float* floss_d, void* stream);
+/* rows75_d DEVICE [n, 75], in place: global_orient = log(R(global_orient) R_y(pi)), the body turned 180 degrees about its y. */
+int fdcap_fit2d_flip_orient(float* rows75_d, int32_t n, void* stream);
+/* The better of a frame's two fits.  rows_d [n + m, 75] and loss_d [n + m]: problems 0..n-1 the frames, problem n + i a twin of frame
+ * src_d [i] (int32 [m], ascending and unique; m may be 0, src_d then NULL); jaw_d [n + m, 3] optional with jaw_out_d [n, 3].  Per frame
+ * the twin is taken iff its loss is strictly lower, a NaN loss counting as +inf (both NaN: the frame's own): rows_out_d [n, 75],
+ * chosen_d int32 [n] (0 / 1, optional).  All DEVICE. */
+int fdcap_fit2d_select(const float* rows_d, const float* loss_d, const int32_t* src_d, int32_t n, int32_t m, const float* jaw_d,
+                       float* rows_out_d, float* jaw_out_d, int32_t* chosen_d, void* stream);
+
 /* Multi-GPU iteration tail with ONE collective per iteration (instead of an all-reduce before the
  * step and point-to-point halo messages after it):
  *   fdcap_opt_step_rows_and_pack : Adam on body_rotation_rec / camera_ext of the owned rows, then writes
