@@ -37,7 +37,8 @@ def load_smplx_npz(model_folder: str, gender: str = "neutral", num_pca_comps: in
         hands_componentsl=np.asarray(d["hands_componentsl"], dtype=np.float32)[:num_pca_comps],
         hands_componentsr=np.asarray(d["hands_componentsr"], dtype=np.float32)[:num_pca_comps],
         hands_meanl=np.asarray(d["hands_meanl"], dtype=np.float32),
-        hands_meanr=np.asarray(d["hands_meanr"], dtype=np.float32))
+        hands_meanr=np.asarray(d["hands_meanr"], dtype=np.float32),
+        faces=np.ascontiguousarray(d["f"], dtype=np.int64).astype(np.int32) if "f" in d.files else None)
 
 
 def load_vposer_snapshot(ckpt_dir: str) -> VPoserData:

@@ -52,6 +52,11 @@ class Fit2dInit(ctypes.Structure):
                 ("conf_thr", c_float), ("default_depth", c_float), ("side_view_px", c_float), ("w_data", c_float), ("w_depth", c_float)]
 
 
+class CollisionParams(ctypes.Structure):
+    """include/fdcap.h fdcap_collision_params: the cone's opening, the term's weight, pairs kept per frame, the every-pair checker."""
+    _fields_ = [("sigma", c_float), ("w_coll", c_float), ("capacity", c_int32), ("every_pair", c_int32)]
+
+
 class LbfgsConfig(ctypes.Structure):
     """include/fdcap.h fdcap_lbfgs_config: torch.optim.LBFGS's arguments + SMPLify-X's loop around optimizer.step()."""
     _fields_ = [("dim", c_int32), ("history", c_int32), ("max_iter", c_int32), ("max_eval", c_int32), ("max_steps", c_int32),
@@ -88,6 +93,10 @@ SYMBOLS = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "fdcap_chamfer_fwd_scene": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "fdcap_chamfer_bwd_scene": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_set_collision_mesh": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "fdcap_collision_eval": (c_int32, [c_void_p, c_void_p, c_int32, POINTER(CollisionParams), c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "fdcap_debug_collision_tree": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_set_nn_kernel": (c_int32, [c_int32]),
     "fdcap_vposer_decode": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fdcap_vposer_decode_bwd": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -148,6 +157,7 @@ SYMBOLS = {
     "fdcap_debug_keypoints3d": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_backward_fit2d": (c_int32, [c_void_p, POINTER(Fit2dStage), c_int32, c_void_p]),
     "fdcap_opt_set_fit2d_extra": (c_int32, [c_void_p, POINTER(Fit2dExtra)]),
+    "fdcap_opt_set_fit2d_collision": (c_int32, [c_void_p, POINTER(CollisionParams)]),
     "fdcap_opt_set_jaw": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_get_jaw": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_reset_adam": (c_int32, [c_void_p, c_void_p]),
@@ -338,6 +348,35 @@ class Context:
         check(self.lib.fdcap_set_keypoint_map(self.handle, j.shape[0], j.ctypes.data_as(POINTER(c_int32)), t.ctypes.data_as(POINTER(c_int32)),
                                               _fp(b)), "fdcap_set_keypoint_map")
         self.num_keypoints = j.shape[0]
+
+    def set_collision_mesh(self, faces, face_part=None, ignore=None):
+        """The mesh of the self-interpenetration term (ops.SelfCollision, the inner fit): faces [F,3]; face_part [F] in 0..63 or None;
+        ignore: the 64 x 64 bit matrix as [64] uint64 (innerfit.collision_filter) or None.  An empty `faces` clears it."""
+        f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        part = mat = None
+        if face_part is not None:
+            fp = np.asarray(face_part).reshape(-1)
+            if fp.shape[0] != f.shape[0]:
+                raise FdcapError("face_part must have one entry per face")
+            if fp.size and (fp.min() < 0 or fp.max() > 63):
+                raise FdcapError("a face's part must be in 0..63")
+            part = np.ascontiguousarray(fp, dtype=np.uint8)
+        if ignore is not None:
+            mat = np.ascontiguousarray(ignore, dtype=np.uint64).reshape(-1)
+            if mat.shape[0] != 64:
+                raise FdcapError("ignore must be [64] uint64: a 64 x 64 bit matrix")
+        check(self.lib.fdcap_set_collision_mesh(self.handle, f.shape[0], f.ctypes.data_as(c_void_p),
+                                                None if part is None else part.ctypes.data_as(c_void_p),
+                                                None if mat is None else mat.ctypes.data_as(c_void_p)), "fdcap_set_collision_mesh")
+        self.num_faces = f.shape[0]
+
+    def collision_tree(self):
+        """-> (leaf size, order [leaves x leaf size]: tree position -> face id, -1 padding) of the registered collision mesh"""
+        info = (c_int32 * 4)()
+        check(self.lib.fdcap_debug_collision_tree(self.handle, info, None), "fdcap_debug_collision_tree")
+        order = np.empty(info[1] * info[2], dtype=np.int32)
+        check(self.lib.fdcap_debug_collision_tree(self.handle, info, order.ctypes.data_as(c_void_p)), "fdcap_debug_collision_tree")
+        return int(info[1]), order
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle:

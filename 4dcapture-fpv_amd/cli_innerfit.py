@@ -74,7 +74,14 @@ def main(argv=None, body_model=None, vposer=None):
     ap.add_argument("--vertex-ids", default=None, metavar="FILE", help="smplx's 21 vertex ids: adds the keypoints regressed from vertices")
     ap.add_argument("--fit-jaw", action="store_true")
     ap.add_argument("--frames-per-batch", type=int, default=DEFAULT_FRAMES_PER_BATCH)
+    ap.add_argument("--collision", action="store_true", help="penalise self-interpenetration of the model's faces in the last two stages")
+    ap.add_argument("--collision-parts", default=None, metavar="FILE", help=".npz with face_part [F] (0..63) and part_parent: a part is not "
+                    "tested against itself or its parent part")
     a = ap.parse_args(argv)
+    if a.collision_parts and not a.collision:
+        ap.error("--collision-parts belongs to --collision")
+    if a.collision and a.fit_jaw:
+        ap.error("--collision does not go with --fit-jaw")
 
     from . import assets, io
     from .innerfit import DEFAULT_INTRINSICS, InnerFitOP, KeypointMap
@@ -87,11 +94,20 @@ def main(argv=None, body_model=None, vposer=None):
     bm = body_model if body_model is not None else assets.load_smplx_npz(a.models)
     vp = vposer if vposer is not None else assets.load_vposer_snapshot(a.vposer)
     intrinsics = tuple(a.intrinsics) if a.intrinsics else DEFAULT_INTRINSICS
+    collision = None
+    if a.collision:
+        if getattr(bm, "faces", None) is None:
+            raise SystemExit("[ERROR][innerfit] --collision needs the model's faces (key `f` of the npz)")
+        collision = {}
+        if a.collision_parts:
+            parts = np.load(a.collision_parts)
+            collision = dict(face_part=parts["face_part"], part_parent=parts["part_parent"])
     rows, jaws, ops = [], [], {}
     for lo, hi in plan_frame_batches(len(files), a.frames_per_batch):
         n = hi - lo
         if n not in ops:                                     # (at most two sizes: the full batches and the remainder)
-            ops[n] = InnerFitOP(bm, vp, n, intrinsics=intrinsics, optimizer=a.optimizer, keypoint_map=kmap, fit_jaw=a.fit_jaw, init={})
+            ops[n] = InnerFitOP(bm, vp, n, intrinsics=intrinsics, optimizer=a.optimizer, keypoint_map=kmap, fit_jaw=a.fit_jaw, init={},
+                                collision=collision)
         rows.append(ops[n].fitting(None, kp[lo:hi]).cpu().numpy())
         if a.fit_jaw:
             jaws.append(ops[n].jaw_pose.cpu().numpy())

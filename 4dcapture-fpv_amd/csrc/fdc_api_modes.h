@@ -480,6 +480,78 @@ int fdcap_lbfgs_get_stats(fdcap_lbfgs* L, int32_t* it, int32_t* ev, float* loss,
     return (int)hipGetLastError();
 }
 
+// ---- the inner fit's self-interpenetration term (csrc/fdc_collide.h) ---------------------------------------------------------------
+int fdcap_opt_set_fit2d_collision(fdcap_ctx* c, const fdcap_collision_params* p) {
+    if (!c || !c->opt || opt_is_batch(c) || !opt_whole_clips(c->opt)) return FDCAP_E_STATE;
+    OptState* o = c->opt;
+    if (!p) { o->coll_on = false; return FDCAP_OK; }
+    if (!coll_params_ok(p->sigma, p->w_coll, p->capacity)) return FDCAP_E_ARG;
+    if (c->coll.h.F <= 0 || o->jaw_on) return FDCAP_E_STATE;  // no registered mesh; a free jaw (the full-mesh pass skins with the shut jaw's A)
+    o->coll = *p;
+    o->coll_on = p->w_coll != 0.f;                            // (weight 0: every value and gradient an exact zero -- no launch)
+    return FDCAP_OK;
+}
+
+namespace {
+// the second buffers: the first ones' shapes one behind the other, [dA R x 660 | dPF R x 496 | dtransl_v R x 3 | dMv R x 12 | dsv R]
+constexpr int COLL2_DPF = NJ * 12, COLL2_DT = COLL2_DPF + NPFX, COLL2_DM = COLL2_DT + 3, COLL2_DS = COLL2_DM + 12, COLL2_LD = COLL2_DS + 1;
+struct Coll2 { float *dA, *dPF, *dtv, *dMv, *dsv; };
+inline Coll2 coll2_view(float* b, int R) {
+    return Coll2{b, b + (size_t)R * COLL2_DPF, b + (size_t)R * COLL2_DT, b + (size_t)R * COLL2_DM, b + (size_t)R * COLL2_DS};
+}
+// first <- first + second, elementwise, for the five sums of the vertex branch of row row0 + blockIdx.x
+__global__ __launch_bounds__(256) void fit2d_coll_add_kernel(Coll2 s, int row0, float* __restrict__ dA, float* __restrict__ dPF,
+                                                             float* __restrict__ dtv, float* __restrict__ dMv, float* __restrict__ dsv) {
+    const size_t r = (size_t)(row0 + blockIdx.x);
+    for (int e = threadIdx.x; e < COLL2_LD; e += 256) {
+        float* d; const float* a;
+        if (e < COLL2_DPF) { d = dA + r * NJ * 12 + e; a = s.dA + r * NJ * 12 + e; }
+        else if (e < COLL2_DT) { d = dPF + r * NPFX + (e - COLL2_DPF); a = s.dPF + r * NPFX + (e - COLL2_DPF); }
+        else if (e < COLL2_DM) { d = dtv + r * 3 + (e - COLL2_DT); a = s.dtv + r * 3 + (e - COLL2_DT); }
+        else if (e < COLL2_DS) { d = dMv + r * 12 + (e - COLL2_DM); a = s.dMv + r * 12 + (e - COLL2_DM); }
+        else { d = dsv + r; a = s.dsv + r; }
+        *d = *d + *a;
+    }
+}
+// floss[frame] += the frame's value; losses[FDCAP_LOSS_FIT2D_COLLISION] = the frames' values added in frame order (both optional)
+__global__ __launch_bounds__(64) void fit2d_coll_value_kernel(const float* __restrict__ val, int n, float* __restrict__ floss, double* __restrict__ losses) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (floss && f < n) floss[f] += val[f];
+    if (losses && f == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < n; ++i) sum += (double)val[i];
+        losses[FDCAP_LOSS_FIT2D_COLLISION] = sum;
+    }
+}
+}  // namespace
+
+// The term's pass of one evaluation, after the pose forward and the data term: full-mesh blend and skinning forward over the n_local
+// rows, fdcap_collision_eval on the world vertices, skinning and blend backward.  second: the data term has assigned the vertex
+// branch's five sums, so these go to buffers of their own and one launch adds them on; else they are the only ones.
+static int fit2d_collision_pass(fdcap_ctx* c, bool second, double* losses, float* floss, hipStream_t st) {
+    OptState* o = c->opt;
+    const int nl = o->cfg.n_local, R = o->R, V = c->V;
+    const size_t nv3 = (size_t)3 * V;
+    { int e = ensure_full_set(c); if (e) return e; }
+    HIP_TRY(o->VoffF.ensure((size_t)R * nv3)); HIP_TRY(o->VwF.ensure((size_t)R * nv3)); HIP_TRY(o->dVF.ensure((size_t)R * nv3));
+    HIP_TRY(o->coll_loss.ensure(nl)); HIP_TRY(o->coll_count.ensure(nl));
+    if (second) HIP_TRY(o->coll2.ensure((size_t)R * COLL2_LD));
+    HIP_TRY(blend_forward(c->full, o->PF.p + 2 * NPFX, nl, o->VoffF.p + 2 * nv3, st));
+    note_form(form_name(F_SKIN_FWD));
+    hipLaunchKernelGGL(skin_fwd_kernel, dim3((V + 255) / 256, nl), dim3(256), 0, st, c->full.model(), V, o->X.p, XDIM, X_BETAS, X_TRANSL, o->VoffF.p,
+                       o->A.p, o->M.p, o->scale.p, 2, 1, o->VwF.p);
+    { int e = fdcap_collision_eval(c, o->VwF.p + 2 * nv3, nl, &o->coll, nullptr, o->coll_count.p, o->coll_loss.p, o->dVF.p + 2 * nv3, st); if (e) return e; }
+    const Coll2 first = {o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p};
+    const Coll2 t = second ? coll2_view(o->coll2.p, R) : first;
+    { int es = skin_bwd_any<false>(c->ws_skin, st, nl, c->full.model(), V, o->X.p, o->VoffF.p, o->A.p, o->M.p, o->scale.p, 2, o->dVF.p, o->dVF.p, t.dA,
+                                   (float*)nullptr, t.dtv, t.dMv, t.dsv, ContactGradIn()); if (es) return es; }
+    HIP_TRY(blend_backward(c->full, o->dVF.p + 2 * nv3, nl, t.dPF + 2 * NPFX, 0, c->ws_kpart, st));
+    if (second) hipLaunchKernelGGL(fit2d_coll_add_kernel, dim3(nl), dim3(256), 0, st, t, 2, first.dA, first.dPF, first.dtv, first.dMv, first.dsv);
+    if (floss || losses)
+        hipLaunchKernelGGL(fit2d_coll_value_kernel, dim3((nl + 63) / 64), dim3(64), 0, st, (const float*)o->coll_loss.p, nl, floss, losses);
+    return (int)hipGetLastError();
+}
+
 // one evaluation of the inner fit's objective: forward, loss (+ per-frame value), backward
 static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses, float* floss, hipStream_t st, bool fold) {
     OptState* o = c->opt;
@@ -487,6 +559,8 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
     Fit2dStage s = {sg->fx, sg->fy, sg->cx, sg->cy, sg->rho, sg->w_data, sg->w_pose, sg->w_shape, sg->w_hand};
     PoseModel pm = c->pose_model();
     if (o->jaw_on && !o->kp_mapped) return FDCAP_E_STATE;     // (no keypoint of the 23-joint layout follows the jaw)
+    const bool coll = o->coll_on;                             // (fdcap_opt_set_fit2d_collision; off: not one launch or argument differs)
+    if (coll && (o->jaw_on || c->coll.h.F <= 0)) return FDCAP_E_STATE;
     const JawIO jw = {o->jaw.p, o->jawR9.p, {o->w_jaw[0], o->w_jaw[1], o->w_jaw[2]}};
     const bool bend = o->bend.n > 0;                          // (fdcap_opt_set_fit2d_extra; off: not one launch or argument differs)
     int row_lo, row_hi;
@@ -520,17 +594,30 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
                                (float*)nullptr, (const float*)nullptr, (float*)nullptr);
         // the bending prior: its launch adds to the dPF the vertex branch left (the kernel's or blend_backward's), or -- a map of
         // joints 0..22 alone -- assigns the row, which pose_bwd_kernel then reads without the branch's other sums
-        if (bend && vb) hipLaunchKernelGGL(fit2d_bend_kernel<true>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
+        // the self-interpenetration term: its full-mesh pass adds to the vertex branch's sums, or -- no vertex branch -- leaves the only ones
+        if (coll) { int ec = fit2d_collision_pass(c, vb, losses, floss, st); if (ec) return ec; }
+        const bool vs = vb || coll;                               // the vertex branch's sums are there
+        if (bend && vs) hipLaunchKernelGGL(fit2d_bend_kernel<true>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
         else if (bend) hipLaunchKernelGGL(fit2d_bend_kernel<false>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
         hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
-                           o->Jrest.p, o->G.p, vb ? o->dA.p : (const float*)nullptr, (vb || bend) ? o->dPF.p : (const float*)nullptr, o->dJw.p,
-                           vb ? o->dMv.p : (const float*)nullptr, vb ? o->dsv.p : (const float*)nullptr,
-                           vb ? o->dPF.p + NPF : (const float*)nullptr, vb ? NPFX : 0, vb ? o->dtransl_v.p : (const float*)nullptr, o->dX.p, o->dO.p,
+                           o->Jrest.p, o->G.p, vs ? o->dA.p : (const float*)nullptr, (vs || bend) ? o->dPF.p : (const float*)nullptr, o->dJw.p,
+                           vs ? o->dMv.p : (const float*)nullptr, vs ? o->dsv.p : (const float*)nullptr,
+                           vs ? o->dPF.p + NPF : (const float*)nullptr, vs ? NPFX : 0, vs ? o->dtransl_v.p : (const float*)nullptr, o->dX.p, o->dO.p,
                            o->dCAM.p, o->dscale_row.p, ParamLossIn(), (const float*)nullptr);
         { int eb = opt_vposer_backward(c, fold, st); if (eb) return eb; }
         return (int)hipGetLastError();
     }
     hipLaunchKernelGGL(fit2d_loss_kernel, dim3(nl), dim3(128), 0, st, s, o->X.p, o->Jw.p, o->kp2d.p, 2, o->dX.p, o->dJw.p, losses, floss);
+    if (coll) {                                                 // the full-mesh pass's sums are the only vertex-branch sums: straight to the pose backward
+        { int ec = fit2d_collision_pass(c, false, losses, floss, st); if (ec) return ec; }
+        if (bend) hipLaunchKernelGGL(fit2d_bend_kernel<true>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
+        hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
+                           o->Jrest.p, o->G.p, (const float*)o->dA.p, (const float*)o->dPF.p, o->dJw.p, (const float*)o->dMv.p, (const float*)o->dsv.p,
+                           (const float*)(o->dPF.p + NPF), NPFX, (const float*)o->dtransl_v.p, o->dX.p, o->dO.p, o->dCAM.p, o->dscale_row.p, ParamLossIn(),
+                           (const float*)nullptr);
+        { int eb = opt_vposer_backward(c, fold, st); if (eb) return eb; }
+        return (int)hipGetLastError();
+    }
     if (bend) hipLaunchKernelGGL(fit2d_bend_kernel<false>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
     hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
                        o->Jrest.p, o->G.p, (const float*)nullptr, bend ? o->dPF.p : (const float*)nullptr, o->dJw.p, (const float*)nullptr,

@@ -735,4 +735,93 @@ int fdcap_smplx_backward(fdcap_ctx* c, const float* go, const float* bp, const f
     return (int)hipGetLastError();
 }
 
+// ---- Op 4: self-interpenetration (fdc_collide.h) -------------------------------------------------------------------------------------
+static int ensure_full_set(fdcap_ctx* c) {
+    if (c->full_ready) return FDCAP_OK;
+    std::vector<int64_t> all(c->V);
+    for (int i = 0; i < c->V; ++i) all[i] = i;
+    int e = build_skin_set(c, all, &c->full);
+    if (e) return e;
+    c->full_ready = true;
+    return FDCAP_OK;
+}
+
+int fdcap_set_collision_mesh(fdcap_ctx* c, int32_t n_faces, const int32_t* faces, const uint8_t* face_part, const uint64_t* ignore) {
+    if (!c || n_faces < 0) return FDCAP_E_ARG;
+    if (c->opt) return FDCAP_E_STATE;                  // (see fdcap_set_scene)
+    if (n_faces == 0) { c->coll.h = CollTables(); return FDCAP_OK; }
+    // FDCAP_COLL_LEAF=64: leaves of 64 faces instead of 32 (read at every registration; a mesh too large for 32 takes 64 anyway)
+    const char* lf = getenv("FDCAP_COLL_LEAF");
+    CollTables t;
+    if (coll_mesh_build(n_faces, faces, face_part, ignore, c->V, c->h_vt.data(), lf && !strcmp(lf, "64") ? 64 : 32, &t)) return FDCAP_E_ARG;
+    c->coll.h = CollTables();                          // (no mesh until the new tables are on the device)
+    HIP_TRY(c->coll.tri.upload(t.tri.data(), t.tri.size()));
+    HIP_TRY(c->coll.order.upload(t.order.data(), t.order.size()));
+    HIP_TRY(c->coll.ign.upload(t.ign.data(), t.ign.size()));
+    int e = ensure_full_set(c);                        // what the inner fit's full-mesh pass skins with
+    if (e) return e;
+    c->coll.h = std::move(t);
+    return FDCAP_OK;
+}
+
+// test / diagnosis: the registered mesh's tree: info4 = {F, leaf, NL, NLp}; order_out (may be NULL) [NL * leaf] tree position -> face id, -1 padding
+int fdcap_debug_collision_tree(fdcap_ctx* c, int32_t* info4, int32_t* order_out) {
+    if (!c || !info4) return FDCAP_E_ARG;
+    const CollTables& t = c->coll.h;
+    if (t.F <= 0) return FDCAP_E_STATE;
+    info4[0] = t.F; info4[1] = t.leaf; info4[2] = t.NL; info4[3] = t.NLp;
+    if (order_out) memcpy(order_out, t.order.data(), t.order.size() * sizeof(int32_t));
+    return FDCAP_OK;
+}
+
+int fdcap_collision_eval(fdcap_ctx* c, const float* verts, int32_t n, const fdcap_collision_params* p, int32_t* pairs, int32_t* count,
+                         float* loss, float* dverts, void* stream) {
+    if (!c || !verts || !p || !count || !loss || n <= 0) return FDCAP_E_ARG;
+    if (!coll_params_ok(p->sigma, p->w_coll, p->capacity)) return FDCAP_E_ARG;
+    fdcap_ctx::CollisionSet& cs = c->coll;
+    if (cs.h.F <= 0) return FDCAP_E_STATE;
+    const CollMesh m = cs.view();
+    const int V = c->V, cap = p->capacity, npos = m.NL * m.leaf;
+    const long long slots = (long long)n * cap, total = 6 * slots;
+    // the grouping's keys are frame x V + vertex in 32 bits, its positions ints
+    if (total > CB_MAX_SORT || (long long)n * V >= 0xffffffffLL || (long long)n * npos > 0x7fffffffLL) return FDCAP_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(cs.cnt.ensure((size_t)n * npos)); HIP_TRY(cs.list.ensure(2 * (size_t)slots)); HIP_TRY(cs.val.ensure((size_t)slots));
+    int2* const list = (int2*)cs.list.p;
+    if (p->every_pair) {
+        const dim3 g((npos + 255) / 256, n);
+        hipLaunchKernelGGL(coll_every_kernel<false>, g, dim3(256), 0, st, m, verts, V, cs.cnt.p, cap, list);
+        hipLaunchKernelGGL(coll_prefix_kernel, dim3(n), dim3(256), 0, st, cs.cnt.p, npos, count);
+        hipLaunchKernelGGL(coll_every_kernel<true>, g, dim3(256), 0, st, m, verts, V, cs.cnt.p, cap, list);
+    } else {
+        HIP_TRY(cs.nodes.ensure((size_t)n * 2 * m.NLp * 6));
+        const size_t lds = (size_t)2 * m.NLp * 6 * sizeof(float);
+        const dim3 g((m.NL + 3) / 4, n);
+        if (m.leaf == 64) {
+            hipLaunchKernelGGL(coll_refit_kernel<64>, dim3(n), dim3(256), lds, st, m, verts, V, cs.nodes.p);
+            hipLaunchKernelGGL((coll_search_kernel<64, false>), g, dim3(256), 0, st, m, verts, V, cs.nodes.p, cs.cnt.p, cap, list);
+            hipLaunchKernelGGL(coll_prefix_kernel, dim3(n), dim3(256), 0, st, cs.cnt.p, npos, count);
+            hipLaunchKernelGGL((coll_search_kernel<64, true>), g, dim3(256), 0, st, m, verts, V, cs.nodes.p, cs.cnt.p, cap, list);
+        } else {
+            hipLaunchKernelGGL(coll_refit_kernel<32>, dim3(n), dim3(256), lds, st, m, verts, V, cs.nodes.p);
+            hipLaunchKernelGGL((coll_search_kernel<32, false>), g, dim3(256), 0, st, m, verts, V, cs.nodes.p, cs.cnt.p, cap, list);
+            hipLaunchKernelGGL(coll_prefix_kernel, dim3(n), dim3(256), 0, st, cs.cnt.p, npos, count);
+            hipLaunchKernelGGL((coll_search_kernel<32, true>), g, dim3(256), 0, st, m, verts, V, cs.nodes.p, cs.cnt.p, cap, list);
+        }
+    }
+    if (dverts) { HIP_TRY(cs.grad.ensure(18 * (size_t)slots)); HIP_TRY(cs.dest.ensure((size_t)total)); }
+    hipLaunchKernelGGL(coll_penalty_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, m, verts, V, n, (const int*)count, cap,
+                       (const int2*)list, p->sigma, p->w_coll, cs.val.p, dverts ? cs.grad.p : nullptr, dverts ? cs.dest.p : nullptr, pairs);
+    hipLaunchKernelGGL(coll_frame_sum_kernel, dim3((n + 63) / 64), dim3(64), 0, st, cs.val.p, (const int*)count, n, cap, p->w_coll, loss);
+    if (dverts) {
+        HIP_TRY(cs.key.ensure(cb_key_words(total))); HIP_TRY(cs.sval.ensure(2 * (size_t)total));
+        int buf = 0;
+        HIP_TRY(cb_group(cs.dest.p, n, 6 * cap, V, true, cs.key.p, cs.sval.p, cs.key.p + 2 * (size_t)total, st, &buf));
+        const long long nd = (long long)n * V;
+        hipLaunchKernelGGL(coll_gather_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, cs.key.p + (size_t)buf * total,
+                           cs.sval.p + (size_t)buf * total, (int)total, cs.grad.p, nd, dverts);
+    }
+    return (int)hipGetLastError();
+}
+
 }  // extern "C"

@@ -180,6 +180,11 @@ struct OptState {
     int lbfgs_rolled_back = 0;                                 // frames the last fdcap_opt_fit2d_lbfgs call found inside a line search when its rounds ran out
     float w_jaw[3] = {0.f, 0.f, 0.f};                          // the jaw prior's weights (fdcap_opt_set_fit2d_extra)
     Fit2dBend bend = {};      // ... its bending prior (fdcap_opt_set_fit2d_extra): w_bend and the terms; n = 0: off
+    bool coll_on = false;     // ... its self-interpenetration term (fdcap_opt_set_fit2d_collision; off: not one launch or argument differs)
+    fdcap_collision_params coll = {};
+    DevBuf<float> coll_loss;  // ... the term's per-frame values [n_local]
+    DevBuf<int> coll_count;   // ... and pairs found [n_local]
+    DevBuf<float> coll2;      // ... the full-mesh pass's sums where the keypoint kernel has assigned the first buffers: dA | dPF | dtransl_v | dMv | dsv
     DevBuf<float> cam_setup;  // ... its camera stage (csrc/fdc_fit2d_init.h): per frame the torso's offsets, the pelvis base and z0 [n_local, CAM_SETUP_LD]
     bool cam_ready = false;   // ... they belong to the current rows and to cam_init's torso (fdcap_opt_set_inputs, any other pose forward: no longer)
     Fit2dInit cam_init = {};
@@ -304,6 +309,17 @@ struct fdcap_ctx {
     SkinSet full, contact;
     bool full_ready = false;
     KeypointSet kpset;             // fdcap_set_keypoint_map (h.n_kp = 0: no map)
+    // fdcap_set_collision_mesh (h.F = 0: no mesh): the faces in tree order, and fdcap_collision_eval's workspace (fdc_collide.h)
+    struct CollisionSet {
+        CollTables h;
+        DevBuf<int32_t> tri, order;
+        DevBuf<unsigned long long> ign;
+        DevBuf<float> nodes, val, grad;     // node boxes [n][2 NLp][6]; per kept pair its value and 18 gradient components
+        DevBuf<int> cnt, list, dest;        // per tree position pairs owned / their prefix; kept pairs {owner, other}; corner -> vertex
+        DevBuf<unsigned> key;               // the grouping's sort scratch (cb_key_words)
+        DevBuf<int> sval;
+        CollMesh view() const { return CollMesh{h.F, h.leaf, h.NL, h.NLp, h.H, (const int4*)tri.p, order.p, ign.p}; }
+    } coll;
     KpSet kp_view() const {
         const KeypointSet& k = kpset;
         return KpSet{k.h.n_kp, k.h.nr, k.h.np, k.K, k.ss.ldp, k.kjoint.p, k.kref.p, k.kbary.p, k.vl_start.p, k.vl_k.p, k.vl_w.p, k.jl_start.p, k.jl_k.p,

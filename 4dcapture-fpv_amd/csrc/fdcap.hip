@@ -33,6 +33,7 @@ __device__ unsigned long long g_fr_times[3][2048 * 8];
 #include "fdc_own.h"         // DevBuf, PinnedBuf, DevEvent(s): who owns device memory and events (ahead of fdc_scene.h, which uses it)
 #include "fdc_chamfer.h"
 #include "fdc_chamfer_bwd.h"
+#include "fdc_collide.h"
 #include "fdc_comm.h"
 #include "fdc_dct.h"
 #include "fdc_fit2d.h"

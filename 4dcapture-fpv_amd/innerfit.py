@@ -52,6 +52,45 @@ DEFAULT_INIT = dict(edges=((16, 1), (17, 2)), torso=(16, 17, 1, 2), shoulders=(1
                     w_data=None, w_depth=100.0)
 MAX_INIT_EDGES, MAX_INIT_TORSO = 4, 8       # fdcap_fit2d_init's lists
 
+# The self-interpenetration term (csrc/fdc_collide.h): the cone's opening, the weight per stage (on in the last two), pairs kept per
+# frame, and which pairs of body parts are never tested (a part with itself, a part with its parent part, the listed pairs).
+# [upstream-recall: SMPLify-X's fit_smplx.yaml coll_loss_weights 0, 0, 0, 0.01, 1.0, penalize_outside / df_cone_height 0.5 with
+# torch-mesh-isect's DistanceFieldPenetrationLoss (sigma 0.5, point2plane false), max_collisions 128 per BVH query, and its
+# part_segm_fn / ign_part_pairs filter of a part against itself and its parent; neither package nor the segmentation file is part of
+# this repository: defaults a caller can replace through collision, never constants of a kernel]
+DEFAULT_COLLISION = dict(faces=None, face_part=None, part_parent=None, ignore_pairs=(), same_part=True, sigma=0.5,
+                         weights=(0.0, 0.0, 0.0, 0.01, 1.0), capacity=4096)
+COLLISION_PARTS = 64    # parts of include/fdcap.h's 64 x 64 bit matrix
+
+
+def collision_filter(face_part=None, part_parent=None, ignore_pairs=(), same_part=True):
+    """-> [64] uint64, the 64 x 64 bit matrix of fdcap_set_collision_mesh: bit b of row a drops every pair of faces of parts a and b
+    (either way round).  Sets the listed `ignore_pairs` (a, b); with `same_part` a part with itself and -- `part_parent` [<= 64],
+    -1 for none -- a part with its parent part.  `face_part` limits `same_part` to the parts that occur (None: all 64).  Pure host code."""
+    m = [0] * COLLISION_PARTS
+
+    def put(a, b):
+        a, b = int(a), int(b)
+        if not (0 <= a < COLLISION_PARTS and 0 <= b < COLLISION_PARTS):
+            raise capi.FdcapError(f"a part must be in 0..{COLLISION_PARTS - 1}: ({a}, {b})")
+        m[a] |= 1 << b
+        m[b] |= 1 << a
+
+    for a, b in ignore_pairs:
+        put(a, b)
+    if same_part:
+        parts = range(COLLISION_PARTS) if face_part is None else sorted(set(int(p) for p in np.asarray(face_part).reshape(-1)))
+        for a in parts:
+            put(a, a)
+        if part_parent is not None:
+            pp = np.asarray(part_parent).reshape(-1)
+            if pp.shape[0] > COLLISION_PARTS:
+                raise capi.FdcapError(f"part_parent has more than {COLLISION_PARTS} entries")
+            for a, b in enumerate(pp):
+                if b >= 0:
+                    put(a, b)
+    return np.array(m, dtype=np.uint64)
+
 
 class KeypointMap:
     """Which body point each detected keypoint is (include/fdcap.h fdcap_set_keypoint_map): joint[k] >= 0 an SMPL-X joint, else the
@@ -143,7 +182,7 @@ class InnerFitOP:
     def __init__(self, body_model, vposer, num_frames, intrinsics=DEFAULT_INTRINSICS, rho=100.0, lr=0.01,
                  stages=DEFAULT_STAGES, iters_per_stage=30, optimizer="adam", lbfgs=None, max_rounds=4000,
                  keypoint_map=None, group_of=None, group_weights=None, fit_jaw=False, jaw_prior=None,
-                 bend_prior=None, init=None, orientations="auto"):
+                 bend_prior=None, init=None, orientations="auto", collision=None):
         """optimizer "adam": iters_per_stage steps of Adam(lr) per stage; "lbfgs": per frame and stage, SMPLify-X's L-BFGS loop
         with the settings `lbfgs` (keys of DEFAULT_LBFGS; missing ones take their defaults), at most max_rounds objective
         evaluations per stage.
@@ -160,13 +199,41 @@ class InnerFitOP:
         keys of DEFAULT_INIT (missing ones take their defaults; {} is all defaults): fitting() then starts as SMPLify-X does -- a depth
         guess from torso edge lengths, a camera stage over global_orient and camera_translation alone on the torso keypoints, and
         by `orientations` a twin problem per frame with the body turned 180 degrees about y, the fit with the lower final objective
-        kept: "auto" for the frames whose shoulders nearly coincide in the image, "both" for all, "given" for none."""
+        kept: "auto" for the frames whose shoulders nearly coincide in the image, "both" for all, "given" for none.
+        collision: None (off: not one more library call), or a dict with keys of DEFAULT_COLLISION (missing ones take their defaults):
+        the self-interpenetration term of csrc/fdc_collide.h on `faces` [F,3] (default: body_model.faces), weighted per stage by
+        `weights`; `face_part` [F] in 0..63, `part_parent`, `ignore_pairs` and `same_part` go through collision_filter.  Not with
+        fit_jaw: the full-mesh pass skins with the shut jaw."""
         import torch
+        self.collision = None
+        if collision is not None:                             # (checked before anything touches the device)
+            unknown = set(collision) - set(DEFAULT_COLLISION)
+            if unknown:
+                raise capi.FdcapError(f"unknown collision settings {sorted(unknown)}")
+            q = {**DEFAULT_COLLISION, **collision}
+            if fit_jaw:
+                raise capi.FdcapError("collision does not go with fit_jaw: the full-mesh pass skins with the shut jaw's transforms")
+            faces = q["faces"] if q["faces"] is not None else getattr(body_model, "faces", None)
+            if faces is None:
+                raise capi.FdcapError("collision needs faces: the body model has none, pass collision=dict(faces=...)")
+            faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+            nv = int(np.asarray(body_model.v_template).shape[0])
+            if not 3 <= faces.shape[0] <= 65535 or faces.min() < 0 or faces.max() >= nv:
+                raise capi.FdcapError("collision: 3 .. 65535 faces with vertex indices inside the body model")
+            w = tuple(float(v) for v in q["weights"])
+            if len(w) != len(tuple(stages)) or any(not (v >= 0.0 and np.isfinite(v)) for v in w):
+                raise capi.FdcapError("collision weights: one finite weight >= 0 per stage")
+            if not 0.0 < float(q["sigma"]) < 1.0 or int(q["capacity"]) <= 0:
+                raise capi.FdcapError("collision: sigma in (0, 1) and capacity > 0")
+            ign = collision_filter(q["face_part"], q["part_parent"], q["ignore_pairs"], q["same_part"]) if q["face_part"] is not None or q["ignore_pairs"] else None
+            self.collision = dict(faces=faces, face_part=q["face_part"], ignore=ign, sigma=float(q["sigma"]), weights=w, capacity=int(q["capacity"]))
         if not torch.cuda.is_available():
             raise capi.FdcapError("no HIP device: the fdcap_amd inner fit only runs on the GPU")
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.ctx = capi.Context(body_model, vposer)
         self.ctx.set_scene(np.zeros((0, 3), np.float32))
+        if self.collision is not None:
+            self.ctx.set_collision_mesh(self.collision["faces"], self.collision["face_part"], self.collision["ignore"])
         self.n = int(num_frames)
         self.intrinsics, self.rho, self.lr = tuple(float(v) for v in intrinsics), float(rho), float(lr)
         self.stages, self.iters_per_stage = tuple(stages), int(iters_per_stage)
@@ -375,6 +442,10 @@ class InnerFitOP:
             sg = self._last_stage = capi.Fit2dStage(fx, fy, cx, cy, self.rho, w_data, w_pose, w_shape, w_hand)
             if self.bend_prior is not None or self.fit_jaw:
                 self._set_extra(si, w_pose)
+            if self.collision is not None:                    # this stage's weight (0: the term is off, no launch)
+                q = self.collision
+                prm = capi.CollisionParams(q["sigma"], q["weights"][si], q["capacity"], 0)
+                capi.check(lib.fdcap_opt_set_fit2d_collision(h, ctypes.byref(prm)), "fdcap_opt_set_fit2d_collision")
             if self.optimizer == "lbfgs":
                 q = self.lbfgs
                 cf = capi.LbfgsConfig(capi.XDIM, q["history"], q["max_iter"], q["max_eval"], q["max_steps"], q["max_ls"], q["lr"],

@@ -237,6 +237,49 @@ class BodyModel:
         return self
 
 
+class _SelfCollisionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, verts, fctx, sigma, weight, capacity, every_pair):
+        n, V, _ = verts.shape
+        v = verts.contiguous()
+        dev = v.device
+        pairs = torch.empty(n, capacity, 2, device=dev, dtype=torch.int32)
+        count = torch.empty(n, device=dev, dtype=torch.int32)
+        loss = torch.empty(n, device=dev)
+        grad = torch.empty_like(v) if verts.requires_grad else None
+        prm = capi.CollisionParams(sigma, weight, capacity, 1 if every_pair else 0)
+        capi.check(fctx.lib.fdcap_collision_eval(fctx.handle, capi.dptr(v), n, prm, capi.dptr(pairs), capi.dptr(count), capi.dptr(loss),
+                                                 capi.dptr(grad), capi.current_stream()), "fdcap_collision_eval")
+        ctx.grad = grad
+        ctx.mark_non_differentiable(pairs, count)
+        return loss, pairs, count
+
+    @staticmethod
+    def backward(ctx, g, _gp, _gc):
+        return ctx.grad * g.reshape(-1, 1, 1), None, None, None, None, None
+
+
+class SelfCollision(torch.nn.Module):
+    """Self-interpenetration of the context's registered mesh (Context.set_collision_mesh): forward(verts [n,V,3]) -> the per-frame
+    penalty [n]; differentiable with respect to `verts` (the total derivative, computed with the forward by the library in a defined
+    order, so two calls give the same bits).  last_pairs [n,capacity,2] (registered face ids, -1 behind a frame's kept pairs) and
+    last_count [n] (pairs FOUND: above `capacity` the list overflowed) are the last call's.  `every_pair`: the tree-less checker."""
+
+    def __init__(self, ctx, sigma: float = 0.5, weight: float = 1.0, capacity: int = 4096, every_pair: bool = False):
+        super().__init__()
+        self.fctx = _ctx_of(ctx)
+        if not (0.0 < sigma < 1.0) or not (weight >= 0.0 and np.isfinite(weight)) or capacity <= 0:
+            raise capi.FdcapError("SelfCollision: sigma in (0, 1), a finite weight >= 0 and capacity > 0")
+        self.sigma, self.weight, self.capacity, self.every_pair = float(sigma), float(weight), int(capacity), bool(every_pair)
+        self.last_pairs = self.last_count = None
+
+    def forward(self, verts):
+        if verts.dim() != 3 or verts.shape[1] != self.fctx.num_verts or verts.shape[2] != 3 or verts.dtype != torch.float32:
+            raise capi.FdcapError(f"SelfCollision: verts must be float32 [n, {self.fctx.num_verts}, 3]")
+        loss, self.last_pairs, self.last_count = _SelfCollisionFn.apply(verts, self.fctx, self.sigma, self.weight, self.capacity, self.every_pair)
+        return loss
+
+
 def body_forward_from_params(ctx, params75: torch.Tensor, want_vertices=True):
     """[B,75] SMPLify-X rows -> (vertices [B,V,3], joints [B,55,3]) through VPoser + SMPL-X in one
     call (what global_vis.py:131-146 does per frame on the CPU)."""

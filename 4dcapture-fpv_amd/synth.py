@@ -69,20 +69,15 @@ class BodyModelData:
     hands_componentsr: np.ndarray  # [12,45]
     hands_meanl: np.ndarray     # [45]
     hands_meanr: np.ndarray     # [45]
+    faces: np.ndarray | None = None   # [F,3] int32 triangles (key `f` of the npz), where the file or the generator has them
 
     @property
     def num_verts(self) -> int:
         return int(self.v_template.shape[0])
 
 
-def make_body_model(num_verts: int = NUM_VERTS_SMPLX, seed: int = 0, lbs_nnz: int = 4) -> BodyModelData:
-    """`lbs_nnz`: non-zero skinning weights per vertex (nearest joints).  4 is the SURVEY §8d spec; the real SMPLX_NEUTRAL.npz
-    is not promised to be 4-sparse (global_optimization.py:154-168 loads whatever the file holds), so 8 / 12 exercise the
-    general-K skinning paths.  Every other array is identical for every lbs_nnz."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    J = _rest_skeleton()
-    parents = SMPLX_PARENTS
-    # vertices: points on capsules around each bone (parent -> child), radius by body part
+def _bones_and_radii(J, parents):
+    """The bones (parent joint, child joint), their padded lengths and the capsule radius by body part."""
     bones = [(int(parents[j]), j) for j in range(1, NUM_JOINTS)]
     lens = np.array([np.linalg.norm(J[c] - J[p]) + 0.03 for p, c in bones])
     radius = np.full(len(bones), 0.05)
@@ -95,29 +90,25 @@ def make_body_model(num_verts: int = NUM_VERTS_SMPLX, seed: int = 0, lbs_nnz: in
             radius[bi] = 0.075
         elif c in (15, 22, 23, 24):
             radius[bi] = 0.09
-    prob = lens * radius
-    prob = prob / prob.sum()
-    which = rng.choice(len(bones), size=num_verts, p=prob)
-    t = rng.random(num_verts)
-    ang = rng.random(num_verts) * 2.0 * math.pi
-    v = np.zeros((num_verts, 3))
-    for bi, (p, c) in enumerate(bones):
-        sel = np.nonzero(which == bi)[0]
-        if sel.size == 0:
-            continue
-        a, b = J[p], J[c]
-        d = b - a
-        n = np.linalg.norm(d)
-        d = d / n if n > 1e-9 else np.array([0.0, 1.0, 0.0])
-        e1 = np.cross(d, [0.0, 0.0, 1.0])
-        if np.linalg.norm(e1) < 1e-6:
-            e1 = np.cross(d, [1.0, 0.0, 0.0])
-        e1 /= np.linalg.norm(e1)
-        e2 = np.cross(d, e1)
-        tt = (t[sel] * 1.2 - 0.1)[:, None]
-        v[sel] = a + tt * (b - a) + radius[bi] * (np.cos(ang[sel])[:, None] * e1 +
-                                                  np.sin(ang[sel])[:, None] * e2)
-    # guarantee each joint has vertices close by (regressor rows stay local)
+    return bones, lens, radius
+
+
+def _bone_frame(a, b):
+    """Two unit vectors across the bone a -> b."""
+    d = b - a
+    n = np.linalg.norm(d)
+    d = d / n if n > 1e-9 else np.array([0.0, 1.0, 0.0])
+    e1 = np.cross(d, [0.0, 0.0, 1.0])
+    if np.linalg.norm(e1) < 1e-6:
+        e1 = np.cross(d, [1.0, 0.0, 0.0])
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(d, e1)
+    return e1, e2
+
+
+def _model_around(rng, v, J, parents, lbs_nnz, faces=None) -> BodyModelData:
+    """Blend shapes, joint regressor, skinning weights and hand tables for the vertices v [V,3] (float64)."""
+    num_verts = v.shape[0]
     v_template = v.astype(np.float32)
 
     shapedirs = (rng.standard_normal((num_verts, 3, 20)) * 0.01).astype(np.float32)
@@ -148,7 +139,73 @@ def make_body_model(num_verts: int = NUM_VERTS_SMPLX, seed: int = 0, lbs_nnz: in
         hands_componentsr=(rng.standard_normal((NUM_HAND_PCA, 45)) * 0.1).astype(np.float32),
         hands_meanl=(rng.standard_normal(45) * 0.1).astype(np.float32),
         hands_meanr=(rng.standard_normal(45) * 0.1).astype(np.float32),
+        faces=faces,
     )
+
+
+def make_body_model(num_verts: int = NUM_VERTS_SMPLX, seed: int = 0, lbs_nnz: int = 4) -> BodyModelData:
+    """`lbs_nnz`: non-zero skinning weights per vertex (nearest joints).  4 is the SURVEY §8d spec; the real SMPLX_NEUTRAL.npz
+    is not promised to be 4-sparse (global_optimization.py:154-168 loads whatever the file holds), so 8 / 12 exercise the
+    general-K skinning paths.  Every other array is identical for every lbs_nnz."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    J = _rest_skeleton()
+    parents = SMPLX_PARENTS
+    # vertices: points on capsules around each bone (parent -> child), radius by body part
+    bones, lens, radius = _bones_and_radii(J, parents)
+    prob = lens * radius
+    prob = prob / prob.sum()
+    which = rng.choice(len(bones), size=num_verts, p=prob)
+    t = rng.random(num_verts)
+    ang = rng.random(num_verts) * 2.0 * math.pi
+    v = np.zeros((num_verts, 3))
+    for bi, (p, c) in enumerate(bones):
+        sel = np.nonzero(which == bi)[0]
+        if sel.size == 0:
+            continue
+        a, b = J[p], J[c]
+        e1, e2 = _bone_frame(a, b)
+        tt = (t[sel] * 1.2 - 0.1)[:, None]
+        v[sel] = a + tt * (b - a) + radius[bi] * (np.cos(ang[sel])[:, None] * e1 +
+                                                  np.sin(ang[sel])[:, None] * e2)
+    return _model_around(rng, v, J, parents, lbs_nnz)
+
+
+def make_body_mesh(num_verts: int = NUM_VERTS_SMPLX, seed: int = 0, lbs_nnz: int = 4):
+    """A seeded body WITH a surface, for the self-interpenetration term's tests and timings: around every bone an open tube, its
+    vertices on a grid of rings x segments (ring and segment counts by the bone's share of `num_verts`, so the vertex count comes
+    close to `num_verts`, not onto it), the grid's triangles its faces.  Radii jitter by 3 % so that no two faces are coplanar.
+    -> (BodyModelData with .faces [F,3] int32, face_part [F] uint8: the bone's child joint folded into 0..63, part_parent [64] int32:
+    the part of the bone that ends where this one starts, -1 for none).  Tubes of neighbouring bones run through each other at the
+    joints, as a real body's parts meet there: innerfit.collision_filter(same_part=True, with parent) drops those pairs."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    J = _rest_skeleton()
+    parents = SMPLX_PARENTS
+    bones, lens, radius = _bones_and_radii(J, parents)
+    share = lens * radius / (lens * radius).sum() * num_verts
+    verts, faces, part = [], [], []
+    part_parent = np.full(64, -1, dtype=np.int32)
+    base = 0
+    for bi, (p, c) in enumerate(bones):
+        ring = max(3, int(round(math.sqrt(share[bi] * 2.0 * math.pi * radius[bi] / lens[bi]))))
+        rows = max(2, int(round(share[bi] / ring)))
+        a, b = J[p], J[c]
+        e1, e2 = _bone_frame(a, b)
+        tt = np.linspace(-0.1, 1.1, rows)[:, None, None]
+        ang = (rng.random() + np.arange(ring)) * (2.0 * math.pi / ring)
+        rad = radius[bi] * (1.0 + 0.03 * (2.0 * rng.random((rows, ring)) - 1.0))[:, :, None]
+        grid = a + tt * (b - a) + rad * (np.cos(ang)[None, :, None] * e1 + np.sin(ang)[None, :, None] * e2)
+        verts.append(grid.reshape(-1, 3))
+        r, k = np.meshgrid(np.arange(rows - 1), np.arange(ring), indexing="ij")
+        v00, v01 = base + r * ring + k, base + r * ring + (k + 1) % ring
+        v10, v11 = v00 + ring, v01 + ring
+        faces.append(np.concatenate([np.stack([v00, v01, v11], -1).reshape(-1, 3), np.stack([v00, v11, v10], -1).reshape(-1, 3)]))
+        part.append(np.full(2 * (rows - 1) * ring, c % 64, dtype=np.uint8))
+        if p > 0:
+            part_parent[c % 64] = p % 64
+        base += rows * ring
+    faces = np.ascontiguousarray(np.concatenate(faces), dtype=np.int32)
+    bm = _model_around(rng, np.concatenate(verts), J, parents, lbs_nnz, faces=faces)
+    return bm, np.concatenate(part), part_parent
 
 
 @dataclass

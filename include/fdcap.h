@@ -178,6 +178,37 @@ int fdcap_chamfer_bwd_both(fdcap_ctx* ctx, const float* xyz1_d, const float* xyz
                            const float* gdist1_d, const int32_t* idx1_d, const float* gdist2_d, const int32_t* idx2_d,
                            float* gxyz1_d, float* gxyz2_d, int32_t reduce2, void* stream);
 
+/* ---- Op 4: self-interpenetration of the body mesh (csrc/fdc_collide.h states the set, the order and the penalty in full) ---- */
+/* Registers the mesh whose faces are tested against each other, static per context like the contact set: faces [n_faces,3] vertex
+ * indices; face_part [n_faces] in 0..63 (NULL: all 0); ignore [64], a 64 x 64 bit matrix (NULL: none): bit (part[s], part[t]) or bit
+ * (part[t], part[s]) drops the pair {s, t}.  The faces are ordered once, by the template's face centroids, under a box tree whose shape
+ * never changes (leaves of 32 faces; FDCAP_COLL_LEAF=64, or a mesh above 32 768 faces: of 64).  Also readies the full-mesh vertex set.
+ * n_faces = 0 clears the mesh.  FDCAP_E_ARG: n_faces outside {0} and [3, 65535], a vertex index outside [0, V), a part above 63.
+ * FDCAP_E_STATE: a live optimiser (as scene registration). */
+int fdcap_set_collision_mesh(fdcap_ctx* ctx, int32_t n_faces, const int32_t* faces, const uint8_t* face_part, const uint64_t* ignore);
+typedef struct {
+    float sigma;        /* the cone's opening, in (0, 1) */
+    float w_coll;       /* weight of the term (not squared), finite and >= 0 */
+    int32_t capacity;   /* pairs kept per frame, > 0 */
+    int32_t every_pair; /* != 0: every pair of faces is tested, no tree (the checker: the same pairs, loss and gradient bit for bit) */
+} fdcap_collision_params;
+/* verts_d [n,V,3] world vertices -> per frame the pairs of faces that intersect and the penalty on them:
+ *   count_d [n]              pairs FOUND (above capacity: the frame's list overflowed and holds the first `capacity` in list order)
+ *   pairs_d [n,capacity,2]   or NULL: face ids as registered, the face earlier in tree order first, the list ordered by tree
+ *                            position (owner, then other); -1 behind the kept pairs
+ *   loss_d [n]               w_coll x (the kept pairs' values added in list order)
+ *   dverts_d [n,V,3]         or NULL: d loss / d verts, the total derivative (the receiving face's normal, circumcentre and radius
+ *                            move with its corners); per vertex its contributions added in ascending (list position, corner) order
+ * No float atomics: the same call gives the same bits.  A face with a non-finite corner or |e0 x e1|^2 <= 1e-30 is in no pair.
+ * Keeps no state between calls beyond workspace (context-owned, grown on demand: 4 bytes per face and frame, about 200 bytes per kept-pair slot
+ * with dverts_d).  FDCAP_E_ARG: a null ctx / verts_d / params / count_d / loss_d, n <= 0, sigma outside (0, 1), a negative or
+ * non-finite weight, capacity <= 0, 6 n capacity above 2^31 - 8193 or n V above 2^32 - 2.  FDCAP_E_STATE: no registered mesh. */
+int fdcap_collision_eval(fdcap_ctx* ctx, const float* verts_d, int32_t n, const fdcap_collision_params* params, int32_t* pairs_d,
+                         int32_t* count_d, float* loss_d, float* dverts_d, void* stream);
+/* test / diagnosis: the registered mesh's tree.  info4 = {faces, leaf size, leaves, leaves padded to a power of two}; order_out (may
+ * be NULL) [leaves x leaf size]: tree position -> face id, -1 behind the last face.  FDCAP_E_STATE: no registered mesh. */
+int fdcap_debug_collision_tree(fdcap_ctx* ctx, int32_t* info4, int32_t* order_out);
+
 /* Nearest-neighbour kernel selection for A/B measurement: 0 = by size (default), 1 = plain VALU
  * scan (nn_direct_kernel), 2 = MFMA-filtered exact scan (nn_mfma_kernel).  Both give bit-identical
  * results.  Process-wide. */
@@ -543,6 +574,17 @@ int fdcap_opt_set_jaw(fdcap_ctx* ctx, const float* jaw_d, void* stream);
 /* the jaw and -- optional -- the objective's gradient with respect to it at the last evaluation, DEVICE [n_local, 3] each (either may
  * be NULL, not both).  FDCAP_E_STATE: no free jaw; djaw_d before an evaluation. */
 int fdcap_opt_get_jaw(fdcap_ctx* ctx, float* jaw_d, float* djaw_d, void* stream);
+/* The inner fit's self-interpenetration term on the mesh of fdcap_set_collision_mesh; holds until the next call; params = NULL or
+ * w_coll == 0: off, and then not one launch or argument of an evaluation differs.  With it every evaluation (fdcap_opt_backward_fit2d,
+ * fdcap_opt_fit2d_lbfgs, fdcap_opt_fit2d_frame_loss) runs, after the pose forward and the data term, the full-mesh blend and skinning
+ * forward over the n_local rows, fdcap_collision_eval's steps on those world vertices (every_pair honoured) and the skinning and
+ * blend backward; the sums join the data term's before the bending prior and the pose backward.  A frame's value joins its
+ * objective (what the L-BFGS driver sees); log_terms != 0: losses_d [FDCAP_LOSS_FIT2D_COLLISION] = the frames' values, a slot the
+ * inner fit otherwise leaves at zero.  FDCAP_E_ARG: what fdcap_collision_eval refuses in params.  FDCAP_E_STATE: no optimiser, a
+ * batch of clips, one rank's share of a clip, no registered mesh, a FREE JAW (here, or at the evaluation when the jaw was freed
+ * later: the full-mesh pass skins with the transforms the pose kernels wrote, in which the jaw is shut). */
+#define FDCAP_LOSS_FIT2D_COLLISION 4
+int fdcap_opt_set_fit2d_collision(fdcap_ctx* ctx, const fdcap_collision_params* params);
 int fdcap_opt_reset_adam(fdcap_ctx* ctx, void* stream);
 
 /* ---- batched L-BFGS with a strong-Wolfe line search (csrc/fdc_lbfgs.h) ----
