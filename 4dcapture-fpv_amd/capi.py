@@ -97,6 +97,7 @@ SYMBOLS = {
     "fdcap_collision_eval": (c_int32, [c_void_p, c_void_p, c_int32, POINTER(CollisionParams), c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
     "fdcap_debug_collision_tree": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "fdcap_debug_collision_nodes": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "fdcap_set_nn_kernel": (c_int32, [c_int32]),
     "fdcap_vposer_decode": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fdcap_vposer_decode_bwd": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -377,6 +378,18 @@ class Context:
         order = np.empty(info[1] * info[2], dtype=np.int32)
         check(self.lib.fdcap_debug_collision_tree(self.handle, info, order.ctypes.data_as(c_void_p)), "fdcap_debug_collision_tree")
         return int(info[1]), order
+
+    def collision_nodes(self, verts):
+        """verts: device tensor [n,V,3] float32 -> the refit tree's boxes [n, 2 x padded leaves, 6] {lo, hi} (device; node 0 unspecified)"""
+        import torch
+        info = (c_int32 * 4)()
+        check(self.lib.fdcap_debug_collision_tree(self.handle, info, None), "fdcap_debug_collision_tree")
+        if verts.dim() != 3 or verts.shape[1] != self.num_verts or verts.shape[2] != 3 or verts.dtype != torch.float32:
+            raise FdcapError(f"verts must be float32 [n, {self.num_verts}, 3]")
+        out = torch.empty((verts.shape[0], 2 * info[3], 6), dtype=torch.float32, device=verts.device)
+        check(self.lib.fdcap_debug_collision_nodes(self.handle, dptr(verts), verts.shape[0], dptr(out), current_stream()),
+              "fdcap_debug_collision_nodes")
+        return out
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle:

@@ -774,6 +774,23 @@ int fdcap_debug_collision_tree(fdcap_ctx* c, int32_t* info4, int32_t* order_out)
     return FDCAP_OK;
 }
 
+// test / diagnosis: coll_refit_kernel alone on verts [n,V,3] -> nodes_out (device) [n][2 NLp][6] {lo, hi}; node 0 is whatever the
+// workspace held (the kernel never writes it)
+int fdcap_debug_collision_nodes(fdcap_ctx* c, const float* verts, int32_t n, float* nodes_out, void* stream) {
+    if (!c || !verts || !nodes_out || n <= 0) return FDCAP_E_ARG;
+    fdcap_ctx::CollisionSet& cs = c->coll;
+    if (cs.h.F <= 0) return FDCAP_E_STATE;
+    const CollMesh m = cs.view();
+    const size_t words = (size_t)n * 2 * m.NLp * 6;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(cs.nodes.ensure(words));
+    const size_t lds = (size_t)2 * m.NLp * 6 * sizeof(float);
+    if (m.leaf == 64) hipLaunchKernelGGL(coll_refit_kernel<64>, dim3(n), dim3(256), lds, st, m, verts, c->V, cs.nodes.p);
+    else hipLaunchKernelGGL(coll_refit_kernel<32>, dim3(n), dim3(256), lds, st, m, verts, c->V, cs.nodes.p);
+    HIP_TRY(hipMemcpyAsync(nodes_out, cs.nodes.p, words * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return (int)hipGetLastError();
+}
+
 int fdcap_collision_eval(fdcap_ctx* c, const float* verts, int32_t n, const fdcap_collision_params* p, int32_t* pairs, int32_t* count,
                          float* loss, float* dverts, void* stream) {
     if (!c || !verts || !p || !count || !loss || n <= 0) return FDCAP_E_ARG;

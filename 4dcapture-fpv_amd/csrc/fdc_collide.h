@@ -392,7 +392,8 @@ __global__ __launch_bounds__(256) void coll_refit_kernel(CollMesh m, const float
         for (int sh = 1; sh < LEAF; sh *= 2)
 #pragma unroll
             for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], sh)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], sh)); }
-        if (pos % LEAF == 0) {
+        // (the fold above runs on all 256 lanes; a tree of fewer than 256 positions -- F <= 128 -- has no leaf behind npos to store)
+        if (pos < npos && pos % LEAF == 0) {
             float* const b = coll_lds + 6 * (size_t)(m.NLp + pos / LEAF);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { b[k] = lo[k]; b[3 + k] = hi[k]; }

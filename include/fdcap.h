@@ -208,6 +208,10 @@ int fdcap_collision_eval(fdcap_ctx* ctx, const float* verts_d, int32_t n, const 
 /* test / diagnosis: the registered mesh's tree.  info4 = {faces, leaf size, leaves, leaves padded to a power of two}; order_out (may
  * be NULL) [leaves x leaf size]: tree position -> face id, -1 behind the last face.  FDCAP_E_STATE: no registered mesh. */
 int fdcap_debug_collision_tree(fdcap_ctx* ctx, int32_t* info4, int32_t* order_out);
+/* test / diagnosis: the tree's boxes refit to verts_d [n,V,3], the refit kernel alone.  nodes_out_d (DEVICE) [n][2 x padded leaves][6]:
+ * node i's {lo x y z, hi x y z} in heap numbering (root 1, leaf l = padded leaves + l); an empty node is {+inf, -inf}; node 0 is
+ * unspecified.  FDCAP_E_ARG: a null ctx / verts_d / nodes_out_d, n <= 0.  FDCAP_E_STATE: no registered mesh. */
+int fdcap_debug_collision_nodes(fdcap_ctx* ctx, const float* verts_d, int32_t n, float* nodes_out_d, void* stream);
 
 /* Nearest-neighbour kernel selection for A/B measurement: 0 = by size (default), 1 = plain VALU
  * scan (nn_direct_kernel), 2 = MFMA-filtered exact scan (nn_mfma_kernel).  Both give bit-identical

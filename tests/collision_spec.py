@@ -1,9 +1,10 @@
 """The self-interpenetration term as a twin (csrc/fdc_collide.h states the same in words): the collision set by testing every pair
 (numpy, fp64 or fp32), the penalty with torch autograd (fp64 or fp32), the face order of the registered tree.  Not a test itself:
-tests/test_collision_cpu.py and tests/test_gpu_collision.py check the header and the kernels against it.
+tests/test_collision_cpu.py, tests/test_gpu_collision.py and tests/test_gpu_collision_edges.py check the header and the kernels against it.
 
 Parity with SMPLify-X / torch-mesh-isect is UNPINNED (neither is available): the specification is restated from Tzionas et al.
 (IJCV 2016) and this file is the checker."""
+import functools
 import os
 import subprocess
 
@@ -49,6 +50,68 @@ def host_pairs(verts, faces, face_part, ignore, tmp_path):
     return {tuple(int(t) for t in ln.split()) for ln in lines}
 
 
+def _sweep_candidates(lo, hi, ids, axis, strict, chunk=1 << 22):
+    """the usable faces `ids` sorted by lo[axis]; face a's candidates are the faces b behind it in that order with lo_b <= hi_a
+    (strict: <, the mutant of tests/test_collision_cpu.py) -- lo_a <= lo_b <= hi_b gives the other half of the overlap on this axis --
+    -> yields (a, b) arrays of face ids whose boxes overlap on all three axes"""
+    o = ids[np.argsort(lo[ids, axis], kind="stable")]
+    lox, hix = lo[o, axis], hi[o, axis]
+    end = np.searchsorted(lox, hix, side="left" if strict else "right")           # the first position whose lo is > (strict: >=) hi_a
+    cnt = np.maximum(end - (np.arange(len(o)) + 1), 0)
+    other = [k for k in range(3) if k != axis]
+    a0 = 0
+    while a0 < len(o):
+        a1 = a0 + max(1, int(np.searchsorted(np.cumsum(cnt[a0:]), chunk, side="right")))
+        c = cnt[a0:a1]
+        ia = np.repeat(np.arange(a0, a1), c)
+        ib = np.arange(c.sum()) - np.repeat(np.cumsum(c) - c, c) + ia + 1
+        fa, fb = o[ia], o[ib]
+        for k in other:
+            keep = (lo[fa, k] <= hi[fb, k]) & (lo[fb, k] <= hi[fa, k])
+            fa, fb = fa[keep], fb[keep]
+        yield fa, fb
+        a0 = a1
+
+
+def sweep_pairs(verts, faces, face_part, ignore, tmp_path, strict=False):
+    """host_pairs' set without testing every pair (that takes 15 s at 16 512 faces and 52 s at 32 896): the predicate's steps in the header's
+    order, the cheap ones here and the 17 axes by the header itself.  (0) face_ok in fp32; (1) per-face fp32 boxes (min, max and <=
+    are exact, so numpy and the header cannot differ) and a sort-and-sweep along the axis that leaves the fewest candidates, the other
+    two axes compared directly; (2) shared vertex index; (3) the part matrix, either way round; (4) `coll_check sat` on what is left.
+    -> set of (i, j), i < j by face id.  strict: the sweep axis's overlap test made strict -- wrong, for the test that shows the sweep
+    is looked at."""
+    v = np.asarray(verts, np.float32)
+    faces = np.asarray(faces)
+    F = faces.shape[0]
+    P = v[faces]
+    with np.errstate(all="ignore"):
+        ids = np.nonzero(face_ok(P))[0]
+        lo, hi = P.min(1), P.max(1)
+    if len(ids) < 2:
+        return set()
+
+    def n_candidates(axis):
+        l = np.sort(lo[ids, axis])
+        return int(np.searchsorted(l, hi[ids, axis], side="right").sum())
+    axis = min(range(3), key=n_candidates)
+    part = np.zeros(F, np.int64) if face_part is None else np.asarray(face_part, np.int64)
+    ign = None if ignore is None else np.asarray(ignore, np.uint64)
+    bit = lambda a, b: (ign[a] >> b.astype(np.uint64)) & np.uint64(1)
+    A, B = [], []
+    for fa, fb in _sweep_candidates(lo, hi, ids, axis, strict):
+        keep = ~(faces[fa][:, :, None] == faces[fb][:, None, :]).any((1, 2))
+        if ign is not None:
+            keep &= (bit(part[fa], part[fb]) | bit(part[fb], part[fa])) == 0
+        A.append(fa[keep]); B.append(fb[keep])
+    A, B = np.concatenate(A), np.concatenate(B)
+    if len(A) == 0:
+        return set()
+    got = np.array([int(l) for l in run_host("sat", [np.array([len(A)], np.int32), np.concatenate([P[A], P[B]], 1)], tmp_path)])
+    assert not (got == 2).any(), "face_ok here and coll_face_ok in the header disagree"
+    i, j = np.minimum(A, B)[got == 1], np.maximum(A, B)[got == 1]
+    return {(int(a), int(b)) for a, b in zip(i, j)}
+
+
 # ---- the collision set ---------------------------------------------------------------------------------------------------------------
 def _axes(S, T):
     """S, T [N,3,3] -> axes [N,17,3] and the product of the lengths of the vectors each is a cross product of [N,17]"""
@@ -90,8 +153,8 @@ def sat(S, T, in_plane=True):
 
 def face_ok(P):
     """P [N,3,3] -> usable [N]"""
-    w = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
     with np.errstate(invalid="ignore", over="ignore"):
+        w = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
         return np.isfinite(P).all((1, 2)) & ((w * w).sum(-1) > DEGENERATE)
 
 
@@ -179,6 +242,38 @@ def pair_values(P, sigma, detach_receiver=False):
     return e
 
 
+TAG_ABOVE, TAG_RHO, TAG_OUTSIDE, TAG_DEEP, TAG_QUAD = range(5)
+TAG_NAMES = ("h >= sigma", "rho <= 0", "phi >= 1", "deep (h <= -sigma)", "quadratic")
+
+
+def psi_tags(P, sigma, dtype=torch.float64):
+    """P [N,6,3] (s0 s1 s2 t0 t1 t2), computed in `dtype` with _psi2's expressions -> tags [N,2,3] (pair, receiver: 0 = the first face,
+    intruder corner): which return of the header's coll_psi2 is taken, in its order -- TAG_ABOVE (h >= sigma: zero), TAG_RHO (rho <= 0:
+    zero), TAG_OUTSIDE (phi >= 1: zero), TAG_DEEP (Y's linear branch), TAG_QUAD (Y's quadratic branch).
+    TAG_RHO cannot be reached: rho = r (1 - h / sigma), and behind the first return h < sigma, while r > 0 for a usable face; only a
+    rounding of (r / sigma) h up to r itself, h within an ulp of sigma, could give it.  No case is asked to hit it."""
+    P = torch.as_tensor(np.asarray(P), dtype=dtype)
+    out = np.zeros((P.shape[0], 2, 3), np.int64)
+    for recv in (0, 1):
+        R, O = P[:, 3 * recv:3 * recv + 3], P[:, 3 * (1 - recv):3 * (1 - recv) + 3]
+        n, o, r = _field(R[:, 0], R[:, 1], R[:, 2])
+        for k in range(3):
+            d = O[:, k] - o
+            h = (n * d).sum(-1)
+            rho = r - (r / sigma) * h
+            t = d - h[..., None] * n
+            t2 = (t * t).sum(-1)
+            pos = t2 > 0
+            tn = torch.where(pos, torch.sqrt(torch.where(pos, t2, torch.ones_like(t2))), torch.zeros_like(t2))
+            phi = tn / torch.where(rho > 0, rho, torch.ones_like(rho))
+            tag = torch.where(h <= -sigma, TAG_DEEP, TAG_QUAD)
+            tag = torch.where(~(phi < 1), TAG_OUTSIDE, tag)
+            tag = torch.where(~(rho > 0), TAG_RHO, tag)
+            tag = torch.where(~(h < sigma), TAG_ABOVE, tag)
+            out[:, recv, k] = tag.numpy()
+    return out
+
+
 def penalty(verts, faces, pairs, sigma, w_coll, detach_receiver=False):
     """verts [n,V,3] torch (its dtype is the precision), pairs: per frame a list of (owner face, other face) -> E [n]"""
     faces = torch.as_tensor(np.asarray(faces), dtype=torch.long)
@@ -227,6 +322,28 @@ def face_order(v_template, faces, leaf_want=32):
     return leaf, NL, NLp, order
 
 
+def node_boxes(verts_frame, faces, order, leaf, NL, NLp):
+    """The refit's specification, numpy fp32 (min and max are exact): -> [2 NLp, 6] {lo, hi} in heap numbering (root 1, children 2 i and
+    2 i + 1, leaf l = node NLp + l).  A leaf's box is the min / max over the corners of its usable faces (face_ok), an upper node's the
+    min / max of its children's, an empty node's (+inf, -inf).  Node 0 is unspecified (here: empty)."""
+    v = np.asarray(verts_frame, np.float32)
+    order = np.asarray(order)
+    assert order.shape == (NL * leaf,) and NLp >= NL
+    box = np.empty((2 * NLp, 6), np.float32)
+    box[:, :3], box[:, 3:] = np.inf, -np.inf
+    with np.errstate(all="ignore"):
+        for l in range(NL):
+            ids = order[l * leaf:(l + 1) * leaf]
+            P = v[np.asarray(faces)[ids[ids >= 0]]]
+            P = P[face_ok(P)]
+            if len(P):
+                box[NLp + l, :3], box[NLp + l, 3:] = P.min((0, 1)), P.max((0, 1))
+    for i in range(NLp - 1, 0, -1):
+        box[i, :3] = np.minimum(box[2 * i, :3], box[2 * i + 1, :3])
+        box[i, 3:] = np.maximum(box[2 * i, 3:], box[2 * i + 1, 3:])
+    return box
+
+
 # ---- meshes the tests share ----------------------------------------------------------------------------------------------------------------
 def tube(center0, center1, radius, rings, around, phase=0.0):
     """an open tube from center0 to center1 -> verts [rings * around, 3] float32, faces [2 (rings - 1) around, 3]"""
@@ -254,6 +371,78 @@ def flat_grid(nx, ny, h=0.1):
     v00 = i * (ny + 1) + j
     f = np.concatenate([np.stack([v00, v00 + ny + 1, v00 + ny + 2], -1).reshape(-1, 3), np.stack([v00, v00 + ny + 2, v00 + 1], -1).reshape(-1, 3)])
     return v, f.astype(np.int32)
+
+
+def frames_of(verts, faces, n, moving):
+    """n frames that differ: the vertices `moving` shifted a little more in every frame"""
+    out = np.repeat(verts[None], n, 0).copy()
+    for f in range(n):
+        out[f, moving] += np.array([0.004, -0.003, 0.002], np.float32) * f
+    return out
+
+
+def crossing_tubes(rings=7, around=8, r=0.05):
+    va, fa = tube((-0.3, 0.0, 3.0), (0.3, 0.0, 3.0), r, rings, around)
+    vb, fb = tube((0.02, -0.3, 3.01), (0.0, 0.3, 3.03), r, rings, around, phase=0.2)
+    return np.concatenate([va, vb]), np.concatenate([fa, fb + len(va)]), np.arange(len(va), len(va) + len(vb))
+
+
+def bent_tube():
+    """a straight tube (the template) folded into a hairpin whose legs run through each other: faces far apart in tree order collide"""
+    rings, around, r = 41, 8, 0.04
+    vt, f = tube((0.0, 0.0, 3.0), (1.6, 0.0, 3.0), r, rings, around)
+    s = vt[:, 0].astype(np.float64)                                            # arc length along the axis
+    half = 0.8
+    off = vt.astype(np.float64) - np.stack([s, np.zeros_like(s), np.full_like(s, 3.0)], 1)
+    back = s > half
+    x = np.where(back, 2 * half - s, s)                                         # out, then back
+    y = np.where(back, 0.05 + 0.0 * s, 0.0)                                     # the return leg 0.05 beside the first: closer than 2 r
+    off[back, 0] *= -1
+    v = np.stack([x, y, np.full_like(s, 3.0)], 1) + off
+    v[:, 2] += 0.01 * np.sin(9 * s)                                             # no two legs exactly parallel
+    return vt, f, v.astype(np.float32)
+
+
+MESHES = ("tubes", "tubes64", "bent", "grid", "two_leaves_5", "one_leaf", "random")
+
+
+@functools.lru_cache(maxsize=None)
+def mesh_case(name):
+    """-> template [V,3], faces, frame vertices [V,3], indices that move from frame to frame"""
+    if name in ("tubes", "tubes64"):
+        v, f, mv = crossing_tubes()
+        assert len(f) == 2 * 96
+        return v, f, v, mv
+    if name == "bent":
+        vt, f, v = bent_tube()
+        return vt, f, v, np.arange(len(v) // 2, len(v))
+    if name == "grid":
+        v, f = flat_grid(6, 5)
+        return v, f, v, np.arange(10)
+    if name == "two_leaves_5":                                                  # F = 2 x 32 + 5
+        v, f, mv = crossing_tubes(rings=4, around=6)
+        f = np.concatenate([f[:36], f[36:69]])
+        assert len(f) == 69
+        return v, f, v, mv
+    if name == "one_leaf":
+        v, f, mv = crossing_tubes(rings=2, around=4, r=0.08)
+        assert len(f) == 16
+        return v, f, v, mv
+    if name == "random":                                                        # vertices unrelated to the template the tree was built on
+        vt, f, _ = crossing_tubes()
+        rng = np.random.Generator(np.random.PCG64(8))
+        v = (rng.standard_normal(vt.shape) * 0.08 + np.array([0.0, 0.0, 3.0])).astype(np.float32)
+        return vt, f, v, np.arange(0, len(v), 3)
+    raise KeyError(name)
+
+
+def long_tubes(rings, around=32, r=0.08):
+    """two tubes of 2 (rings - 1) around faces each that cross at right angles, both diagonal in x, y: no coordinate axis along which
+    one of them is a single heap of overlapping boxes (sweep_pairs, and the tree's boxes, see both spread out) -> verts, faces,
+    the second tube's vertices"""
+    va, fa = tube((-0.35, -0.35, 3.0), (0.35, 0.35, 3.0), r, rings, around)
+    vb, fb = tube((-0.33, 0.36, 3.02), (0.37, -0.34, 3.05), r, rings, around, phase=0.1)
+    return np.concatenate([va, vb]), np.concatenate([fa, fb + len(va)]), np.arange(len(va), len(va) + len(vb))
 
 
 # ---- the inner fit with the term ---------------------------------------------------------------------------------------------------------

@@ -282,3 +282,173 @@ def test_make_body_mesh_and_the_unchanged_body_model():
         assert _digest(bm2) == _digest(bm) and np.array_equal(bm2.faces, f) and np.array_equal(part2, part)
         assert _digest(synth.make_body_mesh(nv, seed=3, lbs_nnz=nnz)[0]) != _digest(bm)
     assert abs(synth.make_body_mesh(10475)[0].num_verts - 10475) < 200
+
+
+# ---- the twin's additions for tests/test_gpu_collision_edges.py ---------------------------------------------------------------------------
+def _case_digest(name):
+    h = hashlib.sha256()
+    vt, f, v, mv = spec.mesh_case(name)
+    for a in (vt, f, v, mv, spec.frames_of(v, f, 3, mv)):
+        a = np.ascontiguousarray(a)
+        h.update(str((a.dtype, a.shape)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def test_the_moved_mesh_builders_give_the_bytes_they_gave_in_the_gpu_module():
+    """digests of (template, faces, frame, moving, three frames of it) taken from tests/test_gpu_collision.py's builders before they
+    moved to tests/collision_spec.py"""
+    want = {"tubes": "8791fa45d59f93730db8208bb0bb533723f180eda50b32e3f8694d7ad682558f",
+            "tubes64": "8791fa45d59f93730db8208bb0bb533723f180eda50b32e3f8694d7ad682558f",
+            "bent": "44165e2be7c62fb3fb4facd0f876c692550065e9f500edc8633919dd471cd438",
+            "grid": "7b26691e9ab7ee5d156bd6aec4f44053323da6dfde8fc6c6f4fb4ca89bbddc41",
+            "two_leaves_5": "b870f2ecbe5a6754fbe4fb6362260d19d2c313ac979ef90988cd6bbea001b658",
+            "one_leaf": "72dbc002bf3ae1a7e0fdd859b572420f3296892f69cd8e61b8791871d6748a1b",
+            "random": "8f6b14695d5c5a040a32ff4bf64b1791b29daf12ab232fee2795bb4a05668cfa"}
+    assert set(want) == set(spec.MESHES)
+    assert {name: _case_digest(name) for name in spec.MESHES} == want
+
+
+@pytest.mark.parametrize("name", spec.MESHES)
+def test_sweep_pairs_equals_every_pair_on_the_host(name, tmp_path):
+    vt, faces, v0, moving = spec.mesh_case(name)
+    verts = spec.frames_of(v0, faces, 3, moving)
+    sizes = []
+    for f in (0, 2):
+        host = spec.host_pairs(verts[f], faces, None, None, tmp_path)
+        assert spec.sweep_pairs(verts[f], faces, None, None, tmp_path) == host
+        sizes.append(len(host))
+    print(name, "pairs", sizes)
+    assert name == "grid" or min(sizes) > 0
+
+
+def test_sweep_pairs_with_parts_a_matrix_and_unusable_faces(tmp_path):
+    vt, faces, v0, moving = spec.mesh_case("tubes")
+    verts = spec.frames_of(v0, faces, 2, moving)[1]
+    base = spec.host_pairs(verts, faces, None, None, tmp_path)
+    part = (np.arange(len(faces)) * 7 % 5).astype(np.uint8)
+    part[96:] += 40
+    a0, b0 = sorted(base)[0]
+    one_sided = np.zeros(64, np.uint64)
+    one_sided[int(part[b0])] = np.uint64(1) << np.uint64(int(part[a0]))
+    top = np.where(np.arange(len(faces)) < 96, 0, 63).astype(np.uint8)           # part 63 and bit 63
+    bit = lambda a, b: np.uint64(1) << np.uint64(b)
+    m63_0, m0_63, m63_63 = (np.zeros(64, np.uint64) for _ in range(3))
+    m63_0[63], m0_63[0], m63_63[63] = bit(63, 0), bit(0, 63), bit(63, 63)
+    for p, ign in ((part, innerfit.collision_filter(ignore_pairs=[(int(part[a0]), int(part[b0])), (0, 40)], same_part=False)), (part, one_sided),
+                   (part, None), (None, one_sided), (top, m63_0), (top, m0_63), (top, m63_63), (top[::-1].copy(), m63_63)):
+        host = spec.host_pairs(verts, faces, p, ign, tmp_path)
+        assert spec.sweep_pairs(verts, faces, p, ign, tmp_path) == host
+        if p is part and ign is not None:
+            assert 0 < len(host) < len(base)
+    assert spec.host_pairs(verts, faces, top, m63_0, tmp_path) == spec.host_pairs(verts, faces, top, m0_63, tmp_path) == \
+        {p for p in base if (p[0] < 96) == (p[1] < 96)}                          # either one-sided bit drops every cross-tube pair
+    # unusable faces: +inf, -inf, NaN, an exactly zero-area face, and a frame with no usable face
+    hit = sorted({i for p in base for i in p})
+    for k, (val, how) in enumerate(((np.inf, "coord"), (-np.inf, "coord"), (np.nan, "coord"), (None, "flat"))):
+        v = verts.copy()
+        f = faces[hit[k]]
+        if how == "coord":
+            v[f[0], 1] = val
+            gone = {int(i) for i in np.nonzero((faces == f[0]).any(1))[0]}
+        else:
+            v[f[1]] = v[f[0]]                                                    # the same position twice: e0 = 0 exactly
+            gone = {hit[k]}
+        host = spec.host_pairs(v, faces, None, None, tmp_path)
+        assert spec.sweep_pairs(v, faces, None, None, tmp_path) == host
+        assert not any(set(p) & gone for p in host) and len(host) > 0
+        if how == "coord":                                                       # (the moved corner of the flat face bends its neighbours)
+            assert host == {p for p in base if not set(p) & gone} and len(host) < len(base)
+    dead = np.full_like(verts, np.nan)
+    assert spec.sweep_pairs(dead, faces, None, None, tmp_path) == spec.host_pairs(dead, faces, None, None, tmp_path) == set()
+
+
+def test_sweep_pairs_a_strict_sweep_loses_boxes_that_touch(tmp_path):
+    """two faces that meet in the one point (4, 4, 0), where their boxes touch on all three axes (exact in fp32): a hit for the header,
+    kept by the sweep's <=, lost by the mutant's < whichever axis it sweeps"""
+    v = np.array([(0, 0, 0), (4, 4, 0), (0, 4, 0), (4, 4, 0), (8, 4, 0), (4, 8, 3), (20, 20, 20), (21, 20, 20), (20, 21, 20)], np.float32)
+    f = np.arange(9, dtype=np.int32).reshape(3, 3)
+    host = spec.host_pairs(v, f, None, None, tmp_path)
+    assert host == {(0, 1)}
+    assert spec.sweep_pairs(v, f, None, None, tmp_path) == host
+    assert spec.sweep_pairs(v, f, None, None, tmp_path, strict=True) == set()
+    # ... and on a mesh, where a strict sweep is otherwise right, faces moved to touch in this way are what it loses
+    vt, faces, v0, _ = spec.mesh_case("tubes")
+    vv = np.concatenate([v0, v[:6] + np.array([16, 16, 0], np.float32)])           # (clear of the tubes)
+    ff = np.concatenate([faces, f[:2] + len(v0)])
+    host = spec.host_pairs(vv, ff, None, None, tmp_path)
+    assert spec.sweep_pairs(vv, ff, None, None, tmp_path) == host
+    assert host - spec.sweep_pairs(vv, ff, None, None, tmp_path, strict=True) == {(len(faces), len(faces) + 1)}
+
+
+def _tube_pairs(f, tmp_path):
+    vt, faces, v0, moving = spec.mesh_case("tubes")
+    verts = spec.frames_of(v0, faces, f + 1, moving)[f]
+    pr = np.array(sorted(spec.host_pairs(verts, faces, None, None, tmp_path)))
+    return np.concatenate([verts[faces[pr[:, 0]]], verts[faces[pr[:, 1]]]], 1)
+
+
+def test_psi_tags_names_the_return_taken(tmp_path):
+    """the tubes' frame 0 (48 pairs x 6 intruders): sigma 0.5 never reaches the deep branch or the h >= sigma return, sigma 0.05 reaches all
+    four; the fp32 and the fp64 twin take the same return for every intruder of frames 0..2 at every sigma tried"""
+    P = _tube_pairs(0, tmp_path)
+    assert P.shape == (48, 6, 3)
+    count = lambda sigma: np.bincount(spec.psi_tags(P, sigma).reshape(-1), minlength=5).tolist()
+    assert count(0.5) == [0, 0, 75, 0, 213]
+    assert count(0.05) == [64, 0, 73, 19, 132]
+    for f in range(3):
+        Pf = _tube_pairs(f, tmp_path)
+        for sigma in (0.5, 0.05, 0.02, 0.01):
+            t64, t32 = spec.psi_tags(Pf, sigma), spec.psi_tags(Pf, sigma, torch.float32)
+            assert (t64 == t32).all() and not (t64 == spec.TAG_RHO).any(), (f, sigma)
+            # against the twin's own value: zero exactly where a zero return is named, per intruder
+            Pt = torch.tensor(Pf, dtype=torch.float64)
+            for recv in (0, 1):
+                R, O = Pt[:, 3 * recv:3 * recv + 3], Pt[:, 3 * (1 - recv):3 * (1 - recv) + 3]
+                n, o, r = spec._field(R[:, 0], R[:, 1], R[:, 2])
+                for k in range(3):
+                    val = spec._psi2(n, o, r, O[:, k], sigma).numpy()
+                    np.testing.assert_array_equal(val == 0, t64[:, recv, k] <= spec.TAG_OUTSIDE)
+    # by hand: a unit right triangle in z = 0 (circumcentre (0.5, 0.5, 0), r = 0.7071), intruders above its circumcentre
+    recv = np.array([(0, 0, 0), (1, 0, 0), (0, 1, 0)], float)
+    intr = np.array([(0.5, 0.5, 0.3), (0.5, 0.5, -0.3), (0.5, 0.5, 0.1)])       # sigma 0.2: above, deep, quadratic
+    tags = spec.psi_tags(np.concatenate([recv, intr])[None], 0.2)[0, 0]
+    assert tags.tolist() == [spec.TAG_ABOVE, spec.TAG_DEEP, spec.TAG_QUAD]
+    wide = np.array([(3.0, 0.5, 0.1), (0.5, 0.5, 0.1), (0.5, 0.5, 0.1)])         # beside the cone: phi >= 1
+    assert spec.psi_tags(np.concatenate([recv, wide])[None], 0.2)[0, 0, 0] == spec.TAG_OUTSIDE
+
+
+def test_node_boxes_by_hand_and_by_their_properties():
+    # by hand: five faces in leaves of two under a four-leaf tree; the face at x = 2 has a NaN corner
+    v = np.zeros((15, 3), np.float32)
+    for f in range(5):
+        v[3 * f:3 * f + 3] = np.array([(f, 0, 0), (f + 0.5, 0, 1), (f, 0.25, 0)])
+    v[7, 2] = np.nan
+    faces = np.arange(15, dtype=np.int32).reshape(5, 3)
+    order = np.array([0, 1, 2, 3, 4, -1], np.int32)
+    b = spec.node_boxes(v, faces, order, 2, 3, 4)
+    inf = np.inf
+    assert b.dtype == np.float32 and b.shape == (8, 6)
+    assert b[4].tolist() == [0, 0, 0, 1.5, 0.25, 1] and b[5].tolist() == [3, 0, 0, 3.5, 0.25, 1] and b[6].tolist() == [4, 0, 0, 4.5, 0.25, 1]
+    assert b[7].tolist() == [inf, inf, inf, -inf, -inf, -inf]
+    assert b[2].tolist() == [0, 0, 0, 3.5, 0.25, 1] and b[3].tolist() == b[6].tolist() and b[1].tolist() == [0, 0, 0, 4.5, 0.25, 1]
+    # properties on a mesh whose frame has nothing to do with the template
+    vt, faces, v0, _ = spec.mesh_case("random")
+    for leaf_want in (32, 64):
+        leaf, NL, NLp, order = spec.face_order(vt, faces, leaf_want)
+        v = v0.copy()
+        v[faces[order[0]][0], 0] = np.inf
+        b = spec.node_boxes(v, faces, order, leaf, NL, NLp)
+        ok = spec.face_ok(v[faces])
+        assert not ok.all()
+        P = v[faces[ok]]
+        assert b[1, :3].tolist() == P.min((0, 1)).tolist() and b[1, 3:].tolist() == P.max((0, 1)).tolist() and np.isfinite(b[1]).all()
+        for p, f in enumerate(order):
+            if f >= 0 and ok[f]:
+                node = NLp + p // leaf
+                while node >= 1:                                              # inside its leaf's box and every ancestor's
+                    assert (b[node, :3] <= v[faces[f]].min(0)).all() and (v[faces[f]].max(0) <= b[node, 3:]).all()
+                    node //= 2
+        assert (b[NLp + NL:, :3] == inf).all() and (b[NLp + NL:, 3:] == -inf).all()
+    dead = spec.node_boxes(np.full_like(v0, np.nan), faces, order, leaf, NL, NLp)
+    assert (dead[:, :3] == inf).all() and (dead[:, 3:] == -inf).all()

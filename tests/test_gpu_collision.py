@@ -6,7 +6,6 @@ and gradient are held at tests/gradient_bars.py's formula, the bar taken from th
 no marginal pair enters.  No bar is taken from a HIP result."""
 import ctypes
 import dataclasses
-import functools
 
 import numpy as np
 import pytest
@@ -55,34 +54,8 @@ def as_set(lst):
     return {(min(a, b), max(a, b)) for a, b in lst}
 
 
-def frames_of(verts, faces, n, moving):
-    """n frames that differ: the vertices `moving` shifted a little more in every frame"""
-    out = np.repeat(verts[None], n, 0).copy()
-    for f in range(n):
-        out[f, moving] += np.array([0.004, -0.003, 0.002], np.float32) * f
-    return out
-
-
-def crossing_tubes(rings=7, around=8, r=0.05):
-    va, fa = spec.tube((-0.3, 0.0, 3.0), (0.3, 0.0, 3.0), r, rings, around)
-    vb, fb = spec.tube((0.02, -0.3, 3.01), (0.0, 0.3, 3.03), r, rings, around, phase=0.2)
-    return np.concatenate([va, vb]), np.concatenate([fa, fb + len(va)]), np.arange(len(va), len(va) + len(vb))
-
-
-def bent_tube():
-    """a straight tube (the template) folded into a hairpin whose legs run through each other: faces far apart in tree order collide"""
-    rings, around, r = 41, 8, 0.04
-    vt, f = spec.tube((0.0, 0.0, 3.0), (1.6, 0.0, 3.0), r, rings, around)
-    s = vt[:, 0].astype(np.float64)                                            # arc length along the axis
-    half = 0.8
-    off = vt.astype(np.float64) - np.stack([s, np.zeros_like(s), np.full_like(s, 3.0)], 1)
-    back = s > half
-    x = np.where(back, 2 * half - s, s)                                         # out, then back
-    y = np.where(back, 0.05 + 0.0 * s, 0.0)                                     # the return leg 0.05 beside the first: closer than 2 r
-    off[back, 0] *= -1
-    v = np.stack([x, y, np.full_like(s, 3.0)], 1) + off
-    v[:, 2] += 0.01 * np.sin(9 * s)                                             # no two legs exactly parallel
-    return vt, f, v.astype(np.float32)
+# the meshes: tests/collision_spec.py holds them, for the CPU tests too
+from tests.collision_spec import MESHES, bent_tube, crossing_tubes, frames_of, mesh_case  # noqa: E402,F401
 
 
 def check_order(ctx, lst):
@@ -92,39 +65,6 @@ def check_order(ctx, lst):
     pos[order[order >= 0]] = np.nonzero(order >= 0)[0]
     keys = [(pos[a], pos[b]) for a, b in lst]
     assert all(a < b for a, b in keys) and keys == sorted(keys) and len(set(keys)) == len(keys)
-
-
-MESHES = ("tubes", "tubes64", "bent", "grid", "two_leaves_5", "one_leaf", "random")
-
-
-@functools.lru_cache(maxsize=None)
-def mesh_case(name):
-    """-> template [V,3], faces, frame vertices [V,3], indices that move from frame to frame"""
-    if name in ("tubes", "tubes64"):
-        v, f, mv = crossing_tubes()
-        assert len(f) == 2 * 96
-        return v, f, v, mv
-    if name == "bent":
-        vt, f, v = bent_tube()
-        return vt, f, v, np.arange(len(v) // 2, len(v))
-    if name == "grid":
-        v, f = spec.flat_grid(6, 5)
-        return v, f, v, np.arange(10)
-    if name == "two_leaves_5":                                                  # F = 2 x 32 + 5
-        v, f, mv = crossing_tubes(rings=4, around=6)
-        f = np.concatenate([f[:36], f[36:69]])
-        assert len(f) == 69
-        return v, f, v, mv
-    if name == "one_leaf":
-        v, f, mv = crossing_tubes(rings=2, around=4, r=0.08)
-        assert len(f) == 16
-        return v, f, v, mv
-    if name == "random":                                                        # vertices unrelated to the template the tree was built on
-        vt, f, _ = crossing_tubes()
-        rng = np.random.Generator(np.random.PCG64(8))
-        v = (rng.standard_normal(vt.shape) * 0.08 + np.array([0.0, 0.0, 3.0])).astype(np.float32)
-        return vt, f, v, np.arange(0, len(v), 3)
-    raise KeyError(name)
 
 
 @pytest.mark.parametrize("n", [1, 3])
