@@ -161,6 +161,9 @@ SYMBOLS = {
     "fdcap_opt_set_fit2d_collision": (c_int32, [c_void_p, POINTER(CollisionParams)]),
     "fdcap_opt_set_jaw": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_get_jaw": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_set_expression": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_get_expression": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_set_expression_prior": (c_int32, [c_void_p, c_float]),
     "fdcap_opt_reset_adam": (c_int32, [c_void_p, c_void_p]),
     "fdcap_lbfgs_create": (c_int32, [c_int32, POINTER(LbfgsConfig), POINTER(c_void_p)]),
     "fdcap_lbfgs_destroy": (None, [c_void_p]),

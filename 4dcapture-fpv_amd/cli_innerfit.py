@@ -1,11 +1,12 @@
 """Command line of the per-frame inner fit, from a detector's output to what global_optimization_hip.py reads:
 
     python3 innerfit_hip.py KEYPOINT_DIR BODY_PATH [--models DIR] [--vposer DIR] [--intrinsics FX FY CX CY] [--optimizer lbfgs|adam]
-                            [--hands] [--vertex-ids FILE] [--fit-jaw] [--frames-per-batch N]
+                            [--hands] [--vertex-ids FILE] [--fit-jaw] [--fit-expression] [--frames-per-batch N]
 
 KEYPOINT_DIR holds OpenPose's `*_keypoints.json`, one per frame (io.read_openpose_json; sorted by name).  Every frame starts from
 neutral rows: innerfit.InnerFitOP(init={}) makes the depth guess, runs the camera stage and tries the turned body where the
-shoulders nearly coincide.  Output: `<BODY_PATH>/results/frame_%06d/000.pkl` (io.write_body_gen), with `jaw_pose` under --fit-jaw.
+shoulders nearly coincide.  Output: `<BODY_PATH>/results/frame_%06d/000.pkl` (io.write_body_gen), with `jaw_pose` under --fit-jaw
+and `expression` under --fit-expression.
 
 The keypoint map holds the BODY_25 (with --hands: and hand) keypoints that are SMPL-X joints.  The keypoints smplx regresses from
 mesh vertices (nose, eyes, ears, toes, heels, fingertips) join it only when --vertex-ids names a file with smplx's 21 vertex ids
@@ -73,6 +74,7 @@ def main(argv=None, body_model=None, vposer=None):
     ap.add_argument("--hands", action="store_true", help="read and fit the hand keypoints too")
     ap.add_argument("--vertex-ids", default=None, metavar="FILE", help="smplx's 21 vertex ids: adds the keypoints regressed from vertices")
     ap.add_argument("--fit-jaw", action="store_true")
+    ap.add_argument("--fit-expression", action="store_true", help="fit SMPL-X's ten expression coefficients per frame (face keypoints see them)")
     ap.add_argument("--frames-per-batch", type=int, default=DEFAULT_FRAMES_PER_BATCH)
     ap.add_argument("--collision", action="store_true", help="penalise self-interpenetration of the model's faces in the last two stages")
     ap.add_argument("--collision-parts", default=None, metavar="FILE", help=".npz with face_part [F] (0..63) and part_parent: a part is not "
@@ -82,6 +84,8 @@ def main(argv=None, body_model=None, vposer=None):
         ap.error("--collision-parts belongs to --collision")
     if a.collision and a.fit_jaw:
         ap.error("--collision does not go with --fit-jaw")
+    if a.collision and a.fit_expression:
+        ap.error("--collision does not go with --fit-expression")
 
     from . import assets, io
     from .innerfit import DEFAULT_INTRINSICS, InnerFitOP, KeypointMap
@@ -102,17 +106,20 @@ def main(argv=None, body_model=None, vposer=None):
         if a.collision_parts:
             parts = np.load(a.collision_parts)
             collision = dict(face_part=parts["face_part"], part_parent=parts["part_parent"])
-    rows, jaws, ops = [], [], {}
+    rows, jaws, exprs, ops = [], [], [], {}
     for lo, hi in plan_frame_batches(len(files), a.frames_per_batch):
         n = hi - lo
         if n not in ops:                                     # (at most two sizes: the full batches and the remainder)
             ops[n] = InnerFitOP(bm, vp, n, intrinsics=intrinsics, optimizer=a.optimizer, keypoint_map=kmap, fit_jaw=a.fit_jaw, init={},
-                                collision=collision)
+                                collision=collision, fit_expression=a.fit_expression)
         rows.append(ops[n].fitting(None, kp[lo:hi]).cpu().numpy())
         if a.fit_jaw:
             jaws.append(ops[n].jaw_pose.cpu().numpy())
+        if a.fit_expression:
+            exprs.append(ops[n].expression.cpu().numpy())
     for op in ops.values():
         op.close()
-    io.write_body_gen(np.concatenate(rows), a.body_path, jaw_pose=np.concatenate(jaws) if a.fit_jaw else None)
+    io.write_body_gen(np.concatenate(rows), a.body_path, jaw_pose=np.concatenate(jaws) if a.fit_jaw else None,
+                      expression=np.concatenate(exprs) if a.fit_expression else None)
     print(f"[INFO][innerfit] {len(files)} frames -> {a.body_path}/results")
     return 0

@@ -278,6 +278,17 @@ int fdcap_set_keypoint_map(fdcap_ctx* c, int32_t n_kp, const int32_t* joint, con
     HIP_TRY(ks.wj.upload(wj.data(), wj.size())); HIP_TRY(ks.ww.upload(ww.data(), ww.size())); HIP_TRY(ks.vt.upload(vt.data(), vt.size()));
     HIP_TRY(ks.csc_start.upload(csc_start.data(), csc_start.size())); HIP_TRY(ks.csc_u.upload(csc_u.data(), csc_u.size()));
     HIP_TRY(ks.csc_w.upload(csc_w.data(), csc_w.size()));
+    if (!c->h_E10.empty()) {                           // the free expression's tables (fdcap_opt_set_expression)
+        const int lde = std::max(ldb, 4);
+        std::vector<float> es((size_t)NEXPR * lde, 0.f);
+        for (int u = 0; u < nu; ++u)
+            for (int e = 0; e < 3; ++e)
+                for (int l = 0; l < NEXPR; ++l)
+                    es[(size_t)l * lde + 3 * u + e] = u < nr ? c->h_E10[((size_t)3 * t.real_ids[u] + e) * NEXPR + l]
+                                                             : c->h_JE[(size_t)(3 * t.pseudo_joint[u - nr] + e) * NEXPR + l];
+        HIP_TRY(ks.E.upload(es.data(), es.size())); HIP_TRY(ks.JE.upload(c->h_JE.data(), c->h_JE.size()));
+        ks.lde = lde;
+    }
     ks.K = K;
     ks.h = std::move(t);                               // (last: a failure above leaves no map)
     return FDCAP_OK;
@@ -312,6 +323,19 @@ int fdcap_debug_keypoints3d(fdcap_ctx* c, float* out_d, void* stream) {
     opt_row_range(o, 1, &row_lo, &row_hi);
     int e = opt_pose_forward(c, row_lo, row_hi, st);
     if (e) return e;
+    if (o->expr_on) {                                         // (positions only: no gradient is written)
+        const ExprIO ex = c->expr_view(o->psi.p, nullptr, 0.f);
+        if (o->jaw_on)
+            hipLaunchKernelGGL((fit2d_kp_expr_jaw_kernel<true, false>), dim3(o->cfg.n_local), dim3(KP_NT), 0, st, Fit2dStage(), c->kp_view(), o->X.p, o->PF.p,
+                               o->A.p, o->M.p, o->scale.p, o->Jw.p, (const float*)nullptr, 2, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                               (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (double*)nullptr, (float*)nullptr, out_d,
+                               (const float*)nullptr, (float*)nullptr, JawIO{o->jaw.p, o->jawR9.p, {0.f, 0.f, 0.f}}, ex);
+        else
+            hipLaunchKernelGGL((fit2d_kp_expr_kernel<true, false>), dim3(o->cfg.n_local), dim3(KP_NT), 0, st, Fit2dStage(), c->kp_view(), o->X.p, o->PF.p,
+                               o->A.p, o->M.p, o->scale.p, o->Jw.p, (const float*)nullptr, 2, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                               (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (double*)nullptr, (float*)nullptr, out_d,
+                               (const float*)nullptr, (float*)nullptr, ex);
+    } else
     if (o->jaw_on)
         hipLaunchKernelGGL((fit2d_kp_jaw_kernel<true, false>), dim3(o->cfg.n_local), dim3(KP_NT), 0, st, Fit2dStage(), c->kp_view(), o->X.p, o->PF.p, o->A.p,
                            o->M.p, o->scale.p, o->Jw.p, (const float*)nullptr, 2, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,
@@ -393,6 +417,42 @@ int fdcap_opt_get_jaw(fdcap_ctx* c, float* jaw_d, float* djaw_d, void* stream) {
     return (int)hipGetLastError();
 }
 
+// ---- the free expression coefficients (csrc/fdc_keypoints.h) ------------------------------------------------------------------
+int fdcap_opt_set_expression(fdcap_ctx* c, const float* expr_d, void* stream) {
+    if (!c || !c->opt || opt_is_batch(c) || !opt_whole_clips(c->opt)) return FDCAP_E_STATE;
+    OptState* o = c->opt;
+    hipStream_t st = (hipStream_t)stream;
+    o->expr_eval = false;
+    if (!expr_d) { o->expr_on = false; return FDCAP_OK; }
+    if (c->h_E10.empty()) return FDCAP_E_STATE;               // (a model without expression directions: num_shape < 20)
+    for (int j = 1; j < NJ; ++j) if (c->h_parents[j] >= j) return FDCAP_E_ARG;         // (pose_forward's own condition: a joint follows its parent)
+    const size_t n = (size_t)o->cfg.n_local * NEXPR;
+    HIP_TRY(o->psi.ensure(n)); HIP_TRY(o->dpsi.ensure(n)); HIP_TRY(o->mPsi.ensure(n)); HIP_TRY(o->vPsi.ensure(n));
+    HIP_TRY(hipMemcpyAsync(o->psi.p, expr_d, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(o->dpsi.p, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o->mPsi.p, 0, n * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(o->vPsi.p, 0, n * sizeof(float), st));
+    o->expr_on = true;
+    return FDCAP_OK;
+}
+int fdcap_opt_get_expression(fdcap_ctx* c, float* expr_d, float* dexpr_d, void* stream) {
+    if (!c || !c->opt || !c->opt->expr_on) return FDCAP_E_STATE;
+    if (!expr_d && !dexpr_d) return FDCAP_E_ARG;
+    OptState* o = c->opt;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)o->cfg.n_local * NEXPR;
+    if (dexpr_d && !o->expr_eval) return FDCAP_E_STATE;      // (no evaluation since fdcap_opt_set_expression: no gradient)
+    if (expr_d) HIP_TRY(hipMemcpyAsync(expr_d, o->psi.p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (dexpr_d) HIP_TRY(hipMemcpyAsync(dexpr_d, o->dpsi.p, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return FDCAP_OK;
+}
+int fdcap_opt_set_expression_prior(fdcap_ctx* c, float w_expr) {
+    if (!c || !c->opt || opt_is_batch(c) || !opt_whole_clips(c->opt)) return FDCAP_E_STATE;
+    if (!std::isfinite(w_expr)) return FDCAP_E_ARG;
+    c->opt->w_expr = w_expr;
+    return FDCAP_OK;
+}
+
 // ---- batched L-BFGS (csrc/fdc_lbfgs.h) ------------------------------------------------------------------------------
 static int lbfgs_cfg_ok(const fdcap_lbfgs_config* cf) {
     return cf && cf->dim > 0 && cf->dim <= LB_DPAD && cf->history > 0 && cf->history <= LB_HMAX && cf->max_iter > 0 && cf->max_steps > 0 &&
@@ -415,6 +475,8 @@ int fdcap_lbfgs_create(int32_t n, const fdcap_lbfgs_config* cf, fdcap_lbfgs** ou
                                                  (int)lbfgs_lds_bytes(LB_HMAX));
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)lbfgs_advance_tail_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lbfgs_lds_bytes(LB_HMAX));
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)lbfgs_advance_expr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)lbfgs_lds_bytes(LB_HMAX));
     if (e == hipSuccess) { int r = fdcap_lbfgs_reset(L, nullptr); if (r == 0) e = hipDeviceSynchronize(); else e = (hipError_t)r; }
     if (e != hipSuccess) { fdcap_lbfgs_destroy(L); return (int)e; }
     *out = L;
@@ -432,13 +494,23 @@ int fdcap_lbfgs_reset(fdcap_lbfgs* L, void* stream) {
     return FDCAP_OK;
 }
 static int lbfgs_advance_impl(fdcap_lbfgs* L, float* x, int32_t x_stride, const float* f, const float* g, int32_t g_stride, int32_t* n_active,
-                              LbfgsFold fold, void* stream, JawGradIn tail = JawGradIn());
+                              LbfgsFold fold, void* stream, JawGradIn tail = JawGradIn(), ExprTail et = ExprTail());
 int fdcap_lbfgs_advance(fdcap_lbfgs* L, float* x, int32_t x_stride, const float* f, const float* g, int32_t g_stride, int32_t* n_active,
                         void* stream) {
     return lbfgs_advance_impl(L, x, x_stride, f, g, g_stride, n_active, LbfgsFold(), stream);
 }
 static int lbfgs_advance_impl(fdcap_lbfgs* L, float* x, int32_t x_stride, const float* f, const float* g, int32_t g_stride, int32_t* n_active,
-                              LbfgsFold fold, void* stream, JawGradIn tail) {
+                              LbfgsFold fold, void* stream, JawGradIn tail, ExprTail et) {
+    if (et.psi) {                                             // the wide tail: psi's ten columns (and the jaw's three) in their own arrays
+        const int row = L ? L->cf.dim - et.w : 0;
+        if (!L || !x || !f || !g || row < 64 || x_stride < row || g_stride < row) return FDCAP_E_ARG;
+        int* const cnt = L->active.p + (L->round & 1);
+        hipLaunchKernelGGL(lbfgs_advance_expr_kernel, dim3(L->n), dim3(LB_NT), lbfgs_lds_bytes(L->cf.hist), (hipStream_t)stream, L->cf, L->S.p, L->W.p,
+                           L->RO.p, x, x_stride, f, g, g_stride, cnt, L->active.p + ((L->round + 1) & 1), fold, et);
+        L->round++;
+        if (n_active) HIP_TRY(hipMemcpyAsync(n_active, cnt, sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return (int)hipGetLastError();
+    }
     const int in_row = L ? L->cf.dim - (tail.jaw ? 3 : 0) : 0;          // (the tail's three columns live in its own array)
     if (!L || !x || !f || !g || in_row <= 0 || x_stride < in_row || g_stride < in_row || (tail.jaw && in_row < 64)) return FDCAP_E_ARG;   // (the tail form keeps its three columns in a lane's second element)
     hipStream_t st = (hipStream_t)stream;
@@ -487,6 +559,7 @@ int fdcap_opt_set_fit2d_collision(fdcap_ctx* c, const fdcap_collision_params* p)
     if (!p) { o->coll_on = false; return FDCAP_OK; }
     if (!coll_params_ok(p->sigma, p->w_coll, p->capacity)) return FDCAP_E_ARG;
     if (c->coll.h.F <= 0 || o->jaw_on) return FDCAP_E_STATE;  // no registered mesh; a free jaw (the full-mesh pass skins with the shut jaw's A)
+    if (o->expr_on) return FDCAP_E_STATE;                     // ... free expression coefficients (the same reason: the pose kernels' A, at psi = 0)
     o->coll = *p;
     o->coll_on = p->w_coll != 0.f;                            // (weight 0: every value and gradient an exact zero -- no launch)
     return FDCAP_OK;
@@ -561,6 +634,8 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
     if (o->jaw_on && !o->kp_mapped) return FDCAP_E_STATE;     // (no keypoint of the 23-joint layout follows the jaw)
     const bool coll = o->coll_on;                             // (fdcap_opt_set_fit2d_collision; off: not one launch or argument differs)
     if (coll && (o->jaw_on || c->coll.h.F <= 0)) return FDCAP_E_STATE;
+    const bool expr = o->expr_on;                             // (fdcap_opt_set_expression; off: not one launch or argument differs)
+    if (expr && (!o->kp_mapped || coll || c->kpset.E.p == nullptr)) return FDCAP_E_STATE;      // (the 23-joint layout; the full-mesh pass skins at psi = 0)
     const JawIO jw = {o->jaw.p, o->jawR9.p, {o->w_jaw[0], o->w_jaw[1], o->w_jaw[2]}};
     const bool bend = o->bend.n > 0;                          // (fdcap_opt_set_fit2d_extra; off: not one launch or argument differs)
     int row_lo, row_hi;
@@ -573,6 +648,33 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
         // (kp_panel: the set's two blend products as panel products around it, kp_blend_by_panels)
         const bool vb = c->kpset.h.nu() > 0;
         if (o->jaw_on) { o->jaw_eval = true; o->jaw_gp = vb; }
+        if (expr) {
+            // the same three places with the expression forms: the kernel corrects A and Jw for psi itself, writes dA on every path
+            // (a map of joints 0..22 alone: only the rotation addends) and leaves d psi complete
+            const ExprIO ex = c->expr_view(o->psi.p, o->dpsi.p, o->w_expr);
+            o->expr_eval = true;
+            if (o->kp_panel) HIP_TRY(blend_forward(c->kpset.ss, o->PF.p + 2 * NPFX, nl, o->kpV.p, st));
+            const float* const vin = o->kp_panel ? o->kpV.p : nullptr;
+            float* const vout = o->kp_panel ? o->kpdV.p : nullptr;
+#define FDC_EXPR_LAUNCH(KERNEL, ...)                                                                                                             \
+            hipLaunchKernelGGL(KERNEL, dim3(nl), dim3(KP_NT), 0, st, s, c->kp_view(), o->X.p, o->PF.p, o->A.p, o->M.p, o->scale.p, o->Jw.p, o->kp2d.p, 2, \
+                               o->dX.p, o->dJw.p, o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, losses, floss, (float*)nullptr, vin, vout, __VA_ARGS__)
+            if (o->kp_panel && o->jaw_on) FDC_EXPR_LAUNCH((fit2d_kp_expr_jaw_kernel<false, true>), jw, ex);
+            else if (o->kp_panel) FDC_EXPR_LAUNCH((fit2d_kp_expr_kernel<false, true>), ex);
+            else if (o->jaw_on) FDC_EXPR_LAUNCH((fit2d_kp_expr_jaw_kernel<false, false>), jw, ex);
+            else FDC_EXPR_LAUNCH((fit2d_kp_expr_kernel<false, false>), ex);
+#undef FDC_EXPR_LAUNCH
+            if (o->kp_panel) HIP_TRY(blend_backward(c->kpset.ss, o->kpdV.p, nl, o->dPF.p + 2 * NPFX, 0, c->ws_kpart, st));
+            if (bend && vb) hipLaunchKernelGGL(fit2d_bend_kernel<true>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
+            else if (bend) hipLaunchKernelGGL(fit2d_bend_kernel<false>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
+            hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
+                               o->Jrest.p, o->G.p, (const float*)o->dA.p, (vb || bend) ? o->dPF.p : (const float*)nullptr, o->dJw.p,
+                               vb ? o->dMv.p : (const float*)nullptr, vb ? o->dsv.p : (const float*)nullptr,
+                               vb ? o->dPF.p + NPF : (const float*)nullptr, vb ? NPFX : 0, vb ? o->dtransl_v.p : (const float*)nullptr, o->dX.p, o->dO.p,
+                               o->dCAM.p, o->dscale_row.p, ParamLossIn(), (const float*)nullptr);
+            { int eb = opt_vposer_backward(c, fold, st); if (eb) return eb; }
+            return (int)hipGetLastError();
+        }
         if (o->kp_panel) {
             HIP_TRY(blend_forward(c->kpset.ss, o->PF.p + 2 * NPFX, nl, o->kpV.p, st));
             if (o->jaw_on)
@@ -638,6 +740,7 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap
     const int nl = o->cfg.n_local;
     fdcap_lbfgs_config cf = *cfg;
     cf.dim = o->jaw_on ? XDIM + 3 : XDIM;                     // a free jaw: [the row | the jaw], the last three in the jaw's own array
+    if (o->expr_on) cf.dim += NEXPR;                          // free expression: [the row | psi | the jaw], psi in its own array too
     if (!lbfgs_cfg_ok(&cf)) return FDCAP_E_ARG;
     if (o->lbfgs && (o->lbfgs->n != nl || o->lbfgs->cf.hist != cf.history)) { fdcap_lbfgs_destroy(o->lbfgs); o->lbfgs = nullptr; }
     if (!o->lbfgs) { int e = fdcap_lbfgs_create(nl, &cf, &o->lbfgs); if (e) return e; }
@@ -655,7 +758,9 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap
         LbfgsFold fold;
         fold.part = o->dZpart.p + (size_t)2 * VP_Z; fold.stride = (size_t)o->R * VP_Z; fold.col0 = X_LATENT; fold.n = VP_Z;
         e = lbfgs_advance_impl(L, o->X.p + 2 * XDIM, XDIM, o->floss.p, o->dX.p + 2 * XDIM, XDIM, nullptr, fold, st,
-                               o->jaw_on ? opt_jaw_grad_in(c) : JawGradIn());
+                               o->jaw_on && !o->expr_on ? opt_jaw_grad_in(c) : JawGradIn(),
+                               o->expr_on ? ExprTail{o->psi.p, o->dpsi.p, o->jaw_on ? opt_jaw_grad_in(c) : JawGradIn(), o->jaw_on ? NEXPR + 3 : NEXPR}
+                                          : ExprTail());
         if (e) break;
         ++rounds;
         if (rounds % poll == 0 || rounds == max_rounds) {
@@ -670,7 +775,8 @@ int fdcap_opt_fit2d_lbfgs(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const fdcap
     if (!e && rounds >= max_rounds && *L->active_h.p != 0) {
         o->lbfgs_rolled_back = *L->active_h.p;               // (a problem that is not finished waits inside a line search, a trial point in its row)
         if (o->jaw_on) hipLaunchKernelGGL(lbfgs_finalize_tail_kernel, dim3((nl + 63) / 64), dim3(64), 0, st, L->cf, L->S.p, L->W.p, o->jaw.p, nl);
-        e = lbfgs_finalize_impl(L, o->X.p + 2 * XDIM, XDIM, nullptr, o->jaw_on ? 3 : 0, st);
+        if (o->expr_on) hipLaunchKernelGGL(lbfgs_finalize_expr_kernel, dim3((nl + 63) / 64), dim3(64), 0, st, L->cf, L->S.p, L->W.p, o->psi.p, XDIM, nl);
+        e = lbfgs_finalize_impl(L, o->X.p + 2 * XDIM, XDIM, nullptr, (o->jaw_on ? 3 : 0) + (o->expr_on ? NEXPR : 0), st);
     }
     if (o->dz_pending) {                                      // leave dX complete, as every other backward of the API does
         hipLaunchKernelGGL(vposer_fold_dz_kernel, dim3((nl * VP_Z + 255) / 256), dim3(256), 0, st, o->dZpart.p, (size_t)o->R * VP_Z, 2, nl, o->dX.p);
@@ -752,6 +858,7 @@ static int fit2d_camera_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, const Fi
     hipLaunchKernelGGL(fit2d_camera_kernel, dim3(nl), dim3(64), 0, st, s, ci, o->X.p, o->cam_setup.p, o->kp2d.p, n_kp, 2, o->dX.p, losses, floss);
     o->dz_pending = false;                                    // (the latent's columns are zeros of this launch: no partial belongs to them)
     o->jaw_eval = false;                                      // (... and no gradient part to a free jaw: a step leaves it where it is)
+    o->expr_eval = false;                                     // (... nor to free expression coefficients)
     return (int)hipGetLastError();
 }
 
@@ -851,6 +958,10 @@ int fdcap_opt_reset_adam(fdcap_ctx* c, void* stream) {
     if (o->jaw_on) {
         HIP_TRY(hipMemsetAsync(o->mJaw.p, 0, (size_t)3 * o->cfg.n_local * sizeof(float), (hipStream_t)stream));
         HIP_TRY(hipMemsetAsync(o->vJaw.p, 0, (size_t)3 * o->cfg.n_local * sizeof(float), (hipStream_t)stream));
+    }
+    if (o->expr_on) {
+        HIP_TRY(hipMemsetAsync(o->mPsi.p, 0, (size_t)NEXPR * o->cfg.n_local * sizeof(float), (hipStream_t)stream));
+        HIP_TRY(hipMemsetAsync(o->vPsi.p, 0, (size_t)NEXPR * o->cfg.n_local * sizeof(float), (hipStream_t)stream));
     }
     return FDCAP_OK;
 }

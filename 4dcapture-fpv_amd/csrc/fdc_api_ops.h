@@ -147,6 +147,13 @@ int fdcap_ctx_create(const fdcap_model_desc* md, fdcap_ctx** out) {
     for (size_t i = 0; i < (size_t)V * 3; ++i)
         for (int l = 0; l < NBETA; ++l) c->h_S10[i * NBETA + l] = md->shapedirs[i * md->num_shape + l];
     c->h_lbs.assign(md->lbs_weights, md->lbs_weights + (size_t)V * NJ);
+    if (md->num_shape >= NBETA + NEXPR) {                 // the expression directions, kept for fdcap_set_keypoint_map's tables
+        c->h_E10.resize((size_t)V * 3 * NEXPR);
+        for (size_t i = 0; i < (size_t)V * 3; ++i)
+            for (int l = 0; l < NEXPR; ++l) c->h_E10[i * NEXPR + l] = md->shapedirs[i * md->num_shape + NBETA + l];
+        c->h_JE.resize((size_t)NJ * 3 * NEXPR);
+        expr_joint_dirs(V, c->h_E10.data(), md->J_regressor, c->h_JE.data());
+    }
     tr.mark("host copies of the model");
     {   // posedirs (61 MB for SMPL-X) goes straight to the device: vertex sets gather their blend matrix there (build_skin_set)
         hipError_t e_ = c->d_posedirs.upload(md->posedirs, (size_t)NPF * 3 * V);

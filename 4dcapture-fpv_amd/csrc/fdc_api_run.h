@@ -107,6 +107,12 @@ static int opt_step_x_impl(fdcap_ctx* c, int32_t step, hipStream_t st) {
                            o->mJaw.p, o->vJaw.p, adam_scalars(o->cfg.lr, step));
         o->jaw_eval = false;                                 // (consumed: a step after another mode's backward must not read this gradient's parts again)
     }
+    if (o->expr_on && o->expr_eval) {                        // the free expression coefficients: same lr, same step number, one small launch
+        const int ne = o->cfg.n_local * NEXPR;
+        hipLaunchKernelGGL(expr_adam_kernel, dim3((ne + 255) / 256), dim3(256), 0, st, o->psi.p, (const float*)o->dpsi.p, o->mPsi.p, o->vPsi.p, ne,
+                           adam_scalars(o->cfg.lr, step));
+        o->expr_eval = false;                                // (consumed)
+    }
     return (int)hipGetLastError();
 }
 

@@ -195,6 +195,91 @@ FDC_HD JawBwd jaw_backward(const JawFwd& f, const float* dAp) {
     return b;
 }
 
+// ---- the free expression (host and device) --------------------------------------------------------------------------------------
+// SMPL-X's expression coefficients psi [10] are ten more shape directions: v_shaped = v_template + S betas + E psi, and the joints
+// are regressed from v_shaped, so every joint's rest position moves by delta_j = JE_j psi (JE = J_regressor E, [55 3][10]).  The pose
+// forward ran at psi = 0; with (R_j, t_j) its chain (R_j = the rotation of A_j) and p the parent of j
+//     Dt_0 = delta_0,  Dt_j = Dt_p + R_p (delta_j - delta_p),   A_j.t += Dt_j - R_j delta_j,   Jw_j += W Dt_j  (j < 23)
+// which is the model itself, not an approximation.  The set's real vertices gain E_u psi in front of the skinning and a pseudo-vertex
+// delta_j; rotations and the pose feature stay.  The recursion is unrolled per joint -- Dt_j = delta_0 + the sum over j's path to the
+// root -- so that 55 lanes walk their own paths side by side and nobody waits for a level.
+// Backward, from d loss / d A' (the kernel's sums) and d loss / d Jw: own_j = dA'_j.t + W^T dJw_j is what reaches Dt_j directly, S_j
+// the sum of own over j's strict descendants -- S_j = the sum over j's children c of g_c, g_j = S_j + own_j, formed level by level from
+// the deepest (expr_subtree_children; lane j = joint j of one wave, as the pose backward's subtree sums) -- and
+//     d delta_j = -R_j^T (dA'_j.t + S_j) + (j > 0 ? R_p^T g_j : g_0)
+//     dA_j.R   += -dA'_j.t delta_j^T + sum over the children c of j of g_c (delta_c - delta_j)^T
+// pose_bwd_kernel then differentiates the unchanged chain from the augmented dA.  All sums in a fixed order.
+constexpr int NEXPR = 10;
+FDC_HD float expr_delta_entry(const float* JE, const float* psi, int e) {          // delta [55 3], entry e = 3 j + c
+    float acc = 0.f;
+    for (int l = 0; l < NEXPR; ++l) acc += JE[e * NEXPR + l] * psi[l];
+    return acc;
+}
+// Dt_j; A: [55][12] rows [R | t] (only the rotations are read)
+FDC_HD V3 expr_chain_shift(const float* A, const int* parents, const float* delta, int j) {
+    V3 acc = v3(0.f, 0.f, 0.f);
+    for (int a = j, p = parents[j]; p >= 0; a = p, p = parents[p]) {
+        const float* R = A + 12 * p;
+        const V3 d = v3(delta[3 * a] - delta[3 * p], delta[3 * a + 1] - delta[3 * p + 1], delta[3 * a + 2] - delta[3 * p + 2]);
+        acc = acc + v3(R[0] * d.x + R[1] * d.y + R[2] * d.z, R[4] * d.x + R[5] * d.y + R[6] * d.z, R[8] * d.x + R[9] * d.y + R[10] * d.z);
+    }
+    return acc + v3(delta[0], delta[1], delta[2]);
+}
+// joint j: A_j.t += Dt_j - R_j delta_j (reads rotations only, writes A_j's translation only: the joints run side by side); -> Dt_j
+FDC_HD V3 expr_forward(float* A, const int* parents, const float* delta, int j) {
+    const V3 dt = expr_chain_shift(A, parents, delta, j);
+    float* a = A + 12 * j;
+    const V3 d = v3(delta[3 * j], delta[3 * j + 1], delta[3 * j + 2]);
+    a[3] += dt.x - (a[0] * d.x + a[1] * d.y + a[2] * d.z);
+    a[7] += dt.y - (a[4] * d.x + a[5] * d.y + a[6] * d.z);
+    a[11] += dt.z - (a[8] * d.x + a[9] * d.y + a[10] * d.z);
+    return dt;
+}
+// S_j: g_c = S_c + own_c over the children c of j, ascending -- the children's S must be there: joints by level, the deepest first
+FDC_HD V3 expr_subtree_children(const int* child_start, const int* child_list, const float* own, const float* S, int j) {
+    V3 acc = v3(0.f, 0.f, 0.f);
+    for (int q = child_start[j]; q < child_start[j + 1]; ++q) {
+        const int c = child_list[q];
+        acc = acc + v3(S[3 * c] + own[3 * c], S[3 * c + 1] + own[3 * c + 1], S[3 * c + 2] + own[3 * c + 2]);
+    }
+    return acc;
+}
+// d delta_j; dA: [55][12] d loss / d A' (its translation column is read)
+FDC_HD V3 expr_backward_delta(const float* A, const int* parents, const float* own, const float* S, const float* dA, int j) {
+    const float* R = A + 12 * j;
+    const V3 s = v3(S[3 * j], S[3 * j + 1], S[3 * j + 2]);
+    const V3 g = s + v3(own[3 * j], own[3 * j + 1], own[3 * j + 2]);
+    const V3 v = v3(dA[12 * j + 3], dA[12 * j + 7], dA[12 * j + 11]) + s;
+    const V3 a = v3(R[0] * v.x + R[4] * v.y + R[8] * v.z, R[1] * v.x + R[5] * v.y + R[9] * v.z, R[2] * v.x + R[6] * v.y + R[10] * v.z);
+    const int p = parents[j];
+    if (p < 0) return g - a;
+    const float* P = A + 12 * p;
+    return v3(P[0] * g.x + P[4] * g.y + P[8] * g.z, P[1] * g.x + P[5] * g.y + P[9] * g.z, P[2] * g.x + P[6] * g.y + P[10] * g.z) - a;
+}
+// the addend to entry (i, col) of dA_j's rotation
+FDC_HD float expr_backward_rot_entry(const int* child_start, const int* child_list, const float* delta, const float* own, const float* S,
+                                     const float* dA, int j, int i, int col) {
+    float acc = -dA[12 * j + 4 * i + 3] * delta[3 * j + col];
+    for (int q = child_start[j]; q < child_start[j + 1]; ++q) {
+        const int c = child_list[q];
+        acc += (S[3 * c + i] + own[3 * c + i]) * (delta[3 * c + col] - delta[3 * j + col]);
+    }
+    return acc;
+}
+// JE = J_regressor E in double, as host_pose_setup builds Jd.  E10: [V 3][10] (shapedirs' columns 10..19), JE: [55 3][10]
+inline void expr_joint_dirs(int V, const float* E10, const float* J_regressor, float* JE) {
+    for (int j = 0; j < NJ; ++j)
+        for (int k = 0; k < 3; ++k) {
+            double d[NEXPR] = {0};
+            for (int v = 0; v < V; ++v) {
+                const double w = J_regressor[(size_t)j * V + v];
+                if (w == 0.0) continue;
+                for (int l = 0; l < NEXPR; ++l) d[l] += w * E10[((size_t)3 * v + k) * NEXPR + l];
+            }
+            for (int l = 0; l < NEXPR; ++l) JE[(3 * j + k) * NEXPR + l] = (float)d[l];
+        }
+}
+
 // One frame on the host, in the kernel's order: positions, data term and d loss / d keypoint, then the gradients of the set
 // vertices' positions (gvw [nu][3]) and of the 23 world joints (dJw [23][3]).  Returns the frame's data term.
 inline float kp_frame_host(const Fit2dStage& s, const KeypointTables& t, const float* Jw, const float* vw, const float* kp, float* pos,
@@ -273,6 +358,79 @@ struct JawIO { const float* jaw; float* R9; float w[3]; };
 #undef FDC_LB_TAIL_T
 #undef FDC_LB_TAIL_X2
 #undef FDC_LB_TAIL_GRAD
+
+// The free expression: the same text with FDC_KP_EXPR 1, without and with the jaw (fit2d_kp_expr_kernel, fit2d_kp_expr_jaw_kernel).
+// psi [frame][10] in, dpsi [frame][10] out -- complete when the kernel ends: the chain's share, the set vertices' through E (PANEL too:
+// blend_backward knows nothing of psi) and the prior w^2 |psi|^2, whose ten terms join `prior` on threads XDIM + 3 .. XDIM + 12.
+// E [10][lde]: per set vertex column 3 u + c the expression directions (a pseudo-vertex: JE_j's rows), JE [55 3][10]; the tree's arrays
+// (parents, children, each joint's level) are the pose model's.  A map of joints 0..22 alone still stages A and M, and dA is written on every
+// path: pose_bwd_kernel must be handed it.
+struct ExprIO {
+    const float* psi; float* dpsi; float w;
+    const float* E; int lde; const float* JE;
+    const int *parents, *child_start, *child_list, *depth; int nlevels;
+};
+#define FDC_KP_EXPR 1
+#define FDC_KP_KERNEL fit2d_kp_expr_kernel
+#define FDC_KP_JAW 0
+#include "fdc_keypoints_kernel.inc"
+#undef FDC_KP_KERNEL
+#undef FDC_KP_JAW
+#define FDC_KP_KERNEL fit2d_kp_expr_jaw_kernel
+#define FDC_KP_JAW 1
+#include "fdc_keypoints_kernel.inc"
+#undef FDC_KP_KERNEL
+#undef FDC_KP_JAW
+#undef FDC_KP_EXPR
+
+// The inner fit's L-BFGS with free expression coefficients: 88 unknowns per frame, or 91 with the jaw -- [the row's 78 | psi 10 | jaw 3],
+// the advance kernel's form with a tail of the width its argument carries.  psi's gradient is the array the data term's kernel left,
+// the jaw's is completed here as in the three-column form.
+struct ExprTail { float* psi; const float* dpsi; JawGradIn jg; int w; };       // w = 10, or 13 with jg.jaw
+__device__ __forceinline__ float expr_tail_ld(const ExprTail& t, int p, int c) {
+    return c < NEXPR ? t.psi[(size_t)p * NEXPR + c] : t.jg.jaw[(size_t)p * 3 + c - NEXPR];
+}
+__device__ __forceinline__ void expr_tail_st(const ExprTail& t, int p, int c, float v) {
+    if (c < NEXPR) t.psi[(size_t)p * NEXPR + c] = v;
+    else t.jg.jaw[(size_t)p * 3 + c - NEXPR] = v;
+}
+__device__ __forceinline__ float expr_tail_grad(const ExprTail& t, int p, int c) {
+    if (c < NEXPR) return t.dpsi[(size_t)p * NEXPR + c];
+    const V3 g = jaw_grad_frame(t.jg, p);
+    return c == NEXPR ? g.x : c == NEXPR + 1 ? g.y : g.z;
+}
+#define FDC_LB_KERNEL lbfgs_advance_expr_kernel
+#define FDC_LB_TAIL 2
+#define FDC_LB_TAIL_T ExprTail
+#define FDC_LB_TAIL_W(t) (t).w
+#define FDC_LB_TAIL_LD(t, p, c) expr_tail_ld(t, p, c)
+#define FDC_LB_TAIL_ST(t, p, c, v) expr_tail_st(t, p, c, v)
+#define FDC_LB_TAIL_G(t, p, c) expr_tail_grad(t, p, c)
+#include "fdc_lbfgs_advance.inc"
+#undef FDC_LB_KERNEL
+#undef FDC_LB_TAIL
+#undef FDC_LB_TAIL_T
+#undef FDC_LB_TAIL_W
+#undef FDC_LB_TAIL_LD
+#undef FDC_LB_TAIL_ST
+#undef FDC_LB_TAIL_G
+// ... and a stopped line search's starting point put back into psi (columns col0 .. col0 + 9 of the vector): launched BEFORE
+// lbfgs_finalize_kernel, as lbfgs_finalize_tail_kernel is for the jaw (the vector's last three columns)
+__global__ __launch_bounds__(64) void lbfgs_finalize_expr_kernel(LbfgsCfg cf, const LbfgsScalars* __restrict__ S, const float* __restrict__ W,
+                                                                float* __restrict__ psi, int col0, int n) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    const int phase = S[p].phase;
+    if (phase != LB_WAIT_BRACKET && phase != LB_WAIT_ZOOM) return;
+    const float* xi = W + (size_t)p * lbfgs_ws_floats(cf.hist) + (size_t)LV_XINIT * LB_DPAD;
+    for (int c = 0; c < NEXPR; ++c) psi[(size_t)p * NEXPR + c] = xi[col0 + c];
+}
+// one Adam step of psi with the gradient an evaluation left: thread per entry
+__global__ void expr_adam_kernel(float* __restrict__ psi, const float* __restrict__ dpsi, float* __restrict__ m, float* __restrict__ v, int n,
+                                 AdamScalars a) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) adam_update(psi[e], m[e], v[e], dpsi[e], a);
+}
 #endif
 
 }  // namespace fdc

@@ -1,6 +1,12 @@
 // The keypoint kernel's text (csrc/fdc_keypoints.h includes it twice): FDC_KP_KERNEL is the kernel's name, FDC_KP_JAW 0 the kernel as
 // it stands without a jaw -- fit2d_kp_kernel, whose code the second form must not perturb -- and 1 the form with a free jaw
-// (fit2d_kp_jaw_kernel: one more argument, the blocks between #if FDC_KP_JAW).  No include guard, on purpose.
+// (fit2d_kp_jaw_kernel: one more argument, the blocks between #if FDC_KP_JAW).  FDC_KP_EXPR 1 (the includer leaves it undefined for
+// the two kernels above: 0) adds the free expression coefficients, with or without the jaw: one more argument again and the blocks
+// between #if FDC_KP_EXPR -- none of which reaches the text of the forms without it.  No include guard, on purpose.
+#ifndef FDC_KP_EXPR
+#define FDC_KP_EXPR 0
+#define FDC_KP_EXPR_DEFAULTED
+#endif
 template <bool POS, bool PANEL>
 __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, const float* __restrict__ X, const float* __restrict__ PF,
                                                          const float* __restrict__ A, const float* __restrict__ M,
@@ -13,6 +19,9 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
 #if FDC_KP_JAW
                                                          , JawIO jw
 #endif
+#if FDC_KP_EXPR
+                                                         , ExprIO ex
+#endif
                                                          ) {
     __shared__ float s_x[XDIM + 2], s_pf[NPFX], s_A[NJ * 12], s_M[12], s_jw[NJW * 3 + 3], s_kp[KP_MAX * 3], s_dk[KP_MAX * 3];
     __shared__ float s_v[KP_MAXV * 3];         // pose + shape offsets of the real vertices, later every set vertex's d loss / d v_posed
@@ -21,6 +30,11 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
     __shared__ float s_red[16][16], s_sred[4][2], s_db[NBETA];
 #if FDC_KP_JAW
     __shared__ JawFwd s_jf;                    // the jaw's forward, kept for the backward
+#endif
+#if FDC_KP_EXPR
+    __shared__ float s_psi[NEXPR], s_dl[NJ * 3], s_djw[NJW * 3];      // the coefficients, delta = JE psi (kept for the backward), d loss / d Jw
+    __shared__ int s_par[NJ], s_cs[NJ + 1], s_cl[NJ + 1], s_dep[NJ];  // the tree: walked from LDS, not through dependent global loads
+    __shared__ float s_eb[PANEL ? NJ * 12 + 3 * NJ * 3 + 16 * NEXPR : 1];   // the backward's transients where the products' workspace is not there
 #endif
     const int tid = threadIdx.x, r = row0 + blockIdx.x;
     const int nr = ks.nr, nu = ks.nr + ks.np, nkp = ks.n_kp, ncol = 3 * ks.nr;
@@ -34,13 +48,49 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         if (tid < 12) s_M[tid] = M[(size_t)r * 12 + tid];
         if (PANEL) for (int e = tid; e < ncol; e += KP_NT) s_v[e] = Voff[(size_t)blockIdx.x * 3 * nu + e];
     }
+#if FDC_KP_EXPR
+    if (nu == 0) {                                         // (a map of joints 0..22 alone: the chain's correction still needs A and M)
+        for (int e = tid; e < NJ * 12; e += KP_NT) s_A[e] = A[(size_t)r * NJ * 12 + e];
+        if (tid < 12) s_M[tid] = M[(size_t)r * 12 + tid];
+    }
+    if (tid < NEXPR) s_psi[tid] = ex.psi[(size_t)blockIdx.x * NEXPR + tid];
+    if (tid >= 64 && tid < 64 + NJ) { s_par[tid - 64] = ex.parents[tid - 64]; s_dep[tid - 64] = ex.depth[tid - 64]; }
+    if (tid >= 128 && tid < 128 + NJ + 1) s_cs[tid - 128] = ex.child_start[tid - 128];
+    if (tid >= 192 && tid < 192 + NJ) s_cl[tid - 192] = ex.child_list[tid - 192];      // (NJ - 1 children and host_pose_setup's one pad)
+#endif
     const float sc = scale[0];
     __syncthreads();
+#if FDC_KP_EXPR
+    {   // delta, then every joint's own path to the root side by side (expr_forward); the world joints follow by W = M's rotation
+        if (tid < NJ * 3) s_dl[tid] = expr_delta_entry(ex.JE, s_psi, tid);
+        __syncthreads();
+        if (tid < NJ) {
+            const V3 dt = expr_forward(s_A, s_par, s_dl, tid);
+            if (tid < NJW) {
+                s_jw[3 * tid] += s_M[0] * dt.x + s_M[1] * dt.y + s_M[2] * dt.z;
+                s_jw[3 * tid + 1] += s_M[4] * dt.x + s_M[5] * dt.y + s_M[6] * dt.z;
+                s_jw[3 * tid + 2] += s_M[8] * dt.x + s_M[9] * dt.y + s_M[10] * dt.z;
+            }
+        }
+        if (PANEL)                                         // (blend_forward knows nothing of psi)
+            for (int c = tid; c < ncol; c += KP_NT) {
+                float acc = 0.f;
+                for (int l = 0; l < NEXPR; ++l) acc += ex.E[(size_t)l * ex.lde + c] * s_psi[l];
+                s_v[c] += acc;
+            }
+        __syncthreads();
+    }
+#endif
 #if FDC_KP_JAW
     if (nu > 0) {
         if (tid == 0) {
             const float* w = jw.jaw + (size_t)blockIdx.x * 3;
+#if FDC_KP_EXPR
+            s_jf = jaw_forward(v3(w[0], w[1], w[2]), kp_joint_rest(ks.Jt, ks.Jd, s_x + X_BETAS, JAW_J) + v3(s_dl[3 * JAW_J], s_dl[3 * JAW_J + 1], s_dl[3 * JAW_J + 2]),
+                               s_A + 12 * JAW_J, s_pf + 9 * (JAW_J - 1));
+#else
             s_jf = jaw_forward(v3(w[0], w[1], w[2]), kp_joint_rest(ks.Jt, ks.Jd, s_x + X_BETAS, JAW_J), s_A + 12 * JAW_J, s_pf + 9 * (JAW_J - 1));
+#endif
         }
         __syncthreads();
         if (PANEL) {
@@ -67,6 +117,11 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         for (int c = tid; c < ncol; c += KP_NT) {
             float acc = s_part[c];
             for (int p = 1; p < nparts; ++p) acc += s_part[p * ncol + c];
+#if FDC_KP_EXPR
+            float ea = 0.f;
+            for (int l = 0; l < NEXPR; ++l) ea += ex.E[(size_t)l * ex.lde + c] * s_psi[l];
+            acc += ea;
+#endif
             s_v[c] = acc;
         }
         __syncthreads();
@@ -80,6 +135,9 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         for (int c = 0; c < 3; ++c) {                      // (pose_forward's joint_rest, term for term)
             float acc = ks.Jt[3 * j + c];
             for (int l = 0; l < NBETA; ++l) acc += ks.Jd[(3 * j + c) * NBETA + l] * s_x[X_BETAS + l];
+#if FDC_KP_EXPR
+            acc += s_dl[3 * j + c];
+#endif
             p[c] = acc;
         }
         return v3(p[0], p[1], p[2]);
@@ -126,6 +184,12 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         prior = v * v;
     }
 #endif
+#if FDC_KP_EXPR
+    if (tid >= XDIM + 3 && tid < XDIM + 3 + NEXPR) {
+        const float v = ex.w * s_psi[tid - (XDIM + 3)];
+        prior = v * v;
+    }
+#endif
     if (losses || floss) {
         float vals[2] = {data, prior};
 #pragma unroll
@@ -144,9 +208,77 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         const V3 g = kp_joint_grad(tid, ks.jl_start, ks.jl_k, s_dk);
         float* o = dJw + ((size_t)r * NJW + tid) * 3;
         o[0] = g.x; o[1] = g.y; o[2] = g.z;
+#if FDC_KP_EXPR
+        s_djw[3 * tid] = g.x; s_djw[3 * tid + 1] = g.y; s_djw[3 * tid + 2] = g.z;
+#endif
     }
+#if FDC_KP_EXPR
+    // The correction's backward (csrc/fdc_keypoints.h): s_ew holds d loss / d A' [55][12]; dA (=) that plus the rotation addends, and
+    // dpsi (=) JE^T d delta + E^T d v_posed + the prior's, complete when the kernel ends.  s_ew: the products' workspace, free between the
+    // two products -- the panel form has none (its products run outside), so there the transients have 5.3 KB of their own.
+    float* const s_ew = PANEL ? s_eb : s_part;
+    auto expr_bwd = [&]() {
+        float *const s_da = s_ew, *const s_own = s_ew + NJ * 12, *const s_S = s_own + NJ * 3, *const s_dd = s_S + NJ * 3, *const s_pp = s_dd + NJ * 3;
+        static_assert(NJ * 12 + 3 * NJ * 3 + 16 * NEXPR <= KP_PART, "the workspace holds the expression's backward");
+        if (tid < NJ * 3) {
+            const int j = tid / 3, c = tid - 3 * j;
+            float o = s_da[12 * j + 4 * c + 3];
+            // W^T dJw_j, W = the rotation of M (rows of four: [R | t], as A's): column c.  The inner fit's set-up has W = I, so the tests see
+            // the identity here; the forward above applies the same rows
+            if (j < NJW) o += (s_M[c] * s_djw[3 * j] + s_M[4 + c] * s_djw[3 * j + 1]) + s_M[8 + c] * s_djw[3 * j + 2];
+            s_own[tid] = o;
+        }
+        __syncthreads();
+        if (tid < 64) {                                    // lane j = joint j, the levels from the deepest: a wave's LDS operations execute in order
+            const int dep = tid < NJ ? s_dep[tid] : -1;
+            for (int L = ex.nlevels - 1; L >= 0; --L) {
+                if (dep == L) {
+                    const V3 sj = expr_subtree_children(s_cs, s_cl, s_own, s_S, tid);
+                    s_S[3 * tid] = sj.x; s_S[3 * tid + 1] = sj.y; s_S[3 * tid + 2] = sj.z;
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __syncthreads();
+        if (tid < NJ) {
+            V3 d = expr_backward_delta(s_A, s_par, s_own, s_S, s_da, tid);
+#if FDC_KP_JAW
+            if (tid == JAW_J && nu > 0) d = d + v3(s_dk[16], s_dk[17], s_dk[18]);      // (J22 = its rest position + delta_22)
+#endif
+            s_dd[3 * tid] = d.x; s_dd[3 * tid + 1] = d.y; s_dd[3 * tid + 2] = d.z;
+        }
+        if (tid >= 64 && tid < 64 + NJ * 12) {             // (beside the first wave's joints)
+            const int q = tid - 64, j = q / 12, e = q - 12 * j, i = e >> 2, c = e & 3;
+            float v = s_da[q];
+            if (c < 3) v += expr_backward_rot_entry(s_cs, s_cl, s_dl, s_own, s_S, s_da, j, i, c);
+            dA[(size_t)r * NJ * 12 + q] = v;
+        }
+        __syncthreads();
+        if (tid < 16 * NEXPR) {                            // sixteen partial sums per coefficient: entries part, part + 16, ..
+            const int part = tid & 15, l = tid >> 4;
+            float acc = 0.f;
+            for (int e = part; e < NJ * 3; e += 16) acc += ex.JE[e * NEXPR + l] * s_dd[e];
+            for (int c = part; c < 3 * nu; c += 16) acc += ex.E[(size_t)l * ex.lde + c] * s_v[c];
+            s_pp[tid] = acc;
+        }
+        __syncthreads();
+        if (tid < NEXPR) {
+            float acc = s_pp[16 * tid];
+            for (int p = 1; p < 16; ++p) acc += s_pp[16 * tid + p];
+            ex.dpsi[(size_t)blockIdx.x * NEXPR + tid] = acc + 2.f * ex.w * ex.w * s_psi[tid];
+        }
+        __syncthreads();
+    };
+#endif
 #if FDC_KP_JAW
     if (nu == 0 && tid < 9) jw.R9[(size_t)blockIdx.x * 9 + tid] = 0.f;                // (no vertex follows the jaw)
+#endif
+#if FDC_KP_EXPR
+    if (nu == 0) {                                         // (kernel-uniform) only the world joints' gradients reach the chain's correction
+        for (int e = tid; e < NJ * 12; e += KP_NT) s_ew[e] = 0.f;
+        __syncthreads();
+        expr_bwd();
+    }
 #endif
     if (nu == 0) return;                                   // (kernel-uniform: no vertex branch, nothing else is written or read)
     // set vertex u: its position's gradient from its list, back through the world transform and the skinning
@@ -174,14 +306,23 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         if (j == JAW_J) s_dk[e] = acc;                     // (d loss / d A'_22: through jaw_backward below; s_dk is free by now)
         else
 #endif
+#if FDC_KP_EXPR
+        s_ew[it] = acc;                                    // (d loss / d A': through expr_bwd below)
+#else
         dA[(size_t)r * NJ * 12 + it] = acc;
+#endif
     }
 #if FDC_KP_JAW
     {
         __syncthreads();
         if (tid == 0) {
             const JawBwd b = jaw_backward(s_jf, s_dk);
+#if FDC_KP_EXPR
+            for (int e = 0; e < 12; ++e) s_ew[12 * JAW_J + e] = b.dA22[e];
+            for (int i = 0; i < 3; ++i) for (int c = 0; c < 3; ++c) s_A[12 * JAW_J + 4 * i + c] = s_jf.RA.m[3 * i + c];   // (the chain's rotation again)
+#else
             for (int e = 0; e < 12; ++e) dA[(size_t)r * NJ * 12 + 12 * JAW_J + e] = b.dA22[e];
+#endif
             for (int e = 0; e < 9; ++e) jw.R9[(size_t)blockIdx.x * 9 + e] = b.dRw.m[e];
             s_dk[16] = b.dJ22.x; s_dk[17] = b.dJ22.y; s_dk[18] = b.dJ22.z;
         }
@@ -193,6 +334,10 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
             dX[(size_t)r * XDIM + tid] += acc;
         }
     }
+#endif
+#if FDC_KP_EXPR
+    __syncthreads();
+    expr_bwd();
 #endif
     // the sixteen per-frame sums over the set's vertices -- dM [12], d scale, d transl [3] (skin_backward_vertex's dM, ds, gv) -- in two
     // steps: sixteen partial sums over u = part, part + 16, .. each, then those in order
@@ -256,3 +401,7 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         else dtransl_v[(size_t)r * 3 + tid - 13] = acc;
     }
 }
+#ifdef FDC_KP_EXPR_DEFAULTED
+#undef FDC_KP_EXPR
+#undef FDC_KP_EXPR_DEFAULTED
+#endif

@@ -1,7 +1,10 @@
 // The L-BFGS advance kernel's text (csrc/fdc_lbfgs.h includes it with FDC_LB_TAIL 0: lbfgs_advance_kernel, compiled from exactly the
 // text it had).  FDC_LB_TAIL 1 gives the form with three more columns in a second array (csrc/fdc_lbfgs.h's comment); the includer
 // names the kernel (FDC_LB_KERNEL), the type of its extra argument (FDC_LB_TAIL_T), the array in it (FDC_LB_TAIL_X2(tail): float*
-// [nprob][3]) and the three columns' gradient of problem p (FDC_LB_TAIL_GRAD(tail, p): a V3).  No include guard, on purpose.
+// [nprob][3]) and the three columns' gradient of problem p (FDC_LB_TAIL_GRAD(tail, p): a V3).  FDC_LB_TAIL 2 gives a tail of a width
+// the argument carries -- FDC_LB_TAIL_W(tail) columns, at most 64 and the x row still at least 64 wide -- whose entries the includer
+// reads, writes and differentiates one by one: FDC_LB_TAIL_LD(tail, p, c), FDC_LB_TAIL_ST(tail, p, c, v), FDC_LB_TAIL_G(tail, p, c).
+// No include guard, on purpose.
 __global__ __launch_bounds__(LB_NT) void FDC_LB_KERNEL(LbfgsCfg cf, LbfgsScalars* __restrict__ S, float* __restrict__ W,
                                                            float* __restrict__ RO, float* __restrict__ X, int x_stride,
                                                            const float* __restrict__ F, const float* __restrict__ G, int g_stride,
@@ -43,7 +46,12 @@ __global__ __launch_bounds__(LB_NT) void FDC_LB_KERNEL(LbfgsCfg cf, LbfgsScalars
         // ... and the work vectors and the x row with it: read one by one along the state machine they were another six to
         // eight dependent round trips
         if (threadIdx.x < LV_NUM * (LB_DPAD / 4)) s_hist4[2 * so + threadIdx.x] = ((const float4*)w)[threadIdx.x];
-#if FDC_LB_TAIL
+#if FDC_LB_TAIL == 2
+        {
+            const int t = threadIdx.x, c = t - (cf.dim - FDC_LB_TAIL_W(tail));
+            if (t < LB_DPAD) s_x[t] = t >= cf.dim ? 0.f : c >= 0 ? FDC_LB_TAIL_LD(tail, p, c) : X[(size_t)p * x_stride + t];
+        }
+#elif FDC_LB_TAIL
         {
             const int t = threadIdx.x, c = t - (cf.dim - 3);
             if (t < LB_DPAD) s_x[t] = t >= cf.dim ? 0.f : c >= 0 ? FDC_LB_TAIL_X2(tail)[(size_t)p * 3 + c] : X[(size_t)p * x_stride + t];
@@ -55,7 +63,13 @@ __global__ __launch_bounds__(LB_NT) void FDC_LB_KERNEL(LbfgsCfg cf, LbfgsScalars
     const int lane = threadIdx.x & 63;
     const float* const gr = G + (size_t)p * g_stride;
     const float f_new = F[p];
-#if FDC_LB_TAIL
+#if FDC_LB_TAIL == 2
+    LV g_new = {lane < cf.dim ? gr[lane] : 0.f, lane + 64 < cf.dim - FDC_LB_TAIL_W(tail) ? gr[lane + 64] : 0.f};
+    {
+        const int c = lane + 64 - (cf.dim - FDC_LB_TAIL_W(tail));
+        if (c >= 0 && c < FDC_LB_TAIL_W(tail)) g_new.b = FDC_LB_TAIL_G(tail, p, c);
+    }
+#elif FDC_LB_TAIL
     LV g_new = {lane < cf.dim ? gr[lane] : 0.f, lane + 64 < cf.dim - 3 ? gr[lane + 64] : 0.f};
     {
         const int c = lane + 64 - (cf.dim - 3);
@@ -108,7 +122,13 @@ __global__ __launch_bounds__(LB_NT) void FDC_LB_KERNEL(LbfgsCfg cf, LbfgsScalars
         const LV xi = wld(LV_XINIT);
         const float xa = fmaf(t, d.a, xi.a), xb = fmaf(t, d.b, xi.b);
         if (lane < cf.dim) x[lane] = xa;
-#if FDC_LB_TAIL
+#if FDC_LB_TAIL == 2
+        {
+            const int c = lane + 64 - (cf.dim - FDC_LB_TAIL_W(tail));
+            if (c < 0) x[lane + 64] = xb;
+            else if (c < FDC_LB_TAIL_W(tail)) FDC_LB_TAIL_ST(tail, p, c, xb);
+        }
+#elif FDC_LB_TAIL
         {
             const int c = lane + 64 - (cf.dim - 3);
             if (c < 0) x[lane + 64] = xb;

@@ -85,6 +85,10 @@ struct KeypointSet {
     DevBuf<int32_t> kjoint, kref, vl_start, vl_k, jl_start, jl_k, pjoint, wj, csc_start, csc_u;
     DevBuf<float> kbary, vl_w, vt, ww, csc_w, Bt;
     SkinSet ss;               // the set's blend matrix (posedirs, ldp) and its panels: what blend_forward / blend_backward take; nothing else of it is filled
+    // the free expression's tables (a model with expression directions: fdcap_ctx::h_E10): E [10][lde] the set's expression directions
+    // per column 3 u + c (a pseudo-vertex: JE_j's rows), JE [55 3][10]
+    DevBuf<float> E, JE;
+    int lde = 0;
     void release() { *this = KeypointSet(); }
 };
 
@@ -176,6 +180,10 @@ struct OptState {
     DevBuf<float> floss;      // ... and the per-frame objective of its L-BFGS variant
     DevBuf<float> jaw, mJaw, vJaw, jawR9;   // ... its free jaw (fdcap_opt_set_jaw) [n_local, 3], Adam's moments of it, and the skinning part of
                               // d loss / d R_w [n_local, 9] an evaluation leaves (fit2d_kp_jaw_kernel; jaw_grad adds dPF's block)
+    DevBuf<float> psi, dpsi, mPsi, vPsi;    // ... its free expression coefficients (fdcap_opt_set_expression) [n_local, 10], the gradient an
+                              // evaluation leaves (complete: fit2d_kp_expr_kernel) and Adam's moments
+    bool expr_on = false, expr_eval = false;                   // free; an evaluation's gradient is there (until a step consumes it)
+    float w_expr = 0.f;                                        // the expression prior's weight (fdcap_opt_set_expression_prior)
     bool jaw_on = false, jaw_eval = false, jaw_gp = false;     // free; an evaluation's gradient parts are there (until a step consumes them); ... with dPF (a set with vertices)
     int lbfgs_rolled_back = 0;                                 // frames the last fdcap_opt_fit2d_lbfgs call found inside a line search when its rounds ran out
     float w_jaw[3] = {0.f, 0.f, 0.f};                          // the jaw prior's weights (fdcap_opt_set_fit2d_extra)
@@ -293,6 +301,7 @@ struct fdcap_ctx {
     int V = 0;
     // host copies needed to build vertex subsets
     std::vector<float> h_vt, h_S10, h_lbs;
+    std::vector<float> h_E10, h_JE;     // a model with num_shape >= 20: shapedirs' columns 10..19 [3V, 10] and J_regressor times them [55 3][10] (else empty)
     DevBuf<float> d_posedirs, d_S10;    // posedirs [486, 3V] and shapedirs' first ten [3V, 10]: what a vertex set's blend matrix is gathered from (r6: on the device)
     // device constants
     DevBuf<float> Jt, Jd, hand_comp, hand_mean;
@@ -324,6 +333,9 @@ struct fdcap_ctx {
         const KeypointSet& k = kpset;
         return KpSet{k.h.n_kp, k.h.nr, k.h.np, k.K, k.ss.ldp, k.kjoint.p, k.kref.p, k.kbary.p, k.vl_start.p, k.vl_k.p, k.vl_w.p, k.jl_start.p, k.jl_k.p,
                      k.vt.p, k.pjoint.p, k.wj.p, k.ww.p, k.csc_start.p, k.csc_u.p, k.csc_w.p, k.ss.posedirs.p, k.Bt.p, Jt.p, Jd.p};
+    }
+    ExprIO expr_view(const float* psi, float* dpsi, float w) const {
+        return ExprIO{psi, dpsi, w, kpset.E.p, kpset.lde, kpset.JE.p, parents.p, child_start.p, child_list.p, depth.p, nlevels};
     }
     // The registered scenes: slot 0 is THE scene of every one-scene entry point (fdcap_set_scene, the scene operator, the
     // diagnostics); the other slots only serve a batch whose clips name them (fdcap_opt_create_clips_scenes).

@@ -41,6 +41,10 @@ DEFAULT_BEND_RATIO = 3.17
 MAX_BEND_TERMS = 8      # FDCAP_MAX_BEND_TERMS
 # The jaw prior's weights (x, y, z of the jaw's axis-angle) per stage.  [upstream-recall: fit_smplx.yaml's jaw_pose_prior_weights]
 DEFAULT_JAW_PRIOR = ((4.04e3, 4.04e4, 4.04e4), (4.04e3, 4.04e4, 4.04e4), (574.0, 5740.0, 5740.0), (47.8, 478.0, 478.0), (47.8, 478.0, 478.0))
+# The expression prior's weight per stage: w^2 |expression|^2.  [upstream-recall: fit_smplx.yaml's expr_weights; not part of this
+# repository: a default a caller can replace through expression_prior, never a constant of a kernel]
+DEFAULT_EXPRESSION_PRIOR = (1e2, 5e1, 1e1, 0.5e1, 0.5e1)
+NUM_EXPRESSION = 10
 
 # How a fit starts from keypoints alone (csrc/fdc_fit2d_init.h), as SMPL-X JOINTS -- resolved to keypoint slots per layout: the depth
 # guess's torso edges (left shoulder - left hip, right shoulder - right hip), the camera stage's keypoints (both shoulders, both hips)
@@ -182,7 +186,7 @@ class InnerFitOP:
     def __init__(self, body_model, vposer, num_frames, intrinsics=DEFAULT_INTRINSICS, rho=100.0, lr=0.01,
                  stages=DEFAULT_STAGES, iters_per_stage=30, optimizer="adam", lbfgs=None, max_rounds=4000,
                  keypoint_map=None, group_of=None, group_weights=None, fit_jaw=False, jaw_prior=None,
-                 bend_prior=None, init=None, orientations="auto", collision=None):
+                 bend_prior=None, init=None, orientations="auto", collision=None, fit_expression=False, expression_prior=None):
         """optimizer "adam": iters_per_stage steps of Adam(lr) per stage; "lbfgs": per frame and stage, SMPLify-X's L-BFGS loop
         with the settings `lbfgs` (keys of DEFAULT_LBFGS; missing ones take their defaults), at most max_rounds objective
         evaluations per stage.
@@ -203,8 +207,26 @@ class InnerFitOP:
         collision: None (off: not one more library call), or a dict with keys of DEFAULT_COLLISION (missing ones take their defaults):
         the self-interpenetration term of csrc/fdc_collide.h on `faces` [F,3] (default: body_model.faces), weighted per stage by
         `weights`; `face_part` [F] in 0..63, `part_parent`, `ignore_pairs` and `same_part` go through collision_filter.  Not with
-        fit_jaw: the full-mesh pass skins with the shut jaw."""
+        fit_jaw: the full-mesh pass skins with the shut jaw.
+        fit_expression: SMPL-X's ten expression coefficients are free per frame next to the row (and the jaw) -- needs a keypoint_map,
+        whose face landmarks are what sees them, and a body model with expression directions (shapedirs [V,3,20]); not with collision
+        (the full-mesh pass skins at expression zero); fitting() leaves them in self.expression.  expression_prior [stages]: the weight
+        w of w^2 |expression|^2 per stage (default DEFAULT_EXPRESSION_PRIOR when stages has its five)."""
         import torch
+        if collision is not None and fit_expression:         # (checked before anything touches the device)
+            raise capi.FdcapError("collision does not go with fit_expression: the full-mesh pass skins at expression zero")
+        if fit_expression and keypoint_map is None:
+            raise capi.FdcapError("fit_expression needs a keypoint_map: the correction runs in the mapped data term")
+        if expression_prior is not None and not fit_expression:
+            raise capi.FdcapError("expression_prior belongs to fit_expression")
+        self.fit_expression, self.expression_prior, self.expression = bool(fit_expression), None, None
+        if self.fit_expression:
+            ep = np.asarray(DEFAULT_EXPRESSION_PRIOR if expression_prior is None else expression_prior, dtype=np.float32).reshape(-1)
+            if ep.shape != (len(tuple(stages)),) or not np.all(np.isfinite(ep)):
+                raise capi.FdcapError("expression_prior must be [stages], finite")
+            if np.asarray(body_model.shapedirs).shape[2] < 10 + NUM_EXPRESSION:
+                raise capi.FdcapError("fit_expression needs a body model with expression directions: shapedirs [V,3,20]")
+            self.expression_prior = ep
         self.collision = None
         if collision is not None:                             # (checked before anything touches the device)
             unknown = set(collision) - set(DEFAULT_COLLISION)
@@ -301,10 +323,11 @@ class InnerFitOP:
                 ex.joint[t], ex.axis[t], ex.sign[t] = j, a, s
         capi.check(self.ctx.lib.fdcap_opt_set_fit2d_extra(self.ctx.handle, ctypes.byref(ex)), "fdcap_opt_set_fit2d_extra")
 
-    def fitting(self, rows75, keypoints, log_every=0, jaw_init=None):
+    def fitting(self, rows75, keypoints, log_every=0, jaw_init=None, expression_init=None):
         """rows75 [N,75] initial parameters (device tensor or numpy), keypoints [N,23,3] (u, v, confidence) -- with a keypoint_map
         [N,len(map),3] in its order -- -> optimised rows [N,75] (device tensor).  fit_jaw: the jaw starts from jaw_init [N,3] (default
-        zero) and ends in self.jaw_pose [N,3] (device tensor).
+        zero) and ends in self.jaw_pose [N,3] (device tensor); fit_expression: the coefficients start from expression_init [N,10]
+        (default zero) and end in self.expression [N,10] (device tensor).
         With init: rows75 may be None (neutral rows: all zero); of given rows everything but camera_translation is kept.  Leaves
         self.depth_guess / depth_valid [N] (numpy), self.camera_rows [N,75] (the rows after the camera stage), self.tried_both [N]
         (numpy bool), self.chosen [N] (numpy, 1: the turned body won), self.camera_rounds (L-BFGS: the camera stages' evaluations) and, when a
@@ -313,8 +336,8 @@ class InnerFitOP:
         if self.init is None:
             if rows75 is None:
                 raise capi.FdcapError("fitting(None, ...) needs init: without it the rows must already stand in front of the camera")
-            return self._fit(self.n, rows75, keypoints, log_every, jaw_init)
-        return self._fit_from_keypoints(rows75, keypoints, log_every, jaw_init)
+            return self._fit(self.n, rows75, keypoints, log_every, jaw_init, expression_init)
+        return self._fit_from_keypoints(rows75, keypoints, log_every, jaw_init, expression_init)
 
     def _tensor(self, a):
         import torch
@@ -349,7 +372,7 @@ class InnerFitOP:
         capi.check(lib.fdcap_opt_get_results(h, capi.dptr(out), None, None, capi.current_stream()), "fdcap_opt_get_results")
         return out, found
 
-    def _fit_from_keypoints(self, rows75, keypoints, log_every, jaw_init):
+    def _fit_from_keypoints(self, rows75, keypoints, log_every, jaw_init, expression_init=None):
         import torch
         lib, h, dev, n = self.ctx.lib, self.ctx.handle, self.device, self.n
         kp = self._tensor(keypoints)
@@ -364,7 +387,7 @@ class InnerFitOP:
         src = torch.from_numpy(np.flatnonzero(flagged).astype(np.int32)).to(dev)
         m = int(src.shape[0])
         if m == 0:
-            return self._fit(n, rows, kp, log_every, jaw_init)
+            return self._fit(n, rows, kp, log_every, jaw_init, expression_init)
         # the twins: the same start at the guessed depth, the body turned, their own camera stage -- then all n + m through the stages
         pick = src.long()
         twin = start[pick].contiguous()
@@ -375,7 +398,11 @@ class InnerFitOP:
         if jaw_init is not None:
             jaw0 = self._tensor(jaw_init)
             jaw_all = torch.cat([jaw0, jaw0[pick]]).contiguous()
-        both = self._fit(n + m, torch.cat([rows, twin]).contiguous(), torch.cat([kp, kp[pick]]).contiguous(), log_every, jaw_all)
+        expr_all = None
+        if expression_init is not None:
+            expr0 = self._tensor(expression_init)
+            expr_all = torch.cat([expr0, expr0[pick]]).contiguous()
+        both = self._fit(n + m, torch.cat([rows, twin]).contiguous(), torch.cat([kp, kp[pick]]).contiguous(), log_every, jaw_all, expr_all)
         floss = torch.empty(n + m, device=dev)
         capi.check(lib.fdcap_opt_fit2d_frame_loss(h, ctypes.byref(self._last_stage), capi.dptr(floss), capi.current_stream()), "fdcap_opt_fit2d_frame_loss")
         out, chosen = torch.empty(n, capi.PDIM, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
@@ -385,6 +412,11 @@ class InnerFitOP:
         self.chosen, self.final_loss = chosen.cpu().numpy(), floss
         if self.fit_jaw:
             self.jaw_pose = jaw_out
+        if self.fit_expression:                               # (fdcap_fit2d_select does not carry them: the twin's where it won)
+            twin_of = torch.full((n,), -1, dtype=torch.long, device=dev)
+            twin_of[pick] = n + torch.arange(m, device=dev)
+            take = torch.where(chosen.long() != 0, twin_of, torch.arange(n, device=dev))
+            self.expression = self.expression[take].contiguous()
         return out
 
     def _setup(self, n, rows75, kp):
@@ -417,7 +449,7 @@ class InnerFitOP:
         else:
             capi.check(lib.fdcap_opt_set_keypoints_mapped(h, capi.dptr(kp), st), "fdcap_opt_set_keypoints_mapped")
 
-    def _fit(self, n, rows75, keypoints, log_every, jaw_init):
+    def _fit(self, n, rows75, keypoints, log_every, jaw_init, expression_init=None):
         """the stages over n problems from rows that stand in front of the camera"""
         import torch
         lib, h, dev = self.ctx.lib, self.ctx.handle, self.device
@@ -432,6 +464,13 @@ class InnerFitOP:
             capi.check(lib.fdcap_opt_set_jaw(h, capi.dptr(jaw0), st), "fdcap_opt_set_jaw")
         elif jaw_init is not None:
             raise capi.FdcapError("jaw_init belongs to fit_jaw")
+        if self.fit_expression:
+            expr0 = torch.zeros(n, NUM_EXPRESSION, device=dev) if expression_init is None else t(expression_init)
+            if tuple(expr0.shape) != (n, NUM_EXPRESSION):
+                raise capi.FdcapError(f"expected expression_init [{n},{NUM_EXPRESSION}]")
+            capi.check(lib.fdcap_opt_set_expression(h, capi.dptr(expr0), st), "fdcap_opt_set_expression")
+        elif expression_init is not None:
+            raise capi.FdcapError("expression_init belongs to fit_expression")
         self.log, self.rounds, self.frame_iterations, self.frame_loss = [], [], [], []
         fx, fy, cx, cy = self.intrinsics
         for si, (w_data, w_pose, w_shape, w_hand) in enumerate(self.stages):
@@ -442,6 +481,8 @@ class InnerFitOP:
             sg = self._last_stage = capi.Fit2dStage(fx, fy, cx, cy, self.rho, w_data, w_pose, w_shape, w_hand)
             if self.bend_prior is not None or self.fit_jaw:
                 self._set_extra(si, w_pose)
+            if self.fit_expression:
+                capi.check(lib.fdcap_opt_set_expression_prior(h, float(self.expression_prior[si])), "fdcap_opt_set_expression_prior")
             if self.collision is not None:                    # this stage's weight (0: the term is off, no launch)
                 q = self.collision
                 prm = capi.CollisionParams(q["sigma"], q["weights"][si], q["capacity"], 0)
@@ -480,6 +521,9 @@ class InnerFitOP:
         if self.fit_jaw:
             self.jaw_pose = torch.empty(n, 3, device=dev)
             capi.check(lib.fdcap_opt_get_jaw(h, capi.dptr(self.jaw_pose), None, capi.current_stream()), "fdcap_opt_get_jaw")
+        if self.fit_expression:
+            self.expression = torch.empty(n, NUM_EXPRESSION, device=dev)
+            capi.check(lib.fdcap_opt_get_expression(h, capi.dptr(self.expression), None, capi.current_stream()), "fdcap_opt_get_expression")
         return out
 
     def close(self):

@@ -86,9 +86,13 @@ def save_result(body_rec, scale, camera_ext, fit_path: str) -> list:
     return files
 
 
-def write_body_gen(body_params: np.ndarray, body_path: str, jaw_pose=None) -> None:
+def write_body_gen(body_params: np.ndarray, body_path: str, jaw_pose=None, expression=None) -> None:
     """Inverse of load_body_gen: lay a [N,75] array out as SMPLify-X result folders.  jaw_pose [N,3] (the inner fit's free jaw) adds
-    SMPLify-X's `jaw_pose` key; load_body_gen does not read it, as the reference's loader does not."""
+    SMPLify-X's `jaw_pose` key and expression [N,10] (its free expression coefficients) the `expression` key; load_body_gen reads
+    neither, as the reference's loader does not."""
+    expr = None if expression is None else np.asarray(expression, dtype=np.float32).reshape(-1, 10)
+    if expr is not None and expr.shape[0] != len(body_params):
+        raise ValueError("expression must hold ten coefficients per row of body_params")
     jaw = None if jaw_pose is None else np.asarray(jaw_pose, dtype=np.float32).reshape(-1, 3)
     if jaw is not None and jaw.shape[0] != len(body_params):
         raise ValueError("jaw_pose must hold one axis-angle per row of body_params")
@@ -98,6 +102,8 @@ def write_body_gen(body_params: np.ndarray, body_path: str, jaw_pose=None) -> No
         rec = {k: row[None, lo:hi].copy() for k, (lo, hi) in SLICES_75.items()}
         if jaw is not None:
             rec["jaw_pose"] = jaw[None, i].copy()
+        if expr is not None:
+            rec["expression"] = expr[None, i].copy()
         with open(os.path.join(d, "000.pkl"), "wb") as f:
             pickle.dump(rec, f)
 

@@ -578,6 +578,27 @@ int fdcap_opt_set_jaw(fdcap_ctx* ctx, const float* jaw_d, void* stream);
 /* the jaw and -- optional -- the objective's gradient with respect to it at the last evaluation, DEVICE [n_local, 3] each (either may
  * be NULL, not both).  FDCAP_E_STATE: no free jaw; djaw_d before an evaluation. */
 int fdcap_opt_get_jaw(fdcap_ctx* ctx, float* jaw_d, float* djaw_d, void* stream);
+/* FREE EXPRESSION COEFFICIENTS for the mapped data term (csrc/fdc_keypoints.h): ten per frame, expr_d DEVICE [n_local, 10], copied; NULL:
+ * fixed at zero again, the model every other call of this library uses.  SMPL-X treats them as ten more shape directions (shapedirs'
+ * columns 10..19 of fdcap_model_desc): v_shaped = v_template + S betas + E psi with the joints regressed from v_shaped -- the exact
+ * model, evaluated as a correction of the pose kernels' chain inside the data term's kernel.  From here on fdcap_debug_keypoints3d,
+ * fdcap_opt_backward_fit2d, fdcap_opt_fit2d_frame_loss and fdcap_opt_fit2d_lbfgs (88 unknowns per frame, 91 with a free jaw: the row,
+ * psi, then the jaw; fdcap_opt_fit2d_lbfgs_rolled_back counts as before and psi is rolled back with its row) honour them,
+ * fdcap_opt_step_x steps them with the rows' lr and step number, fdcap_opt_reset_adam zeroes their moments too.  The camera stage
+ * (fdcap_opt_backward_fit2d_camera, fdcap_opt_fit2d_camera_lbfgs) ignores them and leaves them where they are; fdcap_opt_get_results,
+ * the full-mesh operators and the clip-level modes keep psi = 0.  fdcap_fit2d_select does not carry them: gather them with chosen_d.
+ * FDCAP_E_ARG: a model with a joint in front of its parent.  FDCAP_E_STATE: no optimiser, a batch of clips, one rank's share of a clip,
+ * a model with num_shape < 20; from an evaluation on the 23-joint layout (fdcap_opt_set_keypoints: the correction runs in the mapped
+ * term's kernel); and together with the self-interpenetration term, at the evaluation or in fdcap_opt_set_fit2d_collision (the
+ * full-mesh pass skins with the transforms the pose kernels wrote, at psi = 0). */
+int fdcap_opt_set_expression(fdcap_ctx* ctx, const float* expr_d, void* stream);
+/* the coefficients and -- optional -- the objective's gradient with respect to them at the last evaluation, DEVICE [n_local, 10] each
+ * (either may be NULL, not both: FDCAP_E_ARG).  FDCAP_E_STATE: no free expression; dexpr_d before an evaluation. */
+int fdcap_opt_get_expression(fdcap_ctx* ctx, float* expr_d, float* dexpr_d, void* stream);
+/* the weight of the prior w_expr^2 |psi|^2, which joins losses_d [1] and every frame's objective; holds until the next call (0 at
+ * fdcap_opt_create); without free expression coefficients nothing reads it.  FDCAP_E_ARG: a non-finite weight.  FDCAP_E_STATE: as
+ * fdcap_opt_set_expression's first three. */
+int fdcap_opt_set_expression_prior(fdcap_ctx* ctx, float w_expr);
 /* The inner fit's self-interpenetration term on the mesh of fdcap_set_collision_mesh; holds until the next call; params = NULL or
  * w_coll == 0: off, and then not one launch or argument of an evaluation differs.  With it every evaluation (fdcap_opt_backward_fit2d,
  * fdcap_opt_fit2d_lbfgs, fdcap_opt_fit2d_frame_loss) runs, after the pose forward and the data term, the full-mesh blend and skinning
