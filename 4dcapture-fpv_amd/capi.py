@@ -108,6 +108,10 @@ SYMBOLS = {
     "fdcap_params_78_to_75": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
     "fdcap_smplx_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                        c_void_p, c_void_p, c_void_p]),
+    "fdcap_body_forward_face": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_world_mesh_face": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_smplx_forward_face": (c_int32, [c_void_p] * 7 + [c_int32] + [c_void_p] * 5),
+    "fdcap_smplx_backward_face": (c_int32, [c_void_p] * 7 + [c_int32] + [c_void_p] * 13),
     "fdcap_opt_create": (c_int32, [c_void_p, POINTER(OptConfig), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_create_clips": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_create_clips_var": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p,
@@ -159,6 +163,7 @@ SYMBOLS = {
     "fdcap_opt_backward_fit2d": (c_int32, [c_void_p, POINTER(Fit2dStage), c_int32, c_void_p]),
     "fdcap_opt_set_fit2d_extra": (c_int32, [c_void_p, POINTER(Fit2dExtra)]),
     "fdcap_opt_set_fit2d_collision": (c_int32, [c_void_p, POINTER(CollisionParams)]),
+    "fdcap_opt_set_fit2d_collision_face": (c_int32, [c_void_p, c_int32]),
     "fdcap_opt_set_jaw": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_get_jaw": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_set_expression": (c_int32, [c_void_p, c_void_p, c_void_p]),

@@ -82,10 +82,6 @@ def main(argv=None, body_model=None, vposer=None):
     a = ap.parse_args(argv)
     if a.collision_parts and not a.collision:
         ap.error("--collision-parts belongs to --collision")
-    if a.collision and a.fit_jaw:
-        ap.error("--collision does not go with --fit-jaw")
-    if a.collision and a.fit_expression:
-        ap.error("--collision does not go with --fit-expression")
 
     from . import assets, io
     from .innerfit import DEFAULT_INTRINSICS, InnerFitOP, KeypointMap
@@ -106,6 +102,8 @@ def main(argv=None, body_model=None, vposer=None):
         if a.collision_parts:
             parts = np.load(a.collision_parts)
             collision = dict(face_part=parts["face_part"], part_parent=parts["part_parent"])
+        if a.fit_jaw or a.fit_expression:                    # the term's full-mesh pass skins the fitted face
+            collision["follow_face"] = True
     rows, jaws, exprs, ops = [], [], [], {}
     for lo, hi in plan_frame_batches(len(files), a.frames_per_batch):
         n = hi - lo

@@ -558,10 +558,19 @@ int fdcap_opt_set_fit2d_collision(fdcap_ctx* c, const fdcap_collision_params* p)
     OptState* o = c->opt;
     if (!p) { o->coll_on = false; return FDCAP_OK; }
     if (!coll_params_ok(p->sigma, p->w_coll, p->capacity)) return FDCAP_E_ARG;
-    if (c->coll.h.F <= 0 || o->jaw_on) return FDCAP_E_STATE;  // no registered mesh; a free jaw (the full-mesh pass skins with the shut jaw's A)
-    if (o->expr_on) return FDCAP_E_STATE;                     // ... free expression coefficients (the same reason: the pose kernels' A, at psi = 0)
+    // no registered mesh; a free jaw or free expression coefficients without the opt-in (the full-mesh pass then skins with the pose
+    // kernels' A: the shut jaw, psi = 0)
+    if (c->coll.h.F <= 0 || ((o->jaw_on || o->expr_on) && !o->coll_face)) return FDCAP_E_STATE;
     o->coll = *p;
     o->coll_on = p->w_coll != 0.f;                            // (weight 0: every value and gradient an exact zero -- no launch)
+    return FDCAP_OK;
+}
+// on != 0: the term follows a free jaw and free expression coefficients -- its full-mesh pass corrects the transforms, the PF row and the
+// offsets (csrc/fdc_face_mesh.h) and its share of d psi and of the jaw's two gradient parts joins the data term's.  0 (the default): both
+// are refused as before, and not one launch or argument of an evaluation differs.
+int fdcap_opt_set_fit2d_collision_face(fdcap_ctx* c, int32_t on) {
+    if (!c || !c->opt || opt_is_batch(c) || !opt_whole_clips(c->opt)) return FDCAP_E_STATE;
+    c->opt->coll_face = on != 0;
     return FDCAP_OK;
 }
 
@@ -601,6 +610,59 @@ __global__ __launch_bounds__(64) void fit2d_coll_value_kernel(const float* __res
 // The term's pass of one evaluation, after the pose forward and the data term: full-mesh blend and skinning forward over the n_local
 // rows, fdcap_collision_eval on the world vertices, skinning and blend backward.  second: the data term has assigned the vertex
 // branch's five sums, so these go to buffers of their own and one launch adds them on; else they are the only ones.
+// ... with a free jaw and / or free psi (fdcap_opt_set_fit2d_collision_face): face_fwd_kernel corrects the frame's transforms into faceA and
+// -- jaw -- copies the PF row with the jaw's block into facePF (o->A and o->PF stay: the keypoint kernels read them), expr_offsets_kernel
+// completes the offsets, and the skinning kernels run on those.  Backward: expr_dpsi_kernel, blend_backward, then face_bwd_kernel takes the
+// sums for A' to sums for A in place, ADDS the term's share to d psi and to the jaw's skinning part where the data term left its own, and
+// J22's share to the betas' entries of dX.  The sums always go to the second buffers and are added on: the first ones hold the data term's,
+// or -- `assigned` false: a map without vertices -- are zeroed here where the data term's kernel wrote none.
+static int fit2d_collision_pass_face(fdcap_ctx* c, bool assigned, double* losses, float* floss, hipStream_t st) {
+    OptState* o = c->opt;
+    const int nl = o->cfg.n_local, R = o->R, V = c->V;
+    const size_t nv3 = (size_t)3 * V;
+    const float* const psi = o->expr_on ? o->psi.p : nullptr;
+    const float* const jaw = o->jaw_on ? o->jaw.p : nullptr;
+    const int nch = face_nchunk(3 * V);
+    if (psi) { int e = ensure_face_tables(c); if (e) return e; }
+    HIP_TRY(o->coll2.ensure((size_t)R * COLL2_LD)); HIP_TRY(o->faceA.ensure((size_t)R * NJ * 12));
+    if (jaw) HIP_TRY(o->facePF.ensure((size_t)R * NPFX));
+    if (psi) HIP_TRY(o->face_part.ensure((size_t)nl * nch * NEXPR));
+    const Coll2 first = {o->dA.p, o->dPF.p, o->dtransl_v.p, o->dMv.p, o->dsv.p};
+    const Coll2 t = coll2_view(o->coll2.p, R);
+    if (!assigned) {                                          // (the expression forms write dA on every path)
+        if (!psi) HIP_TRY(hipMemsetAsync(first.dA + (size_t)2 * NJ * 12, 0, (size_t)nl * NJ * 12 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(first.dPF + (size_t)2 * NPFX, 0, (size_t)nl * NPFX * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(first.dtv + 2 * 3, 0, (size_t)nl * 3 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(first.dMv + 2 * 12, 0, (size_t)nl * 12 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(first.dsv + 2, 0, (size_t)nl * sizeof(float), st));
+    }
+    float* const PF2 = jaw ? o->facePF.p : nullptr;
+    hipLaunchKernelGGL(face_fwd_kernel, dim3(nl), dim3(FACE_NT), 0, st, c->face_tabs(), (const float*)o->A.p, (const float*)o->PF.p, (const float*)nullptr,
+                       (const float*)o->X.p, XDIM, X_BETAS, X_TRANSL, 2, psi, jaw, o->faceA.p, PF2, (float*)nullptr);
+    HIP_TRY(blend_forward(c->full, (PF2 ? PF2 : o->PF.p) + 2 * NPFX, nl, o->VoffF.p + 2 * nv3, st));
+    if (psi)
+        hipLaunchKernelGGL(expr_offsets_kernel, dim3((3 * V + 255) / 256, (nl + FACE_FS - 1) / FACE_FS), dim3(256), 0, st, c->d_Ef.p, c->lde_f, 3 * V, psi,
+                           nl, o->VoffF.p + 2 * nv3, nv3);
+    note_form(form_name(F_SKIN_FWD));
+    hipLaunchKernelGGL(skin_fwd_kernel, dim3((V + 255) / 256, nl), dim3(256), 0, st, c->full.model(), V, o->X.p, XDIM, X_BETAS, X_TRANSL, o->VoffF.p,
+                       o->faceA.p, o->M.p, o->scale.p, 2, 1, o->VwF.p);
+    { int e = fdcap_collision_eval(c, o->VwF.p + 2 * nv3, nl, &o->coll, nullptr, o->coll_count.p, o->coll_loss.p, o->dVF.p + 2 * nv3, st); if (e) return e; }
+    { int es = skin_bwd_any<false>(c->ws_skin, st, nl, c->full.model(), V, o->X.p, o->VoffF.p, o->faceA.p, o->M.p, o->scale.p, 2, o->dVF.p, o->dVF.p, t.dA,
+                                   (float*)nullptr, t.dtv, t.dMv, t.dsv, ContactGradIn()); if (es) return es; }
+    if (psi)
+        hipLaunchKernelGGL(expr_dpsi_kernel, dim3(nch, (nl + FACE_FS - 1) / FACE_FS), dim3(256), 0, st, c->d_Ef.p, c->lde_f, 3 * V,
+                           (const float*)(o->dVF.p + 2 * nv3), nv3, nl, o->face_part.p, nch);
+    HIP_TRY(blend_backward(c->full, o->dVF.p + 2 * nv3, nl, t.dPF + 2 * NPFX, 0, c->ws_kpart, st));
+    hipLaunchKernelGGL(face_bwd_kernel, dim3(nl), dim3(FACE_NT), 0, st, c->face_tabs(), (const float*)o->A.p, (const float*)t.dA, (const float*)o->X.p, XDIM,
+                       X_BETAS, 2, psi, jaw, (const float*)nullptr, psi ? (const float*)o->face_part.p : nullptr, nch, t.dA, psi ? o->dpsi.p : nullptr,
+                       jaw ? o->jawR9.p : nullptr, o->dX.p, 1);
+    hipLaunchKernelGGL(fit2d_coll_add_kernel, dim3(nl), dim3(256), 0, st, t, 2, first.dA, first.dPF, first.dtv, first.dMv, first.dsv);
+    if (jaw) o->jaw_gp = true;                                // (dPF's jaw block is there now, whatever the map holds)
+    if (floss || losses)
+        hipLaunchKernelGGL(fit2d_coll_value_kernel, dim3((nl + 63) / 64), dim3(64), 0, st, (const float*)o->coll_loss.p, nl, floss, losses);
+    return (int)hipGetLastError();
+}
+
 static int fit2d_collision_pass(fdcap_ctx* c, bool second, double* losses, float* floss, hipStream_t st) {
     OptState* o = c->opt;
     const int nl = o->cfg.n_local, R = o->R, V = c->V;
@@ -608,6 +670,7 @@ static int fit2d_collision_pass(fdcap_ctx* c, bool second, double* losses, float
     { int e = ensure_full_set(c); if (e) return e; }
     HIP_TRY(o->VoffF.ensure((size_t)R * nv3)); HIP_TRY(o->VwF.ensure((size_t)R * nv3)); HIP_TRY(o->dVF.ensure((size_t)R * nv3));
     HIP_TRY(o->coll_loss.ensure(nl)); HIP_TRY(o->coll_count.ensure(nl));
+    if (o->coll_face && (o->jaw_on || o->expr_on)) return fit2d_collision_pass_face(c, second, losses, floss, st);
     if (second) HIP_TRY(o->coll2.ensure((size_t)R * COLL2_LD));
     HIP_TRY(blend_forward(c->full, o->PF.p + 2 * NPFX, nl, o->VoffF.p + 2 * nv3, st));
     note_form(form_name(F_SKIN_FWD));
@@ -633,9 +696,9 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
     PoseModel pm = c->pose_model();
     if (o->jaw_on && !o->kp_mapped) return FDCAP_E_STATE;     // (no keypoint of the 23-joint layout follows the jaw)
     const bool coll = o->coll_on;                             // (fdcap_opt_set_fit2d_collision; off: not one launch or argument differs)
-    if (coll && (o->jaw_on || c->coll.h.F <= 0)) return FDCAP_E_STATE;
+    if (coll && ((o->jaw_on && !o->coll_face) || c->coll.h.F <= 0)) return FDCAP_E_STATE;
     const bool expr = o->expr_on;                             // (fdcap_opt_set_expression; off: not one launch or argument differs)
-    if (expr && (!o->kp_mapped || coll || c->kpset.E.p == nullptr)) return FDCAP_E_STATE;      // (the 23-joint layout; the full-mesh pass skins at psi = 0)
+    if (expr && (!o->kp_mapped || (coll && !o->coll_face) || c->kpset.E.p == nullptr)) return FDCAP_E_STATE;      // (the 23-joint layout; without the opt-in the full-mesh pass skins at psi = 0)
     const JawIO jw = {o->jaw.p, o->jawR9.p, {o->w_jaw[0], o->w_jaw[1], o->w_jaw[2]}};
     const bool bend = o->bend.n > 0;                          // (fdcap_opt_set_fit2d_extra; off: not one launch or argument differs)
     int row_lo, row_hi;
@@ -665,12 +728,15 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
             else FDC_EXPR_LAUNCH((fit2d_kp_expr_kernel<false, false>), ex);
 #undef FDC_EXPR_LAUNCH
             if (o->kp_panel) HIP_TRY(blend_backward(c->kpset.ss, o->kpdV.p, nl, o->dPF.p + 2 * NPFX, 0, c->ws_kpart, st));
-            if (bend && vb) hipLaunchKernelGGL(fit2d_bend_kernel<true>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
+            // the self-interpenetration term on the fitted face (fdcap_opt_set_fit2d_collision_face; off: vs = vb, nothing differs)
+            if (coll) { int ec = fit2d_collision_pass(c, vb, losses, floss, st); if (ec) return ec; }
+            const bool vs = vb || coll;
+            if (bend && vs) hipLaunchKernelGGL(fit2d_bend_kernel<true>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
             else if (bend) hipLaunchKernelGGL(fit2d_bend_kernel<false>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
             hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
-                               o->Jrest.p, o->G.p, (const float*)o->dA.p, (vb || bend) ? o->dPF.p : (const float*)nullptr, o->dJw.p,
-                               vb ? o->dMv.p : (const float*)nullptr, vb ? o->dsv.p : (const float*)nullptr,
-                               vb ? o->dPF.p + NPF : (const float*)nullptr, vb ? NPFX : 0, vb ? o->dtransl_v.p : (const float*)nullptr, o->dX.p, o->dO.p,
+                               o->Jrest.p, o->G.p, (const float*)o->dA.p, (vs || bend) ? o->dPF.p : (const float*)nullptr, o->dJw.p,
+                               vs ? o->dMv.p : (const float*)nullptr, vs ? o->dsv.p : (const float*)nullptr,
+                               vs ? o->dPF.p + NPF : (const float*)nullptr, vs ? NPFX : 0, vs ? o->dtransl_v.p : (const float*)nullptr, o->dX.p, o->dO.p,
                                o->dCAM.p, o->dscale_row.p, ParamLossIn(), (const float*)nullptr);
             { int eb = opt_vposer_backward(c, fold, st); if (eb) return eb; }
             return (int)hipGetLastError();

@@ -742,7 +742,6 @@ int fdcap_smplx_backward(fdcap_ctx* c, const float* go, const float* bp, const f
     return (int)hipGetLastError();
 }
 
-// ---- Op 4: self-interpenetration (fdc_collide.h) -------------------------------------------------------------------------------------
 static int ensure_full_set(fdcap_ctx* c) {
     if (c->full_ready) return FDCAP_OK;
     std::vector<int64_t> all(c->V);
@@ -752,6 +751,195 @@ static int ensure_full_set(fdcap_ctx* c) {
     c->full_ready = true;
     return FDCAP_OK;
 }
+
+// ---- Op 2 with the fitted face (fdc_face_mesh.h) ---------------------------------------------------------------------------------------
+// jaw_pose [B,3] and expression [B,10], each NULL on its own; both NULL: the entry point without `_face`, launch for launch.  The chain
+// runs as it does there (jaw = 0, psi = 0); face_fwd_kernel corrects its transforms into ws_face[0] (and the PF row into ws_face[1]),
+// expr_offsets_kernel completes the offsets, and the skinning kernels run on those.
+// the full mesh's expression table, a coefficient's directions along a row, and JE: built at the first call that needs them (as
+// ensure_full_set builds the full vertex set), so that a context that never asks for the face is created as before
+static int ensure_face_tables(fdcap_ctx* c) {
+    if (c->d_JEf.p) return FDCAP_OK;
+    if (c->h_E10.empty()) return FDCAP_E_STATE;            // (a model without expression directions: num_shape < 20)
+    const int V = c->V;
+    c->lde_f = (3 * V + 3) & ~3;
+    std::vector<float> ef((size_t)NEXPR * c->lde_f, 0.f);
+    for (size_t i = 0; i < (size_t)V * 3; ++i)
+        for (int l = 0; l < NEXPR; ++l) ef[(size_t)l * c->lde_f + i] = c->h_E10[i * NEXPR + l];
+    HIP_TRY(c->d_Ef.upload(ef.data(), ef.size()));
+    HIP_TRY(c->d_JEf.upload(c->h_JE.data(), c->h_JE.size()));
+    return FDCAP_OK;
+}
+static int face_args_check(fdcap_ctx* c, const float* jaw, const float* expr) {
+    if (expr) { int e = ensure_face_tables(c); if (e) return e; }
+    if (jaw) for (int j = 0; j < NJ; ++j) if (c->h_parents[j] == JAW_J) return FDCAP_E_ARG;     // (the leaf argument needs a leaf)
+    if (expr) for (int j = 1; j < NJ; ++j) if (c->h_parents[j] >= j) return FDCAP_E_ARG;        // (pose_forward's own condition)
+    return FDCAP_OK;
+}
+// after the pose forward: A' (and PF'), the joints, then -- vertices -- the blend product, E psi and the skinning on A'
+static int face_forward_tail(fdcap_ctx* c, int32_t B, const float* X, const float* PF, const float* G, const float* A, const float* jaw,
+                             const float* expr, const float* Mw, const float* S, int world, float* Voff, float* vertices, float* joints,
+                             hipStream_t st) {
+    const int V = c->V;
+    HIP_TRY(c->ws_face[0].ensure((size_t)B * NJ * 12));
+    if (jaw) HIP_TRY(c->ws_face[1].ensure((size_t)B * NPFX));
+    float* const A2 = c->ws_face[0].p;
+    float* const PF2 = jaw && vertices ? c->ws_face[1].p : nullptr;
+    hipLaunchKernelGGL(face_fwd_kernel, dim3(B), dim3(FACE_NT), 0, st, c->face_tabs(), A, PF, G, X, XDIM, X_BETAS, X_TRANSL, 0, expr, jaw, A2, PF2,
+                       joints);
+    if (vertices) {
+        HIP_TRY(blend_forward(c->full, PF2 ? PF2 : PF, B, Voff, st));
+        if (expr)
+            hipLaunchKernelGGL(expr_offsets_kernel, dim3((3 * V + 255) / 256, (B + FACE_FS - 1) / FACE_FS), dim3(256), 0, st, c->d_Ef.p, c->lde_f,
+                               3 * V, expr, B, Voff, (size_t)3 * V);
+        hipLaunchKernelGGL(skin_fwd_kernel, dim3((V + 255) / 256, B), dim3(256), 0, st, c->full.model(), V, X, XDIM, X_BETAS, X_TRANSL, Voff, A2, Mw,
+                           S, 0, world, vertices);
+    }
+    return (int)hipGetLastError();
+}
+
+static int body_forward_face_impl(fdcap_ctx* c, const float* params, int32_t B, const float* jaw, const float* expr, const float* cam_ext,
+                                  const float* scale, float* vertices, float* joints, hipStream_t st) {
+    { int e = face_args_check(c, jaw, expr); if (e) return e; }
+    if (vertices) { int e = ensure_full_set(c); if (e) return e; }
+    const int V = c->V;
+    const bool world = cam_ext != nullptr && scale != nullptr;
+    DevBuf<float>* w = c->ws_f;
+    HIP_TRY(w[2].ensure((size_t)B * 512)); HIP_TRY(w[3].ensure((size_t)B * 512)); HIP_TRY(w[4].ensure((size_t)B * ODIM));
+    HIP_TRY(w[5].ensure((size_t)B * XDIM)); HIP_TRY(w[6].ensure((size_t)B * NPFX)); HIP_TRY(w[7].ensure((size_t)B * NJ * 12));
+    HIP_TRY(w[8].ensure((size_t)B * NJ * 12)); HIP_TRY(w[9].ensure((size_t)B * 16)); HIP_TRY(w[10].ensure(1));
+    HIP_TRY(w[1].ensure((size_t)B * 12));
+    if (vertices) HIP_TRY(w[11].ensure((size_t)B * 3 * V));
+    float* X = w[5].p;
+    hipLaunchKernelGGL(p75_to_78_kernel, dim3((B + 127) / 128), dim3(128), 0, st, params, B, X);
+    HIP_TRY(c->ws_part.ensure((size_t)4 * B * ODIM));
+    int e = vposer_forward(c, X, XDIM, X_LATENT, 0, B, w[2].p, w[3].p, c->ws_part.p, (size_t)B * ODIM, w[4].p, st);
+    if (e) return e;
+    if (!world) {
+        HIP_TRY(hipMemsetAsync(w[9].p, 0, (size_t)B * 16 * sizeof(float), st));
+        HIP_TRY(hipMemsetAsync(w[10].p, 0, sizeof(float), st));
+    }
+    const float* CAM = world ? cam_ext : w[9].p;
+    const float* S = world ? scale : w[10].p;
+    hipLaunchKernelGGL(pose_fwd_kernel<false>, dim3(B), dim3(64 * POSE_NW), 0, st, c->pose_model(), X, w[4].p, CAM, S, 0,
+                       (float*)nullptr, w[6].p, (float*)nullptr, w[7].p, w[8].p, w[1].p, (float*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr, (size_t)0);
+    return face_forward_tail(c, B, X, w[6].p, w[7].p, w[8].p, jaw, expr, w[1].p, S, world ? 1 : 0, w[11].p, vertices, joints, st);
+}
+
+int fdcap_body_forward_face(fdcap_ctx* c, const float* params, int32_t B, const float* jaw_pose, const float* expression, float* vertices,
+                            float* joints, void* stream) {
+    if (!jaw_pose && !expression) return fdcap_body_forward(c, params, B, vertices, joints, stream);
+    if (!c || !params || B <= 0 || (!vertices && !joints)) return FDCAP_E_ARG;
+    return body_forward_face_impl(c, params, B, jaw_pose, expression, nullptr, nullptr, vertices, joints, (hipStream_t)stream);
+}
+
+int fdcap_world_mesh_face(fdcap_ctx* c, const float* params, int32_t B, const float* jaw_pose, const float* expression, const float* cam_ext,
+                          const float* scale, float* vertices, void* stream) {
+    if (!jaw_pose && !expression) return fdcap_world_mesh(c, params, B, cam_ext, scale, vertices, stream);
+    if (!c || !params || B <= 0 || !cam_ext || !scale || !vertices) return FDCAP_E_ARG;
+    return body_forward_face_impl(c, params, B, jaw_pose, expression, cam_ext, scale, vertices, nullptr, (hipStream_t)stream);
+}
+
+int fdcap_smplx_forward_face(fdcap_ctx* c, const float* go, const float* bp, const float* betas, const float* lh, const float* rh,
+                             const float* transl, int32_t B, const float* jaw_pose, const float* expression, float* vertices, float* joints,
+                             void* stream) {
+    if (!jaw_pose && !expression) return fdcap_smplx_forward(c, go, bp, betas, lh, rh, transl, B, vertices, joints, stream);
+    if (!c || !go || !bp || !betas || !lh || !rh || !transl || B <= 0 || (!vertices && !joints)) return FDCAP_E_ARG;
+    { int e = face_args_check(c, jaw_pose, expression); if (e) return e; }
+    hipStream_t st = (hipStream_t)stream;
+    if (vertices) { int e = ensure_full_set(c); if (e) return e; }
+    const int V = c->V;
+    DevBuf<float>* w = c->ws_f;
+    HIP_TRY(w[4].ensure((size_t)B * 66));
+    HIP_TRY(w[5].ensure((size_t)B * XDIM)); HIP_TRY(w[6].ensure((size_t)B * NPFX)); HIP_TRY(w[7].ensure((size_t)B * NJ * 12));
+    HIP_TRY(w[8].ensure((size_t)B * NJ * 12)); HIP_TRY(w[9].ensure((size_t)B * 16)); HIP_TRY(w[10].ensure(1));
+    if (vertices) HIP_TRY(w[11].ensure((size_t)B * 3 * V));
+    float* X = w[5].p;
+    hipLaunchKernelGGL(assemble_rows_kernel, dim3((B + 127) / 128), dim3(128), 0, st, go, bp, betas, lh, rh, transl, B, X, w[4].p);
+    HIP_TRY(hipMemsetAsync(w[9].p, 0, (size_t)B * 16 * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(w[10].p, 0, sizeof(float), st));
+    hipLaunchKernelGGL(pose_fwd_kernel<false>, dim3(B), dim3(64 * POSE_NW), 0, st, c->pose_model(), X, (float*)nullptr, w[9].p, w[10].p, 0,
+                       (float*)nullptr, w[6].p, (float*)nullptr, w[7].p, w[8].p, (float*)nullptr, (float*)nullptr, (const float*)w[4].p,
+                       (const float*)nullptr, (size_t)0);
+    return face_forward_tail(c, B, X, w[6].p, w[7].p, w[8].p, jaw_pose, expression, nullptr, nullptr, 0, w[11].p, vertices, joints, st);
+}
+
+// g_jaw_pose [B,3] / g_expression [B,10]: may be NULL each (the input is then a constant of the call); an input that is NULL has no
+// gradient: its output must be NULL too.  Two calls give the same bits: every sum in a fixed order.
+int fdcap_smplx_backward_face(fdcap_ctx* c, const float* go, const float* bp, const float* betas, const float* lh, const float* rh,
+                              const float* transl, int32_t B, const float* jaw_pose, const float* expression, const float* g_vertices,
+                              const float* g_joints, float* g_go, float* g_bp, float* g_betas, float* g_lh, float* g_rh, float* g_transl,
+                              float* g_jaw_pose, float* g_expression, void* stream) {
+    if ((g_jaw_pose && !jaw_pose) || (g_expression && !expression)) return FDCAP_E_ARG;
+    if (!jaw_pose && !expression)
+        return fdcap_smplx_backward(c, go, bp, betas, lh, rh, transl, B, g_vertices, g_joints, g_go, g_bp, g_betas, g_lh, g_rh, g_transl, stream);
+    if (!c || !go || !bp || !betas || !lh || !rh || !transl || B <= 0 || (!g_vertices && !g_joints)) return FDCAP_E_ARG;
+    { int e = face_args_check(c, jaw_pose, expression); if (e) return e; }
+    hipStream_t st = (hipStream_t)stream;
+    if (g_vertices) { int e = ensure_full_set(c); if (e) return e; }
+    const int V = c->V;
+    const size_t nv3 = (size_t)3 * V;
+    const int nch = face_nchunk(3 * V);
+    DevBuf<float>* w = c->ws_b;
+    // forward state (recomputed: the operator keeps none): X rows, AA, PF, Rm, Jrest, G, A; then A' and PF'
+    HIP_TRY(w[0].ensure((size_t)B * XDIM)); HIP_TRY(w[1].ensure((size_t)B * 66)); HIP_TRY(w[2].ensure((size_t)B * NPFX));
+    HIP_TRY(w[3].ensure((size_t)B * NJ * 9)); HIP_TRY(w[4].ensure((size_t)B * NJ * 3)); HIP_TRY(w[5].ensure((size_t)B * NJ * 12));
+    HIP_TRY(w[6].ensure((size_t)B * NJ * 12));
+    HIP_TRY(w[7].ensure((size_t)B * NJ * 12)); HIP_TRY(w[8].ensure((size_t)B * 44 + 4)); HIP_TRY(w[9].ensure((size_t)B * NPFX));
+    HIP_TRY(w[10].ensure((size_t)B * XDIM)); HIP_TRY(w[11].ensure((size_t)B * 66));
+    HIP_TRY(c->ws_face[0].ensure((size_t)B * NJ * 12)); HIP_TRY(c->ws_face[1].ensure((size_t)B * NPFX));
+    HIP_TRY(c->ws_face[2].ensure((size_t)B * nch * NEXPR)); HIP_TRY(c->ws_face[3].ensure((size_t)B * 9));
+    float* X = w[0].p; float* AA = w[1].p; float* PF = w[2].p;
+    float* dtv = w[8].p; float* dMv = dtv + (size_t)B * 3; float* dsv = dMv + (size_t)B * 12; float* Mid = dsv + B;
+    float* cam0 = Mid + (size_t)B * 12; float* one = cam0 + (size_t)B * 16;
+    float* const A2 = c->ws_face[0].p;
+    float* const PF2 = jaw_pose && g_vertices ? c->ws_face[1].p : nullptr;
+    float* const R9 = c->ws_face[3].p;
+    hipLaunchKernelGGL(assemble_rows_kernel, dim3((B + 127) / 128), dim3(128), 0, st, go, bp, betas, lh, rh, transl, B, X, AA);
+    HIP_TRY(hipMemsetAsync(cam0, 0, ((size_t)B * 16 + 4) * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(w[10].p, 0, (size_t)B * XDIM * sizeof(float), st));
+    hipLaunchKernelGGL(pose_fwd_kernel<false>, dim3(B), dim3(64 * POSE_NW), 0, st, c->pose_model(), X, (float*)nullptr, cam0, one /* = 0 here */, 0,
+                       w[3].p, PF, w[4].p, w[5].p, w[6].p, (float*)nullptr, (float*)nullptr, (const float*)AA, (const float*)nullptr,
+                       (size_t)0);
+    hipLaunchKernelGGL(face_fwd_kernel, dim3(B), dim3(FACE_NT), 0, st, c->face_tabs(), (const float*)w[6].p, (const float*)PF, (const float*)nullptr,
+                       (const float*)X, XDIM, X_BETAS, X_TRANSL, 0, expression, jaw_pose, A2, PF2, (float*)nullptr);
+    const float* dPF = nullptr; const float* dtr = nullptr; const float* part = nullptr;
+    if (g_vertices) {
+        hipLaunchKernelGGL(identity_rows_kernel, dim3((B * 12 + 255) / 256), dim3(256), 0, st, Mid, B, one);
+        DevBuf<float>* wf = c->ws_f;
+        HIP_TRY(wf[11].ensure((size_t)B * nv3));                 // pose + shape + expression offsets
+        HIP_TRY(wf[0].ensure((size_t)B * nv3));                  // d offsets
+        HIP_TRY(blend_forward(c->full, PF2 ? PF2 : PF, B, wf[11].p, st));
+        if (expression)
+            hipLaunchKernelGGL(expr_offsets_kernel, dim3((3 * V + 255) / 256, (B + FACE_FS - 1) / FACE_FS), dim3(256), 0, st, c->d_Ef.p, c->lde_f,
+                               3 * V, expression, B, wf[11].p, nv3);
+        { int es = skin_bwd_any<false>(c->ws_skin, st, B, c->full.model(), V, X, wf[11].p, A2, Mid, one, 0, g_vertices, wf[0].p, w[7].p,
+                                       (float*)nullptr, dtv, dMv, dsv, ContactGradIn()); if (es) return es; }
+        HIP_TRY(blend_backward(c->full, wf[0].p, B, w[9].p, 0, c->ws_kpart, st));
+        if (g_expression) {
+            hipLaunchKernelGGL(expr_dpsi_kernel, dim3(nch, (B + FACE_FS - 1) / FACE_FS), dim3(256), 0, st, c->d_Ef.p, c->lde_f, 3 * V,
+                               (const float*)wf[0].p, nv3, B, c->ws_face[2].p, nch);
+            part = c->ws_face[2].p;
+        }
+        dPF = w[9].p; dtr = dtv;
+    }
+    // d loss / d A' -> d loss / d A in place (w[7]; without vertices the kernel takes d loss / d A' as zero and assigns every row)
+    hipLaunchKernelGGL(face_bwd_kernel, dim3(B), dim3(FACE_NT), 0, st, c->face_tabs(), (const float*)w[6].p, g_vertices ? (const float*)w[7].p : nullptr,
+                       (const float*)X, XDIM, X_BETAS, 0, expression, jaw_pose, g_joints, part, nch, w[7].p, g_expression, R9, w[10].p, 0);
+    if (g_jaw_pose) {                                        // the fit's own consumer of the jaw's two parts (fdc_fit2d.h), without a prior
+        JawGradIn jg;
+        jg.jaw = const_cast<float*>(jaw_pose); jg.R9 = R9; jg.gP = dPF ? dPF + 9 * (JAW_J - 1) : nullptr; jg.gp_stride = NPFX;
+        hipLaunchKernelGGL(jaw_grad_kernel, dim3((B + 63) / 64), dim3(64), 0, st, jg, B, g_jaw_pose, (float*)nullptr, (float*)nullptr, AdamScalars());
+    }
+    hipLaunchKernelGGL(pose_bwd_op_kernel, dim3(B), dim3(64), 0, st, c->pose_model(), X, AA, w[3].p, w[4].p, w[5].p, (const float*)w[7].p, dPF, dtr,
+                       g_joints, w[10].p, w[11].p);
+    hipLaunchKernelGGL(smplx_bwd_split_kernel, dim3((B + 127) / 128), dim3(128), 0, st, w[10].p, w[11].p, B, g_go, g_bp, g_betas, g_lh,
+                       g_rh, g_transl);
+    return (int)hipGetLastError();
+}
+
+// ---- Op 4: self-interpenetration (fdc_collide.h) -------------------------------------------------------------------------------------
 
 int fdcap_set_collision_mesh(fdcap_ctx* c, int32_t n_faces, const int32_t* faces, const uint8_t* face_part, const uint64_t* ignore) {
     if (!c || n_faces < 0) return FDCAP_E_ARG;

@@ -192,6 +192,8 @@ struct OptState {
     fdcap_collision_params coll = {};
     DevBuf<float> coll_loss;  // ... the term's per-frame values [n_local]
     DevBuf<int> coll_count;   // ... and pairs found [n_local]
+    bool coll_face = false;   // ... may follow a free jaw and free psi (fdcap_opt_set_fit2d_collision_face; off: both are refused as before)
+    DevBuf<float> faceA, facePF, face_part;     // ... then: the corrected transforms [R, 660], the PF rows with the jaw's block [R, 496], d psi's chunk partials
     DevBuf<float> coll2;      // ... the full-mesh pass's sums where the keypoint kernel has assigned the first buffers: dA | dPF | dtransl_v | dMv | dsv
     DevBuf<float> cam_setup;  // ... its camera stage (csrc/fdc_fit2d_init.h): per frame the torso's offsets, the pelvis base and z0 [n_local, CAM_SETUP_LD]
     bool cam_ready = false;   // ... they belong to the current rows and to cam_init's torso (fdcap_opt_set_inputs, any other pose forward: no longer)
@@ -303,6 +305,10 @@ struct fdcap_ctx {
     std::vector<float> h_vt, h_S10, h_lbs;
     std::vector<float> h_E10, h_JE;     // a model with num_shape >= 20: shapedirs' columns 10..19 [3V, 10] and J_regressor times them [55 3][10] (else empty)
     DevBuf<float> d_posedirs, d_S10;    // posedirs [486, 3V] and shapedirs' first ten [3V, 10]: what a vertex set's blend matrix is gathered from (r6: on the device)
+    // the full mesh's expression directions as expr_offsets_kernel / expr_dpsi_kernel read them, [10][lde_f] (column 3 v + k; lde_f = 3V
+    // rounded up to 4), and JE [55 3][10] (csrc/fdc_face_mesh.h; built by the first call that needs them: ensure_face_tables)
+    DevBuf<float> d_Ef, d_JEf;
+    int lde_f = 0;
     // device constants
     DevBuf<float> Jt, Jd, hand_comp, hand_mean;
     DevBuf<int> parents, order, level_start, child_start, child_list, depth;
@@ -365,6 +371,7 @@ struct fdcap_ctx {
     DevBuf<int> ws_cv;              // ... and the positions that travel with them [2][N]; N = max(B n, B m) of the largest call so far
     DevBuf<float> ws_skin;         // chunk partials of the split skinning backward (skin_bwd_any)
     DevBuf<float> ws_kpart;         // K-part partial products of the full-mesh data gradient (blend_backward)
+    DevBuf<float> ws_face[4];       // the `_face` operators: A' [B, 660], PF' [B, 496], d psi's chunk partials [B, nch, 10], the jaw's R9 [B, 9]
     // Op 1 against the registered scene (fdcap_chamfer_fwd_scene): the previous call's neighbours = the next call's seeds
     struct SceneOp {
         DevBuf<float> dist;
@@ -378,6 +385,7 @@ struct fdcap_ctx {
     DevBuf<float> xch_send, xch_all;
     std::string comm_err;
 
+    FaceTabs face_tabs() const { return FaceTabs{d_JEf.p, Jt.p, Jd.p, parents.p, child_start.p, child_list.p, depth.p, nlevels}; }
     PoseModel pose_model() const {
         PoseModel pm;
         pm.tab = pose_tab.p;

@@ -40,6 +40,7 @@ __device__ unsigned long long g_fr_times[3][2048 * 8];
 #include "fdc_fit2d_init.h"
 #include "fdc_frame.h"
 #include "fdc_keypoints.h"
+#include "fdc_face_mesh.h"
 #include "fdc_gemm.h"
 #include "fdc_host_setup.h"
 #include "fdc_lbfgs.h"

@@ -63,7 +63,7 @@ MAX_INIT_EDGES, MAX_INIT_TORSO = 4, 8       # fdcap_fit2d_init's lists
 # part_segm_fn / ign_part_pairs filter of a part against itself and its parent; neither package nor the segmentation file is part of
 # this repository: defaults a caller can replace through collision, never constants of a kernel]
 DEFAULT_COLLISION = dict(faces=None, face_part=None, part_parent=None, ignore_pairs=(), same_part=True, sigma=0.5,
-                         weights=(0.0, 0.0, 0.0, 0.01, 1.0), capacity=4096)
+                         weights=(0.0, 0.0, 0.0, 0.01, 1.0), capacity=4096, follow_face=False)
 COLLISION_PARTS = 64    # parts of include/fdcap.h's 64 x 64 bit matrix
 
 
@@ -206,14 +206,17 @@ class InnerFitOP:
         kept: "auto" for the frames whose shoulders nearly coincide in the image, "both" for all, "given" for none.
         collision: None (off: not one more library call), or a dict with keys of DEFAULT_COLLISION (missing ones take their defaults):
         the self-interpenetration term of csrc/fdc_collide.h on `faces` [F,3] (default: body_model.faces), weighted per stage by
-        `weights`; `face_part` [F] in 0..63, `part_parent`, `ignore_pairs` and `same_part` go through collision_filter.  Not with
-        fit_jaw: the full-mesh pass skins with the shut jaw.
+        `weights`; `face_part` [F] in 0..63, `part_parent`, `ignore_pairs` and `same_part` go through collision_filter.  With
+        fit_jaw or fit_expression it needs `follow_face=True`: the term's full-mesh pass then skins the fitted face
+        (fdcap_opt_set_fit2d_collision_face) and its gradient reaches the jaw and the coefficients; without the key the pass would skin
+        with the shut jaw at expression zero, and both combinations are refused.
         fit_expression: SMPL-X's ten expression coefficients are free per frame next to the row (and the jaw) -- needs a keypoint_map,
-        whose face landmarks are what sees them, and a body model with expression directions (shapedirs [V,3,20]); not with collision
-        (the full-mesh pass skins at expression zero); fitting() leaves them in self.expression.  expression_prior [stages]: the weight
+        whose face landmarks are what sees them, and a body model with expression directions (shapedirs [V,3,20]); with collision only
+        under its `follow_face=True`; fitting() leaves them in self.expression.  expression_prior [stages]: the weight
         w of w^2 |expression|^2 per stage (default DEFAULT_EXPRESSION_PRIOR when stages has its five)."""
         import torch
-        if collision is not None and fit_expression:         # (checked before anything touches the device)
+        follow = bool(collision.get("follow_face", False)) if collision is not None else False
+        if collision is not None and fit_expression and not follow:         # (checked before anything touches the device)
             raise capi.FdcapError("collision does not go with fit_expression: the full-mesh pass skins at expression zero")
         if fit_expression and keypoint_map is None:
             raise capi.FdcapError("fit_expression needs a keypoint_map: the correction runs in the mapped data term")
@@ -233,7 +236,7 @@ class InnerFitOP:
             if unknown:
                 raise capi.FdcapError(f"unknown collision settings {sorted(unknown)}")
             q = {**DEFAULT_COLLISION, **collision}
-            if fit_jaw:
+            if fit_jaw and not follow:
                 raise capi.FdcapError("collision does not go with fit_jaw: the full-mesh pass skins with the shut jaw's transforms")
             faces = q["faces"] if q["faces"] is not None else getattr(body_model, "faces", None)
             if faces is None:
@@ -248,7 +251,8 @@ class InnerFitOP:
             if not 0.0 < float(q["sigma"]) < 1.0 or int(q["capacity"]) <= 0:
                 raise capi.FdcapError("collision: sigma in (0, 1) and capacity > 0")
             ign = collision_filter(q["face_part"], q["part_parent"], q["ignore_pairs"], q["same_part"]) if q["face_part"] is not None or q["ignore_pairs"] else None
-            self.collision = dict(faces=faces, face_part=q["face_part"], ignore=ign, sigma=float(q["sigma"]), weights=w, capacity=int(q["capacity"]))
+            self.collision = dict(faces=faces, face_part=q["face_part"], ignore=ign, sigma=float(q["sigma"]), weights=w, capacity=int(q["capacity"]),
+                                  follow_face=follow)
         if not torch.cuda.is_available():
             raise capi.FdcapError("no HIP device: the fdcap_amd inner fit only runs on the GPU")
         self.device = torch.device("cuda", torch.cuda.current_device())
@@ -280,6 +284,7 @@ class InnerFitOP:
                 self.group_weights = gw
             self.ctx.set_keypoint_map(keypoint_map.joint, keypoint_map.tri, keypoint_map.bary)
         self.fit_jaw, self.jaw_prior, self.jaw_pose = bool(fit_jaw), None, None
+        self.rows75 = None                                    # the rows the last fitting() returned [N,75] (device tensor): what face_mesh() skins
         if self.fit_jaw:
             if keypoint_map is None:
                 raise capi.FdcapError("fit_jaw needs a keypoint_map: no keypoint of the 23-joint layout follows the jaw")
@@ -336,8 +341,21 @@ class InnerFitOP:
         if self.init is None:
             if rows75 is None:
                 raise capi.FdcapError("fitting(None, ...) needs init: without it the rows must already stand in front of the camera")
-            return self._fit(self.n, rows75, keypoints, log_every, jaw_init, expression_init)
-        return self._fit_from_keypoints(rows75, keypoints, log_every, jaw_init, expression_init)
+            self.rows75 = self._fit(self.n, rows75, keypoints, log_every, jaw_init, expression_init)
+        else:
+            self.rows75 = self._fit_from_keypoints(rows75, keypoints, log_every, jaw_init, expression_init)
+        return self.rows75
+
+    def face_mesh(self):
+        """Vertices [N,V,3] (device tensor) of the rows fitting() returned, WITH the fitted face -- self.jaw_pose and self.expression where
+        they were free -- in the frame the keypoints are projected from: SMPL-X's output + transl + camera_translation.  The full mesh
+        through ops.body_forward_from_params (fdcap_body_forward_face)."""
+        from . import ops
+        if self.rows75 is None:
+            raise capi.FdcapError("face_mesh() needs fitted rows: call fitting() first")
+        verts, _ = ops.body_forward_from_params(self.ctx, self.rows75, True, jaw_pose=self.jaw_pose if self.fit_jaw else None,
+                                                expression=self.expression if self.fit_expression else None)
+        return verts + self.rows75[:, None, 72:75]
 
     def _tensor(self, a):
         import torch
@@ -457,6 +475,8 @@ class InnerFitOP:
         rows75, kp = t(rows75), t(keypoints)
         self._setup(n, rows75, kp)
         st = capi.current_stream()
+        if self.collision is not None and self.collision["follow_face"]:      # (before the jaw and the coefficients are set free)
+            capi.check(lib.fdcap_opt_set_fit2d_collision_face(h, 1), "fdcap_opt_set_fit2d_collision_face")
         if self.fit_jaw:
             jaw0 = torch.zeros(n, 3, device=dev) if jaw_init is None else t(jaw_init)
             if tuple(jaw0.shape) != (n, 3):

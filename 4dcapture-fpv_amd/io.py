@@ -44,6 +44,32 @@ def load_body_gen(body_path: str) -> np.ndarray:
     return np.vstack(rows).astype(np.float32)
 
 
+def load_body_face(body_path: str):
+    """The fitted face next to load_body_gen's rows: -> (jaw_pose [N,3] | None, expression [N,10] | None), fp32, from the keys
+    write_body_gen adds (same files, same order).  A key is None when no file has it; a folder where only some files have it is an
+    error.  What ops.BodyModel / ops.world_mesh take as `jaw_pose=` and `expression=`."""
+    files = sorted(glob.glob(os.path.join(body_path, "results/*/*.pkl")))
+    if not files:
+        raise FileNotFoundError(f"no SMPLify-X results under {body_path}/results/*/*.pkl")
+    got = {"jaw_pose": [], "expression": []}
+    for fn in files:
+        with open(fn, "rb") as f:
+            try:
+                d = pickle.load(f)
+            except UnicodeDecodeError:
+                f.seek(0)
+                d = pickle.load(f, encoding="latin1")
+        for k, w in (("jaw_pose", 3), ("expression", 10)):
+            if k in d:
+                got[k].append(np.asarray(d[k], dtype=np.float32).reshape(-1)[:w])
+    out = []
+    for k in ("jaw_pose", "expression"):
+        if got[k] and len(got[k]) != len(files):
+            raise ValueError(f"{len(got[k])} of {len(files)} result files under {body_path} have the key {k!r}")
+        out.append(np.vstack(got[k]).astype(np.float32) if got[k] else None)
+    return out[0], out[1]
+
+
 def load_dct_base(mat_path=None, num_frames: int = 60, num_coef: int = 5) -> np.ndarray:
     """global_optimization.py:131-136: `loadmat(DCT_MAT_PATH)['D'][:DCT_NUM].T` -> [60,5].  The .mat
     (../Data/DCT_Basis/60.mat, :45) is not part of the repository; without it the orthonormal DCT-II

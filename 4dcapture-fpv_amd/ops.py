@@ -216,21 +216,66 @@ class _BodyModelFn(torch.autograd.Function):
         return (*outs, None, None)
 
 
+class _BodyModelFaceFn(torch.autograd.Function):
+    """_BodyModelFn with the fitted face: jaw_pose [B,3] and / or expression [B,10] (either may be None, not both), through
+    fdcap_smplx_forward_face / fdcap_smplx_backward_face."""
+
+    @staticmethod
+    def forward(ctx, go, bp, be, lh, rh, tr, jaw, expr, fctx, return_verts):
+        B, dev = bp.shape[0], bp.device
+        V = fctx.num_verts
+        verts = torch.empty(B, V, 3, device=dev) if return_verts else None
+        joints = torch.empty(B, 55, 3, device=dev)
+        capi.check(fctx.lib.fdcap_smplx_forward_face(fctx.handle, capi.dptr(go), capi.dptr(bp), capi.dptr(be), capi.dptr(lh),
+                                                     capi.dptr(rh), capi.dptr(tr), B, capi.dptr(jaw), capi.dptr(expr), capi.dptr(verts),
+                                                     capi.dptr(joints), capi.current_stream()), "fdcap_smplx_forward_face")
+        ctx.fctx, ctx.return_verts, ctx.has = fctx, return_verts, (jaw is not None, expr is not None)
+        ctx.save_for_backward(go, bp, be, lh, rh, tr, *[t for t in (jaw, expr) if t is not None])
+        if return_verts:
+            return verts, joints
+        return torch.zeros(0, device=dev), joints
+
+    @staticmethod
+    def backward(ctx, gv, gj):
+        go, bp, be, lh, rh, tr, *face = ctx.saved_tensors
+        jaw = face.pop(0) if ctx.has[0] else None
+        expr = face.pop(0) if ctx.has[1] else None
+        fctx = ctx.fctx
+        B = bp.shape[0]
+        gv = gv.contiguous().float() if (ctx.return_verts and gv is not None) else None
+        gj = gj.contiguous().float() if gj is not None else None
+        if gv is None and gj is None:
+            return (None,) * 10
+        ins = (go, bp, be, lh, rh, tr, jaw, expr)
+        outs = [torch.empty_like(t) if (t is not None and need) else None for t, need in zip(ins, ctx.needs_input_grad[:8])]
+        capi.check(fctx.lib.fdcap_smplx_backward_face(fctx.handle, capi.dptr(go), capi.dptr(bp), capi.dptr(be), capi.dptr(lh),
+                                                      capi.dptr(rh), capi.dptr(tr), B, capi.dptr(jaw), capi.dptr(expr), capi.dptr(gv),
+                                                      capi.dptr(gj), *[capi.dptr(o) for o in outs], capi.current_stream()),
+                   "fdcap_smplx_backward_face")
+        return (*outs, None, None)
+
+
 class BodyModel:
-    """smplx.create(..., model_type='smplx', num_pca_comps=12) stand-in, differentiable with respect to all six inputs.
-    `joints` holds the 55 posed joints (the reference reads [:, 0:23])."""
+    """smplx.create(..., model_type='smplx', num_pca_comps=12) stand-in, differentiable with respect to all six inputs and -- when
+    given -- `jaw_pose` [B,3] (joint 22's axis-angle) and `expression` [B,10] (shapedirs' columns 10..19): the two keys the inner fit
+    writes (io.load_body_face).  `joints` holds the 55 posed joints (the reference reads [:, 0:23])."""
 
     def __init__(self, ctx):
         self.fctx = _ctx_of(ctx)
 
     def __call__(self, return_verts=True, body_pose=None, transl=None, global_orient=None, betas=None,
-                 left_hand_pose=None, right_hand_pose=None, **unused):
+                 left_hand_pose=None, right_hand_pose=None, jaw_pose=None, expression=None, **unused):
         B = body_pose.shape[0]
         dev = body_pose.device
         c = lambda t, w: (torch.zeros(B, w, device=dev) if t is None else t.reshape(B, w).float().contiguous())
         go, bp, be = c(global_orient, 3), c(body_pose, 63), c(betas, 10)
         lh, rh, tr = c(left_hand_pose, 12), c(right_hand_pose, 12), c(transl, 3)
-        verts, joints = _BodyModelFn.apply(go, bp, be, lh, rh, tr, self.fctx, bool(return_verts))
+        if jaw_pose is None and expression is None:
+            verts, joints = _BodyModelFn.apply(go, bp, be, lh, rh, tr, self.fctx, bool(return_verts))
+        else:
+            jaw = None if jaw_pose is None else c(jaw_pose, 3)
+            expr = None if expression is None else c(expression, 10)
+            verts, joints = _BodyModelFaceFn.apply(go, bp, be, lh, rh, tr, jaw, expr, self.fctx, bool(return_verts))
         return SimpleNamespace(vertices=verts if return_verts else None, joints=joints)
 
     def to(self, *a, **k):
@@ -280,23 +325,40 @@ class SelfCollision(torch.nn.Module):
         return loss
 
 
-def body_forward_from_params(ctx, params75: torch.Tensor, want_vertices=True):
+def _face_rows(t, B, w, dev, name):
+    if t is None:
+        return None
+    t = torch.as_tensor(t, dtype=torch.float32, device=dev).reshape(-1, w).contiguous()
+    if t.shape[0] != B:
+        raise capi.FdcapError(f"{name} must be [{B}, {w}]")
+    return t
+
+
+def body_forward_from_params(ctx, params75: torch.Tensor, want_vertices=True, jaw_pose=None, expression=None):
     """[B,75] SMPLify-X rows -> (vertices [B,V,3], joints [B,55,3]) through VPoser + SMPL-X in one
-    call (what global_vis.py:131-146 does per frame on the CPU)."""
+    call (what global_vis.py:131-146 does per frame on the CPU).  jaw_pose [B,3] / expression [B,10]: the fitted face
+    (io.load_body_face); None each: the jaw shut, psi = 0."""
     fctx = _ctx_of(ctx)
     p = params75.float().contiguous()
     B = p.shape[0]
     verts = torch.empty(B, fctx.num_verts, 3, device=p.device) if want_vertices else None
     joints = torch.empty(B, 55, 3, device=p.device)
-    capi.check(fctx.lib.fdcap_body_forward(fctx.handle, capi.dptr(p), B, capi.dptr(verts), capi.dptr(joints),
-                                           capi.current_stream()), "fdcap_body_forward")
+    jaw, expr = _face_rows(jaw_pose, B, 3, p.device, "jaw_pose"), _face_rows(expression, B, 10, p.device, "expression")
+    if jaw is None and expr is None:
+        capi.check(fctx.lib.fdcap_body_forward(fctx.handle, capi.dptr(p), B, capi.dptr(verts), capi.dptr(joints),
+                                               capi.current_stream()), "fdcap_body_forward")
+    else:
+        capi.check(fctx.lib.fdcap_body_forward_face(fctx.handle, capi.dptr(p), B, capi.dptr(jaw), capi.dptr(expr), capi.dptr(verts),
+                                                    capi.dptr(joints), capi.current_stream()), "fdcap_body_forward_face")
     return verts, joints
 
 
-def world_mesh(ctx, params75: torch.Tensor, scale, camera_ext: torch.Tensor, shape_from_first: bool = False):
+def world_mesh(ctx, params75: torch.Tensor, scale, camera_ext: torch.Tensor, shape_from_first: bool = False, jaw_pose=None,
+               expression=None):
     """World-space vertices [B,V,3] of optimised results: what global_vis.py:116-152 computes frame by
     frame on the CPU (`verts * scale`, then `camera_ext @ T(camera_translation * scale)`).
-    shape_from_first=True reuses frame 0's betas for every frame like the viewer does (:118-119, :141)."""
+    shape_from_first=True reuses frame 0's betas for every frame like the viewer does (:118-119, :141).
+    jaw_pose [B,3] / expression [B,10]: the fitted face (io.load_body_face); None each: the jaw shut, psi = 0."""
     fctx = _ctx_of(ctx)
     p = params75.float().contiguous().clone()
     if shape_from_first:
@@ -305,6 +367,11 @@ def world_mesh(ctx, params75: torch.Tensor, scale, camera_ext: torch.Tensor, sha
     cam = camera_ext.float().reshape(B, 16).contiguous()
     s = torch.as_tensor(scale, dtype=torch.float32, device=p.device).reshape(1).contiguous()
     verts = torch.empty(B, fctx.num_verts, 3, device=p.device)
-    capi.check(fctx.lib.fdcap_world_mesh(fctx.handle, capi.dptr(p), B, capi.dptr(cam), capi.dptr(s), capi.dptr(verts),
-                                         capi.current_stream()), "fdcap_world_mesh")
+    jaw, expr = _face_rows(jaw_pose, B, 3, p.device, "jaw_pose"), _face_rows(expression, B, 10, p.device, "expression")
+    if jaw is None and expr is None:
+        capi.check(fctx.lib.fdcap_world_mesh(fctx.handle, capi.dptr(p), B, capi.dptr(cam), capi.dptr(s), capi.dptr(verts),
+                                             capi.current_stream()), "fdcap_world_mesh")
+    else:
+        capi.check(fctx.lib.fdcap_world_mesh_face(fctx.handle, capi.dptr(p), B, capi.dptr(jaw), capi.dptr(expr), capi.dptr(cam), capi.dptr(s),
+                                                  capi.dptr(verts), capi.current_stream()), "fdcap_world_mesh_face")
     return verts

@@ -257,6 +257,26 @@ int fdcap_smplx_backward(fdcap_ctx* ctx, const float* global_orient_d, const flo
                          const float* g_vertices_d, const float* g_joints_d, float* g_global_orient_d,
                          float* g_body_pose_d, float* g_betas_d, float* g_left_hand_pose_d,
                          float* g_right_hand_pose_d, float* g_transl_d, void* stream);
+/* Op 2 WITH THE FITTED FACE (csrc/fdc_face_mesh.h): the four entry points above with the two keys the inner fit writes next to its
+ * rows -- jaw_pose_d [B,3], joint 22's axis-angle (the same Rodrigues as the fit's jaw), and expression_d [B,10], SMPL-X's expression
+ * coefficients (shapedirs' columns 10..19).  Each may be NULL on its own (the jaw shut, psi = 0); with both NULL a call is the entry
+ * point without `_face`: the same launches, the same bits.  Vertices and the 55 joints are those of smplx with `expression` in the
+ * shape components and `jaw_pose` in joint 22's slot (the jaw moves no joint).  The backward adds g_jaw_pose_d [B,3] and
+ * g_expression_d [B,10] (NULL: not wanted; FDCAP_E_ARG for the gradient of an input that is NULL); every sum runs in a fixed order, so
+ * two calls give the same bits.
+ * FDCAP_E_STATE: expression_d on a model with num_shape < 20.  FDCAP_E_ARG: jaw_pose_d on a model whose joint 22 has a child. */
+int fdcap_body_forward_face(fdcap_ctx* ctx, const float* params_d, int32_t B, const float* jaw_pose_d, const float* expression_d,
+                            float* vertices_d, float* joints_d, void* stream);
+int fdcap_world_mesh_face(fdcap_ctx* ctx, const float* params_d, int32_t B, const float* jaw_pose_d, const float* expression_d,
+                          const float* cam_ext_d, const float* scale_d, float* vertices_d, void* stream);
+int fdcap_smplx_forward_face(fdcap_ctx* ctx, const float* global_orient_d, const float* body_pose_d, const float* betas_d,
+                             const float* left_hand_pose_d, const float* right_hand_pose_d, const float* transl_d, int32_t B,
+                             const float* jaw_pose_d, const float* expression_d, float* vertices_d, float* joints_d, void* stream);
+int fdcap_smplx_backward_face(fdcap_ctx* ctx, const float* global_orient_d, const float* body_pose_d, const float* betas_d,
+                              const float* left_hand_pose_d, const float* right_hand_pose_d, const float* transl_d, int32_t B,
+                              const float* jaw_pose_d, const float* expression_d, const float* g_vertices_d, const float* g_joints_d,
+                              float* g_global_orient_d, float* g_body_pose_d, float* g_betas_d, float* g_left_hand_pose_d,
+                              float* g_right_hand_pose_d, float* g_transl_d, float* g_jaw_pose_d, float* g_expression_d, void* stream);
 
 /* ---- parameter-vector conversions (global_optimization.py:96-115, cvae.py:62-93) ----------- */
 int fdcap_params_75_to_78(const float* p75_d, int32_t B, float* x78_d, void* stream);
@@ -571,7 +591,10 @@ int fdcap_opt_set_fit2d_extra(fdcap_ctx* ctx, const fdcap_fit2d_extra* extra);
  * pose-feature block of that joint and its skinning transform and nothing else: the vertices skinned to the jaw follow it, no joint
  * moves.  From here on fdcap_debug_keypoints3d, fdcap_opt_backward_fit2d and fdcap_opt_fit2d_lbfgs (81 unknowns per frame: the row,
  * then the jaw) honour it, fdcap_opt_step_x steps it with the rows' lr and step number, fdcap_opt_reset_adam zeroes its moments too.
- * fdcap_opt_get_results, the full-mesh operators and the clip-level modes keep the jaw at zero.
+ * fdcap_opt_get_results and the clip-level modes keep the jaw at zero (the self-interpenetration term too, unless
+ * fdcap_opt_set_fit2d_collision_face opts in); the full-mesh operators
+ * take it, and the expression coefficients, through their `_face` forms (fdcap_smplx_forward_face, fdcap_body_forward_face,
+ * fdcap_world_mesh_face: what turns fdcap_opt_get_jaw / fdcap_opt_get_expression back into vertices).
  * FDCAP_E_ARG: a model whose joint 22 has a child.  FDCAP_E_STATE: no optimiser, a batch of clips or one rank's share of a clip; and
  * from an evaluation with a free jaw on the 23-joint layout (fdcap_opt_set_keypoints: no keypoint there follows the jaw). */
 int fdcap_opt_set_jaw(fdcap_ctx* ctx, const float* jaw_d, void* stream);
@@ -586,7 +609,8 @@ int fdcap_opt_get_jaw(fdcap_ctx* ctx, float* jaw_d, float* djaw_d, void* stream)
  * psi, then the jaw; fdcap_opt_fit2d_lbfgs_rolled_back counts as before and psi is rolled back with its row) honour them,
  * fdcap_opt_step_x steps them with the rows' lr and step number, fdcap_opt_reset_adam zeroes their moments too.  The camera stage
  * (fdcap_opt_backward_fit2d_camera, fdcap_opt_fit2d_camera_lbfgs) ignores them and leaves them where they are; fdcap_opt_get_results,
- * the full-mesh operators and the clip-level modes keep psi = 0.  fdcap_fit2d_select does not carry them: gather them with chosen_d.
+ * the clip-level modes and -- without fdcap_opt_set_fit2d_collision_face -- the self-interpenetration term keep psi = 0 (the full-mesh
+ * operators take it through their `_face` forms).  fdcap_fit2d_select does not carry them: gather them with chosen_d.
  * FDCAP_E_ARG: a model with a joint in front of its parent.  FDCAP_E_STATE: no optimiser, a batch of clips, one rank's share of a clip,
  * a model with num_shape < 20; from an evaluation on the 23-joint layout (fdcap_opt_set_keypoints: the correction runs in the mapped
  * term's kernel); and together with the self-interpenetration term, at the evaluation or in fdcap_opt_set_fit2d_collision (the
@@ -610,6 +634,14 @@ int fdcap_opt_set_expression_prior(fdcap_ctx* ctx, float w_expr);
  * later: the full-mesh pass skins with the transforms the pose kernels wrote, in which the jaw is shut). */
 #define FDCAP_LOSS_FIT2D_COLLISION 4
 int fdcap_opt_set_fit2d_collision(fdcap_ctx* ctx, const fdcap_collision_params* params);
+/* OPT-IN: the term may follow a free jaw and free expression coefficients.  on != 0: fdcap_opt_set_fit2d_collision accepts both, and
+ * the term's full-mesh pass skins the FITTED face (csrc/fdc_face_mesh.h: the corrected transforms, the jaw's pose-feature block, E psi on the
+ * offsets); its share of d psi and of the jaw's two gradient parts joins the data term's in a fixed order, in the arrays fdcap_opt_get_jaw /
+ * fdcap_opt_get_expression, fdcap_opt_step_x and fdcap_opt_fit2d_lbfgs read, and fdcap_opt_fit2d_frame_loss includes the term.  0 (the
+ * default): a free jaw and free psi are refused as above, and with the term off or the face fixed not one launch or argument of an
+ * evaluation differs.  Still FDCAP_E_STATE: no optimiser, a batch of clips, one rank's share of a clip; and, from an evaluation, a free
+ * jaw or psi on the 23-joint layout. */
+int fdcap_opt_set_fit2d_collision_face(fdcap_ctx* ctx, int32_t on);
 int fdcap_opt_reset_adam(fdcap_ctx* ctx, void* stream);
 
 /* ---- batched L-BFGS with a strong-Wolfe line search (csrc/fdc_lbfgs.h) ----
