@@ -1419,14 +1419,15 @@ struct NNOrder {
     int sorted_groups = 0;      // number of groups the current table was sorted for (0: none yet)
     int cur = 0;                // which of the two order tables is current
     int age = 0;                // launches since it was written
-    int every = 32;             // re-sort period (work per group drifts over tens of iterations)
+    int every = 32;             // base re-sort period (work per group drifts over tens of iterations); the period in force follows
+                                // the fit's rebuild count: nn_order_period(every, n_rebuilds, nq), fdc_forms.h
     // r7: the query order (NNCache::perm).  Rebuilt after the seeding launch and then in place of every re-sort of the launch
     // order, which follows it one launch later (the work items it sorts must be the new groups').
     int* qbuf = nullptr;        // device: perm [nq] + sort scratch (nn_query_order_ints); nullptr: no query order
     int perm_n = 0;             // the nq perm holds an order for (0: none yet)
     int perm_mode = 0;          // 0: locality order, rebuilt; 1: identity; 2: imposed by the caller, never rebuilt (fdcap_debug_nn_query_order)
     // tests / diagnosis (fdcap_debug_contact_diet): launches that kept unchanged records (NNCache::keep), launches that ran under a
-    // query order, rebuilds of the query order
+    // query order, rebuilds of the query order in the current fit (restarts with the fit's seeding launch: the period follows it)
     int n_kept = 0, n_permuted = 0, n_rebuilds = 0;
     // r15 (fdcap_debug_nn_box_tests): one-wave launches by the lanes per box they were given (by count, 2, 4, 8)
     int n_box[4] = {0, 0, 0, 0};
@@ -1458,7 +1459,8 @@ static inline hipError_t nn_stream_upkeep(const NNCache& nc, NNOrder* ord, int g
                                           hipStream_t st) {
     const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && wpg == 1;
     const bool qorder = ordered && ord->qbuf != nullptr && ord->perm_mode != 1;
-    const bool resort = ordered && (ord->sorted_groups != groups || ++ord->age >= ord->every);
+    if (ord && seed_missing) ord->n_rebuilds = 0;             // a fit's first launch: its schedule starts over
+    const bool resort = ordered && (ord->sorted_groups != groups || ++ord->age >= nn_order_period(ord->every, ord->n_rebuilds, nq));
     if (qorder && ord->perm_mode == 0 && (ord->perm_n != nq || seed_missing || (resort && ord->sorted_groups == groups))) {
         // new groups: their kept lists go (hdr = -1, by the key kernel), the next launch records its work items in
         // plain launch order and the launch order is sorted after it

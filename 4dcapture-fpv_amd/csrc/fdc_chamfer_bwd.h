@@ -56,7 +56,7 @@ static inline hipError_t cb_group(const int* idx, int B, int cnt, int ndest, boo
         const size_t a = (size_t)(pass & 1) * total, b = (size_t)((pass & 1) ^ 1) * total;
         hipLaunchKernelGGL(sc_rs_hist_kernel, dim3(nb), dim3(256), 0, st, key + a, total, 8 * pass, hist, nb);
         hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
-        hipLaunchKernelGGL(nn_qs_scatter_kernel, dim3(nb), dim3(256), 0, st, key + a, val + a, key + b, val + b, total, 8 * pass, hist, tot, nb);
+        hipLaunchKernelGGL((nn_qs_scatter_kernel<QS_ROUNDS>), dim3(nb), dim3(256), 0, st, key + a, val + a, key + b, val + b, total, 8 * pass, hist, tot, nb);
     }
     *buf = passes & 1;
     return hipGetLastError();

@@ -46,7 +46,7 @@ struct FormSwitches {
     // 1 / 2 / 4 waves per group of 32 queries; unset (< 0): waves per group by launch size
     int nn_stream = -2;
     bool nn_seed = true, nn_cull = true;      // FDCAP_NN_SEED=0 / FDCAP_NN_CULL=0: no seeds from the last iteration / no chunk culling
-    int nn_order = 32;           // FDCAP_NN_ORDER: re-sort period of the in-loop search's launch order; 0 turns it off
+    int nn_order = 32;           // FDCAP_NN_ORDER: base re-sort period of the in-loop search's launch and query order (nn_order_period below); 0 turns it off
     float nn_cache_slack = 0.03f;             // FDCAP_NN_CACHE_SLACK: metres; 0 disables the kept work lists
     bool skin_vec = true;        // FDCAP_SKIN_VEC=0 (A/B): the scalar-load skinning backward
     bool fuse_skin = true;       // FDCAP_FUSE_SKIN=0 (A/B): blend product and skinning forward as two launches
@@ -380,6 +380,35 @@ constexpr FDC_FORMS_HD unsigned long long nn_box_fold(unsigned long long hits, i
 // written in ascending entry order.  nn_box_count: how many the pass keeps.
 FDC_FORMS_HD inline int nn_box_rank(unsigned long long folded, int lane) { return __builtin_popcountll(folded & ((1ull << lane) - 1ull)); }
 FDC_FORMS_HD inline int nn_box_count(unsigned long long folded) { return __builtin_popcountll(folded); }
+
+// r18.  When the streaming search's query order is rebuilt (fdc_chamfer.h NNOrder, nn_stream_upkeep): the period, in search
+// launches, that follows the fit's `rebuilds`-th rebuild (1: the one after the seeding launch) of an order over nq queries.  base
+// is FDCAP_NN_ORDER; 0: off.  A rebuild costs about 80 us at 512 k queries (six sort launches 57, the launch-order sort 13, the next
+// search launch's dropped lists 10) and pays only while the neighbours still move between quarters: on a config-3 fit a fixed
+// period of 128 loses to 32 only in launches 25-125 (+0.9 .. +3.4 us per launch, 240 us in all), 64 to 32 only in launches 25-75,
+// and from launch 130 on 32, 64 and 128 run the same launches within 1 us (profiles/r18_search_upkeep_ab.txt).  So the first
+// NN_PERIOD_HOLD rebuilds keep the base period -- about a hundred launches at the default 32 -- and every later one doubles it, up
+// to NN_PERIOD_MAX.  A shorter first period gained nothing (16 against 32 over launches 1-100: 51.3 / 51.3 us per launch), so
+// there is none.  The rule knows the rebuild count alone, not the fit's length.  Never decreasing in `rebuilds`; a base above
+// NN_PERIOD_MAX stays as given.
+// The rule is open-loop: the host enqueues a whole fit ahead of the device and cannot see how far the bodies still move.  What a
+// skipped rebuild saves is a rebuild (60-100 us up to 2 M queries); what a stale order can cost grows with the search launch.
+// Config 5 (5.36 M queries, 0.6 ms per launch) still moves its bodies by centimetres in launches 100-300, and there the growing
+// period LOSES: launches 200-300 ran 549-771 us against 436-627 under the fixed 32, 2.8 % of the step.  With config 3's body and
+// scene the growing period wins at 128 k, 150 k, 512 k, 1.02 M and 2.05 M queries (search launch unchanged or faster, 7 rebuilds
+// fewer).  So it is taken up to NN_PERIOD_GROW_MAX_QUERIES, the largest size it was measured to win at; above, the fixed base.
+// -DFDC_NN_PERIOD_GROWTH=0 (A/B): the fixed period of every build before r18.
+#ifndef FDC_NN_PERIOD_GROWTH
+#define FDC_NN_PERIOD_GROWTH 1
+#endif
+constexpr int NN_PERIOD_HOLD = 3, NN_PERIOD_MAX = 128, NN_PERIOD_GROW_MAX_QUERIES = 1 << 21;
+constexpr FDC_FORMS_HD int nn_order_period(int base, int rebuilds, int nq) {
+    if (base <= 0) return 0;
+    int p = base;
+    if (FDC_NN_PERIOD_GROWTH && nq <= NN_PERIOD_GROW_MAX_QUERIES)
+        for (int r = NN_PERIOD_HOLD; r < rebuilds && p < NN_PERIOD_MAX; ++r) p = 2 * p < NN_PERIOD_MAX ? 2 * p : NN_PERIOD_MAX;
+    return p;
+}
 
 struct NNPlan {
     Form form = F_NN_DIRECT;

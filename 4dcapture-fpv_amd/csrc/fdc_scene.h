@@ -138,21 +138,32 @@ __global__ __launch_bounds__(256) void sc_rs_scatter_kernel(const unsigned* __re
 // build's sort above would give, without its one-workgroup scan of all 256 x blocks counters.  Six launches: keys + pass-0
 // histogram | row prefixes | scatter | pass-1 histogram | row prefixes | scatter.  A launch boundary is the only synchronisation
 // between workgroups.  Buffer: perm [nq] | values [nq] | keys [2][nq] | histogram [256 x blocks] | digit totals [256].
-constexpr int QS_ROUNDS = 16;                    // a 256-thread block sorts 16 rounds of 256 keys
+// r18: a block's tile is ROUNDS rounds of 256 keys, 16 or 8.  With 4096-key tiles the 512 000 queries of config 3 are 125 blocks on
+// 256 CUs; 2048-key tiles make them 250 and every tile-sized launch shorter.  They also double the counter matrix the row kernel
+// walks and the blocks that scan the 256 totals, which loses once the 4096-key blocks fill the chip anyway.  The rebuild alone on
+// uniform positions (tools/query_sort_check.py, 4096 -> 2048-key tiles, us): 512 k queries 65.6 -> 49.1, 786 k 68.5 -> 54.8,
+// 1.04 M 70.2 -> 60.8, 1.57 M 77.7 -> 74.7, 2.1 M 92.5 -> 97.0, 5.36 M (config 5) 194 -> 204 (profiles/r18_search_upkeep_ab.txt).
+// So the short tile is taken while the long one would leave CUs without a block (QS_FILL_BLOCKS: the chip's 256 CUs), which
+// stays below the measured crossover.
+constexpr int QS_ROUNDS = 16;                    // a 256-thread block sorts 16 rounds of 256 keys (the tile of every other user of these kernels)
 constexpr int QS_TILE = 256 * QS_ROUNDS;
-static inline int nn_query_order_blocks(int nq) { return (nq + QS_TILE - 1) / QS_TILE; }
+constexpr int QS_ROUNDS_SHORT = 8, QS_FILL_BLOCKS = 256;
+static inline int nn_query_order_rounds(int nq) { return (nq + QS_TILE - 1) / QS_TILE < QS_FILL_BLOCKS ? QS_ROUNDS_SHORT : QS_ROUNDS; }
+static inline int nn_query_order_blocks(int nq) { const int tile = 256 * nn_query_order_rounds(nq); return (nq + tile - 1) / tile; }
 static inline size_t nn_query_order_ints(int nq) { return 4 * (size_t)nq + 256 * (size_t)nn_query_order_blocks(nq) + 256; }
 
 // key and identity value of every query, the per-tile histogram of the low digit (hist[digit][tile]) and hdr[0 .. groups) = -1
+template <int ROUNDS>
 __global__ __launch_bounds__(256) void nn_qs_keys_kernel(const float4* __restrict__ seedpt, int nq, unsigned* __restrict__ key,
                                                          int* __restrict__ val, unsigned* __restrict__ hist, int nb,
                                                          int* __restrict__ hdr, int groups) {
+    constexpr int TILE = 256 * ROUNDS;
     __shared__ unsigned h[256];
     const int tid = threadIdx.x;
     h[tid] = 0;
     __syncthreads();
-    const int tile0 = blockIdx.x * QS_TILE;
-    for (int r = 0; r < QS_ROUNDS; ++r) {
+    const int tile0 = blockIdx.x * TILE;
+    for (int r = 0; r < ROUNDS; ++r) {
         const int i = tile0 + r * 256 + tid;
         if (i < nq) {
             const int pos = __float_as_int(seedpt[i].w);          // -1: no neighbour (a NaN query): last
@@ -163,19 +174,20 @@ __global__ __launch_bounds__(256) void nn_qs_keys_kernel(const float4* __restric
         }
     }
     // the groups change: no kept list survives (the last block takes whatever lies beyond the tiles)
-    const int ghi = blockIdx.x == gridDim.x - 1 ? groups : min(groups, tile0 + QS_TILE);
+    const int ghi = blockIdx.x == gridDim.x - 1 ? groups : min(groups, tile0 + TILE);
     for (int i = tile0 + tid; i < ghi; i += 256) hdr[i] = -1;
     __syncthreads();
     hist[(size_t)tid * nb + blockIdx.x] = h[tid];
 }
 
 // pass 1's per-tile histogram (the high digit of the keys as pass 0 left them)
+template <int ROUNDS>
 __global__ __launch_bounds__(256) void nn_qs_hist_kernel(const unsigned* __restrict__ keys, int n, unsigned* __restrict__ hist, int nb) {
     __shared__ unsigned h[256];
     h[threadIdx.x] = 0;
     __syncthreads();
-    const int tile0 = blockIdx.x * QS_TILE;
-    for (int r = 0; r < QS_ROUNDS; ++r) {
+    const int tile0 = blockIdx.x * (256 * ROUNDS);
+    for (int r = 0; r < ROUNDS; ++r) {
         const int i = tile0 + r * 256 + threadIdx.x;
         if (i < n) atomicAdd(&h[(keys[i] >> 8) & 255u], 1u);
     }
@@ -208,6 +220,7 @@ __global__ __launch_bounds__(256) void nn_qs_rows_kernel(unsigned* __restrict__ 
 
 // one pass, as sc_rs_scatter_kernel, but hist holds the row-local prefixes and tot the 256 digit totals: the block forms the
 // digit bases itself (one 256-entry exclusive scan) and adds its own row-local prefix
+template <int ROUNDS = QS_ROUNDS>
 __global__ __launch_bounds__(256) void nn_qs_scatter_kernel(const unsigned* __restrict__ kin, const int* __restrict__ vin,
                                                             unsigned* __restrict__ kout, int* __restrict__ vout, int n, int shift,
                                                             const unsigned* __restrict__ hist, const unsigned* __restrict__ tot, int nb) {
@@ -226,8 +239,8 @@ __global__ __launch_bounds__(256) void nn_qs_scatter_kernel(const unsigned* __re
         for (int k = 0; k < wave; ++k) off += wtot[k];
         base[tid] = off + hist[(size_t)tid * nb + blockIdx.x];
     }
-    const int tile0 = blockIdx.x * QS_TILE;
-    for (int r = 0; r < QS_ROUNDS; ++r) {
+    const int tile0 = blockIdx.x * (256 * ROUNDS);
+    for (int r = 0; r < ROUNDS; ++r) {
         const int i = tile0 + r * 256 + tid;
         const bool valid = i < n;
         const unsigned key = valid ? kin[i] : 0u;
@@ -257,6 +270,17 @@ __global__ __launch_bounds__(256) void nn_qs_scatter_kernel(const unsigned* __re
     }
 }
 
+template <int ROUNDS>
+static inline void nn_query_order_launches(const float4* seedpt, int nq, unsigned* key, int* perm, int* val, unsigned* hist, unsigned* tot, int nb,
+                                           int* hdr, int groups, hipStream_t st) {
+    // 16-bit keys: (perm, key) -> (val, key + nq) -> (perm, key)
+    hipLaunchKernelGGL((nn_qs_keys_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, seedpt, nq, key, perm, hist, nb, hdr, groups);
+    hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
+    hipLaunchKernelGGL((nn_qs_scatter_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, key, perm, key + nq, val, nq, 0, hist, tot, nb);
+    hipLaunchKernelGGL((nn_qs_hist_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, key + nq, nq, hist, nb);
+    hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
+    hipLaunchKernelGGL((nn_qs_scatter_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, key + nq, val, key, perm, nq, 8, hist, tot, nb);
+}
 static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st) {
     const int nb = nn_query_order_blocks(nq);
     int* const perm = qbuf;
@@ -264,13 +288,8 @@ static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf,
     unsigned* const key = (unsigned*)(qbuf + 2 * (size_t)nq);
     unsigned* const hist = key + 2 * (size_t)nq;
     unsigned* const tot = hist + 256 * (size_t)nb;
-    // 16-bit keys: (perm, key) -> (val, key + nq) -> (perm, key)
-    hipLaunchKernelGGL(nn_qs_keys_kernel, dim3(nb), dim3(256), 0, st, seedpt, nq, key, perm, hist, nb, hdr, groups);
-    hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
-    hipLaunchKernelGGL(nn_qs_scatter_kernel, dim3(nb), dim3(256), 0, st, key, perm, key + nq, val, nq, 0, hist, tot, nb);
-    hipLaunchKernelGGL(nn_qs_hist_kernel, dim3(nb), dim3(256), 0, st, key + nq, nq, hist, nb);
-    hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
-    hipLaunchKernelGGL(nn_qs_scatter_kernel, dim3(nb), dim3(256), 0, st, key + nq, val, key, perm, nq, 8, hist, tot, nb);
+    if (nn_query_order_rounds(nq) == QS_ROUNDS_SHORT) nn_query_order_launches<QS_ROUNDS_SHORT>(seedpt, nq, key, perm, val, hist, tot, nb, hdr, groups, st);
+    else nn_query_order_launches<QS_ROUNDS>(seedpt, nq, key, perm, val, hist, tot, nb, hdr, groups, st);
     return hipGetLastError();
 }
 
