@@ -145,7 +145,8 @@ def test_dct_mode_legacy_zero_grad_lets_c_dct_coast():
 
 
 def test_dct_gradient_matches_autograd():
-    """d(1e-4 dct + 0.5 rec + 0.1 contact)/d(body_rotation_rec, scale) vs fp64 autograd."""
+    """d(1e-4 dct + 0.5 rec + 0.1 contact)/d(body_rotation_rec, scale) vs fp64 autograd.
+    The tight check of the DCT term alone, per column block, is tests/test_gpu_local2_bars.py (bars: tests/dct_bars.py)."""
     n = 120
     bm, vp, clip, scene, vid, c0 = _dct_case(n, 160, 900, seed=77)
     D = load_dct_base(None)

@@ -208,7 +208,8 @@ def test_second_loop_gradient_of_a_ragged_batch_matches_the_fp64_oracle(model):
     """Lengths (10, 7, 3), parameters perturbed by 0.01 randn, the caller's own weights through jj0 = 1, jj1 = 2, flags = 1: two
     frames per clip at 0.8 and 0.3 (the thresholding of :421-422 on both sides of 0.5), a clip's first and a clip's last frame among
     them (pair (i, i + 1) uses w[i + 1] of the SAME clip).  Each clip's gradient against cal_loss2 of that clip alone; the bars are
-    those of test_gpu_parity.py::test_local_mode_second_loop_gradient_matches_autograd (the same arithmetic)."""
+    those of test_gpu_parity.py::test_local_mode_second_loop_gradient_matches_autograd (the same arithmetic).
+    The tight check of a batch's gradient, per clip and column block, is tests/test_gpu_local2_bars.py."""
     bm, vp, scene, vid = model
     lens = (10, 7, 3)
     clips_d = [synth.make_clip(n, seed=90 + k, num_outliers=2) for k, n in enumerate(lens)]

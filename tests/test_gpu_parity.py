@@ -871,6 +871,7 @@ def test_local_mode_checkpoint_resume_is_bit_identical(tmp_path):
 
 
 def test_local_mode_second_loop_gradient_matches_autograd():
+    """The whole-matrix bar with all four terms mixed; the tight check, per column block, is tests/test_gpu_local2_bars.py."""
     n = 10
     fop, bm, vp, clip, scene, vid = _make_fop(n, 260, 700, 12, 500, seed=90)
     dt = torch.float64
