@@ -633,7 +633,7 @@ static int fit2d_collision_pass_face(fdcap_ctx* c, bool assigned, double* losses
         if (!psi) HIP_TRY(hipMemsetAsync(first.dA + (size_t)2 * NJ * 12, 0, (size_t)nl * NJ * 12 * sizeof(float), st));
         HIP_TRY(hipMemsetAsync(first.dPF + (size_t)2 * NPFX, 0, (size_t)nl * NPFX * sizeof(float), st));
         HIP_TRY(hipMemsetAsync(first.dtv + 2 * 3, 0, (size_t)nl * 3 * sizeof(float), st));
-        HIP_TRY(hipMemsetAsync(first.dMv + 2 * 12, 0, (size_t)nl * 12 * sizeof(float), st));
+        if (!psi) HIP_TRY(hipMemsetAsync(first.dMv + 2 * 12, 0, (size_t)nl * 12 * sizeof(float), st));    // (... and dMv)
         HIP_TRY(hipMemsetAsync(first.dsv + 2, 0, (size_t)nl * sizeof(float), st));
     }
     float* const PF2 = jaw ? o->facePF.p : nullptr;
@@ -735,7 +735,7 @@ static int fit2d_eval(fdcap_ctx* c, const fdcap_fit2d_stage* sg, double* losses,
             else if (bend) hipLaunchKernelGGL(fit2d_bend_kernel<false>, dim3(nl), dim3(64), 0, st, o->bend, o->PF.p, 2, o->dPF.p, losses, floss);
             hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
                                o->Jrest.p, o->G.p, (const float*)o->dA.p, (vs || bend) ? o->dPF.p : (const float*)nullptr, o->dJw.p,
-                               vs ? o->dMv.p : (const float*)nullptr, vs ? o->dsv.p : (const float*)nullptr,
+                               (const float*)o->dMv.p /* (written on every path, as dA: the correction's share of d M) */, vs ? o->dsv.p : (const float*)nullptr,
                                vs ? o->dPF.p + NPF : (const float*)nullptr, vs ? NPFX : 0, vs ? o->dtransl_v.p : (const float*)nullptr, o->dX.p, o->dO.p,
                                o->dCAM.p, o->dscale_row.p, ParamLossIn(), (const float*)nullptr);
             { int eb = opt_vposer_backward(c, fold, st); if (eb) return eb; }

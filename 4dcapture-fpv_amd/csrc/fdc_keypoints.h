@@ -363,8 +363,9 @@ struct JawIO { const float* jaw; float* R9; float w[3]; };
 // psi [frame][10] in, dpsi [frame][10] out -- complete when the kernel ends: the chain's share, the set vertices' through E (PANEL too:
 // blend_backward knows nothing of psi) and the prior w^2 |psi|^2, whose ten terms join `prior` on threads XDIM + 3 .. XDIM + 12.
 // E [10][lde]: per set vertex column 3 u + c the expression directions (a pseudo-vertex: JE_j's rows), JE [55 3][10]; the tree's arrays
-// (parents, children, each joint's level) are the pose model's.  A map of joints 0..22 alone still stages A and M, and dA is written on every
-// path: pose_bwd_kernel must be handed it.
+// (parents, children, each joint's level) are the pose model's.  A map of joints 0..22 alone still stages A and M, and dA and dMv are written
+// on every path: pose_bwd_kernel must be handed both.  dMv's rotation part carries sum_j dJw_j (x) Dt_j, the world joints' correction's share
+// of d camera_ext, which the pose backward -- it forms d M from G_j.t + transl -- cannot know (zero at psi = 0, and without joints 0..22).
 struct ExprIO {
     const float* psi; float* dpsi; float w;
     const float* E; int lde; const float* JE;

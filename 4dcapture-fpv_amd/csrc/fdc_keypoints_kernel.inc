@@ -33,6 +33,7 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
 #endif
 #if FDC_KP_EXPR
     __shared__ float s_psi[NEXPR], s_dl[NJ * 3], s_djw[NJW * 3];      // the coefficients, delta = JE psi (kept for the backward), d loss / d Jw
+    __shared__ float s_dt[NJW * 3];            // the world joints' correction before W (kept for the backward: d M's rotation part)
     __shared__ int s_par[NJ], s_cs[NJ + 1], s_cl[NJ + 1], s_dep[NJ];  // the tree: walked from LDS, not through dependent global loads
     __shared__ float s_eb[PANEL ? NJ * 12 + 3 * NJ * 3 + 16 * NEXPR : 1];   // the backward's transients where the products' workspace is not there
 #endif
@@ -67,6 +68,7 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         if (tid < NJ) {
             const V3 dt = expr_forward(s_A, s_par, s_dl, tid);
             if (tid < NJW) {
+                s_dt[3 * tid] = dt.x; s_dt[3 * tid + 1] = dt.y; s_dt[3 * tid + 2] = dt.z;
                 s_jw[3 * tid] += s_M[0] * dt.x + s_M[1] * dt.y + s_M[2] * dt.z;
                 s_jw[3 * tid + 1] += s_M[4] * dt.x + s_M[5] * dt.y + s_M[6] * dt.z;
                 s_jw[3 * tid + 2] += s_M[8] * dt.x + s_M[9] * dt.y + s_M[10] * dt.z;
@@ -223,8 +225,8 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         if (tid < NJ * 3) {
             const int j = tid / 3, c = tid - 3 * j;
             float o = s_da[12 * j + 4 * c + 3];
-            // W^T dJw_j, W = the rotation of M (rows of four: [R | t], as A's): column c.  The inner fit's set-up has W = I, so the tests see
-            // the identity here; the forward above applies the same rows
+            // W^T dJw_j, W = the rotation of M (rows of four: [R | t], as A's): column c; the forward above applies the same rows
+            // (tests/test_gpu_world_frame.py runs both under cameras other than the identity)
             if (j < NJW) o += (s_M[c] * s_djw[3 * j] + s_M[4 + c] * s_djw[3 * j + 1]) + s_M[8 + c] * s_djw[3 * j + 2];
             s_own[tid] = o;
         }
@@ -278,6 +280,14 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
         for (int e = tid; e < NJ * 12; e += KP_NT) s_ew[e] = 0.f;
         __syncthreads();
         expr_bwd();
+        // Jw_j = W (G_j.t + Dt_j + transl) + M.t: pose_bwd_kernel forms d M's rotation part from G_j.t + transl, which it knows; the
+        // correction's share, sum_j dJw_j (x) Dt_j, is this kernel's to add -- here it is all of dMv (no vertex: the other sums stay unread)
+        if (tid < 12) {
+            const int i = tid >> 2, c = tid & 3;
+            float acc = 0.f;
+            if (c < 3) for (int j = 0; j < NJW; ++j) acc += s_djw[3 * j + i] * s_dt[3 * j + c];
+            dMv[(size_t)r * 12 + tid] = acc;
+        }
     }
 #endif
     if (nu == 0) return;                                   // (kernel-uniform: no vertex branch, nothing else is written or read)
@@ -358,6 +368,12 @@ __global__ __launch_bounds__(KP_NT) void FDC_KP_KERNEL(Fit2dStage s, KpSet ks, c
             } else
                 acc += s_gv[3 * u + o - 13];
         }
+#if FDC_KP_EXPR
+        // the world joints' share of d M's rotation part that pose_bwd_kernel cannot form: sum_j dJw_j (x) Dt_j (Jw_j = W (G_j.t + Dt_j +
+        // transl) + M.t, and the pose backward knows G_j.t + transl alone); an exact zero at psi = 0
+        if (part == 0 && o < 12 && (o & 3) < 3)
+            for (int j = 0; j < NJW; ++j) acc += s_djw[3 * j + (o >> 2)] * s_dt[3 * j + (o & 3)];
+#endif
         s_red[part][o] = acc;
     }
     if (PANEL) {                                           // the products' share is blend_backward's

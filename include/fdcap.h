@@ -537,7 +537,11 @@ int fdcap_frame_smoother(fdcap_ctx* ctx, const float* data78_d, int32_t N, int32
  * vis.py:358-360).  Objective restated from the published SMPLify-X data term and L2 priors (csrc/fdc_fit2d.h);
  * frames are independent.  Use: fdcap_opt_create (scale_init = 1), fdcap_opt_set_inputs (camera_ext rows = identity, so
  * the "world" joints are camera-frame joints + camera_translation), fdcap_opt_set_keypoints, then per iteration
- * fdcap_opt_backward_fit2d + fdcap_opt_step_x; fdcap_opt_reset_adam between stages; fdcap_opt_get_results. */
+ * fdcap_opt_backward_fit2d + fdcap_opt_step_x; fdcap_opt_reset_adam between stages; fdcap_opt_get_results.
+ * The evaluation itself honours whatever camera_ext rows and scale the registered buffers hold -- points are projected from the
+ * clip-level loop's world frame, and fdcap_opt_get_grads' d camera_ext is that evaluation's (tests/test_gpu_world_frame.py) -- while
+ * the start from keypoints alone (fdcap_opt_fit2d_guess, the camera stage, fdcap_fit2d_flip_orient, fdcap_fit2d_select;
+ * csrc/fdc_fit2d_init.h) is written for the identity set-up and does not. */
 typedef struct fdcap_fit2d_stage {
     float fx, fy, cx, cy;   /* pinhole intrinsics */
     float rho;              /* GMoF scale in pixels (SMPLify-X: 100) */
@@ -548,7 +552,9 @@ int fdcap_opt_set_keypoints(fdcap_ctx* ctx, const float* kp_d, void* stream);
 /* ... on a detector's keypoints (csrc/fdc_keypoints.h): a map, static per context, from keypoint k to an SMPL-X joint or a point of
  * the mesh surface.  Every kind's position is "SMPL-X output + transl + camera_translation" under the inner fit's set-up above
  * (camera_ext rows = identity, scale = 1); joints 0..22 are the 23-joint path's own world joints, so a map of exactly those in
- * order gives that path's bits. */
+ * order gives that path's bits.  At scale != 1 the finger joints 23..54 follow the vertex formula, camera_ext R [scale (p + transl +
+ * camera_translation)] + t (the kernel forms them as pseudo-vertices), and not the world joints' R [(J + transl) + scale
+ * camera_translation] + t. */
 #define FDCAP_MAX_KEYPOINTS 160
 /* joint[k] >= 0: SMPL-X joint; joint[k] < 0: surface point tri[k][0..2] (vertex ids), bary[k][0..2].  HOST arrays.
  * n_kp = 0 clears the map.  FDCAP_E_ARG: n_kp < 0 or > FDCAP_MAX_KEYPOINTS, joint >= 55, a vertex id outside [0, V),
