@@ -265,8 +265,10 @@ class BodyModel:
 
     def __call__(self, return_verts=True, body_pose=None, transl=None, global_orient=None, betas=None,
                  left_hand_pose=None, right_hand_pose=None, jaw_pose=None, expression=None, **unused):
-        B = body_pose.shape[0]
-        dev = body_pose.device
+        given = [t for t in (body_pose, transl, global_orient, betas, left_hand_pose, right_hand_pose, jaw_pose, expression) if t is not None]
+        if not given:
+            raise capi.FdcapError("BodyModel: at least one argument must be given (the batch size and the device are read from it)")
+        B, dev = given[0].shape[0], given[0].device                 # (body_pose = None is the rest pose, like every other argument)
         c = lambda t, w: (torch.zeros(B, w, device=dev) if t is None else t.reshape(B, w).float().contiguous())
         go, bp, be = c(global_orient, 3), c(body_pose, 63), c(betas, 10)
         lh, rh, tr = c(left_hand_pose, 12), c(right_hand_pose, 12), c(transl, 3)

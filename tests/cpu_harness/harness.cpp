@@ -288,6 +288,36 @@ void h_rotmat_to_aa_bwd(const float* R, const float* g, int n, float* dR) {
     }
 }
 
+// the bare Gram-Schmidt and Rodrigues pairs (tests/test_rotation_edges_cpu.py): s [n,6] in the decoder's interleaved layout,
+// r [n,3], R / dR [n,9] row-major
+void h_gs_forward(const float* s, int n, float* R) {
+    for (int i = 0; i < n; ++i) {
+        M3 m = gs_forward(s + (size_t)i * 6, 1, nullptr);
+        for (int e = 0; e < 9; ++e) R[(size_t)i * 9 + e] = m.m[e];
+    }
+}
+void h_gs_backward(const float* s, const float* dR, int n, float* ds) {
+    for (int i = 0; i < n; ++i) {
+        GsCache c;
+        gs_forward(s + (size_t)i * 6, 1, &c);
+        M3 d; for (int e = 0; e < 9; ++e) d.m[e] = dR[(size_t)i * 9 + e];
+        gs_backward(c, d, ds + (size_t)i * 6, 1);
+    }
+}
+void h_rodrigues(const float* r, int n, float* R) {
+    for (int i = 0; i < n; ++i) {
+        M3 m = rodrigues_forward(v3(r[3 * i], r[3 * i + 1], r[3 * i + 2]));
+        for (int e = 0; e < 9; ++e) R[(size_t)i * 9 + e] = m.m[e];
+    }
+}
+void h_rodrigues_bwd(const float* r, const float* dR, int n, float* dr) {
+    for (int i = 0; i < n; ++i) {
+        M3 d; for (int e = 0; e < 9; ++e) d.m[e] = dR[(size_t)i * 9 + e];
+        V3 g = rodrigues_backward(v3(r[3 * i], r[3 * i + 1], r[3 * i + 2]), d);
+        dr[3 * i] = g.x; dr[3 * i + 1] = g.y; dr[3 * i + 2] = g.z;
+    }
+}
+
 // operator-level body model (fdcap_smplx_forward / fdcap_smplx_backward): global_orient + body pose as axis-angle rows AA
 // [rows,66], gradient of the 55 body-frame joints dJb [rows,165] -> dX rows (transl, betas, hands) and dAA [rows,66]
 void h_pose_forward_aa(void* hv, int rows, const float* X, const float* AA, float* Rm, float* PF, float* Jrest, float* G, float* A) {

@@ -123,11 +123,14 @@ def _neighbours(f, vid):
         return np.stack([nn_direct(verts[b, vid], f.s_verts_batch[b])[1].numpy() for b in range(verts.shape[0])])
 
 
-def start_state(case):
+def start_state(case, edit=None):
     """What the GPU is given and then holds: the fp32 start rows `x78` for init(), `rows` after init() (outlier rows replaced) and
-    `+= fp32(perturbation)`, and the start scale."""
+    `+= fp32(perturbation)`, and the start scale.  edit: sc.term_gradients' (None: the clip as it is)."""
     c = sc.make_case(*case)
-    x78 = rotrepr.convert_to_6D_rot(torch.tensor(c[2].body_params, dtype=torch.float64)).detach().float()
+    body_params = c[2].body_params if edit is None else edit.clip(c[2].body_params)
+    x78 = rotrepr.convert_to_6D_rot(torch.tensor(body_params, dtype=torch.float64)).detach().float()
+    if edit is not None:
+        x78 = edit.rows(x78)
     idx1, pos = find_outliers_and_sources(x78)
     rows = x78.clone()
     if len(idx1) and len(pos):
@@ -137,17 +140,18 @@ def start_state(case):
 
 
 @functools.lru_cache(maxsize=None)
-def isolated_terms(case):
+def isolated_terms(case, edit=None):
     """case = (n, V, scene points, contact vertices per part, seed), the models of tests/test_gpu_parity.py _make_fop.
     -> {"g64", "g32": {term: {block: array}}, "bar": {term: {block: float}}, "x78", "rows", "scale"}: the oracle's gradients of
     l_con alone (d rows, d scale) and of l_ws alone (d rows, d camera_ext), unweighted, in both precisions at the state the GPU holds
     (start rows rounded to fp32, + fp32(0.01 randn, seed 5), scale fp32(1.8)), and the bars.  Multiply all three by COEFF[term].
-    "l1": the fp64 row gradient of l_rec + l_sm, for the default phase-1 mix."""
+    "l1": the fp64 row gradient of l_rec + l_sm, for the default phase-1 mix.
+    edit: sc.term_gradients' (None: the clip as it is; the existing cases)."""
     c = sc.make_case(*case)
     vid = c[4]
-    t64 = sc.term_gradients(c, sc.DEFAULTS["scale_init"], torch.float64, ("rec", "sm", "con", "ws"), as_the_gpu_holds_it=True)
-    t32 = sc.term_gradients(c, sc.DEFAULTS["scale_init"], torch.float32, ("con", "ws"), as_the_gpu_holds_it=True)
-    start = start_state(case)
+    t64 = sc.term_gradients(c, sc.DEFAULTS["scale_init"], torch.float64, ("rec", "sm", "con", "ws"), as_the_gpu_holds_it=True, edit=edit)
+    t32 = sc.term_gradients(c, sc.DEFAULTS["scale_init"], torch.float32, ("con", "ws"), as_the_gpu_holds_it=True, edit=edit)
+    start = start_state(case, edit)
     assert np.array_equal(t64["rows"].numpy(), start["rows"].astype(np.float64)) and np.array_equal(t32["rows"].numpy(), start["rows"])
     # a bar that contained a nearest-neighbour flip between the two precisions would be no rounding yardstick
     assert np.array_equal(_neighbours(t64["oracle"], vid), _neighbours(t32["oracle"], vid)), f"nearest neighbours differ between fp32 and fp64: take another seed than {case}"

@@ -98,22 +98,27 @@ def perturbation(n):
 TERMS = ("rec", "vp", "sm", "con", "ws")
 
 
-def term_gradients(case, scale_init, dtype=torch.float64, terms=TERMS, as_the_gpu_holds_it=False, body_cls=SMPLXOracle, vposer_cls=VPoserDecoder):
+def term_gradients(case, scale_init, dtype=torch.float64, terms=TERMS, as_the_gpu_holds_it=False, body_cls=SMPLXOracle, vposer_cls=VPoserDecoder,
+                   edit=None):
     """Values and gradients of the UNWEIGHTED terms (rec, vposer, smoothing, contact, world smoothing) at the perturbed start, each
     term's gradient taken on its own.  -> {"val": {term: float}, "g": {term: (d rows [n,78], d scale, d camera_ext [n,16])}, ...}
     as_the_gpu_holds_it: the start rows, the perturbation, their sum, scale and camera_ext rounded to fp32 before the oracle
     (in `dtype`) sees them -- the state a FittingOP holds after init() and `rows += perturbation.float()`.
-    body_cls / vposer_cls: the oracle's models, or subclasses that override tap() (tests/gradient_bars.py)."""
+    body_cls / vposer_cls: the oracle's models, or subclasses that override tap() (tests/gradient_bars.py).
+    edit (with as_the_gpu_holds_it; None: the clip as it is): `edit.clip(body_params [n,75]) -> [n,75]` replaces the clip's rows and
+    `edit.rows(x78 fp32 [n,78]) -> [n,78]` the start rows before init() (tests/rotation_edges.py HalfTurnClip)."""
     bm, vp, clip, scene, vid, n = case
+    assert edit is None or as_the_gpu_holds_it
     if as_the_gpu_holds_it:
         scale_init = float(np.float32(scale_init))
     s = dict(DEFAULTS, scale_init=scale_init)
     f = FittingOracle(body_cls(bm, dtype), vposer_cls.from_data(vp, dtype), scene, vid, clip.camerapose_lines, n, init_lr_h=s["lr"],
                       weight_loss_rec=1.0, weight_loss_vposer=1.0, weight_contact=1.0, dtype=dtype, scale_init=scale_init)
-    x78 = rotrepr.convert_to_6D_rot(torch.tensor(clip.body_params, dtype=torch.float64)).detach()
+    body_params = clip.body_params if edit is None else edit.clip(clip.body_params)
+    x78 = rotrepr.convert_to_6D_rot(torch.tensor(body_params, dtype=torch.float64)).detach()
     idx1, _ = find_outliers(x78.numpy().astype(np.float32))
     if as_the_gpu_holds_it:
-        x78 = x78.float()
+        x78 = x78.float() if edit is None else edit.rows(x78.float())
         f.init(x78)
         f.body_rotation_rec.data = (f.body_rotation_rec.data + perturbation(n).float()).to(dtype)       # the sum in fp32, as on the device
         f.camera_ext.data = f.camera_ext.data.float().to(dtype)                                         # (rounded from its fp64 inverse)
