@@ -206,6 +206,8 @@ SYMBOLS = {
     "fdcap_debug_nn_box_tests": (c_int32, [c_void_p, c_void_p]),
     "fdcap_debug_contact_perm": (c_int32, [c_void_p, c_void_p, c_int32]),
     "fdcap_debug_nn_query_sort": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "fdcap_debug_nn_query_sort_shift": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
+    "fdcap_debug_nn_search_form": (c_int32, [c_void_p, c_int32, c_int32]),
     "fdcap_opt_launch_timing": (c_int32, [c_void_p, c_int32]),
     "fdcap_opt_launch_timing_read": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_time_chamfer": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_float), c_void_p]),

@@ -260,7 +260,7 @@ static int scene_set_build(SceneSet* c, const float* xyz, int64_t ns) {
     // Results never depend on this order.
     const int64_t nchunk = (ns + MF_CH - 1) / MF_CH, nsuper = (nchunk + ST4_SUPER - 1) / ST4_SUPER;
     HIP_TRY(c->scene.ensure((size_t)ns)); HIP_TRY(c->scene_sorted.ensure((size_t)ns)); HIP_TRY(c->scene_inv.ensure((size_t)ns));
-    HIP_TRY(c->scene_bounds.ensure((size_t)nchunk * 2)); HIP_TRY(c->scene_qbounds.ensure((size_t)nchunk * 8));
+    HIP_TRY(c->scene_bounds.ensure((size_t)nchunk * 2)); HIP_TRY(c->scene_qbounds.ensure((size_t)nchunk * 24));    // (quarters, then eighths)
     HIP_TRY(c->scene_frags.ensure((size_t)nchunk * (MF_CH / 32) * 64)); HIP_TRY(c->scene_centers.ensure((size_t)nchunk));
     {
         std::vector<float4> sb((size_t)std::max<int64_t>(nsuper, 1) * 2, make_float4(0.f, 0.f, 0.f, 0.f));

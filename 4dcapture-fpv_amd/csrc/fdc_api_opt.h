@@ -586,10 +586,11 @@ int fdcap_debug_nn_query_order(fdcap_ctx* c, int32_t mode, const int32_t* perm_h
 }
 
 // Tests / diagnosis: the query order's sort on its own (nn_query_order, exactly as nn_search launches it) on neighbour positions
-// given by the caller.  Owns its buffers; needs no optimiser state.
-int fdcap_debug_nn_query_sort(fdcap_ctx* c, const int32_t* pos_host, int32_t nq, int32_t groups, int32_t hdr_len, int32_t* hdr_io,
-                              int32_t* perm_out, void* stream) {
+// given by the caller, under the key pos >> shift.  Owns its buffers; needs no optimiser state.
+int fdcap_debug_nn_query_sort_shift(fdcap_ctx* c, const int32_t* pos_host, int32_t nq, int32_t groups, int32_t hdr_len, int32_t* hdr_io,
+                                    int32_t* perm_out, int32_t shift, void* stream) {
     if (!c || !pos_host || !hdr_io || !perm_out || nq <= 0 || groups < 0 || hdr_len < groups) return FDCAP_E_ARG;
+    if (shift < NN_KEY_SHIFT_MIN || shift > NN_KEY_SHIFT_MAX) return FDCAP_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     std::vector<float4> sp((size_t)nq);
     for (int i = 0; i < nq; ++i) {                           // (seedpt[i].w carries the position's int bits)
@@ -602,13 +603,50 @@ int fdcap_debug_nn_query_sort(fdcap_ctx* c, const int32_t* pos_host, int32_t nq,
     if (e == hipSuccess) e = qbuf.ensure(nn_query_order_ints(nq));
     if (e == hipSuccess) e = hdr.upload(hdr_io, (size_t)hdr_len);
     if (e == hipSuccess) {                                   // (the three buffers are freed on return: wait, whatever the launches said)
-        e = nn_query_order(seedpt.p, nq, qbuf.p, hdr.p, groups, st);
+        e = nn_query_order(seedpt.p, nq, qbuf.p, hdr.p, groups, shift, st);
         const hipError_t es = hipStreamSynchronize(st);
         if (e == hipSuccess) e = es;
     }
     if (e == hipSuccess) e = hipMemcpy(perm_out, qbuf.p, (size_t)nq * sizeof(int), hipMemcpyDeviceToHost);
     if (e == hipSuccess && hdr_len > 0) e = hipMemcpy(hdr_io, hdr.p, (size_t)hdr_len * sizeof(int), hipMemcpyDeviceToHost);
     return e == hipSuccess ? FDCAP_OK : (int)e;
+}
+// ... under the quarter key every build before r21 sorted by (pos >> 7)
+int fdcap_debug_nn_query_sort(fdcap_ctx* c, const int32_t* pos_host, int32_t nq, int32_t groups, int32_t hdr_len, int32_t* hdr_io,
+                              int32_t* perm_out, void* stream) {
+    return fdcap_debug_nn_query_sort_shift(c, pos_host, nq, groups, hdr_len, hdr_io, perm_out, 7, stream);
+}
+
+// Tests / diagnosis (r21): the streaming search's scheduling choices in one build, process-wide as fdcap_set_nn_kernel.  key_shift: the
+// query order's key is the neighbour's position >> key_shift (5, 6, 7; 0: by the scene, nn_order_key_shift).  items_per_chunk: work
+// items per 512-point chunk of the one-wave form (4: quarters; 8: 64-point eighths, where their ids fit 16 bits; 0:
+// plan_nn_items_per_chunk).  The kept work lists of this context go -- they hold item ids -- the scene operator starts over and an
+// optimiser's order is rebuilt after its next launch.
+int fdcap_debug_nn_search_form(fdcap_ctx* c, int32_t key_shift, int32_t items_per_chunk) {
+    if (!c) return FDCAP_E_STATE;
+    if (key_shift != 0 && (key_shift < NN_KEY_SHIFT_MIN || key_shift > NN_KEY_SHIFT_MAX)) return FDCAP_E_ARG;
+    if (items_per_chunk != 0 && items_per_chunk != 4 && items_per_chunk != 8) return FDCAP_E_ARG;
+    HIP_TRY(hipDeviceSynchronize());                         // (no launch in flight reads the table or the lists)
+    nn_key_shift_ref() = key_shift;
+    nn_items_ref() = items_per_chunk;
+    c->sop.nq = 0;
+    OptState* o = c->opt;
+    if (!o || !o->contact_on) return FDCAP_OK;
+    auto reset = [&](NNOrder& ord, int* hdr, size_t groups) -> hipError_t {
+        if (hdr == nullptr || groups == 0) return hipSuccess;
+        if (ord.qbuf != nullptr) {
+            if (ord.perm_mode == 0) ord.perm_n = 0;           // the next launch runs in query order and builds one after it
+            ord.sorted_groups = 0;
+            ord.age = 0;
+        }
+        return hipMemset(hdr, 0xFF, groups * sizeof(int));
+    };
+    if (!o->segs.empty()) {                                   // (clips of several scenes: an order per segment)
+        for (SegSearch& g : o->segs) HIP_TRY(reset(g.ord, g.hdr.p, (size_t)g.seg.groups));
+    } else {
+        HIP_TRY(reset(o->nn_order, o->nnc_hdr.p, ((size_t)o->cfg.n_local * c->nc + 31) / 32));
+    }
+    return FDCAP_OK;
 }
 
 }  // extern "C"

@@ -33,7 +33,9 @@ struct NNTarget {
     int n;
     const float4* bounds;     // optional [2 * ceil(n / MF_CH)] axis-aligned box {lo xyz, -}, {hi xyz, -} of each chunk (pts spatially sorted)
     const float4* sbounds;    // with bounds: [2 * ceil(nchunk / 16)] boxes of 16 consecutive chunks (two-level survivor test)
-    const float4* qbounds;    // with frags: [2 * 4 * nchunk] boxes of the quarter chunks (the unit the streaming kernel lists and scans)
+    const float4* qbounds;    // with frags: [2 * 4 * nchunk] boxes of the quarter chunks (the unit the streaming kernel lists and scans); r21: behind
+                              // them [2 * 8 * nchunk] boxes of the 64-point eighths, the two halves of every quarter (the one-wave form's work
+                              // items where their ids fit 16 bits: plan_nn_items_per_chunk, fdc_forms.h)
     const int* inv_perm;      // optional [n] original index -> position in pts (null: identity)
     // optional, static per scene: MFMA A fragments precomputed per chunk RELATIVE TO THE CHUNK'S OWN CENTRE
     // ([chunk][tile 0..15][k-half][point 0..31] uint4) + the centres {cx, cy, cz, radius}: lets a wave
@@ -619,7 +621,10 @@ static_assert(sizeof(NNSegs) <= 3072, "the descriptors travel as a kernel argume
 template <bool SEG> struct NNSegArg { typedef NNNoSegs type; };
 template <> struct NNSegArg<true> { typedef NNSegs type; };
 
-template <int WPG, int WPB = 4, bool SEG = false>
+// IPC (r21, the one-wave form only, as KEEP and BOX_BY_COUNT): work items per chunk -- 4: quarters (128 points, four tiles, boxes in
+// qbounds), 8: eighths (64 points, two tiles, boxes behind the quarters').  A quarter some query touches is scanned whole; of its two halves
+// usually one is out of every query's reach.  List ids are IPC k + item, the main loop is the same loop over QT = NT / IPC tiles.
+template <int WPG, int WPB = 4, bool SEG = false, int IPC = 4>
 __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const float* __restrict__ q, int nq, NNTarget T,
                                                          const int* __restrict__ seed, float4* __restrict__ seedpt,
                                                          float* __restrict__ dist, int* __restrict__ idx, NNCache cache,
@@ -641,6 +646,7 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
     __shared__ int s_q[WPB][32];                                 // the query each slot serves (cache.perm)
     static_assert(WPG == 1 || WPG == 2 || WPG == 4, "waves per query group");
     static_assert(WPB % WPG == 0 && WPB <= 4, "a group's waves share a workgroup");
+    static_assert(IPC == 4 || (IPC == 8 && WPG == 1 && WPB == 1), "64-point work items: the one-wave form");
     constexpr int GPW = WPB / WPG;                               // query groups per workgroup
     constexpr int CPS = ST4_SUPER / WPG;                         // chunks of a super-cell that belong to one wave
     // (the wave's index as a scalar: every [wave] address below is then a scalar base.  As a per-lane value the multi-wave forms kept
@@ -848,7 +854,7 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
     // r15: lanes per box by each stage's count (nn_box_stage above).  Per form, as KEEP: a form keeps it only where it measured no slower.
     constexpr bool BOX_BY_COUNT = WPB == 1;
     const int box_forced = __builtin_amdgcn_readfirstlane(cache.box_lanes);
-    int nsurv = 4 * myn;                                         // work items are quarter chunks: 4 k + quarter
+    int nsurv = IPC * myn;                                       // work items are quarter chunks (IPC = 8: eighths): IPC k + item
     bool listed = false;
     if (cull && n_kept >= 0) {                                    // the kept list is still a superset of what this launch can need
         nsurv = n_kept;
@@ -919,12 +925,13 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
         // (32 quarters = 8 chunks per pass with a pair), boxes straight from global memory into their registers.
         ncell = __builtin_amdgcn_readfirstlane(ncell);
         if (listed) {
-            nsurv = nn_box_stage<BOX_BY_COUNT>(sq, lane, 4 * ncell, box_forced, ST4_MAXLIST, 1,
-                [&](int jq, bool valid, float4& blo, float4& bhi, int& tag) __attribute__((always_inline)) {       // cell jq >> 2 of the list, its quarter jq & 3
-                    const int k4 = 4 * (int)clist[wave][valid ? (jq >> 2) : 0];
-                    const size_t qb = ((size_t)(WPG * (k4 >> 2) + sub) * 4 + (jq & 3)) * 2;
-                    blo = T.qbounds[qb]; bhi = T.qbounds[qb + 1];
-                    tag = k4 + (jq & 3);
+            const float4* const ibounds = IPC == 8 ? T.qbounds + 8 * (size_t)nchunk : T.qbounds;
+            nsurv = nn_box_stage<BOX_BY_COUNT>(sq, lane, IPC * ncell, box_forced, ST4_MAXLIST, 1,
+                [&](int jq, bool valid, float4& blo, float4& bhi, int& tag) __attribute__((always_inline)) {       // entry jq: an item of a listed cell
+                    const int k = (int)clist[wave][valid ? nn_item_chunk(IPC, jq) : 0], item = nn_item_of(IPC, jq);
+                    const size_t qb = ((size_t)(WPG * k + sub) * IPC + item) * 2;
+                    blo = ibounds[qb]; bhi = ibounds[qb + 1];
+                    tag = nn_item_id(IPC, k, item);
                 },
                 [&](int at, int tag) __attribute__((always_inline)) { slist[wave][at] = (unsigned short)tag; });
             if (nsurv < 0) { listed = false; nsurv = 0; }
@@ -941,7 +948,7 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
             if (half == 0 && ok)                                  // R_i with the validity test's rounding margin taken off; no list: never valid
                 cache.anchor[(size_t)sub * nq + qidx] = make_float4(qx, qy, qz, keep ? (rq + slack_of(rq)) * 0.99998f - 2e-6f : -1.f);
         }
-        if (!listed) nsurv = 4 * myn;                           // list overflow: scan this wave's whole share (still exact)
+        if (!listed) nsurv = IPC * myn;                         // list overflow: scan this wave's whole share (still exact)
     }
     TL_STAMP(1);
     // With a cache the list (kept or just built) was made for inflated radii: filter it by the per-query box test with the
@@ -957,8 +964,9 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
         const int nout = nn_box_stage<BOX_BY_COUNT>(sq, lane, n_raw, box_forced, ST4_MAXLIST, 2,
             [&](int kk, bool valid, float4& blo, float4& bhi, int& id) __attribute__((always_inline)) {
                 id = (int)slist[wave][valid ? kk : 0];
-                const size_t qb = ((size_t)(WPG * (id >> 2) + sub) * 4 + (id & 3)) * 2;
-                blo = T.qbounds[qb]; bhi = T.qbounds[qb + 1];
+                const size_t qb = ((size_t)(WPG * nn_item_chunk(IPC, id) + sub) * IPC + nn_item_of(IPC, id)) * 2;
+                const float4* const ibounds = IPC == 8 ? T.qbounds + 8 * (size_t)nchunk : T.qbounds;
+                blo = ibounds[qb]; bhi = ibounds[qb + 1];
             },
             [&](int at, int id) __attribute__((always_inline)) { slist[wave][at] = (unsigned short)id; });   // (in place: a pass reads its ids before it writes, and writes trail reads)
         nsurv = nout;
@@ -970,7 +978,7 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
 #endif
     const f32x16_t zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     constexpr int NT = MF_CH / 32;                               // 16 tiles per chunk (padding rows score 1e30)
-    constexpr int QT = NT / 4;                                   // tiles per work item (quarter chunk)
+    constexpr int QT = NT / IPC;                                 // tiles per work item (quarter chunk: 4; eighth: 2)
     static_assert(QT % ST4_PF == 0, "the prefetch ring turns a whole number of times per work item");
 
 #ifdef FDC_NN_STATS
@@ -984,7 +992,7 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
         // work items (quarter chunks) are wave-uniform: ids kept in SGPRs (readfirstlane), so fragment addresses are scalar
         // base + lane offset + immediate and the centres come through the scalar cache, one item ahead
         int id = __builtin_amdgcn_readfirstlane(listed ? (int)slist[wave][0] : 0);
-        int ch = __builtin_amdgcn_readfirstlane(WPG * (id >> 2) + sub), qd = id & 3;
+        int ch = __builtin_amdgcn_readfirstlane(WPG * nn_item_chunk(IPC, id) + sub), qd = nn_item_of(IPC, id);
         // The fragment stream goes through BUFFER loads (r3): one resource descriptor for the whole fragment array in SGPRs, the
         // item's byte offset as the scalar offset, lane * 16 as the vector offset, the tile within the item as the immediate --
         // `buffer_load_dwordx4 v, v_lane, s[rsrc], s_item offen offset:imm`.  The r2 form (global loads from a scalar base
@@ -1033,8 +1041,8 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
         for (int s = 0; s < nsurv; ++s) {
             const int s1 = min(s + 1, nsurv - 1);                          // last item: harmless re-fetch of itself
             const int id_next = __builtin_amdgcn_readfirstlane(listed ? (int)slist[wave][s1] : s1);
-            const int ch_next = __builtin_amdgcn_readfirstlane(WPG * (id_next >> 2) + sub);
-            const unsigned fo_next = (unsigned)(ch_next * NT + (id_next & 3) * QT) * 1024u;
+            const int ch_next = __builtin_amdgcn_readfirstlane(WPG * nn_item_chunk(IPC, id_next) + sub);
+            const unsigned fo_next = (unsigned)(ch_next * NT + nn_item_of(IPC, id_next) * QT) * 1024u;
             const cf4_t cc = cc_next;
             cc_next = centers_c[ch_next];
             FDC_STAT(3, lane == 0);
@@ -1134,7 +1142,7 @@ __global__ __launch_bounds__(64 * WPB, FDC_ST4_OCC) void nn_stream4_kernel(const
                 }
             }
             ch = ch_next;
-            qd = id_next & 3;
+            qd = nn_item_of(IPC, id_next);
             fo = fo_next;
         }
     }
@@ -1381,6 +1389,11 @@ inline std::atomic<int>& nn_mode_ref() {
     static std::atomic<int> mode{0};
     return mode;
 }
+// r21, scheduling of the one-wave streaming form, never results.  fdcap_debug_nn_search_form() sets them (tests, A/B within one
+// build); 0: automatic.  The query order's key shift (else nn_order_key_shift of the scene) and the work items per chunk (else
+// plan_nn_items_per_chunk).
+inline std::atomic<int>& nn_key_shift_ref() { static std::atomic<int> v{0}; return v; }
+inline std::atomic<int>& nn_items_ref() { static std::atomic<int> v{0}; return v; }
 
 // Launch order of nn_stream4_kernel's one-wave workgroups: position -> group, most work items first (counting sort on the
 // counts the last launch wrote; ties in no particular order -- the order decides when a group runs, never what it returns).
@@ -1433,7 +1446,7 @@ struct NNOrder {
     int n_box[4] = {0, 0, 0, 0};
 };
 static inline size_t nn_query_order_ints(int nq);                       // fdc_scene.h (the radix sort lives there)
-static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st);
+static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, int shift, hipStream_t st);
 
 // The host's share of ONE streaming launch over `groups` groups of `wpg` waves, in two halves around the launch (nn_search; the
 // segmented launch calls both once per segment).  Before: the kernel's cache argument -- launch order, query order and whether
@@ -1455,8 +1468,8 @@ static inline NNCache nn_stream_args(const NNCache* cache, NNOrder* ord, int gro
     return nc;
 }
 // After (nc: what nn_stream_args returned for this launch): the query order's rebuild or the launch order's re-sort, when due.
-static inline hipError_t nn_stream_upkeep(const NNCache& nc, NNOrder* ord, int groups, int wpg, int nq, const float4* seedpt, bool seed_missing,
-                                          hipStream_t st) {
+static inline hipError_t nn_stream_upkeep(const NNCache& nc, NNOrder* ord, int groups, int wpg, int nq, int ns, const float4* seedpt,
+                                          bool seed_missing, hipStream_t st) {
     const bool ordered = ord != nullptr && ord->on && nc.hdr != nullptr && ord->every > 0 && wpg == 1;
     const bool qorder = ordered && ord->qbuf != nullptr && ord->perm_mode != 1;
     if (ord && seed_missing) ord->n_rebuilds = 0;             // a fit's first launch: its schedule starts over
@@ -1464,7 +1477,7 @@ static inline hipError_t nn_stream_upkeep(const NNCache& nc, NNOrder* ord, int g
     if (qorder && ord->perm_mode == 0 && (ord->perm_n != nq || seed_missing || (resort && ord->sorted_groups == groups))) {
         // new groups: their kept lists go (hdr = -1, by the key kernel), the next launch records its work items in
         // plain launch order and the launch order is sorted after it
-        const hipError_t e = nn_query_order(seedpt, nq, ord->qbuf, nc.hdr, groups, st);
+        const hipError_t e = nn_query_order(seedpt, nq, ord->qbuf, nc.hdr, groups, nn_key_shift_ref() ? (int)nn_key_shift_ref() : nn_order_key_shift(ns), st);
         if (e != hipSuccess) return e;
         ord->perm_n = nq;
         ord->sorted_groups = 0;
@@ -1503,8 +1516,10 @@ static inline hipError_t nn_search(const float* q, int nq, const NNTarget& T, fl
             const NNCache nc = nn_stream_args(cache, ord, groups, wpg, nq, seed, idx, seedpt, seed_missing);
             if (wpg == 4) hipLaunchKernelGGL((nn_stream4_kernel<4>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc, NNNoSegs{});
             else if (wpg == 2) hipLaunchKernelGGL((nn_stream4_kernel<2>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc, NNNoSegs{});
+            else if (plan_nn_items_per_chunk(nq, (T.n + MF_CH - 1) / MF_CH, T.qbounds != nullptr, nn_items_ref()) == 8)
+                hipLaunchKernelGGL((nn_stream4_kernel<1, 1, false, 8>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc, NNNoSegs{});
             else hipLaunchKernelGGL((nn_stream4_kernel<1, 1>), grid, block, 0, st, q, nq, T, seed, seedpt, dist, idx, nc, NNNoSegs{});
-            const hipError_t e = nn_stream_upkeep(nc, ord, groups, wpg, nq, seedpt, seed_missing, st);
+            const hipError_t e = nn_stream_upkeep(nc, ord, groups, wpg, nq, T.n, seedpt, seed_missing, st);
             if (e != hipSuccess) return e;
         }
         return hipGetLastError();
@@ -1525,8 +1540,10 @@ static inline hipError_t nn_search_segments(const NNSegPlan& pl, const NNSegSear
     if (!pl.one_launch || nseg < 1 || nseg > NN_MAX_SEGS || pl.grid_y != nseg) return hipErrorInvalidValue;
     note_form(pl.name);
     NNSegs a{};
+    bool eighths = true;                                         // one kernel for all segments: 64-point work items where every segment takes them
     for (int s = 0; s < nseg; ++s) {
         const NNSegSearch& g = sg[s];
+        eighths = eighths && plan_nn_items_per_chunk(g.nq, (g.T.n + MF_CH - 1) / MF_CH, g.T.qbounds != nullptr, nn_items_ref()) == 8;
         const int groups = (g.nq + 31) / 32;
         if (g.nq <= 0 || groups > pl.grid_x) return hipErrorInvalidValue;
         if (g.seed_missing)
@@ -1536,11 +1553,15 @@ static inline hipError_t nn_search_segments(const NNSegPlan& pl, const NNSegSear
         d.cache = nn_stream_args(&g.cache, g.ord, groups, 1, g.nq, g.idx, g.idx, g.seedpt, g.seed_missing);
     }
     // (the per-launch arguments are unused: every workgroup takes its segment's from the descriptors)
-    hipLaunchKernelGGL((nn_stream4_kernel<1, 1, true>), dim3(pl.grid_x, nseg), dim3(pl.block), 0, st, (const float*)nullptr, 0, NNTarget{},
-                       (const int*)nullptr, (float4*)nullptr, (float*)nullptr, (int*)nullptr, NNCache{nullptr, nullptr, nullptr, 0.f}, a);
+    if (eighths)
+        hipLaunchKernelGGL((nn_stream4_kernel<1, 1, true, 8>), dim3(pl.grid_x, nseg), dim3(pl.block), 0, st, (const float*)nullptr, 0, NNTarget{},
+                           (const int*)nullptr, (float4*)nullptr, (float*)nullptr, (int*)nullptr, NNCache{nullptr, nullptr, nullptr, 0.f}, a);
+    else
+        hipLaunchKernelGGL((nn_stream4_kernel<1, 1, true>), dim3(pl.grid_x, nseg), dim3(pl.block), 0, st, (const float*)nullptr, 0, NNTarget{},
+                           (const int*)nullptr, (float4*)nullptr, (float*)nullptr, (int*)nullptr, NNCache{nullptr, nullptr, nullptr, 0.f}, a);
     for (int s = 0; s < nseg; ++s) {
         const NNSegSearch& g = sg[s];
-        const hipError_t e = nn_stream_upkeep(a.s[s].cache, g.ord, a.s[s].groups, 1, g.nq, g.seedpt, g.seed_missing, st);
+        const hipError_t e = nn_stream_upkeep(a.s[s].cache, g.ord, a.s[s].groups, 1, g.nq, g.T.n, g.seedpt, g.seed_missing, st);
         if (e != hipSuccess) return e;
     }
     return hipGetLastError();

@@ -410,6 +410,35 @@ constexpr FDC_FORMS_HD int nn_order_period(int base, int rebuilds, int nq) {
     return p;
 }
 
+// r21.  The query order's key is the k-d node of each query's current neighbour: its position in a sorted scene of ns points,
+// shifted down by this.  5 is the 32-point MFMA tile, the unit the main loop scores; the two 8-bit radix passes hold 16 bits and
+// 0xFFFF stays the no-neighbour sentinel, so the finest of tile (5), 64-point node (6) and quarter (7) whose last key stays below
+// it: 5 up to 2 097 120 points (both bench scenes), 6 up to 4 194 240, 7 beyond (where the far end of the scene clamps onto the sentinel, as before).
+constexpr int NN_KEY_SHIFT_MIN = 5, NN_KEY_SHIFT_MAX = 7;
+constexpr FDC_FORMS_HD int nn_order_key_shift(int ns) {
+    int s = NN_KEY_SHIFT_MIN;
+    while (s < NN_KEY_SHIFT_MAX && ((ns > 0 ? ns - 1 : 0) >> s) >= 0xFFFF) ++s;
+    return s;
+}
+
+// r21.  Work items of the one-wave streaming form: ipc per 512-point chunk -- 4 quarters (128 points) or 8 eighths (64 points).
+// A work list holds 16-bit ids ipc * chunk + item, so eighths are taken while 8 * nchunk <= 0xFFFF (8191 chunks, 4.19 M points);
+// larger scenes keep quarters, as every other form does.  eighths: the scene has their boxes (behind NNTarget::qbounds).
+// Eighths cut the tiles a wave scores by a third (config 3: 18.5 -> 12.7 per wave) and lengthen its lists by 60 % (10.5 -> 17
+// listed, 4.7 -> 6.3 scanned items): they pay where a launch is bound by what its waves score, not by a wave's set-up chain.  With
+// config 3's body and scene, us per launch, quarters / eighths: 512 k queries 42.9 / 43.5, 1.02 M 68.6 / 69.0, 2.05 M 125.6 / 127.7,
+// 4.1 M 300.5 / 281.9; config 5 (5.36 M) 571.8 / 531.8 and 408.5 -> 392.1 ms per step (profiles/r21_search_items_ab.txt).  So
+// eighths are taken above NN_ITEMS8_MIN_QUERIES, the largest size they were measured to lose at; the crossing lies between 2.05 M
+// and 4.1 M queries.  forced: 0 automatic, 4 or 8 as fdcap_debug_nn_search_form asked -- 8 still only where the ids fit.
+constexpr int NN_ITEM_ID_MAX = 0xFFFF, NN_ITEMS8_MIN_QUERIES = 1 << 21;
+constexpr FDC_FORMS_HD int plan_nn_items_per_chunk(int nq, int nchunk, bool eighths, int forced) {
+    return eighths && forced != 4 && 8LL * nchunk <= NN_ITEM_ID_MAX && (forced == 8 || nq > NN_ITEMS8_MIN_QUERIES) ? 8 : 4;
+}
+// (ipc is 4 or 8: shifts and masks, the kernel's own arithmetic)
+constexpr FDC_FORMS_HD int nn_item_id(int ipc, int chunk, int item) { return ipc * chunk + item; }
+constexpr FDC_FORMS_HD int nn_item_chunk(int ipc, int id) { return id >> (ipc == 8 ? 3 : 2); }
+constexpr FDC_FORMS_HD int nn_item_of(int ipc, int id) { return id & (ipc - 1); }
+
 struct NNPlan {
     Form form = F_NN_DIRECT;
     int wpg = 0;               // F_NN_STREAM_*: waves per group of 32 queries

@@ -131,8 +131,10 @@ __global__ __launch_bounds__(256) void sc_rs_scatter_kernel(const unsigned* __re
 }
 
 // ---- the in-loop search's query order (fdc_chamfer.h NNCache::perm, r7) ------------------------------------------------------
-// Slot -> query, by the k-d quarter of each query's current neighbour (seedpt.w: its position in the sorted scene, >> 7), ties by
+// Slot -> query, by the k-d node of each query's current neighbour (seedpt.w: its position in the sorted scene, >> shift), ties by
 // query index (the sort is stable and starts from the identity): waves of 32 queries that reach nearly one list of quarters.
+// r21: the node is the 32-point tile where the scene's tiles fit the 16-bit key (nn_order_key_shift, fdc_forms.h), not the
+// 128-point quarter of r7: queries of one quarter can sit at opposite ends of it, and their union reaches the whole ring around it.
 // A log-bucket of the neighbour distance as a second key was modelled on the bench scene and did not shrink the lists further.
 // The sort (r11) is the query order's own LSD radix sort, two 8-bit passes over the 16-bit key, stable: the order the scene
 // build's sort above would give, without its one-workgroup scan of all 256 x blocks counters.  Six launches: keys + pass-0
@@ -156,7 +158,7 @@ static inline size_t nn_query_order_ints(int nq) { return 4 * (size_t)nq + 256 *
 template <int ROUNDS>
 __global__ __launch_bounds__(256) void nn_qs_keys_kernel(const float4* __restrict__ seedpt, int nq, unsigned* __restrict__ key,
                                                          int* __restrict__ val, unsigned* __restrict__ hist, int nb,
-                                                         int* __restrict__ hdr, int groups) {
+                                                         int* __restrict__ hdr, int groups, int shift) {
     constexpr int TILE = 256 * ROUNDS;
     __shared__ unsigned h[256];
     const int tid = threadIdx.x;
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(256) void nn_qs_keys_kernel(const float4* __restric
         const int i = tile0 + r * 256 + tid;
         if (i < nq) {
             const int pos = __float_as_int(seedpt[i].w);          // -1: no neighbour (a NaN query): last
-            const unsigned k = pos >= 0 ? min((unsigned)pos >> 7, 0xFFFFu) : 0xFFFFu;
+            const unsigned k = pos >= 0 ? min((unsigned)pos >> shift, 0xFFFFu) : 0xFFFFu;
             key[i] = k;
             val[i] = i;
             atomicAdd(&h[k & 255u], 1u);
@@ -272,24 +274,24 @@ __global__ __launch_bounds__(256) void nn_qs_scatter_kernel(const unsigned* __re
 
 template <int ROUNDS>
 static inline void nn_query_order_launches(const float4* seedpt, int nq, unsigned* key, int* perm, int* val, unsigned* hist, unsigned* tot, int nb,
-                                           int* hdr, int groups, hipStream_t st) {
+                                           int* hdr, int groups, int shift, hipStream_t st) {
     // 16-bit keys: (perm, key) -> (val, key + nq) -> (perm, key)
-    hipLaunchKernelGGL((nn_qs_keys_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, seedpt, nq, key, perm, hist, nb, hdr, groups);
+    hipLaunchKernelGGL((nn_qs_keys_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, seedpt, nq, key, perm, hist, nb, hdr, groups, shift);
     hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
     hipLaunchKernelGGL((nn_qs_scatter_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, key, perm, key + nq, val, nq, 0, hist, tot, nb);
     hipLaunchKernelGGL((nn_qs_hist_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, key + nq, nq, hist, nb);
     hipLaunchKernelGGL(nn_qs_rows_kernel, dim3(64), dim3(256), 0, st, hist, nb, tot);
     hipLaunchKernelGGL((nn_qs_scatter_kernel<ROUNDS>), dim3(nb), dim3(256), 0, st, key + nq, val, key, perm, nq, 8, hist, tot, nb);
 }
-static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, hipStream_t st) {
+static inline hipError_t nn_query_order(const float4* seedpt, int nq, int* qbuf, int* hdr, int groups, int shift, hipStream_t st) {
     const int nb = nn_query_order_blocks(nq);
     int* const perm = qbuf;
     int* const val = qbuf + nq;
     unsigned* const key = (unsigned*)(qbuf + 2 * (size_t)nq);
     unsigned* const hist = key + 2 * (size_t)nq;
     unsigned* const tot = hist + 256 * (size_t)nb;
-    if (nn_query_order_rounds(nq) == QS_ROUNDS_SHORT) nn_query_order_launches<QS_ROUNDS_SHORT>(seedpt, nq, key, perm, val, hist, tot, nb, hdr, groups, st);
-    else nn_query_order_launches<QS_ROUNDS>(seedpt, nq, key, perm, val, hist, tot, nb, hdr, groups, st);
+    if (nn_query_order_rounds(nq) == QS_ROUNDS_SHORT) nn_query_order_launches<QS_ROUNDS_SHORT>(seedpt, nq, key, perm, val, hist, tot, nb, hdr, groups, shift, st);
+    else nn_query_order_launches<QS_ROUNDS>(seedpt, nq, key, perm, val, hist, tot, nb, hdr, groups, shift, st);
     return hipGetLastError();
 }
 
@@ -414,7 +416,7 @@ __device__ __forceinline__ float sc_pad(float lo, float hi) {                // 
 __global__ __launch_bounds__(MF_CH) void sc_finalize_kernel(const float* __restrict__ xyz, const int* __restrict__ order, int n,
                                                             float4* __restrict__ orig, float4* __restrict__ sorted, int* __restrict__ inv,
                                                             float4* __restrict__ bounds, float4* __restrict__ qbounds,
-                                                            uint4* __restrict__ frags, float4* __restrict__ centers) {
+                                                            float4* __restrict__ ebounds, uint4* __restrict__ frags, float4* __restrict__ centers) {
 #pragma clang fp contract(off)
     static_assert(MF_CH % 256 == 0 && MF_CH / 4 % 64 == 0, "a quarter cell is a whole number of waves");
     constexpr int NW = MF_CH / 64, WPQ = NW / 4;
@@ -452,6 +454,17 @@ __global__ __launch_bounds__(MF_CH) void sc_finalize_kernel(const float* __restr
             for (int k = 0; k < 3; ++k) qh[k] = INFINITY;
         qbounds[2 * ((size_t)ch * 4 + j)] = make_float4(ql[0], ql[1], ql[2], 0.f);
         qbounds[2 * ((size_t)ch * 4 + j) + 1] = make_float4(qh[0], qh[1], qh[2], 0.f);
+    }
+    if (j >= 64 && j < 64 + NW) {                                             // r21: the 64-point eighths (one wave each), as the quarters
+        const int w = j - 64;
+        float el[3], eh[3];
+        for (int k = 0; k < 3; ++k) { el[k] = wlo[w][k]; eh[k] = whi[w][k]; }
+        if (ch * MF_CH + w * 64 < n)
+            for (int k = 0; k < 3; ++k) { const float pad = sc_pad(el[k], eh[k]); el[k] -= pad; eh[k] += pad; }
+        else
+            for (int k = 0; k < 3; ++k) eh[k] = INFINITY;
+        ebounds[2 * ((size_t)ch * NW + w)] = make_float4(el[0], el[1], el[2], 0.f);
+        ebounds[2 * ((size_t)ch * NW + w) + 1] = make_float4(eh[0], eh[1], eh[2], 0.f);
     }
     if (j == 0) {                                                             // the cell's box (never empty) and its centre
         float cl[3], chh[3];
@@ -568,7 +581,8 @@ inline void scene_order_host(const float* xyz, int64_t ns, std::vector<int>& ord
     }
 }
 
-struct SceneTables {            // device pointers, sized by the caller: ns points, nchunk = ceil(ns / MF_CH) cells
+struct SceneTables {            // device pointers, sized by the caller: ns points, nchunk = ceil(ns / MF_CH) cells; qbounds: 8 + 16 boxes' float4
+                                // per cell -- [nchunk][4]{lo, hi} of the quarters, then [nchunk][8]{lo, hi} of the 64-point eighths
     float4* orig; float4* sorted; int* inv; float4* bounds; float4* qbounds; float4* sbounds; uint4* frags; float4* centers;
 };
 
@@ -640,7 +654,7 @@ inline hipError_t scene_build_device(const float* xyz_host, int64_t ns64, const 
         }
         order = list[3][cur];
     }
-    hipLaunchKernelGGL(sc_finalize_kernel, dim3(nchunk), dim3(MF_CH), 0, st, xyz, order, ns, T.orig, T.sorted, T.inv, T.bounds, T.qbounds,
+    hipLaunchKernelGGL(sc_finalize_kernel, dim3(nchunk), dim3(MF_CH), 0, st, xyz, order, ns, T.orig, T.sorted, T.inv, T.bounds, T.qbounds, T.qbounds + 8 * (size_t)nchunk,
                        T.frags, T.centers);
     hipLaunchKernelGGL(sc_super_kernel, dim3((nsuper + 255) / 256), dim3(256), 0, st, T.bounds, nchunk, T.sbounds, nsuper);
     e = hipGetLastError();

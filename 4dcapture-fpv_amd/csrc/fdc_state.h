@@ -98,7 +98,7 @@ struct SceneSet {
     DevBuf<float4> scene_sorted;   // k-d cell order {x,y,z,bits(original index)}: what the NN scan streams
     DevBuf<float4> scene_bounds;   // axis-aligned box {lo},{hi} of each MF_CH-point chunk of scene_sorted
     DevBuf<float4> scene_sbounds;  // ... of each run of ST4_SUPER chunks
-    DevBuf<float4> scene_qbounds;  // ... of each quarter chunk (128 points = four MFMA tiles, one k-d node): [chunk][4]{lo},{hi}
+    DevBuf<float4> scene_qbounds;  // ... of each quarter chunk (128 points = four MFMA tiles, one k-d node): [chunk][4]{lo},{hi}; then [chunk][8] of the eighths
     DevBuf<int> scene_inv;         // original index -> position in scene_sorted
     DevBuf<uint4> scene_frags;     // precomputed chunk-centred bf16 MFMA A fragments of scene_sorted
     DevBuf<float4> scene_centers;  // chunk centres {x,y,z,radius}

@@ -861,6 +861,18 @@ int fdcap_debug_contact_perm(fdcap_ctx* ctx, int32_t* perm_h, int32_t n);
  * Needs no optimiser; allocates and frees its own device buffers.  Synchronises `stream`. */
 int fdcap_debug_nn_query_sort(fdcap_ctx* ctx, const int32_t* pos_h, int32_t nq, int32_t groups, int32_t hdr_len, int32_t* hdr_io,
                               int32_t* perm_out, void* stream);
+/* ... under the key min(pos >> shift, 0xFFFF), shift 5, 6 or 7 (r21: the order's key is the neighbour's 32-point tile wherever the
+ * scene's tiles fit 16 bits; else FDCAP_E_ARG).  fdcap_debug_nn_query_sort is this call with shift 7. */
+int fdcap_debug_nn_query_sort_shift(fdcap_ctx* ctx, const int32_t* pos_h, int32_t nq, int32_t groups, int32_t hdr_len, int32_t* hdr_io,
+                                    int32_t* perm_out, int32_t shift, void* stream);
+/* Tests / diagnosis (r21): the streaming search's scheduling choices within one build (scheduling only: the same bits), process-wide
+ * like fdcap_set_nn_kernel.  key_shift: the query order's key is the neighbour's position in the sorted scene >> key_shift -- 5, 6 or
+ * 7; 0: automatic, the finest of them whose keys stay below 0xFFFF for the scene's size.  items_per_chunk: work items per 512-point
+ * chunk of the one-wave form -- 4 (quarters), 8 (64-point eighths; quarters all the same where 8 x chunks exceeds the 16-bit ids) or 0
+ * (automatic: 8 where the ids fit and the launch has more than 2^21 queries); anything else FDCAP_E_ARG.  Drops the kept work lists of this context (the optimiser's, every
+ * segment of a batch of scenes, and fdcap_chamfer_fwd_scene's, which starts over); an optimiser's order is rebuilt after its next
+ * search launch.  Other contexts of the process must not hold kept lists across the call.  Synchronises the device. */
+int fdcap_debug_nn_search_form(fdcap_ctx* ctx, int32_t key_shift, int32_t items_per_chunk);
 
 /* In-loop timing of EVERY launch of an iteration (r6; bench.py's roofline.per_kernel[].us_live): while enabled (max_events > 0) the
  * optimiser records a HIP event on its launch stream at every boundary between two launches of an iteration (up to max_events

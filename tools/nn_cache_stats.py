@@ -2,6 +2,9 @@
 """Work-list cache of the in-loop NN launch over a whole fit: kept / rebuilt waves and list sizes per block of iterations.
 BOX_HIST=<block> (r15): instead, per block of that many launches, the count n that enters each of the search's three box-test stages
 (near chunks of a batch, 4 x listed chunks, the filter's raw list): stages run, mean and largest n, shares n <= 8 / <= 16 / <= 32.
+ITEMS=<block> (r21): instead, per block of that many launches and per wave: listed items (the raw list the filter takes), scanned items
+(after the filter), 32-point tiles scored and tiles with a filter hit.  KEY_SHIFT=<5|6|7> forces the query order's key
+and ITEMS_PER_CHUNK=<4|8> its work items (fdcap_debug_nn_search_form; default: the build's own choice).
 Needs the -DFDC_NN_STATS build (FDCAP_LIB)."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,6 +29,9 @@ x78 = torch.empty(N, capi.XDIM, device="cuda")
 capi.check(lib.fdcap_params_75_to_78(capi.dptr(body), N, capi.dptr(x78), capi.current_stream()), "75->78")
 fop._mode = "global"; fop.init(x78)
 P = first_phase2_iter(500)
+if os.environ.get("KEY_SHIFT") or os.environ.get("ITEMS_PER_CHUNK"):
+    capi.check(lib.fdcap_debug_nn_search_form(h, int(os.environ.get("KEY_SHIFT", "0")), int(os.environ.get("ITEMS_PER_CHUNK", "0"))), "nn_search_form")
+ITEMS = int(os.environ.get("ITEMS", "0"))
 out = (ctypes.c_ulonglong * 8)()
 raw.fdcap_debug_nn_stats(out)
 BOX = int(os.environ.get("BOX_HIST", "0"))
@@ -34,6 +40,13 @@ if BOX: raw.fdcap_debug_nn_box_hist.argtypes = [ctypes.POINTER(ctypes.c_ulonglon
 for ii in range(P):
     st = capi.current_stream()
     capi.check(lib.fdcap_opt_backward(h, ii, P, 0, st), "bwd"); capi.check(lib.fdcap_opt_step(h, ii, P, st), "step")
+    if ITEMS:
+        if ii % ITEMS == ITEMS - 1 or ii == P - 1:
+            raw.fdcap_debug_nn_stats(out)
+            w = max(out[4] + out[5], 1)
+            print(f"launches {ii - ii % ITEMS:3d}-{ii:3d}: per wave listed {out[6] / w:5.2f}  scanned {out[3] / w:5.2f}  tiles {out[0] / w:5.2f}  "
+                  f"tiles with a hit {out[1] / w:5.2f}  (lists kept {out[4] / w:6.1%})")
+        continue
     if BOX:
         if ii % BOX == BOX - 1 or ii == P - 1:
             raw.fdcap_debug_nn_box_hist(box)
