@@ -82,6 +82,7 @@ SYMBOLS = {
     "fdcap_debug_scene_hash": (c_int32, [c_void_p, c_void_p]),
     "fdcap_debug_scene_table": (c_int32, [c_void_p, c_int32, c_void_p, POINTER(c_int64)]),
     "fdcap_debug_kernel_forms": (c_int32, [c_void_p, c_int32, c_int32]),
+    "fdcap_debug_wave_sum_pack": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
     "fdcap_debug_live_allocations": (c_int32, [c_void_p]),
     "fdcap_debug_pose_joint_sets": (c_int32, [c_void_p, c_void_p]),
     "fdcap_set_contact_ids": (c_int32, [c_void_p, c_void_p, c_int32]),
@@ -205,6 +206,7 @@ SYMBOLS = {
     "fdcap_debug_contact_diet": (c_int32, [c_void_p, c_void_p]),
     "fdcap_debug_nn_box_tests": (c_int32, [c_void_p, c_void_p]),
     "fdcap_debug_contact_perm": (c_int32, [c_void_p, c_void_p, c_int32]),
+    "fdcap_debug_skin_bwd_sums": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fdcap_debug_nn_query_sort": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "fdcap_debug_nn_query_sort_shift": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p]),
     "fdcap_debug_nn_search_form": (c_int32, [c_void_p, c_int32, c_int32]),

@@ -107,6 +107,27 @@ int fdcap_debug_kernel_forms(char* buf, int32_t len, int32_t reset) {
     return FDCAP_OK;
 }
 
+// test / diagnosis: the packed wave sums (fdc_math.h wave_sum64_pack) next to wave_sum64 per value, one wave on in_h [64][n]
+int fdcap_debug_wave_sum_pack(const float* in_h, int32_t n, float* packed_h, float* each_h) {
+    if (!in_h || !packed_h || !each_h || n < 1 || n > 16) return FDCAP_E_ARG;
+    DevBuf<float> in, out;
+    hipError_t e = in.upload(in_h, (size_t)64 * n);
+    if (e == hipSuccess) e = out.ensure((size_t)2 * n);
+    if (e != hipSuccess) return (int)e;
+    switch (n) {
+#define FDC_WSP_CASE(N) case N: wave_sum_pack_debug_kernel<N><<<1, 64>>>(in.p, out.p, out.p + n); break;
+    FDC_WSP_CASE(1) FDC_WSP_CASE(2) FDC_WSP_CASE(3) FDC_WSP_CASE(4) FDC_WSP_CASE(5) FDC_WSP_CASE(6) FDC_WSP_CASE(7) FDC_WSP_CASE(8)
+    FDC_WSP_CASE(9) FDC_WSP_CASE(10) FDC_WSP_CASE(11) FDC_WSP_CASE(12) FDC_WSP_CASE(13) FDC_WSP_CASE(14) FDC_WSP_CASE(15) FDC_WSP_CASE(16)
+#undef FDC_WSP_CASE
+    }
+    e = hipGetLastError();
+    const hipError_t es = hipDeviceSynchronize();                // (the buffers are freed on return: wait, whatever the launch said)
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) e = hipMemcpy(packed_h, out.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(each_h, out.p + n, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? FDCAP_OK : (int)e;
+}
+
 // test / diagnosis: what the owning types of fdc_own.h hold in this process right now: out3 = {blocks (device and pinned host), their
 // bytes, events}.  Tests take differences around a create ... destroy pair.
 int fdcap_debug_live_allocations(int64_t* out3) {

@@ -63,6 +63,7 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->seeded = false;
     o->nnpt_valid = false;
     o->n_recompute = 0;
+    o->skb_valid = false;
     o->dctT = o->dctC = o->dctW = 0;
     o->dct_clips = false;
     o->dct_grad = false;
@@ -378,6 +379,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
     const bool contact_grad = o->contact_on && lw.contact != 0.f;
     const bool contact_fwd = o->contact_on && (contact_grad || log_terms);
     o->lt.phase = contact_grad ? 0 : 1;
+    o->skb_valid = false;                                   // (fdcap_debug_skin_bwd_sums: set again below where this backward has a contact gradient)
     // The joints this iteration's loss can reach (plan_pose_joints, fdc_forms.h): the contact terms through the skinning transforms of
     // the joints the contact set is skinned to, everything else through the world joints -- phase 2's world smoothing (world_on), the
     // DCT term, every printed term of a logging iteration.  A sharded run keeps the world joints too: its run-ahead forward and the
@@ -433,6 +435,7 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         // (gathered records stand in for the scene pointer only: the launch stays the one a stand-alone fit's staged search leads to)
         cg.recompute = pl.form == F_SKIN_BWD_VEC && cg.nnpt != nullptr && o->sw.contact_recompute && !(o->multi_scene() && o->nnpt_filled);
         o->n_recompute += cg.recompute;
+        o->skb_cg = cg; o->skb_kn = kn; o->skb_ctab = ctab; o->skb_valid = true;
         const dim3 grid(pl.grid), block(pl.block);
 #define FDC_SKC(KERNEL) hipLaunchKernelGGL(KERNEL, grid, block, pl.lds, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, o->M.p, o->scale.p, 2, o->dVoff.p, \
                                            o->dA.p, o->dtransl_v.p, o->dMv.p, o->dsv.p, cg, kn, ctab)
@@ -583,6 +586,50 @@ int fdcap_debug_nn_query_order(fdcap_ctx* c, int32_t mode, const int32_t* perm_h
     ord.sorted_groups = 0;
     ord.age = 0;
     return FDCAP_OK;
+}
+
+// Tests / diagnosis (r22): what the skinning backward of the last fdcap_opt_backward with a contact gradient left, per frame: dA
+// [n_local][55 * 12] (rows below *ja_hi_out are written), dtransl [n_local][3], dM [n_local][12], ds [n_local], dVoff [n_local][nc][3].
+// reference != 0: not what the launch left but the same state run again through skin_bwd_small_kernel<., ., false> -- every sum by
+// wave_sum on its own, as every build before r22 formed them -- into buffers of its own (contact sets of at most 512 vertices).
+int fdcap_debug_skin_bwd_sums(fdcap_ctx* c, int32_t reference, float* dA_d, float* dtransl_d, float* dMv_d, float* dsv_d, float* dVoff_d,
+                              int32_t* ja_hi_out, void* stream) {
+    if (!c || !c->opt) return FDCAP_E_STATE;
+    if (!dA_d || !dtransl_d || !dMv_d || !dsv_d || !dVoff_d || !ja_hi_out) return FDCAP_E_ARG;
+    OptState* o = c->opt;
+    if (!o->skb_valid) return FDCAP_E_STATE;
+    hipStream_t st = (hipStream_t)stream;
+    const int nl = o->cfg.n_local, nc = c->nc;
+    const size_t R = (size_t)o->R;
+    const float *sA = o->dA.p, *sT = o->dtransl_v.p, *sM = o->dMv.p, *sS = o->dsv.p, *sV = o->dVoff.p;
+    DevBuf<float> tA, tT, tM, tS, tV;
+    if (reference) {
+        const SkinModel smc = c->contact.model();
+        const int nnz = c->contact.nnz;
+        const size_t lds = (size_t)6 * nc * sizeof(float) + (size_t)nnz * sizeof(float) + (((size_t)nnz * 2 + 15) & ~(size_t)15);
+        if (nc > 512 || nnz > SKS_MAXNNZ || lds > 57000) return FDCAP_E_STATE;
+        HIP_TRY(tA.ensure(R * NJ * 12)); HIP_TRY(tT.ensure(R * 3)); HIP_TRY(tM.ensure(R * 12)); HIP_TRY(tS.ensure(R)); HIP_TRY(tV.ensure(R * nc * 3));
+        HIP_TRY(hipMemsetAsync(tA.p, 0, R * NJ * 12 * sizeof(float), st));
+        ContactGradIn cg = o->skb_cg;
+        cg.recompute = 0; cg.loss_rows = nullptr;
+        if (nnz <= 2048)
+            hipLaunchKernelGGL((skin_bwd_small_kernel<2, 8, false>), dim3(nl), dim3(256), lds, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, o->M.p,
+                               o->scale.p, 2, tV.p, tA.p, tT.p, tM.p, tS.p, cg, o->skb_kn, o->skb_ctab);
+        else
+            hipLaunchKernelGGL((skin_bwd_small_kernel<2, 24, false>), dim3(nl), dim3(256), lds, st, smc, nc, nnz, o->X.p, o->Voff.p, o->A.p, o->M.p,
+                               o->scale.p, 2, tV.p, tA.p, tT.p, tM.p, tS.p, cg, o->skb_kn, o->skb_ctab);
+        HIP_TRY(hipGetLastError());
+        sA = tA.p; sT = tT.p; sM = tM.p; sS = tS.p; sV = tV.p;
+    }
+    *ja_hi_out = c->contact.ja_hi;
+    hipError_t e = hipMemcpyAsync(dA_d, sA + (size_t)2 * NJ * 12, (size_t)nl * NJ * 12 * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dtransl_d, sT + 2 * 3, (size_t)nl * 3 * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dMv_d, sM + 2 * 12, (size_t)nl * 12 * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dsv_d, sS + 2, (size_t)nl * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dVoff_d, sV + (size_t)2 * nc * 3, (size_t)nl * nc * 3 * sizeof(float), hipMemcpyDeviceToDevice, st);
+    const hipError_t es = hipStreamSynchronize(st);            // (the reference's buffers are freed on return)
+    if (e == hipSuccess) e = es;
+    return e == hipSuccess ? FDCAP_OK : (int)e;
 }
 
 // Tests / diagnosis: the query order's sort on its own (nn_query_order, exactly as nn_search launches it) on neighbour positions

@@ -182,6 +182,23 @@ __global__ __launch_bounds__(768) void blend_skin_fwd_kernel(const float* __rest
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 
+// test / diagnosis (fdcap_debug_wave_sum_pack): one wave, in [64][N]; packed[i] = lane WAVE_PACK_LANE0 + i of wave_sum64_pack,
+// each[i] = wave_sum64 of value i on its own
+template <int N>
+__global__ __launch_bounds__(64) void wave_sum_pack_debug_kernel(const float* __restrict__ in, float* __restrict__ packed, float* __restrict__ each) {
+    const int lane = threadIdx.x;
+    float v[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = in[lane * N + i];
+    const float p = wave_sum64_pack(v, lane);
+    if (lane >= WAVE_PACK_LANE0 && lane < WAVE_PACK_LANE0 + N) packed[lane - WAVE_PACK_LANE0] = p;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const float e = wave_sum64(v[i]);
+        if (lane == 0) each[i] = e;
+    }
+}
+
 // workgroup per frame: skinning + world-transform backward of d loss / d world vertices, reduced over
 // the frame's vertex set.  dVw / dVoff are [rows, nc, 3] and may alias (each thread reads its vertex's
 // gradient before it writes the vertex's pose-blend gradient).
@@ -464,6 +481,8 @@ __global__ __launch_bounds__(256, FDC_SKB_OCC) void skin_bwd_kernel(SkinModel sm
 #pragma unroll
                     for (int e = 0; e < 12; ++e) pa[e] += w * t[e];
                 }
+                // (one by one here and at the kernel's end, not wave_sum64_pack as in the contact-set kernels: next to the prefetched
+                // lists the packed tree's temporaries spill 17 registers in the <true, false> instance at its five waves per SIMD)
 #pragma unroll
                 for (int e = 0; e < 12; ++e) {
                     float v = wave_sum(pa[e]);
@@ -540,7 +559,9 @@ __global__ __launch_bounds__(256) void skin_bwd_reduce_kernel(const float* __res
 // The dA sums run joint by joint over ascending vertices with the same wave-sum tree: run-to-run reproducible.
 // (VPT vertices and KC weight-list entries per thread in registers: 130 VGPRs for 4 / 16 cost a wave per SIMD -- the launch
 // then needs a second generation of workgroups; the loop's 500 vertices / 2000 weights take the 2 / 8 instance)
-template <int SKS_VPT, int SKS_KC>
+// PACK = false (fdcap_debug_skin_bwd_sums only): every sum through wave_sum on its own, lane 0 stores -- the form every build before r22
+// ran, kept as the specification of the packed sums' bits
+template <int SKS_VPT, int SKS_KC, bool PACK = true>
 __global__ __launch_bounds__(256) void skin_bwd_small_kernel(SkinModel sm, int nc, int nnz, const float* __restrict__ X,
                                                              const float* __restrict__ Voff, const float* __restrict__ A,
                                                              const float* __restrict__ M, const float* __restrict__ scale,
@@ -668,18 +689,33 @@ __global__ __launch_bounds__(256) void skin_bwd_small_kernel(SkinModel sm, int n
                 pa[4] += gy * px; pa[5] += gy * py; pa[6] += gy * pz; pa[7] += gy;
                 pa[8] += gz * px; pa[9] += gz * py; pa[10] += gz * pz; pa[11] += gz;
             }
+            if (PACK) {
+                // the twelve sums in one packed tree (wave_sum64_pack: wave_sum's bits), stored by the twelve lanes that hold them
+                const float v = wave_sum64_pack(pa, lane);
+                if (lane >= WAVE_PACK_LANE0 && lane < WAVE_PACK_LANE0 + 12) sdA[j * 12 + lane - WAVE_PACK_LANE0] = v;
+            } else {
 #pragma unroll
-            for (int e = 0; e < 12; ++e) {
-                const float v = wave_sum(pa[e]);
-                if (lane == 0) sdA[j * 12 + e] = v;
+                for (int e = 0; e < 12; ++e) {
+                    const float v = wave_sum(pa[e]);
+                    if (lane == 0) sdA[j * 12 + e] = v;
+                }
             }
         }
     }
     FDC_FR_STAMP(2, 3);
+    if (!PACK) {
 #pragma unroll
-    for (int i = NBETA; i < SKB_NACC; ++i) {
-        const float v = wave_sum(acc[i]);
-        if (lane == 0) sred[wave][i] = v;
+        for (int i = NBETA; i < SKB_NACC; ++i) {
+            const float v = wave_sum(acc[i]);
+            if (lane == 0) sred[wave][i] = v;
+        }
+    } else {   // the sixteen per-frame sums likewise
+        static_assert(SKB_NACC - NBETA == 16, "one packed tree");
+        float t[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) t[i] = acc[NBETA + i];
+        const float v = wave_sum64_pack(t, lane);
+        if (lane >= WAVE_PACK_LANE0) sred[wave][NBETA + lane - WAVE_PACK_LANE0] = v;
     }
     const float ct = (cg.loss_rows != nullptr) ? wave_sum(cterm) : 0.f;
     if (cg.loss_rows && lane == 0) sred[wave][0] = ct;
@@ -842,18 +878,19 @@ __global__ __launch_bounds__(256) void skin_bwd_vec_kernel(SkinModel sm, int nc,
                 pa[4] += gy * px; pa[5] += gy * py; pa[6] += gy * pz; pa[7] += gy;
                 pa[8] += gz * px; pa[9] += gz * py; pa[10] += gz * pz; pa[11] += gz;
             }
-#pragma unroll
-            for (int e = 0; e < 12; ++e) {
-                const float v = wave_sum(pa[e]);
-                if (lane == 0) sdA[j * 12 + e] = v;
-            }
+            // the twelve sums in one packed tree (wave_sum64_pack: wave_sum's bits), stored by the twelve lanes that hold them
+            const float v = wave_sum64_pack(pa, lane);
+            if (lane >= WAVE_PACK_LANE0 && lane < WAVE_PACK_LANE0 + 12) sdA[j * 12 + lane - WAVE_PACK_LANE0] = v;
         }
     }
     FDC_FR_STAMP(2, 3);
+    {   // the sixteen per-frame sums likewise
+        static_assert(SKB_NACC - NBETA == 16, "one packed tree");
+        float t[16];
 #pragma unroll
-    for (int i = NBETA; i < SKB_NACC; ++i) {
-        const float v = wave_sum(acc[i]);
-        if (lane == 0) sred[wave][i] = v;
+        for (int i = 0; i < 16; ++i) t[i] = acc[NBETA + i];
+        const float v = wave_sum64_pack(t, lane);
+        if (lane >= WAVE_PACK_LANE0) sred[wave][NBETA + lane - WAVE_PACK_LANE0] = v;
     }
     const float ct = (cg.loss_rows != nullptr) ? wave_sum(cterm) : 0.f;
     if (cg.loss_rows && lane == 0) sred[wave][0] = ct;

@@ -13,8 +13,10 @@
 
 #if defined(__HIPCC__)
 #define FDC_HD __host__ __device__ __forceinline__
+#define FDC_UNROLL _Pragma("unroll")
 #else
 #define FDC_HD inline
+#define FDC_UNROLL
 #endif
 
 namespace fdc {
@@ -48,6 +50,128 @@ __device__ __forceinline__ float wave_sum64(float v) {
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0x4, 0xF, false));
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0x8, 0xF, false));
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+// One register of a wavefront as wave_sum64_pack_w sees it: the lane's float, moved by DPP and by the LDS crossbar.  (The host
+// build has WaveModel below in its place: sixty-four floats and the same moves spelled out.)
+struct WaveReg {
+    float x;
+    static __device__ __forceinline__ WaveReg zero() { return {0.f}; }
+    static __device__ __forceinline__ WaveReg add(WaveReg a, WaveReg b) { return {a.x + b.x}; }
+    // lanes whose DPP source is outside their row, or whose bank (quad of the row) is not in BANK, keep `old`
+    template <int CTRL, int BANK = 0xF>
+    static __device__ __forceinline__ WaveReg dpp(WaveReg old, WaveReg a) {
+        return {__int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old.x), __float_as_int(a.x), CTRL, 0xF, BANK, false))};
+    }
+    // (lane & mask) == mask ? b : a
+    static __device__ __forceinline__ WaveReg sel(int mask, int lane, WaveReg a, WaveReg b) { return {(lane & mask) == mask ? b.x : a.x}; }
+    // lane l reads lane l - 16 (row 0 reads row 3)
+    static __device__ __forceinline__ WaveReg row_down(WaveReg a, int lane) {
+        return {__int_as_float(__builtin_amdgcn_ds_bpermute(((lane - 16) & 63) << 2, __float_as_int(a.x)))};
+    }
+};
+#else
+// The sixty-four lanes of a wavefront on the host (tests only): DPP moves by their control word -- quad_perm, row_shl / row_shr,
+// row_mirror, row_half_mirror, row_bcast15 -- with row and bank write masks; a lane that is masked off or whose source lies outside
+// its row keeps `old` (bound_ctrl off).
+struct WaveModel {
+    float x[64];
+    static WaveModel zero() { WaveModel r; for (int l = 0; l < 64; ++l) r.x[l] = 0.f; return r; }
+    static WaveModel add(const WaveModel& a, const WaveModel& b) { WaveModel r; for (int l = 0; l < 64; ++l) r.x[l] = a.x[l] + b.x[l]; return r; }
+    static int dpp_src(int ctrl, int l) {                   // -1: no source
+        const int i = l & 15, row = l & ~15;
+        if (ctrl < 0x100) return (l & ~3) | ((ctrl >> (2 * (l & 3))) & 3);
+        if (ctrl >= 0x101 && ctrl <= 0x10F) return i + (ctrl - 0x100) < 16 ? l + (ctrl - 0x100) : -1;
+        if (ctrl >= 0x111 && ctrl <= 0x11F) return i >= ctrl - 0x110 ? l - (ctrl - 0x110) : -1;
+        if (ctrl == 0x140) return row | (15 - i);
+        if (ctrl == 0x141) return (l & ~7) | (7 - (l & 7));
+        if (ctrl == 0x142) return row ? row - 1 : -1;
+        return -1;
+    }
+    template <int CTRL, int BANK = 0xF, int ROW = 0xF>
+    static WaveModel dpp(const WaveModel& old, const WaveModel& a) {
+        WaveModel r;
+        for (int l = 0; l < 64; ++l) {
+            const int s = dpp_src(CTRL, l);
+            const bool on = s >= 0 && ((ROW >> (l >> 4)) & 1) && ((BANK >> ((l >> 2) & 3)) & 1);
+            r.x[l] = on ? a.x[s] : old.x[l];
+        }
+        return r;
+    }
+    static WaveModel sel(int mask, int, const WaveModel& a, const WaveModel& b) {
+        WaveModel r;
+        for (int l = 0; l < 64; ++l) r.x[l] = (l & mask) == mask ? b.x[l] : a.x[l];
+        return r;
+    }
+    static WaveModel row_down(const WaveModel& a, int) { WaveModel r; for (int l = 0; l < 64; ++l) r.x[l] = a.x[(l - 16) & 63]; return r; }
+};
+// wave_sum64's moves on the model: lane 63 holds what the device function returns
+inline float wave_sum64_model(WaveModel v) {
+    typedef WaveModel W;
+    v = W::add(v, W::dpp<0xB1>(W::zero(), v));
+    v = W::add(v, W::dpp<0x4E>(W::zero(), v));
+    v = W::add(v, W::dpp<0x141>(W::zero(), v));
+    v = W::add(v, W::dpp<0x140>(W::zero(), v));
+    v = W::add(v, W::dpp<0x142, 0xF, 0x2>(W::zero(), v));
+    v = W::add(v, W::dpp<0x142, 0xF, 0x4>(W::zero(), v));
+    v = W::add(v, W::dpp<0x142, 0xF, 0x8>(W::zero(), v));
+    return v.x[63];
+}
+#endif
+
+// N <= 16 wave sums at once: lane WAVE_PACK_LANE0 + i of the result holds wave_sum64(v[i]), bit for bit.  wave_sum64 leaves the same
+// partial sum in two lanes after its first step, in four after the second, in sixteen after the fourth; here the lanes of a quad
+// carry four different values' sums from the second step on, and the sixteen lanes of a row sixteen values' from the fourth:
+//   pairs            v + quad_perm [1,0,3,2], per value                              (a pair's two lanes: the same sum, a + b = b + a)
+//   quads            values 4 g + {0, 1} and {2, 3} merged by lane parity, + quad_perm [2,3,0,1]; then merged by lane & 2
+//   octets, rows     + row_shr:4, + row_shr:8 -- partners of equal lane & 3 (the mirrors of wave_sum64 would reverse them); lanes
+//                    12..15 of a row hold (Q3 + Q2) + (Q1 + Q0) of values 4 g .. 4 g + 3
+//   down the rows    group g moves to lanes 4 g .. 4 g + 3 (row_shl under its bank mask), then three times self + the row above
+//                    (ds_bpermute: row_bcast15 hands on one lane only): r1 + r0, r2 + (r1 + r0), r3 + (r2 + (r1 + r0)) in row 3
+// The association per value is wave_sum64's; operands change sides only (IEEE addition commutes in value; of two NaNs with different payloads the one returned may depend on the side, so bit equality
+// holds where a value's NaNs share one payload, as those of one frame's arithmetic do).  About 3 N + 6 adds, selects and moves
+// in place of 8 N, and no readlane: the caller stores from lanes LANE0 .. LANE0 + N - 1 in one instruction.  Every lane must be active.
+// W: WaveReg on the device, WaveModel on the host (tests/wave_sum_pack_cpu).
+constexpr int WAVE_PACK_LANE0 = 48;
+template <class W, int N>
+FDC_HD W wave_sum64_pack_w(const W (&v)[N], int lane) {
+    static_assert(N >= 1 && N <= 16, "a row carries sixteen values");
+    constexpr int NG = (N + 3) / 4;
+    W out = W::zero();
+FDC_UNROLL
+    for (int g = 0; g < NG; ++g) {
+        W s[4] = {W::zero(), W::zero(), W::zero(), W::zero()};
+FDC_UNROLL
+        for (int k = 0; k < 4; ++k)
+            if (4 * g + k < N) s[k] = W::add(v[4 * g + k], W::template dpp<0xB1>(W::zero(), v[4 * g + k]));
+        W r = 4 * g + 1 < N ? W::sel(1, lane, s[0], s[1]) : s[0];
+        r = W::add(r, W::template dpp<0x4E>(W::zero(), r));
+        if (4 * g + 2 < N) {
+            W q = 4 * g + 3 < N ? W::sel(1, lane, s[2], s[3]) : s[2];
+            q = W::add(q, W::template dpp<0x4E>(W::zero(), q));
+            r = W::sel(2, lane, r, q);
+        }
+        r = W::add(r, W::template dpp<0x114>(W::zero(), r));
+        r = W::add(r, W::template dpp<0x118>(W::zero(), r));
+        switch (g) {
+        case 0: out = W::template dpp<0x10C, 0x1>(out, r); break;
+        case 1: out = W::template dpp<0x108, 0x2>(out, r); break;
+        case 2: out = W::template dpp<0x104, 0x4>(out, r); break;
+        default: out = W::sel(12, lane, out, r); break;
+        }
+    }
+    // (wave_sum64's rows 2 and 3 have had +0.0 added by the masked steps before their own: a row sum of -0.0 enters as +0.0)
+    const W outz = W::add(out, W::zero());
+    W u = W::add(out, W::row_down(out, lane));
+    u = W::add(outz, W::row_down(u, lane));
+    return W::add(outz, W::row_down(u, lane));
+}
+#if defined(__HIPCC__)
+template <int N>
+__device__ __forceinline__ float wave_sum64_pack(const float (&v)[N], int lane) {
+    WaveReg w[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i].x = v[i];
+    return wave_sum64_pack_w<WaveReg, N>(w, lane).x;
 }
 __device__ __forceinline__ float wave_min64(float v) {
     v = fminf(v, dpp_move<0xB1>(v)); v = fminf(v, dpp_move<0x4E>(v)); v = fminf(v, dpp_move<0x141>(v)); v = fminf(v, dpp_move<0x140>(v));

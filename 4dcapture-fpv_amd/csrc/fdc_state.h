@@ -276,6 +276,11 @@ struct OptState {
     // rows and the scale-dependent outputs (ahead_blend: the contact set's pose-blend product is done as well)
     bool ahead = false, ahead_blend = false;
     bool nnpt_valid = false;  // the last contact forward left the neighbours' coordinates in seedpt
+    // tests / diagnosis (fdcap_debug_skin_bwd_sums): what the last skinning backward with a contact gradient was launched with
+    ContactGradIn skb_cg{};
+    int skb_kn = 0;
+    const ClipRow* skb_ctab = nullptr;
+    bool skb_valid = false;
     int n_recompute = 0;      // tests / diagnosis (fdcap_debug_contact_diet): skinning backwards launched with ContactGradIn::recompute
 };
 

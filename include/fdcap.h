@@ -122,6 +122,10 @@ int fdcap_debug_scene_table(fdcap_ctx* ctx, int32_t which, void* host_out, int64
  * check that it ran.  FDCAP_CLIP_FORMS_MIN_ROWS (environment, read once per process) lowers the row count from which the
  * clip-sized forms are selected (default 336): the reference's 300-frame fixtures then run through them. */
 int fdcap_debug_kernel_forms(char* buf, int32_t len, int32_t reset);
+/* test / diagnosis: one wave of the packed wave sums the skinning backward reduces with (csrc/fdc_math.h wave_sum64_pack) on the HOST
+ * array in_h [64][n] (lane-major), 1 <= n <= 16: packed_h [n] <- the packed tree's sums as its lanes hold them, each_h [n] <- the
+ * one-value tree (wave_sum64) per value.  The two must agree bit for bit.  Synchronises the device. */
+int fdcap_debug_wave_sum_pack(const float* in_h, int32_t n, float* packed_h, float* each_h);
 /* test / diagnosis: what the library holds in this process right now, out3 = {live memory blocks (device and pinned host), their
  * bytes, live HIP events}.  Every allocation and every event of the library is owned by a type of csrc/fdc_own.h that counts here
  * where it allocates and frees; nothing on a per-iteration path does.  A create ... destroy pair leaves all three where they were
@@ -850,6 +854,15 @@ int fdcap_debug_contact_diet(fdcap_ctx* ctx, int32_t* out4);
 /* Tests / diagnosis: one-wave search launches since fdcap_opt_create[_clips] by the lanes per listed box they were launched with
  * (FDCAP_NN_BOX_LANES): out4[0] by each stage's count, out4[1] / [2] / [3] forced 2 / 4 / 8. */
 int fdcap_debug_nn_box_tests(fdcap_ctx* ctx, int32_t* out4);
+/* Tests / diagnosis: what the skinning backward of the last fdcap_opt_backward that had a contact gradient left, per frame, into DEVICE
+ * arrays: dA_d [n_local][55 * 12] (the rows of joints below *ja_hi_out -- a HOST int -- are written), dtransl_d [n_local][3], dMv_d
+ * [n_local][12], dsv_d [n_local], dVoff_d [n_local][contacts][3] (contacts in slot order).  reference != 0: instead, the same state --
+ * parameters, pose offsets, transforms, neighbours -- run once more through the contact-set kernel with every wave sum formed on its
+ * own (lane 0 stores), as every build before the packed sums did, into buffers of its own: the two must agree byte for byte.
+ * reference needs a contact set of at most 512 vertices (else FDCAP_E_STATE).  FDCAP_E_STATE also when the last backward of this
+ * optimiser had no contact gradient, or none has run since it was created.  Synchronises `stream`. */
+int fdcap_debug_skin_bwd_sums(fdcap_ctx* ctx, int32_t reference, float* dA_d, float* dtransl_d, float* dMv_d, float* dsv_d, float* dVoff_d,
+                              int32_t* ja_hi_out, void* stream);
 /* Tests / diagnosis: perm_h [n = contacts]: internal contact slot -> position in the caller's id array (fdcap_set_contact_ids);
  * a frame's queries lie in idx / seedpt in slot order.  Synchronous copy. */
 int fdcap_debug_contact_perm(fdcap_ctx* ctx, int32_t* perm_h, int32_t n);
