@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FDCAP_LIB") or os.path.join(_HERE, "libfdcap_hip.so")
 
 NUM_LOSSES = 8
+LOSS_REPROJ = 6         # FDCAP_LOSS_REPROJ: the clip-level reprojection term's slot of losses_d
 MAX_SCENES = 8          # FDCAP_MAX_SCENES: scene slots of a context
 MAX_KEYPOINTS = 160     # FDCAP_MAX_KEYPOINTS: keypoints of a context's map
 XDIM = 78
@@ -62,6 +63,11 @@ class LbfgsConfig(ctypes.Structure):
     _fields_ = [("dim", c_int32), ("history", c_int32), ("max_iter", c_int32), ("max_eval", c_int32), ("max_steps", c_int32),
                 ("max_ls", c_int32), ("lr", c_float), ("tolerance_grad", c_float), ("tolerance_change", c_float),
                 ("ftol", c_float), ("gtol", c_float)]
+
+
+class ReprojParams(ctypes.Structure):
+    """include/fdcap.h fdcap_reproj_params: the clip-level reprojection term's intrinsics, GMoF's rho and the term's weight."""
+    _fields_ = [("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("rho", c_float), ("weight", c_float)]
 
 
 class OptConfig(ctypes.Structure):
@@ -120,6 +126,7 @@ SYMBOLS = {
     "fdcap_opt_create_clips_scenes": (c_int32, [c_void_p, POINTER(OptConfig), c_int32, POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p,
                                                 c_void_p, c_void_p, c_void_p]),
     "fdcap_opt_set_inputs": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fdcap_opt_set_reproj": (c_int32, [c_void_p, POINTER(ReprojParams), c_void_p, c_void_p]),
     "fdcap_opt_backward": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "fdcap_opt_step": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
     "fdcap_opt_backward_and_step": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),

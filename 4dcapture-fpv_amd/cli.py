@@ -27,7 +27,12 @@ its full segments).  Every clip's result is the one its own batch-of-one gives.
 every video has its own reconstruction, so without this a video of one or two clips is a batch of one or two.  Batches are filled in
 input order up to MULTICLIP_ROW_CAP rows and MAX_SCENES scenes (plan_batches_scenes); the fitter keeps the scenes in the context's
 slots by path, so a scene that the next batch uses again is neither read nor registered again.  Without the flag every planner,
-batch and refusal above is what it was."""
+batch and refusal above is what it was.
+
+`--keypoints DIR --weight-reproj W [--intrinsics FX FY CX CY] [--rho R]` (one-clip form, mode 'global'): the clip-level 2D-keypoint
+reprojection term (fitting.FittingOP.fitting(keypoints=...)).  DIR holds a detector's OpenPose-format files; the
+sorted `*_keypoints.json` are paired one per frame with the `results/*/*.pkl` files (a count mismatch is an error naming both counts) and
+mapped to the 23 body joints by innerfit.joints23_from_openpose.  With --clips the options are refused."""
 from __future__ import annotations
 
 import argparse
@@ -128,6 +133,15 @@ def plan_batches_scenes(clips, clips_per_batch=None, row_cap: int = MULTICLIP_RO
     return out
 
 
+def keypoint_files(keypoints_dir: str, n_frames: int):
+    """The sorted `*_keypoints.json` files of a directory, one per frame: ValueError naming both counts when they differ."""
+    import glob
+    files = sorted(glob.glob(os.path.join(keypoints_dir, "*_keypoints.json")))
+    if len(files) != n_frames:
+        raise ValueError(f"{len(files)} *_keypoints.json files in {keypoints_dir} for {n_frames} frames (results/*/*.pkl)")
+    return files
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="global_optimization (fdcap_amd / MI355X)")
     ap.add_argument("body_path", nargs="?")
@@ -157,9 +171,21 @@ def main(argv=None):
     ap.add_argument("--log-every", type=int, default=0)
     ap.add_argument("--dct-mat", default="../Data/DCT_Basis/60.mat", help="DCT basis .mat (:45); generated if absent")
     ap.add_argument("--dct-num-iter", type=int, default=10000, help="iterations of mode 'dct' (:596)")
+    ap.add_argument("--keypoints", default=None, metavar="DIR",
+                    help="one-clip form: a detector's *_keypoints.json files (OpenPose format), one per frame, for the reprojection term")
+    ap.add_argument("--weight-reproj", type=float, default=0.0, help="one-clip form, mode 'global': weight of the reprojection term (0: off)")
+    ap.add_argument("--intrinsics", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"),
+                    help="pinhole intrinsics of the reprojection term (default 692 692 640 360)")
+    ap.add_argument("--rho", type=float, default=None, help="GMoF's rho of the reprojection term, in pixels (default 100)")
     a = ap.parse_args(argv)
     if a.clips is not None:
+        if a.keypoints is not None or a.weight_reproj != 0.0 or a.intrinsics is not None or a.rho is not None:
+            ap.error("--keypoints / --weight-reproj / --intrinsics / --rho belong to the one-clip form: the reprojection term is not implemented for --clips")
         return _main_clips(ap, a)
+    if (a.weight_reproj != 0.0) != (a.keypoints is not None):
+        ap.error("--keypoints DIR and a non-zero --weight-reproj W go together")
+    if a.weight_reproj != 0.0 and a.mode != "global":
+        ap.error(f"--weight-reproj: the reprojection term is implemented for mode 'global' (got mode '{a.mode}')")
     if a.mix_lengths:
         ap.error("--mix-lengths belongs to the multi-clip form (--clips ... --fit-root DIR)")
     if a.mix_scenes:
@@ -180,8 +206,18 @@ def main(argv=None):
                      "verbose": bool(a.log_every), "dct_mat_path": a.dct_mat}
     lossconfig = {"weight_loss_rec": 1, "weight_loss_vposer": 0.001, "weight_contact": 0.1, "weight_collision": 0.5}
     data = io.load_body_gen(a.body_path)                                         # :688-707
+    reproj = {}
+    if a.weight_reproj != 0.0:
+        from . import innerfit
+        try:
+            files = keypoint_files(a.keypoints, data.shape[0])
+        except ValueError as e:
+            ap.error(str(e))
+        lossconfig["weight_reproj"] = a.weight_reproj
+        reproj = dict(keypoints=innerfit.joints23_from_openpose([io.read_openpose_json(f, hands=False) for f in files]),
+                      intrinsics=tuple(a.intrinsics) if a.intrinsics else innerfit.DEFAULT_INTRINSICS, rho=100.0 if a.rho is None else a.rho)
     fop = FittingOP(fittingconfig, lossconfig, data.shape[0], dct_num_iter=a.dct_num_iter)
-    body_rec, scale, camera_ext = fop.fitting(torch.tensor(data).cuda(), a.mode, log_every=a.log_every)
+    body_rec, scale, camera_ext = fop.fitting(torch.tensor(data).cuda(), a.mode, log_every=a.log_every, **reproj)
     fop.save_result(body_rec, scale, camera_ext, a.fit_path)                     # :714
     print("[INFO][fitting] fitting finish, returning optimal value")
     return 0

@@ -7,6 +7,7 @@ extern "C" {
 // ---- mode 'dct' (global_optimization.py:595-630) -----------------------------------------------
 int fdcap_opt_set_dct(fdcap_ctx* c, const float* dct_mtx, int32_t T, int32_t C, const float* c_dct_d, void* stream) {
     if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: mode 'global' only)
+    if (opt_has_reproj(c)) return FDCAP_E_STATE;         // (the clip-level reprojection term is on: mode 'global' only)
     if (!c || !c->opt || !dct_mtx || !c_dct_d || T <= 0 || T > DCT_MAXT || C <= 0 || C > DCT_MAXC) return FDCAP_E_ARG;
     OptState* o = c->opt;
     const int W = o->cfg.n_total / T;
@@ -33,6 +34,7 @@ int fdcap_opt_set_dct_clips(fdcap_ctx* c, const float* dct_mtx, int32_t T, int32
     OptState* o = c->opt;
     if (!opt_whole_clips(o)) return FDCAP_E_STATE;       // (a shard of a clip: FittingOP's loop, window by window)
     if (o->multi_scene()) return FDCAP_E_STATE;          // (clips of several scenes: mode 'global' only)
+    if (opt_has_reproj(c)) return FDCAP_E_STATE;         // (the clip-level reprojection term is on: mode 'global' only)
     if (!dct_mtx || !c_dct_d || T <= 0 || T > DCT_MAXT || C <= 0 || C > DCT_MAXC) return FDCAP_E_ARG;
     if (o->nclip == 1) return fdcap_opt_set_dct(c, dct_mtx, T, C, c_dct_d, stream);
     const int K = o->nclip;
@@ -115,6 +117,7 @@ static int opt_dct_fit_impl(fdcap_ctx* c, int32_t iters, int32_t step0, float we
 int fdcap_opt_dct_fit(fdcap_ctx* c, int32_t iters, int32_t step0, float weight, float* obj_hist, int32_t log_stride,
                       void* stream) {
     if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_dct only)
+    if (opt_has_reproj(c)) return FDCAP_E_STATE;         // (the clip-level reprojection term is on: mode 'global' only)
     if (!c || !c->opt || iters < 0 || step0 < 0 || (obj_hist && log_stride <= 0)) return FDCAP_E_ARG;
     return opt_dct_fit_impl(c, iters, step0, weight, obj_hist, log_stride, (hipStream_t)stream);
 }
@@ -127,6 +130,7 @@ static int opt_backward_dct_impl(fdcap_ctx* c, float w_dct, float w_rec, float w
 
 int fdcap_opt_backward_dct(fdcap_ctx* c, float w_dct, float w_rec, float w_contact, int32_t log_terms, void* stream) {
     if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_dct only)
+    if (opt_has_reproj(c)) return FDCAP_E_STATE;         // (the clip-level reprojection term is on: mode 'global' only)
     if (!c || !c->opt) return FDCAP_E_STATE;
     return opt_backward_dct_impl(c, w_dct, w_rec, w_contact, log_terms, (hipStream_t)stream);
 }

@@ -59,6 +59,7 @@ static int opt_create_impl(fdcap_ctx* c, const fdcap_opt_config* cfg, int32_t n_
     o->dz_pending = false;
     o->log_pending = false;
     o->kp_mapped = false;
+    o->reproj = fdcap_reproj_params{};                      // (the reprojection term is an input of a fit, handed over after every create)
     o->cam_ready = false;
     o->seeded = false;
     o->nnpt_valid = false;
@@ -235,6 +236,23 @@ int fdcap_opt_set_inputs(fdcap_ctx* c, const float* data78, const float* init78,
     return FDCAP_OK;
 }
 
+// The clip-level fit's 2D-keypoint reprojection term (fdcap.h; csrc/fdc_fit2d.h ReprojIn).  A refused call changes nothing.
+int fdcap_opt_set_reproj(fdcap_ctx* c, const fdcap_reproj_params* p, const float* kp_d, void* stream) {
+    if (!c || !c->opt) return FDCAP_E_STATE;
+    OptState* o = c->opt;
+    if (o->nclip > 1 || o->dctW > 0) return FDCAP_E_STATE;  // (a batch of clips, a DCT term set up: the term is mode 'global''s, one clip)
+    if (!p || (reproj_finite(p->weight) && p->weight == 0.f)) {     // off: every launch is again the one it was
+        o->reproj = fdcap_reproj_params{};
+        return FDCAP_OK;
+    }
+    if (reproj_params_check(p->fx, p->fy, p->cx, p->cy, p->rho, p->weight) || !kp_d) return FDCAP_E_ARG;
+    const size_t n = (size_t)o->cfg.n_local * NJW * 3;
+    HIP_TRY(o->reproj_kp.ensure(n));
+    HIP_TRY(hipMemcpyAsync(o->reproj_kp.p, kp_d, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    o->reproj = *p;
+    return FDCAP_OK;
+}
+
 // The in-loop search of a batch of clips of several scenes: every segment against its own scene with its own pruning state, into
 // the flat dist / idx / seedpt.  One launch for all segments where plan_nn_segments says so, else -- the specification -- one
 // nn_search launch set per segment in segment order.  Either way seedpt holds every neighbour's coordinates afterwards: the
@@ -387,8 +405,11 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
     // (Mode 'dct' -- a DCT term is set up -- keeps the full sets, as every caller outside this function does.)
     const bool contact_state = contact_fwd || (dct_on || o->dctW > 0);
     const bool need_world = lw.world_on || dct_on || o->dctW > 0 || log_terms != 0 || ahead || cf.n_local != cf.n_total;
+    // (The reprojection term reads the body-frame joints 0..22 -- G's translations -- in every iteration: jn >= 23 while it is on.)
+    const bool reproj = o->reproj_on();
+    if (reproj && (o->dctW > 0 || o->nclip > 1)) return FDCAP_E_STATE;
     const PoseJoints pj = plan_pose_joints(c->h_parents.data(), c->h_depth.data(), contact_fwd ? c->contact.ja_hi : 0, contact_state, need_world,
-                                           o->sw.pose_trim && o->dctW == 0);
+                                           o->sw.pose_trim && o->dctW == 0, reproj);
     if (contact_grad && (pj.jr != NJ || pj.jn < c->contact.ja_hi)) return FDCAP_E_STATE;     // (dPF reaches every rotation, dA the rows below ja_hi)
     int e = ahead ? opt_pose_forward_rest(c, row_lo, row_hi, st) : opt_pose_forward(c, row_lo, row_hi, st, contact_state, &pj);
     o->ahead = false;
@@ -465,15 +486,28 @@ static int opt_backward_impl(fdcap_ctx* c, const LossWeights& lw, int32_t log_te
         else hipLaunchKernelGGL(contact_loss_rows_kernel, dim3(nl), dim3(256), 0, st, o->dist.p, nc, 2, o->loss_rows.p);
     }
     const bool joint_grad = lw.world_on || dct_on;
-    hipLaunchKernelGGL(pose_bwd_kernel, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p,
-                       o->Jrest.p, o->G.p, contact_grad ? o->dA.p : nullptr, contact_grad ? o->dPF.p : nullptr,
-                       joint_grad ? o->dJw.p : nullptr, contact_grad ? o->dMv.p : nullptr, contact_grad ? o->dsv.p : nullptr,
-                       contact_grad ? o->dPF.p + NPF : nullptr, NPFX, contact_grad ? o->dtransl_v.p : nullptr, o->dX.p, o->dO.p,
-                       o->dCAM.p, o->dscale_row.p, pli, (contact_grad && dpf_split) ? (const float*)(o->dPF.p + (size_t)o->R * NPFX) : (const float*)nullptr,
-                       dA_rows, kn, ctab, pj.jn, pj.jr, pj.nlev);
+#define FDC_POSE_BWD(KERNEL, ...) \
+    hipLaunchKernelGGL(KERNEL, dim3(nl), dim3(64 * POSE_NW), 0, st, pm, o->X.p, o->O.p, o->CAM.p, o->scale.p, 2, o->Rm.p, \
+                       o->Jrest.p, o->G.p, contact_grad ? o->dA.p : nullptr, contact_grad ? o->dPF.p : nullptr, \
+                       joint_grad ? o->dJw.p : nullptr, contact_grad ? o->dMv.p : nullptr, contact_grad ? o->dsv.p : nullptr, \
+                       contact_grad ? o->dPF.p + NPF : nullptr, NPFX, contact_grad ? o->dtransl_v.p : nullptr, o->dX.p, o->dO.p, \
+                       o->dCAM.p, o->dscale_row.p, pli, (contact_grad && dpf_split) ? (const float*)(o->dPF.p + (size_t)o->R * NPFX) : (const float*)nullptr, \
+                       dA_rows, kn, ctab, pj.jn, pj.jr, pj.nlev, ##__VA_ARGS__)
+    if (reproj) {
+        // the term rides in this launch (csrc/fdc_k_pose_bwd.inc with FDC_PB_REPROJ): no launch more than without it, booked on FDCAP_LT_POSE_BWD
+        if (pj.jn < NJW) return FDCAP_E_STATE;
+        const fdcap_reproj_params& q = o->reproj;
+        const ReprojIn rp = {o->reproj_kp.p, q.fx, q.fy, q.cx, q.cy, q.rho, q.weight / (float)(NJW * (double)cf.n_total),
+                             rows_log ? o->loss_rows.p : nullptr};
+        note_form("pose_bwd_reproj_kernel");
+        FDC_POSE_BWD(pose_bwd_reproj_kernel, rp);
+    } else
+        FDC_POSE_BWD(pose_bwd_kernel);
+#undef FDC_POSE_BWD
     o->pj_bwd = pj;
     lt_mark(o, FDCAP_LT_POSE_BWD, st);
-    const unsigned log_mask = (rows_log ? 0x17u : 0u) | (contact_fwd ? 0x8u : 0u);     // 0 rec, 1 z^2, 2 smoothing, 4 world | 3 contact
+    // 0 rec, 1 z^2, 2 smoothing, 4 world | 3 contact | 6 reprojection
+    const unsigned log_mask = (rows_log ? 0x17u : 0u) | (contact_fwd ? 0x8u : 0u) | (reproj && rows_log ? 0x40u : 0u);
     bool log_in_tail = false;
     {
         ScaleTail tail;

@@ -88,6 +88,7 @@ static int opt_backward_local2_impl(fdcap_ctx* c, const float* contact_weight, i
 
 int fdcap_opt_backward_local2(fdcap_ctx* c, const float* contact_weight, int32_t n_left, void* stream) {
     if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_local2 only)
+    if (opt_has_reproj(c)) return FDCAP_E_STATE;         // (the clip-level reprojection term is on: mode 'global' only)
     if (!c || !c->opt || !contact_weight || n_left <= 0 || n_left >= c->nc) return FDCAP_E_ARG;
     return opt_backward_local2_impl(c, contact_weight, n_left, (hipStream_t)stream);
 }
@@ -118,6 +119,7 @@ static int opt_step_x_impl(fdcap_ctx* c, int32_t step, hipStream_t st) {
 
 int fdcap_opt_step_x(fdcap_ctx* c, int32_t step, void* stream) {
     if (opt_is_batch(c)) return FDCAP_E_STATE;           // (a batch of clips: through fdcap_opt_run_local2 only)
+    if (opt_has_reproj(c)) return FDCAP_E_STATE;         // (the clip-level reprojection term is on: mode 'global' only)
     if (!c || !c->opt || step <= 0) return FDCAP_E_ARG;
     return opt_step_x_impl(c, step, (hipStream_t)stream);
 }
@@ -134,6 +136,7 @@ int fdcap_opt_run_local2(fdcap_ctx* c, int32_t n_left, int32_t jj0, int32_t jj1,
     if (n_logged) *n_logged = 0;
     if (!c || !c->opt) return FDCAP_E_STATE;
     if (opt_is_multi_scene(c)) return FDCAP_E_STATE;     // (clips of several scenes: mode 'global' only)
+    if (opt_has_reproj(c)) return FDCAP_E_STATE;         // (the clip-level reprojection term is on: mode 'global' only)
     if (n_left <= 0 || n_left >= c->nc || jj0 < 0 || jj1 < jj0 || num_iter < 0 || log_every < 0 || !contact_weight_d) return FDCAP_E_ARG;
     OptState* o = c->opt;
     // (a sharded context: the halo exchange between two iterations of this loop stays with the caller)
@@ -182,6 +185,7 @@ int fdcap_opt_run_dct(fdcap_ctx* c, int32_t ii0, int32_t ii1, int32_t num_iter, 
     if (n_logged) *n_logged = 0;
     if (!c || !c->opt) return FDCAP_E_STATE;
     if (opt_is_multi_scene(c)) return FDCAP_E_STATE;     // (clips of several scenes: mode 'global' only)
+    if (opt_has_reproj(c)) return FDCAP_E_STATE;         // (the clip-level reprojection term is on: mode 'global' only)
     if (ii0 < 0 || ii1 < ii0 || ii1 > num_iter || log_every < 0) return FDCAP_E_ARG;
     OptState* o = c->opt;
     if (o->dctW <= 0 || !opt_whole_clips(o)) return FDCAP_E_STATE;     // (a shard of a clip: the exchange stays with the caller)

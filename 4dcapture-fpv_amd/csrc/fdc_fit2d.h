@@ -10,6 +10,8 @@
 // Frames are independent problems (no temporal term), so one launch covers a whole batch of frames.
 #pragma once
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 
 #include "fdc_frame.h"
 #include "fdc_loss.h"
@@ -38,6 +40,36 @@ FDC_HD float fit2d_joint(const Fit2dStage& s, V3 J, float ku, float kv, float co
     dJ->y = dv * s.fy * iz;
     dJ->z = -(du * s.fx * J.x + dv * s.fy * J.y) * iz * iz;
     return w * (gu + gv);
+}
+
+// ---- the clip-level fit's reprojection term (fdcap_opt_set_reproj) --------------------------------------------
+//   weight / (23 N) * sum_ij conf_ij^2 [ GMoF_rho(k^u_ij - u_ij) + GMoF_rho(k^v_ij - v_ij) ]   on   p_ij = G_ij.t + transl_i + cam_t_i
+// the frame SMPLify-X fitted in: no `scale`, no camera_ext.  kp: this rank's rows [n_local][23][3] (u, v, conf); wn = weight / (23 N);
+// loss_rows: a logging backward's per-frame partials (slot 6, un-normalised: without wn), else null.
+struct ReprojIn { const float* kp; float fx, fy, cx, cy, rho, wn; float* loss_rows; };
+// The term's joint: fit2d_joint at w_data = 1, with an undetected keypoint (conf == 0) skipped -- its value and gradient are exact
+// zeros whatever its coordinates hold (NaN included) and whatever J.z is.  The inner fit's callers keep fit2d_joint as it is.
+FDC_HD float reproj_joint(const ReprojIn& rp, V3 J, float ku, float kv, float conf, V3* dJ) {
+    if (conf == 0.f) {
+        dJ->x = dJ->y = dJ->z = 0.f;
+        return 0.f;
+    }
+    const Fit2dStage s = {rp.fx, rp.fy, rp.cx, rp.cy, rp.rho, 1.f, 0.f, 0.f, 0.f};
+    const float val = fit2d_joint(s, J, ku, kv, conf, dJ);
+    dJ->x *= rp.wn; dJ->y *= rp.wn; dJ->z *= rp.wn;           // (the gradient carries the normalisation, the logged partial does not)
+    return val;
+}
+// 0, or -1 (FDCAP_E_ARG): a non-finite or non-positive focal length or rho, a non-finite or negative weight
+// (finite by the exponent's bits: the library is built with -fno-honor-nans, under which a floating-point test for NaN may be folded away)
+inline bool reproj_finite(float v) {
+    uint32_t u;
+    memcpy(&u, &v, sizeof(u));
+    return (u & 0x7f800000u) != 0x7f800000u;
+}
+inline int reproj_params_check(float fx, float fy, float cx, float cy, float rho, float weight) {
+    if (!reproj_finite(fx) || !reproj_finite(fy) || !reproj_finite(rho) || !reproj_finite(cx) || !reproj_finite(cy) || !reproj_finite(weight)) return -1;
+    if (!(fx > 0.f) || !(fy > 0.f) || !(rho > 0.f) || weight < 0.f) return -1;
+    return 0;
 }
 
 // gradient of the L2 priors on element e of the 78-d row

@@ -549,12 +549,15 @@ struct PoseJoints {
     int jn = POSE_NJ, jr = POSE_NJ, nlev = -1;     // nlev < 0: every level of the tree (pose_forward / pose_backward take it so)
     bool world = true;                             // the world joints Jw are written
 };
-inline PoseJoints plan_pose_joints(const int* parents, const int* depth, int ja_hi, bool contact_state, bool need_world, bool trim = true) {
+// body_joints: the loss also reads the posed body-frame joints 0 .. POSE_NJW - 1 (the clip-level reprojection term,
+// fdcap_opt_set_reproj): jn >= POSE_NJW in every iteration, whether or not the world joints are written (`world` and jr are as without it).
+inline PoseJoints plan_pose_joints(const int* parents, const int* depth, int ja_hi, bool contact_state, bool need_world, bool trim = true,
+                                   bool body_joints = false) {
     PoseJoints p;                                  // the full plan: what every launch was before the sets existed
     p.nlev = 0;
     for (int j = 0; j < POSE_NJ; ++j) p.nlev = std::max(p.nlev, depth[j] + 1);
     if (!trim) return p;
-    const int jn = std::min(POSE_NJ, std::max(1, std::max(contact_state ? ja_hi : 0, need_world ? POSE_NJW : 0)));
+    const int jn = std::min(POSE_NJ, std::max(1, std::max(contact_state ? ja_hi : 0, (need_world || body_joints) ? POSE_NJW : 0)));
     if (jn == POSE_NJ) return p;                   // (every vertex a contact: the identical launch)
     for (int j = 0; j < jn; ++j) if (parents[j] >= j) return p;
     p.jn = jn;

@@ -173,6 +173,11 @@ struct OptState {
     PoseJoints pj_fwd, pj_bwd;         // the joint sets of the last pose_fwd_kernel / pose_bwd_kernel launch (fdcap_debug_pose_joint_sets)
     DevBuf<float> Voff, Vw, dist, pd, dVoff;
     DevBuf<int> idx, pi;
+    // the clip-level reprojection term (fdcap_opt_set_reproj): on while reproj.weight != 0 -- the library's copy of this rank's
+    // keypoint rows [n_local,23,3] and the parameters; off (the state after every fdcap_opt_create*): no launch or argument differs
+    DevBuf<float> reproj_kp;
+    fdcap_reproj_params reproj = {};
+    bool reproj_on() const { return reproj.weight != 0.f; }
     DevBuf<float> kp2d;       // per-frame inner fit: 2D keypoints [n_local,23,3] (u, v, confidence), or [n_local,n_kp,3] in map order
     bool kp_mapped = false;   // ... the latter (fdcap_opt_set_keypoints_mapped): the data term runs over the context's keypoint map
     bool kp_panel = false;    // ... with the set's blend products as panel products around the kernel (kp_blend_by_panels)
@@ -728,6 +733,9 @@ inline bool opt_is_batch(const fdcap_ctx* c) { return c && c->opt && c->opt->ncl
 // ... of clips of several scenes (fdcap_opt_create_clips_scenes, more than one segment): mode 'global' only -- on top of what a batch
 // is refused, fdcap_opt_run_local2, fdcap_opt_set_dct_clips and fdcap_opt_run_dct return FDCAP_E_STATE
 inline bool opt_is_multi_scene(const fdcap_ctx* c) { return c && c->opt && c->opt->multi_scene(); }
+// the clip-level reprojection term is on (fdcap_opt_set_reproj): mode 'global' only -- mode 'local''s second loop and every DCT call
+// return FDCAP_E_STATE
+inline bool opt_has_reproj(const fdcap_ctx* c) { return c && c->opt && c->opt->reproj_on(); }
 
 // rows of the optimiser's buffers whose pose is needed: the owned frames plus `halo` frames on each side that has a neighbour
 void opt_row_range(const OptState* o, int halo, int* lo, int* hi) {

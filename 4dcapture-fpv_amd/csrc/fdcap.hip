@@ -63,6 +63,15 @@ using namespace fdc;
 #include "fdc_k_pose.h"      // per-frame pose kernels (forward, backward + parameter-space losses)
 #include "fdc_k_skin.h"      // skinning forward / backward (+ contact robustifier)
 #include "fdc_k_step.h"      // mode 'local' kernels, loss reductions, Adam / exchange step, conversions, operator helpers
+// pose_bwd_reproj_kernel (fdc_k_pose.h's comment): the second compilation of csrc/fdc_k_pose_bwd.inc, placed behind every other kernel
+// so that no kernel that existed before it moves in the code object
+namespace {
+#define FDC_PB_KERNEL pose_bwd_reproj_kernel
+#define FDC_PB_REPROJ 1
+#include "fdc_k_pose_bwd.inc"
+#undef FDC_PB_KERNEL
+#undef FDC_PB_REPROJ
+}  // namespace
 #include "fdc_state.h"       // fdcap_ctx, OptState, shared host helpers
 #include "fdc_api_ops.h"     // C-ABI: context, scene, contact ids, Op 1-3 (+ backward), conversions
 #include "fdc_api_opt.h"     // C-ABI: the clip optimiser's iteration

@@ -16,7 +16,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import capi, io
+from . import capi, innerfit, io
 from .dist import (FrameShard, agree_on, allgather_packed, allreduce_scalars, exchange_halos, same_on_all_ranks,
                    staged_collective)
 
@@ -45,8 +45,9 @@ DEFAULT_FITTINGCONFIG = {
     "device": "cuda", "contact_id_folder": "./body_segments", "contact_part": ["L_Leg", "R_Leg"],
     "verbose": False,
 }
+# weight_reproj (not in the reference; 0 = off): the clip-level 2D-keypoint reprojection term, FittingOP.fitting(keypoints=...)
 DEFAULT_LOSSCONFIG = {"weight_loss_rec": 1, "weight_loss_vposer": 0.001, "weight_contact": 0.1,
-                      "weight_collision": 0.5}
+                      "weight_collision": 0.5, "weight_reproj": 0}
 
 
 def first_phase2_iter(num_iter: int) -> int:
@@ -135,6 +136,27 @@ def logged_losses(s, n, nc, weight_loss_rec, weight_loss_vposer, weight_contact,
     return l_rec, l_vp, l_sm, l_con, l_ws, total
 
 
+def reproj_loss(s, n, weight_reproj):
+    """The reprojection term of one logged iteration from its un-normalised partial sum (slot capi.LOSS_REPROJ of losses_d):
+    weight_reproj / (23 n) * sum conf^2 [GMoF + GMoF]; it joins the total of either phase with coefficient 1."""
+    return weight_reproj * s[capi.LOSS_REPROJ] / (23 * n)
+
+
+def check_keypoints(keypoints, num_body, intrinsics, rho):
+    """The reprojection term's inputs, checked on the host -> (keypoints [num_body,23,3] float32, (fx, fy, cx, cy), rho)."""
+    if keypoints is None:
+        raise ValueError("weight_reproj is non-zero: fitting() needs keypoints [N,23,3] (u, v, confidence) in SMPL-X joint order")
+    kp = np.ascontiguousarray(keypoints.detach().cpu().numpy() if hasattr(keypoints, "detach") else keypoints, dtype=np.float32)
+    if kp.shape != (num_body, 23, 3):
+        raise ValueError(f"keypoints must be [{num_body},23,3], got {kp.shape}")
+    intr = tuple(float(v) for v in intrinsics)
+    if len(intr) != 4 or not all(math.isfinite(v) for v in intr) or intr[0] <= 0 or intr[1] <= 0:
+        raise ValueError(f"intrinsics must be finite (fx, fy, cx, cy) with positive focal lengths, got {intrinsics}")
+    if not (math.isfinite(rho) and rho > 0):
+        raise ValueError(f"rho must be finite and positive, got {rho}")
+    return kp, intr, float(rho)
+
+
 def local2_losses(s, n, num_verts, weight_loss_rec):
     """One logged iteration of mode 'local''s second loop (:404-429) as [l_rec, loss_local_smoothing, loss_smoothing,
     loss_contact_smoothing, total]; a mean over nothing (n = 2) is inf or NaN, without a warning."""
@@ -171,6 +193,7 @@ class FitLog:
     loss_contact: list = field(default_factory=list)
     loss_world_smoothing: list = field(default_factory=list)
     total: list = field(default_factory=list)
+    reproj: list = field(default_factory=list)      # loss_reproj per logged iteration, while the term is on (else empty)
 
     def append(self, ii, terms):
         """terms: the six of logged_losses"""
@@ -418,7 +441,7 @@ class FittingOP(_Fitter):
 
     # ---- :491-635 -------------------------------------------------------------------------
     def fitting(self, body_data, mode="global", log_every=0, checkpoint_every=0, checkpoint_path=None, resume=None,
-                check_finite_every=0, snapshot_at=()):
+                check_finite_every=0, snapshot_at=(), keypoints=None, intrinsics=innerfit.DEFAULT_INTRINSICS, rho=100.0):
         """body_data: [N,75] (device tensor or numpy), SMPLify-X layout (:64-76).
         Returns (body_rec [N_local,75] device tensor, scale numpy scalar, camera_ext [N_local,4,4])
         -- the whole clip when not sharded, exactly the reference's triple (:635).
@@ -435,6 +458,11 @@ class FittingOP(_Fitter):
             parameters from then on;
           snapshot_at=(k, ...) (mode 'global'): after the k-th optimiser step keep device copies of (body_rotation_rec [N_local,78],
             scale, camera_ext [N_local,16]) in self.snapshots[k] -- no host sync; for trajectory comparisons (tests/test_gpu_parity500.py).
+          keypoints=[N,23,3] (u, v, confidence; SMPL-X joint order, the whole clip on every rank; innerfit.joints23_from_openpose),
+            intrinsics=(fx, fy, cx, cy), rho: with lossconfig['weight_reproj'] != 0 (mode 'global' only) the loss total of both phases
+            gains weight_reproj / (23 N) * sum conf^2 GMoF_rho(keypoint - projection) on the body joints in the camera frame (DESIGN.md
+            section 5.7); the logged value is kept in self.log.reproj and printed as a trailing loss_reproj.  Keypoints are an input,
+            not state: a resumed fit is handed them again.  With weight_reproj == 0 they are ignored and nothing changes.
         Sharded runs: every argument of this call and `num_iter` must be the same on all ranks (they decide which collectives
         are issued).  `verbose` may differ -- prints come from rank 0 only, and rank 0's flag alone decides whether the loss
         history is read back (all-reduced) during the loop, so a rank-0-only verbose run is legal."""
@@ -447,6 +475,13 @@ class FittingOP(_Fitter):
             raise ValueError("snapshot_at is implemented for mode 'global'")
         if checkpoint_every and not checkpoint_path:
             raise ValueError("checkpoint_every needs checkpoint_path")
+        self._reproj = None
+        if float(self.weight_reproj) != 0.0:                 # (all of it on the host, before anything touches the device)
+            if mode != "global":
+                raise ValueError("weight_reproj: the reprojection term is implemented for mode 'global'")
+            if not (math.isfinite(float(self.weight_reproj)) and float(self.weight_reproj) > 0):
+                raise ValueError(f"weight_reproj must be finite and positive (0: off), got {self.weight_reproj}")
+            self._reproj = check_keypoints(keypoints, self.num_body, intrinsics, rho)
         if mode == "dct" and checkpoint_every and log_every and checkpoint_every % log_every:
             raise ValueError("mode 'dct': checkpoint_every must be a multiple of log_every (the first phase's objective history is "
                              "written by the launch itself, every log_every-th iteration counted from the launch's first)")
@@ -462,6 +497,8 @@ class FittingOP(_Fitter):
         capi.check(self.ctx.lib.fdcap_params_75_to_78(capi.dptr(body_data), n, capi.dptr(x78), capi.current_stream()), "fdcap_params_75_to_78")
         self.init(x78)                                                                      # :495
         ii0, resumed = self._load_checkpoint(resume) if resume else (0, {})
+        if self._reproj is not None:
+            self._set_reproj(*self._reproj)
         # FDCAP_FORCE_EXCHANGE=1: run the sharded iteration tail (pack -> all-gather -> unpack) even on a one-rank
         # group -- lets a single-GPU box exercise the RCCL calls of the multi-GPU path
         multi = self.shard.world > 1 or (self.group is not None and os.environ.get("FDCAP_FORCE_EXCHANGE") == "1")
@@ -625,12 +662,28 @@ class FittingOP(_Fitter):
         else:
             capi.check(lib.fdcap_opt_step(h, ii, P, st), "fdcap_opt_step")
 
+    def _set_reproj(self, kp, intr, rho):
+        """fdcap_opt_set_reproj with this rank's keypoint rows (after init(): every fdcap_opt_create switches the term off)"""
+        import torch
+        sh = self.shard
+        d_kp = torch.from_numpy(kp[sh.frame0:sh.frame0 + sh.n_local]).to(self.device)
+        par = capi.ReprojParams(*intr, rho, float(self.weight_reproj))
+        capi.check(self.ctx.lib.fdcap_opt_set_reproj(self.ctx.handle, ctypes.byref(par), capi.dptr(d_kp), capi.current_stream()), "fdcap_opt_set_reproj")
+        torch.cuda.current_stream().synchronize()           # (d_kp is copied by then)
+
     def _append_log(self, log, ii, phase2, s):
         terms = logged_losses(s, self.num_body, self.ctx.num_contact, self.weight_loss_rec, self.weight_loss_vposer, self.weight_contact,
                               phase2, self._mode == "local")
-        log.append(ii, terms)
+        names = list(MAIN_TERMS)
+        if getattr(self, "_reproj", None) is not None:      # the total gains the term, the row one more trailing field
+            l_rp = reproj_loss(s, self.num_body, float(self.weight_reproj))
+            terms = terms[:5] + (terms[5] + l_rp, l_rp)
+            names.append("loss_reproj")
+            log.reproj.append(l_rp)
+        log.append(ii, terms[:6])
         shown = [0, 1, 2, 3, 4, 5] if phase2 else [0, 1, 2, 3, 5]         # (phase 1 prints no loss_world_smoothing, :573-575)
-        self._print_row(ii, [MAIN_TERMS[k] for k in shown], [terms[k] for k in shown])
+        shown += [6] if len(terms) > 6 else []
+        self._print_row(ii, [names[k] for k in shown], [terms[k] for k in shown])
 
     def _print_row(self, ii, names, values):
         """the reference's per-iteration print, from rank 0 of a verbose fit"""
@@ -939,6 +992,8 @@ class ClipBatchFitter(_Fitter):
 
     def __init__(self, fittingconfig, lossconfig, body_model=None, vposer=None, contact_ids=None, legacy_zero_grad=False, n_left=None,
                  dct_num_iter=DCT_NUM_ITER):
+        if float((lossconfig or {}).get("weight_reproj", 0) or 0) != 0.0:        # (before anything touches the device)
+            raise ValueError("weight_reproj: the reprojection term is implemented for one clip (FittingOP, mode 'global'), not for a batch of clips")
         super().__init__(fittingconfig, lossconfig, body_model, vposer, contact_ids, n_left, legacy_zero_grad, dct_num_iter)
         self.ctx.set_contact_ids(self.vid)
         self.scene_key = None

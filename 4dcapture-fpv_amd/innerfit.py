@@ -67,6 +67,22 @@ DEFAULT_COLLISION = dict(faces=None, face_part=None, part_parent=None, ignore_pa
 COLLISION_PARTS = 64    # parts of include/fdcap.h's 64 x 64 bit matrix
 
 
+def joints23_from_openpose(rows):
+    """io.read_openpose_json rows, one per frame ([n, >= 25, 3] or a list of [>= 25, 3] arrays: u, v, confidence with BODY_25 first)
+    -> [n,23,3] float32 in SMPL-X joint order, the layout fdcap_opt_set_keypoints and FittingOP.fitting(keypoints=...) take.  The 14
+    BODY_25 keypoints whose OPENPOSE_BODY25 target is a body joint (below 23) go to that joint; every other joint -- the pelvis' three
+    spine joints, the collars, the feet -- gets zeros: confidence 0, no data term.  Pure host code."""
+    rows = [np.asarray(r, dtype=np.float32) for r in rows]
+    out = np.zeros((len(rows), 23, 3), np.float32)
+    for i, r in enumerate(rows):
+        if r.ndim != 2 or r.shape[0] < len(OPENPOSE_BODY25) or r.shape[1] != 3:
+            raise ValueError(f"frame {i}: expected [>= {len(OPENPOSE_BODY25)}, 3] keypoint rows, got {r.shape}")
+        for k, j in enumerate(OPENPOSE_BODY25):
+            if j < 23:
+                out[i, j] = r[k]
+    return out
+
+
 def collision_filter(face_part=None, part_parent=None, ignore_pairs=(), same_part=True):
     """-> [64] uint64, the 64 x 64 bit matrix of fdcap_set_collision_mesh: bit b of row a drops every pair of faces of parts a and b
     (either way round).  Sets the listed `ignore_pairs` (a, b); with `same_part` a part with itself and -- `part_parent` [<= 64],

@@ -38,7 +38,9 @@ extern "C" {
 #define FDCAP_PDIM 75         /* file row:      transl3 aa3 betas10 latent32 lh12 rh12 camt3 */
 #define FDCAP_MAX_SCENE_POINTS 67000000   /* fdcap_set_scene refuses more (FDCAP_E_ARG): 32 B of MFMA fragments per point, 32-bit offsets */
 #define FDCAP_MAX_SCENES 8    /* scene slots of a context (fdcap_set_scene_slot); slot 0 is fdcap_set_scene's */
-#define FDCAP_NUM_LOSSES 8   /* rec, vposer, smoothing, contact, world_smoothing, total, 2 spare */
+#define FDCAP_NUM_LOSSES 8   /* rec, vposer, smoothing, contact, world_smoothing, total, reprojection (FDCAP_LOSS_REPROJ), 1 spare */
+#define FDCAP_LOSS_REPROJ 6  /* slot of the clip-level reprojection term's partial sum (fdcap_opt_set_reproj); mode 'local''s second loop, which the
+                              * term excludes, keeps its own use of the slot */
 
 typedef struct fdcap_ctx fdcap_ctx;
 
@@ -360,6 +362,31 @@ int fdcap_opt_create_clips_scenes(fdcap_ctx* ctx, const fdcap_opt_config* cfg, i
  * cam_ext_d[n_local,16]: extract_ext() (:455).  All copied. */
 int fdcap_opt_set_inputs(fdcap_ctx* ctx, const float* data78_d, const float* init78_d,
                          const float* mask_d, const float* cam_ext_d, void* stream);
+/* The clip-level fit's 2D-keypoint reprojection term on the body joints (not in the reference, which has no such term: parity-unpinned
+ * like the per-frame inner fit, and checked against an fp64 autograd twin of the definition instead, tests/reproj_spec.py).  Per frame
+ * i of the clip's N = n_total frames and SMPL-X joint j in 0..22:
+ *     p_ij = G_ij.t + transl_i + cam_t_i        camera frame; cam_t = row columns 75:78, NOT multiplied by `scale`
+ *     u, v = fx p.x / p.z + cx,  fy p.y / p.z + cy
+ *     loss_reproj = weight / (23 N) * sum_ij conf_ij^2 [ GMoF_rho(k^u_ij - u) + GMoF_rho(k^v_ij - v) ]
+ * the frame SMPLify-X fitted in (body and camera offset both times `scale` cancel in the projection).  The term depends on neither
+ * `scale` nor camera_ext -- by construction: its gradient enters the pose backward as the gradient of the posed body-frame joints and
+ * never meets the world matrix -- and reaches the rows alone: transl, the rotations and betas through the chain, cam_t by sum_j of
+ * the joints' gradients.  A keypoint with conf == 0 is skipped (value and gradient exact zeros, whatever its coordinates hold, NaN
+ * included) and still counts in 23 N.  Outlier frames are not masked.  The term joins both phase totals with coefficient 1.
+ *   kp_d DEVICE [n_local,23,3] (u, v, conf) in SMPL-X joint order, this rank's own rows (fdcap_opt_set_keypoints' layout); copied.
+ *   params NULL or weight == 0: off -- then every launch is the one it was, with the arguments it had.
+ * On: fdcap_opt_backward, fdcap_opt_backward_and_step and fdcap_opt_run carry the term, on a whole clip and on one rank's share (no
+ * neighbour row is read: the exchange is untouched); a logging backward leaves the un-normalised partial sum
+ * sum conf^2 [GMoF + GMoF] in losses_d [FDCAP_LOSS_REPROJ]; the pose kernels keep joints 0..22 in every iteration.  The term rides in
+ * the pose backward's launch (pose_bwd_reproj_kernel in pose_bwd_kernel's place): an iteration has no launch more, and
+ * fdcap_opt_launch_timing books it on FDCAP_LT_POSE_BWD.
+ * FDCAP_E_ARG: fx, fy or rho non-finite or not positive, cx or cy non-finite, weight non-finite or negative, kp_d NULL with a non-zero
+ * weight.  FDCAP_E_STATE: no optimiser, a batch of clips, a DCT term set up.  A refused call leaves the term as it was.  While the
+ * term is on, fdcap_opt_run_local2, fdcap_opt_backward_local2, fdcap_opt_step_x and the DCT calls (fdcap_opt_set_dct[_clips],
+ * fdcap_opt_dct_fit, fdcap_opt_backward_dct, fdcap_opt_run_dct) return FDCAP_E_STATE.  Every fdcap_opt_create* switches it off:
+ * keypoints are an input of a fit, not state (a resumed fit hands them over again). */
+typedef struct fdcap_reproj_params { float fx, fy, cx, cy, rho, weight; } fdcap_reproj_params;
+int fdcap_opt_set_reproj(fdcap_ctx* ctx, const fdcap_reproj_params* params, const float* kp_d, void* stream);
 /* One pass of the loop body :562-592 for iteration `ii` of `num_iter`, split in two so a
  * multi-GPU caller can all-reduce the scalar `scale` gradient in between:
  *   backward: zero_grad + cal_loss + loss.backward()  -> gradients + loss partial sums
@@ -900,7 +927,7 @@ int fdcap_debug_nn_search_form(fdcap_ctx* ctx, int32_t key_shift, int32_t items_
 #define FDCAP_LT_CHAMFER_NN 3    /* Chamfer nearest-neighbour search (+ its seeding launch in a fit's first iteration) */
 #define FDCAP_LT_SKIN_BWD 4      /* contact robustifier + skinning backward */
 #define FDCAP_LT_BLEND_BWD 5     /* data gradient of the blend product */
-#define FDCAP_LT_POSE_BWD 6      /* chain / rotation backward + parameter-space losses */
+#define FDCAP_LT_POSE_BWD 6      /* chain / rotation backward + parameter-space losses (+ the reprojection term, fdcap_opt_set_reproj) */
 #define FDCAP_LT_VPOSER_BWD 7    /* VPoser data gradient (+ the `scale` step) */
 #define FDCAP_LT_NUM 8
 int fdcap_opt_launch_timing(fdcap_ctx* ctx, int32_t max_events);
